@@ -6,8 +6,8 @@ the reference's assets are stripped, so the scene is generated) at 1920×1080.  
 samples of every pixel of the frame; the default 16 steps × 64 spp = the 1024 spp of BASELINE.json's metric.
 Inputs (scene, BVH, queues) are resident in HBM before the timed region.
 
-Contract: W untimed warm-up steps, then exactly K timed steps bracketed by barrier +
-torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE JSON line.
+Contract: W untimed warm-up steps, then exactly K timed steps bracketed by ptc_sync (N > 1: and barrier +
+torch.cuda.synchronize()) on both sides, MAX over ranks, rank 0 prints ONE JSON line.
 N > 1: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`; one process per
 GPU, 32×32-pixel tiles interleaved over ranks, and the single collective of the path — the RCCL fp32
 sum of the framebuffer onto rank 0 (ncclReduce through the C-ABI, ptc_comm_reduce_radiance) — is inside
@@ -32,8 +32,17 @@ Extra objects on the JSON line:
                from the profile's serialised run.
   kernels      the same two rooflines (valu_issue, hbm) for k_trace_closest, k_trace_any and k_shade.
   whole_frame  VALU issue and HBM rates of the three kernels together over the timed wall time.
-  cpu_baseline the oracle (scalar C restatement, kind "port") timed on this box's host cores on a
-               bounded sample of the same workload (rank 0, N=1 only).
+  cpu_baseline the oracle (scalar C restatement, kind "port") timed on the host's cores on a
+               bounded sample of the same workload (rank 0, N=1 only; --full).
+  scene_refit_seconds / scene_refit_host_seconds
+               ptc_scene_refit of the unchanged scene on the device and on the host path (--full; null otherwise).
+
+A plain run sets up, warms up, times the K steps and prints the line; the roofline blocks above come from the counters of
+those same steps.  `--full` adds the measurements that take work of their own: the refits and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path computed, the resolved frame as a caller reads it (ptc_read_radiance_rgba32f:
+height x width x 4 float32), to DIR/radiance.npy after the timed steps (rank 0); a frame over 64 MB is written as a seeded sample
+of its pixels (DIR/radiance_sample.npy, with their flat pixel indices in DIR/radiance_sample_pixels.npy).  The scene and the
+samples are seeded: the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -56,6 +65,22 @@ N_SIMD = 1024          # 256 CUs × 4 SIMD32
 # VALU issue: a wave64 instruction occupies a SIMD32 for 2 cycles → 1024 SIMDs × 2.4 GHz / 2 = 1228.8 G wave-instr/s on paper;
 # measured with an all-v_fma_f32 stream at 7 waves per SIMD (profiles/r02_valu_issue.json): 1.127 ns per instruction and SIMD.
 VALU_PEAK_PAPER_GIPS = N_SIMD * 2.4 / 2.0
+DUMP_BYTES_MAX = 64 << 20
+
+
+def _dump_outputs(dirname, img):
+    """--dump-outputs: the frame as the caller receives it, or a fixed, seeded sample of its pixels when it is over the budget."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    if img.nbytes <= DUMP_BYTES_MAX:
+        np.save(os.path.join(dirname, "radiance.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = (DUMP_BYTES_MAX - (1 << 20)) // (flat.shape[1] * 4 + 8)        # the samples (float32) and their indices (float64), headers aside
+    pix = np.sort(np.random.default_rng(0).choice(flat.shape[0], n, replace=False))
+    np.save(os.path.join(dirname, "radiance_sample.npy"), flat[pix])
+    np.save(os.path.join(dirname, "radiance_sample_pixels.npy"), pix.astype(np.float64))
 
 
 def _load_json(path):
@@ -82,7 +107,10 @@ def main():
                          "albedo/normal/metal-rough textures and a 2048x1024 environment light")
     ap.add_argument("--direct-scene", action="store_true", help="hand the generated arrays to the C-ABI directly instead of through a GLB file + the glTF loader")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work of the bounded CPU-baseline render")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: ptc_scene_refit on the device and on the host, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame they computed to DIR/*.npy (float32, at most 64 MB)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend; 'gloo' + --share-device rehearses N ranks on a one-GPU box")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
@@ -93,10 +121,8 @@ def main():
     ap.add_argument("--reduce", choices=["cabi", "torch"], default="cabi",
                     help="N > 1: cabi = ncclReduce through the C-ABI (ptc_comm_*), the id shipped over torch.distributed; torch = torch.distributed.reduce on the zero-copy tensor")
     args = ap.parse_args()
-
-    import numpy as np
-    import torch
-    import torch.distributed as dist
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import pbr_amd
     from pbr_amd import dist as pdist
@@ -105,12 +131,18 @@ def main():
     rank, world, local_rank = pdist.env_rank_world()
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} needs WORLD_SIZE={args.gpus} (launch with torch.distributed.run); got {world}")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU: the path tracer is HIP-only (no CPU fallback)")
     if args.share_device:
         local_rank = 0
-    torch.cuda.set_device(local_rank)
+    # torch carries the N > 1 plumbing only (process group, broadcasts, reductions); one GPU needs the library alone, whose
+    # ptc_sync waits for every lane of the context
+    torch = dist = None
     if world > 1:
+        import torch
+        import torch.distributed as dist
+
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: the path tracer is HIP-only (no CPU fallback)")
+        torch.cuda.set_device(local_rank)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if args.backend == "nccl":
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
@@ -122,7 +154,10 @@ def main():
     # The metric is quoted on a glTF scene: the generated scene is written as a binary glTF and comes in through the library's own
     # loader (ptc_gltf_load: JSON, accessors, node hierarchy, PNG textures) — bit-identical to handing the arrays over directly
     # (tests/test_gltf.py, test_gpu_parity.py::test_gltf_loaded_scene_renders_identically).
-    pt = pbr_amd.PathTracer(local_rank)
+    try:
+        pt = pbr_amd.PathTracer(local_rank)
+    except pbr_amd.PtcError as e:
+        raise SystemExit(f"bench.py needs a GPU: the path tracer is HIP-only (no CPU fallback): {e}")
     scene_source = "generated arrays handed to the C-ABI"
     if args.direct_scene:
         pt.load_scene(desc)
@@ -148,17 +183,19 @@ def main():
         assert n_tri == desc.n_triangles, (n_tri, desc.n_triangles)
         scene_source = f"binary glTF ({os.path.getsize(glb) / 1e6:.1f} MB) written from the generator by rank 0, loaded by ptc_gltf_load"
         td.cleanup()
-    # scene dynamics: what a transform change costs (ptc_scene_refit of the unchanged scene re-computes and re-uploads exactly what a real one does)
-    pt.scene_refit()                                       # the first one also builds and uploads the refit plan
-    pt.scene_refit()
-    refit_seconds = pt.stats()["seconds_refit"]
-    os.environ["PTC_REFIT"] = "host"                       # the same refit computed on the host and uploaded (the cross-check path)
-    try:
+    refit_seconds = refit_host_seconds = None
+    if args.full:
+        # scene dynamics: what a transform change costs (ptc_scene_refit of the unchanged scene re-computes and re-uploads exactly what a real one does)
+        pt.scene_refit()                                   # the first one also builds and uploads the refit plan
         pt.scene_refit()
-    finally:
-        del os.environ["PTC_REFIT"]
-    refit_host_seconds = pt.stats()["seconds_refit"]
-    pt.scene_refit()                                       # leave the device-refitted scene (the same bytes) in place
+        refit_seconds = pt.stats()["seconds_refit"]
+        os.environ["PTC_REFIT"] = "host"                   # the same refit computed on the host and uploaded (the cross-check path)
+        try:
+            pt.scene_refit()
+        finally:
+            del os.environ["PTC_REFIT"]
+        refit_host_seconds = pt.stats()["seconds_refit"]
+        pt.scene_refit()                                   # leave the device-refitted scene (the same bytes) in place
     K, W, S = args.steps, args.warmup, args.spp_per_step * (world if args.scaling == "weak" else 1)
     spp_total = (K + W) * S
     tile_count = world if world > 1 else max(1, args.rehearse_tiles)
@@ -197,6 +234,10 @@ def main():
         if world > 1:
             dist.barrier()
 
+    def device_sync():                           # one GPU: pt.sync() just before has waited for all of the context's work
+        if world > 1:
+            torch.cuda.synchronize()
+
     def reduce_to_root():
         if world > 1 and reduce_impl.startswith("ncclReduce"):
             pt.comm_reduce_radiance(0)           # queued on the context's stream behind the resolve
@@ -215,17 +256,19 @@ def main():
     pt.sync()
     s0 = pt.stats()
     barrier()
-    torch.cuda.synchronize()
+    device_sync()
     t0 = time.perf_counter()
     for _ in range(K):
         pt.frame_add_samples(S)
     pt.frame_resolve()
     reduce_to_root()
-    torch.cuda.synchronize()
+    device_sync()
     barrier()
     t1 = time.perf_counter()
     s1 = pt.stats()
     dt = t1 - t0
+    if args.dump_outputs and rank == 0:          # rank 0 holds the reduced frame
+        _dump_outputs(args.dump_outputs, pt.read_radiance())
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -390,7 +433,7 @@ def main():
                          "node_visits": (tot["node_visits_closest"] + tot["node_visits_any"]) / paths,
                          "algorithmic_bytes": tot["algorithmic_bytes"] / paths},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import ora  # the checker, timed as the CPU baseline; never on the product path
 
             o = ora.Oracle().load_scene(desc)

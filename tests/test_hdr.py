@@ -1,12 +1,14 @@
 """The Radiance RGBE (.hdr) decoder (host/image_io.hpp decode_hdr, ptc_hdr_decode_rgb32f) against the REFERENCE's own decoder: oracle/_ref is the reference's vendored
 stb_image translation unit compiled where it lies (stbi_loadf_from_memory(..., 3): what its image path yields for such a file); the committed fixtures
-tests/golden/hdr_* were generated from it (tests/golden/make_hdr_golden.py) and pin the decoder where the reference checkout is absent (the GPU box)."""
+tests/golden/hdr_* were generated from it (tests/golden/make_hdr_golden.py) and pin the decoder where the reference checkout is absent.
+The random files are held against the digests of that build's decodes (tests/golden/ref_stb_digests.json, tests/stb_reference.py) where oracle/_ref is not built."""
 import glob
 import os
 import subprocess
 
 import numpy as np
 import pytest
+from stb_reference import equals_reference, refused_by_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -27,8 +29,6 @@ def test_hdr_decoder_equals_the_fixtures_of_the_reference_stb(g):
 
 
 def test_hdr_decoder_equals_reference_stb_on_random_files(g, ora):
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     rng = np.random.default_rng(7)
     for k in range(60):
         h, w = int(rng.integers(1, 40)), int(rng.integers(1, 70))
@@ -38,8 +38,8 @@ def test_hdr_decoder_equals_reference_stb_on_random_files(g, ora):
         if k % 5 == 0:
             img[rng.random((h, w)) < 0.2] = 0.0                            # black pixels: exponent byte 0
         data = g.hdr_encode(img, rle=bool(k % 2), magic="#?RGBE" if k % 7 == 0 else "#?RADIANCE")
-        want, got = ora.ref_stb_decode_float(data), g.hdr_decode(data)
-        assert got.shape == want.shape == (h, w, 3) and np.array_equal(got.view(np.uint32), want.view(np.uint32)), k
+        got = g.hdr_decode(data)
+        assert got.shape == (h, w, 3) and equals_reference(ora, data, got, floats=True), k
         # the quantisation of the shared-exponent format: a pixel comes back within 1/128 of its largest channel
         assert np.all(np.abs(got - img) <= img.max(2, keepdims=True) / 128.0 + 1e-30)
 
@@ -51,9 +51,8 @@ def test_hdr_decoder_refuses_what_stb_refuses(g, ora):
     for k, data in enumerate(bad):
         with pytest.raises(ValueError):
             g.hdr_decode(data)
-        if ora.have_ref_stb() and data:
-            with pytest.raises(ValueError):
-                ora.ref_stb_decode_float(data)
+        if data:
+            assert refused_by_reference(ora, data, floats=True), k
 
 
 @pytest.mark.gpu

@@ -4,13 +4,15 @@ reference's vendored stb_image translation unit (src/pbr_engine/image/stb/stb_im
 RGBA8 texels, bit for bit.  JPEG inputs are written with Pillow (baseline / progressive, 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1 /
 4:4:0, optimised tables, restart intervals, grey, CMYK, odd sizes); PNG inputs with pbr_amd.gltf.png_encode.
 The committed fixtures tests/golden/jpeg_*.jpg + .npy (made by tests/golden/make_jpeg_golden.py from the same reference
-build) pin the decoder where the reference checkout is absent."""
+build) pin the decoder where the reference checkout is absent; there the other files are held against the digests of that build's
+decodes in tests/golden/ref_stb_digests.json (tests/stb_reference.py)."""
 import glob
 import io
 import os
 
 import numpy as np
 import pytest
+from stb_reference import equals_reference
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -62,34 +64,26 @@ CASES += [((33, 50), dict(quality=85, subsampling=1, restart_marker_rows=1))]
 @pytest.mark.parametrize("size,kw", CASES)
 def test_colour_jpeg_equals_reference_stb(g, ora, size, kw):
     pytest.importorskip("PIL")
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     try:
         data = _jpeg(_picture(*size, seed=size[0] * 31 + size[1]), **kw)
     except Exception as e:      # an encoder option this Pillow does not know
         pytest.skip(f"Pillow cannot write this variant: {e}")
-    want = ora.ref_stb_decode(data)
     got = g.jpeg_decode(data)
-    assert got.shape == want.shape
-    assert (got == want).all(), f"{int((got != want).sum())} bytes differ"
+    assert equals_reference(ora, data, got)
 
 
 @pytest.mark.parametrize("prog", [False, True])
 @pytest.mark.parametrize("mode", ["L", "CMYK"])
 def test_grey_and_cmyk_jpeg_equal_reference_stb(g, ora, mode, prog):
     pytest.importorskip("PIL")
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     for size in ((9, 14), (48, 32)):
         data = _jpeg(_picture(*size, seed=3), mode=mode, quality=80, progressive=prog)
-        want, got = ora.ref_stb_decode(data), g.jpeg_decode(data)
-        assert got.shape == want.shape and (got == want).all(), (mode, prog, size)
+        got = g.jpeg_decode(data)
+        assert equals_reference(ora, data, got), (mode, prog, size)
 
 
 def test_png_decoder_equals_reference_stb(g, ora):
     """The PNG side of the same contract: every colour type / depth / interlacing that tests/test_png.py writes."""
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     rng = np.random.default_rng(9)
     n = 0
     for ct, depths in ((0, (1, 2, 4, 8, 16)), (2, (8, 16)), (3, (1, 2, 4, 8)), (4, (8, 16)), (6, (8, 16))):
@@ -101,8 +95,8 @@ def test_png_decoder_equals_reference_stb(g, ora):
                 s = rng.integers(0, hi, (13, 21, ch))
                 trns = bytes(rng.integers(0, 256, hi // 2 + 1, dtype=np.uint8)) if ct == 3 else None
                 data = g.png_encode(s, ct, dp, interlace=il, palette=pal, trns=trns)
-                want, got = ora.ref_stb_decode(data), g.png_decode(data)
-                assert got.shape == want.shape and (got == want).all(), (ct, dp, il)
+                got = g.png_decode(data)
+                assert equals_reference(ora, data, got), (ct, dp, il)
                 n += 1
     assert n == 30
 
@@ -270,23 +264,19 @@ LAYOUTS = [
 
 @pytest.mark.parametrize("factors,what", LAYOUTS)
 def test_sampling_layouts_equal_reference_stb(g, ora, factors, what):
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     for (h, w) in ((5, 3), (16, 16), (37, 29), (50, 70)):
         pic = _picture(h, w, seed=h)
         planes = [pic[..., 0], pic[..., 1], pic[..., 2]]
         for kw in (dict(), dict(interleaved=False), dict(restart=2)):
             data = _write_jpeg(planes, factors, **kw)
-            want, got = ora.ref_stb_decode(data), g.jpeg_decode(data)
-            assert got.shape == want.shape == (h, w, 4) and (got == want).all(), (what, h, w, kw)
+            got = g.jpeg_decode(data)
+            assert got.shape == (h, w, 4) and equals_reference(ora, data, got), (what, h, w, kw)
 
 
 def test_colour_space_tags_equal_reference_stb(g, ora):
     """Component ids 'R','G','B' (no conversion), Adobe APP14 transform 0 without JFIF (RGB), Adobe CMYK and YCCK, JFIF."""
     import struct
 
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     pic = _picture(24, 40, seed=5)
     planes = [pic[..., 0], pic[..., 1], pic[..., 2]]
     four = planes + [255 - pic[..., 0]]
@@ -296,5 +286,5 @@ def test_colour_space_tags_equal_reference_stb(g, ora):
     for data in (_write_jpeg(planes, f3, ids=(82, 71, 66)), _write_jpeg(planes, f3, app=adobe(0)), _write_jpeg(planes, f3, app=jfif + adobe(0)), _write_jpeg(planes, f3, app=jfif),
                  _write_jpeg(four, f4, ids=(1, 2, 3, 4), app=adobe(0)), _write_jpeg(four, f4, ids=(1, 2, 3, 4), app=adobe(2)), _write_jpeg(four, f4, ids=(1, 2, 3, 4)),
                  _write_jpeg([(2, 2), (1, 1), (1, 1), (2, 2)] and four, [(2, 2), (1, 1), (1, 1), (2, 2)], ids=(1, 2, 3, 4), app=adobe(2))):
-        want, got = ora.ref_stb_decode(data), g.jpeg_decode(data)
-        assert got.shape == want.shape and (got == want).all()
+        got = g.jpeg_decode(data)
+        assert equals_reference(ora, data, got)

@@ -1,7 +1,8 @@
 """The BMP / TGA / PGM / PPM / GIF / PSD / PIC / Radiance-as-texture decoders of the glTF loader (host/misc_decode.hpp, ptc_image_decode_rgba8) against the REFERENCE's own decoder: image::loadImage2D hands a glTF
 image's bytes to stbi_load_from_memory(..., 4) whatever format they are in (src/pbr_engine/image/pbr/image/LoadImage.cpp:56-73); oracle/_ref is that vendored stb_image
 translation unit compiled where it lies.  The committed fixture tests/golden/misc_images.npz was generated from it (tests/golden/make_misc_golden.py) and pins the decoders where the
-reference checkout is absent (the GPU box); with the checkout present every file of the corpus, random files and cut-short files are held against it directly."""
+reference checkout is absent; with the checkout present every file of the corpus, random files and cut-short files are held against it directly.
+Without it the random and cut-short files and the refusals are held against the digests of its decodes (tests/golden/ref_stb_digests.json, tests/stb_reference.py)."""
 import json
 import os
 import struct
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import misc_image_files as mif
+from stb_reference import equals_reference, refused_by_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "misc_images.npz")
@@ -38,8 +40,6 @@ def test_the_corpus_is_what_the_fixture_was_made_from(g):
 
 
 def test_decoders_equal_reference_stb_on_random_files(g, ora):
-    if not ora.have_ref_stb():
-        pytest.skip("oracle/_ref not built (no reference checkout)")
     rng = np.random.default_rng(23)
     n = 0
     for k in range(120):
@@ -87,8 +87,8 @@ def test_decoders_equal_reference_stb_on_random_files(g, ora):
         files.append(mif.tga(rng.integers(0, nc, (h, w)), f"map{int(rng.choice([15, 16, 24, 32]))}", rle=bool(k % 2), top_down=bool(k % 3), palette=np.concatenate([pal, pal[:, :1]], 1),
                              index_bits=16 if nc > 255 or k % 7 == 0 else 8))
         for data in files:
-            want, got = ora.ref_stb_decode(data), g.image_decode(data)
-            assert got.shape == want.shape and np.array_equal(got, want), (k, data[:32])
+            got = g.image_decode(data)
+            assert equals_reference(ora, data, got), (k, data[:32])
             n += 1
     assert n > 1400
 
@@ -104,20 +104,16 @@ def test_files_cut_short(g, ora):
         for cut in (len(data) - 1, len(data) - 40, len(data) - 150):
             got = g.image_decode(data[:cut])
             assert got.shape == whole.shape and (cut > len(data) - 150 or not np.array_equal(got, whole))       # (the last bytes may be row padding)
-            if ora.have_ref_stb():
-                assert np.array_equal(got, ora.ref_stb_decode(data[:cut])), cut
+            assert equals_reference(ora, data[:cut], got), cut
     # a GIF cut short ends its image where the data ends (a block length of 0 terminates it); a raw PSD reads zeros
     for data in (mif.gif(rng.integers(0, 16, (30, 40)), rng.integers(0, 256, (16, 3), dtype=np.uint8), bgindex=3), mif.psd(img, 4, 8), mif.psd(img, 3, 16)):
         for cut in (len(data) - 2, len(data) - 60, len(data) * 2 // 3):
             got = g.image_decode(data[:cut])
-            if ora.have_ref_stb():
-                assert np.array_equal(got, ora.ref_stb_decode(data[:cut])), cut
+            assert equals_reference(ora, data[:cut], got), cut
     for data in (mif.tga(img, "24"), mif.tga(img, "8"), mif.pnm(img[:, :, :3]), mif.pnm(img[:, :, :3].astype(np.uint32) * 200, True, 65535)):
         with pytest.raises(ValueError, match="truncated"):
             g.image_decode(data[:-3])
-    if ora.have_ref_stb():
-        with pytest.raises(ValueError):
-            ora.ref_stb_decode(mif.pnm(img[:, :, :3])[:-3])
+    assert refused_by_reference(ora, mif.pnm(img[:, :, :3])[:-3])
 
 
 def test_decoders_refuse_what_stb_refuses(g, ora):
@@ -151,9 +147,7 @@ def test_decoders_refuse_what_stb_refuses(g, ora):
     for k, data in enumerate(bad):
         with pytest.raises(ValueError):
             g.image_decode(data)
-        if ora.have_ref_stb():
-            with pytest.raises(ValueError):
-                ora.ref_stb_decode(data)
+        assert refused_by_reference(ora, data), k
     for data in (b"", b"BM", b"P6", b"P7\n1 1\n255\n\0\0\0", bytes(64), mif.tga(img, "24")[:2] + b"\x07" + mif.tga(img, "24")[3:]):
         with pytest.raises(ValueError):
             g.image_decode(data)
