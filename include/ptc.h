@@ -102,7 +102,7 @@ typedef struct ptc_stats {
    * of the two is what examples/viewer_shim.cpp watches. */
   double bvh_sa_cost;
   double bvh_sa_cost_built;
-  double seconds_rebuild;     /* the last ptc_scene_rebuild: flatten + LBVH build + refit pass, all on the device                */
+  double seconds_rebuild;     /* the last ptc_scene_rebuild: flatten + build (the device builder's) + refit pass, all on the device */
 } ptc_stats;
 
 /* ---- context ------------------------------------------------------------------------------
@@ -183,7 +183,8 @@ int ptc_scene_refit(ptc_ctx*);
  * costs, the same cost-optimal 8-wide collapse, octant slots, quantisation and unit layout as the host's LBVH builder (PTC_BVH_LBVH) — the bytes a
  * fresh ptc_scene_commit of the moved scene with that builder would upload (tests/test_gpu_parity.py compares them), in milliseconds and without
  * the description crossing the bus again.  The image does not depend on the tree; counters and speed are those of the new tree.  Whatever builder
- * the commit used, the rebuilt tree is the LBVH.  Needs a device; PTC_E_STATE before the first commit; a move that changes which triangles are
+ * the commit used, the rebuilt tree is the device builder's (ptc_set_device_builder): the LBVH by default, the host's binned-SAH tree (the
+ * bytes of a fresh PTC_BVH_SAH commit of the moved scene) with PTC_BVH_SAH.  Needs a device; PTC_E_STATE before the first commit; a move that changes which triangles are
  * emitters falls back to a host build + upload (as ptc_scene_refit does).  ptc_stats.bvh_sa_cost / bvh_sa_cost_built say when it is worth calling. */
 int ptc_scene_rebuild(ptc_ctx*);
 
@@ -213,12 +214,22 @@ int ptc_set_texture_filter(ptc_ctx*, int filter);
 enum { PTC_BVH_SAH = 0, PTC_BVH_LBVH = 1 };
 int ptc_set_bvh_builder(ptc_ctx*, int builder);
 
+/* The tree a build ON THE DEVICE makes (context setting, kept across ptc_scene_begin; default PTC_BVH_LBVH, or PTC_BVH_SAH when the
+ * environment has PTC_DEVICE_BVH=sah at ptc_create).  With PTC_BVH_SAH, ptc_scene_commit of a PTC_BVH_SAH scene on a device context
+ * builds on the device too (csrc/pt_build.hip: the host's binned-SAH binary tree, cut for cut, then the same collapse and layout — the
+ * bytes of the host's SAH commit), and ptc_scene_rebuild makes the SAH tree whatever builder the commit used; the host fallbacks of a
+ * rebuild (PTC_REBUILD=host, a change of the emitters, a single triangle) build the SAH tree too.  A PTC_BVH_LBVH scene still commits
+ * as the LBVH.  ptc_group_scene_commit keeps its one host build on device 0.  A description-only context takes the setting and builds
+ * on the host as before.  ptc_debug_get_internals [7] bit 2 says that the tree in HBM is a device SAH build. */
+int ptc_set_device_builder(ptc_ctx*, int builder);   /* PTC_BVH_LBVH | PTC_BVH_SAH; anything else: PTC_E_ARG, setting unchanged */
+
 /* Flatten instances to world space (geometry_pass/vertex.glsl:25-36), build + flatten the BVH,
  * build the emitter CDF, upload everything to HBM.  With PTC_BVH_SAH (the default) flatten and build run on the host's
- * thread pool (75 ms at 250 k triangles).  With PTC_BVH_LBVH on a device context the host only describes (indices,
- * materials, emitter table, textures) and the DEVICE flattens the vertices, writes the shading records and builds the
- * tree (csrc/pt_refit.hip, csrc/pt_build.hip): 3-5 ms at 250 k triangles, the arrays in HBM byte for byte those of the
- * host's LBVH commit (PTC_COMMIT=host in the environment keeps that path; ptc_debug_get_internals [7] bit 1 says which ran). */
+ * thread pool (75 ms at 250 k triangles).  With PTC_BVH_LBVH on a device context — or PTC_BVH_SAH with the SAH device
+ * builder (ptc_set_device_builder) — the host only describes (indices, materials, emitter table, textures) and the DEVICE
+ * flattens the vertices, writes the shading records and builds the tree (csrc/pt_refit.hip, csrc/pt_build.hip): 3-5 ms at
+ * 250 k triangles for the LBVH, the arrays in HBM byte for byte those of the host's commit with the same builder
+ * (PTC_COMMIT=host in the environment keeps that path; ptc_debug_get_internals [7] bit 1 says which ran). */
 int ptc_scene_commit(ptc_ctx*);
 
 /* ---- rendering ----------------------------------------------------------------------------
@@ -357,7 +368,8 @@ uint64_t ptc_debug_host_build_id(const ptc_ctx*);
  * collected, [2] queue capacity (paths) of a lane, [3] samples of one full batch, [4] samples accepted but not yet
  * issued, [5] trace blocks per CU, [6] stack entries per lane kept in LDS, [7] bit 0: the last ptc_scene_refit ran on the
  * device (csrc/pt_refit.hip), not on the host; bit 1: the last ptc_scene_commit flattened and built on the device
- * (csrc/pt_refit.hip + csrc/pt_build.hip: the LBVH builder on a device context). */
+ * (csrc/pt_refit.hip + csrc/pt_build.hip: the LBVH builder on a device context, or the SAH builder with the SAH device builder); bit 2: the
+ * tree now in HBM was built on the device by the SAH front end (ptc_set_device_builder). */
 int ptc_debug_get_internals(ptc_ctx*, uint64_t out[8]);
 
 /* The host's share of a commit ON THE DEVICE (the LBVH builder on a device context: indices and material per primitive, materials, the emitter table from the

@@ -7,8 +7,12 @@
 // from the world-space vertices a refit keeps in HBM (DevRefit::wverts / widx) — so a scene that has moved far from its commit is rebuilt where it
 // lies (ptc_scene_rebuild), in milliseconds, instead of flattened, built and uploaded by the host again.
 //
+// pt_build_sah makes the host's binned-SAH tree instead (PTC_BVH_SAH: ptc_scene.cpp build_split_tree / split_range) with the k_sah_* front end below and the
+// same back end from k_bld_up on: one level of open ranges per launch, top down — bins, the cut, the stable partition, the children (pt_build.hip).
+//
 // Stages (one stream, no host arithmetic; the host reads back a node count per level of the 8-wide tree and the final sizes):
 //   k_bld_prims    triangle boxes + the bounds of their centres                       k_bld_codes   Morton keys
+//   k_sah_*        (SAH front end) centres; per level: small ranges one wave each (k_sah_small), big ranges several workgroups each (bins, count, scatter, finish)
 //   k_sort_*       LSD radix sort of the 64-bit keys with their primitive ids, 8 bits per pass: per-wave tiles, digit ranking by ballot / mbcnt
 //   k_bld_radix    every internal node of the radix tree from the sorted keys alone (Karras 2012)
 //   k_bld_up       bottom-up from the leaves (second arrival proceeds): box and collapse-cost table of every internal node
@@ -34,3 +38,6 @@ struct BuildOut {
 // Builds the tree of the n_tris triangles (wverts, widx on the device; prim_cls = material class per primitive, on the device).  Returns an empty string or the error.
 std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n_tris, uint32_t toplet_budget,
                           BuildScratch& scratch, BuildOut& out);
+// The same with the host's binned-SAH binary tree (bvh_builder = PTC_BVH_SAH: build_split_tree) in place of the radix tree: the bytes of the host's SAH build.
+std::string pt_build_sah(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n_tris, uint32_t toplet_budget,
+                         BuildScratch& scratch, BuildOut& out);

@@ -1,4 +1,4 @@
-// pt_build.hip — the LBVH build on the device (see pt_build.h; the definition of every value is the host build in ptc_scene.cpp, bvh_builder = LBVH).
+// pt_build.hip — the LBVH and binned-SAH builds on the device (see pt_build.h; the definition of every value is the host build in ptc_scene.cpp).
 //
 // Everything here is integer / byte work with a few float comparisons per node: HBM- and latency-bound, nothing for MFMA.  The arithmetic that decides
 // the tree — centres, Morton quantisation, box unions, half areas, the collapse-cost sums, the slot scores — is written with the host's expressions in
@@ -28,6 +28,9 @@ struct Bld {
   int32_t* w_radix; uint32_t* w_parent; int32_t* w_link; uint32_t* w_child; uint32_t *w_own, *w_sub, *w_baddr, *w_naddr;
   uint32_t* counters;    // [0] 8-wide nodes so far, [1] units of the array, [2] entries of top_order
   uint32_t* top_order;
+  // the binned-SAH front end (k_sah_*): centres, the open ranges of a level (small: one wave each; big: several workgroups each) double-buffered by level parity,
+  // their counts per level, the big ranges' global bins, per-workgroup left counts, the root's cut
+  float4* ctr; struct SahRange *s_list[2], *s_big[2]; uint32_t *s_cnt, *s_bigcnt; struct SahSlot* s_slot; uint32_t *s_blk, *s_root;   // s_root[1]: error bits
 };
 
 __device__ inline uint32_t ordered_u(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -225,6 +228,320 @@ __global__ __launch_bounds__(kBlock) void k_bld_radix(Bld b) {
   if (left < 0) b.leaf_parent[gamma] = (uint32_t)i; else b.r_parent[gamma] = (uint32_t)i;
   if (right < 0) b.leaf_parent[gamma + 1] = (uint32_t)i; else b.r_parent[gamma + 1] = (uint32_t)i;
   if (i == 0) b.r_parent[0] = kUnset;
+}
+
+// ---- the binned-SAH binary tree (ptc_scene.cpp: build_split_tree, split_range, split_range_parallel), top down, one LEVEL of open ranges per launch.  Per range:
+// the bounds of its centres come with it (its parent's partition reduced them); on every axis with ch > cl, 32 bins of j = min((int)((c - cl) * (32 / (ch - cl))), 31)
+// hold a count and a box union (integer atomics: counts add, boxes take min / max of the order-preserving encoding — exact in any order); the suffix and prefix
+// sweeps are lane scans of the same min / max and integer sums; each boundary's cost is the host's expression; the cut is the first strict minimum in (axis, bin)
+// order, or the middle when no axis has a candidate; the partition of ord[lo..hi] is stable on both sides.  So the tree is the host's, node for node.
+// Node ids: an internal node is named by its cut (the last position of its left part), the root's cut swapped with 0 so that the root is node 0 — every id in
+// [0, n - 2], no allocation; a child writes its own id into its parent's link when it is cut.
+struct SahRange { uint32_t lo, hi, parent, bnd[6]; };     // parent: node id | side << 31 (kUnset for the root); bnd: ordered_u of the centre bounds lo[3], hi[3]
+constexpr int kSahBins = 32;
+constexpr int kBinWords = 7 * 3 * kSahBins;               // [field][axis * 32 + bin]: field 0 the count, 1..3 box lo, 4..6 box hi (ordered_u)
+constexpr uint32_t kSahBig = 1024;                        // ranges of at least this many triangles are cut by several workgroups (k_sah_big_*)
+constexpr uint32_t kSahChunk = 4096;                      // triangles per workgroup of the big-range kernels
+constexpr uint32_t kOrdPosInf = 0xff800000u, kOrdNegInf = 0x007fffffu;     // ordered_u(+inf), ordered_u(-inf)
+struct SahSlot { uint32_t bins[kBinWords]; uint32_t cbnd[12]; int32_t axis, bin; };   // a big range's bins, its children's centre bounds (left lo/hi, right lo/hi), its cut
+struct SahCut { int axis, bin; };
+
+__device__ inline uint32_t sah_bin_init(uint32_t w) { return w < 3u * kSahBins ? 0u : (w < 12u * kSahBins ? kOrdPosInf : kOrdNegInf); }
+__device__ inline uint32_t sah_cbnd_init(uint32_t w) { return (w % 6u) < 3u ? kOrdPosInf : kOrdNegInf; }
+__device__ inline int sah_bin(float c, float cl, float scale) {
+  const int j = (int)((c - cl) * scale);
+  return j > kSahBins - 1 ? kSahBins - 1 : (j < 0 ? 0 : j);
+}
+struct SahAxes {
+  float cl[3], ch[3], scale[3];
+  __device__ explicit SahAxes(const uint32_t* bnd) {
+    for (int k = 0; k < 3; ++k) {
+      cl[k] = unordered_f(bnd[k]); ch[k] = unordered_f(bnd[3 + k]);
+      scale[k] = ch[k] > cl[k] ? (float)kSahBins / (ch[k] - cl[k]) : 0.0f;
+    }
+  }
+  __device__ bool on(int k) const { return ch[k] > cl[k]; }
+};
+// adds triangle p to the bins (LDS or global)
+__device__ inline void sah_bin_add(uint32_t* bins, const SahAxes& ax, const float4& c, const Box6& t) {
+  const float cc[3] = {c.x, c.y, c.z};
+  for (int k = 0; k < 3; ++k) {
+    if (!ax.on(k)) continue;
+    const uint32_t w = (uint32_t)k * kSahBins + (uint32_t)sah_bin(cc[k], ax.cl[k], ax.scale[k]);
+    atomicAdd(&bins[w], 1u);
+    for (int d = 0; d < 3; ++d) { atomicMin(&bins[(1 + d) * 3 * kSahBins + w], ordered_u(t.lo[d])); atomicMax(&bins[(4 + d) * 3 * kSahBins + w], ordered_u(t.hi[d])); }
+  }
+}
+// The cut from complete bins, by one whole wave (every lane returns it): lane j holds bin j (lanes 32..63 empty bins), the sweeps are inclusive lane scans.
+__device__ SahCut sah_choose(const uint32_t* bins, const SahAxes& ax) {
+  const uint32_t lane = lane_of();
+  float best = INFINITY; SahCut cut{-1, 0};
+  for (int k = 0; k < 3; ++k) {
+    if (!ax.on(k)) continue;
+    uint32_t cnt = 0; Box6 bx;
+    for (int d = 0; d < 3; ++d) { bx.lo[d] = INFINITY; bx.hi[d] = -INFINITY; }
+    if (lane < (uint32_t)kSahBins) {
+      const uint32_t w = (uint32_t)k * kSahBins + lane;
+      cnt = bins[w];
+      for (int d = 0; d < 3; ++d) { bx.lo[d] = unordered_f(bins[(1 + d) * 3 * kSahBins + w]); bx.hi[d] = unordered_f(bins[(4 + d) * 3 * kSahBins + w]); }
+    }
+    uint32_t sc = cnt, pc = cnt; Box6 sb = bx, pb = bx;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t osc = __shfl_down(sc, o), opc = __shfl_up(pc, o);
+      Box6 os, op;
+      for (int d = 0; d < 3; ++d) {
+        os.lo[d] = __shfl_down(sb.lo[d], o); os.hi[d] = __shfl_down(sb.hi[d], o);
+        op.lo[d] = __shfl_up(pb.lo[d], o); op.hi[d] = __shfl_up(pb.hi[d], o);
+      }
+      if (lane + (uint32_t)o < 64u) { sc += osc; grow6(sb, os); }
+      if (lane >= (uint32_t)o) { pc += opc; grow6(pb, op); }
+    }
+    const float sa = sc ? half_area6(sb) : 0.0f;                   // suffix_area[lane]
+    const uint32_t nsc = __shfl_down(sc, 1);
+    const float nsa = __shfl_down(sa, 1);
+    float cost = INFINITY;
+    if (lane + 1u < (uint32_t)kSahBins && pc != 0u && nsc != 0u) cost = half_area6(pb) * (float)pc + nsa * (float)nsc;
+    if (!(cost < INFINITY)) cost = INFINITY;                        // +inf and NaN never win
+    int bj = (int)lane;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float oc = __shfl_xor(cost, o); const int oj = __shfl_xor(bj, o);
+      if (oc < cost || (oc == cost && oj < bj)) { cost = oc; bj = oj; }
+    }
+    if (cost < best) { best = cost; cut.axis = k; cut.bin = bj; }
+  }
+  return cut;
+}
+__device__ inline bool sah_left(const SahCut& cut, const SahAxes& ax, const float4& c, uint32_t i, uint32_t mid) {
+  if (cut.axis < 0) return i <= mid;
+  const float cc = cut.axis == 0 ? c.x : (cut.axis == 1 ? c.y : c.z);
+  return sah_bin(cc, ax.cl[cut.axis], ax.scale[cut.axis]) <= cut.bin;
+}
+__device__ inline void bnd_add(float* bd, const float4& c) {
+  bd[0] = fminf(bd[0], c.x); bd[1] = fminf(bd[1], c.y); bd[2] = fminf(bd[2], c.z);
+  bd[3] = fmaxf(bd[3], c.x); bd[4] = fmaxf(bd[4], c.y); bd[5] = fmaxf(bd[5], c.z);
+}
+__device__ inline void bnd_wave(float* bd) {
+  for (int o = 32; o >= 1; o >>= 1)
+    for (int d = 0; d < 3; ++d) { bd[d] = fminf(bd[d], __shfl_xor(bd[d], o)); bd[3 + d] = fmaxf(bd[3 + d], __shfl_xor(bd[3 + d], o)); }
+}
+__device__ void sah_push(const Bld& b, uint32_t lo, uint32_t hi, uint32_t parent, const float* bd, uint32_t level) {
+  SahRange e;
+  e.lo = lo; e.hi = hi; e.parent = parent;
+  for (int d = 0; d < 6; ++d) e.bnd[d] = ordered_u(bd[d]);
+  if (hi - lo + 1u >= kSahBig) b.s_big[level & 1u][atomicAdd(&b.s_bigcnt[level], 1u)] = e;
+  else b.s_list[level & 1u][atomicAdd(&b.s_cnt[level], 1u)] = e;
+}
+// range r of `level` is cut after position g: its node, its link in its parent, its leaves, its children for the next level
+__device__ void sah_finish(const Bld& b, const SahRange& r, uint32_t g, const float* lb, const float* rb, uint32_t level) {
+  if (g < r.lo || g >= r.hi) { atomicOr(&b.s_root[1], 1u); g = r.lo + (r.hi - r.lo) / 2u; }      // cannot happen (both sides of a cut hold a triangle): reported, kept in bounds
+  uint32_t id = 0;
+  if (r.parent == kUnset) *b.s_root = g;
+  else {
+    const uint32_t g0 = *b.s_root;
+    id = g == g0 ? 0u : (g == 0u ? g0 : g);
+    if (r.parent >> 31) b.r_right[r.parent & 0x7fffffffu] = (int32_t)id; else b.r_left[r.parent] = (int32_t)id;
+  }
+  b.r_lo[id] = r.lo; b.r_hi[id] = r.hi;
+  if (g == r.lo) b.r_left[id] = ~(int32_t)g; else sah_push(b, r.lo, g, id, lb, level + 1u);
+  if (g + 1u == r.hi) b.r_right[id] = ~(int32_t)r.hi; else sah_push(b, g + 1u, r.hi, id | 0x80000000u, rb, level + 1u);
+}
+
+// centres, the identity order, the root range (its centre bounds are k_bld_prims')
+__global__ __launch_bounds__(kBlock) void k_sah_init(Bld b) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= b.n) return;
+  const Box6 t = b.tbox[p];
+  b.ctr[p] = make_float4(0.5f * (t.lo[0] + t.hi[0]), 0.5f * (t.lo[1] + t.hi[1]), 0.5f * (t.lo[2] + t.hi[2]), 0.0f);
+  b.val_a[p] = p;
+  if (p == 0) {
+    SahRange e;
+    e.lo = 0; e.hi = b.n - 1u; e.parent = kUnset;
+    for (int d = 0; d < 6; ++d) e.bnd[d] = b.cb[d];
+    if (b.n >= kSahBig) { b.s_big[0][0] = e; b.s_bigcnt[0] = 1u; } else { b.s_list[0][0] = e; b.s_cnt[0] = 1u; }
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_sah_clear(Bld b, uint32_t slots) {
+  constexpr uint32_t per = sizeof(SahSlot) / 4u;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < slots * per; i += gridDim.x * kBlock) {
+    const uint32_t w = i % per;
+    uint32_t* s = reinterpret_cast<uint32_t*>(b.s_slot);
+    s[i] = w < (uint32_t)kBinWords ? sah_bin_init(w) : (w < (uint32_t)kBinWords + 12u ? sah_cbnd_init(w - (uint32_t)kBinWords) : 0u);
+  }
+}
+
+// Every internal node written, every link and range in bounds (the back end follows them): else error bit 2.  r_left / r_right / r_hi start as 0x7f7f7f7f.
+__global__ __launch_bounds__(kBlock) void k_sah_check(Bld b) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i + 1u >= b.n) return;
+  const int32_t l = b.r_left[i], r = b.r_right[i];
+  const uint32_t lo = b.r_lo[i], hi = b.r_hi[i];
+  const auto ok = [&](int32_t k) { return k >= 0 ? (uint32_t)k + 1u < b.n : (uint32_t)~k < b.n; };
+  if (!ok(l) || !ok(r) || hi >= b.n || lo >= hi) atomicOr(&b.s_root[1], 2u);
+}
+
+// Small ranges: one wave per range does everything — bins in LDS, the cut, the stable partition (left part in place: a left triangle is written at or below the
+// position it was read from; right part to val_b, then back), the children's centre bounds.  Persistent: the waves stride over the level's list.
+__global__ __launch_bounds__(kBlock) void k_sah_small(Bld b, uint32_t level) {
+  __shared__ uint32_t sbins[kBlock / 64][kBinWords];
+  const uint32_t wave = threadIdx.x >> 6, lane = lane_of();
+  uint32_t* bins = sbins[wave];
+  const uint32_t count = b.s_cnt[level];
+  const SahRange* list = b.s_list[level & 1u];
+  for (uint32_t e = blockIdx.x * (kBlock / 64) + wave; e < count; e += gridDim.x * (kBlock / 64)) {
+    const SahRange r = list[e];
+    const SahAxes ax(r.bnd);
+    for (uint32_t w = lane; w < (uint32_t)kBinWords; w += 64u) bins[w] = sah_bin_init(w);
+    wave_sync_lds();
+    for (uint32_t i = r.lo + lane; i <= r.hi; i += 64u) { const uint32_t p = b.val_a[i]; sah_bin_add(bins, ax, b.ctr[p], b.tbox[p]); }
+    wave_sync_lds();
+    const SahCut cut = sah_choose(bins, ax);
+    wave_sync_lds();                                            // the bins are read: the next range may clear them
+    const uint32_t mid = r.lo + (r.hi - r.lo) / 2u;
+    uint32_t nl = 0, nr = 0;
+    float lb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY}, rb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t base = r.lo; base <= r.hi; base += 64u) {
+      const uint32_t i = base + lane;
+      const bool valid = i <= r.hi;
+      uint32_t p = 0; float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (valid) { p = b.val_a[i]; c = b.ctr[p]; }
+      const bool left = valid && sah_left(cut, ax, c, i, mid), right = valid && !left;
+      const unsigned long long ml = __ballot(left), mr = __ballot(right);
+      if (cut.axis >= 0) {
+        if (left) b.val_a[r.lo + nl + mbcnt_u64(ml)] = p;
+        if (right) b.val_b[r.lo + nr + mbcnt_u64(mr)] = p;
+      }
+      nl += (uint32_t)__popcll(ml); nr += (uint32_t)__popcll(mr);
+      if (left) bnd_add(lb, c);
+      if (right) bnd_add(rb, c);
+    }
+    if (cut.axis >= 0) {
+      __threadfence_block();
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t k = lane; k < nr; k += 64u) b.val_a[r.lo + nl + k] = b.val_b[r.lo + k];
+    }
+    bnd_wave(lb); bnd_wave(rb);
+    if (lane == 0u) sah_finish(b, r, r.lo + nl - 1u, lb, rb, level);
+  }
+}
+
+// Big ranges: chunks of kSahChunk triangles, one workgroup each, over all big ranges of the level (the grid is an upper bound; the spare workgroups return).
+// k_sah_big_bins: per-workgroup bins in LDS, merged into the range's slot; k_sah_big_count: the cut (every workgroup of the range makes it from the slot, the
+// first one records it), left triangles per workgroup; k_sah_big_scatter: stable scatter into val_b (exclusive prefix over the range's earlier workgroups + rank
+// in the chunk by ballot / mbcnt), the children's centre bounds; k_sah_big_finish: back to val_a, the first workgroup finishes the range and clears its slot.
+__device__ inline bool sah_locate(const Bld& b, uint32_t level, uint32_t& r, uint32_t& first, SahRange& e) {
+  const uint32_t nb = b.s_bigcnt[level];
+  const SahRange* list = b.s_big[level & 1u];
+  for (uint32_t k = 0, acc = 0; k < nb; ++k) {
+    const uint32_t nblk = (list[k].hi - list[k].lo + kSahChunk) / kSahChunk;
+    if (blockIdx.x < acc + nblk) { r = k; first = acc; e = list[k]; return true; }
+    acc += nblk;
+  }
+  return false;
+}
+__global__ __launch_bounds__(kBlock) void k_sah_big_bins(Bld b, uint32_t level) {
+  __shared__ uint32_t bins[kBinWords];
+  uint32_t r, first; SahRange e;
+  if (!sah_locate(b, level, r, first, e)) return;
+  const SahAxes ax(e.bnd);
+  for (uint32_t w = threadIdx.x; w < (uint32_t)kBinWords; w += kBlock) bins[w] = sah_bin_init(w);
+  __syncthreads();
+  const uint32_t a = e.lo + (blockIdx.x - first) * kSahChunk, z = min(a + kSahChunk - 1u, e.hi);
+  for (uint32_t i = a + threadIdx.x; i <= z; i += kBlock) { const uint32_t p = b.val_a[i]; sah_bin_add(bins, ax, b.ctr[p], b.tbox[p]); }
+  __syncthreads();
+  uint32_t* g = b.s_slot[r].bins;
+  for (uint32_t w = threadIdx.x; w < 3u * kSahBins; w += kBlock) {
+    const uint32_t cnt = bins[w];
+    if (!cnt) continue;
+    atomicAdd(&g[w], cnt);
+    for (int d = 0; d < 3; ++d) { atomicMin(&g[(1 + d) * 3 * kSahBins + w], bins[(1 + d) * 3 * kSahBins + w]); atomicMax(&g[(4 + d) * 3 * kSahBins + w], bins[(4 + d) * 3 * kSahBins + w]); }
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_sah_big_count(Bld b, uint32_t level) {
+  __shared__ int cut_s[2];
+  __shared__ uint32_t wl[kBlock / 64];
+  uint32_t r, first; SahRange e;
+  if (!sah_locate(b, level, r, first, e)) return;
+  const SahAxes ax(e.bnd);
+  if (threadIdx.x < 64u) {
+    const SahCut cut = sah_choose(b.s_slot[r].bins, ax);
+    if (threadIdx.x == 0) { cut_s[0] = cut.axis; cut_s[1] = cut.bin; if (blockIdx.x == first) { b.s_slot[r].axis = cut.axis; b.s_slot[r].bin = cut.bin; } }
+  }
+  __syncthreads();
+  const SahCut cut{cut_s[0], cut_s[1]};
+  const uint32_t mid = e.lo + (e.hi - e.lo) / 2u;
+  const uint32_t a = e.lo + (blockIdx.x - first) * kSahChunk, z = min(a + kSahChunk - 1u, e.hi);
+  uint32_t k = 0;
+  for (uint32_t i = a + threadIdx.x; i <= z; i += kBlock) k += sah_left(cut, ax, b.ctr[b.val_a[i]], i, mid) ? 1u : 0u;
+  for (int o = 32; o >= 1; o >>= 1) k += __shfl_xor(k, o);
+  if (lane_of() == 0u) wl[threadIdx.x >> 6] = k;
+  __syncthreads();
+  if (threadIdx.x == 0) { uint32_t s = 0; for (int w = 0; w < kBlock / 64; ++w) s += wl[w]; b.s_blk[blockIdx.x] = s; }
+}
+__global__ __launch_bounds__(kBlock) void k_sah_big_scatter(Bld b, uint32_t level) {
+  __shared__ uint32_t base_s[2];
+  __shared__ uint32_t wl[kBlock / 64], wr[kBlock / 64];
+  uint32_t r, first; SahRange e;
+  if (!sah_locate(b, level, r, first, e)) return;
+  const SahAxes ax(e.bnd);
+  const SahCut cut{b.s_slot[r].axis, b.s_slot[r].bin};
+  const uint32_t nblk = (e.hi - e.lo + kSahChunk) / kSahChunk;
+  if (threadIdx.x == 0) {
+    uint32_t before = 0, total = 0;
+    for (uint32_t k = 0; k < nblk; ++k) { const uint32_t v = b.s_blk[first + k]; if (first + k < blockIdx.x) before += v; total += v; }
+    const uint32_t a = e.lo + (blockIdx.x - first) * kSahChunk;
+    base_s[0] = e.lo + before; base_s[1] = e.lo + total + (a - e.lo - before);
+  }
+  __syncthreads();
+  uint32_t lpos = base_s[0], rpos = base_s[1];
+  const uint32_t wave = threadIdx.x >> 6, mid = e.lo + (e.hi - e.lo) / 2u;
+  const uint32_t a = e.lo + (blockIdx.x - first) * kSahChunk, z = min(a + kSahChunk - 1u, e.hi);
+  float lb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY}, rb[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t base = a; base <= z; base += kBlock) {
+    const uint32_t i = base + threadIdx.x;
+    const bool valid = i <= z;
+    uint32_t p = 0; float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (valid) { p = b.val_a[i]; c = b.ctr[p]; }
+    const bool left = valid && sah_left(cut, ax, c, i, mid), right = valid && !left;
+    const unsigned long long ml = __ballot(left), mr = __ballot(right);
+    if (lane_of() == 0u) { wl[wave] = (uint32_t)__popcll(ml); wr[wave] = (uint32_t)__popcll(mr); }
+    __syncthreads();
+    uint32_t bl = 0, br = 0, tl = 0, tr = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) { if (w < wave) { bl += wl[w]; br += wr[w]; } tl += wl[w]; tr += wr[w]; }
+    if (left) { b.val_b[lpos + bl + mbcnt_u64(ml)] = p; bnd_add(lb, c); }
+    if (right) { b.val_b[rpos + br + mbcnt_u64(mr)] = p; bnd_add(rb, c); }
+    lpos += tl; rpos += tr;
+    __syncthreads();
+  }
+  bnd_wave(lb); bnd_wave(rb);
+  if (lane_of() == 0u) {
+    uint32_t* cb = b.s_slot[r].cbnd;
+    for (int d = 0; d < 3; ++d) {
+      if (lb[d] <= lb[3 + d]) { atomicMin(&cb[d], ordered_u(lb[d])); atomicMax(&cb[3 + d], ordered_u(lb[3 + d])); }
+      if (rb[d] <= rb[3 + d]) { atomicMin(&cb[6 + d], ordered_u(rb[d])); atomicMax(&cb[9 + d], ordered_u(rb[3 + d])); }
+    }
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_sah_big_finish(Bld b, uint32_t level) {
+  uint32_t r, first; SahRange e;
+  if (!sah_locate(b, level, r, first, e)) return;
+  const uint32_t a = e.lo + (blockIdx.x - first) * kSahChunk, z = min(a + kSahChunk - 1u, e.hi);
+  for (uint32_t i = a + threadIdx.x; i <= z; i += kBlock) b.val_a[i] = b.val_b[i];
+  if (blockIdx.x != first) return;
+  SahSlot& s = b.s_slot[r];
+  if (threadIdx.x == 0) {
+    const uint32_t nblk = (e.hi - e.lo + kSahChunk) / kSahChunk;
+    uint32_t nl = 0;
+    for (uint32_t k = 0; k < nblk; ++k) nl += b.s_blk[first + k];
+    float lb[6], rb[6];
+    for (int d = 0; d < 6; ++d) { lb[d] = unordered_f(s.cbnd[d]); rb[d] = unordered_f(s.cbnd[6 + d]); }
+    sah_finish(b, e, e.lo + nl - 1u, lb, rb, level);
+  }
+  __syncthreads();
+  for (uint32_t w = threadIdx.x; w < (uint32_t)kBinWords + 12u; w += kBlock) {
+    if (w < (uint32_t)kBinWords) s.bins[w] = sah_bin_init(w); else s.cbnd[w - kBinWords] = sah_cbnd_init(w - kBinWords);
+  }
 }
 
 // ---- bottom-up: box and collapse-cost table of every internal node (ptc_scene.cpp: compute_radix_boxes + "cost tables, bottom-up").  One ROUND per launch: a
@@ -427,8 +744,11 @@ template <class T> T* carve(char*& p, size_t count) {
 #define BLD_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return std::string("device build: ") + hipGetErrorString(e_); } while (0)
 }  // namespace
 
-std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n, uint32_t toplet_budget,
-                          BuildScratch& S, BuildOut& out) {
+namespace {
+// The front end (sah: the binned-SAH tree, else the LBVH) leaves val_a (sorted position -> primitive id) and r_left / r_right / r_lo / r_hi (internal nodes, the root
+// is node 0); the back end from k_bld_up on takes any binary tree over the sorted positions.
+std::string build_tree(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n, uint32_t toplet_budget,
+                       BuildScratch& S, BuildOut& out, bool sah) {
   if (n < 2u) return "device build: fewer than two triangles (the host build handles the special case)";
   if (n > (1u << 24)) return "device build: more than 2^24 triangles";
   const uint32_t tiles = (n + kSortTile - 1u) / kSortTile;
@@ -447,6 +767,12 @@ std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32
     b.w_radix = carve<int32_t>(p, n); b.w_parent = carve<uint32_t>(p, n); b.w_link = carve<int32_t>(p, (size_t)n * 8); b.w_child = carve<uint32_t>(p, (size_t)n * 8);
     b.w_own = carve<uint32_t>(p, n); b.w_sub = carve<uint32_t>(p, n); b.w_baddr = carve<uint32_t>(p, n); b.w_naddr = carve<uint32_t>(p, n);
     b.counters = carve<uint32_t>(p, 8); b.top_order = carve<uint32_t>(p, budget + 16);
+    if (sah) {
+      b.ctr = carve<float4>(p, n);
+      for (int k = 0; k < 2; ++k) { b.s_list[k] = carve<SahRange>(p, n / 2u + 2u); b.s_big[k] = carve<SahRange>(p, n / kSahBig + 2u); }
+      b.s_cnt = carve<uint32_t>(p, (size_t)n + 32u); b.s_bigcnt = carve<uint32_t>(p, (size_t)n + 32u);
+      b.s_slot = carve<SahSlot>(p, n / kSahBig + 2u); b.s_blk = carve<uint32_t>(p, n / kSahChunk + n / kSahBig + 4u); b.s_root = carve<uint32_t>(p, 2);
+    }
     return (size_t)(p - base);
   };
   const size_t need = layout(nullptr);
@@ -462,27 +788,67 @@ std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32
   hipLaunchKernelGGL(k_bld_init, dim3(1), dim3(64), 0, st, b);
   BLD_TRY(hipMemsetAsync(b.r_flag, 0, (size_t)n * 4, st));
   { uint32_t g = (n + kBlock - 1u) / kBlock; if (g > 1024u) g = 1024u; hipLaunchKernelGGL(k_bld_prims, dim3(g), dim3(kBlock), 0, st, b); }
-  hipLaunchKernelGGL(k_bld_codes, blocks(n, kBlock), dim3(kBlock), 0, st, b);
-  {
-    const dim3 g((tiles + kBlock / 64 - 1u) / (kBlock / 64));
-    unsigned long long *ki = b.key_a, *ko = b.key_b; uint32_t *vi = b.val_a, *vo = b.val_b;
-    for (int pass = 0; pass < 8; ++pass) {          // 63 bits of code: 8 passes of 8; an even number of passes leaves the result in key_a / val_a
-      hipLaunchKernelGGL(k_sort_hist, g, dim3(kBlock), 0, st, ki, n, pass * 8, b.hist);
-      hipLaunchKernelGGL(k_sort_scan_tiles, dim3(256), dim3(256), 0, st, b.hist, tiles, b.digit_total);
-      hipLaunchKernelGGL(k_sort_scan_digits, dim3(1), dim3(256), 0, st, b.digit_total);
-      hipLaunchKernelGGL(k_sort_scatter, g, dim3(kBlock), 0, st, ki, vi, n, pass * 8, b.hist, b.digit_total, ko, vo);
-      std::swap(ki, ko); std::swap(vi, vo);
+  if (sah) {
+    // ---- the binned-SAH binary tree, top down: levels with big ranges one at a time (the host reads back whether the next level has any), then batches of 16
+    // levels of small ranges between read-backs (a level's kernel reads its count from device memory; past the last level the lists are empty) ----
+    BLD_TRY(hipMemsetAsync(b.s_cnt, 0, ((size_t)n + 32u) * 4, st));
+    BLD_TRY(hipMemsetAsync(b.s_bigcnt, 0, ((size_t)n + 32u) * 4, st));
+    BLD_TRY(hipMemsetAsync(b.s_root, 0, 8, st));
+    for (void* q : {(void*)b.r_left, (void*)b.r_right, (void*)b.r_hi}) BLD_TRY(hipMemsetAsync(q, 0x7f, (size_t)n * 4, st));
+    const uint32_t slots = n / kSahBig + 2u;
+    hipLaunchKernelGGL(k_sah_clear, dim3((slots * (uint32_t)(sizeof(SahSlot) / 4u) + kBlock - 1u) / kBlock), dim3(kBlock), 0, st, b, slots);
+    hipLaunchKernelGGL(k_sah_init, blocks(n, kBlock), dim3(kBlock), 0, st, b);
+    uint32_t gs = (n / 2u + kBlock / 64 - 1u) / (kBlock / 64);
+    gs = gs > 2048u ? 2048u : gs;
+    const dim3 gsmall(gs), gbig(n / kSahChunk + n / kSahBig + 2u);
+    uint32_t level = 0;
+    for (uint32_t nbig = n >= kSahBig ? 1u : 0u; nbig;) {
+      hipLaunchKernelGGL(k_sah_small, gsmall, dim3(kBlock), 0, st, b, level);
+      hipLaunchKernelGGL(k_sah_big_bins, gbig, dim3(kBlock), 0, st, b, level);
+      hipLaunchKernelGGL(k_sah_big_count, gbig, dim3(kBlock), 0, st, b, level);
+      hipLaunchKernelGGL(k_sah_big_scatter, gbig, dim3(kBlock), 0, st, b, level);
+      hipLaunchKernelGGL(k_sah_big_finish, gbig, dim3(kBlock), 0, st, b, level);
+      ++level;
+      BLD_TRY(hipMemcpyAsync(&nbig, &b.s_bigcnt[level], 4, hipMemcpyDeviceToHost, st));
+      BLD_TRY(hipStreamSynchronize(st));
     }
+    for (;;) {
+      for (int k = 0; k < 16; ++k, ++level) hipLaunchKernelGGL(k_sah_small, gsmall, dim3(kBlock), 0, st, b, level);
+      uint32_t open = 0;
+      BLD_TRY(hipMemcpyAsync(&open, &b.s_cnt[level], 4, hipMemcpyDeviceToHost, st));
+      BLD_TRY(hipStreamSynchronize(st));
+      if (!open) break;
+      if (level + 16u >= n + 32u) return "device build: the SAH tree is deeper than its triangle count";
+    }
+    hipLaunchKernelGGL(k_sah_check, blocks(n - 1u, kBlock), dim3(kBlock), 0, st, b);
+    uint32_t err = 0;
+    BLD_TRY(hipMemcpyAsync(&err, &b.s_root[1], 4, hipMemcpyDeviceToHost, st));
+    BLD_TRY(hipStreamSynchronize(st));
+    if (err) return "device build: the SAH front end left an inconsistent tree (error bits " + std::to_string(err) + ")";
+  } else {
+    hipLaunchKernelGGL(k_bld_codes, blocks(n, kBlock), dim3(kBlock), 0, st, b);
+    {
+      const dim3 g((tiles + kBlock / 64 - 1u) / (kBlock / 64));
+      unsigned long long *ki = b.key_a, *ko = b.key_b; uint32_t *vi = b.val_a, *vo = b.val_b;
+      for (int pass = 0; pass < 8; ++pass) {          // 63 bits of code: 8 passes of 8; an even number of passes leaves the result in key_a / val_a
+        hipLaunchKernelGGL(k_sort_hist, g, dim3(kBlock), 0, st, ki, n, pass * 8, b.hist);
+        hipLaunchKernelGGL(k_sort_scan_tiles, dim3(256), dim3(256), 0, st, b.hist, tiles, b.digit_total);
+        hipLaunchKernelGGL(k_sort_scan_digits, dim3(1), dim3(256), 0, st, b.digit_total);
+        hipLaunchKernelGGL(k_sort_scatter, g, dim3(kBlock), 0, st, ki, vi, n, pass * 8, b.hist, b.digit_total, ko, vo);
+        std::swap(ki, ko); std::swap(vi, vo);
+      }
+    }
+    // ---- the radix tree ----
+    hipLaunchKernelGGL(k_bld_radix, blocks(n - 1u, kBlock), dim3(kBlock), 0, st, b);
   }
-  // ---- binary tree, boxes, cost tables ----
-  hipLaunchKernelGGL(k_bld_radix, blocks(n - 1u, kBlock), dim3(kBlock), 0, st, b);
+  // ---- boxes, cost tables ----
   for (uint32_t round = 1;;) {            // rounds = the height of the binary tree (40-70 for a scene's Morton codes); the root's stamp is read back every 16
     for (int k = 0; k < 16; ++k, ++round) hipLaunchKernelGGL(k_bld_up, blocks(n - 1u, kBlock), dim3(kBlock), 0, st, b, round);
     uint32_t root_done = 0;
     BLD_TRY(hipMemcpyAsync(&root_done, &b.r_flag[0], 4, hipMemcpyDeviceToHost, st));
     BLD_TRY(hipStreamSynchronize(st));
     if (root_done) break;
-    if (round > 8192u) return "device build: the binary tree is deeper than 8192 levels";
+    if (round > 8192u && round > n + 16u) return "device build: the binary tree is deeper than 8192 levels";     // (a SAH tree can be as deep as n - 1)
   }
   // ---- 8-wide collapse, level by level ----
   std::vector<uint32_t> lvl_first{0u};
@@ -531,4 +897,14 @@ std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32
   BLD_TRY(hipGetLastError());
   out.n_nodes = total; out.n_units = n_units; out.max_depth = (uint32_t)levels - 1u; out.n_tri_records = n;
   return std::string();
+}
+}  // namespace
+
+std::string pt_build_lbvh(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n, uint32_t toplet_budget,
+                          BuildScratch& scratch, BuildOut& out) {
+  return build_tree(st, wverts, widx, prim_cls, n, toplet_budget, scratch, out, /*sah=*/false);
+}
+std::string pt_build_sah(hipStream_t st, const HostVertex* wverts, const uint32_t* widx, const uint32_t* prim_cls, uint32_t n, uint32_t toplet_budget,
+                         BuildScratch& scratch, BuildOut& out) {
+  return build_tree(st, wverts, widx, prim_cls, n, toplet_budget, scratch, out, /*sah=*/true);
 }

@@ -109,6 +109,7 @@ struct ptc_ctx {
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
+  int device_builder = PTC_BVH_LBVH;     // PTC_BVH_*: the tree a build ON THE DEVICE makes (ptc_set_device_builder; PTC_DEVICE_BVH=sah in the environment), kept across ptc_scene_begin
   // committed scene
   bool committed = false;
   size_t committed_insts = 0;       // instances the committed scene was built from (ptc_scene_refit refuses a description that has grown since)
@@ -124,6 +125,7 @@ struct ptc_ctx {
   bool host_stale = false;          // the device refitted in place: built's vertex-dependent arrays are those of an earlier state until refresh_host_copy
   bool last_refit_on_device = false;
   bool commit_on_device = false;      // the last ptc_scene_commit flattened and built on the device (device_commit)
+  bool tree_device_sah = false;       // the tree in HBM was built on the device by the SAH front end (pt_build_sah)
   int trace_rays_per_lane = 8;      // PTC_TRACE_RAYS_PER_LANE: rays per lane of the trace kernels' grid a batch should offer before the grid is made smaller (run_batch)
   int trace_overlap = 1;            // PTC_TRACE_OVERLAP: the shadow rays of bounce b are traced on the lane's second stream beside the closest-hit launch of bounce b + 1 (they are
                                     // independent; k_shade(b + 1) waits for both).  1 (default) = batches of up to 2^26 paths, whose launches do not keep the chip full for long:
@@ -546,6 +548,7 @@ ptc_ctx* ptc_create(int device_id) {
     c->device = PTC_DEVICE_NONE;
     if (const char* s = std::getenv("PTC_NODELETS")) c->toplet_budget = (uint32_t)std::strtoul(s, nullptr, 10);
     if (const char* s = std::getenv("PTC_BVH")) { if (std::strcmp(s, "lbvh") == 0) c->bvh_default = c->bvh_builder = PTC_BVH_LBVH; }
+    if (const char* s = std::getenv("PTC_DEVICE_BVH")) { if (std::strcmp(s, "sah") == 0) c->device_builder = PTC_BVH_SAH; }
     return c;
   }
   int n = 0;
@@ -580,6 +583,7 @@ ptc_ctx* ptc_create(int device_id) {
   if (const char* s = std::getenv("PTC_BATCH_PATHS")) { size_t v = std::strtoull(s, nullptr, 10); if (v >= 1024) c->max_batch_paths = v; }
   if (const char* s = std::getenv("PTC_TIMING")) { const int v = std::atoi(s); c->timing = v < 0 ? 0 : (v > 2 ? 2 : v); }
   if (const char* s = std::getenv("PTC_BVH")) { if (std::strcmp(s, "lbvh") == 0) c->bvh_default = c->bvh_builder = PTC_BVH_LBVH; }
+  if (const char* s = std::getenv("PTC_DEVICE_BVH")) { if (std::strcmp(s, "sah") == 0) c->device_builder = PTC_BVH_SAH; }
   if (const char* s = std::getenv("PTC_LANES")) { int v = std::atoi(s); if (v >= 1 && v <= 8) c->n_lanes = v; }
   c->lanes.resize((size_t)c->n_lanes);
   bool ok = true;
@@ -829,7 +833,8 @@ void scene_free(ptc_ctx* c, const void* p) {
 // ptc_scene_rebuild on the device: a refit's geometry pass, then a NEW tree for the vertices as they now lie in HBM (pt_build.hip), then the refit's node pass over
 // it.  Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed, fewer than two triangles): the caller builds on the host.
 // fresh: the device half of a COMMIT on the device (device_commit): there is no tree yet, the launch configuration follows the tree and is the caller's.
-int device_rebuild(ptc_ctx* c, bool fresh = false) {
+// builder: the tree the device builds (PTC_BVH_LBVH: pt_build_lbvh, PTC_BVH_SAH: pt_build_sah).
+int device_rebuild(ptc_ctx* c, int builder, bool fresh = false) {
   { int rc = ensure_refit_plan(c); if (rc) return rc; }
   if (c->built->n_tris < 2u) return 1;
   std::vector<float> xf, lights, cdf;
@@ -860,7 +865,8 @@ int device_rebuild(ptc_ctx* c, bool fresh = false) {
   BuildOut out;
   out.recs = c->rb_spare.recs; out.recs_cap = c->rb_spare.recs_cap; out.level_nodes = c->rb_spare.levels; out.level_cap = c->rb_spare.levels_cap;
   c->rb_spare.recs = nullptr; c->rb_spare.levels = nullptr; c->rb_spare.recs_cap = c->rb_spare.levels_cap = 0;      // the build owns them now (it may free them)
-  const std::string e = pt_build_lbvh(st, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out);
+  const std::string e = builder == PTC_BVH_SAH ? pt_build_sah(st, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out)
+                                                : pt_build_lbvh(st, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out);
   if (!e.empty()) { if (out.recs) (void)hipFree(out.recs); if (out.level_nodes) (void)hipFree(out.level_nodes); return fail(c, PTC_E_DEVICE, e); }
   // the new tree replaces the old one: unit array, the refit's level lists, the per-record boxes; the replaced arrays are the next rebuild's spare set
   const size_t nbox_need = (size_t)(out.n_units / 4u + 1u) * 6;
@@ -927,7 +933,7 @@ int device_rebuild(ptc_ctx* c, bool fresh = false) {
   B.sa_cost_fixed = cost_fixed;
   c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)cost_fixed / (double)PTC_SA_COST_ONE;
   c->stats.n_bvh_nodes = B.n_nodes; c->stats.bvh_max_depth = B.max_depth;
-  c->host_stale = true; c->last_refit_on_device = true;
+  c->host_stale = true; c->last_refit_on_device = true; c->tree_device_sah = builder == PTC_BVH_SAH;
   c->xf_live.swap(xf);
   return PTC_OK;
 }
@@ -948,9 +954,12 @@ int refresh_host_copy(ptc_ctx* c) {
   return PTC_OK;
 }
 // A full host build of the description as it stands + upload (what ptc_scene_commit does), keeping what a refit / rebuild keeps of the statistics.
+// The tree: a rebuild's is the device builder's (the one device_rebuild would have made); a refit's is the scene's builder, or the SAH when the tree it replaces
+// is a device SAH build.
 int host_build_and_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool as_refit) {
   auto built = std::make_shared<HostBuilt>();
-  const std::string e = ptc_build_scene(c->mats, c->meshes, c->insts, c->texs, c->env, c->toplet_budget, as_refit ? c->bvh_builder : PTC_BVH_LBVH, *built);
+  const int builder = as_refit ? (c->tree_device_sah ? PTC_BVH_SAH : c->bvh_builder) : c->device_builder;
+  const std::string e = ptc_build_scene(c->mats, c->meshes, c->insts, c->texs, c->env, c->toplet_budget, builder, *built);
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
   const ptc_stats keep = c->stats;
   c->built = built;
@@ -1023,7 +1032,7 @@ int ptc_scene_rebuild(ptc_ctx* c) {
   const auto t0 = std::chrono::steady_clock::now();
   if (c->built.use_count() > 1) c->built = std::make_shared<HostBuilt>(*c->built);      // a group shares one build: this context now gets its own
   const char* how = std::getenv("PTC_REBUILD");
-  int rd = (how && std::strcmp(how, "host") == 0) ? 1 : device_rebuild(c);
+  int rd = (how && std::strcmp(how, "host") == 0) ? 1 : device_rebuild(c, c->device_builder);
   if (rd < 0) return rd;
   if (rd > 0) { if ((rd = host_build_and_upload(c, t0, /*as_refit=*/false))) return rd; }      // PTC_REBUILD=host, an emitter appeared or vanished, a single triangle
   else c->stats.seconds_rebuild = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1054,6 +1063,13 @@ int ptc_set_bvh_builder(ptc_ctx* c, int builder) {
   return PTC_OK;
 }
 
+int ptc_set_device_builder(ptc_ctx* c, int builder) {
+  if (!c) return PTC_E_ARG;
+  if (builder != PTC_BVH_SAH && builder != PTC_BVH_LBVH) return fail(c, PTC_E_ARG, "set_device_builder: unknown builder");
+  c->device_builder = builder;
+  return PTC_OK;
+}
+
 int ptc_set_env_latlong_rgb32f(ptc_ctx* c, const float* rgb, int w, int h) {
   if (!c) return PTC_E_ARG;
   if (!rgb) { c->env = HostEnv{}; return PTC_OK; }
@@ -1079,7 +1095,7 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool ske
     c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)c->built->sa_cost_fixed / (double)PTC_SA_COST_ONE;
     return PTC_OK;
   }
-  c->committed = false; c->commit_on_device = false;
+  c->committed = false; c->commit_on_device = false; c->tree_device_sah = false;
   free_all(c->scene_allocs);
   free_rebuild_spare(c);
   c->refit_ready = false; c->host_stale = false; c->plan = RefitPlan(); c->drf = DevRefit{}; c->xf_live.clear();
@@ -1141,9 +1157,9 @@ int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
   return PTC_OK;
 }
 
-// ptc_scene_commit with the LBVH builder on a device context: the host describes (ptc_build_skeleton: indices, materials, emitters, textures), the DEVICE flattens the
+// ptc_scene_commit with the LBVH builder (or the SAH builder with the SAH device builder) on a device context: the host describes (ptc_build_skeleton: indices, materials, emitters, textures), the DEVICE flattens the
 // vertices, writes the shading records and builds the tree (pt_refit.hip, pt_build.hip) — the arrays in HBM are byte for byte those of the host's LBVH commit
-// (tests/test_gpu_parity.py).  Returns PTC_OK, an error, or +1: "not this way" (fewer than two triangles): the caller commits on the host.
+// (tests/test_gpu_parity.py, tests/test_gpu_device_sah.py).  Returns PTC_OK, an error, or +1: "not this way" (fewer than two triangles): the caller commits on the host.
 int device_commit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
   const bool timing = std::getenv("PTC_BUILD_TIMING") != nullptr;      // phase times on stderr, as the host build prints them
   auto tprev = std::chrono::steady_clock::now();
@@ -1170,7 +1186,7 @@ int device_commit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
     if (rc) { free_all(c->scene_allocs); return rc; }
     pt_launch_refit_seed(c->lanes[0].stream, c->drf, d_mat, d_light);
   }
-  const int rd = device_rebuild(c, /*fresh=*/true);
+  const int rd = device_rebuild(c, c->bvh_builder, /*fresh=*/true);
   if (rd) { free_all(c->scene_allocs); c->refit_ready = false; return rd; }
   lap("flatten + build on the device");
   const int rf = commit_finish(c, t0);
@@ -1180,7 +1196,9 @@ int device_commit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
 }
 }  // namespace
 
-int ptc_scene_commit(ptc_ctx* c) {
+namespace {
+// device_ok: the commit may build on the device (not for device 0 of a group with the SAH device builder: the others share its host build)
+int scene_commit(ptc_ctx* c, bool device_ok) {
   if (!c) return PTC_E_ARG;
   if (!c->have_cam) return fail(c, PTC_E_STATE, "scene_commit: no camera");
   if (c->device >= 0) {
@@ -1188,7 +1206,8 @@ int ptc_scene_commit(ptc_ctx* c) {
     { int rs = sync_all_lanes(c); if (rs) return rs; }
   }
   const auto t0 = std::chrono::steady_clock::now();
-  if (c->device >= 0 && c->bvh_builder == PTC_BVH_LBVH) {      // north_star's tree is the one that builds on the device: PTC_COMMIT=host keeps the host's build of it (the cross-check path)
+  // north_star's tree builds on the device, and so does the SAH tree with the SAH device builder: PTC_COMMIT=host keeps the host's build (the cross-check path)
+  if (device_ok && c->device >= 0 && (c->bvh_builder == PTC_BVH_LBVH || c->device_builder == PTC_BVH_SAH)) {
     const char* how = std::getenv("PTC_COMMIT");
     if (!(how && std::strcmp(how, "host") == 0)) {
       const int rd = device_commit(c, t0);
@@ -1201,6 +1220,9 @@ int ptc_scene_commit(ptc_ctx* c) {
   c->built = built;
   return commit_upload(c, t0);
 }
+}  // namespace
+
+int ptc_scene_commit(ptc_ctx* c) { return scene_commit(c, true); }
 
 int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
   { int rd = need_device(c); if (rd) return rd; }
@@ -1509,7 +1531,10 @@ int ptc_group_size(const ptc_group* g) { return g ? (int)g->ctx.size() : 0; }
 int ptc_group_scene_commit(ptc_group* g) {
   if (!g || g->ctx.empty()) return PTC_E_ARG;
   ptc_ctx* c0 = g->ctx[0];
-  int rc = c0->committed ? PTC_OK : ptc_scene_commit(c0);     // flatten + BVH build, once, on the host (a scene device 0 has committed already is taken as it is)
+  // flatten + BVH build, once, on the host (a scene device 0 has committed already is taken as it is; with the SAH device builder, a commit device 0 made on the
+  // device is made again on the host: the other devices share device 0's host arrays)
+  const bool sah_dev = c0->device_builder == PTC_BVH_SAH;
+  int rc = c0->committed && !(sah_dev && c0->commit_on_device) ? PTC_OK : scene_commit(c0, /*device_ok=*/!sah_dev);
   if (rc) { g->err = std::string("device 0: ") + ptc_last_error(c0); return rc; }
   for (size_t i = 1; i < g->ctx.size(); ++i) {
     ptc_ctx* c = g->ctx[i];
@@ -1737,7 +1762,8 @@ int ptc_debug_get_internals(ptc_ctx* c, uint64_t out[8]) {
   if (!c || !out) return PTC_E_ARG;
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = c->events_created; out[1] = c->spans.size(); out[2] = c->lanes.empty() ? 0 : c->lanes[0].q.cap; out[3] = c->per_batch; out[4] = c->pending;
-  out[5] = (uint64_t)c->cfg.trace_blocks_per_cu; out[6] = (uint64_t)c->cfg.stack_lds; out[7] = (c->last_refit_on_device ? 1u : 0u) | (c->commit_on_device ? 2u : 0u);
+  out[5] = (uint64_t)c->cfg.trace_blocks_per_cu; out[6] = (uint64_t)c->cfg.stack_lds;
+  out[7] = (c->last_refit_on_device ? 1u : 0u) | (c->commit_on_device ? 2u : 0u) | (c->tree_device_sah ? 4u : 0u);
   return PTC_OK;
 }
 

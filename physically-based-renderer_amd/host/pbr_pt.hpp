@@ -110,6 +110,9 @@ public:
   }
   // PTC_BVH_SAH (default) or PTC_BVH_LBVH, for the scene being described
   auto setBvhBuilder(int builder) -> void { ck(ptc_set_bvh_builder(_ctx, builder)); }
+  // the tree a build on the device makes (kept across beginScene): PTC_BVH_LBVH (default), or PTC_BVH_SAH — a SAH scene then commits on the device and
+  // ptc_scene_rebuild makes the SAH tree
+  auto setDeviceBuilder(int builder) -> void { ck(ptc_set_device_builder(_ctx, builder)); }
   auto commitScene() -> void { ck(ptc_scene_commit(_ctx)); }
 
   // replaces PbrRenderSystem::render: fills an fp32 RGBA radiance buffer (w*h*4, y-down)

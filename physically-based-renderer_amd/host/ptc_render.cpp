@@ -1,6 +1,6 @@
 // ptc_render — dependency-free C++17 offline renderer over the C-ABI (include/ptc.h).
 //   ptc_render (--scene cornell|sphere | --gltf file.glb [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
-//              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device D] [--gpus N]
+//              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16]
 // --gpus N: devices D..D+N-1 share the frame by 32x32-pixel tiles, one RCCL reduce brings it to device D (ptc_group_*).
 // --raster16: the reference's Blinn-Phong pass lit from its G-buffer formats; --half writes the RGBA16F buffer (raw little-endian halves).
@@ -108,6 +108,7 @@ int main(int argc, char** argv) {
   bool sky = false;
   int filter = PTC_FILTER_NEAREST;          // what the reference's default-constructed samplers do
   int bvh = -1;                             // -1: the context's default (SAH, or PTC_BVH in the environment)
+  int deviceBvh = -1;                       // --device-bvh: the tree a build on the device makes; -1: the context's default (LBVH, or PTC_DEVICE_BVH)
   float camPos[3] = {0, 0, 0}, camTarget[3] = {0, 0, -1}, fovDeg = 60.0f;
   bool haveCam = false;
   float viewerFov = 0.0f;                    // --viewer-camera: the reference's fov in radians, passed on without a degree round trip
@@ -134,6 +135,7 @@ int main(int argc, char** argv) {
     else if (a == "--cam-target") { for (float& v : camTarget) v = (float)std::atof(next()); }
     else if (a == "--fov") fovDeg = (float)std::atof(next());
     else if (a == "--bvh") { const std::string f = next(); if (f == "lbvh") bvh = PTC_BVH_LBVH; else if (f == "sah") bvh = PTC_BVH_SAH; else { std::cerr << "--bvh sah|lbvh\n"; return 2; } }
+    else if (a == "--device-bvh") { const std::string f = next(); if (f == "lbvh") deviceBvh = PTC_BVH_LBVH; else if (f == "sah") deviceBvh = PTC_BVH_SAH; else { std::cerr << "--device-bvh sah|lbvh\n"; return 2; } }
     else if (a == "--out") out = next(); else if (a == "--png") png = next(); else if (a == "--ppm") ppm = next(); else if (a == "--raster") integrator = PTC_INTEGRATOR_RASTER_COMPAT;
     else { std::cerr << "unknown argument " << a << "\n"; return 2; }
   }
@@ -141,6 +143,7 @@ int main(int argc, char** argv) {
     if (gpus < 0) throw std::runtime_error("--gpus must be >= 1");
     if (gltf.empty() && (!envPath.empty() || sky)) throw std::runtime_error("--env / --sky light a --gltf scene; the built-in scenes carry their own lights");
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
+    if (deviceBvh >= 0) rs.setDeviceBuilder(deviceBvh);
     if (!gltf.empty()) {
       const pbr::gltf::FlatScene fs = pbr::gltf::load(gltf);
       rs.beginScene();

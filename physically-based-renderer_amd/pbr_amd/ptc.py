@@ -30,7 +30,7 @@ ABI_VERSION = 4
 # every symbol include/ptc.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ptc_create", "ptc_destroy", "ptc_last_error", "ptc_abi_version", "ptc_build_info", "ptc_launch_policy", "ptc_scene_begin", "ptc_add_material",
-    "ptc_add_texture_rgba8", "ptc_add_mesh", "ptc_add_instance", "ptc_add_instance_matrix", "ptc_update_instance", "ptc_update_instance_matrix", "ptc_scene_refit", "ptc_scene_rebuild", "ptc_set_camera", "ptc_set_env_latlong_rgb32f", "ptc_set_texture_filter", "ptc_set_bvh_builder", "ptc_scene_commit", "ptc_render",
+    "ptc_add_texture_rgba8", "ptc_add_mesh", "ptc_add_instance", "ptc_add_instance_matrix", "ptc_update_instance", "ptc_update_instance_matrix", "ptc_scene_refit", "ptc_scene_rebuild", "ptc_set_camera", "ptc_set_env_latlong_rgb32f", "ptc_set_texture_filter", "ptc_set_bvh_builder", "ptc_set_device_builder", "ptc_scene_commit", "ptc_render",
     "ptc_frame_begin", "ptc_frame_add_samples", "ptc_frame_reserve", "ptc_frame_resolve", "ptc_frame_checkpoint", "ptc_frame_restore", "ptc_frame_set_sample_range", "ptc_sync", "ptc_read_radiance_rgba32f",
     "ptc_radiance_device_ptr", "ptc_write_radiance_rgba32f", "ptc_tonemap_rgba8", "ptc_get_stats",
     "ptc_debug_trace_closest", "ptc_debug_trace_any", "ptc_debug_get_flat_scene", "ptc_debug_get_bvh", "ptc_debug_get_counters",
@@ -99,6 +99,7 @@ def load_library():
     L.ptc_set_env_latlong_rgb32f.argtypes = [vp, fp, C.c_int, C.c_int]
     L.ptc_set_texture_filter.argtypes = [vp, C.c_int]
     L.ptc_set_bvh_builder.argtypes = [vp, C.c_int]
+    L.ptc_set_device_builder.argtypes = [vp, C.c_int]
     L.ptc_scene_commit.argtypes = [vp]
     L.ptc_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int]
     L.ptc_frame_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -195,6 +196,8 @@ class PathTracer:
 
     # ---- scene ------------------------------------------------------------------------------------
     def load_scene(self, desc):
+        """Describe `desc` and commit it (ptc_scene_commit): on the host, or on the device for an LBVH scene — and for a SAH scene when the device builder is
+        the SAH (set_device_builder("sah") before this call, or PTC_DEVICE_BVH=sah in the environment)."""
         L, h = self._L, self._h
         self._ck(L.ptc_scene_begin(h))
         for t in getattr(desc, "textures", []):
@@ -247,8 +250,14 @@ class PathTracer:
         """ptc_launch_policy of this context (after a commit: with the launch configuration that followed)."""
         return self._L.ptc_launch_policy(self._h).decode()
 
+    def set_device_builder(self, builder):
+        """ptc_set_device_builder: the tree a build on the device makes, "lbvh" (the default) or "sah" (the host's binned-SAH tree, byte for byte); kept across
+        load_scene.  With "sah" a SAH scene commits on the device and scene_rebuild makes the SAH tree."""
+        self._ck(self._L.ptc_set_device_builder(self._h, {"sah": 0, "lbvh": 1}[builder]))
+        return self
+
     def scene_rebuild(self):
-        """ptc_scene_rebuild: pending transforms + a new LBVH for the moved geometry, built on the device."""
+        """ptc_scene_rebuild: pending transforms + a new tree for the moved geometry, built on the device: the device builder's (set_device_builder), the LBVH by default."""
         self._ck(self._L.ptc_scene_rebuild(self._h))
         return self
 
@@ -398,6 +407,7 @@ class PathTracer:
         keys = ("events_created", "spans_waiting", "queue_cap", "per_batch", "pending", "trace_blocks_per_cu", "stack_lds", "refit_on_device")
         d = {k: int(buf[i]) for i, k in enumerate(keys)}
         d["commit_on_device"] = (d["refit_on_device"] >> 1) & 1
+        d["device_build_sah"] = (d["refit_on_device"] >> 2) & 1
         d["refit_on_device"] &= 1
         return d
 

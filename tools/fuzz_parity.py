@@ -3,7 +3,8 @@
 scene through the LBVH builder (committed ON THE DEVICE — flatten, shading records, tree — and held byte for byte against the host's commit of the same description), every other scene moved and refitted afterwards (ptc_update_instance + ptc_scene_refit against the oracle's; the refit runs on
 the device, csrc/pt_refit.hip, and its BVH units and shading tables are also held byte for byte against a host refit of the same moves on a description-only context);
 every scene with two triangles or more is finally REBUILT on the device (ptc_scene_rebuild, csrc/pt_build.hip) and held, byte for byte, against a fresh host commit of the scene
-as it then stands with the LBVH builder, and its image and counters against the oracle's LBVH of it.
+as it then stands with the LBVH builder, and its image and counters against the oracle's LBVH of it.  With PTC_DEVICE_BVH=sah in the environment the device builds the
+binned-SAH tree (ptc_set_device_builder): the SAH scenes commit on the device too, and every rebuild is held against a host commit with the SAH builder.
 usage: python tools/fuzz_parity.py [n] [seed]"""
 import importlib.util, os, sys
 import numpy as np
@@ -18,6 +19,8 @@ bad = 0
 n_dev_refits = 0
 n_rebuilds = 0
 n_dev_commits = 0
+n_sah_commits = n_sah_rebuilds = 0
+rebuild_builder = "sah" if os.environ.get("PTC_DEVICE_BVH") == "sah" else "lbvh"      # the tree ptc_scene_rebuild makes
 for k in range(n):
     if k % 50 == 0: print("scene", k, flush=True)
     d = tg._random_scene(pbr.scene, rng, k)
@@ -32,6 +35,7 @@ for k in range(n):
         print("MISMATCH scene", k, d.bvh_builder, "pixels", int((g != c).any(-1).sum()), flush=True)
     if pt.internals()["commit_on_device"]:       # an LBVH scene on a device context flattens and builds ON THE DEVICE: the bytes of the host's commit of the same description
         n_dev_commits += 1
+        n_sah_commits += pt.internals()["device_build_sah"]
         a, b = tg._scene_bytes(pt), tg._scene_bytes(pbr.PathTracer(pbr.DEVICE_NONE).load_scene(d))
         if not all(a[key].shape == b[key].shape and np.array_equal(a[key], b[key]) for key in a):
             bad += 1
@@ -71,7 +75,7 @@ for k in range(n):
     if pt.stats()["n_triangles"] >= 2:
         import copy
         d2 = copy.deepcopy(d)
-        d2.bvh_builder = "lbvh"
+        d2.bvh_builder = rebuild_builder
         try:
             pt.scene_rebuild()
         except pbr.PtcError as e:
@@ -79,6 +83,7 @@ for k in range(n):
             print("REBUILD FAILED scene", k, e, flush=True)
             continue
         n_rebuilds += 1
+        n_sah_rebuilds += pt.internals()["device_build_sah"]
         for i, m in moves:                      # the moves, written into the description: a commit of THAT is what the rebuilt tree must equal
             if m[0] == "m":
                 d2.instances[i].matrix = m[1]
@@ -89,11 +94,11 @@ for k in range(n):
         a, b = tg._scene_bytes(pt), tg._scene_bytes(fresh)
         if not all(a[x].shape == b[x].shape and np.array_equal(a[x], b[x]) for x in a):
             bad += 1
-            print("MISMATCH device rebuild vs host LBVH commit, scene", k, [x for x in a if not (a[x].shape == b[x].shape and np.array_equal(a[x], b[x]))], flush=True)
+            print(f"MISMATCH device rebuild vs host {rebuild_builder} commit, scene", k, [x for x in a if not (a[x].shape == b[x].shape and np.array_equal(a[x], b[x]))], flush=True)
         g, c = pt.render(w, h, spp, seed=s, max_bounces=mb), o2.render(w, h, spp, seed=s, max_bounces=mb)
         ok = np.array_equal(g.view(np.uint32), c.view(np.uint32)) and all(pt.stats()[x] == o2.stats()[x] for x in tg.COUNTERS)
         if not ok:
             bad += 1
             print("MISMATCH after rebuild, scene", k, "pixels", int((g != c).any(-1).sum()), flush=True)
-print(f"{n} scenes, {n_dev_commits} commits on the device, {n_dev_refits} refits on the device, {n_rebuilds} rebuilds on the device, {bad} mismatches")
+print(f"{n} scenes, {n_dev_commits} commits on the device ({n_sah_commits} SAH), {n_dev_refits} refits on the device, {n_rebuilds} rebuilds on the device ({n_sah_rebuilds} SAH), {bad} mismatches")
 sys.exit(1 if bad else 0)

@@ -3,7 +3,8 @@
 instances get a new rotation (ptc_update_instance), the scene is refitted (ptc_scene_refit, on the device), the frame is path-traced at `spp` samples
 per pixel and resolved into the RGBA16F image the viewer's tonemapper reads (ptc_radiance_rgba16f_device_ptr: no copy to the host).  Wall time per
 frame over `frames` frames, and where it goes.  VIEWER_REBUILD_RATIO=r in the environment adds the policy of examples/viewer_shim.cpp: after the refit, a rebuild on the
-device (ptc_scene_rebuild) when ptc_stats.bvh_sa_cost has grown past r times bvh_sa_cost_built.  usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h]"""
+device (ptc_scene_rebuild) when ptc_stats.bvh_sa_cost has grown past r times bvh_sa_cost_built; the frame times before and after the first rebuild are reported apart.
+With PTC_DEVICE_BVH=sah in the environment the rebuilt tree is the binned-SAH tree (ptc_set_device_builder), else the LBVH.  usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h]"""
 import json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))
@@ -20,6 +21,7 @@ moving = [i for i, it in enumerate(d.instances) if i % 3 == 0 and getattr(it, "m
 t_refit, t_frame = [], []
 ratio = float(os.environ.get("VIEWER_REBUILD_RATIO", "0"))
 rebuilds = 0
+first_rebuild = None                                  # index into t_frame of the first frame after the first rebuild
 for k in range(frames + 5):
     t0 = time.perf_counter()
     a = 0.01 * (k + 1)
@@ -30,6 +32,7 @@ for k in range(frames + 5):
         st_ = pt.stats()
         if st_["bvh_sa_cost"] > ratio * st_["bvh_sa_cost_built"]:
             pt.scene_rebuild(); rebuilds += 1
+            if first_rebuild is None: first_rebuild = max(k - 5, 0)
     t1 = time.perf_counter()
     pt.frame_begin(w, h, spp, seed=k, max_bounces=8)
     pt.frame_add_samples(spp)
@@ -45,5 +48,9 @@ out = {"scene": d.name, "triangles": st["n_triangles"], "moving_instances": len(
        "fps": 1.0 / float(np.median(t_frame)),
        "ms_update_and_refit": 1e3 * float(np.median(t_refit)), "ms_refit_device_side": 1e3 * st["seconds_refit"],
        "Mpaths_per_s": w * h * spp / float(np.median(t_frame)) / 1e6, "half_image_device_ptr": hex(ptr),
-       "rebuild_ratio": ratio, "rebuilds": rebuilds, "sa_cost_ratio_at_end": st["bvh_sa_cost"] / st["bvh_sa_cost_built"]}
+       "rebuild_ratio": ratio, "rebuilds": rebuilds, "sa_cost_ratio_at_end": st["bvh_sa_cost"] / st["bvh_sa_cost_built"],
+       "device_builder": "sah" if os.environ.get("PTC_DEVICE_BVH") == "sah" else "lbvh"}
+if first_rebuild is not None and 0 < first_rebuild < len(t_frame) - 1:     # the rebuild frame itself counts in neither
+    out["ms_per_frame_before_first_rebuild"] = 1e3 * float(np.median(t_frame[:first_rebuild]))
+    out["ms_per_frame_after_first_rebuild"] = 1e3 * float(np.median(t_frame[first_rebuild + 1:]))
 print(json.dumps(out))
