@@ -42,13 +42,39 @@ struct Lane {
   hipStream_t stream = nullptr;
   DevQueues q{};
   std::vector<void*> allocs;        // the large queue arrays (sized q.cap)
-  uint2* stack_ovf = nullptr;       // traversal-stack overflow slab (belongs to the committed scene)
+  uint2* stack_ovf = nullptr;       // traversal-stack overflow slab of the committed scene (ensure_overflow_slabs; freed by release_scene)
   DevScene* d_scene = nullptr;      // this lane's DevScene in device memory (k_shade reads it through a pointer instead of ~200 B of kernel arguments)
   hipEvent_t acc_done = nullptr;    // "this lane's last accumulate finished"
   // PTC_TRACE_OVERLAP=1: the shadow rays of bounce b are traced on a second stream beside the closest-hit launch of bounce b + 1
   hipStream_t stream2 = nullptr;
   uint2* stack_ovf2 = nullptr;      // the any-hit launches' own overflow slab (concurrent kernels must not share one)
   std::vector<hipEvent_t> ev_scan, ev_any;
+  void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
+};
+
+// The arrays of a tree in HBM: unit array, the refit's level list, the per-record node boxes, with their capacities (a rebuild writes into arrays large enough)
+struct TreeBufs {
+  float4* recs = nullptr; size_t recs_cap = 0; uint32_t* levels = nullptr; size_t levels_cap = 0; float* nbox = nullptr; size_t nbox_cap = 0;
+  void release() { for (void* p : {(void*)recs, (void*)levels, (void*)nbox}) if (p) (void)hipFree(p); *this = TreeBufs(); }
+};
+
+// The committed scene on the device and what the refit, the rebuild and the commit on the device keep of it.  release_scene frees all of it.
+struct CommittedScene {
+  DevScene dsc{};
+  std::vector<void*> allocs;        // every array of dsc and drf but the tree's
+  size_t insts = 0;                 // instances the committed scene was built from (ptc_scene_refit refuses a description that has grown since)
+  // refit on the device (pt_refit.h): the plan is built and uploaded by the first ptc_scene_refit after a commit
+  RefitPlan plan;
+  DevRefit drf{};
+  bool refit_ready = false;
+  bool host_stale = false;          // the device refitted in place: built's vertex-dependent arrays are those of an earlier state until refresh_host_copy
+  TreeBufs live, spare;             // the tree in use; a rebuild writes the new tree into the spare set and the arrays it replaces become the spare: no
+                                    // allocation in a viewer's steady state
+  std::vector<float> xf_live;       // instance transforms of the last refit the device completed (a refused one re-flattens its scratch vertices from these)
+  // how the last calls went (ptc_debug_get_internals); release_scene keeps them
+  bool last_refit_on_device = false;
+  bool commit_on_device = false;      // the last ptc_scene_commit flattened and built on the device (device_commit)
+  bool tree_device_sah = false;       // the tree in HBM was built on the device by the SAH front end (pt_build_sah)
 };
 
 // ---- RCCL, loaded on first use (a renderer that never reduces does not need librccl at load time) -------------------
@@ -112,20 +138,10 @@ struct ptc_ctx {
   int device_builder = PTC_BVH_LBVH;     // PTC_BVH_*: the tree a build ON THE DEVICE makes (ptc_set_device_builder; PTC_DEVICE_BVH=sah in the environment), kept across ptc_scene_begin
   // committed scene
   bool committed = false;
-  size_t committed_insts = 0;       // instances the committed scene was built from (ptc_scene_refit refuses a description that has grown since)
   std::shared_ptr<HostBuilt> built = std::make_shared<HostBuilt>();   // the host build; the contexts of a ptc_group share one (ptc_group_scene_commit)
-  DevScene dsc{};
+  CommittedScene scene;
   DevCamera cam{};
-  std::vector<void*> scene_allocs;
-  // refit on the device (pt_refit.h): the plan is built and uploaded by the first ptc_scene_refit after a commit
   int refit_on_device = 1;          // PTC_REFIT=host: ptc_scene_refit recomputes on the host and uploads (the round-3a path, kept as the cross-check)
-  bool refit_ready = false;
-  RefitPlan plan;
-  DevRefit drf{};
-  bool host_stale = false;          // the device refitted in place: built's vertex-dependent arrays are those of an earlier state until refresh_host_copy
-  bool last_refit_on_device = false;
-  bool commit_on_device = false;      // the last ptc_scene_commit flattened and built on the device (device_commit)
-  bool tree_device_sah = false;       // the tree in HBM was built on the device by the SAH front end (pt_build_sah)
   int trace_rays_per_lane = 8;      // PTC_TRACE_RAYS_PER_LANE: rays per lane of the trace kernels' grid a batch should offer before the grid is made smaller (run_batch)
   int trace_overlap = 1;            // PTC_TRACE_OVERLAP: the shadow rays of bounce b are traced on the lane's second stream beside the closest-hit launch of bounce b + 1 (they are
                                     // independent; k_shade(b + 1) waits for both).  1 (default) = batches of up to 2^26 paths, whose launches do not keep the chip full for long:
@@ -133,10 +149,6 @@ struct ptc_ctx {
                                     // batch size, but the two kernels' launch durations then include each other: not the default, so that what bench.py and rocprofv3 time
                                     // per kernel stays a kernel's own time); 0 = never
   BuildScratch bscratch;            // device scratch of ptc_scene_rebuild (pt_build.hip), grow-only
-  struct RebuildBufs { float4* recs = nullptr; size_t recs_cap = 0; uint32_t* levels = nullptr; size_t levels_cap = 0; float* nbox = nullptr; size_t nbox_cap = 0; };
-  RebuildBufs rb_spare, rb_live;    // a rebuild writes the new tree into the spare unit array / level list / box array and the ones it replaces become the spare: no
-                                    // allocation in a viewer's steady state (rb_live: capacities of the arrays in use; the spare set is not in scene_allocs)
-  std::vector<float> xf_live;       // instance transforms of the last refit the device completed (a refused one re-flattens its scratch vertices from these)
   // lanes: lane 0 is the context's primary stream (resolve, tonemap, conversions, the reduce)
   std::vector<Lane> lanes;
   int n_lanes = 1;                  // PTC_LANES: >1 runs successive batches on separate streams.  With the round-2 kernels one lane
@@ -211,11 +223,15 @@ template <class T> int dev_upload(ptc_ctx* c, std::vector<void*>& owner, const T
   return PTC_OK;
 }
 void free_all(std::vector<void*>& v) { for (void* p : v) (void)hipFree(p); v.clear(); }
-void free_rebuild_spare(ptc_ctx* c) {      // the arrays a rebuild replaced (kept for the next one); the live set is in scene_allocs
-  if (c->rb_spare.recs) (void)hipFree(c->rb_spare.recs);
-  if (c->rb_spare.levels) (void)hipFree(c->rb_spare.levels);
-  if (c->rb_spare.nbox) (void)hipFree(c->rb_spare.nbox);
-  c->rb_spare = ptc_ctx::RebuildBufs(); c->rb_live = ptc_ctx::RebuildBufs();
+// Frees every array of the committed scene, the lanes' overflow slabs included, and forgets its state; the flags of how the last calls went stay
+void release_scene(ptc_ctx* c) {
+  CommittedScene& s = c->scene;
+  free_all(s.allocs);
+  s.live.release(); s.spare.release();
+  for (auto& ln : c->lanes) ln.free_overflow_slabs();
+  CommittedScene fresh;
+  fresh.last_refit_on_device = s.last_refit_on_device; fresh.commit_on_device = s.commit_on_device; fresh.tree_device_sah = s.tree_device_sah;
+  s = std::move(fresh);
 }
 
 template <class T> int ensure_buf(ptc_ctx* c, DevBuf<T>& b, size_t n) {
@@ -311,6 +327,27 @@ int trace_blocks_per_cu_cached(size_t lds) {
   return v;
 }
 
+// Traversal-stack overflow slabs deep enough for the tree beyond the stack entries kept in LDS, allocated when the slabs there are shallower (a commit has none): one
+// per lane, and with trace overlap the any-hit launches' own (concurrent kernels must not share one).  A lane's new slabs are allocated before its old ones are
+// freed, so a failed allocation leaves the old, still valid, ones in place.
+int ensure_overflow_slabs(ptc_ctx* c) {
+  const int need = (int)c->built->max_depth + 2;
+  const uint32_t ovf = (uint32_t)(need - c->cfg.stack_lds > 0 ? need - c->cfg.stack_lds : 1);
+  if (ovf <= c->scene.dsc.ovf_depth) return PTC_OK;
+  const size_t total_waves = (size_t)c->cfg.n_cu * (size_t)c->cfg.trace_blocks_per_cu * (size_t)(pt_trace_block_threads() / 64);   // the persistent grid
+  for (auto& ln : c->lanes) {
+    std::vector<void*> fresh;
+    uint2 *a = nullptr, *b = nullptr;
+    int rc = dev_alloc(c, fresh, &a, total_waves * ovf * 64);
+    if (!rc && c->trace_overlap) rc = dev_alloc(c, fresh, &b, total_waves * ovf * 64);
+    if (rc) { free_all(fresh); return rc; }
+    ln.free_overflow_slabs();
+    ln.stack_ovf = a; ln.stack_ovf2 = b;
+  }
+  c->scene.dsc.ovf_depth = ovf;
+  return PTC_OK;
+}
+
 int configure_launch(ptc_ctx* c) {
   // Traversal stack: at most one group of pending children per tree level, so a ray needs at most depth+1 entries.
   // `stack_lds` of them live in LDS (8 B each, 512 B per level and wave), the rest in a global overflow slab.
@@ -325,7 +362,7 @@ int configure_launch(ptc_ctx* c) {
   size_t lds = 0;
   for (;; --l) {
     c->cfg.stack_lds = l;
-    lds = pt_trace_lds_bytes(c->cfg, c->dsc);
+    lds = pt_trace_lds_bytes(c->cfg, c->scene.dsc);
     if (lds > 160u * 1024u) { if (l > 1 && !l_forced) continue; return fail(c, PTC_E_ARG, "configure_launch: staged tree top + stack exceed the 160 KiB of LDS"); }
     per_cu = trace_blocks_per_cu_cached(lds);     // registers, static LDS and launch bounds included
     if (per_cu >= 8 || l <= 2 || l_forced) break;
@@ -333,25 +370,22 @@ int configure_launch(ptc_ctx* c) {
   if (per_cu < 1) return fail(c, PTC_E_DEVICE, "configure_launch: the trace kernels do not fit a CU with this LDS size");
   if (const char* e = std::getenv("PTC_TRACE_BLOCKS_PER_CU")) { int v = std::atoi(e); if (v >= 1 && v <= per_cu) per_cu = v; }
   c->cfg.trace_blocks_per_cu = per_cu;
-  const uint32_t ovf = (uint32_t)(need - l > 0 ? need - l : 1);
-  const size_t total_waves = (size_t)c->cfg.n_cu * (size_t)per_cu * (size_t)(pt_trace_block_threads() / 64);   // the persistent grid
-  c->dsc.ovf_depth = ovf;
-  for (auto& ln : c->lanes) {                                    // concurrent kernels must not share a slab
-    uint2* pl = nullptr;
-    int rc = dev_alloc(c, c->scene_allocs, &pl, total_waves * ovf * 64);
-    if (rc) return rc;
-    ln.stack_ovf = pl;
-    ln.stack_ovf2 = nullptr;
-    if (c->trace_overlap) {
-      if ((rc = dev_alloc(c, c->scene_allocs, &pl, total_waves * ovf * 64))) return rc;
-      ln.stack_ovf2 = pl;
+  { int rc = ensure_overflow_slabs(c); if (rc) return rc; }
+  if (c->trace_overlap)
+    for (auto& ln : c->lanes)
       if (!ln.stream2 && hipStreamCreateWithFlags(&ln.stream2, hipStreamNonBlocking) != hipSuccess) return fail(c, PTC_E_DEVICE, "configure_launch: hipStreamCreate failed");
-    }
-  }
   return PTC_OK;
 }
 
-DevScene lane_scene(ptc_ctx* c, int l) { DevScene d = c->dsc; d.stack_ovf = c->lanes[(size_t)l].stack_ovf; return d; }
+DevScene lane_scene(ptc_ctx* c, int l) { DevScene d = c->scene.dsc; d.stack_ovf = c->lanes[(size_t)l].stack_ovf; return d; }
+// Every lane's copy of the scene (k_shade reads it through a pointer), enqueued on `st`: the caller synchronises
+int publish_lane_scenes(ptc_ctx* c, hipStream_t st) {
+  for (int l = 0; l < c->n_lanes; ++l) {
+    const DevScene ds = lane_scene(c, l);
+    HIP_TRY(c, hipMemcpyAsync(c->lanes[(size_t)l].d_scene, &ds, sizeof ds, hipMemcpyHostToDevice, st));
+  }
+  return PTC_OK;
+}
 // the lane's queues with the segment layout of a batch of n slots (ptc_internal.h, "SEGMENTED queues")
 DevQueues batch_queues(ptc_ctx* c, int l, uint32_t n) {
   DevQueues q = c->lanes[(size_t)l].q;
@@ -534,7 +568,7 @@ const char* ptc_launch_policy(const ptc_ctx* c) {
   out = std::string(pt_kernel_policy()) + buf;
   if (c && c->committed && c->device >= 0) {
     std::snprintf(buf, sizeof buf, " | trace_blocks_per_cu=%d stack_lds=%d lds_units=%u ovf_depth=%u shade_segments=%d shade_tables_lds=%d", c->cfg.trace_blocks_per_cu, c->cfg.stack_lds,
-                  c->dsc.n_lds_units, c->dsc.ovf_depth, c->cfg.shade_waves, c->cfg.shade_tables_lds);
+                  c->scene.dsc.n_lds_units, c->scene.dsc.ovf_depth, c->cfg.shade_waves, c->cfg.shade_tables_lds);
     out += buf;
   }
   return out.c_str();
@@ -616,14 +650,13 @@ void ptc_destroy(ptc_ctx* c) {
     if (ln.q.stats) (void)hipFree(ln.q.stats);
     if (ln.q.seg_ray[0]) (void)hipFree(ln.q.seg_ray[0]);
     if (ln.d_scene) (void)hipFree(ln.d_scene);
-    if (c->bscratch.p) { (void)hipFree(c->bscratch.p); c->bscratch = BuildScratch(); }
-    free_rebuild_spare(c);
     if (ln.stream) (void)hipStreamDestroy(ln.stream);
     if (ln.stream2) (void)hipStreamDestroy(ln.stream2);
     for (hipEvent_t e : ln.ev_scan) (void)hipEventDestroy(e);
     for (hipEvent_t e : ln.ev_any) (void)hipEventDestroy(e);
   }
-  free_all(c->scene_allocs);
+  release_scene(c);
+  if (c->bscratch.p) (void)hipFree(c->bscratch.p);
   c->owned.release(); c->accum.release(); c->radiance.release(); c->ldr.release(); c->half.release();
   delete c;
 }
@@ -639,8 +672,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->mats.clear(); c->meshes.clear(); c->insts.clear(); c->texs.clear(); c->env = HostEnv{}; c->tex_linear = 0;
   c->bvh_builder = c->bvh_default;
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0;
-  free_all(c->scene_allocs);
-  for (auto& ln : c->lanes) ln.stack_ovf = nullptr;
+  release_scene(c);
   return PTC_OK;
 }
 
@@ -709,18 +741,17 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool ske
 // environment and materials stay where they are); else (an emitter appeared or vanished under a degenerate scale) upload everything.
 int refit_upload(ptc_ctx* c, bool same_sizes, std::chrono::steady_clock::time_point t0) {
   const HostBuilt& B = *c->built;
-  c->host_stale = false; c->last_refit_on_device = false;
+  DevScene& d = c->scene.dsc;
+  c->scene.host_stale = false; c->scene.last_refit_on_device = false;
   if (!same_sizes) return commit_upload(c, t0);
-  HIP_TRY(c, hipMemcpy((void*)c->dsc.recs, B.recs.data(), B.recs.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy((void*)c->dsc.shade, B.shade.data(), B.shade.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy((void*)c->dsc.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy((void*)c->dsc.cdf, B.cdf.data(), B.cdf.size() * 4, hipMemcpyHostToDevice));
-  c->dsc.ray_eps = B.ray_eps; c->dsc.n_lights = B.n_lights;
-  for (int k = 0; k < 3; ++k) { c->dsc.grid_lo[k] = B.grid_lo[k]; c->dsc.grid_step[k] = B.grid_step[k]; }
-  for (int l = 0; l < c->n_lanes; ++l) {
-    const DevScene ds = lane_scene(c, l);
-    HIP_TRY(c, hipMemcpy(c->lanes[(size_t)l].d_scene, &ds, sizeof ds, hipMemcpyHostToDevice));
-  }
+  HIP_TRY(c, hipMemcpy((void*)d.recs, B.recs.data(), B.recs.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy((void*)d.shade, B.shade.data(), B.shade.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy((void*)d.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy((void*)d.cdf, B.cdf.data(), B.cdf.size() * 4, hipMemcpyHostToDevice));
+  d.ray_eps = B.ray_eps; d.n_lights = B.n_lights;
+  for (int k = 0; k < 3; ++k) { d.grid_lo[k] = B.grid_lo[k]; d.grid_step[k] = B.grid_step[k]; }
+  { int rc = publish_lane_scenes(c, c->lanes[0].stream); if (rc) return rc; }
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
   return PTC_OK;
 }
 
@@ -729,31 +760,41 @@ bool refit_on_device(ptc_ctx* c) {
   return c->refit_on_device != 0;
 }
 
-// The plan of the committed scene in HBM + the scratch arrays of the refit kernels; once per commit.
+void use_live_tree(ptc_ctx* c) {      // dsc and drf address the live tree set
+  CommittedScene& s = c->scene;
+  s.dsc.recs = s.live.recs; s.drf.recs = s.live.recs; s.drf.level_nodes = s.live.levels; s.drf.nbox = s.live.nbox;
+}
+
+// The plan of the committed scene in HBM + the scratch arrays of the refit kernels; once per commit.  The level list and the node boxes join the live tree set.
 int ensure_refit_plan(ptc_ctx* c) {
-  if (c->refit_ready) return PTC_OK;
+  CommittedScene& s = c->scene;
+  if (s.refit_ready) return PTC_OK;
   const HostBuilt& B = *c->built;
-  ptc_refit_plan(c->mats, c->meshes, c->insts, B, c->plan);
-  const RefitPlan& P = c->plan;
+  ptc_refit_plan(c->mats, c->meshes, c->insts, B, s.plan);
+  const RefitPlan& P = s.plan;
+  const size_t nbox_cap = (size_t)(B.n_units / 4u + 1u) * 6;
   DevRefit d{};
-  int rc = dev_upload(c, c->scene_allocs, &d.mesh_verts, P.mesh_verts);
-  if (!rc) rc = dev_upload(c, c->scene_allocs, &d.vert_inst, P.vert_inst);
-  if (!rc) rc = dev_upload(c, c->scene_allocs, &d.inst_first, P.inst_first);
-  if (!rc) rc = dev_upload(c, c->scene_allocs, &d.inst_src, P.inst_src);
-  if (!rc) rc = dev_upload(c, c->scene_allocs, &d.widx, B.widx);
-  if (!rc) rc = dev_upload(c, c->scene_allocs, &d.level_nodes, P.level_nodes);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.inst_xf, c->insts.size() * 21);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.wverts, (size_t)P.n_verts);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.wbt, (size_t)P.n_verts * 3);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.nbox, (size_t)(B.n_units / 4u + 1u) * 6);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.bounds, 8);
-  if (!rc) rc = dev_alloc(c, c->scene_allocs, &d.cost, 1);
-  if (!rc) { std::vector<uint32_t> cls; ptc_prim_classes(c->mats, B.tri_mat, cls); rc = dev_upload(c, c->scene_allocs, &d.prim_cls, cls); }
-  if (rc) return rc;
-  d.recs = const_cast<float4*>(c->dsc.recs); d.shade = const_cast<float4*>(c->dsc.shade);
+  std::vector<void*> tree;
+  int rc = dev_upload(c, s.allocs, &d.mesh_verts, P.mesh_verts);
+  if (!rc) rc = dev_upload(c, s.allocs, &d.vert_inst, P.vert_inst);
+  if (!rc) rc = dev_upload(c, s.allocs, &d.inst_first, P.inst_first);
+  if (!rc) rc = dev_upload(c, s.allocs, &d.inst_src, P.inst_src);
+  if (!rc) rc = dev_upload(c, s.allocs, &d.widx, B.widx);
+  if (!rc) rc = dev_upload(c, tree, &d.level_nodes, P.level_nodes);
+  if (!rc) rc = dev_alloc(c, s.allocs, &d.inst_xf, c->insts.size() * 21);
+  if (!rc) rc = dev_alloc(c, s.allocs, &d.wverts, (size_t)P.n_verts);
+  if (!rc) rc = dev_alloc(c, s.allocs, &d.wbt, (size_t)P.n_verts * 3);
+  if (!rc) rc = dev_alloc(c, tree, &d.nbox, nbox_cap);
+  if (!rc) rc = dev_alloc(c, s.allocs, &d.bounds, 8);
+  if (!rc) rc = dev_alloc(c, s.allocs, &d.cost, 1);
+  if (!rc) { std::vector<uint32_t> cls; ptc_prim_classes(c->mats, B.tri_mat, cls); rc = dev_upload(c, s.allocs, &d.prim_cls, cls); }
+  if (rc) { free_all(tree); return rc; }
+  s.live.levels = const_cast<uint32_t*>(d.level_nodes); s.live.levels_cap = P.level_nodes.size(); s.live.nbox = d.nbox; s.live.nbox_cap = nbox_cap;
+  d.shade = const_cast<float4*>(s.dsc.shade);
   d.n_verts = P.n_verts; d.n_tris = P.n_tris; d.shade_stride = B.shade_stride;
-  c->drf = d;
-  c->refit_ready = true;
+  s.drf = d;
+  use_live_tree(c);
+  s.refit_ready = true;
   return PTC_OK;
 }
 
@@ -761,7 +802,7 @@ int ensure_refit_plan(ptc_ctx* c) {
 // description that has grown since would index the committed arrays out of bounds — on the device without anybody noticing.  Same test, same
 // error as the host path (build_or_refit), made before anything is uploaded or launched.
 bool description_matches_commit(const ptc_ctx* c) {
-  if (c->insts.size() != c->committed_insts) return false;
+  if (c->insts.size() != c->scene.insts) return false;
   uint64_t nv = 0, nt = 0;
   for (const HostInstance& in : c->insts) {
     if (in.mesh < 0 || (size_t)in.mesh >= c->meshes.size()) return false;
@@ -770,187 +811,149 @@ bool description_matches_commit(const ptc_ctx* c) {
   return nv == c->built->n_wverts && nt == c->built->n_tris;
 }
 const char* const kDescriptionChanged = "scene_refit: the scene's meshes or instances changed since the commit (only transforms may)";
+const char* const kNonFinite = "scene_commit: non-finite vertex position after the instance transform";
+// A group member takes device 0's description: materials are counted from it, a later ptc_scene_commit on this context rebuilds from it
+void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
+  c->mats = c0->mats; c->meshes = c0->meshes; c->insts = c0->insts; c->texs = c0->texs; c->env = c0->env;
+  std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
+  c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
+}
 
 float scene_half_area(const float lo[3], const float hi[3]) {      // the host's box_half_area of the scene box
   const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
   return ex * ey + ey * ez + ez * ex;
 }
 
-// Refit on the device.  Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed) — the caller refits on the host.
-// may_write_built: c->built is this context's own, or a group's fresh copy every member writes the same values to.
-int device_refit(ptc_ctx* c) {
-  { int rc = ensure_refit_plan(c); if (rc) return rc; }
-  std::vector<float> xf, lights, cdf;
-  if (!ptc_refit_instance_transforms(c->insts, xf)) return fail(c, PTC_E_STATE, "scene_commit: non-finite vertex position after the instance transform");
-  if (!ptc_refit_emitters(c->mats, c->meshes, c->insts, c->plan, *c->built, lights, cdf)) return 1;
+// What the geometry pass hands on: the instance transforms, the emitter table of the moved scene, the scene box
+struct Moved { std::vector<float> xf, lights, cdf; float lo[3], hi[3]; };
+
+// The geometry pass of a refit, a rebuild or a commit on the device: world vertices and shading records of the current transforms in HBM, the scene box.
+// Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed), decided before anything is launched.
+int geometry_pass(ptc_ctx* c, Moved& m) {
+  CommittedScene& s = c->scene;
+  if (!ptc_refit_instance_transforms(c->insts, m.xf)) return fail(c, PTC_E_STATE, kNonFinite);
+  if (!ptc_refit_emitters(c->mats, c->meshes, c->insts, s.plan, *c->built, m.lights, m.cdf)) return 1;
   hipStream_t st = c->lanes[0].stream;
-  const DevRefit& d = c->drf;
-  HIP_TRY(c, hipMemcpyAsync(d.inst_xf, xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
+  const DevRefit& d = s.drf;
+  HIP_TRY(c, hipMemcpyAsync(d.inst_xf, m.xf.data(), m.xf.size() * 4, hipMemcpyHostToDevice, st));
   pt_launch_refit_geometry(st, d);
   uint32_t raw[8];
   HIP_TRY(c, hipMemcpyAsync(raw, d.bounds, sizeof raw, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  float lo[3], hi[3]; bool bad = false;
-  pt_refit_decode_bounds(raw, lo, hi, &bad);
+  bool bad = false;
+  pt_refit_decode_bounds(raw, m.lo, m.hi, &bad);
   if (bad) {     // nothing of the scene was written (k_refit_prims saw the flag); the scratch vertices go back to the state the scene in HBM was made from
-    if (!c->xf_live.empty()) {
-      HIP_TRY(c, hipMemcpyAsync(d.inst_xf, c->xf_live.data(), c->xf_live.size() * 4, hipMemcpyHostToDevice, st));
+    if (!s.xf_live.empty()) {
+      HIP_TRY(c, hipMemcpyAsync(d.inst_xf, s.xf_live.data(), s.xf_live.size() * 4, hipMemcpyHostToDevice, st));
       pt_launch_refit_geometry(st, d);
       HIP_TRY(c, hipStreamSynchronize(st));
     }
-    return fail(c, PTC_E_STATE, "scene_commit: non-finite vertex position after the instance transform");
+    return fail(c, PTC_E_STATE, kNonFinite);
   }
-  HostBuilt& B = *c->built;
-  ptc_refit_grid(lo, hi, B.grid_lo, B.grid_step, &B.ray_eps);
-  pt_launch_refit_nodes(st, d, c->plan.level_first, B.grid_lo, B.grid_step, B.sa_unit);      // the cost in the unit of the build: comparable with bvh_sa_cost_built
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long cost_fixed = 0;
-  HIP_TRY(c, hipMemcpyAsync(&cost_fixed, d.cost, sizeof cost_fixed, hipMemcpyDeviceToHost, st));
-  B.lights = lights; B.cdf = cdf;
-  HIP_TRY(c, hipMemcpyAsync((void*)c->dsc.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync((void*)c->dsc.cdf, B.cdf.data(), B.cdf.size() * 4, hipMemcpyHostToDevice, st));
-  c->dsc.ray_eps = B.ray_eps;
-  for (int k = 0; k < 3; ++k) { c->dsc.grid_lo[k] = B.grid_lo[k]; c->dsc.grid_step[k] = B.grid_step[k]; }
-  for (int l = 0; l < c->n_lanes; ++l) {
-    const DevScene ds = lane_scene(c, l);
-    HIP_TRY(c, hipMemcpyAsync(c->lanes[(size_t)l].d_scene, &ds, sizeof ds, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  B.sa_cost_fixed = cost_fixed;
-  c->stats.bvh_sa_cost = (double)cost_fixed / (double)PTC_SA_COST_ONE;
-  c->host_stale = true; c->last_refit_on_device = true;
-  c->xf_live.swap(xf);
   return PTC_OK;
 }
 
-// scene_allocs bookkeeping of ptc_scene_rebuild: an array of the committed scene is replaced
-void scene_free(ptc_ctx* c, const void* p) {
-  if (!p) return;
-  auto it = std::find(c->scene_allocs.begin(), c->scene_allocs.end(), const_cast<void*>(p));
-  if (it != c->scene_allocs.end()) { (void)hipFree(*it); c->scene_allocs.erase(it); }
-}
-
-// ptc_scene_rebuild on the device: a refit's geometry pass, then a NEW tree for the vertices as they now lie in HBM (pt_build.hip), then the refit's node pass over
-// it.  Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed, fewer than two triangles): the caller builds on the host.
-// fresh: the device half of a COMMIT on the device (device_commit): there is no tree yet, the launch configuration follows the tree and is the caller's.
-// builder: the tree the device builds (PTC_BVH_LBVH: pt_build_lbvh, PTC_BVH_SAH: pt_build_sah).
-int device_rebuild(ptc_ctx* c, int builder, bool fresh = false) {
-  { int rc = ensure_refit_plan(c); if (rc) return rc; }
-  if (c->built->n_tris < 2u) return 1;
-  std::vector<float> xf, lights, cdf;
-  if (!ptc_refit_instance_transforms(c->insts, xf)) return fail(c, PTC_E_STATE, "scene_commit: non-finite vertex position after the instance transform");
-  if (!ptc_refit_emitters(c->mats, c->meshes, c->insts, c->plan, *c->built, lights, cdf)) return 1;
-  hipStream_t st = c->lanes[0].stream;
-  DevRefit& d = c->drf;
-  HIP_TRY(c, hipMemcpyAsync(d.inst_xf, xf.data(), xf.size() * 4, hipMemcpyHostToDevice, st));
-  pt_launch_refit_geometry(st, d);
-  uint32_t raw[8];
-  HIP_TRY(c, hipMemcpyAsync(raw, d.bounds, sizeof raw, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  float lo[3], hi[3]; bool bad = false;
-  pt_refit_decode_bounds(raw, lo, hi, &bad);
-  if (bad) {
-    if (!c->xf_live.empty()) {
-      HIP_TRY(c, hipMemcpyAsync(d.inst_xf, c->xf_live.data(), c->xf_live.size() * 4, hipMemcpyHostToDevice, st));
-      pt_launch_refit_geometry(st, d);
-      HIP_TRY(c, hipStreamSynchronize(st));
-    }
-    return fail(c, PTC_E_STATE, "scene_commit: non-finite vertex position after the instance transform");
-  }
-  if (!c->rb_live.recs) {       // first rebuild since the commit: the arrays in use are the commit's, exactly as large as their content
-    c->rb_live.recs = const_cast<float4*>(c->dsc.recs); c->rb_live.recs_cap = c->built->n_units;
-    c->rb_live.levels = const_cast<uint32_t*>(d.level_nodes); c->rb_live.levels_cap = c->built->n_nodes;
-    c->rb_live.nbox = d.nbox; c->rb_live.nbox_cap = (size_t)(c->built->n_units / 4u + 1u) * 6;
-  }
-  BuildOut out;
-  out.recs = c->rb_spare.recs; out.recs_cap = c->rb_spare.recs_cap; out.level_nodes = c->rb_spare.levels; out.level_cap = c->rb_spare.levels_cap;
-  c->rb_spare.recs = nullptr; c->rb_spare.levels = nullptr; c->rb_spare.recs_cap = c->rb_spare.levels_cap = 0;      // the build owns them now (it may free them)
-  const std::string e = builder == PTC_BVH_SAH ? pt_build_sah(st, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out)
-                                                : pt_build_lbvh(st, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out);
-  if (!e.empty()) { if (out.recs) (void)hipFree(out.recs); if (out.level_nodes) (void)hipFree(out.level_nodes); return fail(c, PTC_E_DEVICE, e); }
-  // the new tree replaces the old one: unit array, the refit's level lists, the per-record boxes; the replaced arrays are the next rebuild's spare set
-  const size_t nbox_need = (size_t)(out.n_units / 4u + 1u) * 6;
-  float* nbox = c->rb_spare.nbox; size_t nbox_cap = c->rb_spare.nbox_cap;
-  c->rb_spare.nbox = nullptr; c->rb_spare.nbox_cap = 0;
-  if (!nbox || nbox_cap < nbox_need) {
-    if (nbox) (void)hipFree(nbox);
-    nbox_cap = nbox_need + nbox_need / 8u;
-    if (hipMalloc((void**)&nbox, nbox_cap * sizeof(float)) != hipSuccess) { (void)hipFree(out.recs); (void)hipFree(out.level_nodes); return fail(c, PTC_E_NOMEM, "scene_rebuild: out of device memory"); }
-  }
-  for (void* old : {(void*)c->rb_live.recs, (void*)c->rb_live.levels, (void*)c->rb_live.nbox}) {       // out of the scene's list, not freed
-    auto it = std::find(c->scene_allocs.begin(), c->scene_allocs.end(), old);
-    if (it != c->scene_allocs.end()) c->scene_allocs.erase(it);
-  }
-  c->rb_spare = c->rb_live;
-  c->rb_live.recs = out.recs; c->rb_live.recs_cap = out.recs_cap; c->rb_live.levels = out.level_nodes; c->rb_live.levels_cap = out.level_cap; c->rb_live.nbox = nbox; c->rb_live.nbox_cap = nbox_cap;
-  c->scene_allocs.push_back(out.recs); c->scene_allocs.push_back(out.level_nodes); c->scene_allocs.push_back(nbox);
-  d.recs = out.recs; d.level_nodes = out.level_nodes; d.nbox = nbox;
-  c->plan.level_first = out.level_first; c->plan.level_nodes.clear();
+// The node pass over the live tree: the origin grid of the scene box, the nodes from the leaves up and their cost (in the unit of the build: comparable with
+// bvh_sa_cost_built), the emitter table; with `publish` the lanes' copies of the scene follow (a commit publishes them after its launch configuration).
+// The host's build then holds the grid, the emitters and the cost; its other vertex-dependent arrays are stale.
+int node_pass(ptc_ctx* c, Moved& m, bool publish) {
+  CommittedScene& s = c->scene;
   HostBuilt& B = *c->built;
-  ptc_refit_grid(lo, hi, B.grid_lo, B.grid_step, &B.ray_eps);
-  B.sa_unit = scene_half_area(lo, hi);                      // a new topology: a new unit of its cost
-  pt_launch_refit_nodes(st, d, c->plan.level_first, B.grid_lo, B.grid_step, B.sa_unit);
+  hipStream_t st = c->lanes[0].stream;
+  ptc_refit_grid(m.lo, m.hi, B.grid_lo, B.grid_step, &B.ray_eps);
+  pt_launch_refit_nodes(st, s.drf, s.plan.level_first, B.grid_lo, B.grid_step, B.sa_unit);
   HIP_TRY(c, hipGetLastError());
   unsigned long long cost_fixed = 0;
-  HIP_TRY(c, hipMemcpyAsync(&cost_fixed, d.cost, sizeof cost_fixed, hipMemcpyDeviceToHost, st));
-  B.lights = lights; B.cdf = cdf;
-  HIP_TRY(c, hipMemcpyAsync((void*)c->dsc.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync((void*)c->dsc.cdf, B.cdf.data(), B.cdf.size() * 4, hipMemcpyHostToDevice, st));
-  // the host's picture of the build: sizes follow the new tree, the arrays come back from HBM when somebody asks (refresh_host_copy), and the topology the host
-  // refit needs is gone — the next host-path refit builds from scratch
+  HIP_TRY(c, hipMemcpyAsync(&cost_fixed, s.drf.cost, sizeof cost_fixed, hipMemcpyDeviceToHost, st));
+  B.lights = m.lights; B.cdf = m.cdf;
+  HIP_TRY(c, hipMemcpyAsync((void*)s.dsc.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync((void*)s.dsc.cdf, B.cdf.data(), B.cdf.size() * 4, hipMemcpyHostToDevice, st));
+  s.dsc.ray_eps = B.ray_eps;
+  for (int k = 0; k < 3; ++k) { s.dsc.grid_lo[k] = B.grid_lo[k]; s.dsc.grid_step[k] = B.grid_step[k]; }
+  if (publish) { int rc = publish_lane_scenes(c, st); if (rc) return rc; }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  B.sa_cost_fixed = cost_fixed;
+  s.host_stale = true; s.last_refit_on_device = true;
+  s.xf_live.swap(m.xf);
+  return PTC_OK;
+}
+
+// Refit on the device (t0: the start of the call).  Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed) — the caller refits on the host.
+int device_refit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
+  { int rc = ensure_refit_plan(c); if (rc) return rc; }
+  Moved m;
+  int rc = geometry_pass(c, m);
+  if (!rc) rc = node_pass(c, m, /*publish=*/true);
+  if (rc) return rc;
+  c->stats.bvh_sa_cost = (double)c->built->sa_cost_fixed / (double)PTC_SA_COST_ONE;
+  c->in_frame = false; c->pending = 0;
+  c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return PTC_OK;
+}
+
+// A NEW tree for the vertices as they lie in HBM (pt_build.hip; builder: PTC_BVH_LBVH pt_build_lbvh, PTC_BVH_SAH pt_build_sah), written into the spare tree set, which
+// becomes the live one: the replaced arrays are the next rebuild's spare set.  The host's picture of the build follows: sizes of the new tree, the arrays come back
+// from HBM when somebody asks (refresh_host_copy), and the topology the host refit needs is gone — the next host-path refit builds from scratch.
+int device_build(ptc_ctx* c, int builder, const Moved& m) {
+  CommittedScene& s = c->scene;
+  const DevRefit& d = s.drf;
+  TreeBufs& t = s.spare;
+  BuildOut out;      // the build owns the spare unit array and level list now (it may free them); what it hands back is the spare set's again, whatever happened
+  out.recs = t.recs; out.recs_cap = t.recs_cap; out.level_nodes = t.levels; out.level_cap = t.levels_cap;
+  const std::string e = builder == PTC_BVH_SAH ? pt_build_sah(c->lanes[0].stream, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out)
+                                                : pt_build_lbvh(c->lanes[0].stream, d.wverts, d.widx, d.prim_cls, d.n_tris, c->toplet_budget, c->bscratch, out);
+  t.recs = out.recs; t.recs_cap = out.recs_cap; t.levels = out.level_nodes; t.levels_cap = out.level_cap;
+  if (!e.empty()) return fail(c, PTC_E_DEVICE, e);
+  const size_t nbox_need = (size_t)(out.n_units / 4u + 1u) * 6;
+  if (t.nbox_cap < nbox_need) {
+    if (t.nbox) (void)hipFree(t.nbox);
+    t.nbox = nullptr; t.nbox_cap = nbox_need + nbox_need / 8u;
+    if (hipMalloc((void**)&t.nbox, t.nbox_cap * sizeof(float)) != hipSuccess) { t.nbox = nullptr; t.nbox_cap = 0; return fail(c, PTC_E_NOMEM, "scene_rebuild: out of device memory"); }
+  }
+  std::swap(s.live, s.spare);
+  use_live_tree(c);
+  s.plan.level_first = out.level_first; s.plan.level_nodes.clear();
+  HostBuilt& B = *c->built;
+  B.sa_unit = scene_half_area(m.lo, m.hi);                  // a new topology: a new unit of its cost
   B.n_nodes = out.n_nodes; B.n_units = out.n_units; B.max_depth = out.max_depth; B.n_tri_records = out.n_tri_records;
   B.n_lds_units = B.n_units < c->toplet_budget * 4u ? B.n_units : c->toplet_budget * 4u;
   B.recs.clear();                       // refresh_host_copy sizes and fills them when somebody asks
   B.topology.reset();
-  c->dsc.recs = out.recs; c->dsc.n_lds_units = B.n_lds_units; c->dsc.ray_eps = B.ray_eps;
-  for (int k = 0; k < 3; ++k) { c->dsc.grid_lo[k] = B.grid_lo[k]; c->dsc.grid_step[k] = B.grid_step[k]; }
-  if (!fresh) {   // a deeper tree needs a deeper overflow slab behind the stack entries kept in LDS
-    const int need = (int)B.max_depth + 2;
-    const uint32_t ovf = (uint32_t)(need - c->cfg.stack_lds > 0 ? need - c->cfg.stack_lds : 1);
-    if (ovf > c->dsc.ovf_depth) {
-      const size_t total_waves = (size_t)c->cfg.n_cu * (size_t)c->cfg.trace_blocks_per_cu * (size_t)(pt_trace_block_threads() / 64);
-      for (auto& ln : c->lanes) {
-        uint2* pl = nullptr;
-        scene_free(c, ln.stack_ovf); ln.stack_ovf = nullptr;
-        int rc = dev_alloc(c, c->scene_allocs, &pl, total_waves * ovf * 64);
-        if (rc) return rc;
-        ln.stack_ovf = pl;
-        if (ln.stack_ovf2) {
-          scene_free(c, ln.stack_ovf2); ln.stack_ovf2 = nullptr;
-          if ((rc = dev_alloc(c, c->scene_allocs, &pl, total_waves * ovf * 64))) return rc;
-          ln.stack_ovf2 = pl;
-        }
-      }
-      c->dsc.ovf_depth = ovf;
-    }
-  }
-  if (!fresh)
-    for (int l = 0; l < c->n_lanes; ++l) {
-      const DevScene ds = lane_scene(c, l);
-      HIP_TRY(c, hipMemcpyAsync(c->lanes[(size_t)l].d_scene, &ds, sizeof ds, hipMemcpyHostToDevice, st));
-    }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  B.sa_cost_fixed = cost_fixed;
-  c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)cost_fixed / (double)PTC_SA_COST_ONE;
+  s.dsc.n_lds_units = B.n_lds_units;
+  return PTC_OK;
+}
+
+// ptc_scene_rebuild on the device: the geometry pass, a new tree, the node pass over it.  Returns PTC_OK, an error, or +1: "not this way" (the set of emitters changed,
+// fewer than two triangles): the caller builds on the host.
+int device_rebuild(ptc_ctx* c, int builder) {
+  { int rc = ensure_refit_plan(c); if (rc) return rc; }
+  if (c->built->n_tris < 2u) return 1;
+  Moved m;
+  int rc = geometry_pass(c, m);
+  if (!rc) rc = device_build(c, builder, m);
+  if (!rc) rc = ensure_overflow_slabs(c);      // a deeper tree needs deeper slabs
+  if (!rc) rc = node_pass(c, m, /*publish=*/true);
+  if (rc) return rc;
+  const HostBuilt& B = *c->built;
+  c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)B.sa_cost_fixed / (double)PTC_SA_COST_ONE;
   c->stats.n_bvh_nodes = B.n_nodes; c->stats.bvh_max_depth = B.max_depth;
-  c->host_stale = true; c->last_refit_on_device = true; c->tree_device_sah = builder == PTC_BVH_SAH;
-  c->xf_live.swap(xf);
+  c->scene.tree_device_sah = builder == PTC_BVH_SAH;
   return PTC_OK;
 }
 
 // The debug getters read the host build: after a refit on the device its vertex-dependent arrays come back from HBM first.
 int refresh_host_copy(ptc_ctx* c) {
-  if (!c->host_stale || c->device < 0) return PTC_OK;
+  if (!c->scene.host_stale || c->device < 0) return PTC_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   HostBuilt& B = *c->built;
   B.recs.resize((size_t)B.n_units * 4);                                     // a tree or a commit made on the device left the host arrays unsized
   B.shade.resize((size_t)B.n_tris * B.shade_stride * 4);
   B.wverts.resize(B.n_wverts);
-  HIP_TRY(c, hipMemcpy(B.recs.data(), c->dsc.recs, B.recs.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(B.shade.data(), c->dsc.shade, B.shade.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(B.wverts.data(), c->drf.wverts, B.wverts.size() * sizeof(HostVertex), hipMemcpyDeviceToHost));
-  c->host_stale = false;
+  HIP_TRY(c, hipMemcpy(B.recs.data(), c->scene.dsc.recs, B.recs.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.shade.data(), c->scene.dsc.shade, B.shade.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.wverts.data(), c->scene.drf.wverts, B.wverts.size() * sizeof(HostVertex), hipMemcpyDeviceToHost));
+  c->scene.host_stale = false;
   return PTC_OK;
 }
 // A full host build of the description as it stands + upload (what ptc_scene_commit does), keeping what a refit / rebuild keeps of the statistics.
@@ -958,14 +961,14 @@ int refresh_host_copy(ptc_ctx* c) {
 // is a device SAH build.
 int host_build_and_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool as_refit) {
   auto built = std::make_shared<HostBuilt>();
-  const int builder = as_refit ? (c->tree_device_sah ? PTC_BVH_SAH : c->bvh_builder) : c->device_builder;
+  const int builder = as_refit ? (c->scene.tree_device_sah ? PTC_BVH_SAH : c->bvh_builder) : c->device_builder;
   const std::string e = ptc_build_scene(c->mats, c->meshes, c->insts, c->texs, c->env, c->toplet_budget, builder, *built);
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
   const ptc_stats keep = c->stats;
   c->built = built;
   const int rc = commit_upload(c, t0);
   if (rc) return rc;
-  c->last_refit_on_device = false;
+  c->scene.last_refit_on_device = false;
   const double dt = c->stats.seconds_commit;
   c->stats.seconds_commit = keep.seconds_commit; c->stats.seconds_refit = keep.seconds_refit; c->stats.seconds_rebuild = keep.seconds_rebuild;
   (as_refit ? c->stats.seconds_refit : c->stats.seconds_rebuild) = dt;
@@ -1001,11 +1004,8 @@ int ptc_scene_refit(ptc_ctx* c) {
   const auto t0 = std::chrono::steady_clock::now();
   if (c->built.use_count() > 1) c->built = std::make_shared<HostBuilt>(*c->built);      // a group shares one build: this context now gets its own
   if (c->device >= 0 && refit_on_device(c)) {
-    const int rd = device_refit(c);
-    if (rd <= 0) {
-      if (rd == PTC_OK) { c->in_frame = false; c->pending = 0; c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-      return rd;
-    }
+    const int rd = device_refit(c, t0);
+    if (rd <= 0) return rd;
   }
   if (!c->built->topology) return host_build_and_upload(c, t0, /*as_refit=*/true);      // the tree in HBM was built on the device (ptc_scene_rebuild): the host has no topology to refit
   HostBuilt& B = *c->built;
@@ -1079,82 +1079,83 @@ int ptc_set_env_latlong_rgb32f(ptc_ctx* c, const float* rgb, int w, int h) {
 }
 
 namespace {
-int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0);
+// the statistics of a commit: the figures of the build, everything else zero
+void commit_stats(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
+  const HostBuilt& B = *c->built;
+  std::memset(&c->stats, 0, sizeof c->stats);
+  c->stats.seconds_commit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->stats.n_triangles = B.n_tris; c->stats.n_bvh_nodes = B.n_nodes; c->stats.n_emitters = B.n_lights; c->stats.bvh_max_depth = B.max_depth;
+  c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)B.sa_cost_fixed / (double)PTC_SA_COST_ONE;
+}
+// the launches follow the tree (its depth, the staged top): configuration, the lanes' copies of the scene, the statistics of a commit
+int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
+  const bool timing = std::getenv("PTC_BUILD_TIMING") != nullptr;
+  const auto tc0 = std::chrono::steady_clock::now();
+  { int rc = configure_launch(c); if (rc) { release_scene(c); return rc; } }
+  if (timing) std::fprintf(stderr, "    configure_launch            %7.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
+  c->cfg.shade_tables_lds = pt_shade_tables_fit(c->scene.dsc) ? 1 : 0;
+  { int rc = publish_lane_scenes(c, c->lanes[0].stream); if (rc) return rc; }
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  c->committed = true;
+  commit_stats(c, t0);
+  return PTC_OK;
+}
 // Device half of a commit: upload c->built, size the launches.  The caller has set c->built, the camera and seconds_commit's start.
 // skeleton: c->built is ptc_build_skeleton's — the tables are uploaded, the shading records allocated and zeroed, there is no tree yet: device_commit goes on from here.
 int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool skeleton) {
   ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
   c->in_frame = false; c->pending = 0;
-  c->committed_insts = c->insts.size();
+  c->committed = false;
+  release_scene(c);
+  CommittedScene& s = c->scene;
+  s.insts = c->insts.size();
   if (c->device < 0) {   // description-only context: nothing to upload
     c->committed = true;
-    std::memset(&c->stats, 0, sizeof c->stats);
-    c->stats.seconds_commit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    c->stats.n_triangles = c->built->n_tris; c->stats.n_bvh_nodes = c->built->n_nodes; c->stats.n_emitters = c->built->n_lights;
-    c->stats.bvh_max_depth = c->built->max_depth;
-    c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)c->built->sa_cost_fixed / (double)PTC_SA_COST_ONE;
+    commit_stats(c, t0);
     return PTC_OK;
   }
-  c->committed = false; c->commit_on_device = false; c->tree_device_sah = false;
-  free_all(c->scene_allocs);
-  free_rebuild_spare(c);
-  c->refit_ready = false; c->host_stale = false; c->plan = RefitPlan(); c->drf = DevRefit{}; c->xf_live.clear();
-  for (auto& ln : c->lanes) ln.stack_ovf = nullptr;
+  s.commit_on_device = false; s.tree_device_sah = false;
   const HostBuilt& B = *c->built;
   DevScene d{};
   int rc = 0;
   {
     const float* p = nullptr;
-    auto up = [&](const std::vector<float>& v, const float4** out) { if (!rc) { rc = dev_upload(c, c->scene_allocs, &p, v); *out = (const float4*)p; } };
-    if (!skeleton) up(B.recs, &d.recs);
+    if (!skeleton) {      // the unit array is the live tree set's
+      std::vector<void*> tree;
+      if ((rc = dev_upload(c, tree, &p, B.recs))) free_all(tree);
+      s.live.recs = (float4*)p; s.live.recs_cap = B.n_units;
+    }
+    auto up = [&](const std::vector<float>& v, const float4** out) { if (!rc) { rc = dev_upload(c, s.allocs, &p, v); *out = (const float4*)p; } };
     up(B.mats, &d.mats); up(B.lights, &d.lights);
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.cdf, B.cdf);
+    if (!rc) rc = dev_upload(c, s.allocs, &d.cdf, B.cdf);
     if (!skeleton) up(B.shade, &d.shade);
     else if (!rc) {
       float4* sh = nullptr;
       const size_t units = (size_t)B.n_tris * B.shade_stride;
-      rc = dev_alloc(c, c->scene_allocs, &sh, units);
+      rc = dev_alloc(c, s.allocs, &sh, units);
       if (!rc && hipMemsetAsync(sh, 0, units * sizeof(float4), c->lanes[0].stream) != hipSuccess) rc = fail(c, PTC_E_DEVICE, "scene_commit: hipMemset failed");
       d.shade = sh;
     }
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.texels, B.texels);
-    if (!rc) { const int32_t* ti = nullptr; rc = dev_upload(c, c->scene_allocs, &ti, B.tex_info); d.tex_info = (const int4*)ti; }
-    if (!rc) { const uint32_t* st = nullptr; rc = dev_upload(c, c->scene_allocs, &st, B.set_texels); d.set_texels = (const uint4*)st; }
-    if (!rc) { const int32_t* si = nullptr; rc = dev_upload(c, c->scene_allocs, &si, B.set_info); d.set_info = (const int4*)si; }
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.env_marg_guide, B.env_marg_guide);
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.env_cond_guide, B.env_cond_guide);
+    if (!rc) rc = dev_upload(c, s.allocs, &d.texels, B.texels);
+    if (!rc) { const int32_t* ti = nullptr; rc = dev_upload(c, s.allocs, &ti, B.tex_info); d.tex_info = (const int4*)ti; }
+    if (!rc) { const uint32_t* st = nullptr; rc = dev_upload(c, s.allocs, &st, B.set_texels); d.set_texels = (const uint4*)st; }
+    if (!rc) { const int32_t* si = nullptr; rc = dev_upload(c, s.allocs, &si, B.set_info); d.set_info = (const int4*)si; }
+    if (!rc) rc = dev_upload(c, s.allocs, &d.env_marg_guide, B.env_marg_guide);
+    if (!rc) rc = dev_upload(c, s.allocs, &d.env_cond_guide, B.env_cond_guide);
     up(B.env, &d.env);
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.env_marg, B.env_marg);
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d.env_cond, B.env_cond);
+    if (!rc) rc = dev_upload(c, s.allocs, &d.env_marg, B.env_marg);
+    if (!rc) rc = dev_upload(c, s.allocs, &d.env_cond, B.env_cond);
   }
-  if (rc) { free_all(c->scene_allocs); return rc; }
+  if (rc) { release_scene(c); return rc; }
   d.env_w = B.env_w; d.env_h = B.env_h; d.env_ok = B.env_ok;
   d.tex_linear = c->tex_linear;
   d.shade_stride = B.shade_stride;
   d.n_lights = B.n_lights; d.n_mats = (uint32_t)c->mats.size(); d.n_lds_units = B.n_lds_units; d.ray_eps = B.ray_eps;
   for (int k = 0; k < 3; ++k) { d.grid_lo[k] = B.grid_lo[k]; d.grid_step[k] = B.grid_step[k]; }
-  c->dsc = d;
+  s.dsc = d;
+  use_live_tree(c);
   if (skeleton) return PTC_OK;
   return commit_finish(c, t0);
-}
-// the launches follow the tree (its depth, the staged top): configuration, the lanes' copies of the scene, the statistics of a commit
-int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
-  const HostBuilt& B = *c->built;
-  const bool timing = std::getenv("PTC_BUILD_TIMING") != nullptr;
-  const auto tc0 = std::chrono::steady_clock::now();
-  { int rc2 = configure_launch(c); if (rc2) { free_all(c->scene_allocs); return rc2; } }
-  if (timing) std::fprintf(stderr, "    configure_launch            %7.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
-  c->cfg.shade_tables_lds = pt_shade_tables_fit(c->dsc) ? 1 : 0;
-  for (int l = 0; l < c->n_lanes; ++l) {
-    const DevScene ds = lane_scene(c, l);
-    HIP_TRY(c, hipMemcpy(c->lanes[(size_t)l].d_scene, &ds, sizeof ds, hipMemcpyHostToDevice));
-  }
-  c->committed = true;
-  std::memset(&c->stats, 0, sizeof c->stats);
-  c->stats.seconds_commit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  c->stats.n_triangles = B.n_tris; c->stats.n_bvh_nodes = B.n_nodes; c->stats.n_emitters = B.n_lights; c->stats.bvh_max_depth = B.max_depth;
-  c->stats.bvh_sa_cost = c->stats.bvh_sa_cost_built = (double)B.sa_cost_fixed / (double)PTC_SA_COST_ONE;
-  return PTC_OK;
 }
 
 // ptc_scene_commit with the LBVH builder (or the SAH builder with the SAH device builder) on a device context: the host describes (ptc_build_skeleton: indices, materials, emitters, textures), the DEVICE flattens the
@@ -1177,26 +1178,27 @@ int device_commit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
   lap("describe (skeleton)");
   { int rc = commit_upload(c, t0, /*skeleton=*/true); if (rc) return rc; }
   lap("free + tables upload");
-  { int rc = ensure_refit_plan(c); if (rc) { free_all(c->scene_allocs); return rc; } }
+  CommittedScene& s = c->scene;
+  int rc = ensure_refit_plan(c);
+  if (rc) { release_scene(c); return rc; }
   lap("plan + its upload");
-  {
-    const int32_t *d_mat = nullptr, *d_light = nullptr;
-    int rc = dev_upload(c, c->scene_allocs, &d_mat, built->tri_mat);
-    if (!rc) rc = dev_upload(c, c->scene_allocs, &d_light, built->prim_light);
-    if (rc) { free_all(c->scene_allocs); return rc; }
-    pt_launch_refit_seed(c->lanes[0].stream, c->drf, d_mat, d_light);
-  }
-  const int rd = device_rebuild(c, c->bvh_builder, /*fresh=*/true);
-  if (rd) { free_all(c->scene_allocs); c->refit_ready = false; return rd; }
+  const int32_t *d_mat = nullptr, *d_light = nullptr;
+  rc = dev_upload(c, s.allocs, &d_mat, built->tri_mat);
+  if (!rc) rc = dev_upload(c, s.allocs, &d_light, built->prim_light);
+  if (!rc) pt_launch_refit_seed(c->lanes[0].stream, s.drf, d_mat, d_light);
+  Moved m;
+  if (!rc) rc = geometry_pass(c, m);
+  if (!rc) rc = device_build(c, c->bvh_builder, m);
+  if (!rc) rc = node_pass(c, m, /*publish=*/false);
+  if (rc) { release_scene(c); return rc; }
+  s.tree_device_sah = c->bvh_builder == PTC_BVH_SAH;
   lap("flatten + build on the device");
-  const int rf = commit_finish(c, t0);
+  rc = commit_finish(c, t0);
   lap("launch configuration");
-  c->commit_on_device = rf == PTC_OK;
-  return rf;
+  s.commit_on_device = rc == PTC_OK;
+  return rc;
 }
-}  // namespace
 
-namespace {
 // device_ok: the commit may build on the device (not for device 0 of a group with the SAH device builder: the others share its host build)
 int scene_commit(ptc_ctx* c, bool device_ok) {
   if (!c) return PTC_E_ARG;
@@ -1534,7 +1536,7 @@ int ptc_group_scene_commit(ptc_group* g) {
   // flatten + BVH build, once, on the host (a scene device 0 has committed already is taken as it is; with the SAH device builder, a commit device 0 made on the
   // device is made again on the host: the other devices share device 0's host arrays)
   const bool sah_dev = c0->device_builder == PTC_BVH_SAH;
-  int rc = c0->committed && !(sah_dev && c0->commit_on_device) ? PTC_OK : scene_commit(c0, /*device_ok=*/!sah_dev);
+  int rc = c0->committed && !(sah_dev && c0->scene.commit_on_device) ? PTC_OK : scene_commit(c0, /*device_ok=*/!sah_dev);
   if (rc) { g->err = std::string("device 0: ") + ptc_last_error(c0); return rc; }
   for (size_t i = 1; i < g->ctx.size(); ++i) {
     ptc_ctx* c = g->ctx[i];
@@ -1543,10 +1545,7 @@ int ptc_group_scene_commit(ptc_group* g) {
       if ((rc = sync_all_lanes(c))) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
     }
     const auto t0 = std::chrono::steady_clock::now();
-    // the description travels too (materials are counted from it, a later ptc_scene_commit on this context rebuilds from it)
-    c->mats = c0->mats; c->meshes = c0->meshes; c->insts = c0->insts; c->texs = c0->texs; c->env = c0->env;
-    std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
-    c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
+    copy_description(c, c0);
     c->built = c0->built;                             // shared, read-only from here on
     if ((rc = commit_upload(c, t0))) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
   }
@@ -1576,15 +1575,13 @@ int ptc_group_scene_refit(ptc_group* g) {
       if (hipSetDevice(c->device) != hipSuccess) { g->err = "ptc_group_scene_refit: hipSetDevice failed"; return PTC_E_DEVICE; }
       if (i) c->insts = c0->insts;
       c->built = mine;
-      const int rc = device_refit(c);
+      const int rc = device_refit(c, t0);
       if (rc > 0) { host_way = true; break; }      // decided from the description alone, before any kernel ran: all devices take the host path together
       if (rc) {
         g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c);
         if (i == 0) return rc;                     // nothing has been refitted yet (a refused refit leaves the device's scene as it was)
         host_way = true; break;                    // devices 0..i-1 hold the new state: the host path below brings ALL of them to one state, or fails as a whole
       }
-      c->in_frame = false; c->pending = 0;
-      c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     if (!host_way) return PTC_OK;
   }
@@ -1763,7 +1760,7 @@ int ptc_debug_get_internals(ptc_ctx* c, uint64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = c->events_created; out[1] = c->spans.size(); out[2] = c->lanes.empty() ? 0 : c->lanes[0].q.cap; out[3] = c->per_batch; out[4] = c->pending;
   out[5] = (uint64_t)c->cfg.trace_blocks_per_cu; out[6] = (uint64_t)c->cfg.stack_lds;
-  out[7] = (c->last_refit_on_device ? 1u : 0u) | (c->commit_on_device ? 2u : 0u) | (c->tree_device_sah ? 4u : 0u);
+  out[7] = (c->scene.last_refit_on_device ? 1u : 0u) | (c->scene.commit_on_device ? 2u : 0u) | (c->scene.tree_device_sah ? 4u : 0u);
   return PTC_OK;
 }
 
