@@ -57,15 +57,20 @@ public:
   Frame(ptc_ctx* ctx, int w, int h, int sppBudget, std::uint64_t seed) : _ctx(ctx), _w(w), _h(h), _budget(sppBudget), _seed(seed), _staging16((std::size_t)w * h * 4) {}
   // one displayed frame; returns false when the context has no device (description-only run)
   bool record(pbr::ViewerCamera const& cam, bool sceneOrCameraChanged) {
-    const auto target = cam.target();
-    ck(_ctx, ptc_set_camera(_ctx, cam.position.data(), target.data(), cam.fov, (float)_w / (float)_h));
-    int rc = PTC_OK;
-    if (sceneOrCameraChanged || !_begun) rc = ptc_frame_begin(_ctx, _w, _h, _budget, _seed, 8, PTC_INTEGRATOR_PATH, 0, 1);
-    if (rc == PTC_E_DEVICE) return false;
-    ck(_ctx, rc);
+    const bool fresh = sceneOrCameraChanged || !_begun;
+    if (fresh) {                                              // a new camera ends the validity of the guides: set it with the frame it begins
+      const auto target = cam.target();
+      ck(_ctx, ptc_set_camera(_ctx, cam.position.data(), target.data(), cam.fov, (float)_w / (float)_h));
+      const int rc = ptc_frame_begin(_ctx, _w, _h, _budget, _seed, 8, PTC_INTEGRATOR_PATH, 0, 1);
+      if (rc == PTC_E_DEVICE) return false;
+      ck(_ctx, rc);
+      ck(_ctx, ptc_frame_guides(_ctx));                       // albedo / normal / depth at the first hit: once per frame_begin, they do not depend on the samples
+    }
     _begun = true;
     ck(_ctx, ptc_frame_add_samples(_ctx, 1));                 // progressive: one sample per displayed frame
     ck(_ctx, ptc_frame_resolve(_ctx));                        // sum / samples so far
+    ck(_ctx, ptc_denoise(_ctx, nullptr));                     // the few-sample image is mostly noise: filter it along the guides (default parameters) ...
+    ck(_ctx, ptc_select_output(_ctx, PTC_OUTPUT_DENOISED));   // ... and hand the denoised image on (ptc_frame_begin selects the plain radiance again)
     ck(_ctx, ptc_read_radiance_rgba16f(_ctx, _staging16.data()));   // the HdrImage's own format (RGBA16F); the TransferStager copies it into _hdrImage
     return true;
   }

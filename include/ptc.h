@@ -294,6 +294,45 @@ int ptc_frame_set_sample_range(ptc_ctx*, uint32_t first_sample, uint32_t resolve
 
 int ptc_get_stats(ptc_ctx*, ptc_stats* out);
 
+/* ---- first-hit guide buffers, the denoiser, output selection ---------------------------------------------------------------------
+ * A path-traced frame of a few samples is mostly noise; these calls turn it into a displayable image.  Nothing here changes what a context that never
+ * calls them computes.
+ *
+ * ptc_frame_guides: needs a frame begun with PTC_INTEGRATOR_PATH (PTC_E_STATE otherwise: the raster integrators are noise-free).  For EVERY pixel of the
+ *   frame, whatever the frame's tile share (the root of a tile-sharded frame holds the whole image after the reduce), it traces the path integrator's camera ray
+ *   with the jitter fixed at (0.5, 0.5) — no near/far clip, no culling, closest hit = minimum of (t, primitive id) — and writes per pixel
+ *     class K    0 miss, 1 surface, 2 emitter (the hit material's emissive factor has a non-zero component)
+ *     albedo A   K = 1: the base colour rgb after the colour texture (the scene's filter mode included); (1, 1, 1) otherwise
+ *     normal N   K = 1: the normalised interpolated vertex normal (no normal map); 0 otherwise.  depth Z: the hit's t along the unit ray, 0 on a miss
+ *     the primitive id (-1 = miss) and the barycentrics of the hit
+ *   PTC_GUIDE_ALBEDO reads (A, (float)K), PTC_GUIDE_NORMAL_DEPTH (N, Z).  Queued on the context's stream; the frame in progress is not disturbed: sums, sample
+ *   counts, held-back samples, the frame's ptc_stats counters and the RNG are untouched.  The guides stay valid until the next ptc_frame_begin, ptc_set_camera,
+ *   ptc_scene_commit, ptc_scene_refit or ptc_scene_rebuild.
+ * ptc_denoise: the variance-guided edge-avoiding a-trous filter of DESIGN.md ("Denoiser") over the radiance buffer as it lies (after ptc_frame_resolve,
+ *   ptc_comm_reduce_radiance or ptc_write_radiance_rgba32f) and the guides, into a separate RGBA32F buffer (alpha copied); the radiance buffer is not modified.
+ *   Only class-1 pixels are filtered; misses and emitters are copied bit for bit.  params == NULL: the defaults.  PTC_E_STATE without valid guides; PTC_E_ARG for
+ *   iterations outside 0..8 or a negative / non-finite sigma; iterations = 0 copies the radiance bit for bit.
+ * ptc_select_output: which image ptc_read_radiance_rgba32f, ptc_read_radiance_rgba16f, ptc_radiance_rgba16f_device_ptr and ptc_tonemap_rgba8 serve.
+ *   PTC_OUTPUT_RADIANCE by default and again after every ptc_frame_begin; PTC_OUTPUT_DENOISED before any ptc_denoise of the frame: PTC_E_STATE.
+ *   ptc_radiance_device_ptr, ptc_write_radiance_rgba32f and ptc_comm_reduce_radiance always mean the radiance buffer.
+ * ptc_get_denoise_seconds: HIP-event times of the last ptc_frame_guides and the last ptc_denoise (0 when there was none); either pointer may be NULL. */
+enum { PTC_GUIDE_ALBEDO = 0, PTC_GUIDE_NORMAL_DEPTH = 1 };
+enum { PTC_OUTPUT_RADIANCE = 0, PTC_OUTPUT_DENOISED = 1 };
+typedef struct ptc_denoise_params {
+  int iterations;     /* a-trous iterations, step 2^i: 0..8 (default 4)                                            */
+  float sigma_l;      /* luminance: differences are measured in standard deviations of the local estimate (4)      */
+  float sigma_n;      /* normal: exponent of max(0, Np.Nq) (128)                                                   */
+  float sigma_p;      /* plane distance, in pixel footprints at the centre's depth (1)                             */
+  int demodulate;     /* filter radiance / albedo and multiply the albedo back: keeps texture detail (1)           */
+} ptc_denoise_params;
+int ptc_frame_guides(ptc_ctx*);
+int ptc_read_guide_rgba32f(ptc_ctx*, int which, float* out);       /* w*h*4 floats, full frame */
+int ptc_read_guide_hit(ptc_ctx*, int32_t* prim, float* uv);        /* w*h primitive ids, w*h*2 barycentrics; either may be NULL */
+void ptc_denoise_default_params(ptc_denoise_params*);
+int ptc_denoise(ptc_ctx*, const ptc_denoise_params*);
+int ptc_select_output(ptc_ctx*, int output);
+int ptc_get_denoise_seconds(ptc_ctx*, double* guides, double* denoise);
+
 /* ---- multi-GPU: tiles shard over devices, one RCCL reduce brings the framebuffer to the root -----------
  * The reference has no multi-device path (one vk::Device, core/GpuHandle.cpp:94-101); this is BASELINE.json's
  * "independent pixel/sample tiles shard across the 8 GPUs of one node with an RCCL reduce onto rank 0".

@@ -1,0 +1,18 @@
+// pt_denoise.h — launchers of the variance-guided à-trous denoiser (pt_denoise.hip).  The filter is specified in DESIGN.md §"Denoiser"; its inputs are the
+// radiance buffer and the first-hit guide buffers k_guides writes (ptc_internal.h: GuideBufs).
+#pragma once
+#include "ptc_internal.h"
+
+struct DenoiseArgs {
+  int w, h;
+  float sigma_l, sigma_n, sigma_p;
+  int demodulate;
+  float pix;                    // 2 tan(fov_y / 2) / h: the world size of a pixel at unit distance
+  const float4* radiance;       // (C.rgb, alpha)
+  GuideBufs g;
+};
+#define PTC_DENOISE_MAX_ITERATIONS 8
+// radiance, guides -> (D.rgb, Var): the demodulated colour and the variance of its luminance over the 7x7 window
+void pt_launch_denoise_prepare(hipStream_t, const DenoiseArgs&, float4* cv_out);
+// iteration i (step 2^i): (D, Var) -> (D', Var'); the last one re-modulates and writes (colour, alpha of the radiance) instead
+void pt_launch_denoise_iteration(hipStream_t, const DenoiseArgs&, int iteration, const float4* cv_in, float4* out, bool last);

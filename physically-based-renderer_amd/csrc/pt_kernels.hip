@@ -1705,3 +1705,76 @@ void pt_launch_resolve(hipStream_t s, const DevFrame& fr, const float4* accum, f
 void pt_launch_tonemap(hipStream_t s, const float4* radiance, uint32_t* rgba8, int w, int h) {
   hipLaunchKernelGGL(k_tonemap, dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)), dim3(256), 0, s, radiance, rgba8, w, h);
 }
+
+// =================================================================================================
+// First-hit guide buffers of the denoiser (pt_denoise.hip): for EVERY pixel of the frame — an identity pixel list, whatever the frame's tile
+// share — the path integrator's camera ray with the jitter fixed at (0.5, 0.5): k_raygen's arithmetic, no clip interval, no culling.
+// guide_dir is the one place that arithmetic lives for both kernels below, so that the position k_guides writes lies on the ray that was traced.
+PT_DEV v3 guide_dir(const DevCamera& cam, int w, int h, uint32_t pixel) {
+  const uint32_t px = pixel % (uint32_t)w, py = pixel / (uint32_t)w;
+  const float fx = ((float)px + 0.5f) / (float)w, fy = ((float)py + 0.5f) / (float)h;
+  const float dvx = (2.0f * fx - 1.0f) * cam.sx, dvy = (2.0f * fy - 1.0f) * cam.sy;
+  const v3 cs = V3(cam.s[0], cam.s[1], cam.s[2]), cu = V3(cam.u[0], cam.u[1], cam.u[2]), cf = V3(cam.f[0], cam.f[1], cam.f[2]);
+  return normalize3(vfma(cs, dvx, vfma(cu, dvy, cf)));
+}
+// rays of the pixels [first_pixel, first_pixel + n) at the slots [0, n) of ray[0]; the path state words (C, lpath) are not needed: only k_trace_closest follows
+__global__ __launch_bounds__(256) void k_raygen_guides(DevCamera cam, int w, int h, uint32_t first_pixel, uint32_t n, DevQueues q) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n) return;
+  const v3 d = guide_dir(cam, w, h, first_pixel + p);
+  const RayQ& r = q.ray[0];
+  r.A[p] = make_float4(cam.pos[0], cam.pos[1], cam.pos[2], d.x);
+  r.B[p] = make_float4(d.y, d.z, 1.0f, 1.0f);
+  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), 0.0f);
+}
+// q.hit of those rays → the guide buffers (full-frame arrays, indexed by pixel):
+//   albedo_class (A.rgb, K)   K: 0 miss, 1 surface, 2 emitter (an emissive factor with a non-zero component); A: the base colour after the colour texture
+//                             (what apply_textures leaves in base[0..2], filter mode included) for K = 1, else (1, 1, 1)
+//   normal_depth (N.xyz, Z)   N: the normalised interpolated vertex normal (no normal map) for K = 1, else 0; Z: t along the unit ray, 0 on a miss
+//   pos_class    (P.xyz, K)   P = camera position + Z · direction: what the filter's plane-distance weight reads (one 16-byte load per tap beside normal_depth)
+//   prim, uv                  the hit's primitive id (-1: miss) and barycentrics
+__global__ __launch_bounds__(256) void k_guides(DevScene sc, DevCamera cam, int w, int h, uint32_t first_pixel, uint32_t n, const float4* hit,
+                                                float4* albedo_class, float4* normal_depth, float4* pos_class, int32_t* prim_out, float2* uv_out) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t pixel = first_pixel + j;
+  const float4 H = hit[j];
+  const int pc = __float_as_int(H.y);
+  float4 ak = make_float4(1.0f, 1.0f, 1.0f, 0.0f), nz = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  int prim = -1;
+  float2 uv = make_float2(0.0f, 0.0f);
+  if (pc >= 0) {
+    prim = pc & ((1 << HIT_CLASS_SHIFT) - 1);
+    const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
+    uv = make_float2(hu, hv);
+    nz.w = H.x;
+    const float4* rec = sc.shade + (size_t)prim * sc.shade_stride;
+    const float4 r0 = rec[0], r2 = rec[2], r3 = rec[3], r4 = rec[4];
+    const int mat = __float_as_int(r0.w);
+    const float4 M0 = sc.mats[mat * 4 + 0], M1 = sc.mats[mat * 4 + 1], M2 = sc.mats[mat * 4 + 2];
+    if (M1.x != 0.0f || M1.y != 0.0f || M1.z != 0.0f) ak.w = 2.0f;
+    else {
+      const v3 ni = V3(pt_fma(r4.y, hv, pt_fma(r3.z, hu, r2.w * hw)), pt_fma(r4.z, hv, pt_fma(r3.w, hu, r3.x * hw)), pt_fma(r4.w, hv, pt_fma(r4.x, hu, r3.y * hw)));
+      const v3 N = normalize3(ni);
+      v3 ns = N;
+      float base[4] = {M0.x, M0.y, M0.z, M2.x};
+      float metallic = M0.w, roughness = M1.w;
+      if (__float_as_int(M2.y) >= 0 || __float_as_int(M2.z) >= 0 || __float_as_int(M2.w) >= 0)
+        apply_textures(sc, rec[5], rec[6], rec[7], rec[8], rec[9], rec[10], hu, hv, hw, M2, __float_as_int(sc.mats[mat * 4 + 3].x), ni, base, metallic, roughness, ns);
+      ak = make_float4(base[0], base[1], base[2], 1.0f);
+      nz.x = N.x; nz.y = N.y; nz.z = N.z;
+    }
+  }
+  const v3 d = guide_dir(cam, w, h, pixel);
+  albedo_class[pixel] = ak;
+  normal_depth[pixel] = nz;
+  pos_class[pixel] = make_float4(cam.pos[0] + nz.w * d.x, cam.pos[1] + nz.w * d.y, cam.pos[2] + nz.w * d.z, ak.w);
+  prim_out[pixel] = prim;
+  uv_out[pixel] = uv;
+}
+void pt_launch_raygen_guides(hipStream_t s, const DevCamera& cam, int w, int h, uint32_t first_pixel, uint32_t n, const DevQueues& q) {
+  hipLaunchKernelGGL(k_raygen_guides, dim3((n + 255u) / 256u), dim3(256), 0, s, cam, w, h, first_pixel, n, q);
+}
+void pt_launch_guides(hipStream_t s, const DevScene& sc, const DevCamera& cam, int w, int h, uint32_t first_pixel, uint32_t n, const DevQueues& q, const GuideBufs& g) {
+  hipLaunchKernelGGL(k_guides, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, cam, w, h, first_pixel, n, (const float4*)q.hit, g.albedo_class, g.normal_depth, g.pos_class, g.prim, g.uv);
+}

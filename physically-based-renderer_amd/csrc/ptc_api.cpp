@@ -12,6 +12,7 @@
 #include "ptc_internal.h"
 #include "pt_refit.h"
 #include "pt_build.h"
+#include "pt_denoise.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -171,6 +172,15 @@ struct ptc_ctx {
   DevBuf<uint32_t> ldr;
   DevBuf<uint2> half;               // RGBA16F copy of the radiance buffer
   int rad_w = 0, rad_h = 0;
+  // denoiser: the first-hit guides of the current frame (k_guides), the filter's two (colour, variance) buffers, the denoised image and which image the read-backs serve
+  DevBuf<float4> g_albedo, g_normal, g_pos, dn_cv[2], denoised;
+  DevBuf<int32_t> g_prim;
+  DevBuf<float2> g_uv;
+  DevBuf<unsigned long long> g_stats;   // the guide rays' traversal counters: kept apart from the frame's (ptc_stats counts samples only)
+  bool guides_valid = false, denoised_valid = false;
+  int output = PTC_OUTPUT_RADIANCE;
+  hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr};   // start / stop of the last guide pass, start / stop of the last denoise
+  bool ev_dn_recorded[2] = {false, false};
   // multi-GPU
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -193,6 +203,10 @@ namespace {
 constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray ping-pong) + 48 (shadow) + 16 (hit) + 16 (path radiance)
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 int fail(ptc_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; return code; }
+// the frame is over or the scene changed: its guides and its denoised image go with it, the read-backs serve the radiance again
+void drop_guides(ptc_ctx* c) { c->guides_valid = false; c->denoised_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
+// the image ptc_read_radiance_rgba32f / _rgba16f / ptc_tonemap_rgba8 serve (ptc_select_output)
+const float4* served_image(const ptc_ctx* c) { return c->output == PTC_OUTPUT_DENOISED ? c->denoised.p : c->radiance.p; }
 const char* const kNoDevice = "this context has no device (PTC_DEVICE_NONE): the call needs a gfx950 GPU; there is no CPU path";
 
 #define HIP_TRY(c, expr)                                                                                 \
@@ -394,6 +408,16 @@ DevQueues batch_queues(ptc_ctx* c, int l, uint32_t n) {
 }
 bool is_raster(int integrator) { return integrator == PTC_INTEGRATOR_RASTER_COMPAT || integrator == PTC_INTEGRATOR_RASTER_GBUFFER16; }
 
+// the launch configuration of a batch of n_paths rays: the trace kernels' persistent grid follows the batch (see run_batch)
+LaunchCfg batch_cfg(const ptc_ctx* c, uint32_t n_paths) {
+  LaunchCfg cfg = c->cfg;
+  const uint64_t per_block = (uint64_t)pt_trace_block_threads() * (uint64_t)c->trace_rays_per_lane;
+  uint64_t per_cu = ((uint64_t)n_paths + per_block * (uint64_t)cfg.n_cu - 1u) / (per_block * (uint64_t)cfg.n_cu);
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu < (uint64_t)cfg.trace_blocks_per_cu) cfg.trace_blocks_per_cu = (int)per_cu;
+  return cfg;
+}
+
 // One wavefront batch of n samples per owned pixel on lane `l`, fully asynchronous.
 int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
   const uint32_t n_paths = c->fr.n_owned * n_samples;
@@ -404,13 +428,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
   // The persistent grid of the trace kernels follows the batch: a wave wants several refills' worth of rays (c->trace_rays_per_lane per lane) to run in its
   // steady state; 8192 waves over the 2 M rays of a 1080p x 1 spp frame are 4 refills each, most of the launch is start-up and drain (0.8 ms for bounce 0,
   // 0.25 ms for the last bounces: tools/viewer_loop.py).  Batches of the benchmark's size keep the full grid.
-  LaunchCfg cfg = c->cfg;
-  {
-    const uint64_t per_block = (uint64_t)pt_trace_block_threads() * (uint64_t)c->trace_rays_per_lane;
-    uint64_t per_cu = ((uint64_t)n_paths + per_block * (uint64_t)cfg.n_cu - 1u) / (per_block * (uint64_t)cfg.n_cu);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu < (uint64_t)cfg.trace_blocks_per_cu) cfg.trace_blocks_per_cu = (int)per_cu;
-  }
+  const LaunchCfg cfg = batch_cfg(c, n_paths);
   if (c->spans.size() > kMaxSpans) {      // bounded event pool: harvest what has completed; if the host runs far ahead of
     collect_times(c, false);              // the device, wait for the oldest batch (back-pressure) instead of growing
     if (c->spans.size() > kMaxSpans) { (void)hipEventSynchronize(c->spans[c->spans.size() - kMaxSpans].b); collect_times(c, false); }
@@ -528,7 +546,7 @@ int convert_half(ptc_ctx* c) {
   const size_t n = (size_t)c->rad_w * c->rad_h;
   int rc = ensure_buf(c, c->half, n);
   if (rc) return rc;
-  pt_launch_to_half(c->lanes[0].stream, c->radiance.p, c->half.p, (uint32_t)n);
+  pt_launch_to_half(c->lanes[0].stream, served_image(c), c->half.p, (uint32_t)n);
   HIP_TRY(c, hipGetLastError());
   return PTC_OK;
 }
@@ -538,7 +556,7 @@ int debug_prepare(ptc_ctx* c, uint32_t n, const char* who) {
   if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
   { int rf = flush(c); if (rf) return rf; }
   { int rs = sync_all_lanes(c); if (rs) return rs; }
-  c->in_frame = false; c->pending = 0;
+  c->in_frame = false; c->pending = 0; drop_guides(c);
   int rc = ensure_lane_queues(c, n);
   if (rc) return rc;
   for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
@@ -658,6 +676,9 @@ void ptc_destroy(ptc_ctx* c) {
   release_scene(c);
   if (c->bscratch.p) (void)hipFree(c->bscratch.p);
   c->owned.release(); c->accum.release(); c->radiance.release(); c->ldr.release(); c->half.release();
+  c->g_albedo.release(); c->g_normal.release(); c->g_pos.release(); c->dn_cv[0].release(); c->dn_cv[1].release(); c->denoised.release();
+  c->g_prim.release(); c->g_uv.release(); c->g_stats.release();
+  for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
   delete c;
 }
 
@@ -671,7 +692,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   }
   c->mats.clear(); c->meshes.clear(); c->insts.clear(); c->texs.clear(); c->env = HostEnv{}; c->tex_linear = 0;
   c->bvh_builder = c->bvh_default;
-  c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0;
+  c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
   release_scene(c);
   return PTC_OK;
 }
@@ -886,7 +907,7 @@ int device_refit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
   if (!rc) rc = node_pass(c, m, /*publish=*/true);
   if (rc) return rc;
   c->stats.bvh_sa_cost = (double)c->built->sa_cost_fixed / (double)PTC_SA_COST_ONE;
-  c->in_frame = false; c->pending = 0;
+  c->in_frame = false; c->pending = 0; drop_guides(c);
   c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return PTC_OK;
 }
@@ -1012,7 +1033,7 @@ int ptc_scene_refit(ptc_ctx* c) {
   const size_t n_recs = B.recs.size(), n_shade = B.shade.size(), n_lights = B.lights.size(), n_cdf = B.cdf.size();
   const std::string e = ptc_refit_scene(c->mats, c->meshes, c->insts, c->texs, c->env, B);
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
-  c->in_frame = false; c->pending = 0;
+  c->in_frame = false; c->pending = 0; drop_guides(c);
   c->stats.n_emitters = B.n_lights;
   c->stats.bvh_sa_cost = (double)B.sa_cost_fixed / (double)PTC_SA_COST_ONE;
   if (c->device >= 0) {
@@ -1036,7 +1057,7 @@ int ptc_scene_rebuild(ptc_ctx* c) {
   if (rd < 0) return rd;
   if (rd > 0) { if ((rd = host_build_and_upload(c, t0, /*as_refit=*/false))) return rd; }      // PTC_REBUILD=host, an emitter appeared or vanished, a single triangle
   else c->stats.seconds_rebuild = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  c->in_frame = false; c->pending = 0;
+  c->in_frame = false; c->pending = 0; drop_guides(c);
   return PTC_OK;
 }
 
@@ -1045,6 +1066,7 @@ int ptc_set_camera(ptc_ctx* c, const float pos[3], const float target[3], float 
   if (!pos || !target) return fail(c, PTC_E_ARG, "set_camera: null pointer");
   std::memcpy(c->cam_pos, pos, 12); std::memcpy(c->cam_target, target, 12); c->cam_fov = fov_y; c->cam_aspect = aspect;
   c->have_cam = true;
+  c->guides_valid = false;      // the guides are those of the camera they were traced from
   if (c->committed) ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
   return PTC_OK;
 }
@@ -1104,7 +1126,7 @@ int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
 // skeleton: c->built is ptc_build_skeleton's — the tables are uploaded, the shading records allocated and zeroed, there is no tree yet: device_commit goes on from here.
 int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool skeleton) {
   ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
-  c->in_frame = false; c->pending = 0;
+  c->in_frame = false; c->pending = 0; drop_guides(c);
   c->committed = false;
   release_scene(c);
   CommittedScene& s = c->scene;
@@ -1228,7 +1250,7 @@ int ptc_scene_commit(ptc_ctx* c) { return scene_commit(c, true); }
 
 int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
   { int rd = need_device(c); if (rd) return rd; }
-  c->in_frame = false; c->pending = 0;      // whatever happens below, the previous frame is over
+  c->in_frame = false; c->pending = 0; drop_guides(c);      // whatever happens below, the previous frame is over
   if (!c->committed) return fail(c, PTC_E_STATE, "frame_begin: scene not committed");
   if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, "frame_begin: bad size");
   if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, "frame_begin: unknown integrator");
@@ -1392,7 +1414,7 @@ int ptc_read_radiance_rgba32f(ptc_ctx* c, float* out) {
   if (!out) return fail(c, PTC_E_ARG, "read_radiance: null pointer");
   if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "read_radiance: nothing rendered");
   { int rs = sync_all_lanes(c); if (rs) return rs; }
-  HIP_TRY(c, hipMemcpy(out, c->radiance.p, (size_t)c->rad_w * c->rad_h * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(out, served_image(c), (size_t)c->rad_w * c->rad_h * sizeof(float4), hipMemcpyDeviceToHost));
   return PTC_OK;
 }
 
@@ -1429,10 +1451,143 @@ int ptc_tonemap_rgba8(ptc_ctx* c, uint8_t* out) {
   int rc;
   if ((rc = ensure_buf(c, c->ldr, (size_t)c->rad_w * c->rad_h))) return rc;
   hipStream_t s0 = c->lanes[0].stream;
-  pt_launch_tonemap(s0, c->radiance.p, c->ldr.p, c->rad_w, c->rad_h);
+  pt_launch_tonemap(s0, served_image(c), c->ldr.p, c->rad_w, c->rad_h);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(s0));
   HIP_TRY(c, hipMemcpy(out, c->ldr.p, (size_t)c->rad_w * c->rad_h * 4, hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+// ---- first-hit guide buffers + the variance-guided à-trous denoiser (pt_denoise.hip) -----------------------------------------
+namespace {
+int ensure_dn_events(ptc_ctx* c) {
+  for (hipEvent_t& e : c->ev_dn) if (!e) HIP_TRY(c, hipEventCreate(&e));
+  return PTC_OK;
+}
+}  // namespace
+
+int ptc_frame_guides(ptc_ctx* c) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_guides: no frame");
+  if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_guides: the frame is not a PTC_INTEGRATOR_PATH frame (the raster integrators are noise-free)");
+  const uint32_t n = (uint32_t)c->fr.w * (uint32_t)c->fr.h;      // every pixel, whatever the frame's tile share: the root of a sharded frame denoises the whole image
+  int rc;
+  if ((rc = ensure_buf(c, c->g_albedo, n)) || (rc = ensure_buf(c, c->g_normal, n)) || (rc = ensure_buf(c, c->g_pos, n)) || (rc = ensure_buf(c, c->g_prim, n)) ||
+      (rc = ensure_buf(c, c->g_uv, n)) || (rc = ensure_dn_events(c))) return rc;
+  if (!c->g_stats.p) {
+    if ((rc = ensure_buf(c, c->g_stats, (size_t)ST_N * ST_STRIDE))) return rc;
+    HIP_TRY(c, hipMemset(c->g_stats.p, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
+  }
+  // The guide rays borrow lane 0's queues between two batches (a batch leaves nothing in them: its radiance is in the sums once k_accumulate ran) and are
+  // traced in chunks of what the lane holds; a lane without queues yet gets them for one sample per pixel, at most 2 M paths.
+  {
+    const uint32_t want = n < (1u << 21) ? n : (1u << 21);
+    if (c->lanes[0].q.cap < want && (rc = ensure_lane_queues(c, want))) return rc;
+  }
+  Lane& ln = c->lanes[0];
+  hipStream_t st = ln.stream;
+  const DevScene sc = lane_scene(c, 0);
+  const GuideBufs g = {c->g_albedo.p, c->g_normal.p, c->g_pos.p, c->g_prim.p, c->g_uv.p};
+  const uint32_t chunk = ln.q.cap < n ? ln.q.cap : n;
+  HIP_TRY(c, hipEventRecord(c->ev_dn[0], st));
+  for (uint32_t first = 0; first < n; first += chunk) {
+    const uint32_t m = n - first < chunk ? n - first : chunk;
+    DevQueues q = batch_queues(c, 0, m);
+    q.stats = c->g_stats.p;            // the frame's counters do not see the guide rays
+    const LaunchCfg cfg = batch_cfg(c, m);
+    pt_launch_set_counts(st, cfg, q, m, 0);
+    pt_launch_raygen_guides(st, c->cam, c->fr.w, c->fr.h, first, m, q);
+    pt_launch_trace_closest(st, cfg, sc, q, 0, false);
+    pt_launch_guides(st, sc, c->cam, c->fr.w, c->fr.h, first, m, q, g);
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_dn[1], st));
+  HIP_TRY(c, hipGetLastError());
+  c->ev_dn_recorded[0] = true;
+  c->guides_valid = true;
+  return PTC_OK;
+}
+
+int ptc_read_guide_rgba32f(ptc_ctx* c, int which, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "read_guide: null pointer");
+  if (which != PTC_GUIDE_ALBEDO && which != PTC_GUIDE_NORMAL_DEPTH) return fail(c, PTC_E_ARG, "read_guide: unknown guide");
+  if (!c->guides_valid) return fail(c, PTC_E_STATE, "read_guide: no guides (ptc_frame_guides)");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  HIP_TRY(c, hipMemcpy(out, which == PTC_GUIDE_ALBEDO ? c->g_albedo.p : c->g_normal.p, (size_t)c->rad_w * c->rad_h * sizeof(float4), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+int ptc_read_guide_hit(ptc_ctx* c, int32_t* prim, float* uv) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->guides_valid) return fail(c, PTC_E_STATE, "read_guide_hit: no guides (ptc_frame_guides)");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  const size_t n = (size_t)c->rad_w * c->rad_h;
+  if (prim) HIP_TRY(c, hipMemcpy(prim, c->g_prim.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (uv) HIP_TRY(c, hipMemcpy(uv, c->g_uv.p, n * sizeof(float2), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+void ptc_denoise_default_params(ptc_denoise_params* p) {
+  if (!p) return;
+  p->iterations = 4; p->sigma_l = 4.0f; p->sigma_n = 128.0f; p->sigma_p = 1.0f; p->demodulate = 1;
+}
+
+int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) {
+  { int rd = need_device(c); if (rd) return rd; }
+  ptc_denoise_params p;
+  ptc_denoise_default_params(&p);
+  if (params) p = *params;
+  auto bad = [](float v) { return !(v >= 0.0f) || !(v <= 3.0e38f); };      // NaN, negative, infinite
+  if (p.iterations < 0 || p.iterations > PTC_DENOISE_MAX_ITERATIONS) return fail(c, PTC_E_ARG, "denoise: iterations outside 0..8");
+  if (bad(p.sigma_l) || bad(p.sigma_n) || bad(p.sigma_p)) return fail(c, PTC_E_ARG, "denoise: a sigma is negative or not finite");
+  if (!c->guides_valid) return fail(c, PTC_E_STATE, "denoise: no valid guides (ptc_frame_guides after the frame's ptc_frame_begin)");
+  if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "denoise: no radiance buffer");
+  const size_t n = (size_t)c->rad_w * c->rad_h;
+  int rc;
+  if ((rc = ensure_buf(c, c->denoised, n)) || (rc = ensure_dn_events(c))) return rc;
+  if (p.iterations > 0 && ((rc = ensure_buf(c, c->dn_cv[0], n)) || (rc = ensure_buf(c, c->dn_cv[1], n)))) return rc;
+  hipStream_t s0 = c->lanes[0].stream;      // behind the resolve, the reduce and the guide pass
+  HIP_TRY(c, hipEventRecord(c->ev_dn[2], s0));
+  if (p.iterations == 0) HIP_TRY(c, hipMemcpyAsync(c->denoised.p, c->radiance.p, n * sizeof(float4), hipMemcpyDeviceToDevice, s0));
+  else {
+    DenoiseArgs a{};
+    a.w = c->rad_w; a.h = c->rad_h; a.sigma_l = p.sigma_l; a.sigma_n = p.sigma_n; a.sigma_p = p.sigma_p; a.demodulate = p.demodulate ? 1 : 0;
+    a.pix = (2.0f * c->cam.sy) / (float)c->rad_h;
+    a.radiance = c->radiance.p;
+    a.g = GuideBufs{c->g_albedo.p, c->g_normal.p, c->g_pos.p, c->g_prim.p, c->g_uv.p};
+    pt_launch_denoise_prepare(s0, a, c->dn_cv[0].p);
+    for (int i = 0; i < p.iterations; ++i) {
+      const bool last = i == p.iterations - 1;
+      pt_launch_denoise_iteration(s0, a, i, c->dn_cv[i & 1].p, last ? c->denoised.p : c->dn_cv[(i + 1) & 1].p, last);
+    }
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_dn[3], s0));
+  HIP_TRY(c, hipGetLastError());
+  c->ev_dn_recorded[1] = true;
+  c->denoised_valid = true;
+  return PTC_OK;
+}
+
+int ptc_select_output(ptc_ctx* c, int output) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (output != PTC_OUTPUT_RADIANCE && output != PTC_OUTPUT_DENOISED) return fail(c, PTC_E_ARG, "select_output: unknown output");
+  if (output == PTC_OUTPUT_DENOISED && !c->denoised_valid) return fail(c, PTC_E_STATE, "select_output: the frame has no denoised image (ptc_denoise)");
+  c->output = output;
+  return PTC_OK;
+}
+
+int ptc_get_denoise_seconds(ptc_ctx* c, double* guides, double* denoise) {
+  { int rd = need_device(c); if (rd) return rd; }
+  double* out[2] = {guides, denoise};
+  for (int k = 0; k < 2; ++k) {
+    if (!out[k]) continue;
+    *out[k] = 0.0;
+    if (!c->ev_dn_recorded[k]) continue;
+    HIP_TRY(c, hipEventSynchronize(c->ev_dn[2 * k + 1]));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_dn[2 * k], c->ev_dn[2 * k + 1]));
+    *out[k] = 1e-3 * (double)ms;
+  }
   return PTC_OK;
 }
 
@@ -1595,7 +1750,7 @@ int ptc_group_scene_refit(ptc_group* g) {
     if (c->device >= 0 && hipSetDevice(c->device) != hipSuccess) { g->err = "ptc_group_scene_refit: hipSetDevice failed"; return PTC_E_DEVICE; }
     if (i) c->insts = c0->insts;
     c->built = built;
-    c->in_frame = false; c->pending = 0;
+    c->in_frame = false; c->pending = 0; drop_guides(c);
     const int rc = c->device >= 0 ? refit_upload(c, same, t0) : PTC_OK;
     if (rc) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
     c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -138,6 +138,10 @@ void pt_launch_shade_raster(hipStream_t, const DevScene&, const DevCamera&, cons
 void pt_launch_to_half(hipStream_t, const float4* radiance, uint2* out_rgba16f, uint32_t n_pixels);
 void pt_launch_resolve(hipStream_t, const DevFrame&, const float4* accum, float4* radiance, float inv_spp_divisor, bool raster);
 void pt_launch_tonemap(hipStream_t, const float4* radiance, uint32_t* rgba8, int w, int h);
+// first-hit guide buffers of the denoiser, full-frame arrays indexed by pixel (k_guides, pt_kernels.hip; read by pt_denoise.hip)
+struct GuideBufs { float4* albedo_class; float4* normal_depth; float4* pos_class; int32_t* prim; float2* uv; };
+void pt_launch_raygen_guides(hipStream_t, const DevCamera&, int w, int h, uint32_t first_pixel, uint32_t n, const DevQueues&);   // pixel-centre rays of n pixels at the slots [0, n) of ray[0]
+void pt_launch_guides(hipStream_t, const DevScene&, const DevCamera&, int w, int h, uint32_t first_pixel, uint32_t n, const DevQueues&, const GuideBufs&);   // q.hit of those rays -> the guides
 
 // ---- host-side scene build (ptc_scene.cpp) ----------------------------------------------------------
 struct HostMaterial { float base[4]; float metallic, roughness; float emissive[3]; int tex_color, tex_normal, tex_mr; };

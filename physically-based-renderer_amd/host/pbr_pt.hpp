@@ -142,6 +142,25 @@ public:
     _w = w; _h = h;
     return out;
   }
+  // ---- first-hit guides, denoiser, output selection (include/ptc.h; the reference has no counterpart: its raster image is noise-free) ----
+  // guides of every pixel of the frame in progress (render() leaves its frame open, and so does DeviceGroup::render on device(0))
+  auto frameGuides() -> void { ck(ptc_frame_guides(_ctx)); }
+  // PTC_GUIDE_ALBEDO: (albedo rgb, class 0 miss / 1 surface / 2 emitter); PTC_GUIDE_NORMAL_DEPTH: (vertex normal, t along the unit camera ray)
+  auto readGuide(int which) -> std::vector<float> {
+    std::vector<float> out((std::size_t)_w * _h * 4);
+    ck(ptc_read_guide_rgba32f(_ctx, which, out.data()));
+    return out;
+  }
+  auto readGuideHit(std::vector<std::int32_t>& prim, std::vector<float>& uv) -> void {
+    prim.resize((std::size_t)_w * _h); uv.resize((std::size_t)_w * _h * 2);
+    ck(ptc_read_guide_hit(_ctx, prim.data(), uv.data()));
+  }
+  static auto denoiseDefaults() -> ptc_denoise_params { ptc_denoise_params p; ptc_denoise_default_params(&p); return p; }
+  // radiance buffer + guides -> the denoised buffer; selectOutput(PTC_OUTPUT_DENOISED) makes readRadiance / radianceHalf / tonemap serve it
+  auto denoise(ptc_denoise_params const* params = nullptr) -> void { ck(ptc_denoise(_ctx, params)); }
+  auto selectOutput(int output) -> void { ck(ptc_select_output(_ctx, output)); }
+  // HIP-event seconds of the last frameGuides() and the last denoise()
+  auto denoiseSeconds() -> std::array<double, 2> { std::array<double, 2> t{0.0, 0.0}; ck(ptc_get_denoise_seconds(_ctx, &t[0], &t[1])); return t; }
   auto stats() -> ptc_stats { ptc_stats s; ck(ptc_get_stats(_ctx, &s)); return s; }
   auto handle() -> ptc_ctx* { return _ctx; }
 

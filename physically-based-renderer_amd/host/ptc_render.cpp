@@ -1,7 +1,10 @@
 // ptc_render — dependency-free C++17 offline renderer over the C-ABI (include/ptc.h).
 //   ptc_render (--scene cornell|sphere | --gltf file.glb [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
 //              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
-//              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16]
+//              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--guides PREFIX]
+// --denoise: first-hit guides + the variance-guided a-trous filter (ptc_frame_guides, ptc_denoise) after the render; every output is then the denoised
+// image.  --denoise-iters N: N iterations instead of the default 4 (implies --denoise).  --guides PREFIX: PREFIX_albedo.pfm, PREFIX_normal.pfm and
+// PREFIX_depth.pfm (the depth in all three channels) beside the image, for a denoiser outside the library.  With --gpus N device D denoises after the reduce.
 // --gpus N: devices D..D+N-1 share the frame by 32x32-pixel tiles, one RCCL reduce brings it to device D (ptc_group_*).
 // --raster16: the reference's Blinn-Phong pass lit from its G-buffer formats; --half writes the RGBA16F buffer (raw little-endian halves).
 // --env: ordinary lat-long RGB environment map (PFM or Radiance .hdr, top row = up).  The reference's world is y-down (up = -y, CameraData.hpp:28) and
@@ -113,7 +116,9 @@ int main(int argc, char** argv) {
   bool haveCam = false;
   float viewerFov = 0.0f;                    // --viewer-camera: the reference's fov in radians, passed on without a degree round trip
   int w = 256, h = 256, spp = 64, bounces = 8, device = 0, gpus = 0 /* 0: one plain context; N >= 1: a device group of N */, integrator = PTC_INTEGRATOR_PATH;
-  std::string halfPath;
+  std::string halfPath, guidesPrefix;
+  bool denoise = false;
+  int denoiseIters = -1;                     // -1: the library's default
   std::uint64_t seed = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -123,6 +128,7 @@ int main(int argc, char** argv) {
     else if (a == "--bounces") bounces = std::atoi(next()); else if (a == "--device") device = std::atoi(next());
     else if (a == "--gpus") gpus = std::atoi(next()); else if (a == "--half") halfPath = next(); else if (a == "--raster16") integrator = PTC_INTEGRATOR_RASTER_GBUFFER16;
     else if (a == "--gltf") gltf = next();
+    else if (a == "--denoise") denoise = true; else if (a == "--denoise-iters") { denoiseIters = std::atoi(next()); denoise = true; } else if (a == "--guides") guidesPrefix = next();
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -203,6 +209,25 @@ int main(int argc, char** argv) {
     if (!gltf.empty()) scene = gltf;
     ptc_stats st = rs.stats();
     for (int i = 1; i < gpus; ++i) { const ptc_stats o = group->device(i).stats(); st.paths += o.paths; st.node_visits_closest += o.node_visits_closest; st.node_visits_any += o.node_visits_any; }
+    if (denoise || !guidesPrefix.empty()) {
+      if (integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--denoise / --guides need the path integrator (the raster passes are noise-free)");
+      rs.frameGuides();
+      if (!guidesPrefix.empty()) {
+        const std::vector<float> ak = rs.readGuide(PTC_GUIDE_ALBEDO);
+        std::vector<float> nz = rs.readGuide(PTC_GUIDE_NORMAL_DEPTH), zz(nz.size());
+        for (std::size_t p = 0; p < nz.size(); p += 4) zz[p] = zz[p + 1] = zz[p + 2] = zz[p + 3] = nz[p + 3];
+        pbr::image::write_pfm(guidesPrefix + "_albedo.pfm", ak.data(), w, h);
+        pbr::image::write_pfm(guidesPrefix + "_normal.pfm", nz.data(), w, h);
+        pbr::image::write_pfm(guidesPrefix + "_depth.pfm", zz.data(), w, h);
+      }
+      if (denoise) {
+        ptc_denoise_params dp = pbr::PathTraceRenderSystem::denoiseDefaults();
+        if (denoiseIters >= 0) dp.iterations = denoiseIters;
+        rs.denoise(&dp);
+        rs.selectOutput(PTC_OUTPUT_DENOISED);
+        img = rs.readRadiance(w, h);
+      }
+    }
     if (!halfPath.empty()) {
       const std::vector<std::uint16_t> hb = rs.radianceHalf();
       std::ofstream g(halfPath, std::ios::binary);

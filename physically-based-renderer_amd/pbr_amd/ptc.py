@@ -26,6 +26,10 @@ INTEGRATOR_RASTER_COMPAT = 1
 INTEGRATOR_RASTER_GBUFFER16 = 2   # raster-compat lit from the reference's G-buffer formats (RGBA16F P/N, UNORM16 albedo)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
+GUIDE_ALBEDO = 0          # (albedo rgb, class: 0 miss, 1 surface, 2 emitter)
+GUIDE_NORMAL_DEPTH = 1    # (unit vertex normal, t along the unit camera ray)
+OUTPUT_RADIANCE = 0
+OUTPUT_DENOISED = 1
 
 # every symbol include/ptc.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -36,6 +40,7 @@ ABI_SYMBOLS = [
     "ptc_debug_trace_closest", "ptc_debug_trace_any", "ptc_debug_get_flat_scene", "ptc_debug_get_bvh", "ptc_debug_get_counters",
     "ptc_debug_get_description", "ptc_debug_get_material", "ptc_debug_get_texture", "ptc_debug_get_internals", "ptc_debug_host_build_id", "ptc_debug_get_shading_tables", "ptc_debug_refit_host_parts", "ptc_debug_commit_host_parts",
     "ptc_read_radiance_rgba16f", "ptc_radiance_rgba16f_device_ptr",
+    "ptc_frame_guides", "ptc_read_guide_rgba32f", "ptc_read_guide_hit", "ptc_denoise_default_params", "ptc_denoise", "ptc_select_output", "ptc_get_denoise_seconds",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
@@ -52,6 +57,13 @@ class PtcStats(C.Structure):
         ("n_triangles", C.c_uint32), ("n_bvh_nodes", C.c_uint32), ("n_emitters", C.c_uint32), ("bvh_max_depth", C.c_uint32),
         ("bvh_sa_cost", C.c_double), ("bvh_sa_cost_built", C.c_double), ("seconds_rebuild", C.c_double),
     ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -133,6 +145,14 @@ def load_library():
     L.ptc_read_radiance_rgba16f.argtypes = [vp, C.POINTER(C.c_uint16)]
     L.ptc_radiance_rgba16f_device_ptr.argtypes = [vp]
     L.ptc_radiance_rgba16f_device_ptr.restype = vp
+    L.ptc_frame_guides.argtypes = [vp]
+    L.ptc_read_guide_rgba32f.argtypes = [vp, C.c_int, fp]
+    L.ptc_read_guide_hit.argtypes = [vp, i32p, fp]
+    L.ptc_denoise_default_params.argtypes = [C.POINTER(PtcDenoiseParams)]
+    L.ptc_denoise_default_params.restype = None
+    L.ptc_denoise.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
+    L.ptc_select_output.argtypes = [vp, C.c_int]
+    L.ptc_get_denoise_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -320,6 +340,50 @@ class PathTracer:
 
     def radiance_f16_device_ptr(self) -> int:
         return int(self._L.ptc_radiance_rgba16f_device_ptr(self._h) or 0)
+
+    # ---- guide buffers, denoiser, output selection ---------------------------------------------------
+    def frame_guides(self):
+        """ptc_frame_guides: trace the first-hit guides (albedo, normal, depth, class, hit) of every pixel of the frame in progress."""
+        self._ck(self._L.ptc_frame_guides(self._h))
+
+    def read_guide(self, which):
+        """(h, w, 4) float32: GUIDE_ALBEDO = (albedo rgb, class), GUIDE_NORMAL_DEPTH = (normal, depth)."""
+        out = np.empty((self._h_px, self._w, 4), np.float32)
+        self._ck(self._L.ptc_read_guide_rgba32f(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def read_guide_hit(self):
+        """(prim (h, w) int32 with -1 = miss, uv (h, w, 2) float32) of the guide rays' hits."""
+        prim = np.empty((self._h_px, self._w), np.int32)
+        uv = np.empty((self._h_px, self._w, 2), np.float32)
+        self._ck(self._L.ptc_read_guide_hit(self._h, prim.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(C.POINTER(C.c_float))))
+        return prim, uv
+
+    @staticmethod
+    def denoise_default_params():
+        p = PtcDenoiseParams()
+        load_library().ptc_denoise_default_params(C.byref(p))
+        return p.as_dict()
+
+    def denoise(self, **params):
+        """ptc_denoise: radiance buffer + guides -> the denoised buffer.  Keywords (iterations, sigma_l, sigma_n, sigma_p, demodulate) replace the defaults."""
+        p = PtcDenoiseParams()
+        self._L.ptc_denoise_default_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(PtcDenoiseParams._fields_):
+                raise TypeError(f"denoise: unknown parameter {k}")
+            setattr(p, k, v)
+        self._ck(self._L.ptc_denoise(self._h, C.byref(p)))
+
+    def select_output(self, which):
+        """ptc_select_output: OUTPUT_RADIANCE or OUTPUT_DENOISED is what read_radiance / read_radiance_f16 / tonemap serve."""
+        self._ck(self._L.ptc_select_output(self._h, int(which)))
+
+    def denoise_seconds(self):
+        """(guide pass, denoise): HIP-event seconds of the last frame_guides() and the last denoise()."""
+        g, d = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ptc_get_denoise_seconds(self._h, C.byref(g), C.byref(d)))
+        return g.value, d.value
 
     # ---- multi-GPU (RCCL through the C-ABI) ---------------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, n_ranks: int):

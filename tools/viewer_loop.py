@@ -4,17 +4,22 @@ instances get a new rotation (ptc_update_instance), the scene is refitted (ptc_s
 per pixel and resolved into the RGBA16F image the viewer's tonemapper reads (ptc_radiance_rgba16f_device_ptr: no copy to the host).  Wall time per
 frame over `frames` frames, and where it goes.  VIEWER_REBUILD_RATIO=r in the environment adds the policy of examples/viewer_shim.cpp: after the refit, a rebuild on the
 device (ptc_scene_rebuild) when ptc_stats.bvh_sa_cost has grown past r times bvh_sa_cost_built; the frame times before and after the first rebuild are reported apart.
-With PTC_DEVICE_BVH=sah in the environment the rebuilt tree is the binned-SAH tree (ptc_set_device_builder), else the LBVH.  usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h]"""
+With PTC_DEVICE_BVH=sah in the environment the rebuilt tree is the binned-SAH tree (ptc_set_device_builder), else the LBVH.
+--denoise runs the loop a second time in the same process with the first-hit guides (ptc_frame_guides) and the à-trous filter (ptc_denoise, default
+parameters) between the resolve and the RGBA16F hand-off, and reports that frame time beside the plain one, with the HIP-event times of the two passes.
+usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h] [--denoise]"""
 import json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))
 import numpy as np
 import pbr_amd as pbr
 
-name = sys.argv[1] if len(sys.argv) > 1 else "atrium"
-spp = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-frames = int(sys.argv[3]) if len(sys.argv) > 3 else 60
-w, h = (int(sys.argv[4]), int(sys.argv[5])) if len(sys.argv) > 5 else (1920, 1080)
+denoise = "--denoise" in sys.argv
+argv = [a for a in sys.argv if a != "--denoise"]
+name = argv[1] if len(argv) > 1 else "atrium"
+spp = int(argv[2]) if len(argv) > 2 else 1
+frames = int(argv[3]) if len(argv) > 3 else 60
+w, h = (int(argv[4]), int(argv[5])) if len(argv) > 5 else (1920, 1080)
 d = pbr.scenes.by_name("textured_atrium" if name == "textured" else "atrium")
 pt = pbr.PathTracer(0).load_scene(d)
 moving = [i for i, it in enumerate(d.instances) if i % 3 == 0 and getattr(it, "matrix", None) is None]
@@ -53,4 +58,28 @@ out = {"scene": d.name, "triangles": st["n_triangles"], "moving_instances": len(
 if first_rebuild is not None and 0 < first_rebuild < len(t_frame) - 1:     # the rebuild frame itself counts in neither
     out["ms_per_frame_before_first_rebuild"] = 1e3 * float(np.median(t_frame[:first_rebuild]))
     out["ms_per_frame_after_first_rebuild"] = 1e3 * float(np.median(t_frame[first_rebuild + 1:]))
+if denoise:      # the same loop again, the frame filtered before the hand-off: the scene keeps turning, every frame's guides are traced anew
+    t_dn, s_guides, s_filter = [], [], []
+    for k in range(frames + 5, 2 * frames + 10):
+        t0 = time.perf_counter()
+        a = 0.01 * (k + 1)
+        for i in moving:
+            pt.update_instance(i, d.instances[i].t, (math.cos(a / 2), 0.0, math.sin(a / 2), 0.0), d.instances[i].s)
+        pt.scene_refit()
+        pt.frame_begin(w, h, spp, seed=k, max_bounces=8)
+        pt.frame_add_samples(spp)
+        pt.frame_guides()
+        pt.frame_resolve()
+        pt.denoise()
+        pt.select_output(pbr.ptc.OUTPUT_DENOISED)
+        pt.sync()
+        ptr = pt.radiance_f16_device_ptr()
+        t2 = time.perf_counter()
+        if k >= frames + 10:
+            t_dn.append(t2 - t0)
+            g_s, f_s = pt.denoise_seconds()
+            s_guides.append(g_s); s_filter.append(f_s)
+    out["denoise"] = {"params": pbr.PathTracer.denoise_default_params(), "ms_per_frame": {"median": 1e3 * float(np.median(t_dn)), "min": 1e3 * float(np.min(t_dn)), "max": 1e3 * float(np.max(t_dn))},
+                      "ms_added_per_frame": 1e3 * float(np.median(t_dn) - np.median(t_frame)), "ms_guide_pass_device": 1e3 * float(np.median(s_guides)),
+                      "ms_filter_device": 1e3 * float(np.median(s_filter))}
 print(json.dumps(out))
