@@ -1,5 +1,7 @@
 // ptc_scene.cpp — host side of ptc_scene_commit: flatten instances to world space, build the 8-wide SAH BVH,
-// lay it out for the trace kernels, build the emitter table.
+// lay it out for the trace kernels, build the emitter table.  build_or_refit drives the stages of SceneBuild (flatten, triangle boxes, binary tree boxes, cost tables,
+// numbering, addresses, emission, shading records); what the skeleton and the host's share of a device refit need as well (counts and bases, indices, emissive primitives,
+// emitter table, material class, grid) are free functions with one definition each.
 //
 // Reference conventions implemented here (file:line under the reference checkout):
 //   R2  primitive concatenation        src/pbr_engine/engine/pbr/MeshBuilder.cpp:16-55
@@ -598,6 +600,23 @@ void material_sets(const std::vector<HostMaterial>& mats, std::vector<int32_t>& 
     mat_set[i] = found;
   }
 }
+// The material CLASS (texture sets and material classes) travels in the triangle record and the hit word and is what k_shade sorts by (a wave shades 64
+// hits of one class): 0 = untextured Lambert, 1 = untextured GGX, 2..6 = textured, 2 + set % 5; 7 is reserved for environment misses.
+inline uint32_t material_class(const HostMaterial& hm, int32_t set) {
+  if (set >= 0) return 2u + (uint32_t)set % 5u;
+  return (hm.metallic == 0.0f && hm.roughness >= 1.0f) ? 0u : 1u;
+}
+// units per shading record: 5, or 12 with a textured material in the scene
+uint32_t shade_stride_for(const std::vector<HostMaterial>& mats) {
+  bool any_tex = false;
+  for (const auto& m : mats) any_tex = any_tex || m.tex_color >= 0 || m.tex_normal >= 0 || m.tex_mr >= 0;
+  return any_tex ? 12u : 5u;
+}
+// model matrix times (position, 1): m[0]*x + m[1]*y + m[2]*z + m[3] — the flatten's expression, which the emitter table and the device flatten repeat bit for bit
+inline void transform_point(const Mat34& M, const float s[3], float o[3]) {
+  for (int r = 0; r < 3; ++r) o[r] = M.m[0 + r] * s[0] + M.m[4 + r] * s[1] + M.m[8 + r] * s[2] + M.m[12 + r];
+}
+constexpr float kGridCells = 65535.0f;      // node origins are 16 bits per axis on a grid over the scene box (ptc_refit_grid, grid_origin)
 void fill_materials(const std::vector<HostMaterial>& mats, const std::vector<int32_t>& mat_set, HostBuilt& B) {
   B.mats.assign(mats.size() * 16, 0.0f);
   for (size_t i = 0; i < mats.size(); ++i) {
@@ -704,115 +723,287 @@ void fill_textures_env(const std::vector<HostTexture>& texs, const HostEnv& env,
   }
 }
 
-std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes,
-                           const std::vector<HostInstance>& insts, const std::vector<HostTexture>& texs, const HostEnv& env,
-                           uint32_t toplet_budget, int bvh_builder, HostBuilt& B, bool refit) {
+// ---- what the host build, the skeleton and the refit plan share: counts and bases, indices, the emissive primitives ------------
+struct InstanceBases { std::vector<uint32_t> vb, tb; uint64_t nv = 0, nt = 0; };   // per instance: its first world vertex / primitive; the totals
+std::string count_instances(const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, InstanceBases& L) {
+  for (const auto& in : insts) {
+    L.vb.push_back((uint32_t)L.nv); L.tb.push_back((uint32_t)L.nt);
+    L.nv += meshes[(size_t)in.mesh].v.size(); L.nt += meshes[(size_t)in.mesh].idx.size() / 3;
+  }
   if (insts.empty()) return "scene_commit: no instances";
-  const bool timing = std::getenv("PTC_BUILD_TIMING") != nullptr;      // phase times of the host build / refit on stderr
-  auto tprev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "  %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - tprev).count());
-    tprev = now;
-  };
-  uint64_t nv = 0, nt = 0;
-  for (const auto& in : insts) { nv += meshes[(size_t)in.mesh].v.size(); nt += meshes[(size_t)in.mesh].idx.size() / 3; }
-  if (nt >= (1u << 28)) return "scene_commit: too many triangles";
-  std::shared_ptr<Topology> topo;
-  if (refit) {
-    topo = std::static_pointer_cast<Topology>(B.topology);
-    if (!topo || B.n_tris != nt || B.n_wverts != nv) return "scene_refit: the scene's meshes or instances changed since the commit (only transforms may)";
-    toplet_budget = topo->toplet_budget;
-  } else {
-    B = HostBuilt();
-    topo = std::make_shared<Topology>();
-    topo->toplet_budget = toplet_budget;
+  if (L.nt >= (1u << 28)) return "scene_commit: too many triangles";
+  return std::string();
+}
+// work items (instance, slice of `step` of its vertices or triangles), so that one large mesh does not serialise a pass
+struct Slice { uint32_t inst, lo, hi; };
+template <class Count> std::vector<Slice> instance_slices(const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, size_t step, Count&& count) {
+  std::vector<Slice> out;
+  for (size_t i = 0; i < insts.size(); ++i) {
+    const size_t n = count(meshes[(size_t)insts[i].mesh]);
+    for (size_t lo = 0; lo < n; lo += step) out.push_back({(uint32_t)i, (uint32_t)lo, (uint32_t)(lo + step < n ? lo + step : n)});
   }
-  // A refit flattens into temporaries and takes them over only when every position is finite: a refused refit leaves the host build as it was (the device
-  // path restores its scratch vertices likewise), so the debug getters keep describing what is being rendered.
-  std::vector<HostVertex> wverts_new;
-  std::vector<float> wbt_new;
-  std::vector<HostVertex>& wverts = refit ? wverts_new : B.wverts;
-  std::vector<float>& wbt = refit ? wbt_new : topo->wbt;   // world bitangent per vertex (vertex.glsl:35)
-  wverts.resize(nv);
-  B.n_wverts = (uint32_t)nv;
-  wbt.resize(nv * 3);
-  B.widx.resize(nt * 3);
-  B.tri_mat.resize(nt);
-  // ---- flatten ----------------------------------------------------------------------------------
-  std::vector<uint32_t> inst_vb(insts.size()), inst_tb(insts.size());
-  {
-    uint32_t vb = 0, tb = 0;
-    for (size_t i = 0; i < insts.size(); ++i) {
-      inst_vb[i] = vb; inst_tb[i] = tb;
-      vb += (uint32_t)meshes[(size_t)insts[i].mesh].v.size(); tb += (uint32_t)(meshes[(size_t)insts[i].mesh].idx.size() / 3);
+  return out;
+}
+// world vertex indices and material per primitive, and the two counts
+void fill_indices(const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const InstanceBases& L, HostBuilt& B) {
+  B.n_wverts = (uint32_t)L.nv; B.n_tris = (uint32_t)L.nt;
+  B.widx.resize(L.nt * 3);
+  B.tri_mat.resize(L.nt);
+  const std::vector<Slice> slices = instance_slices(meshes, insts, 8192, [](const HostMesh& m) { return m.idx.size() / 3; });
+  parallel_for(slices.size(), 1, [&](size_t s0, size_t s1) {
+    for (size_t si = s0; si < s1; ++si) {
+      const HostMesh& m = meshes[(size_t)insts[slices[si].inst].mesh];
+      const uint32_t vb = L.vb[slices[si].inst], tb = L.tb[slices[si].inst];
+      for (size_t k = slices[si].lo; k < slices[si].hi; ++k) {
+        for (int c = 0; c < 3; ++c) B.widx[(tb + k) * 3 + c] = vb + m.idx[k * 3 + c];
+        B.tri_mat[tb + k] = m.material;
+      }
     }
-  }
-  // work items: (instance, slice of 4096 of its vertices) and (instance, slice of its triangles), so that one large mesh does not serialise the pass
-  struct Slice { uint32_t inst, lo, hi; };
-  std::vector<Slice> vslices, tslices;
+  });
+}
+// per primitive with an emissive material, in primitive order: prim, instance, its 3 vertex indices inside the instance's mesh (RefitPlan::emit_prims)
+void emissive_prims(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const InstanceBases& L,
+                    std::vector<int32_t>& out) {
+  out.clear();
   for (size_t i = 0; i < insts.size(); ++i) {
     const HostMesh& m = meshes[(size_t)insts[i].mesh];
-    for (size_t lo = 0; lo < m.v.size(); lo += 4096) vslices.push_back({(uint32_t)i, (uint32_t)lo, (uint32_t)(lo + 4096 < m.v.size() ? lo + 4096 : m.v.size())});
-    const size_t ntm = m.idx.size() / 3;
-    for (size_t lo = 0; lo < ntm; lo += 8192) tslices.push_back({(uint32_t)i, (uint32_t)lo, (uint32_t)(lo + 8192 < ntm ? lo + 8192 : ntm)});
+    const HostMaterial& hm = mats[(size_t)m.material];
+    if (!(hm.emissive[0] > 0.0f || hm.emissive[1] > 0.0f || hm.emissive[2] > 0.0f)) continue;
+    for (size_t k = 0; k * 3 < m.idx.size(); ++k) {
+      const int32_t e[5] = {(int32_t)(L.tb[i] + k), (int32_t)i, (int32_t)m.idx[k * 3], (int32_t)m.idx[k * 3 + 1], (int32_t)m.idx[k * 3 + 2]};
+      out.insert(out.end(), e, e + 5);
+    }
   }
-  parallel_for(vslices.size(), 1, [&](size_t s0, size_t s1) {
-  for (size_t si = s0; si < s1; ++si) {
-    const HostInstance& in = insts[vslices[si].inst];
-    const HostMesh& m = meshes[(size_t)in.mesh];
-    const Mat34 M = from_matrix(in.m);
-    const uint32_t vb = inst_vb[vslices[si].inst];
-    for (size_t k = vslices[si].lo; k < vslices[si].hi; ++k) {
-      const HostVertex& s = m.v[k];
-      HostVertex& d = wverts[vb + k];
-      for (int r = 0; r < 3; ++r)   // m[0]*x + m[1]*y + m[2]*z + m[3]
-        d.position[r] = M.m[0 + r] * s.position[0] + M.m[4 + r] * s.position[1] + M.m[8 + r] * s.position[2] + M.m[12 + r];
-      mul_n(M.n, s.normal, d.normal);
-      fnormalize(d.normal);
-      mul_n(M.n, s.tangent, d.tangent);
-      fnormalize(d.tangent);
-      d.tangent[3] = s.tangent[3];
-      {
-        float cr[3], sc3[3], bt[3];
-        fcross(s.normal, s.tangent, cr);
-        sc3[0] = cr[0] * s.tangent[3]; sc3[1] = cr[1] * s.tangent[3]; sc3[2] = cr[2] * s.tangent[3];
-        mul_n(M.n, sc3, bt);
-        fnormalize(bt);
-        wbt[(size_t)(vb + k) * 3 + 0] = bt[0]; wbt[(size_t)(vb + k) * 3 + 1] = bt[1]; wbt[(size_t)(vb + k) * 3 + 2] = bt[2];
+}
+// The emitter table (original primitive order; power pmf / cdf) from the emissive primitives alone, each vertex taken through its instance's matrix with the flatten's
+// expression.  Returns the number of emitters.  prim_light (sized by the caller, -1 everywhere) takes the emitter index of every primitive.  committed != nullptr: a refit
+// on the device, which cannot change the set of emitters — -1 when the set is not the committed one.
+int emitters_from_prims(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const std::vector<int32_t>& emit_prims,
+                        const HostBuilt* committed, std::vector<int32_t>* prim_light, std::vector<float>& lights, std::vector<float>& cdf) {
+  lights.clear(); cdf.clear();
+  std::vector<float> weight;
+  int32_t cached_inst = -1;
+  Mat34 M{};
+  for (size_t j = 0; j * 5 < emit_prims.size(); ++j) {
+    const int32_t* e = &emit_prims[j * 5];
+    const uint32_t p = (uint32_t)e[0];
+    const HostMesh& mesh = meshes[(size_t)insts[(size_t)e[1]].mesh];
+    const HostMaterial& m = mats[(size_t)mesh.material];
+    if (e[1] != cached_inst) { M = from_matrix(insts[(size_t)e[1]].m); cached_inst = e[1]; }
+    float w[3][3];
+    for (int c = 0; c < 3; ++c) transform_point(M, mesh.v[(size_t)e[2 + c]].position, w[c]);
+    const float *a = w[0], *b = w[1], *c = w[2];
+    const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    float cr[3];
+    fcross(e1, e2, cr);
+    const float len = sqrtf(fdot(cr, cr));
+    const float area = 0.5f * len;
+    const float lum = fmaf(m.emissive[2], 0.0722f, fmaf(m.emissive[1], 0.7152f, m.emissive[0] * 0.2126f));
+    const float wgt = area * lum;
+    const bool is_light = wgt > 0.0f;
+    if (committed && is_light != (committed->prim_light[p] >= 0)) return -1;
+    if (!is_light) continue;
+    if (committed && committed->prim_light[p] != (int32_t)weight.size()) return -1;
+    if (prim_light) (*prim_light)[p] = (int32_t)weight.size();
+    const float il = 1.0f / len;
+    weight.push_back(wgt);
+    const float rec[20] = {a[0], a[1], a[2], area, e1[0], e1[1], e1[2], 0.0f /*pmf*/, e2[0], e2[1], e2[2], 0.0f,
+                           cr[0] * il, cr[1] * il, cr[2] * il, 0.0f, m.emissive[0], m.emissive[1], m.emissive[2], 0.0f};
+    lights.insert(lights.end(), rec, rec + 20);
+  }
+  if (committed && weight.size() != committed->n_lights) return -1;
+  float total = 0.0f;
+  for (float wv : weight) total += wv;
+  float run = 0.0f;
+  cdf.resize(weight.size());
+  for (size_t i = 0; i < weight.size(); ++i) {
+    run += weight[i];
+    cdf[i] = run / total;
+    lights[i * 20 + 7] = weight[i] / total;
+  }
+  if (!cdf.empty()) cdf.back() = 1.0f;
+  if (cdf.empty()) cdf.push_back(1.0f);
+  if (lights.empty()) lights.assign(20, 0.0f);
+  return (int)weight.size();
+}
+// a commit or a host refit (which is free to change the set of emitters): the table, and the emitter index of every primitive
+void fill_emitters(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const InstanceBases& L, HostBuilt& B) {
+  std::vector<int32_t> emit_prims;
+  emissive_prims(mats, meshes, insts, L, emit_prims);
+  B.prim_light.assign(B.n_tris, -1);
+  B.n_lights = (uint32_t)emitters_from_prims(mats, meshes, insts, emit_prims, nullptr, &B.prim_light, B.lights, B.cdf);
+}
+
+// ---- hierarchy --------------------------------------------------------------------------------------
+// Binary tree by binned surface-area splits (down to single triangles) → 8-wide collapse by dynamic programming over
+// the surface-area cost (Ylitie, Karras, Laine 2017, sec. 3.1): for a binary node n with box half-area A_n and P_n
+// triangles, C(n,i) = least cost of representing its subtree by at most i roots (a root = a leaf or an 8-wide node):
+//   C(n,1) = min(C_leaf, C_int)   C(n,i) = min(C_dist(n,i), C(n,i-1))   C_dist(n,j) = min_k C(left,k) + C(right,j-k)
+//   C_leaf = A_n·P_n·kCostPrim if P_n <= kLeafMax else inf            C_int = C_dist(n,8) + A_n·kCostNode
+// ties: leaf over interior, fewer roots over more, smallest k.  A node's children are the roots of C_dist(n,8), left to
+// right.  The (<= 8) children are then placed into the node's 8 SLOTS so that a
+// child in slot s lies in octant s of the node (bit k of s set = towards +axis k): repeatedly the (child, free
+// slot) pair with the largest  (+-)dx + (+-)dy + (+-)dz,  d = child centre - node centre, ties to the lowest child
+// then the lowest slot.  A ray then orders the slots by its direction signs alone (descending slot ^ octant), with
+// no per-child distance sort.
+//
+// Storage: ONE array of 16-byte units holding 64-byte nodes and 48-byte triangle records; the unit index is the address the
+// kernels use.  A node's origin is kept to 16 bits per axis on a grid over the scene box (org = scene_lo + oq·step, rounded
+// down), child boxes are quantised to 8 bits against that origin:
+//   w0      oq.x | oq.y<<16            w1   oq.z | ex<<16 | ey<<24       w2   ez | imask<<8 | lmask<<16 | two<<24
+//   w3      block: unit address of this node's children block            plane = org + q · 2^(e-127)
+//   w4,5    qlo.x slots 0-3 / 4-7      w6,7  qlo.y     w8,9   qlo.z
+//   w10,11  qhi.x                      w12,13 qhi.y    w14,15 qhi.z               (empty slot: qlo 255, qhi 0)
+// imask / lmask: slots holding an interior / a leaf child; two: leaf slots with 2 triangles.  A children block starts on a
+// 64-byte boundary and holds the interior children (nodes, 4 units each, slot order) followed by the triangles of the leaf
+// children (3 units each, slot order): child node = block + 4·popcount(imask below its slot), triangle = block +
+// 4·popcount(imask) + 3·(number of triangles in lower leaf slots).  The root is the node at unit 0.  64-byte alignment of the
+// nodes is what lets four adjacent lanes fetch one node as one contiguous 64-byte piece (a quarter of the address-processing
+// cost of four unrelated 16-byte gathers: tools/gather_bench.hip).
+// Layout: blocks breadth-first until `toplet_budget` 64-byte records exist (the trace kernels stage that prefix in LDS),
+// then depth-first.
+
+// slot_of[i]: the slot of child i of n (see above)
+void assign_slots(const WChild* kid, int n, int* slot_of) {
+  Box nb = empty_box();
+  for (int i = 0; i < n; ++i) grow(nb, kid[i].box);
+  float d[kWide][3];
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) d[i][k] = 0.5f * (kid[i].box.lo[k] + kid[i].box.hi[k]) - 0.5f * (nb.lo[k] + nb.hi[k]);
+  bool child_done[kWide] = {false}, slot_used[kWide] = {false};
+  for (int round = 0; round < n; ++round) {
+    int bi = -1, bs = -1; float bsc = 0.0f;
+    for (int i = 0; i < n; ++i) {
+      if (child_done[i]) continue;
+      for (int sl = 0; sl < kWide; ++sl) {
+        if (slot_used[sl]) continue;
+        const float sc = ((sl & 1) ? d[i][0] : -d[i][0]) + ((sl & 2) ? d[i][1] : -d[i][1]) + ((sl & 4) ? d[i][2] : -d[i][2]);
+        if (bi < 0 || sc > bsc) { bi = i; bs = sl; bsc = sc; }
       }
-      d.texcoord[0] = s.texcoord[0];
-      d.texcoord[1] = s.texcoord[1];
     }
+    child_done[bi] = true; slot_used[bs] = true; slot_of[bi] = bs;
   }
-  });
-  parallel_for(tslices.size(), 1, [&](size_t s0, size_t s1) {
-  for (size_t si = s0; si < s1; ++si) {
-    const HostInstance& in = insts[tslices[si].inst];
-    const HostMesh& m = meshes[(size_t)in.mesh];
-    const uint32_t vb = inst_vb[tslices[si].inst], tb = inst_tb[tslices[si].inst];
-    for (size_t k = tslices[si].lo; k < tslices[si].hi; ++k) {
-      for (int c = 0; c < 3; ++c) B.widx[(tb + k) * 3 + c] = vb + m.idx[k * 3 + c];
-      B.tri_mat[tb + k] = m.material;
+}
+Wide make_wide(const WChild* kid, int n) {
+  int slot_of[kWide];
+  assign_slots(kid, n, slot_of);
+  Wide w;
+  w.n = n;
+  for (int sl = 0; sl < kWide; ++sl) w.used[sl] = false;
+  for (int i = 0; i < n; ++i) { w.slot[slot_of[i]] = kid[i]; w.used[slot_of[i]] = true; }
+  return w;
+}
+// 8-bit quantisation of the children's [lo,hi] on one axis against the node's [org, nhi]: scale 2^(e-127)
+// is the smallest power of two with (nhi-org)/scale <= 255; lower planes floor, upper planes ceil, each
+// nudged until the float expression org + q*scale brackets the exact plane.
+inline float pow2_biased(uint32_t e) { const uint32_t u = e << 23; float f; std::memcpy(&f, &u, 4); return f; }
+void quantize_axis(const float* clo, const float* chi, int nk, float org, float nhi, uint32_t& e_out, uint32_t* qlo, uint32_t* qhi) {
+  const float f = (nhi - org) / 255.0f;
+  uint32_t u; std::memcpy(&u, &f, 4);
+  uint32_t e = (u >> 23) & 255u;
+  if (u & 0x007fffffu) e += 1u;
+  if (e < 1u) e = 1u;
+  for (;; ++e) {
+    const float sc = pow2_biased(e);
+    bool ok = true;
+    for (int i = 0; i < nk && ok; ++i) {
+      float fl = std::floor((clo[i] - org) / sc);
+      if (fl < 0.0f) fl = 0.0f;
+      if (fl > 255.0f) fl = 255.0f;
+      int q = (int)fl;
+      while (q > 0 && org + (float)q * sc > clo[i]) --q;
+      qlo[i] = (uint32_t)q;
+      float ce = std::ceil((chi[i] - org) / sc);
+      if (ce < 0.0f) ce = 0.0f;
+      if (ce > 255.0f) { ok = false; break; }
+      int q2 = (int)ce;
+      while (q2 < 255 && org + (float)q2 * sc < chi[i]) ++q2;
+      if (org + (float)q2 * sc < chi[i]) { ok = false; break; }
+      qhi[i] = (uint32_t)q2;
     }
+    if (ok) break;
   }
-  });
-  lap("flatten");
-  const uint32_t n = (uint32_t)nt;
-  B.n_tris = n;
-  // NaN / Inf anywhere in the flattened positions (bad vertices or a bad instance matrix) is an error: the builder
-  // computes bin indices from them
-  for (const auto& v : wverts)
-    if (!(std::isfinite(v.position[0]) && std::isfinite(v.position[1]) && std::isfinite(v.position[2]))) return "scene_commit: non-finite vertex position after the instance transform";
-  if (refit) { B.wverts.swap(wverts_new); topo->wbt.swap(wbt_new); }
+  e_out = e;
+}
+// a node's origin on the 16-bit scene grid, rounded down: the largest q with fmaf(q, step, lo) <= the node's lower bound
+uint32_t grid_origin(float nlo, float lo, float step) {
+  float fq = std::floor((nlo - lo) / step);
+  if (fq < 0.0f) fq = 0.0f;
+  if (fq > kGridCells) fq = kGridCells;
+  uint32_t q16 = (uint32_t)fq;
+  while (q16 > 0u && fmaf((float)q16, step, lo) > nlo) --q16;
+  return q16;
+}
+// surface-area cost of a node (ptc_stats.bvh_sa_cost): per used child slot half_area(child) / half_area(scene box at build time), a two-triangle leaf twice, each term
+// truncated to 2^-20 and summed as an integer — the terms and the sum k_refit_nodes forms on the device (pt_refit.hip)
+uint64_t sa_cost_of(const Wide& w, float scene_area) {
+  uint64_t cost = 0;
+  if (scene_area > 0.0f)
+    for (int sl = 0; sl < kWide; ++sl) {
+      if (!w.used[sl]) continue;
+      const uint64_t term = (uint64_t)((box_half_area(w.slot[sl].box) / scene_area) * PTC_SA_COST_ONE);
+      cost += (w.slot[sl].leaf && w.slot[sl].hi - w.slot[sl].lo + 1u == 2u) ? 2u * term : term;
+    }
+  return cost;
+}
+
+struct Dp { float c[8]; uint8_t leaf1, same[8], k[9]; };   // collapse cost table of a binary node.  c[i], same[i]: i = 1..7; k[j]: j = 2..8
+inline int min7(int k) { return k > 7 ? 7 : k; }
+
+// The state of one host build or refit; its member functions are the stages build_or_refit runs, in the order they stand here.
+struct SceneBuild {
+  const std::vector<HostMaterial>& mats;
+  const std::vector<HostMesh>& meshes;
+  const std::vector<HostInstance>& insts;
+  HostBuilt& B;
+  Topology& T;                               // ord: position in BVH order → original primitive id; order / wide / child_base: per 8-wide node, its binary node, children, first interior child
+  InstanceBases L;
+  std::vector<int32_t> mat_set, set_tex;     // set of every material (-1: untextured); 3 texture ids per set
+  std::vector<Box> tbox;                     // box of every primitive
+  Box sb;                                    // scene box
+  std::vector<Box> radix_box;                // box of every binary node
+  std::vector<Dp> dp;
+
+  // ---- flatten: world position / normal / tangent (R3, R4) and bitangent (vertex.glsl:35) of every vertex ---------------------------
+  void flatten(std::vector<HostVertex>& wverts, std::vector<float>& wbt) const {
+    wverts.resize(L.nv);
+    wbt.resize(L.nv * 3);
+    const std::vector<Slice> slices = instance_slices(meshes, insts, 4096, [](const HostMesh& m) { return m.v.size(); });
+    parallel_for(slices.size(), 1, [&](size_t s0, size_t s1) {
+      for (size_t si = s0; si < s1; ++si) {
+        const HostInstance& in = insts[slices[si].inst];
+        const HostMesh& m = meshes[(size_t)in.mesh];
+        const Mat34 M = from_matrix(in.m);
+        const uint32_t vb = L.vb[slices[si].inst];
+        for (size_t k = slices[si].lo; k < slices[si].hi; ++k) {
+          const HostVertex& s = m.v[k];
+          HostVertex& d = wverts[vb + k];
+          transform_point(M, s.position, d.position);
+          mul_n(M.n, s.normal, d.normal);
+          fnormalize(d.normal);
+          mul_n(M.n, s.tangent, d.tangent);
+          fnormalize(d.tangent);
+          d.tangent[3] = s.tangent[3];
+          float cr[3], sc3[3], bt[3];
+          fcross(s.normal, s.tangent, cr);
+          sc3[0] = cr[0] * s.tangent[3]; sc3[1] = cr[1] * s.tangent[3]; sc3[2] = cr[2] * s.tangent[3];
+          mul_n(M.n, sc3, bt);
+          fnormalize(bt);
+          wbt[(size_t)(vb + k) * 3 + 0] = bt[0]; wbt[(size_t)(vb + k) * 3 + 1] = bt[1]; wbt[(size_t)(vb + k) * 3 + 2] = bt[2];
+          d.texcoord[0] = s.texcoord[0];
+          d.texcoord[1] = s.texcoord[1];
+        }
+      }
+    });
+  }
+
   // ---- triangle boxes, scene bounds ------------------------------------------------------------------
-  std::vector<Box> tbox(n);
-  Box sb = empty_box();
-  {
+  void triangle_boxes() {
+    tbox.resize(B.n_tris);
+    sb = empty_box();
     std::vector<Box> part(64, empty_box());          // min / max are exact and order-independent: the merge gives the sequential scene box
     std::atomic<unsigned> next_part{0};
-    parallel_for(n, 16384, [&](size_t p0, size_t p1) {
+    parallel_for(B.n_tris, 16384, [&](size_t p0, size_t p1) {
       Box mine = empty_box();
       for (size_t p = p0; p < p1; ++p) {
         Box b = empty_box();
@@ -827,169 +1018,14 @@ std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vec
     });
     for (const Box& b : part) if (b.lo[0] <= b.hi[0]) grow(sb, b);
   }
-  lap("triangle boxes");
-  float diag = sb.hi[0] - sb.lo[0];
-  if (sb.hi[1] - sb.lo[1] > diag) diag = sb.hi[1] - sb.lo[1];
-  if (sb.hi[2] - sb.lo[2] > diag) diag = sb.hi[2] - sb.lo[2];
-  B.ray_eps = 1e-4f * (diag > 1e-6f ? diag : 1e-6f);
-  std::vector<uint32_t>& ord = topo->ord;        // position in BVH order → original primitive id (partitioned by the build)
-  if (!refit) { ord.resize(n); for (uint32_t p = 0; p < n; ++p) ord[p] = p; }
-  // ---- texture sets and material classes ------------------------------------------------------------------------------------
-  // A texture SET is a distinct (colour, normal, metal-rough) triple of texture ids among the materials that have a texture, numbered in
-  // material order.  The material CLASS travels in the triangle record and the hit word and is what k_shade sorts by (a wave shades 64
-  // hits of one class): 0 = untextured Lambert, 1 = untextured GGX, 2..6 = textured, 2 + set % 5; 7 is reserved for environment misses.
-  std::vector<int32_t> mat_set, set_tex;     // set of every material (-1: untextured); 3 texture ids per set
-  material_sets(mats, mat_set, set_tex);
-  auto material_class = [&](int32_t mi) -> uint32_t {
-    const HostMaterial& hm = mats[(size_t)mi];
-    if (mat_set[(size_t)mi] >= 0) return 2u + (uint32_t)mat_set[(size_t)mi] % 5u;
-    return (hm.metallic == 0.0f && hm.roughness >= 1.0f) ? 0u : 1u;
-  };
-  // triangle record of sorted position i: (v0, prim id) (e1, class) (e2, 0); emitted below in node order
-  auto tri_record = [&](uint32_t i, float* o) {
-    const uint32_t p = ord[i];
-    const float* a = B.wverts[B.widx[p * 3 + 0]].position;
-    const float* b = B.wverts[B.widx[p * 3 + 1]].position;
-    const float* c = B.wverts[B.widx[p * 3 + 2]].position;
-    const uint32_t cls = material_class(B.tri_mat[p]);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; std::memcpy(&o[3], &p, 4);
-    o[4] = b[0] - a[0]; o[5] = b[1] - a[1]; o[6] = b[2] - a[2]; std::memcpy(&o[7], &cls, 4);
-    o[8] = c[0] - a[0]; o[9] = c[1] - a[1]; o[10] = c[2] - a[2]; o[11] = 0.0f;
-  };
-  // ---- hierarchy --------------------------------------------------------------------------------------
-  // Binary tree by binned surface-area splits (down to single triangles) → 8-wide collapse by dynamic programming over
-  // the surface-area cost (Ylitie, Karras, Laine 2017, sec. 3.1): for a binary node n with box half-area A_n and P_n
-  // triangles, C(n,i) = least cost of representing its subtree by at most i roots (a root = a leaf or an 8-wide node):
-  //   C(n,1) = min(C_leaf, C_int)   C(n,i) = min(C_dist(n,i), C(n,i-1))   C_dist(n,j) = min_k C(left,k) + C(right,j-k)
-  //   C_leaf = A_n·P_n·kCostPrim if P_n <= kLeafMax else inf            C_int = C_dist(n,8) + A_n·kCostNode
-  // ties: leaf over interior, fewer roots over more, smallest k.  A node's children are the roots of C_dist(n,8), left to
-  // right.  The (<= 8) children are then placed into the node's 8 SLOTS so that a
-  // child in slot s lies in octant s of the node (bit k of s set = towards +axis k): repeatedly the (child, free
-  // slot) pair with the largest  (+-)dx + (+-)dy + (+-)dz,  d = child centre - node centre, ties to the lowest child
-  // then the lowest slot.  A ray then orders the slots by its direction signs alone (descending slot ^ octant), with
-  // no per-child distance sort.
-  //
-  // Storage: ONE array of 16-byte units holding 64-byte nodes and 48-byte triangle records; the unit index is the address the
-  // kernels use.  A node's origin is kept to 16 bits per axis on a grid over the scene box (org = scene_lo + oq·step, rounded
-  // down), child boxes are quantised to 8 bits against that origin:
-  //   w0      oq.x | oq.y<<16            w1   oq.z | ex<<16 | ey<<24       w2   ez | imask<<8 | lmask<<16 | two<<24
-  //   w3      block: unit address of this node's children block            plane = org + q · 2^(e-127)
-  //   w4,5    qlo.x slots 0-3 / 4-7      w6,7  qlo.y     w8,9   qlo.z
-  //   w10,11  qhi.x                      w12,13 qhi.y    w14,15 qhi.z               (empty slot: qlo 255, qhi 0)
-  // imask / lmask: slots holding an interior / a leaf child; two: leaf slots with 2 triangles.  A children block starts on a
-  // 64-byte boundary and holds the interior children (nodes, 4 units each, slot order) followed by the triangles of the leaf
-  // children (3 units each, slot order): child node = block + 4·popcount(imask below its slot), triangle = block +
-  // 4·popcount(imask) + 3·(number of triangles in lower leaf slots).  The root is the node at unit 0.  64-byte alignment of the
-  // nodes is what lets four adjacent lanes fetch one node as one contiguous 64-byte piece (a quarter of the address-processing
-  // cost of four unrelated 16-byte gathers: tools/gather_bench.hip).
-  // Layout: blocks breadth-first until `toplet_budget` 64-byte records exist (the trace kernels stage that prefix in LDS),
-  // then depth-first.
-  std::vector<SplitNode>& radix = topo->radix;
-  std::vector<Box> radix_box;
-  struct Dp { float c[8]; uint8_t leaf1, same[8], k[9]; };   // c[i], same[i]: i = 1..7; k[j]: j = 2..8
-  std::vector<Dp> dp;
-  auto link_box = [&](int32_t link) { return link < 0 ? tbox[ord[(size_t)~link]] : radix_box[(size_t)link]; };
-  auto dp_cost = [&](int32_t link, int i) { return link < 0 ? box_half_area(link_box(link)) * 1.0f * kCostPrim : dp[(size_t)link].c[i]; };
-  auto min7 = [](int k) { return k > 7 ? 7 : k; };
-  auto assign_slots = [&](const WChild* kid, int n, int* slot_of) {
-    Box nb = empty_box();
-    for (int i = 0; i < n; ++i) grow(nb, kid[i].box);
-    float d[kWide][3];
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < 3; ++k) d[i][k] = 0.5f * (kid[i].box.lo[k] + kid[i].box.hi[k]) - 0.5f * (nb.lo[k] + nb.hi[k]);
-    bool child_done[kWide] = {false}, slot_used[kWide] = {false};
-    for (int round = 0; round < n; ++round) {
-      int bi = -1, bs = -1; float bsc = 0.0f;
-      for (int i = 0; i < n; ++i) {
-        if (child_done[i]) continue;
-        for (int sl = 0; sl < kWide; ++sl) {
-          if (slot_used[sl]) continue;
-          const float sc = ((sl & 1) ? d[i][0] : -d[i][0]) + ((sl & 2) ? d[i][1] : -d[i][1]) + ((sl & 4) ? d[i][2] : -d[i][2]);
-          if (bi < 0 || sc > bsc) { bi = i; bs = sl; bsc = sc; }
-        }
-      }
-      child_done[bi] = true; slot_used[bs] = true; slot_of[bi] = bs;
-    }
-  };
-  // the roots of the best forest of at most i roots below `link`, appended left to right
-  struct ForestJob { int32_t link; int i; };
-  auto forest = [&](int32_t link0, int i0, WChild* kid, int& n) {
-    ForestJob stk[64]; int sp = 0;
-    stk[sp++] = {link0, i0};
-    while (sp > 0) {
-      const ForestJob j = stk[--sp];
-      WChild c;
-      c.box = link_box(j.link);
-      if (j.link < 0) { c.leaf = true; c.lo = c.hi = (uint32_t)~j.link; c.radix = -1; kid[n++] = c; continue; }
-      const SplitNode& r = radix[(size_t)j.link]; const Dp& d = dp[(size_t)j.link];
-      int i = j.i;
-      while (i > 1 && d.same[i]) --i;
-      if (i == 1) { c.leaf = d.leaf1 != 0; c.lo = r.lo; c.hi = r.hi; c.radix = j.link; kid[n++] = c; continue; }
-      const int kk = d.k[i];
-      stk[sp++] = {r.right, min7(i - kk)};      // left first
-      stk[sp++] = {r.left, min7(kk)};
-    }
-  };
-  auto make_wide = [&](const WChild* kid, int n) {
-    int slot_of[kWide];
-    assign_slots(kid, n, slot_of);
-    Wide w;
-    w.n = n;
-    for (int sl = 0; sl < kWide; ++sl) w.used[sl] = false;
-    for (int i = 0; i < n; ++i) { w.slot[slot_of[i]] = kid[i]; w.used[slot_of[i]] = true; }
-    return w;
-  };
-  auto expand = [&](int32_t r) {
-    WChild kid[kWide];
-    int n = 0;
-    const int kk = dp[(size_t)r].k[8];
-    forest(radix[(size_t)r].left, min7(kk), kid, n);
-    forest(radix[(size_t)r].right, min7(8 - kk), kid, n);
-    return make_wide(kid, n);
-  };
-  // 8-bit quantisation of the children's [lo,hi] on one axis against the node's [org, nhi]: scale 2^(e-127)
-  // is the smallest power of two with (nhi-org)/scale <= 255; lower planes floor, upper planes ceil, each
-  // nudged until the float expression org + q*scale brackets the exact plane.
-  auto pow2_biased = [](uint32_t e) { const uint32_t u = e << 23; float f; std::memcpy(&f, &u, 4); return f; };
-  auto quantize_axis = [&](const float* clo, const float* chi, int nk, float org, float nhi, uint32_t& e_out, uint32_t* qlo, uint32_t* qhi) {
-    const float f = (nhi - org) / 255.0f;
-    uint32_t u; std::memcpy(&u, &f, 4);
-    uint32_t e = (u >> 23) & 255u;
-    if (u & 0x007fffffu) e += 1u;
-    if (e < 1u) e = 1u;
-    for (;; ++e) {
-      const float sc = pow2_biased(e);
-      bool ok = true;
-      for (int i = 0; i < nk && ok; ++i) {
-        float fl = std::floor((clo[i] - org) / sc);
-        if (fl < 0.0f) fl = 0.0f;
-        if (fl > 255.0f) fl = 255.0f;
-        int q = (int)fl;
-        while (q > 0 && org + (float)q * sc > clo[i]) --q;
-        qlo[i] = (uint32_t)q;
-        float ce = std::ceil((chi[i] - org) / sc);
-        if (ce < 0.0f) ce = 0.0f;
-        if (ce > 255.0f) { ok = false; break; }
-        int q2 = (int)ce;
-        while (q2 < 255 && org + (float)q2 * sc < chi[i]) ++q2;
-        if (org + (float)q2 * sc < chi[i]) { ok = false; break; }
-        qhi[i] = (uint32_t)q2;
-      }
-      if (ok) break;
-    }
-    e_out = e;
-  };
-  std::vector<Slot>& order = topo->order;              // node index → radix node (or -1 for the single-triangle special case)
-  std::vector<Wide>& wide = topo->wide;                // node index → its children
-  std::vector<uint32_t>& child_base = topo->child_base; // node index → index of its first interior child
-  std::vector<uint32_t>& block_order = topo->block_order; // node indices in the order their children blocks were allocated
-  // boxes of all radix nodes, bottom-up (iterative post-order)
-  // radix nodes are numbered parents-first, so descending index order is a valid post-order; the subtrees the build handed to the pool are disjoint index
+
+  // ---- binary tree boxes, bottom-up ---------------------------------------------------------------------
+  // binary (radix) nodes are numbered parents-first, so descending index order is a valid post-order; the subtrees the build handed to the pool are disjoint index
   // ranges behind the top's, so they go first, in parallel, and the top last
-  auto bottom_up = [&](auto&& visit) {
-    const std::vector<uint32_t>& sf = topo->sub_first;
-    size_t top_end = radix.size();
-    if (sf.size() >= 2 && sf.back() == radix.size()) {
+  template <class Visit> void bottom_up(Visit&& visit) const {
+    const std::vector<uint32_t>& sf = T.sub_first;
+    size_t top_end = T.radix.size();
+    if (sf.size() >= 2 && sf.back() == T.radix.size()) {
       parallel_for(sf.size() - 1, 1, [&](size_t t0, size_t t1) {
         for (size_t t = t0; t < t1; ++t)
           for (size_t idx = sf[t + 1]; idx-- > sf[t];) visit(idx);
@@ -997,40 +1033,35 @@ std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vec
       top_end = sf[0];
     }
     for (size_t idx = top_end; idx-- > 0;) visit(idx);
-  };
-  auto compute_radix_boxes = [&]() {
-    radix_box.assign(radix.size(), empty_box());
+  }
+  Box link_box(int32_t link) const { return link < 0 ? tbox[T.ord[(size_t)~link]] : radix_box[(size_t)link]; }
+  void compute_radix_boxes() {
+    radix_box.assign(T.radix.size(), empty_box());
     bottom_up([&](size_t idx) {
-      const SplitNode& r = radix[idx];
-      Box b = r.left < 0 ? tbox[ord[(size_t)~r.left]] : radix_box[(size_t)r.left];
-      grow(b, r.right < 0 ? tbox[ord[(size_t)~r.right]] : radix_box[(size_t)r.right]);
+      const SplitNode& r = T.radix[idx];
+      Box b = link_box(r.left);
+      grow(b, link_box(r.right));
       radix_box[idx] = b;
     });
-  };
-  if (refit) {    // same tree, same slots: only the boxes of the children follow the moved triangles
-    compute_radix_boxes();
-    parallel_for(wide.size(), 2048, [&](size_t i0, size_t i1) {
+  }
+  // a refit — same tree, same slots: only the boxes of the children follow the moved triangles
+  void refit_child_boxes() {
+    parallel_for(T.wide.size(), 2048, [&](size_t i0, size_t i1) {
       for (size_t i = i0; i < i1; ++i)
         for (int sl = 0; sl < kWide; ++sl) {
-          if (!wide[i].used[sl]) continue;
-          WChild& ch = wide[i].slot[sl];
-          ch.box = ch.radix >= 0 ? radix_box[(size_t)ch.radix] : tbox[ord[ch.lo]];
+          if (!T.wide[i].used[sl]) continue;
+          WChild& ch = T.wide[i].slot[sl];
+          ch.box = ch.radix >= 0 ? radix_box[(size_t)ch.radix] : tbox[T.ord[ch.lo]];
         }
     });
-  } else if (n == 1) {   // a single triangle: two identical leaf children (mirrors the binary special case)
-    WChild kid[2];
-    for (int k = 0; k < 2; ++k) { kid[k].leaf = true; kid[k].lo = kid[k].hi = 0; kid[k].radix = -1; kid[k].box = tbox[0]; }
-    const Wide w = make_wide(kid, 2);
-    order.push_back({-1, 0}); wide.push_back(w); child_base.push_back(1); block_order.push_back(0);
-  } else {
-    build_split_tree(tbox, ord, radix, bvh_builder == 1, topo->sub_first);
-    lap("  binary tree");
-    compute_radix_boxes();
-    lap("  binary boxes");
-    // cost tables, bottom-up: radix nodes are numbered parents-first, so descending index order is a valid post-order
-    dp.assign(radix.size(), Dp());
+  }
+
+  // ---- cost tables, bottom-up ---------------------------------------------------------------------------
+  float dp_cost(int32_t link, int i) const { return link < 0 ? box_half_area(link_box(link)) * 1.0f * kCostPrim : dp[(size_t)link].c[i]; }
+  void cost_tables() {
+    dp.assign(T.radix.size(), Dp());
     bottom_up([&](size_t idx) {
-      const SplitNode& r = radix[idx];
+      const SplitNode& r = T.radix[idx];
       Dp& d = dp[idx];
       float dist[9];
       for (int j = 2; j <= 8; ++j) {
@@ -1050,206 +1081,280 @@ std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vec
         if (dist[i] < d.c[i - 1]) { d.c[i] = dist[i]; d.same[i] = 0; } else { d.c[i] = d.c[i - 1]; d.same[i] = 1; }
       }
     });
-    lap("  collapse cost tables");
-    auto number = [&](int32_t r, uint32_t depth) {
-      order.push_back({r, depth});
-      wide.push_back(expand(r));
-      child_base.push_back(0xffffffffu);
-    };
-    // allocate the interior children of node `idx` as one consecutive block, in slot order
-    auto alloc_children = [&](uint32_t idx) {
-      child_base[idx] = (uint32_t)order.size();
-      block_order.push_back(idx);
-      const Wide w = wide[idx];
-      for (int sl = 0; sl < kWide; ++sl)
-        if (w.used[sl] && !w.slot[sl].leaf) number(w.slot[sl].radix, order[idx].depth + 1);
-    };
+  }
+
+  // ---- wide-node numbering and layout order ---------------------------------------------------------------
+  // the roots of the best forest of at most i roots below `link`, appended left to right
+  void forest(int32_t link0, int i0, WChild* kid, int& n) const {
+    struct ForestJob { int32_t link; int i; };
+    ForestJob stk[64]; int sp = 0;
+    stk[sp++] = {link0, i0};
+    while (sp > 0) {
+      const ForestJob j = stk[--sp];
+      WChild c;
+      c.box = link_box(j.link);
+      if (j.link < 0) { c.leaf = true; c.lo = c.hi = (uint32_t)~j.link; c.radix = -1; kid[n++] = c; continue; }
+      const SplitNode& r = T.radix[(size_t)j.link]; const Dp& d = dp[(size_t)j.link];
+      int i = j.i;
+      while (i > 1 && d.same[i]) --i;
+      if (i == 1) { c.leaf = d.leaf1 != 0; c.lo = r.lo; c.hi = r.hi; c.radix = j.link; kid[n++] = c; continue; }
+      const int kk = d.k[i];
+      stk[sp++] = {r.right, min7(i - kk)};      // left first
+      stk[sp++] = {r.left, min7(kk)};
+    }
+  }
+  Wide expand(int32_t r) const {
+    WChild kid[kWide];
+    int n = 0;
+    const int kk = dp[(size_t)r].k[8];
+    forest(T.radix[(size_t)r].left, min7(kk), kid, n);
+    forest(T.radix[(size_t)r].right, min7(8 - kk), kid, n);
+    return make_wide(kid, n);
+  }
+  void number(int32_t r, uint32_t depth) {
+    T.order.push_back({r, depth});
+    T.wide.push_back(expand(r));
+    T.child_base.push_back(0xffffffffu);
+  }
+  // allocate the interior children of node `idx` as one consecutive block, in slot order
+  void alloc_children(uint32_t idx) {
+    T.child_base[idx] = (uint32_t)T.order.size();
+    T.block_order.push_back(idx);
+    const Wide w = T.wide[idx];
+    for (int sl = 0; sl < kWide; ++sl)
+      if (w.used[sl] && !w.slot[sl].leaf) number(w.slot[sl].radix, T.order[idx].depth + 1);
+  }
+  void number_nodes() {
     number(0, 0);
     size_t head = 0;
-    for (; head < order.size() && order.size() < toplet_budget; ++head) alloc_children((uint32_t)head);   // breadth-first top
-    {
-      std::vector<uint32_t> stack;                                                   // depth-first remainder
-      const size_t n_top = order.size();
-      for (size_t i = head; i < n_top; ++i) {
-        stack.push_back((uint32_t)i);
-        while (!stack.empty()) {
-          const uint32_t idx = stack.back();
-          stack.pop_back();
-          alloc_children(idx);
-          int k = 0;
-          for (int sl = 0; sl < kWide; ++sl) k += (wide[idx].used[sl] && !wide[idx].slot[sl].leaf) ? 1 : 0;
-          for (int j = k - 1; j >= 0; --j) stack.push_back(child_base[idx] + (uint32_t)j);   // first child on top
-        }
+    for (; head < T.order.size() && T.order.size() < T.toplet_budget; ++head) alloc_children((uint32_t)head);   // breadth-first top
+    std::vector<uint32_t> stack;                                                                               // depth-first remainder
+    const size_t n_top = T.order.size();
+    for (size_t i = head; i < n_top; ++i) {
+      stack.push_back((uint32_t)i);
+      while (!stack.empty()) {
+        const uint32_t idx = stack.back();
+        stack.pop_back();
+        alloc_children(idx);
+        int k = 0;
+        for (int sl = 0; sl < kWide; ++sl) k += (T.wide[idx].used[sl] && !T.wide[idx].slot[sl].leaf) ? 1 : 0;
+        for (int j = k - 1; j >= 0; --j) stack.push_back(T.child_base[idx] + (uint32_t)j);   // first child on top
       }
     }
   }
-  lap(refit ? "refit boxes" : "tree build + collapse");
-  // ---- unit addresses: root at 0, then the children blocks in allocation order, each on a 64-byte boundary ---------------
-  B.n_nodes = (uint32_t)order.size();
-  std::vector<uint32_t>& node_addr = topo->node_addr;
-  std::vector<uint32_t>& block_addr = topo->block_addr;
-  uint64_t& next_unit = topo->next_unit;
-  uint32_t& n_tri_records = topo->n_tri_records;
-  if (!refit) { node_addr.assign(B.n_nodes, 0u); block_addr.assign(B.n_nodes, 0u); next_unit = 4; n_tri_records = 0; }
-  for (const uint32_t idx : block_order) {
-    if (refit) break;
-    const Wide& w = wide[idx];
-    uint32_t ni = 0, nt = 0;
-    for (int sl = 0; sl < kWide; ++sl) {
-      if (!w.used[sl]) continue;
-      if (!w.slot[sl].leaf) ++ni; else nt += w.slot[sl].hi - w.slot[sl].lo + 1u;
-    }
-    block_addr[idx] = (uint32_t)next_unit;
-    for (uint32_t i = 0; i < ni; ++i) node_addr[child_base[idx] + i] = (uint32_t)next_unit + 4u * i;
-    next_unit += ((uint64_t)4 * ni + (uint64_t)3 * nt + 3u) & ~(uint64_t)3;
-    n_tri_records += nt;
-    if (next_unit >= (1ull << 31)) return "scene_commit: BVH too large";
+  // a single triangle: two identical leaf children (mirrors the binary special case)
+  void single_triangle_tree() {
+    WChild kid[2];
+    for (int k = 0; k < 2; ++k) { kid[k].leaf = true; kid[k].lo = kid[k].hi = 0; kid[k].radix = -1; kid[k].box = tbox[0]; }
+    T.order.push_back({-1, 0}); T.wide.push_back(make_wide(kid, 2)); T.child_base.push_back(1); T.block_order.push_back(0);
   }
-  // ---- emit nodes and triangles -----------------------------------------------------------------------------------------
-  if (!refit) B.recs.assign((size_t)next_unit * 4, 0.0f);      // a refit rewrites every node and triangle record in place; the padding between blocks stays zero
-  B.n_units = (uint32_t)next_unit;
-  float grid_step[3];
-  for (int k = 0; k < 3; ++k) { const float st = (sb.hi[k] - sb.lo[k]) / 65535.0f; grid_step[k] = st > 0.0f ? st : 1.0f; B.grid_lo[k] = sb.lo[k]; B.grid_step[k] = grid_step[k]; }
-  uint32_t maxd = 0;
-  for (uint32_t idx = 0; idx < B.n_nodes; ++idx) if (order[idx].depth > maxd) maxd = order[idx].depth;
-  // surface-area cost of the tree (ptc_stats.bvh_sa_cost): per used child slot half_area(child) / half_area(scene box at build time), a two-triangle leaf twice, each term
-  // truncated to 2^-20 and summed as an integer — the terms and the sum k_refit_nodes forms on the device (pt_refit.hip)
-  std::atomic<uint64_t> sa_cost{0};
-  if (!refit) B.sa_unit = box_half_area(sb);
-  const float scene_area = B.sa_unit;
-  parallel_for(B.n_nodes, 1024, [&](size_t n0, size_t n1) {
-  uint64_t cost_part = 0;
-  for (uint32_t idx = (uint32_t)n0; idx < (uint32_t)n1; ++idx) {
-    const Wide& w = wide[idx];
-    if (scene_area > 0.0f)
+
+  // ---- unit addresses: root at 0, then the children blocks in allocation order, each on a 64-byte boundary; false: the tree does not fit 2^31 units ------
+  bool assign_addresses() {
+    T.node_addr.assign(T.order.size(), 0u); T.block_addr.assign(T.order.size(), 0u); T.next_unit = 4; T.n_tri_records = 0;
+    for (const uint32_t idx : T.block_order) {
+      const Wide& w = T.wide[idx];
+      uint32_t ni = 0, nt = 0;
       for (int sl = 0; sl < kWide; ++sl) {
         if (!w.used[sl]) continue;
-        const uint64_t term = (uint64_t)((box_half_area(w.slot[sl].box) / scene_area) * PTC_SA_COST_ONE);
-        cost_part += (w.slot[sl].leaf && w.slot[sl].hi - w.slot[sl].lo + 1u == 2u) ? 2u * term : term;
+        if (!w.slot[sl].leaf) ++ni; else nt += w.slot[sl].hi - w.slot[sl].lo + 1u;
       }
-    uint32_t word[kNodeWords] = {0};
+      T.block_addr[idx] = (uint32_t)T.next_unit;
+      for (uint32_t i = 0; i < ni; ++i) T.node_addr[T.child_base[idx] + i] = (uint32_t)T.next_unit + 4u * i;
+      T.next_unit += ((uint64_t)4 * ni + (uint64_t)3 * nt + 3u) & ~(uint64_t)3;
+      T.n_tri_records += nt;
+      if (T.next_unit >= (1ull << 31)) return false;
+    }
+    B.recs.assign((size_t)T.next_unit * 4, 0.0f);      // a refit rewrites every node and triangle record in place; the padding between blocks stays zero
+    return true;
+  }
+
+  // ---- emit nodes and triangles -----------------------------------------------------------------------------------------
+  // triangle record of sorted position i: (v0, prim id) (e1, class) (e2, 0)
+  void tri_record(uint32_t i, float* o) const {
+    const uint32_t p = T.ord[i];
+    const float* a = B.wverts[B.widx[p * 3 + 0]].position;
+    const float* b = B.wverts[B.widx[p * 3 + 1]].position;
+    const float* c = B.wverts[B.widx[p * 3 + 2]].position;
+    const int32_t mi = B.tri_mat[p];
+    const uint32_t cls = material_class(mats[(size_t)mi], mat_set[(size_t)mi]);
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; std::memcpy(&o[3], &p, 4);
+    o[4] = b[0] - a[0]; o[5] = b[1] - a[1]; o[6] = b[2] - a[2]; std::memcpy(&o[7], &cls, 4);
+    o[8] = c[0] - a[0]; o[9] = c[1] - a[1]; o[10] = c[2] - a[2]; o[11] = 0.0f;
+  }
+  void emit_node(uint32_t idx) {
+    const Wide& w = T.wide[idx];
     uint32_t e[3], oq[3], qlo[3][kWide], qhi[3][kWide];
     int sl_of[kWide], nk = 0;                      // used slots in ascending order
     for (int sl = 0; sl < kWide; ++sl) if (w.used[sl]) sl_of[nk++] = sl;
     for (int k = 0; k < 3; ++k) {
+      // the children's planes on this axis and the node's own
       float clo[kWide], chi[kWide], nlo = w.slot[sl_of[0]].box.lo[k], nhi = w.slot[sl_of[0]].box.hi[k];
-      uint32_t ql[kWide], qh[kWide];
       for (int i = 0; i < nk; ++i) {
         clo[i] = w.slot[sl_of[i]].box.lo[k]; chi[i] = w.slot[sl_of[i]].box.hi[k];
         nlo = clo[i] < nlo ? clo[i] : nlo; nhi = chi[i] > nhi ? chi[i] : nhi;
       }
-      // origin on the 16-bit scene grid, rounded down: the largest q with fmaf(q, step, lo) <= the node's lower bound
-      float fq = std::floor((nlo - sb.lo[k]) / grid_step[k]);
-      if (fq < 0.0f) fq = 0.0f;
-      if (fq > 65535.0f) fq = 65535.0f;
-      uint32_t q16 = (uint32_t)fq;
-      while (q16 > 0u && fmaf((float)q16, grid_step[k], sb.lo[k]) > nlo) --q16;
-      oq[k] = q16;
-      const float org = fmaf((float)q16, grid_step[k], sb.lo[k]);
-      for (int sl = 0; sl < kWide; ++sl) { qlo[k][sl] = 255; qhi[k][sl] = 0; }
+      // quantised against the node's origin on the scene grid
+      oq[k] = grid_origin(nlo, B.grid_lo[k], B.grid_step[k]);
+      const float org = fmaf((float)oq[k], B.grid_step[k], B.grid_lo[k]);
+      uint32_t ql[kWide], qh[kWide];
       quantize_axis(clo, chi, nk, org, nhi, e[k], ql, qh);
+      for (int sl = 0; sl < kWide; ++sl) { qlo[k][sl] = 255; qhi[k][sl] = 0; }
       for (int i = 0; i < nk; ++i) { qlo[k][sl_of[i]] = ql[i]; qhi[k][sl_of[i]] = qh[i]; }
     }
+    // the node's words
     uint32_t imask = 0, lmask = 0, two = 0, ni = 0;
-    for (int sl = 0; sl < kWide; ++sl) if (w.used[sl] && !w.slot[sl].leaf) { imask |= 1u << sl; ++ni; }
-    float* tri_out = &B.recs[((size_t)block_addr[idx] + 4u * ni) * 4];
     for (int sl = 0; sl < kWide; ++sl) {
-      if (!w.used[sl] || !w.slot[sl].leaf) continue;
-      const WChild& ch = w.slot[sl];
+      if (!w.used[sl]) continue;
+      if (!w.slot[sl].leaf) { imask |= 1u << sl; ++ni; continue; }
       lmask |= 1u << sl;
-      if (ch.hi - ch.lo + 1u == 2u) two |= 1u << sl;
-      for (uint32_t t = ch.lo; t <= ch.hi; ++t) { tri_record(t, tri_out); tri_out += 12; }
+      if (w.slot[sl].hi - w.slot[sl].lo + 1u == 2u) two |= 1u << sl;
     }
+    uint32_t word[kNodeWords];
     word[0] = oq[0] | (oq[1] << 16);
     word[1] = oq[2] | (e[0] << 16) | (e[1] << 24);
     word[2] = e[2] | (imask << 8) | (lmask << 16) | (two << 24);
-    word[3] = block_addr[idx];
+    word[3] = T.block_addr[idx];
     auto pack4 = [](const uint32_t* q) { return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24); };
     for (int k = 0; k < 3; ++k) {
       word[4 + 2 * k] = pack4(&qlo[k][0]); word[5 + 2 * k] = pack4(&qlo[k][4]);
       word[10 + 2 * k] = pack4(&qhi[k][0]); word[11 + 2 * k] = pack4(&qhi[k][4]);
     }
-    std::memcpy(&B.recs[(size_t)node_addr[idx] * 4], word, sizeof word);
-  }
-  sa_cost.fetch_add(cost_part);
-  });
-  B.sa_cost_fixed = sa_cost.load();
-  lap("emit nodes + triangles");
-  B.max_depth = maxd;
-  B.n_tri_records = n_tri_records;
-  B.n_lds_units = B.n_units < toplet_budget * 4u ? B.n_units : toplet_budget * 4u;
-  // ---- materials --------------------------------------------------------------------------------------
-  fill_materials(mats, mat_set, B);
-  // ---- emitters (original primitive order), power pmf / cdf ----------------------------------------------
-  B.prim_light.assign(n, -1);
-  B.lights.clear(); B.cdf.clear();
-  std::vector<float> weight;
-  for (uint32_t p = 0; p < n; ++p) {
-    const HostMaterial& m = mats[(size_t)B.tri_mat[p]];
-    if (!(m.emissive[0] > 0.0f || m.emissive[1] > 0.0f || m.emissive[2] > 0.0f)) continue;
-    const float* a = B.wverts[B.widx[p * 3 + 0]].position;
-    const float* b = B.wverts[B.widx[p * 3 + 1]].position;
-    const float* c = B.wverts[B.widx[p * 3 + 2]].position;
-    const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    float cr[3];
-    fcross(e1, e2, cr);
-    const float len = sqrtf(fdot(cr, cr));
-    const float area = 0.5f * len;
-    const float lum = fmaf(m.emissive[2], 0.0722f, fmaf(m.emissive[1], 0.7152f, m.emissive[0] * 0.2126f));
-    const float wgt = area * lum;
-    if (!(wgt > 0.0f)) continue;
-    const float il = 1.0f / len;
-    B.prim_light[p] = (int32_t)weight.size();
-    weight.push_back(wgt);
-    const float rec[20] = {a[0], a[1], a[2], area, e1[0], e1[1], e1[2], 0.0f /*pmf*/, e2[0], e2[1], e2[2], 0.0f,
-                           cr[0] * il, cr[1] * il, cr[2] * il, 0.0f, m.emissive[0], m.emissive[1], m.emissive[2], 0.0f};
-    B.lights.insert(B.lights.end(), rec, rec + 20);
-  }
-  B.n_lights = (uint32_t)weight.size();
-  float total = 0.0f;
-  for (float wv : weight) total += wv;
-  float run = 0.0f;
-  B.cdf.resize(weight.size());
-  for (size_t i = 0; i < weight.size(); ++i) {
-    run += weight[i];
-    B.cdf[i] = run / total;
-    B.lights[i * 20 + 7] = weight[i] / total;
-  }
-  lap("materials + emitters");
-  // ---- per-primitive shading records: positions + normals of the three vertices, material, emitter index; with a textured material in
-  // the scene also uv / tangent / bitangent of the three vertices (units 5..10) and a unit of padding
-  bool any_tex = false;
-  for (const auto& m : mats) any_tex = any_tex || m.tex_color >= 0 || m.tex_normal >= 0 || m.tex_mr >= 0;
-  B.shade_stride = any_tex ? 12u : 5u;
-  const size_t fl = (size_t)B.shade_stride * 4;
-  B.shade.assign((size_t)n * fl, 0.0f);
-  parallel_for(n, 8192, [&](size_t p0, size_t p1) {
-  for (uint32_t p = (uint32_t)p0; p < (uint32_t)p1; ++p) {
-    const HostVertex& a = B.wverts[B.widx[p * 3 + 0]];
-    const HostVertex& b = B.wverts[B.widx[p * 3 + 1]];
-    const HostVertex& c = B.wverts[B.widx[p * 3 + 2]];
-    float* o = &B.shade[(size_t)p * fl];
-    o[0] = a.position[0]; o[1] = a.position[1]; o[2] = a.position[2]; std::memcpy(&o[3], &B.tri_mat[p], 4);
-    o[4] = b.position[0]; o[5] = b.position[1]; o[6] = b.position[2]; std::memcpy(&o[7], &B.prim_light[p], 4);
-    o[8] = c.position[0]; o[9] = c.position[1]; o[10] = c.position[2]; o[11] = a.normal[0];
-    o[12] = a.normal[1]; o[13] = a.normal[2]; o[14] = b.normal[0]; o[15] = b.normal[1];
-    o[16] = b.normal[2]; o[17] = c.normal[0]; o[18] = c.normal[1]; o[19] = c.normal[2];
-    if (any_tex) {
-      float* t = o + 20;
-      for (int k = 0; k < 3; ++k) {
-        const uint32_t vi = B.widx[p * 3 + (uint32_t)k];
-        const HostVertex& v = B.wverts[vi];
-        t[k * 2 + 0] = v.texcoord[0]; t[k * 2 + 1] = v.texcoord[1];
-        for (int j = 0; j < 3; ++j) { t[6 + k * 3 + j] = v.tangent[j]; t[15 + k * 3 + j] = topo->wbt[(size_t)vi * 3 + (size_t)j]; }
-      }
+    std::memcpy(&B.recs[(size_t)T.node_addr[idx] * 4], word, sizeof word);
+    // the triangles of its leaf children, behind the interior children in its block
+    float* tri_out = &B.recs[((size_t)T.block_addr[idx] + 4u * ni) * 4];
+    for (int sl = 0; sl < kWide; ++sl) {
+      if (!w.used[sl] || !w.slot[sl].leaf) continue;
+      for (uint32_t t = w.slot[sl].lo; t <= w.slot[sl].hi; ++t) { tri_record(t, tri_out); tri_out += 12; }
     }
   }
-  });
+  void emit_nodes() {
+    B.n_nodes = (uint32_t)T.order.size();
+    B.n_units = (uint32_t)T.next_unit;
+    B.n_tri_records = T.n_tri_records;
+    B.n_lds_units = B.n_units < T.toplet_budget * 4u ? B.n_units : T.toplet_budget * 4u;
+    B.max_depth = 0;
+    for (const Slot& s : T.order) if (s.depth > B.max_depth) B.max_depth = s.depth;
+    std::atomic<uint64_t> sa_cost{0};
+    parallel_for(B.n_nodes, 1024, [&](size_t n0, size_t n1) {
+      uint64_t cost_part = 0;
+      for (uint32_t idx = (uint32_t)n0; idx < (uint32_t)n1; ++idx) {
+        cost_part += sa_cost_of(T.wide[idx], B.sa_unit);
+        emit_node(idx);
+      }
+      sa_cost.fetch_add(cost_part);
+    });
+    B.sa_cost_fixed = sa_cost.load();
+  }
+
+  // ---- per-primitive shading records: positions + normals of the three vertices, material, emitter index; with a textured material in
+  // the scene also uv / tangent / bitangent of the three vertices (units 5..10) and a unit of padding
+  void shading_records() {
+    B.shade_stride = shade_stride_for(mats);
+    const bool any_tex = B.shade_stride > 5u;
+    const size_t fl = (size_t)B.shade_stride * 4;
+    B.shade.assign((size_t)B.n_tris * fl, 0.0f);
+    parallel_for(B.n_tris, 8192, [&](size_t p0, size_t p1) {
+      for (uint32_t p = (uint32_t)p0; p < (uint32_t)p1; ++p) {
+        const HostVertex& a = B.wverts[B.widx[p * 3 + 0]];
+        const HostVertex& b = B.wverts[B.widx[p * 3 + 1]];
+        const HostVertex& c = B.wverts[B.widx[p * 3 + 2]];
+        float* o = &B.shade[(size_t)p * fl];
+        o[0] = a.position[0]; o[1] = a.position[1]; o[2] = a.position[2]; std::memcpy(&o[3], &B.tri_mat[p], 4);
+        o[4] = b.position[0]; o[5] = b.position[1]; o[6] = b.position[2]; std::memcpy(&o[7], &B.prim_light[p], 4);
+        o[8] = c.position[0]; o[9] = c.position[1]; o[10] = c.position[2]; o[11] = a.normal[0];
+        o[12] = a.normal[1]; o[13] = a.normal[2]; o[14] = b.normal[0]; o[15] = b.normal[1];
+        o[16] = b.normal[2]; o[17] = c.normal[0]; o[18] = c.normal[1]; o[19] = c.normal[2];
+        if (any_tex) {
+          float* t = o + 20;
+          for (int k = 0; k < 3; ++k) {
+            const uint32_t vi = B.widx[p * 3 + (uint32_t)k];
+            const HostVertex& v = B.wverts[vi];
+            t[k * 2 + 0] = v.texcoord[0]; t[k * 2 + 1] = v.texcoord[1];
+            for (int j = 0; j < 3; ++j) { t[6 + k * 3 + j] = v.tangent[j]; t[15 + k * 3 + j] = T.wbt[(size_t)vi * 3 + (size_t)j]; }
+          }
+        }
+      }
+    });
+  }
+};
+
+struct Laps {      // PTC_BUILD_TIMING: phase times of the host build / refit on stderr
+  const bool on = std::getenv("PTC_BUILD_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "  %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - prev).count());
+    prev = now;
+  }
+};
+
+// The host commit (refit == false) and the host refit: the stages above.  A refit keeps the Topology of the commit — the order of the triangles, the binary tree, the 8-wide
+// nodes' numbering, slots and addresses, textures and environment — so the stages that make those run on a commit only; everything that depends on vertex positions runs always.
+std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes,
+                           const std::vector<HostInstance>& insts, const std::vector<HostTexture>& texs, const HostEnv& env,
+                           uint32_t toplet_budget, int bvh_builder, HostBuilt& B, bool refit) {
+  Laps lap;
+  InstanceBases L;
+  { const std::string e = count_instances(meshes, insts, L); if (!e.empty()) return e; }
+  std::shared_ptr<Topology> topo;
+  if (refit) {
+    topo = std::static_pointer_cast<Topology>(B.topology);
+    if (!topo || B.n_tris != L.nt || B.n_wverts != L.nv) return "scene_refit: the scene's meshes or instances changed since the commit (only transforms may)";
+  } else {
+    B = HostBuilt();
+    topo = std::make_shared<Topology>();
+    topo->toplet_budget = toplet_budget;
+  }
+  SceneBuild S{mats, meshes, insts, B, *topo, std::move(L)};
+  Topology& T = *topo;
+  // The flatten goes into temporaries that are taken over only when every position is finite: a refused refit leaves the host build as it was (the device
+  // path restores its scratch vertices likewise), so the debug getters keep describing what is being rendered.
+  std::vector<HostVertex> wverts;
+  std::vector<float> wbt;
+  S.flatten(wverts, wbt);
+  fill_indices(meshes, insts, S.L, B);
+  lap("flatten");
+  // NaN / Inf anywhere in the flattened positions (bad vertices or a bad instance matrix) is an error: the builder
+  // computes bin indices from them
+  for (const auto& v : wverts)
+    if (!(std::isfinite(v.position[0]) && std::isfinite(v.position[1]) && std::isfinite(v.position[2]))) return "scene_commit: non-finite vertex position after the instance transform";
+  B.wverts.swap(wverts); T.wbt.swap(wbt);
+  S.triangle_boxes();
+  lap("triangle boxes");
+  ptc_refit_grid(S.sb.lo, S.sb.hi, B.grid_lo, B.grid_step, &B.ray_eps);
+  material_sets(mats, S.mat_set, S.set_tex);
+  if (refit) {
+    S.compute_radix_boxes();
+    S.refit_child_boxes();
+    lap("refit boxes");
+  } else {
+    B.sa_unit = box_half_area(S.sb);      // the unit of the surface-area cost: a refit keeps the commit's
+    T.ord.resize(B.n_tris);
+    for (uint32_t p = 0; p < B.n_tris; ++p) T.ord[p] = p;
+    if (B.n_tris == 1) {
+      S.single_triangle_tree();
+    } else {
+      build_split_tree(S.tbox, T.ord, T.radix, bvh_builder == 1, T.sub_first);
+      lap("  binary tree");
+      S.compute_radix_boxes();
+      lap("  binary boxes");
+      S.cost_tables();
+      lap("  collapse cost tables");
+      S.number_nodes();
+    }
+    lap("tree build + collapse");
+    if (!S.assign_addresses()) return "scene_commit: BVH too large";
+  }
+  S.emit_nodes();
+  lap("emit nodes + triangles");
+  fill_materials(mats, S.mat_set, B);
+  fill_emitters(mats, meshes, insts, S.L, B);
+  lap("materials + emitters");
+  S.shading_records();
   lap("shading records");
-  if (!refit) fill_textures_env(texs, env, set_tex, B);
-  if (!B.cdf.empty()) B.cdf.back() = 1.0f;
-  if (B.cdf.empty()) B.cdf.push_back(1.0f);
-  if (B.lights.empty()) B.lights.assign(20, 0.0f);
+  if (!refit) fill_textures_env(texs, env, S.set_tex, B);
   lap("textures + environment");
   B.topology = topo;
   return std::string();
@@ -1262,62 +1367,6 @@ std::string ptc_build_scene(const std::vector<HostMaterial>& mats, const std::ve
   return build_or_refit(mats, meshes, insts, texs, env, toplet_budget, bvh_builder, B, false);
 }
 
-namespace {
-// The emitter table from the emissive primitives alone (emit_prims: prim, instance, its 3 vertex indices inside the instance's mesh), each vertex taken through its instance's
-// matrix with the flatten's expression.  committed != nullptr: a refit — false when the set of emitters is not the committed one.  committed == nullptr: a commit without a host
-// flatten (ptc_build_skeleton) — the emitter index of every primitive is written to *prim_light (sized by the caller, -1 everywhere).
-bool emitters_from_prims(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const std::vector<int32_t>& emit_prims,
-                         const HostBuilt* committed, std::vector<int32_t>* prim_light, std::vector<float>& lights, std::vector<float>& cdf);
-}
-// The host's share of a commit whose tree is built ON THE DEVICE (ptc_scene_commit with the LBVH builder on a device context): everything that does not need a flattened
-// vertex — world vertex indices and material per primitive, materials, texture sets, environment tables, and the emitter table (the emissive primitives alone, each vertex
-// through its instance's matrix with the flatten's expression).  The flatten, the shading records and the tree are the device's (pt_refit.hip, pt_build.hip): `out` keeps
-// their SIZES, its wverts / shade / recs come back from HBM when somebody asks, and it has no topology (as after ptc_scene_rebuild).
-std::string ptc_build_skeleton(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts,
-                               const std::vector<HostTexture>& texs, const HostEnv& env, uint32_t toplet_budget, HostBuilt& B) {
-  if (insts.empty()) return "scene_commit: no instances";
-  uint64_t nv = 0, nt = 0;
-  for (const auto& in : insts) { nv += meshes[(size_t)in.mesh].v.size(); nt += meshes[(size_t)in.mesh].idx.size() / 3; }
-  if (nt >= (1u << 28)) return "scene_commit: too many triangles";
-  B = HostBuilt();
-  B.n_wverts = (uint32_t)nv;       // the flatten is the device's: refresh_host_copy sizes and fills wverts when somebody asks
-  B.widx.resize(nt * 3);
-  B.tri_mat.resize(nt);
-  B.n_tris = (uint32_t)nt;
-  std::vector<int32_t> emit_prims;
-  {
-    uint32_t vb = 0, tb = 0;
-    for (size_t i = 0; i < insts.size(); ++i) {
-      const HostMesh& m = meshes[(size_t)insts[i].mesh];
-      const size_t ntm = m.idx.size() / 3;
-      for (size_t k = 0; k < ntm; ++k) {
-        for (int c = 0; c < 3; ++c) B.widx[(tb + k) * 3 + c] = vb + m.idx[k * 3 + c];
-        B.tri_mat[tb + k] = m.material;
-      }
-      const HostMaterial& hm = mats[(size_t)m.material];
-      if (hm.emissive[0] > 0.0f || hm.emissive[1] > 0.0f || hm.emissive[2] > 0.0f)
-        for (size_t k = 0; k < ntm; ++k) {
-          const int32_t e[5] = {(int32_t)(tb + k), (int32_t)i, (int32_t)m.idx[k * 3], (int32_t)m.idx[k * 3 + 1], (int32_t)m.idx[k * 3 + 2]};
-          emit_prims.insert(emit_prims.end(), e, e + 5);
-        }
-      vb += (uint32_t)m.v.size(); tb += (uint32_t)ntm;
-    }
-  }
-  std::vector<int32_t> mat_set, set_tex;
-  material_sets(mats, mat_set, set_tex);
-  fill_materials(mats, mat_set, B);
-  B.prim_light.assign(nt, -1);
-  (void)emitters_from_prims(mats, meshes, insts, emit_prims, nullptr, &B.prim_light, B.lights, B.cdf);
-  B.n_lights = 0;
-  for (int32_t l : B.prim_light) B.n_lights += l >= 0 ? 1u : 0u;
-  bool any_tex = false;
-  for (const auto& m : mats) any_tex = any_tex || m.tex_color >= 0 || m.tex_normal >= 0 || m.tex_mr >= 0;
-  B.shade_stride = any_tex ? 12u : 5u;
-  fill_textures_env(texs, env, set_tex, B);
-  B.n_lds_units = toplet_budget * 4u;      // upper bound until the tree exists (it sizes the trace kernels' LDS)
-  return std::string();
-}
-
 // Refit: the instances' transforms changed (and nothing else).  Vertices are flattened again, every box of the committed tree is
 // recomputed bottom-up and re-quantised (the scene box, hence the origin grid and the ray offset, follow the geometry), triangle records,
 // shading records and the emitter table are rewritten; the tree keeps its topology, its slots and its layout.
@@ -1326,46 +1375,47 @@ std::string ptc_refit_scene(const std::vector<HostMaterial>& mats, const std::ve
   return build_or_refit(mats, meshes, insts, texs, env, 0, 0, B, true);
 }
 
+// The host's share of a commit whose tree is built ON THE DEVICE (ptc_scene_commit with the LBVH builder on a device context): everything that does not need a flattened
+// vertex — world vertex indices and material per primitive, materials, texture sets, environment tables, and the emitter table.  The flatten, the shading records and the
+// tree are the device's (pt_refit.hip, pt_build.hip): `out` keeps their SIZES, its wverts / shade / recs come back from HBM when somebody asks, and it has no topology
+// (as after ptc_scene_rebuild).
+std::string ptc_build_skeleton(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts,
+                               const std::vector<HostTexture>& texs, const HostEnv& env, uint32_t toplet_budget, HostBuilt& B) {
+  InstanceBases L;
+  { const std::string e = count_instances(meshes, insts, L); if (!e.empty()) return e; }
+  B = HostBuilt();
+  fill_indices(meshes, insts, L, B);
+  std::vector<int32_t> mat_set, set_tex;
+  material_sets(mats, mat_set, set_tex);
+  fill_materials(mats, mat_set, B);
+  fill_emitters(mats, meshes, insts, L, B);
+  B.shade_stride = shade_stride_for(mats);
+  fill_textures_env(texs, env, set_tex, B);
+  B.n_lds_units = toplet_budget * 4u;      // upper bound until the tree exists (it sizes the trace kernels' LDS)
+  return std::string();
+}
+
 // ---- the host's share of a refit on the device (pt_refit.h) -----------------------------------------------------------------------
 void ptc_prim_classes(const std::vector<HostMaterial>& mats, const std::vector<int32_t>& tri_mat, std::vector<uint32_t>& out) {
-  // as build_or_refit numbers them: a texture SET is a distinct (colour, normal, metal-rough) triple among the textured materials, in material order
-  std::vector<int32_t> mat_set(mats.size(), -1), set_tex;
-  for (size_t i = 0; i < mats.size(); ++i) {
-    const HostMaterial& m = mats[i];
-    if (m.tex_color < 0 && m.tex_normal < 0 && m.tex_mr < 0) continue;
-    int32_t found = -1;
-    for (size_t k = 0; k * 3 < set_tex.size(); ++k)
-      if (set_tex[k * 3] == m.tex_color && set_tex[k * 3 + 1] == m.tex_normal && set_tex[k * 3 + 2] == m.tex_mr) { found = (int32_t)k; break; }
-    if (found < 0) { found = (int32_t)(set_tex.size() / 3); set_tex.push_back(m.tex_color); set_tex.push_back(m.tex_normal); set_tex.push_back(m.tex_mr); }
-    mat_set[i] = found;
-  }
+  std::vector<int32_t> mat_set, set_tex;
+  material_sets(mats, mat_set, set_tex);
   out.resize(tri_mat.size());
-  for (size_t p = 0; p < tri_mat.size(); ++p) {
-    const size_t mi = (size_t)tri_mat[p];
-    const HostMaterial& hm = mats[mi];
-    out[p] = mat_set[mi] >= 0 ? 2u + (uint32_t)mat_set[mi] % 5u : ((hm.metallic == 0.0f && hm.roughness >= 1.0f) ? 0u : 1u);
-  }
+  for (size_t p = 0; p < tri_mat.size(); ++p) out[p] = material_class(mats[(size_t)tri_mat[p]], mat_set[(size_t)tri_mat[p]]);
 }
 
 void ptc_refit_plan(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const HostBuilt& B, RefitPlan& P) {
   P = RefitPlan();
   std::vector<uint32_t> mesh_first(meshes.size());
   for (size_t m = 0; m < meshes.size(); ++m) { mesh_first[m] = (uint32_t)P.mesh_verts.size(); P.mesh_verts.insert(P.mesh_verts.end(), meshes[m].v.begin(), meshes[m].v.end()); }
-  uint32_t vb = 0, tb = 0;
+  InstanceBases L;
+  (void)count_instances(meshes, insts, L);      // the description was committed: its counts passed then
+  P.inst_first = L.vb;
   for (size_t i = 0; i < insts.size(); ++i) {
-    const HostMesh& m = meshes[(size_t)insts[i].mesh];
-    P.inst_first.push_back(vb);
     P.inst_src.push_back(mesh_first[(size_t)insts[i].mesh]);
-    P.vert_inst.insert(P.vert_inst.end(), m.v.size(), (uint32_t)i);
-    const HostMaterial& hm = mats[(size_t)m.material];
-    if (hm.emissive[0] > 0.0f || hm.emissive[1] > 0.0f || hm.emissive[2] > 0.0f)
-      for (size_t k = 0; k * 3 < m.idx.size(); ++k) {
-        const int32_t e[5] = {(int32_t)(tb + k), (int32_t)i, (int32_t)m.idx[k * 3], (int32_t)m.idx[k * 3 + 1], (int32_t)m.idx[k * 3 + 2]};
-        P.emit_prims.insert(P.emit_prims.end(), e, e + 5);
-      }
-    vb += (uint32_t)m.v.size(); tb += (uint32_t)(m.idx.size() / 3);
+    P.vert_inst.insert(P.vert_inst.end(), meshes[(size_t)insts[i].mesh].v.size(), (uint32_t)i);
   }
-  P.n_verts = vb; P.n_tris = tb;
+  emissive_prims(mats, meshes, insts, L, P.emit_prims);
+  P.n_verts = (uint32_t)L.nv; P.n_tris = (uint32_t)L.nt;
   if (!B.topology) { P.level_first.assign(1, 0u); return; }      // a commit on the device (ptc_build_skeleton): the level lists come from the device build
   const Topology& topo = *std::static_pointer_cast<Topology>(B.topology);
   uint32_t maxd = 0;
@@ -1392,68 +1442,16 @@ bool ptc_refit_instance_transforms(const std::vector<HostInstance>& insts, std::
   return finite;
 }
 
+// the scene box → the ray offset and the 16-bit grid of the node origins; the host build, the host refit and the device passes all take them from here
 void ptc_refit_grid(const float lo[3], const float hi[3], float grid_lo[3], float grid_step[3], float* ray_eps) {
   float diag = hi[0] - lo[0];
   if (hi[1] - lo[1] > diag) diag = hi[1] - lo[1];
   if (hi[2] - lo[2] > diag) diag = hi[2] - lo[2];
   *ray_eps = 1e-4f * (diag > 1e-6f ? diag : 1e-6f);
-  for (int k = 0; k < 3; ++k) { const float st = (hi[k] - lo[k]) / 65535.0f; grid_step[k] = st > 0.0f ? st : 1.0f; grid_lo[k] = lo[k]; }
+  for (int k = 0; k < 3; ++k) { const float st = (hi[k] - lo[k]) / kGridCells; grid_step[k] = st > 0.0f ? st : 1.0f; grid_lo[k] = lo[k]; }
 }
 
 bool ptc_refit_emitters(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const RefitPlan& P,
                         const HostBuilt& B, std::vector<float>& lights, std::vector<float>& cdf) {
-  return emitters_from_prims(mats, meshes, insts, P.emit_prims, &B, nullptr, lights, cdf);
+  return emitters_from_prims(mats, meshes, insts, P.emit_prims, &B, nullptr, lights, cdf) >= 0;
 }
-namespace {
-bool emitters_from_prims(const std::vector<HostMaterial>& mats, const std::vector<HostMesh>& meshes, const std::vector<HostInstance>& insts, const std::vector<int32_t>& emit_prims,
-                         const HostBuilt* committed, std::vector<int32_t>* prim_light, std::vector<float>& lights, std::vector<float>& cdf) {
-  lights.clear(); cdf.clear();
-  std::vector<float> weight;
-  int32_t cached_inst = -1;
-  Mat34 M{};
-  for (size_t j = 0; j * 5 < emit_prims.size(); ++j) {
-    const int32_t* e = &emit_prims[j * 5];
-    const uint32_t p = (uint32_t)e[0];
-    const HostMesh& mesh = meshes[(size_t)insts[(size_t)e[1]].mesh];
-    const HostMaterial& m = mats[(size_t)mesh.material];
-    if (e[1] != cached_inst) { M = from_matrix(insts[(size_t)e[1]].m); cached_inst = e[1]; }
-    float w[3][3];
-    for (int c = 0; c < 3; ++c) {
-      const float* s = mesh.v[(size_t)e[2 + c]].position;
-      for (int r = 0; r < 3; ++r) w[c][r] = M.m[0 + r] * s[0] + M.m[4 + r] * s[1] + M.m[8 + r] * s[2] + M.m[12 + r];
-    }
-    const float *a = w[0], *b = w[1], *c = w[2];
-    const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    float cr[3];
-    fcross(e1, e2, cr);
-    const float len = sqrtf(fdot(cr, cr));
-    const float area = 0.5f * len;
-    const float lum = fmaf(m.emissive[2], 0.0722f, fmaf(m.emissive[1], 0.7152f, m.emissive[0] * 0.2126f));
-    const float wgt = area * lum;
-    const bool is_light = wgt > 0.0f;
-    if (committed && is_light != (committed->prim_light[p] >= 0)) return false;
-    if (!is_light) continue;
-    if (committed && committed->prim_light[p] != (int32_t)weight.size()) return false;
-    if (prim_light) (*prim_light)[p] = (int32_t)weight.size();
-    const float il = 1.0f / len;
-    weight.push_back(wgt);
-    const float rec[20] = {a[0], a[1], a[2], area, e1[0], e1[1], e1[2], 0.0f, e2[0], e2[1], e2[2], 0.0f,
-                           cr[0] * il, cr[1] * il, cr[2] * il, 0.0f, m.emissive[0], m.emissive[1], m.emissive[2], 0.0f};
-    lights.insert(lights.end(), rec, rec + 20);
-  }
-  if (committed && weight.size() != committed->n_lights) return false;
-  float total = 0.0f;
-  for (float wv : weight) total += wv;
-  float run = 0.0f;
-  cdf.resize(weight.size());
-  for (size_t i = 0; i < weight.size(); ++i) {
-    run += weight[i];
-    cdf[i] = run / total;
-    lights[i * 20 + 7] = weight[i] / total;
-  }
-  if (!cdf.empty()) cdf.back() = 1.0f;
-  if (cdf.empty()) cdf.push_back(1.0f);
-  if (lights.empty()) lights.assign(20, 0.0f);
-  return true;
-}
-}  // namespace
