@@ -333,6 +333,49 @@ int ptc_denoise(ptc_ctx*, const ptc_denoise_params*);
 int ptc_select_output(ptc_ctx*, int output);
 int ptc_get_denoise_seconds(ptc_ctx*, double* guides, double* denoise);
 
+/* ---- adaptive sampling: a per-pixel error estimate and batches of the pixels that still need samples ------------------------------
+ * A uniform frame spends spp samples on every pixel, converged or not.  An adaptive frame keeps an ACTIVE SET of pixels — at first every owned pixel —
+ * and ptc_frame_add_samples adds its samples to the active pixels only; ptc_frame_adapt takes out the pixels whose estimate has converged.  Nothing here
+ * changes what a context that never calls ptc_frame_set_adaptive computes.  DESIGN.md ("Adaptive sampling") has the specification; in short, all in IEEE
+ * binary32 in the order written:
+ *   per owned pixel  the RGB sum, m1 = sum l_k and m2 = sum l_k l_k in sample order, l_k = (0.2126 r + 0.7152 g) + 0.0722 b of sample k's radiance, and
+ *                    count, the samples received.  Every active pixel has count = the samples added so far.
+ *   ptc_frame_adapt  queues what is held back, then with n = the samples added so far, per active pixel: mean = m1 / n, var = max(m2 / n - mean mean, 0),
+ *                    e = sqrt(var / n) / (mean + 0.01), flag = e > threshold.  A pixel stays active iff n < spp_total and an active pixel within Chebyshev
+ *                    distance `radius` — inside the image and inside the pixel's own 32x32 ownership tile — has its flag set.  A pixel that has left the set
+ *                    never returns.  *n_active (may be NULL) receives the size of the new set.  One 4-byte read-back: the call waits for the device.
+ *                    PTC_E_STATE before the frame's first sample.
+ *   resolve          ptc_frame_resolve divides each pixel's sum by (float)count of that pixel.
+ * The RNG is counter-based and a pixel's sum is taken in sample order, so a pixel with count n holds the bits of the same pixel of a uniform n-spp frame,
+ * whatever its neighbours received; the neighbourhood stops at tile borders, so a tile-sharded adaptive frame is the unsharded one bit for bit.
+ * ptc_frame_set_adaptive: right after a ptc_frame_begin with PTC_INTEGRATOR_PATH, before any sample, once per frame, and not after a
+ *   ptc_frame_set_sample_range with a divisor: PTC_E_STATE otherwise.  params == NULL: the defaults.  PTC_E_ARG, and nothing changed, for a negative or non-finite threshold, a radius
+ *   outside 0..2, min_samples or step_samples < 1.  In an adaptive frame ptc_frame_set_sample_range with a non-zero divisor, ptc_frame_checkpoint and
+ *   ptc_frame_restore return PTC_E_STATE; with an empty active set ptc_frame_add_samples accepts and does nothing.  ptc_stats counts what was traced.
+ *   Guides, denoiser, output selection, the read-backs and ptc_comm_reduce_radiance work on an adaptive frame as on any other; ptc_group_render is uniform.
+ * ptc_read_sample_counts: w*h counts, 0 where this context does not own the pixel.  ptc_get_adaptive_stats: the frame's totals (both wait for the device).
+ *   Both, like ptc_frame_adapt, return PTC_E_STATE in a frame that is not adaptive.
+ * ptc_render_adaptive == frame_begin(max_spp) + set_adaptive + add(min_samples) + { adapt; add(min(step_samples, max_spp - done)) } until nothing is
+ *   active + resolve + sync. */
+typedef struct ptc_adaptive_params {
+  float threshold;    /* relative standard error of the pixel mean's luminance (default 0.05) */
+  int   radius;       /* 0..2, neighbourhood of the keep rule (default 1)                      */
+  int   min_samples;  /* ptc_render_adaptive only: samples before the first decision (16)      */
+  int   step_samples; /* ptc_render_adaptive only: samples between decisions (16)              */
+} ptc_adaptive_params;
+void ptc_adaptive_default_params(ptc_adaptive_params*);
+int  ptc_frame_set_adaptive(ptc_ctx*, const ptc_adaptive_params*);  /* NULL: the defaults */
+int  ptc_frame_adapt(ptc_ctx*, uint64_t* n_active);                 /* decision step; n_active may be NULL */
+int  ptc_read_sample_counts(ptc_ctx*, uint32_t* out);               /* w*h, 0 where not owned */
+int  ptc_render_adaptive(ptc_ctx*, int w, int h, int max_spp, uint64_t seed, int max_bounces,
+                         const ptc_adaptive_params*);
+typedef struct ptc_adaptive_stats {
+  uint64_t owned_pixels, active_pixels, samples_total;   /* samples_total = sum of count */
+  uint32_t passes, max_count;                            /* decision steps so far; the largest count */
+  double   seconds_adapt;                                /* HIP-event time of the decision steps' kernels */
+} ptc_adaptive_stats;
+int  ptc_get_adaptive_stats(ptc_ctx*, ptc_adaptive_stats*);
+
 /* ---- multi-GPU: tiles shard over devices, one RCCL reduce brings the framebuffer to the root -----------
  * The reference has no multi-device path (one vk::Device, core/GpuHandle.cpp:94-101); this is BASELINE.json's
  * "independent pixel/sample tiles shard across the 8 GPUs of one node with an RCCL reduce onto rank 0".

@@ -1,0 +1,156 @@
+// pt_adaptive.hip — adaptive sampling on gfx950: moments, error estimate, keep rule + stable compaction of the active list, per-pixel resolve.
+//
+// A frame in adaptive mode keeps, per owned pixel, the RGB sum (accum, as always), m1 = sum l_k, m2 = sum l_k l_k of the per-sample luminance
+// l_k = (0.2126 r + 0.7152 g) + 0.0722 b, and the number of samples received.  The path kernels see the frame as DevFrame{n_active, active pixels}; the kernels
+// here map an active entry j back to its owned position slot[j].
+//   k_ad_accumulate     pure stream: 16 B per sample and entry in, 28 B of state read and written per entry
+//   k_ad_error          mean = m1 / n, var = max(m2 / n - mean mean, 0), e = sqrt(var / n) / (mean + 0.01), flag = e > threshold: one byte per active pixel
+//   k_ad_compact_*      keep = some flagged pixel within Chebyshev distance `radius`, inside the image and the pixel's own 32x32 tile; then a STABLE compaction
+//                       of (pixel, slot): per-block counts, one block scans them (as k_scan does), ballot + mbcnt prefix per wave and an LDS prefix over the
+//                       block's waves place every kept entry — no atomics, so the list keeps the tile-Morton order and is the same on every run
+//   k_ad_resolve        accum / (float)count per owned pixel
+// Arithmetic: IEEE binary32 in the order written (the Makefile's -ffp-contract=off and correctly rounded division and square root): tests/adaptive_reference.py
+// performs the same operations in numpy and the sample counts are compared exactly.
+#include "pt_adaptive.h"
+
+#define AD_SCAN_BLOCK 1024
+
+namespace {
+__device__ __forceinline__ float ad_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_init(uint32_t n_owned, const uint32_t* __restrict__ owned, uint32_t* __restrict__ pix, uint32_t* __restrict__ slot) {
+  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (j >= n_owned) return;
+  pix[j] = owned[j]; slot[j] = j;
+}
+
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_accumulate(uint32_t n_active, const uint32_t* __restrict__ slot, const float4* __restrict__ lpath, float4* __restrict__ accum,
+                                                                float2* __restrict__ moments, uint32_t* __restrict__ count, uint32_t n_samples) {
+  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (j >= n_active) return;
+  const uint32_t o = slot[j];
+  float4 a = accum[o];
+  float2 m = moments[o];
+  for (uint32_t s = 0; s < n_samples; ++s) {
+    const float4 L = lpath[(size_t)s * n_active + j];
+    a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z;
+    const float l = ad_lum(L.x, L.y, L.z);
+    m.x = m.x + l; m.y = m.y + l * l;
+  }
+  accum[o] = a; moments[o] = m; count[o] += n_samples;
+}
+
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_error(uint32_t n_active, const uint32_t* __restrict__ pix, const uint32_t* __restrict__ slot, const float2* __restrict__ moments,
+                                                           uint8_t* __restrict__ flags, float fn, float threshold) {
+  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (j >= n_active) return;
+  const float2 m = moments[slot[j]];
+  const float mean = m.x / fn;
+  const float var = fmaxf(m.y / fn - mean * mean, 0.0f);
+  const float e = sqrtf(var / fn) / (mean + 0.01f);
+  flags[pix[j]] = e > threshold ? 1 : 0;
+}
+
+// keep predicate per active entry + the number of kept entries per block
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_compact_count(uint32_t n_active, const uint32_t* __restrict__ pix, const uint8_t* __restrict__ flags, uint8_t* __restrict__ keep,
+                                                                   uint32_t* __restrict__ block_tot, int w, int h, int radius) {
+  __shared__ uint32_t s_w[PTC_AD_BLOCK / 64];
+  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  bool k = false;
+  if (j < n_active) {
+    const uint32_t p = pix[j];
+    const int px = (int)(p % (uint32_t)w), py = (int)(p / (uint32_t)w);
+    // the window, clipped to the image and to the pixel's tile
+    const int tx0 = px / PTC_AD_TILE * PTC_AD_TILE, ty0 = py / PTC_AD_TILE * PTC_AD_TILE;
+    const int x0 = max(px - radius, tx0), x1 = min(min(px + radius, tx0 + PTC_AD_TILE - 1), w - 1);
+    const int y0 = max(py - radius, ty0), y1 = min(min(py + radius, ty0 + PTC_AD_TILE - 1), h - 1);
+    for (int y = y0; y <= y1; ++y)
+      for (int x = x0; x <= x1; ++x) k = k || flags[(size_t)y * (size_t)w + (size_t)x] != 0;
+    keep[j] = k ? 1 : 0;
+  }
+  const unsigned long long b = __ballot(k);
+  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int i = 0; i < PTC_AD_BLOCK / 64; ++i) t += s_w[i];
+    block_tot[blockIdx.x] = t;
+  }
+}
+
+// one block: block_tot[0, n_blocks) -> its exclusive prefix in place, the total to n_out[0]
+__global__ __launch_bounds__(AD_SCAN_BLOCK) void k_ad_compact_scan(uint32_t n_blocks, uint32_t* __restrict__ block_tot, uint32_t* __restrict__ n_out) {
+  __shared__ uint32_t s_w[AD_SCAN_BLOCK / 64];
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < n_blocks; base += AD_SCAN_BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < n_blocks ? block_tot[i] : 0u;
+    uint32_t incl = v;
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63u) s_w[wid] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (uint32_t k = 0; k < AD_SCAN_BLOCK / 64; ++k) { const uint32_t t = s_w[k]; if (k < wid) before += t; all += t; }
+    if (i < n_blocks) block_tot[i] = carry + before + (incl - v);
+    carry += all;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) n_out[0] = carry;
+}
+
+// kept entries to their places: block prefix + the waves before this one + the kept lanes before this one
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_compact_write(uint32_t n_active, const uint32_t* __restrict__ pix, const uint32_t* __restrict__ slot, const uint8_t* __restrict__ keep,
+                                                                   const uint32_t* __restrict__ block_pre, uint32_t* __restrict__ pix_out, uint32_t* __restrict__ slot_out) {
+  __shared__ uint32_t s_w[PTC_AD_BLOCK / 64];
+  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  const bool k = j < n_active && keep[j] != 0;
+  const unsigned long long b = __ballot(k);
+  const uint32_t in_wave = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+  const uint32_t wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) s_w[wid] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (!k) return;
+  uint32_t dst = block_pre[blockIdx.x] + in_wave;
+  for (uint32_t i = 0; i < wid; ++i) dst += s_w[i];
+  if (dst >= n_active) return;   // cannot happen (a prefix of kept entries of a list of n_active): the output arrays hold n_active entries
+  pix_out[dst] = pix[j]; slot_out[dst] = slot[j];
+}
+
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_resolve(uint32_t n_owned, const uint32_t* __restrict__ owned, const float4* __restrict__ accum, const uint32_t* __restrict__ count,
+                                                             float4* __restrict__ radiance) {
+  const uint32_t o = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (o >= n_owned) return;
+  const uint32_t n = count[o];
+  if (n == 0) return;
+  const float4 a = accum[o];
+  const float fn = (float)n;
+  radiance[owned[o]] = make_float4(a.x / fn, a.y / fn, a.z / fn, 1.0f);
+}
+}  // namespace
+
+void pt_launch_ad_init(hipStream_t s, uint32_t n_owned, const uint32_t* owned, uint32_t* pix, uint32_t* slot) {
+  if (!n_owned) return;
+  hipLaunchKernelGGL(k_ad_init, dim3(pt_ad_blocks(n_owned)), dim3(PTC_AD_BLOCK), 0, s, n_owned, owned, pix, slot);
+}
+void pt_launch_ad_accumulate(hipStream_t s, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive& ad, uint32_t n_samples) {
+  if (!n_active) return;
+  hipLaunchKernelGGL(k_ad_accumulate, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, n_samples);
+}
+void pt_launch_ad_error(hipStream_t s, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, const DevAdaptive& ad, uint32_t n, float threshold) {
+  if (!n_active) return;
+  hipLaunchKernelGGL(k_ad_error, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, pix, slot, (const float2*)ad.moments, ad.flags, (float)n, threshold);
+}
+void pt_launch_ad_compact(hipStream_t s, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, uint32_t* pix_out, uint32_t* slot_out, const DevAdaptive& ad, int w, int h, int radius) {
+  const uint32_t nb = pt_ad_blocks(n_active);
+  if (nb) hipLaunchKernelGGL(k_ad_compact_count, dim3(nb), dim3(PTC_AD_BLOCK), 0, s, n_active, pix, (const uint8_t*)ad.flags, ad.keep, ad.block_tot, w, h, radius);
+  hipLaunchKernelGGL(k_ad_compact_scan, dim3(1), dim3(AD_SCAN_BLOCK), 0, s, nb, ad.block_tot, ad.n_out);
+  if (nb) hipLaunchKernelGGL(k_ad_compact_write, dim3(nb), dim3(PTC_AD_BLOCK), 0, s, n_active, pix, slot, (const uint8_t*)ad.keep, (const uint32_t*)ad.block_tot, pix_out, slot_out);
+}
+void pt_launch_ad_resolve(hipStream_t s, uint32_t n_owned, const uint32_t* owned, const float4* accum, const uint32_t* count, float4* radiance) {
+  if (!n_owned) return;
+  hipLaunchKernelGGL(k_ad_resolve, dim3(pt_ad_blocks(n_owned)), dim3(PTC_AD_BLOCK), 0, s, n_owned, owned, accum, count, radiance);
+}

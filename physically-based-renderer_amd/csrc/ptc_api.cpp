@@ -13,6 +13,7 @@
 #include "pt_refit.h"
 #include "pt_build.h"
 #include "pt_denoise.h"
+#include "pt_adaptive.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -181,6 +182,18 @@ struct ptc_ctx {
   int output = PTC_OUTPUT_RADIANCE;
   hipEvent_t ev_dn[4] = {nullptr, nullptr, nullptr, nullptr};   // start / stop of the last guide pass, start / stop of the last denoise
   bool ev_dn_recorded[2] = {false, false};
+  // adaptive sampling (pt_adaptive.hip).  In an adaptive frame `fr` describes the ACTIVE pixels (n_owned = their number, owned = ad_pix[ad_cur]): that is all the
+  // path kernels see of a frame; the frame's own pixels stay in owned / owned_n, where the sums, the moments and the counts live.
+  bool adaptive = false;
+  ptc_adaptive_params ad_params{};
+  DevBuf<uint32_t> ad_pix[2], ad_slot[2], ad_count, ad_block, ad_n;   // the active list (pixel, owned position), ping-pong: a decision step compacts one into the other
+  DevBuf<float2> ad_mom;
+  DevBuf<uint8_t> ad_flags, ad_keep;
+  int ad_cur = 0;
+  uint32_t ad_passes = 0;
+  double ad_seconds = 0.0;
+  hipEvent_t ev_ad[2] = {nullptr, nullptr};
+  size_t frame_batch_paths = 0;     // the path budget of a batch as ptc_frame_begin settled it: per_batch follows the active set from it
   // multi-GPU
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -418,7 +431,22 @@ LaunchCfg batch_cfg(const ptc_ctx* c, uint32_t n_paths) {
   return cfg;
 }
 
-// One wavefront batch of n samples per owned pixel on lane `l`, fully asynchronous.
+DevAdaptive dev_adaptive(const ptc_ctx* c) { return DevAdaptive{c->ad_mom.p, c->ad_count.p, c->ad_flags.p, c->ad_keep.p, c->ad_block.p, c->ad_n.p}; }
+
+// samples of one full batch of `n_pixels` pixels: as many as fit `batch_paths` split over the lanes, and 32-bit slot indices
+uint32_t batch_samples(const ptc_ctx* c, size_t n_pixels, size_t batch_paths) {
+  size_t per = !n_pixels ? 1 : batch_paths / n_pixels / (size_t)c->n_lanes;
+  if (per < 1) per = 1;
+  if (per > 0x7fffffffu) per = 0x7fffffffu;
+  {   // slot indices are 32 bits, and the segmented layout pads a batch by up to 64 slots per segment
+    const uint64_t max_slots = 0xfffffff0ull - 64ull * (uint64_t)c->cfg.shade_waves - 64ull;
+    if (n_pixels && (uint64_t)n_pixels * per > max_slots) per = max_slots / n_pixels;
+    if (per < 1) per = 1;
+  }
+  return (uint32_t)per;
+}
+
+// One wavefront batch of n samples per owned pixel (per active pixel of an adaptive frame) on lane `l`, fully asynchronous.
 int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
   const uint32_t n_paths = c->fr.n_owned * n_samples;
   Lane& ln = c->lanes[(size_t)l];
@@ -473,7 +501,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       const int prev = (int)((c->batches_issued - 1) % (uint64_t)c->n_lanes);
       if (prev != l) HIP_TRY(c, hipStreamWaitEvent(st, c->lanes[(size_t)prev].acc_done, 0));
     }
-    pt_launch_accumulate(st, c->fr, q, c->accum.p, n_samples);
+    if (c->adaptive) pt_launch_ad_accumulate(st, c->fr.n_owned, c->ad_slot[c->ad_cur].p, q.lpath, c->accum.p, dev_adaptive(c), n_samples);
+    else pt_launch_accumulate(st, c->fr, q, c->accum.p, n_samples);
     if (c->n_lanes > 1) HIP_TRY(c, hipEventRecord(ln.acc_done, st));
   }
   c->batches_issued++;
@@ -679,6 +708,9 @@ void ptc_destroy(ptc_ctx* c) {
   c->g_albedo.release(); c->g_normal.release(); c->g_pos.release(); c->dn_cv[0].release(); c->dn_cv[1].release(); c->denoised.release();
   c->g_prim.release(); c->g_uv.release(); c->g_stats.release();
   for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
+  for (auto* b : {&c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_count, &c->ad_block, &c->ad_n}) b->release();
+  c->ad_mom.release(); c->ad_flags.release(); c->ad_keep.release();
+  for (hipEvent_t e : c->ev_ad) if (e) (void)hipEventDestroy(e);
   delete c;
 }
 
@@ -1250,7 +1282,7 @@ int ptc_scene_commit(ptc_ctx* c) { return scene_commit(c, true); }
 
 int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
   { int rd = need_device(c); if (rd) return rd; }
-  c->in_frame = false; c->pending = 0; drop_guides(c);      // whatever happens below, the previous frame is over
+  c->in_frame = false; c->pending = 0; c->adaptive = false; drop_guides(c);      // whatever happens below, the previous frame is over
   if (!c->committed) return fail(c, PTC_E_STATE, "frame_begin: scene not committed");
   if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, "frame_begin: bad size");
   if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, "frame_begin: unknown integrator");
@@ -1299,15 +1331,8 @@ int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int 
       if (fit < batch_paths) batch_paths = fit;
     }
   }
-  size_t per = !n_owned ? 1 : batch_paths / n_owned / (size_t)c->n_lanes;
-  if (per < 1) per = 1;
-  if (per > 0x7fffffffu) per = 0x7fffffffu;
-  {   // slot indices are 32 bits, and the segmented layout pads a batch by up to 64 slots per segment
-    const uint64_t max_slots = 0xfffffff0ull - 64ull * (uint64_t)c->cfg.shade_waves - 64ull;
-    if (n_owned && (uint64_t)n_owned * per > max_slots) per = max_slots / n_owned;
-    if (per < 1) per = 1;
-  }
-  c->per_batch = (uint32_t)per;
+  c->frame_batch_paths = batch_paths;
+  c->per_batch = batch_samples(c, n_owned, batch_paths);
   for (auto& ln : c->lanes) HIP_TRY(c, hipMemsetAsync(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long), ln.stream));
   { int rs = sync_all_lanes(c); if (rs) return rs; }     // accum/radiance/statistics are cleared before any lane starts
   c->batches_issued = 0;
@@ -1333,6 +1358,7 @@ int ptc_frame_add_samples(ptc_ctx* c, int n_samples) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_add_samples: no frame");
   if (n_samples <= 0) return fail(c, PTC_E_ARG, "frame_add_samples: n_samples <= 0");
+  if (c->adaptive && c->fr.n_owned == 0) return PTC_OK;      // nothing is active: accepted, nothing to do
   if (!is_raster(c->integrator) && (uint64_t)c->samples_done + c->pending + (uint64_t)n_samples > (uint64_t)c->spp_total)
     return fail(c, PTC_E_ARG, "frame_add_samples: more samples than the spp_total given to frame_begin");
   c->pending += (uint32_t)n_samples;
@@ -1353,7 +1379,8 @@ int ptc_frame_resolve(ptc_ctx* c) {
   { int rf = flush(c); if (rf) return rf; }
   { int rj = join_lanes_on_stream0(c); if (rj) return rj; }
   // divisor: the samples accumulated so far, so a progressive viewer sees a correctly exposed image after every call
-  if (c->fr.n_owned && c->samples_done)
+  if (c->adaptive) { if (c->samples_done) pt_launch_ad_resolve(c->lanes[0].stream, c->owned_n, c->owned.p, c->accum.p, c->ad_count.p, c->radiance.p); }
+  else if (c->fr.n_owned && c->samples_done)
     pt_launch_resolve(c->lanes[0].stream, c->fr, c->accum.p, c->radiance.p, (float)(c->resolve_divisor ? c->resolve_divisor : c->samples_done), is_raster(c->integrator));
   HIP_TRY(c, hipGetLastError());
   return PTC_OK;
@@ -1365,6 +1392,7 @@ int ptc_frame_set_sample_range(ptc_ctx* c, uint32_t first_sample, uint32_t resol
   if (c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_set_sample_range: call it right after ptc_frame_begin, before any sample");
   if (is_raster(c->integrator)) return fail(c, PTC_E_ARG, "frame_set_sample_range: the raster integrators have one sample");
   if ((uint64_t)first_sample + (uint64_t)c->spp_total > 0xffffffffull) return fail(c, PTC_E_ARG, "frame_set_sample_range: sample indices exceed 32 bits");
+  if (c->adaptive && resolve_divisor) return fail(c, PTC_E_STATE, "frame_set_sample_range: an adaptive frame resolves every pixel by its own count, not by a divisor");
   c->sample_base = first_sample; c->resolve_divisor = resolve_divisor;
   return PTC_OK;
 }
@@ -1373,6 +1401,7 @@ int ptc_frame_checkpoint(ptc_ctx* c, float* accum_rgba, uint64_t* n_owned_pixels
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_checkpoint: no frame");
   if (is_raster(c->integrator)) return fail(c, PTC_E_ARG, "frame_checkpoint: the raster integrators have nothing to resume");
+  if (c->adaptive) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in an adaptive frame");
   { int rf = flush(c); if (rf) return rf; }
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   if (n_owned_pixels) *n_owned_pixels = c->fr.n_owned;
@@ -1385,6 +1414,7 @@ int ptc_frame_restore(ptc_ctx* c, const float* accum_rgba, uint64_t n_owned_pixe
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_restore: no frame (ptc_frame_begin with the checkpointed frame's parameters first)");
   if (!accum_rgba) return fail(c, PTC_E_ARG, "frame_restore: null pointer");
+  if (c->adaptive) return fail(c, PTC_E_STATE, "frame_restore: not available in an adaptive frame");
   if (c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_restore: call it right after ptc_frame_begin, before any sample");
   if (is_raster(c->integrator)) return fail(c, PTC_E_ARG, "frame_restore: the raster integrators have nothing to resume");
   if (n_owned_pixels != c->fr.n_owned) return fail(c, PTC_E_ARG, "frame_restore: the checkpoint is of another frame (size or tile share differ)");
@@ -1589,6 +1619,139 @@ int ptc_get_denoise_seconds(ptc_ctx* c, double* guides, double* denoise) {
     *out[k] = 1e-3 * (double)ms;
   }
   return PTC_OK;
+}
+
+// ---- adaptive sampling (pt_adaptive.hip): the active set lives in c->fr, see ptc_ctx ---------------------------------------------------
+void ptc_adaptive_default_params(ptc_adaptive_params* p) {
+  if (!p) return;
+  p->threshold = 0.05f; p->radius = 1; p->min_samples = 16; p->step_samples = 16;
+}
+
+namespace {
+int adaptive_params_ok(ptc_ctx* c, const ptc_adaptive_params& p, const char* who) {
+  if (!(p.threshold >= 0.0f) || !(p.threshold <= 3.4028235e38f)) return fail(c, PTC_E_ARG, std::string(who) + ": the threshold is negative or not finite");
+  if (p.radius < 0 || p.radius > PTC_AD_MAX_RADIUS) return fail(c, PTC_E_ARG, std::string(who) + ": radius outside 0..2");
+  if (p.min_samples < 1 || p.step_samples < 1) return fail(c, PTC_E_ARG, std::string(who) + ": min_samples / step_samples < 1");
+  return PTC_OK;
+}
+int need_adaptive_frame(ptc_ctx* c, const char* who) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->in_frame || !c->adaptive) return fail(c, PTC_E_STATE, std::string(who) + ": no adaptive frame (ptc_frame_set_adaptive right after ptc_frame_begin)");
+  return PTC_OK;
+}
+}  // namespace
+
+int ptc_frame_set_adaptive(ptc_ctx* c, const ptc_adaptive_params* params) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_set_adaptive: no frame");
+  if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame is not a PTC_INTEGRATOR_PATH frame");
+  if (c->adaptive || c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_set_adaptive: call it once, right after ptc_frame_begin, before any sample");
+  if (c->resolve_divisor) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame has a resolve divisor (ptc_frame_set_sample_range)");
+  ptc_adaptive_params p;
+  ptc_adaptive_default_params(&p);
+  if (params) p = *params;
+  { int ra = adaptive_params_ok(c, p, "frame_set_adaptive"); if (ra) return ra; }
+  const size_t n = c->owned_n, wh = (size_t)c->fr.w * (size_t)c->fr.h;
+  int rc;
+  for (int k = 0; k < 2; ++k) if ((rc = ensure_buf(c, c->ad_pix[k], n)) || (rc = ensure_buf(c, c->ad_slot[k], n))) return rc;
+  if ((rc = ensure_buf(c, c->ad_mom, n)) || (rc = ensure_buf(c, c->ad_count, n)) || (rc = ensure_buf(c, c->ad_keep, n)) || (rc = ensure_buf(c, c->ad_flags, wh)) ||
+      (rc = ensure_buf(c, c->ad_block, (size_t)pt_ad_blocks((uint32_t)n) + 1)) || (rc = ensure_buf(c, c->ad_n, 1))) return rc;
+  for (hipEvent_t& e : c->ev_ad) if (!e) HIP_TRY(c, hipEventCreate(&e));
+  hipStream_t s0 = c->lanes[0].stream;
+  HIP_TRY(c, hipMemsetAsync(c->ad_mom.p, 0, (n ? n : 1) * sizeof(float2), s0));
+  HIP_TRY(c, hipMemsetAsync(c->ad_count.p, 0, (n ? n : 1) * sizeof(uint32_t), s0));
+  HIP_TRY(c, hipMemsetAsync(c->ad_flags.p, 0, wh, s0));
+  pt_launch_ad_init(s0, (uint32_t)n, c->owned.p, c->ad_pix[0].p, c->ad_slot[0].p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(s0));      // the other lanes read these arrays too
+  c->ad_cur = 0; c->ad_passes = 0; c->ad_seconds = 0.0; c->ad_params = p;
+  c->fr.owned = c->ad_pix[0].p;              // n_owned is the frame's: everything is active
+  c->adaptive = true;
+  return PTC_OK;
+}
+
+int ptc_frame_adapt(ptc_ctx* c, uint64_t* n_active) {
+  { int ra = need_adaptive_frame(c, "frame_adapt"); if (ra) return ra; }
+  { int rf = flush(c); if (rf) return rf; }
+  const uint32_t n_in = c->fr.n_owned;
+  if (n_in == 0) { if (n_active) *n_active = 0; return PTC_OK; }
+  const uint32_t n = c->samples_done;
+  if (n == 0) return fail(c, PTC_E_STATE, "frame_adapt: the frame has no samples yet");
+  { int rj = join_lanes_on_stream0(c); if (rj) return rj; }
+  hipStream_t s0 = c->lanes[0].stream;
+  const DevAdaptive ad = dev_adaptive(c);
+  const int cur = c->ad_cur;
+  uint32_t n_out = 0;
+  HIP_TRY(c, hipEventRecord(c->ev_ad[0], s0));
+  if (n >= (uint32_t)c->spp_total) {          // the budget is spent: everything stops; no pixel is active, so no flag stays set
+    HIP_TRY(c, hipMemsetAsync(c->ad_flags.p, 0, (size_t)c->fr.w * (size_t)c->fr.h, s0));
+  } else {
+    pt_launch_ad_error(s0, n_in, c->ad_pix[cur].p, c->ad_slot[cur].p, ad, n, c->ad_params.threshold);
+    pt_launch_ad_compact(s0, n_in, c->ad_pix[cur].p, c->ad_slot[cur].p, c->ad_pix[cur ^ 1].p, c->ad_slot[cur ^ 1].p, ad, c->fr.w, c->fr.h, c->ad_params.radius);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&n_out, c->ad_n.p, sizeof n_out, hipMemcpyDeviceToHost, s0));   // the host sizes the next launches by it
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_ad[1], s0));
+  HIP_TRY(c, hipStreamSynchronize(s0));
+  { float ms = 0.0f; if (hipEventElapsedTime(&ms, c->ev_ad[0], c->ev_ad[1]) == hipSuccess) c->ad_seconds += 1e-3 * (double)ms; }
+  if (n_out > n_in) return fail(c, PTC_E_DEVICE, "frame_adapt: the compaction returned more entries than it was given");
+  c->ad_cur = cur ^ 1;
+  c->fr.n_owned = n_out; c->fr.owned = c->ad_pix[c->ad_cur].p;
+  c->per_batch = batch_samples(c, n_out, c->frame_batch_paths);      // as the set shrinks a pass still goes out as the fewest, widest launches
+  c->ad_passes++;
+  if (n_active) *n_active = n_out;
+  return PTC_OK;
+}
+
+int ptc_read_sample_counts(ptc_ctx* c, uint32_t* out) {
+  { int ra = need_adaptive_frame(c, "read_sample_counts"); if (ra) return ra; }
+  if (!out) return fail(c, PTC_E_ARG, "read_sample_counts: null pointer");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  const size_t n = c->owned_n;
+  std::vector<uint32_t> pix(n), cnt(n);
+  if (n) {
+    HIP_TRY(c, hipMemcpy(pix.data(), c->owned.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(cnt.data(), c->ad_count.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  std::memset(out, 0, (size_t)c->rad_w * (size_t)c->rad_h * sizeof(uint32_t));
+  for (size_t i = 0; i < n; ++i) out[pix[i]] = cnt[i];
+  return PTC_OK;
+}
+
+int ptc_get_adaptive_stats(ptc_ctx* c, ptc_adaptive_stats* out) {
+  { int ra = need_adaptive_frame(c, "get_adaptive_stats"); if (ra) return ra; }
+  if (!out) return fail(c, PTC_E_ARG, "get_adaptive_stats: null pointer");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  std::vector<uint32_t> cnt(c->owned_n);
+  if (!cnt.empty()) HIP_TRY(c, hipMemcpy(cnt.data(), c->ad_count.p, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  ptc_adaptive_stats s{};
+  s.owned_pixels = c->owned_n; s.active_pixels = c->fr.n_owned; s.passes = c->ad_passes; s.seconds_adapt = c->ad_seconds;
+  for (uint32_t v : cnt) { s.samples_total += v; if (v > s.max_count) s.max_count = v; }
+  *out = s;
+  return PTC_OK;
+}
+
+int ptc_render_adaptive(ptc_ctx* c, int w, int h, int max_spp, uint64_t seed, int max_bounces, const ptc_adaptive_params* params) {
+  { int rd = need_device(c); if (rd) return rd; }
+  ptc_adaptive_params p;
+  ptc_adaptive_default_params(&p);
+  if (params) p = *params;
+  { int ra = adaptive_params_ok(c, p, "render_adaptive"); if (ra) return ra; }
+  int rc = ptc_frame_begin(c, w, h, max_spp, seed, max_bounces, PTC_INTEGRATOR_PATH, 0, 1);
+  if (rc) return rc;
+  if ((rc = ptc_frame_set_adaptive(c, &p))) return rc;
+  if ((rc = ptc_frame_add_samples(c, p.min_samples < max_spp ? p.min_samples : max_spp))) return rc;
+  for (;;) {
+    uint64_t active = 0;
+    if ((rc = ptc_frame_adapt(c, &active))) return rc;
+    if (!active) break;      // converged everywhere, or the budget is spent (the step at n = max_spp empties the set)
+    const int left = max_spp - (int)c->samples_done;
+    if ((rc = ptc_frame_add_samples(c, p.step_samples < left ? p.step_samples : left))) return rc;
+  }
+  if ((rc = ptc_frame_resolve(c))) return rc;
+  return ptc_sync(c);
 }
 
 int ptc_get_stats(ptc_ctx* c, ptc_stats* out) {

@@ -161,6 +161,21 @@ public:
   auto selectOutput(int output) -> void { ck(ptc_select_output(_ctx, output)); }
   // HIP-event seconds of the last frameGuides() and the last denoise()
   auto denoiseSeconds() -> std::array<double, 2> { std::array<double, 2> t{0.0, 0.0}; ck(ptc_get_denoise_seconds(_ctx, &t[0], &t[1])); return t; }
+  // ---- adaptive sampling (include/ptc.h): samples go to the pixels whose estimate has not converged; at most maxSpp per pixel ----
+  static auto adaptiveDefaults() -> ptc_adaptive_params { ptc_adaptive_params p; ptc_adaptive_default_params(&p); return p; }
+  auto renderAdaptive(int w, int h, int maxSpp, std::uint64_t seed, int maxBounces, ptc_adaptive_params const* params = nullptr) -> std::vector<float> {
+    ck(ptc_render_adaptive(_ctx, w, h, maxSpp, seed, maxBounces, params));
+    return readRadiance(w, h);
+  }
+  // the caller-driven form: after ptc_frame_begin, setAdaptive(); then ptc_frame_add_samples feeds the active pixels and adapt() takes the converged ones out
+  auto setAdaptive(ptc_adaptive_params const* params = nullptr) -> void { ck(ptc_frame_set_adaptive(_ctx, params)); }
+  auto adapt() -> std::uint64_t { std::uint64_t n = 0; ck(ptc_frame_adapt(_ctx, &n)); return n; }
+  auto sampleCounts() -> std::vector<std::uint32_t> {
+    std::vector<std::uint32_t> out((std::size_t)_w * _h);
+    ck(ptc_read_sample_counts(_ctx, out.data()));
+    return out;
+  }
+  auto adaptiveStats() -> ptc_adaptive_stats { ptc_adaptive_stats s; ck(ptc_get_adaptive_stats(_ctx, &s)); return s; }
   auto stats() -> ptc_stats { ptc_stats s; ck(ptc_get_stats(_ctx, &s)); return s; }
   auto handle() -> ptc_ctx* { return _ctx; }
 

@@ -2,9 +2,14 @@
 //   ptc_render (--scene cornell|sphere | --gltf file.glb [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
 //              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--guides PREFIX]
+//              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 // --denoise: first-hit guides + the variance-guided a-trous filter (ptc_frame_guides, ptc_denoise) after the render; every output is then the denoised
 // image.  --denoise-iters N: N iterations instead of the default 4 (implies --denoise).  --guides PREFIX: PREFIX_albedo.pfm, PREFIX_normal.pfm and
 // PREFIX_depth.pfm (the depth in all three channels) beside the image, for a denoiser outside the library.  With --gpus N device D denoises after the reduce.
+// --adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]: adaptive sampling (ptc_render_adaptive): --spp is then the
+// per-pixel maximum, a pixel stops when the relative standard error of its mean luminance is <= THRESH and no pixel within R of it (default 1) is above; N
+// samples before the first decision and between decisions (default 16 each).  --counts writes the per-pixel sample counts (all three channels).  One context
+// only (not with --gpus), path integrator only.
 // --gpus N: devices D..D+N-1 share the frame by 32x32-pixel tiles, one RCCL reduce brings it to device D (ptc_group_*).
 // --raster16: the reference's Blinn-Phong pass lit from its G-buffer formats; --half writes the RGBA16F buffer (raw little-endian halves).
 // --env: ordinary lat-long RGB environment map (PFM or Radiance .hdr, top row = up).  The reference's world is y-down (up = -y, CameraData.hpp:28) and
@@ -120,6 +125,9 @@ int main(int argc, char** argv) {
   bool denoise = false;
   int denoiseIters = -1;                     // -1: the library's default
   std::uint64_t seed = 1;
+  bool adaptive = false;
+  ptc_adaptive_params ap = pbr::PathTraceRenderSystem::adaptiveDefaults();
+  std::string countsPath;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -129,6 +137,8 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = std::atoi(next()); else if (a == "--half") halfPath = next(); else if (a == "--raster16") integrator = PTC_INTEGRATOR_RASTER_GBUFFER16;
     else if (a == "--gltf") gltf = next();
     else if (a == "--denoise") denoise = true; else if (a == "--denoise-iters") { denoiseIters = std::atoi(next()); denoise = true; } else if (a == "--guides") guidesPrefix = next();
+    else if (a == "--adaptive") { ap.threshold = (float)std::atof(next()); adaptive = true; } else if (a == "--min-spp") ap.min_samples = std::atoi(next());
+    else if (a == "--spp-step") ap.step_samples = std::atoi(next()); else if (a == "--adaptive-radius") ap.radius = std::atoi(next()); else if (a == "--counts") countsPath = next();
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -147,6 +157,8 @@ int main(int argc, char** argv) {
   }
   try {
     if (gpus < 0) throw std::runtime_error("--gpus must be >= 1");
+    if (adaptive && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--adaptive renders on one context with the path integrator (not with --gpus / --raster)");
+    if (!adaptive && !countsPath.empty()) throw std::runtime_error("--counts needs --adaptive");
     if (gltf.empty() && (!envPath.empty() || sky)) throw std::runtime_error("--env / --sky light a --gltf scene; the built-in scenes carry their own lights");
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
     if (deviceBvh >= 0) rs.setDeviceBuilder(deviceBvh);
@@ -196,7 +208,7 @@ int main(int argc, char** argv) {
     if (gpus == 0) {
       single.reset(new pbr::PathTraceRenderSystem(device));
       buildScene(*single);
-      img = single->render(w, h, spp, seed, bounces, integrator);
+      img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : single->render(w, h, spp, seed, bounces, integrator);
     } else {
       std::vector<int> ids;
       for (int i = 0; i < gpus; ++i) ids.push_back(device + i);
@@ -209,6 +221,17 @@ int main(int argc, char** argv) {
     if (!gltf.empty()) scene = gltf;
     ptc_stats st = rs.stats();
     for (int i = 1; i < gpus; ++i) { const ptc_stats o = group->device(i).stats(); st.paths += o.paths; st.node_visits_closest += o.node_visits_closest; st.node_visits_any += o.node_visits_any; }
+    if (adaptive) {
+      const ptc_adaptive_stats as = rs.adaptiveStats();
+      std::printf("{\"adaptive_threshold\": %g, \"mean_spp\": %.3f, \"max_spp\": %u, \"passes\": %u, \"seconds_adapt\": %.6f}\n", (double)ap.threshold,
+                  as.owned_pixels ? (double)as.samples_total / (double)as.owned_pixels : 0.0, as.max_count, as.passes, as.seconds_adapt);
+      if (!countsPath.empty()) {
+        const std::vector<std::uint32_t> cnt = rs.sampleCounts();
+        std::vector<float> cf(cnt.size() * 4);
+        for (std::size_t p = 0; p < cnt.size(); ++p) { cf[p * 4] = cf[p * 4 + 1] = cf[p * 4 + 2] = (float)cnt[p]; cf[p * 4 + 3] = 1.0f; }
+        pbr::image::write_pfm(countsPath, cf.data(), w, h);
+      }
+    }
     if (denoise || !guidesPrefix.empty()) {
       if (integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--denoise / --guides need the path integrator (the raster passes are noise-free)");
       rs.frameGuides();

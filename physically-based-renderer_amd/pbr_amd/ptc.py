@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ptc_debug_get_description", "ptc_debug_get_material", "ptc_debug_get_texture", "ptc_debug_get_internals", "ptc_debug_host_build_id", "ptc_debug_get_shading_tables", "ptc_debug_refit_host_parts", "ptc_debug_commit_host_parts",
     "ptc_read_radiance_rgba16f", "ptc_radiance_rgba16f_device_ptr",
     "ptc_frame_guides", "ptc_read_guide_rgba32f", "ptc_read_guide_hit", "ptc_denoise_default_params", "ptc_denoise", "ptc_select_output", "ptc_get_denoise_seconds",
+    "ptc_adaptive_default_params", "ptc_frame_set_adaptive", "ptc_frame_adapt", "ptc_read_sample_counts", "ptc_render_adaptive", "ptc_get_adaptive_stats",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
@@ -64,6 +65,21 @@ class PtcStats(C.Structure):
 
 class PtcDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcAdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("radius", C.c_int), ("min_samples", C.c_int), ("step_samples", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcAdaptiveStats(C.Structure):
+    _fields_ = [("owned_pixels", C.c_uint64), ("active_pixels", C.c_uint64), ("samples_total", C.c_uint64),
+                ("passes", C.c_uint32), ("max_count", C.c_uint32), ("seconds_adapt", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -153,6 +169,13 @@ def load_library():
     L.ptc_denoise.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
     L.ptc_select_output.argtypes = [vp, C.c_int]
     L.ptc_get_denoise_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ptc_adaptive_default_params.argtypes = [C.POINTER(PtcAdaptiveParams)]
+    L.ptc_adaptive_default_params.restype = None
+    L.ptc_frame_set_adaptive.argtypes = [vp, C.POINTER(PtcAdaptiveParams)]
+    L.ptc_frame_adapt.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.ptc_read_sample_counts.argtypes = [vp, u32p]
+    L.ptc_render_adaptive.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(PtcAdaptiveParams)]
+    L.ptc_get_adaptive_stats.argtypes = [vp, C.POINTER(PtcAdaptiveStats)]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -384,6 +407,50 @@ class PathTracer:
         g, d = C.c_double(0), C.c_double(0)
         self._ck(self._L.ptc_get_denoise_seconds(self._h, C.byref(g), C.byref(d)))
         return g.value, d.value
+
+    # ---- adaptive sampling ------------------------------------------------------------------------------
+    @staticmethod
+    def adaptive_default_params():
+        p = PtcAdaptiveParams()
+        load_library().ptc_adaptive_default_params(C.byref(p))
+        return p.as_dict()
+
+    def _adaptive_params(self, params):
+        p = PtcAdaptiveParams()
+        self._L.ptc_adaptive_default_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(PtcAdaptiveParams._fields_):
+                raise TypeError(f"adaptive sampling: unknown parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def frame_set_adaptive(self, **params):
+        """ptc_frame_set_adaptive, right after frame_begin: add_samples then feeds the active pixels only.  Keywords (threshold, radius, min_samples,
+        step_samples) replace the defaults."""
+        self._ck(self._L.ptc_frame_set_adaptive(self._h, C.byref(self._adaptive_params(params))))
+
+    def frame_adapt(self):
+        """ptc_frame_adapt: one decision step; returns the number of pixels still active."""
+        n = C.c_uint64(0)
+        self._ck(self._L.ptc_frame_adapt(self._h, C.byref(n)))
+        return int(n.value)
+
+    def read_sample_counts(self):
+        """(h, w) uint32: samples every pixel of the adaptive frame has received, 0 where this context does not own the pixel."""
+        out = np.zeros((self._h_px, self._w), np.uint32)
+        self._ck(self._L.ptc_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def render_adaptive(self, w, h, max_spp, seed=1, max_bounces=8, **params):
+        """ptc_render_adaptive: at most max_spp samples per pixel, fewer where the estimate has converged; returns the image (read_sample_counts has the counts)."""
+        self._ck(self._L.ptc_render_adaptive(self._h, w, h, max_spp, seed, max_bounces, C.byref(self._adaptive_params(params))))
+        self._w, self._h_px = w, h
+        return self.read_radiance()
+
+    def adaptive_stats(self):
+        s = PtcAdaptiveStats()
+        self._ck(self._L.ptc_get_adaptive_stats(self._h, C.byref(s)))
+        return s.as_dict()
 
     # ---- multi-GPU (RCCL through the C-ABI) ---------------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, n_ranks: int):
