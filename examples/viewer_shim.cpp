@@ -11,7 +11,10 @@
 //   shim::Frame::rotate    App::update's per-frame node rotation    src/gltf_viewer/App.cpp:306-313   (refit; a rebuild on the device when the refitted tree has become too costly)
 // main() drives them the way App::run does: load, then a loop of displayed frames, one sample per frame while the camera is still.
 //
-// usage: viewer_shim DEVICE [frames [rebuild_ratio]]    DEVICE -1 = description only (PTC_DEVICE_NONE): the scene half runs, the render half reports
+// usage: viewer_shim DEVICE [frames [rebuild_ratio [temporal]]]    the word "temporal" opts in to the temporal path: every displayed frame is a frame of its own
+//                                       (1 spp, its own seed) whose result is blended into the reprojected history (ptc_temporal_accumulate) and filtered
+//                                       (ptc_denoise_accumulated) — for a scene or camera that moves every frame, where a progressive frame never gets past 1 spp.
+//                                       DEVICE -1 = description only (PTC_DEVICE_NONE): the scene half runs, the render half reports
 //                                       "no device" and the program still exits 0 — that is what the CPU test runs.
 #include <pbr_pt.hpp>
 
@@ -54,9 +57,11 @@ inline std::vector<int> uploadNode(ptc_ctx* ctx, std::vector<int> const& meshIds
 // App::recordCommands: was `_pbrSystem.render(cmdBuffer, _scene, _gBuffer, _hdrImage.getImage(), extent);`
 class Frame {
 public:
-  Frame(ptc_ctx* ctx, int w, int h, int sppBudget, std::uint64_t seed) : _ctx(ctx), _w(w), _h(h), _budget(sppBudget), _seed(seed), _staging16((std::size_t)w * h * 4) {}
+  Frame(ptc_ctx* ctx, int w, int h, int sppBudget, std::uint64_t seed, bool temporal = false)
+      : _ctx(ctx), _w(w), _h(h), _budget(sppBudget), _seed(seed), _temporal(temporal), _staging16((std::size_t)w * h * 4) {}
   // one displayed frame; returns false when the context has no device (description-only run)
   bool record(pbr::ViewerCamera const& cam, bool sceneOrCameraChanged) {
+    if (_temporal) return recordTemporal(cam);
     const bool fresh = sceneOrCameraChanged || !_begun;
     if (fresh) {                                              // a new camera ends the validity of the guides: set it with the frame it begins
       const auto target = cam.target();
@@ -90,13 +95,33 @@ public:
       ++_rebuilds;
     }
   }
+  // the temporal path: a 1-spp frame per displayed frame, each with a seed of its own; what the earlier frames found comes back through the history, which
+  // survives the new camera, ptc_scene_refit and ptc_scene_rebuild (the primitive ids stay), so `rotate` needs no change
+  bool recordTemporal(pbr::ViewerCamera const& cam) {
+    const auto target = cam.target();
+    ck(_ctx, ptc_set_camera(_ctx, cam.position.data(), target.data(), cam.fov, (float)_w / (float)_h));
+    const int rc = ptc_frame_begin(_ctx, _w, _h, 1, _seed + _shown++, 8, PTC_INTEGRATOR_PATH, 0, 1);
+    if (rc == PTC_E_DEVICE) return false;
+    ck(_ctx, rc);
+    ck(_ctx, ptc_frame_add_samples(_ctx, 1));
+    ck(_ctx, ptc_frame_guides(_ctx));
+    ck(_ctx, ptc_frame_resolve(_ctx));
+    ck(_ctx, ptc_temporal_accumulate(_ctx, nullptr));          // reproject the history through this frame's guides and blend the sample in (default parameters)
+    ck(_ctx, ptc_denoise_accumulated(_ctx, nullptr));          // the filter over the accumulated image, with the temporal variance where the history is long enough
+    ck(_ctx, ptc_select_output(_ctx, PTC_OUTPUT_DENOISED));
+    ck(_ctx, ptc_read_radiance_rgba16f(_ctx, _staging16.data()));
+    return true;
+  }
   [[nodiscard]] auto staging() const -> std::vector<std::uint16_t> const& { return _staging16; }
   [[nodiscard]] auto rebuilds() const -> int { return _rebuilds; }
+  [[nodiscard]] auto shown() const -> std::uint64_t { return _shown; }      // frames the temporal path began
 
 private:
   ptc_ctx* _ctx;
   int _w, _h, _budget;
   std::uint64_t _seed;
+  bool _temporal = false;
+  std::uint64_t _shown = 0;
   bool _begun = false;
   int _rebuilds = 0;
   std::vector<std::uint16_t> _staging16;
@@ -108,6 +133,7 @@ int main(int argc, char** argv) {
   const int device = argc > 1 ? std::atoi(argv[1]) : PTC_DEVICE_NONE;
   const int frames = argc > 2 ? std::atoi(argv[2]) : 4;
   const double rebuildRatio = argc > 3 ? std::atof(argv[3]) : 1.2;
+  const bool temporal = argc > 4 && std::strcmp(argv[4], "temporal") == 0;
   ptc_ctx* ctx = ptc_create(device);
   if (!ctx) { std::fprintf(stderr, "viewer_shim: %s\n", ptc_last_error(nullptr)); return 1; }
   try {
@@ -135,7 +161,7 @@ int main(int argc, char** argv) {
     ptc_stats st;
     shim::ck(ctx, ptc_get_stats(ctx, &st));
     // ---- App::run: displayed frames ----
-    shim::Frame frame(ctx, 160, 90, 64, 7);
+    shim::Frame frame(ctx, 160, 90, 64, 7, temporal);
     bool rendered = true;
     double sum = 0.0;
     for (int f = 0; f < frames && rendered; ++f) {
@@ -151,6 +177,7 @@ int main(int argc, char** argv) {
     if (rendered) for (std::uint16_t h : frame.staging()) sum += (double)h;
     std::printf("{\"device\": %d, \"triangles\": %u, \"rendered\": %s, \"frames\": %d, \"staging_sum\": %.0f, \"rebuilds\": %d}\n", device, st.n_triangles, rendered ? "true" : "false", frames, sum,
                 frame.rebuilds());
+    if (temporal) std::printf("{\"temporal\": true, \"temporal_frames_begun\": %llu}\n", (unsigned long long)frame.shown());
     if (!rendered) std::printf("viewer_shim: no device (PTC_DEVICE_NONE): scene described and committed, render calls answered PTC_E_DEVICE\n");
   } catch (std::exception const& e) {
     std::fprintf(stderr, "viewer_shim: %s\n", e.what());

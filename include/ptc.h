@@ -376,6 +376,51 @@ typedef struct ptc_adaptive_stats {
 } ptc_adaptive_stats;
 int  ptc_get_adaptive_stats(ptc_ctx*, ptc_adaptive_stats*);
 
+/* ---- temporal accumulation: reproject the previous frame's accumulated image and blend the new frame in ---------------------------
+ * A viewer that adds one sample per displayed frame starts every frame from nothing; these calls carry the previous frames' result across camera
+ * motion, ptc_scene_refit and ptc_scene_rebuild.  Nothing here changes what a context that never calls them computes.  DESIGN.md §8c has the
+ * specification; in short, per class-1 pixel: the hit point's position in the HISTORY's frame (the hit primitive's positions as they were then, at the
+ * barycentrics of the guide hit) is projected through the history's camera; the four bilinear taps around it are valid where they lie inside the image,
+ * are class 1, hold history (n > 0) and lie within sigma_z pixel footprints of the tap's plane (the history's normal, depth and position); the valid taps'
+ * weighted mean H of the demodulated colour, of the luminance moments and of n is blended with this frame's D = radiance / max(albedo, 1e-3):
+ * n_new = min(n + 1, max_history), a = 1 / n_new, D_new = (1 - a) H + a D.  Pixels of another class copy the radiance bit for bit.
+ *
+ * ptc_temporal_accumulate: needs valid guides of the current frame (PTC_E_STATE otherwise); reads the radiance buffer as it lies (after
+ *   ptc_frame_resolve, ptc_comm_reduce_radiance or ptc_write_radiance_rgba32f) and never writes it; writes the accumulated image into a buffer of its own and
+ *   replaces the context's history by this frame's state.  Queued on the context's stream; the frame in progress is not disturbed (sums, counts, held-back
+ *   samples, ptc_stats, guides).  params == NULL: the defaults.  PTC_E_ARG, and nothing changed, for max_history outside 1..1024 or a negative or non-finite
+ *   sigma_z.  A call refused with PTC_E_ARG or PTC_E_STATE leaves the history as it is; one that fails for lack of memory (PTC_E_NOMEM, PTC_E_DEVICE) drops it.
+ * The history survives ptc_frame_begin, ptc_set_camera, ptc_scene_refit and ptc_scene_rebuild (and ptc_group_scene_refit).  ptc_temporal_reset, ptc_scene_begin
+ *   (the scene whose shading records the history reads goes) and every commit — ptc_scene_commit, and ptc_group_scene_commit on every context of the group: new
+ *   primitive ids — drop it; a frame of another size, or another `demodulate`, drops it silently at the next accumulate.  Without history every pixel is a
+ *   first frame (n_new = 1).
+ * ptc_select_output(PTC_OUTPUT_ACCUMULATED): the four read-backs serve the accumulated image; PTC_E_STATE before the frame's first ptc_temporal_accumulate.
+ * ptc_denoise_accumulated: ptc_denoise's iterations over the accumulated image into the denoised buffer (PTC_OUTPUT_DENOISED then serves it); the variance
+ *   is a Var_t, the variance of the accumulated mean, where n_new >= 4, and the 7x7 spatial estimate over lum(D_new) elsewhere.  PTC_E_STATE before the frame's
+ *   accumulate, PTC_E_ARG if params->demodulate differs from the accumulate's (and for what ptc_denoise refuses).
+ * ptc_read_temporal_rgba32f: the state the last accumulate left, w*h*4 floats each, w x h the size of the frame it accumulated: PTC_TEMPORAL_HISTORY (D_new.rgb, n_new), PTC_TEMPORAL_MOMENTS
+ *   (m1, m2, Var_t, a), PTC_TEMPORAL_MOTION (x_prev, y_prev, W, reprojected n; zeros without history or behind the history's camera), and the two guide copies
+ *   the history keeps of its frame, PTC_TEMPORAL_NORMAL_DEPTH (N, Z) and PTC_TEMPORAL_POSITION_CLASS (P, K).  PTC_E_STATE without history, and
+ *   when a ptc_frame_begin with another size came after the accumulate (the history is then of a size the caller's buffer is not: accumulate first).
+ * ptc_get_temporal_seconds: HIP-event time of the last ptc_temporal_accumulate (0 when there was none). */
+enum { PTC_OUTPUT_ACCUMULATED = 2 };
+enum { PTC_TEMPORAL_HISTORY = 0,   /* (D.rgb, n)                         */
+       PTC_TEMPORAL_MOMENTS = 1,   /* (m1, m2, Var_t, a)                 */
+       PTC_TEMPORAL_MOTION  = 2,   /* (x_prev, y_prev, W, n_reprojected) */
+       PTC_TEMPORAL_NORMAL_DEPTH = 3,     /* the history's copy of its frame's (N, Z) guide */
+       PTC_TEMPORAL_POSITION_CLASS = 4 }; /* the history's copy of its frame's (P, K)       */
+typedef struct ptc_temporal_params {
+  int   max_history;  /* 1..1024 (default 32)                                          */
+  float sigma_z;      /* plane tolerance of a history tap, in pixel footprints (1)     */
+  int   demodulate;   /* accumulate radiance / albedo (1)                              */
+} ptc_temporal_params;
+void ptc_temporal_default_params(ptc_temporal_params*);
+int  ptc_temporal_accumulate(ptc_ctx*, const ptc_temporal_params*);   /* NULL: the defaults */
+int  ptc_temporal_reset(ptc_ctx*);
+int  ptc_read_temporal_rgba32f(ptc_ctx*, int which, float* out);      /* w*h*4 floats, w x h of the current (= the accumulated) frame */
+int  ptc_denoise_accumulated(ptc_ctx*, const ptc_denoise_params*);    /* NULL: the defaults */
+int  ptc_get_temporal_seconds(ptc_ctx*, double* accumulate);
+
 /* ---- multi-GPU: tiles shard over devices, one RCCL reduce brings the framebuffer to the root -----------
  * The reference has no multi-device path (one vk::Device, core/GpuHandle.cpp:94-101); this is BASELINE.json's
  * "independent pixel/sample tiles shard across the 8 GPUs of one node with an RCCL reduce onto rank 0".

@@ -32,7 +32,11 @@ DN_DEV float4 dn_demodulate(float4 c, float4 ak, int demodulate) {
 #define DN_PREP_HALO 3
 #define DN_PREP_TW (DN_BW + 2 * DN_PREP_HALO)
 #define DN_PREP_TH (DN_BH + 2 * DN_PREP_HALO)
-__global__ __launch_bounds__(DN_BW * DN_BH) void k_dn_prepare(DenoiseArgs a, float4* cv_out) {
+// colour: the filter's input, demodulated here when a.demodulate is set (the radiance), or a (D.rgb, n) image that is demodulated already (a.demodulate = 0:
+// the temporal accumulation's).  TVAR: tvar holds (-, -, Var_t, a) per pixel, and where n >= 4 the variance is a Var_t, the variance of the accumulated mean,
+// instead of the 7x7 estimate.
+template <bool TVAR>
+__global__ __launch_bounds__(DN_BW * DN_BH) void k_dn_prepare(DenoiseArgs a, const float4* __restrict__ colour, const float4* __restrict__ tvar, float4* cv_out) {
   __shared__ float4 s_nl[DN_PREP_TW * DN_PREP_TH];   // (N.xyz, L)
   __shared__ float s_k[DN_PREP_TW * DN_PREP_TH];     // class, -1 outside the image
   const int tx0 = (int)blockIdx.x * DN_BW - DN_PREP_HALO, ty0 = (int)blockIdx.y * DN_BH - DN_PREP_HALO;
@@ -43,7 +47,7 @@ __global__ __launch_bounds__(DN_BW * DN_BH) void k_dn_prepare(DenoiseArgs a, flo
     if (gx >= 0 && gx < a.w && gy >= 0 && gy < a.h) {
       const size_t g = (size_t)gy * (size_t)a.w + (size_t)gx;
       const float4 ak = a.g.albedo_class[g], nz = a.g.normal_depth[g];
-      const float4 d = dn_demodulate(a.radiance[g], ak, a.demodulate);
+      const float4 d = dn_demodulate(colour[g], ak, a.demodulate);
       nl = make_float4(nz.x, nz.y, nz.z, dn_lum(d.x, d.y, d.z));
       k = ak.w;
     }
@@ -55,9 +59,12 @@ __global__ __launch_bounds__(DN_BW * DN_BH) void k_dn_prepare(DenoiseArgs a, flo
   if (x >= a.w || y >= a.h) return;
   const size_t p = (size_t)y * (size_t)a.w + (size_t)x;
   const float4 akp = a.g.albedo_class[p];
-  const float4 d = dn_demodulate(a.radiance[p], akp, a.demodulate);
+  const float4 d = dn_demodulate(colour[p], akp, a.demodulate);
   float var = 0.0f;
-  if (akp.w == 1.0f) {
+  if (TVAR && akp.w == 1.0f && d.w >= 4.0f) {
+    const float4 t = tvar[p];
+    var = t.w * t.z;
+  } else if (akp.w == 1.0f) {
     const float4 np = s_nl[(ly + DN_PREP_HALO) * DN_PREP_TW + lx + DN_PREP_HALO];
     float m1 = 0.0f, m2 = 0.0f, cnt = 0.0f;
     for (int dy = 0; dy < 2 * DN_PREP_HALO + 1; ++dy) {
@@ -169,9 +176,10 @@ template <int S> void launch_atrous(hipStream_t s, const DenoiseArgs& a, int ste
 }
 }  // namespace
 
-void pt_launch_denoise_prepare(hipStream_t s, const DenoiseArgs& a, float4* cv_out) {
+void pt_launch_denoise_prepare(hipStream_t s, const DenoiseArgs& a, const float4* colour, const float4* tvar, float4* cv_out) {
   const dim3 grid((unsigned)((a.w + DN_BW - 1) / DN_BW), (unsigned)((a.h + DN_BH - 1) / DN_BH));
-  hipLaunchKernelGGL(k_dn_prepare, grid, dim3(DN_BW * DN_BH), 0, s, a, cv_out);
+  if (tvar) hipLaunchKernelGGL(k_dn_prepare<true>, grid, dim3(DN_BW * DN_BH), 0, s, a, colour, tvar, cv_out);
+  else hipLaunchKernelGGL(k_dn_prepare<false>, grid, dim3(DN_BW * DN_BH), 0, s, a, colour, tvar, cv_out);
 }
 void pt_launch_denoise_iteration(hipStream_t s, const DenoiseArgs& a, int iteration, const float4* cv_in, float4* out, bool last) {
   const int step = 1 << iteration;

@@ -14,6 +14,7 @@
 #include "pt_build.h"
 #include "pt_denoise.h"
 #include "pt_adaptive.h"
+#include "pt_temporal.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -194,6 +195,18 @@ struct ptc_ctx {
   double ad_seconds = 0.0;
   hipEvent_t ev_ad[2] = {nullptr, nullptr};
   size_t frame_batch_paths = 0;     // the path budget of a batch as ptc_frame_begin settled it: per_batch follows the active set from it
+  // temporal accumulation (pt_temporal.hip).  The history is the state the last ptc_temporal_accumulate left: set tp_cur of the two ping-pong sets, the camera and
+  // the size of its frame.  It outlives frames, cameras, refits and rebuilds; the accumulated image is the current frame's (drop_guides ends its validity).
+  DevBuf<float4> tp_dn[2], tp_mom[2], tp_nz[2], tp_pk[2], tp_motion, tp_accum;
+  DevBuf<float4> tp_snap;           // the position snapshot: 3 x float4 per primitive as the shading records held them when the history was written
+  bool tp_snap_current = false;     // false: the shading records in HBM still are those of the history's frame (nothing moved since), the snapshot is not needed;
+                                    // true: a refit or rebuild came after the history, tp_snap holds the positions it was about to overwrite
+  bool tp_live = false;             // there is a history
+  int tp_cur = 0, tp_w = 0, tp_h = 0, tp_demodulate = 0;
+  DevCamera tp_cam{};
+  bool tp_accum_valid = false;      // the current frame has been accumulated: tp_accum holds its accumulated image
+  hipEvent_t ev_tp[2] = {nullptr, nullptr};
+  bool ev_tp_recorded = false;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -217,9 +230,12 @@ constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray 
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 int fail(ptc_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; return code; }
 // the frame is over or the scene changed: its guides and its denoised image go with it, the read-backs serve the radiance again
-void drop_guides(ptc_ctx* c) { c->guides_valid = false; c->denoised_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
+// the temporal history is about the primitive ids of one committed scene: whatever brings another scene (ptc_scene_begin; every kind of commit, through
+// commit_upload(Upload::NewScene)) ends it, and with it the position snapshot's claim to be current.  Refits and rebuilds keep the ids and the history.
+void drop_history(ptc_ctx* c) { c->tp_live = false; c->tp_snap_current = false; }
+void drop_guides(ptc_ctx* c) { c->guides_valid = false; c->denoised_valid = false; c->tp_accum_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
 // the image ptc_read_radiance_rgba32f / _rgba16f / ptc_tonemap_rgba8 serve (ptc_select_output)
-const float4* served_image(const ptc_ctx* c) { return c->output == PTC_OUTPUT_DENOISED ? c->denoised.p : c->radiance.p; }
+const float4* served_image(const ptc_ctx* c) { return c->output == PTC_OUTPUT_DENOISED ? c->denoised.p : c->output == PTC_OUTPUT_ACCUMULATED ? c->tp_accum.p : c->radiance.p; }
 const char* const kNoDevice = "this context has no device (PTC_DEVICE_NONE): the call needs a gfx950 GPU; there is no CPU path";
 
 #define HIP_TRY(c, expr)                                                                                 \
@@ -551,6 +567,20 @@ int join_lanes_on_stream0(ptc_ctx* c) {
   return PTC_OK;
 }
 
+// A refit or a rebuild is about to overwrite the shading records.  A live temporal history whose frame saw the records as they lie now keeps their positions: the
+// next ptc_temporal_accumulate needs where every primitive WAS.  Queued on stream 0; the callers wait for the lanes before they touch the scene.  A static scene
+// never comes here, and of several refits between two accumulates only the first copies.
+int temporal_keep_positions(ptc_ctx* c) {
+  if (!c->tp_live || c->tp_snap_current || c->device < 0) return PTC_OK;
+  const uint32_t n_prims = c->built->n_tris;
+  int rc = ensure_buf(c, c->tp_snap, (size_t)3 * n_prims);
+  if (rc) return rc;
+  pt_launch_temporal_snapshot(c->lanes[0].stream, c->scene.dsc.shade, c->scene.dsc.shade_stride, n_prims, c->tp_snap.p);
+  HIP_TRY(c, hipGetLastError());
+  c->tp_snap_current = true;
+  return PTC_OK;
+}
+
 int need_device(ptc_ctx* c) {
   if (!c) return PTC_E_ARG;
   if (c->device < 0) return fail(c, PTC_E_DEVICE, kNoDevice);
@@ -711,6 +741,9 @@ void ptc_destroy(ptc_ctx* c) {
   for (auto* b : {&c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_count, &c->ad_block, &c->ad_n}) b->release();
   c->ad_mom.release(); c->ad_flags.release(); c->ad_keep.release();
   for (hipEvent_t e : c->ev_ad) if (e) (void)hipEventDestroy(e);
+  for (int k = 0; k < 2; ++k) { c->tp_dn[k].release(); c->tp_mom[k].release(); c->tp_nz[k].release(); c->tp_pk[k].release(); }
+  c->tp_motion.release(); c->tp_accum.release(); c->tp_snap.release();
+  for (hipEvent_t e : c->ev_tp) if (e) (void)hipEventDestroy(e);
   delete c;
 }
 
@@ -725,6 +758,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->mats.clear(); c->meshes.clear(); c->insts.clear(); c->texs.clear(); c->env = HostEnv{}; c->tex_linear = 0;
   c->bvh_builder = c->bvh_default;
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
+  drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   release_scene(c);
   return PTC_OK;
 }
@@ -789,14 +823,16 @@ int ptc_add_instance_matrix(ptc_ctx* c, int mesh, const float model[16]) {
 }
 
 namespace {
-int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool skeleton = false);
+// what a commit_upload is for: a commit brings new primitive ids (the temporal history goes), a refit or rebuild that has to lay the arrays out anew keeps them
+enum class Upload { NewScene, SameScene };
+int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload what, bool skeleton = false);
 // Device half of a refit: c->built holds the refitted arrays.  same_sizes: overwrite in place what depends on the vertex positions (textures,
 // environment and materials stay where they are); else (an emitter appeared or vanished under a degenerate scale) upload everything.
 int refit_upload(ptc_ctx* c, bool same_sizes, std::chrono::steady_clock::time_point t0) {
   const HostBuilt& B = *c->built;
   DevScene& d = c->scene.dsc;
   c->scene.host_stale = false; c->scene.last_refit_on_device = false;
-  if (!same_sizes) return commit_upload(c, t0);
+  if (!same_sizes) return commit_upload(c, t0, Upload::SameScene);
   HIP_TRY(c, hipMemcpy((void*)d.recs, B.recs.data(), B.recs.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy((void*)d.shade, B.shade.data(), B.shade.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy((void*)d.lights, B.lights.data(), B.lights.size() * 4, hipMemcpyHostToDevice));
@@ -1019,7 +1055,7 @@ int host_build_and_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, 
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
   const ptc_stats keep = c->stats;
   c->built = built;
-  const int rc = commit_upload(c, t0);
+  const int rc = commit_upload(c, t0, Upload::SameScene);
   if (rc) return rc;
   c->scene.last_refit_on_device = false;
   const double dt = c->stats.seconds_commit;
@@ -1052,6 +1088,7 @@ int ptc_scene_refit(ptc_ctx* c) {
   if (c->device >= 0) {
     HIP_TRY(c, hipSetDevice(c->device));
     { int rf = flush(c); if (rf) return rf; }
+    { int rt = temporal_keep_positions(c); if (rt) return rt; }
     { int rs = sync_all_lanes(c); if (rs) return rs; }
   }
   const auto t0 = std::chrono::steady_clock::now();
@@ -1081,6 +1118,7 @@ int ptc_scene_rebuild(ptc_ctx* c) {
   if (!c->committed) return fail(c, PTC_E_STATE, "scene_rebuild: scene not committed");
   if (!description_matches_commit(c)) return fail(c, PTC_E_STATE, kDescriptionChanged);
   { int rf = flush(c); if (rf) return rf; }
+  { int rt = temporal_keep_positions(c); if (rt) return rt; }
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   const auto t0 = std::chrono::steady_clock::now();
   if (c->built.use_count() > 1) c->built = std::make_shared<HostBuilt>(*c->built);      // a group shares one build: this context now gets its own
@@ -1156,7 +1194,8 @@ int commit_finish(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
 }
 // Device half of a commit: upload c->built, size the launches.  The caller has set c->built, the camera and seconds_commit's start.
 // skeleton: c->built is ptc_build_skeleton's — the tables are uploaded, the shading records allocated and zeroed, there is no tree yet: device_commit goes on from here.
-int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool skeleton) {
+int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload what, bool skeleton) {
+  if (what == Upload::NewScene) drop_history(c);      // every commit passes here — ptc_scene_commit on the host or on the device, each context of ptc_group_scene_commit
   ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
   c->in_frame = false; c->pending = 0; drop_guides(c);
   c->committed = false;
@@ -1230,7 +1269,7 @@ int device_commit(ptc_ctx* c, std::chrono::steady_clock::time_point t0) {
   if (built->n_tris < 2u) return 1;
   c->built = built;
   lap("describe (skeleton)");
-  { int rc = commit_upload(c, t0, /*skeleton=*/true); if (rc) return rc; }
+  { int rc = commit_upload(c, t0, Upload::NewScene, /*skeleton=*/true); if (rc) return rc; }
   lap("free + tables upload");
   CommittedScene& s = c->scene;
   int rc = ensure_refit_plan(c);
@@ -1274,7 +1313,7 @@ int scene_commit(ptc_ctx* c, bool device_ok) {
   const std::string e = ptc_build_scene(c->mats, c->meshes, c->insts, c->texs, c->env, c->toplet_budget, c->bvh_builder, *built);
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
   c->built = built;
-  return commit_upload(c, t0);
+  return commit_upload(c, t0, Upload::NewScene);
 }
 }  // namespace
 
@@ -1562,7 +1601,15 @@ void ptc_denoise_default_params(ptc_denoise_params* p) {
   p->iterations = 4; p->sigma_l = 4.0f; p->sigma_n = 128.0f; p->sigma_p = 1.0f; p->demodulate = 1;
 }
 
-int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) {
+namespace {
+int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated);
+}
+int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) { return denoise_image(c, params, false); }
+int ptc_denoise_accumulated(ptc_ctx* c, const ptc_denoise_params* params) { return denoise_image(c, params, true); }
+
+namespace {
+// accumulated: the input is the accumulated image of the frame's ptc_temporal_accumulate, i.e. D_new of the new history (demodulated already) with the temporal variance
+int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated) {
   { int rd = need_device(c); if (rd) return rd; }
   ptc_denoise_params p;
   ptc_denoise_default_params(&p);
@@ -1572,20 +1619,26 @@ int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) {
   if (bad(p.sigma_l) || bad(p.sigma_n) || bad(p.sigma_p)) return fail(c, PTC_E_ARG, "denoise: a sigma is negative or not finite");
   if (!c->guides_valid) return fail(c, PTC_E_STATE, "denoise: no valid guides (ptc_frame_guides after the frame's ptc_frame_begin)");
   if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "denoise: no radiance buffer");
+  if (accumulated && !c->tp_accum_valid) return fail(c, PTC_E_STATE, "denoise_accumulated: the frame has no accumulated image (ptc_temporal_accumulate)");
+  if (accumulated && (p.demodulate ? 1 : 0) != c->tp_demodulate) return fail(c, PTC_E_ARG, "denoise_accumulated: demodulate differs from the accumulate's");
   const size_t n = (size_t)c->rad_w * c->rad_h;
   int rc;
   if ((rc = ensure_buf(c, c->denoised, n)) || (rc = ensure_dn_events(c))) return rc;
   if (p.iterations > 0 && ((rc = ensure_buf(c, c->dn_cv[0], n)) || (rc = ensure_buf(c, c->dn_cv[1], n)))) return rc;
   hipStream_t s0 = c->lanes[0].stream;      // behind the resolve, the reduce and the guide pass
   HIP_TRY(c, hipEventRecord(c->ev_dn[2], s0));
-  if (p.iterations == 0) HIP_TRY(c, hipMemcpyAsync(c->denoised.p, c->radiance.p, n * sizeof(float4), hipMemcpyDeviceToDevice, s0));
+  if (p.iterations == 0) HIP_TRY(c, hipMemcpyAsync(c->denoised.p, accumulated ? c->tp_accum.p : c->radiance.p, n * sizeof(float4), hipMemcpyDeviceToDevice, s0));
   else {
     DenoiseArgs a{};
     a.w = c->rad_w; a.h = c->rad_h; a.sigma_l = p.sigma_l; a.sigma_n = p.sigma_n; a.sigma_p = p.sigma_p; a.demodulate = p.demodulate ? 1 : 0;
     a.pix = (2.0f * c->cam.sy) / (float)c->rad_h;
     a.radiance = c->radiance.p;
     a.g = GuideBufs{c->g_albedo.p, c->g_normal.p, c->g_pos.p, c->g_prim.p, c->g_uv.p};
-    pt_launch_denoise_prepare(s0, a, c->dn_cv[0].p);
+    if (accumulated) {      // D_new lies demodulated in the history; the iterations re-modulate it as they do ptc_denoise's, and pass the other classes' radiance through
+      DenoiseArgs ap = a;
+      ap.demodulate = 0;
+      pt_launch_denoise_prepare(s0, ap, c->tp_dn[c->tp_cur].p, c->tp_mom[c->tp_cur].p, c->dn_cv[0].p);
+    } else pt_launch_denoise_prepare(s0, a, c->radiance.p, nullptr, c->dn_cv[0].p);
     for (int i = 0; i < p.iterations; ++i) {
       const bool last = i == p.iterations - 1;
       pt_launch_denoise_iteration(s0, a, i, c->dn_cv[i & 1].p, last ? c->denoised.p : c->dn_cv[(i + 1) & 1].p, last);
@@ -1597,10 +1650,93 @@ int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) {
   c->denoised_valid = true;
   return PTC_OK;
 }
+}  // namespace
+
+// ---- temporal accumulation (pt_temporal.hip): the history lives in the context, see ptc_ctx ---------------------------------------------------
+void ptc_temporal_default_params(ptc_temporal_params* p) {
+  if (!p) return;
+  p->max_history = 32; p->sigma_z = 1.0f; p->demodulate = 1;
+}
+
+int ptc_temporal_accumulate(ptc_ctx* c, const ptc_temporal_params* params) {
+  { int rd = need_device(c); if (rd) return rd; }
+  ptc_temporal_params p;
+  ptc_temporal_default_params(&p);
+  if (params) p = *params;
+  if (p.max_history < 1 || p.max_history > PTC_TEMPORAL_MAX_HISTORY) return fail(c, PTC_E_ARG, "temporal_accumulate: max_history outside 1..1024");
+  if (!(p.sigma_z >= 0.0f) || !(p.sigma_z <= 3.0e38f)) return fail(c, PTC_E_ARG, "temporal_accumulate: sigma_z is negative or not finite");
+  if (!c->guides_valid) return fail(c, PTC_E_STATE, "temporal_accumulate: no valid guides (ptc_frame_guides after the frame's ptc_frame_begin)");
+  if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "temporal_accumulate: no radiance buffer");
+  const int w = c->rad_w, h = c->rad_h, demodulate = p.demodulate ? 1 : 0;
+  const size_t n = (size_t)w * h;
+  int rc;
+  for (int k = 0; k < 2; ++k)
+    if ((rc = ensure_buf(c, c->tp_dn[k], n)) || (rc = ensure_buf(c, c->tp_mom[k], n)) || (rc = ensure_buf(c, c->tp_nz[k], n)) || (rc = ensure_buf(c, c->tp_pk[k], n))) { drop_history(c); return rc; }
+  // a set may have been regrown above: a failure from here on leaves no history either
+  if ((rc = ensure_buf(c, c->tp_motion, n)) || (rc = ensure_buf(c, c->tp_accum, n))) { drop_history(c); return rc; }
+  for (hipEvent_t& e : c->ev_tp) if (!e) { const hipError_t he = hipEventCreate(&e); if (he != hipSuccess) { drop_history(c); HIP_TRY(c, he); } }
+  if (c->tp_live && (c->tp_w != w || c->tp_h != h || c->tp_demodulate != demodulate)) drop_history(c);      // another size or another quantity: not this frame's history
+  TemporalArgs a{};
+  a.w = w; a.h = h; a.have_history = c->tp_live ? 1 : 0; a.demodulate = demodulate;
+  a.max_history = (float)p.max_history; a.sigma_z = p.sigma_z;
+  a.cam_prev = c->tp_cam;
+  a.pix_prev = (2.0f * c->tp_cam.sy) / (float)h;
+  a.radiance = c->radiance.p;
+  a.g = GuideBufs{c->g_albedo.p, c->g_normal.p, c->g_pos.p, c->g_prim.p, c->g_uv.p};
+  if (c->tp_snap_current) { a.pos = c->tp_snap.p; a.pos_stride = 3; }
+  else { a.pos = c->scene.dsc.shade; a.pos_stride = c->scene.dsc.shade_stride; }
+  const int cur = c->tp_cur, nxt = cur ^ 1;
+  a.prev = TemporalSet{c->tp_dn[cur].p, c->tp_mom[cur].p, c->tp_nz[cur].p, c->tp_pk[cur].p};
+  a.next = TemporalSet{c->tp_dn[nxt].p, c->tp_mom[nxt].p, c->tp_nz[nxt].p, c->tp_pk[nxt].p};
+  a.accumulated = c->tp_accum.p; a.motion = c->tp_motion.p;
+  hipStream_t s0 = c->lanes[0].stream;      // behind the resolve, the reduce and the guide pass
+  HIP_TRY(c, hipEventRecord(c->ev_tp[0], s0));
+  pt_launch_temporal_accumulate(s0, a);
+  HIP_TRY(c, hipEventRecord(c->ev_tp[1], s0));
+  HIP_TRY(c, hipGetLastError());
+  c->ev_tp_recorded = true;
+  c->tp_cur = nxt; c->tp_live = true; c->tp_w = w; c->tp_h = h; c->tp_demodulate = demodulate; c->tp_cam = c->cam;
+  c->tp_snap_current = false;      // the new history's frame saw the shading records as they lie now
+  c->tp_accum_valid = true;
+  return PTC_OK;
+}
+
+int ptc_temporal_reset(ptc_ctx* c) {
+  { int rd = need_device(c); if (rd) return rd; }
+  drop_history(c);
+  return PTC_OK;
+}
+
+int ptc_read_temporal_rgba32f(ptc_ctx* c, int which, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "read_temporal: null pointer");
+  if (which < PTC_TEMPORAL_HISTORY || which > PTC_TEMPORAL_POSITION_CLASS) return fail(c, PTC_E_ARG, "read_temporal: unknown buffer");
+  if (!c->tp_live) return fail(c, PTC_E_STATE, "read_temporal: no history (ptc_temporal_accumulate)");
+  // the caller sizes `out` by the frame it knows, the current one: a history of another size (a frame_begin with a new size, not accumulated yet) is not served
+  if (c->tp_w != c->rad_w || c->tp_h != c->rad_h) return fail(c, PTC_E_STATE, "read_temporal: the history's size is not the current frame's (no ptc_temporal_accumulate since the size changed)");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  const float4* const bufs[5] = {c->tp_dn[c->tp_cur].p, c->tp_mom[c->tp_cur].p, c->tp_motion.p, c->tp_nz[c->tp_cur].p, c->tp_pk[c->tp_cur].p};
+  const float4* src = bufs[which];
+  HIP_TRY(c, hipMemcpy(out, src, (size_t)c->tp_w * c->tp_h * sizeof(float4), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+int ptc_get_temporal_seconds(ptc_ctx* c, double* accumulate) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!accumulate) return PTC_OK;
+  *accumulate = 0.0;
+  if (!c->ev_tp_recorded) return PTC_OK;
+  HIP_TRY(c, hipEventSynchronize(c->ev_tp[1]));
+  float ms = 0.0f;
+  HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_tp[0], c->ev_tp[1]));
+  *accumulate = 1e-3 * (double)ms;
+  return PTC_OK;
+}
 
 int ptc_select_output(ptc_ctx* c, int output) {
   { int rd = need_device(c); if (rd) return rd; }
-  if (output != PTC_OUTPUT_RADIANCE && output != PTC_OUTPUT_DENOISED) return fail(c, PTC_E_ARG, "select_output: unknown output");
+  if (output != PTC_OUTPUT_RADIANCE && output != PTC_OUTPUT_DENOISED && output != PTC_OUTPUT_ACCUMULATED) return fail(c, PTC_E_ARG, "select_output: unknown output");
+  if (output == PTC_OUTPUT_ACCUMULATED && !c->tp_accum_valid) return fail(c, PTC_E_STATE, "select_output: the frame has no accumulated image (ptc_temporal_accumulate)");
   if (output == PTC_OUTPUT_DENOISED && !c->denoised_valid) return fail(c, PTC_E_STATE, "select_output: the frame has no denoised image (ptc_denoise)");
   c->output = output;
   return PTC_OK;
@@ -1865,7 +2001,7 @@ int ptc_group_scene_commit(ptc_group* g) {
     const auto t0 = std::chrono::steady_clock::now();
     copy_description(c, c0);
     c->built = c0->built;                             // shared, read-only from here on
-    if ((rc = commit_upload(c, t0))) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
+    if ((rc = commit_upload(c, t0, Upload::NewScene))) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
   }
   return PTC_OK;
 }
@@ -1881,7 +2017,7 @@ int ptc_group_scene_refit(ptc_group* g) {
   for (ptc_ctx* c : g->ctx) {
     if (c->device < 0) continue;
     if (hipSetDevice(c->device) != hipSuccess) { g->err = "ptc_group_scene_refit: hipSetDevice failed"; return PTC_E_DEVICE; }
-    int rc = flush(c); if (!rc) rc = sync_all_lanes(c);
+    int rc = flush(c); if (!rc) rc = temporal_keep_positions(c); if (!rc) rc = sync_all_lanes(c);
     if (rc) { g->err = std::string("ptc_group_scene_refit: ") + ptc_last_error(c); return rc; }
   }
   const auto t0 = std::chrono::steady_clock::now();

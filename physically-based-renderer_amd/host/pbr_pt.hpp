@@ -161,6 +161,23 @@ public:
   auto selectOutput(int output) -> void { ck(ptc_select_output(_ctx, output)); }
   // HIP-event seconds of the last frameGuides() and the last denoise()
   auto denoiseSeconds() -> std::array<double, 2> { std::array<double, 2> t{0.0, 0.0}; ck(ptc_get_denoise_seconds(_ctx, &t[0], &t[1])); return t; }
+  // ---- temporal accumulation (include/ptc.h): the previous frames' result, reprojected through the guides, blended with this frame's radiance buffer ----
+  static auto temporalDefaults() -> ptc_temporal_params { ptc_temporal_params p; ptc_temporal_default_params(&p); return p; }
+  // needs frameGuides() of the current frame; selectOutput(PTC_OUTPUT_ACCUMULATED) serves the accumulated image.  The history survives a new frame, a new
+  // camera, refit() and rebuild(); temporalReset() and a new commit drop it
+  auto temporalAccumulate(ptc_temporal_params const* params = nullptr) -> void { ck(ptc_temporal_accumulate(_ctx, params)); }
+  auto temporalReset() -> void { ck(ptc_temporal_reset(_ctx)); }
+  // PTC_TEMPORAL_HISTORY (D rgb, n), PTC_TEMPORAL_MOMENTS (m1, m2, Var_t, a), PTC_TEMPORAL_MOTION (x_prev, y_prev, W, reprojected n), PTC_TEMPORAL_NORMAL_DEPTH (N, Z) and
+  // PTC_TEMPORAL_POSITION_CLASS (P, K: the history's copies of its frame's guides).  w x h: the current frame's size, which must be the accumulated frame's — the library
+  // refuses (PTC_E_STATE -> an exception) when a frame of another size was begun since the accumulate, so the buffer sized here is the size that is copied
+  auto readTemporal(int which, int w, int h) -> std::vector<float> {
+    std::vector<float> out((std::size_t)w * (std::size_t)h * 4);
+    ck(ptc_read_temporal_rgba32f(_ctx, which, out.data()));
+    return out;
+  }
+  // the denoiser's iterations over the accumulated image -> the denoised buffer (PTC_OUTPUT_DENOISED)
+  auto denoiseAccumulated(ptc_denoise_params const* params = nullptr) -> void { ck(ptc_denoise_accumulated(_ctx, params)); }
+  auto temporalSeconds() -> double { double t = 0.0; ck(ptc_get_temporal_seconds(_ctx, &t)); return t; }
   // ---- adaptive sampling (include/ptc.h): samples go to the pixels whose estimate has not converged; at most maxSpp per pixel ----
   static auto adaptiveDefaults() -> ptc_adaptive_params { ptc_adaptive_params p; ptc_adaptive_default_params(&p); return p; }
   auto renderAdaptive(int w, int h, int maxSpp, std::uint64_t seed, int maxBounces, ptc_adaptive_params const* params = nullptr) -> std::vector<float> {

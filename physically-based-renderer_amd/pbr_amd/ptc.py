@@ -30,6 +30,12 @@ GUIDE_ALBEDO = 0          # (albedo rgb, class: 0 miss, 1 surface, 2 emitter)
 GUIDE_NORMAL_DEPTH = 1    # (unit vertex normal, t along the unit camera ray)
 OUTPUT_RADIANCE = 0
 OUTPUT_DENOISED = 1
+OUTPUT_ACCUMULATED = 2    # the image of the frame's temporal_accumulate()
+TEMPORAL_HISTORY = 0      # (D rgb, n)
+TEMPORAL_MOMENTS = 1      # (m1, m2, Var_t, a)
+TEMPORAL_MOTION = 2       # (x_prev, y_prev, W, reprojected n)
+TEMPORAL_NORMAL_DEPTH = 3     # the history's copy of its frame's (N, Z)
+TEMPORAL_POSITION_CLASS = 4   # the history's copy of its frame's (P, K)
 
 # every symbol include/ptc.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -41,6 +47,7 @@ ABI_SYMBOLS = [
     "ptc_debug_get_description", "ptc_debug_get_material", "ptc_debug_get_texture", "ptc_debug_get_internals", "ptc_debug_host_build_id", "ptc_debug_get_shading_tables", "ptc_debug_refit_host_parts", "ptc_debug_commit_host_parts",
     "ptc_read_radiance_rgba16f", "ptc_radiance_rgba16f_device_ptr",
     "ptc_frame_guides", "ptc_read_guide_rgba32f", "ptc_read_guide_hit", "ptc_denoise_default_params", "ptc_denoise", "ptc_select_output", "ptc_get_denoise_seconds",
+    "ptc_temporal_default_params", "ptc_temporal_accumulate", "ptc_temporal_reset", "ptc_read_temporal_rgba32f", "ptc_denoise_accumulated", "ptc_get_temporal_seconds",
     "ptc_adaptive_default_params", "ptc_frame_set_adaptive", "ptc_frame_adapt", "ptc_read_sample_counts", "ptc_render_adaptive", "ptc_get_adaptive_stats",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
@@ -65,6 +72,13 @@ class PtcStats(C.Structure):
 
 class PtcDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcTemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("demodulate", C.c_int)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -169,6 +183,13 @@ def load_library():
     L.ptc_denoise.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
     L.ptc_select_output.argtypes = [vp, C.c_int]
     L.ptc_get_denoise_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ptc_temporal_default_params.argtypes = [C.POINTER(PtcTemporalParams)]
+    L.ptc_temporal_default_params.restype = None
+    L.ptc_temporal_accumulate.argtypes = [vp, C.POINTER(PtcTemporalParams)]
+    L.ptc_temporal_reset.argtypes = [vp]
+    L.ptc_read_temporal_rgba32f.argtypes = [vp, C.c_int, fp]
+    L.ptc_denoise_accumulated.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
+    L.ptc_get_temporal_seconds.argtypes = [vp, C.POINTER(C.c_double)]
     L.ptc_adaptive_default_params.argtypes = [C.POINTER(PtcAdaptiveParams)]
     L.ptc_adaptive_default_params.restype = None
     L.ptc_frame_set_adaptive.argtypes = [vp, C.POINTER(PtcAdaptiveParams)]
@@ -388,15 +409,18 @@ class PathTracer:
         load_library().ptc_denoise_default_params(C.byref(p))
         return p.as_dict()
 
-    def denoise(self, **params):
-        """ptc_denoise: radiance buffer + guides -> the denoised buffer.  Keywords (iterations, sigma_l, sigma_n, sigma_p, demodulate) replace the defaults."""
+    def _denoise_params(self, params):
         p = PtcDenoiseParams()
         self._L.ptc_denoise_default_params(C.byref(p))
         for k, v in params.items():
             if k not in dict(PtcDenoiseParams._fields_):
                 raise TypeError(f"denoise: unknown parameter {k}")
             setattr(p, k, v)
-        self._ck(self._L.ptc_denoise(self._h, C.byref(p)))
+        return p
+
+    def denoise(self, **params):
+        """ptc_denoise: radiance buffer + guides -> the denoised buffer.  Keywords (iterations, sigma_l, sigma_n, sigma_p, demodulate) replace the defaults."""
+        self._ck(self._L.ptc_denoise(self._h, C.byref(self._denoise_params(params))))
 
     def select_output(self, which):
         """ptc_select_output: OUTPUT_RADIANCE or OUTPUT_DENOISED is what read_radiance / read_radiance_f16 / tonemap serve."""
@@ -407,6 +431,47 @@ class PathTracer:
         g, d = C.c_double(0), C.c_double(0)
         self._ck(self._L.ptc_get_denoise_seconds(self._h, C.byref(g), C.byref(d)))
         return g.value, d.value
+
+    # ---- temporal accumulation ----------------------------------------------------------------------------
+    @staticmethod
+    def temporal_default_params():
+        p = PtcTemporalParams()
+        load_library().ptc_temporal_default_params(C.byref(p))
+        return p.as_dict()
+
+    def temporal_accumulate(self, **params):
+        """ptc_temporal_accumulate: reproject the history through the frame's guides and blend the radiance buffer in; the accumulated image is
+        OUTPUT_ACCUMULATED.  Keywords (max_history, sigma_z, demodulate) replace the defaults."""
+        p = PtcTemporalParams()
+        self._L.ptc_temporal_default_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(PtcTemporalParams._fields_):
+                raise TypeError(f"temporal_accumulate: unknown parameter {k}")
+            setattr(p, k, v)
+        self._ck(self._L.ptc_temporal_accumulate(self._h, C.byref(p)))
+
+    def temporal_reset(self):
+        """ptc_temporal_reset: drop the history; the next temporal_accumulate() starts from nothing."""
+        self._ck(self._L.ptc_temporal_reset(self._h))
+
+    def read_temporal(self, which):
+        """(h, w, 4) float32 of the last temporal_accumulate(): TEMPORAL_HISTORY (D rgb, n), TEMPORAL_MOMENTS (m1, m2, Var_t, a), TEMPORAL_MOTION
+        (x_prev, y_prev, W, reprojected n), and the history's copies of its frame's guides, TEMPORAL_NORMAL_DEPTH (N, Z) and TEMPORAL_POSITION_CLASS (P, K).
+        (h, w) is the current frame's, which the library holds the history's size to: after a frame_begin with another size it raises (ptc error -2) until
+        the next temporal_accumulate()."""
+        out = np.empty((self._h_px, self._w, 4), np.float32)
+        self._ck(self._L.ptc_read_temporal_rgba32f(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise_accumulated(self, **params):
+        """ptc_denoise_accumulated: the denoiser's iterations over the accumulated image, with the temporal variance where the history is long enough."""
+        self._ck(self._L.ptc_denoise_accumulated(self._h, C.byref(self._denoise_params(params))))
+
+    def temporal_seconds(self):
+        """HIP-event seconds of the last temporal_accumulate()."""
+        t = C.c_double(0)
+        self._ck(self._L.ptc_get_temporal_seconds(self._h, C.byref(t)))
+        return t.value
 
     # ---- adaptive sampling ------------------------------------------------------------------------------
     @staticmethod

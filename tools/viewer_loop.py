@@ -7,7 +7,9 @@ device (ptc_scene_rebuild) when ptc_stats.bvh_sa_cost has grown past r times bvh
 With PTC_DEVICE_BVH=sah in the environment the rebuilt tree is the binned-SAH tree (ptc_set_device_builder), else the LBVH.
 --denoise runs the loop a second time in the same process with the first-hit guides (ptc_frame_guides) and the à-trous filter (ptc_denoise, default
 parameters) between the resolve and the RGBA16F hand-off, and reports that frame time beside the plain one, with the HIP-event times of the two passes.
-usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h] [--denoise]"""
+--temporal runs it once more with the temporal path: guides, ptc_temporal_accumulate (the history reprojected through the refit and blended with the frame),
+ptc_denoise_accumulated, hand-off; reported like --denoise's, against --denoise's frame time when both are given, with the accumulate's HIP-event time.
+usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h] [--denoise] [--temporal]"""
 import json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))
@@ -15,7 +17,8 @@ import numpy as np
 import pbr_amd as pbr
 
 denoise = "--denoise" in sys.argv
-argv = [a for a in sys.argv if a != "--denoise"]
+temporal = "--temporal" in sys.argv
+argv = [a for a in sys.argv if a not in ("--denoise", "--temporal")]
 name = argv[1] if len(argv) > 1 else "atrium"
 spp = int(argv[2]) if len(argv) > 2 else 1
 frames = int(argv[3]) if len(argv) > 3 else 60
@@ -82,4 +85,33 @@ if denoise:      # the same loop again, the frame filtered before the hand-off: 
     out["denoise"] = {"params": pbr.PathTracer.denoise_default_params(), "ms_per_frame": {"median": 1e3 * float(np.median(t_dn)), "min": 1e3 * float(np.min(t_dn)), "max": 1e3 * float(np.max(t_dn))},
                       "ms_added_per_frame": 1e3 * float(np.median(t_dn) - np.median(t_frame)), "ms_guide_pass_device": 1e3 * float(np.median(s_guides)),
                       "ms_filter_device": 1e3 * float(np.median(s_filter))}
+if temporal:     # once more: the frame blended into the reprojected history, then filtered; the history survives every refit
+    t_tp, s_guides, s_acc, s_filter = [], [], [], []
+    for k in range(2 * frames + 10, 3 * frames + 15):
+        t0 = time.perf_counter()
+        a = 0.01 * (k + 1)
+        for i in moving:
+            pt.update_instance(i, d.instances[i].t, (math.cos(a / 2), 0.0, math.sin(a / 2), 0.0), d.instances[i].s)
+        pt.scene_refit()
+        pt.frame_begin(w, h, spp, seed=k, max_bounces=8)
+        pt.frame_add_samples(spp)
+        pt.frame_guides()
+        pt.frame_resolve()
+        pt.temporal_accumulate()
+        pt.denoise_accumulated()
+        pt.select_output(pbr.ptc.OUTPUT_DENOISED)
+        pt.sync()
+        ptr = pt.radiance_f16_device_ptr()
+        t2 = time.perf_counter()
+        if k >= 2 * frames + 15:
+            t_tp.append(t2 - t0)
+            g_s, f_s = pt.denoise_seconds()
+            s_guides.append(g_s); s_filter.append(f_s); s_acc.append(pt.temporal_seconds())
+    n_hist = pt.read_temporal(pbr.ptc.TEMPORAL_HISTORY)[..., 3]
+    out["temporal"] = {"params": pbr.PathTracer.temporal_default_params(), "ms_per_frame": {"median": 1e3 * float(np.median(t_tp)), "min": 1e3 * float(np.min(t_tp)), "max": 1e3 * float(np.max(t_tp))},
+                       "ms_added_per_frame": 1e3 * float(np.median(t_tp) - np.median(t_frame)), "ms_guide_pass_device": 1e3 * float(np.median(s_guides)),
+                       "ms_accumulate_device": 1e3 * float(np.median(s_acc)), "ms_filter_device": 1e3 * float(np.median(s_filter)),
+                       "mean_history_length": float(n_hist[n_hist > 0].mean())}
+    if denoise:
+        out["temporal"]["ms_added_to_denoise_frame"] = 1e3 * float(np.median(t_tp) - np.median(t_dn))
 print(json.dumps(out))
