@@ -376,6 +376,31 @@ typedef struct ptc_adaptive_stats {
 } ptc_adaptive_stats;
 int  ptc_get_adaptive_stats(ptc_ctx*, ptc_adaptive_stats*);
 
+/* ---- denoising from per-sample statistics: the per-pixel RGB covariance of an adaptive frame's samples ------------
+ * ptc_denoise estimates a pixel's variance from the 7x7 window of the mean image; at tens of samples per pixel that window measures the signal, not the
+ * noise.  An adaptive frame begun while ptc_set_sample_covariance is on also keeps, per owned pixel and in sample order, the six sums
+ *   q_rr += r r, q_gg += g g, q_bb += b b, q_rg += r g, q_rb += r b, q_gb += g b            (24 B per owned pixel, zeroed at ptc_frame_set_adaptive)
+ * of every sample's radiance (r, g, b).  Nothing else about the frame changes: image, counts and ptc_stats are those of the frame without them, bit for bit.
+ * A uniform frame with statistics is an adaptive frame on which ptc_frame_adapt is never called.
+ * ptc_denoise_sampled: per owned pixel with count n >= 1, sums s, fn = (float)n, w = (0.2126, 0.7152, 0.0722), albedo guide A, all in binary32 as written:
+ *     mu_c = s_c / fn;   c_ij = q_ij / fn - mu_i mu_j;   a_c = w_c / max(A_c, 1e-3)  (a_c = w_c with demodulate = 0)
+ *     V = ((a_r a_r) c_rr + (a_g a_g) c_gg) + (a_b a_b) c_bb + 2 (((a_r a_g) c_rg + (a_r a_b) c_rb) + (a_g a_b) c_gb);   Var_s = max(V, 0)
+ *   the exact variance of the samples' (demodulated) luminance.  The filter is ptc_denoise_accumulated's with the input (D, fn), D = radiance / max(A, 1e-3)
+ *   (or the radiance), and the variance (1 / fn) Var_s, the variance of the pixel mean, where n >= 4; elsewhere (fewer samples, pixels of another
+ *   context's tiles) ptc_denoise's 7x7 estimate over lum(D).  The result goes to the denoised buffer (PTC_OUTPUT_DENOISED serves it), its time to
+ *   ptc_get_denoise_seconds; the frame is not disturbed.  Parameters as ptc_denoise (NULL: the defaults; PTC_E_ARG alike; iterations = 0 copies the radiance).
+ *   PTC_E_STATE without valid guides, in a frame that is not an adaptive frame keeping the covariance, and when samples were added since the last
+ *   ptc_frame_resolve (the radiance buffer and the sums must describe the same samples).
+ * ptc_set_sample_covariance: a setting of the context (it needs no device), 0 | 1, anything else PTC_E_ARG and the setting unchanged; default 0.  It is read
+ *   by ptc_frame_set_adaptive (ptc_render_adaptive included): a frame keeps what it was begun with.
+ * ptc_read_sample_covariance: the raw sums (rr, gg, bb, rg, rb, gb), 0 where this context does not own the pixel; waits for the device; PTC_E_STATE unless
+ *   the current frame keeps the covariance.
+ * ptc_read_sampled_variance: (Var_s, 1 / fn) as the frame's last ptc_denoise_sampled computed them, (0, 0) where count = 0; PTC_E_STATE before it. */
+int  ptc_set_sample_covariance(ptc_ctx*, int on);
+int  ptc_read_sample_covariance(ptc_ctx*, float* out);                /* w*h*6 floats */
+int  ptc_denoise_sampled(ptc_ctx*, const ptc_denoise_params*);        /* NULL: the defaults */
+int  ptc_read_sampled_variance(ptc_ctx*, float* out);                 /* w*h*2 floats */
+
 /* ---- temporal accumulation: reproject the previous frame's accumulated image and blend the new frame in ---------------------------
  * A viewer that adds one sample per displayed frame starts every frame from nothing; these calls carry the previous frames' result across camera
  * motion, ptc_scene_refit and ptc_scene_rebuild.  Nothing here changes what a context that never calls them computes.  DESIGN.md §8c has the

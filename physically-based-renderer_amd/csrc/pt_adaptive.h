@@ -15,12 +15,15 @@ struct DevAdaptive {
   uint8_t* keep;          // [n_active] scratch of the compaction: the keep predicate per active entry
   uint32_t* block_tot;    // [ceil(n_active / PTC_AD_BLOCK)] scratch: kept entries per block, then their exclusive prefix
   uint32_t* n_out;        // [1] length of the new active list
+  float4* cov4;           // [n_owned] (rr, gg, bb, rg): sums of the products of the per-sample radiance's channels, in sample order; NULL in a frame that
+  float2* cov2;           // [n_owned] (rb, gb)          does not keep the sample covariance (ptc_set_sample_covariance)
 };
 inline uint32_t pt_ad_blocks(uint32_t n) { return (n + PTC_AD_BLOCK - 1u) / PTC_AD_BLOCK; }
 
 // active list := the owned list, slot[j] = j
 void pt_launch_ad_init(hipStream_t, uint32_t n_owned, const uint32_t* owned, uint32_t* pix, uint32_t* slot);
-// k_accumulate's three additions per sample on accum[slot[j]], then m1, m2 and count; lpath[s * n_active + j] is sample s of active entry j
+// k_accumulate's three additions per sample on accum[slot[j]], then m1, m2 and count; lpath[s * n_active + j] is sample s of active entry j.  With ad.cov4 set
+// the six product sums follow (a second instantiation: a frame without them runs the kernel it always ran)
 void pt_launch_ad_accumulate(hipStream_t, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive&, uint32_t n_samples);
 // flags[pixel] = e > threshold for every active entry, n = the samples every active pixel has received
 void pt_launch_ad_error(hipStream_t, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, const DevAdaptive&, uint32_t n, float threshold);
@@ -28,3 +31,8 @@ void pt_launch_ad_error(hipStream_t, uint32_t n_active, const uint32_t* pix, con
 void pt_launch_ad_compact(hipStream_t, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, uint32_t* pix_out, uint32_t* slot_out, const DevAdaptive&, int w, int h, int radius);
 // radiance[owned[o]] = accum[o] / (float)count[o], alpha 1; a pixel without samples is left alone
 void pt_launch_ad_resolve(hipStream_t, uint32_t n_owned, const uint32_t* owned, const float4* accum, const uint32_t* count, float4* radiance);
+// The denoiser's input from the per-sample statistics, per owned entry o with pixel = owned[o] and n = count[o]:
+//   colour[pixel] = (D.rgb, (float)n), D = radiance[pixel] / max(albedo, 1e-3) (or the radiance), svar[pixel] = (0, 0, Var_s, 1 / (float)n); n = 0: (D, 0) and zeros.
+// fill_all: the frame does not own every pixel, so a pass over all w * h pixels writes (D, 0) and zeros first.
+void pt_launch_ad_sampled_variance(hipStream_t, uint32_t n_owned, const uint32_t* owned, const float4* accum, const DevAdaptive&, const float4* albedo, const float4* radiance,
+                                   int demodulate, float4* colour, float4* svar, uint32_t n_pixels, bool fill_all);

@@ -3,12 +3,15 @@
 // A frame in adaptive mode keeps, per owned pixel, the RGB sum (accum, as always), m1 = sum l_k, m2 = sum l_k l_k of the per-sample luminance
 // l_k = (0.2126 r + 0.7152 g) + 0.0722 b, and the number of samples received.  The path kernels see the frame as DevFrame{n_active, active pixels}; the kernels
 // here map an active entry j back to its owned position slot[j].
-//   k_ad_accumulate     pure stream: 16 B per sample and entry in, 28 B of state read and written per entry
+//   k_ad_accumulate     pure stream: 16 B per sample and entry in, 28 B of state read and written per entry; <true>: + the six sums of products of the
+//                       channels (rr, gg, bb, rg | rb, gb), a float4 and a float2 per entry: 52 B of state (ptc_set_sample_covariance)
 //   k_ad_error          mean = m1 / n, var = max(m2 / n - mean mean, 0), e = sqrt(var / n) / (mean + 0.01), flag = e > threshold: one byte per active pixel
 //   k_ad_compact_*      keep = some flagged pixel within Chebyshev distance `radius`, inside the image and the pixel's own 32x32 tile; then a STABLE compaction
 //                       of (pixel, slot): per-block counts, one block scans them (as k_scan does), ballot + mbcnt prefix per wave and an LDS prefix over the
 //                       block's waves place every kept entry — no atomics, so the list keeps the tile-Morton order and is the same on every run
 //   k_ad_resolve        accum / (float)count per owned pixel
+//   k_ad_sampled_*      the denoiser's input from the sums (§8d): the biased covariance of the samples' channels, the variance of the (demodulated) luminance
+//                       as its quadratic form, and the demodulated radiance with the count — the two images pt_launch_denoise_prepare takes
 // Arithmetic: IEEE binary32 in the order written (the Makefile's -ffp-contract=off and correctly rounded division and square root): tests/adaptive_reference.py
 // performs the same operations in numpy and the sample counts are compared exactly.
 #include "pt_adaptive.h"
@@ -24,20 +27,30 @@ __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_init(uint32_t n_owned, cons
   pix[j] = owned[j]; slot[j] = j;
 }
 
+template <bool COV>
 __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_accumulate(uint32_t n_active, const uint32_t* __restrict__ slot, const float4* __restrict__ lpath, float4* __restrict__ accum,
-                                                                float2* __restrict__ moments, uint32_t* __restrict__ count, uint32_t n_samples) {
+                                                                float2* __restrict__ moments, uint32_t* __restrict__ count, float4* __restrict__ cov4, float2* __restrict__ cov2,
+                                                                uint32_t n_samples) {
   const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
   if (j >= n_active) return;
   const uint32_t o = slot[j];
   float4 a = accum[o];
   float2 m = moments[o];
+  float4 q4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float2 q2 = make_float2(0.0f, 0.0f);
+  if (COV) { q4 = cov4[o]; q2 = cov2[o]; }
   for (uint32_t s = 0; s < n_samples; ++s) {
     const float4 L = lpath[(size_t)s * n_active + j];
     a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z;
     const float l = ad_lum(L.x, L.y, L.z);
     m.x = m.x + l; m.y = m.y + l * l;
+    if (COV) {
+      q4.x = q4.x + L.x * L.x; q4.y = q4.y + L.y * L.y; q4.z = q4.z + L.z * L.z; q4.w = q4.w + L.x * L.y;
+      q2.x = q2.x + L.x * L.z; q2.y = q2.y + L.y * L.z;
+    }
   }
   accum[o] = a; moments[o] = m; count[o] += n_samples;
+  if (COV) { cov4[o] = q4; cov2[o] = q2; }
 }
 
 __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_error(uint32_t n_active, const uint32_t* __restrict__ pix, const uint32_t* __restrict__ slot, const float2* __restrict__ moments,
@@ -130,6 +143,52 @@ __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_resolve(uint32_t n_owned, c
   const float fn = (float)n;
   radiance[owned[o]] = make_float4(a.x / fn, a.y / fn, a.z / fn, 1.0f);
 }
+
+#define AD_EPS_A 1e-3f
+__device__ __forceinline__ float4 ad_demodulate(float4 c, float4 ak, int demodulate) {
+  if (!demodulate) return c;
+  return make_float4(c.x / fmaxf(ak.x, AD_EPS_A), c.y / fmaxf(ak.y, AD_EPS_A), c.z / fmaxf(ak.z, AD_EPS_A), c.w);
+}
+
+// every pixel: (D, 0) and zeros, what a pixel the frame does not own keeps
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_sampled_fill(uint32_t n_pixels, const float4* __restrict__ albedo, const float4* __restrict__ radiance, int demodulate,
+                                                                  float4* __restrict__ colour, float4* __restrict__ svar) {
+  const uint32_t p = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (p >= n_pixels) return;
+  const float4 d = ad_demodulate(radiance[p], albedo[p], demodulate);
+  colour[p] = make_float4(d.x, d.y, d.z, 0.0f);
+  svar[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// one owned entry per thread; the owned list is in tile-Morton order, so a wave writes whole 32-pixel rows of a tile
+__global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_sampled_variance(uint32_t n_owned, const uint32_t* __restrict__ owned, const float4* __restrict__ accum,
+                                                                      const float4* __restrict__ cov4, const float2* __restrict__ cov2, const uint32_t* __restrict__ count,
+                                                                      const float4* __restrict__ albedo, const float4* __restrict__ radiance, int demodulate,
+                                                                      float4* __restrict__ colour, float4* __restrict__ svar, uint32_t n_pixels) {
+  const uint32_t o = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
+  if (o >= n_owned) return;
+  const uint32_t p = owned[o];
+  if (p >= n_pixels) return;      // cannot happen (the owned list holds pixels of the frame): both images hold n_pixels entries
+  const uint32_t n = count[o];
+  const float4 ak = albedo[p];
+  const float4 d = ad_demodulate(radiance[p], ak, demodulate);
+  if (n == 0) {
+    colour[p] = make_float4(d.x, d.y, d.z, 0.0f);
+    svar[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  const float4 s = accum[o], q4 = cov4[o];
+  const float2 q2 = cov2[o];
+  const float fn = (float)n;
+  const float mr = s.x / fn, mg = s.y / fn, mb = s.z / fn;
+  const float crr = q4.x / fn - mr * mr, cgg = q4.y / fn - mg * mg, cbb = q4.z / fn - mb * mb;
+  const float crg = q4.w / fn - mr * mg, crb = q2.x / fn - mr * mb, cgb = q2.y / fn - mg * mb;
+  float ar = 0.2126f, ag = 0.7152f, ab = 0.0722f;
+  if (demodulate) { ar = ar / fmaxf(ak.x, AD_EPS_A); ag = ag / fmaxf(ak.y, AD_EPS_A); ab = ab / fmaxf(ak.z, AD_EPS_A); }
+  const float v = (((ar * ar) * crr + (ag * ag) * cgg) + (ab * ab) * cbb) + 2.0f * ((((ar * ag) * crg + (ar * ab) * crb)) + (ag * ab) * cgb);
+  colour[p] = make_float4(d.x, d.y, d.z, fn);
+  svar[p] = make_float4(0.0f, 0.0f, fmaxf(v, 0.0f), 1.0f / fn);
+}
 }  // namespace
 
 void pt_launch_ad_init(hipStream_t s, uint32_t n_owned, const uint32_t* owned, uint32_t* pix, uint32_t* slot) {
@@ -138,7 +197,8 @@ void pt_launch_ad_init(hipStream_t s, uint32_t n_owned, const uint32_t* owned, u
 }
 void pt_launch_ad_accumulate(hipStream_t s, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive& ad, uint32_t n_samples) {
   if (!n_active) return;
-  hipLaunchKernelGGL(k_ad_accumulate, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, n_samples);
+  if (ad.cov4) hipLaunchKernelGGL(k_ad_accumulate<true>, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
+  else hipLaunchKernelGGL(k_ad_accumulate<false>, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
 }
 void pt_launch_ad_error(hipStream_t s, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, const DevAdaptive& ad, uint32_t n, float threshold) {
   if (!n_active) return;
@@ -153,4 +213,11 @@ void pt_launch_ad_compact(hipStream_t s, uint32_t n_active, const uint32_t* pix,
 void pt_launch_ad_resolve(hipStream_t s, uint32_t n_owned, const uint32_t* owned, const float4* accum, const uint32_t* count, float4* radiance) {
   if (!n_owned) return;
   hipLaunchKernelGGL(k_ad_resolve, dim3(pt_ad_blocks(n_owned)), dim3(PTC_AD_BLOCK), 0, s, n_owned, owned, accum, count, radiance);
+}
+void pt_launch_ad_sampled_variance(hipStream_t s, uint32_t n_owned, const uint32_t* owned, const float4* accum, const DevAdaptive& ad, const float4* albedo, const float4* radiance,
+                                   int demodulate, float4* colour, float4* svar, uint32_t n_pixels, bool fill_all) {
+  if (fill_all && n_pixels) hipLaunchKernelGGL(k_ad_sampled_fill, dim3(pt_ad_blocks(n_pixels)), dim3(PTC_AD_BLOCK), 0, s, n_pixels, albedo, radiance, demodulate, colour, svar);
+  if (!n_owned) return;
+  hipLaunchKernelGGL(k_ad_sampled_variance, dim3(pt_ad_blocks(n_owned)), dim3(PTC_AD_BLOCK), 0, s, n_owned, owned, accum, (const float4*)ad.cov4, (const float2*)ad.cov2,
+                     (const uint32_t*)ad.count, albedo, radiance, demodulate, colour, svar, n_pixels);
 }

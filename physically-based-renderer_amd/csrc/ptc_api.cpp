@@ -194,6 +194,12 @@ struct ptc_ctx {
   uint32_t ad_passes = 0;
   double ad_seconds = 0.0;
   hipEvent_t ev_ad[2] = {nullptr, nullptr};
+  // the per-sample RGB covariance: cov_setting is the context's (ptc_set_sample_covariance), cov_on what the current adaptive frame was begun with
+  bool cov_setting = false, cov_on = false;
+  bool cov_resolved = false;        // the radiance buffer holds the resolve of every sample the frame's sums hold
+  bool sv_valid = false;            // sv_var holds the current frame's last ptc_denoise_sampled variance
+  DevBuf<float4> ad_cov4, sv_colour, sv_var;   // (rr, gg, bb, rg) per owned pixel; the filter's input (D, n) and (0, 0, Var_s, 1 / n) per pixel
+  DevBuf<float2> ad_cov2;                      // (rb, gb) per owned pixel
   size_t frame_batch_paths = 0;     // the path budget of a batch as ptc_frame_begin settled it: per_batch follows the active set from it
   // temporal accumulation (pt_temporal.hip).  The history is the state the last ptc_temporal_accumulate left: set tp_cur of the two ping-pong sets, the camera and
   // the size of its frame.  It outlives frames, cameras, refits and rebuilds; the accumulated image is the current frame's (drop_guides ends its validity).
@@ -447,7 +453,9 @@ LaunchCfg batch_cfg(const ptc_ctx* c, uint32_t n_paths) {
   return cfg;
 }
 
-DevAdaptive dev_adaptive(const ptc_ctx* c) { return DevAdaptive{c->ad_mom.p, c->ad_count.p, c->ad_flags.p, c->ad_keep.p, c->ad_block.p, c->ad_n.p}; }
+DevAdaptive dev_adaptive(const ptc_ctx* c) {
+  return DevAdaptive{c->ad_mom.p, c->ad_count.p, c->ad_flags.p, c->ad_keep.p, c->ad_block.p, c->ad_n.p, c->cov_on ? c->ad_cov4.p : nullptr, c->cov_on ? c->ad_cov2.p : nullptr};
+}
 
 // samples of one full batch of `n_pixels` pixels: as many as fit `batch_paths` split over the lanes, and 32-bit slot indices
 uint32_t batch_samples(const ptc_ctx* c, size_t n_pixels, size_t batch_paths) {
@@ -740,6 +748,7 @@ void ptc_destroy(ptc_ctx* c) {
   for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
   for (auto* b : {&c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_count, &c->ad_block, &c->ad_n}) b->release();
   c->ad_mom.release(); c->ad_flags.release(); c->ad_keep.release();
+  c->ad_cov4.release(); c->ad_cov2.release(); c->sv_colour.release(); c->sv_var.release();
   for (hipEvent_t e : c->ev_ad) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2; ++k) { c->tp_dn[k].release(); c->tp_mom[k].release(); c->tp_nz[k].release(); c->tp_pk[k].release(); }
   c->tp_motion.release(); c->tp_accum.release(); c->tp_snap.release();
@@ -1321,7 +1330,7 @@ int ptc_scene_commit(ptc_ctx* c) { return scene_commit(c, true); }
 
 int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
   { int rd = need_device(c); if (rd) return rd; }
-  c->in_frame = false; c->pending = 0; c->adaptive = false; drop_guides(c);      // whatever happens below, the previous frame is over
+  c->in_frame = false; c->pending = 0; c->adaptive = false; c->cov_on = false; c->cov_resolved = false; c->sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
   if (!c->committed) return fail(c, PTC_E_STATE, "frame_begin: scene not committed");
   if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, "frame_begin: bad size");
   if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, "frame_begin: unknown integrator");
@@ -1401,6 +1410,7 @@ int ptc_frame_add_samples(ptc_ctx* c, int n_samples) {
   if (!is_raster(c->integrator) && (uint64_t)c->samples_done + c->pending + (uint64_t)n_samples > (uint64_t)c->spp_total)
     return fail(c, PTC_E_ARG, "frame_add_samples: more samples than the spp_total given to frame_begin");
   c->pending += (uint32_t)n_samples;
+  c->cov_resolved = false;          // the sums are about to hold samples the radiance buffer does not (ptc_denoise_sampled)
   // full batches go out at once; a remainder waits for more samples (or for resolve / sync / a read-back), so that many
   // small calls still produce full-width launches
   while (c->pending >= c->per_batch) {
@@ -1422,6 +1432,7 @@ int ptc_frame_resolve(ptc_ctx* c) {
   else if (c->fr.n_owned && c->samples_done)
     pt_launch_resolve(c->lanes[0].stream, c->fr, c->accum.p, c->radiance.p, (float)(c->resolve_divisor ? c->resolve_divisor : c->samples_done), is_raster(c->integrator));
   HIP_TRY(c, hipGetLastError());
+  c->cov_resolved = true;
   return PTC_OK;
 }
 
@@ -1602,14 +1613,16 @@ void ptc_denoise_default_params(ptc_denoise_params* p) {
 }
 
 namespace {
-int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated);
+int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated, bool sampled = false);
 }
 int ptc_denoise(ptc_ctx* c, const ptc_denoise_params* params) { return denoise_image(c, params, false); }
 int ptc_denoise_accumulated(ptc_ctx* c, const ptc_denoise_params* params) { return denoise_image(c, params, true); }
+int ptc_denoise_sampled(ptc_ctx* c, const ptc_denoise_params* params) { return denoise_image(c, params, false, true); }
 
 namespace {
 // accumulated: the input is the accumulated image of the frame's ptc_temporal_accumulate, i.e. D_new of the new history (demodulated already) with the temporal variance
-int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated) {
+// sampled: the input is the radiance, demodulated by k_ad_sampled_variance, with the variance of the frame's own samples (§8d) where a pixel has four or more
+int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated, bool sampled) {
   { int rd = need_device(c); if (rd) return rd; }
   ptc_denoise_params p;
   ptc_denoise_default_params(&p);
@@ -1621,12 +1634,18 @@ int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated
   if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "denoise: no radiance buffer");
   if (accumulated && !c->tp_accum_valid) return fail(c, PTC_E_STATE, "denoise_accumulated: the frame has no accumulated image (ptc_temporal_accumulate)");
   if (accumulated && (p.demodulate ? 1 : 0) != c->tp_demodulate) return fail(c, PTC_E_ARG, "denoise_accumulated: demodulate differs from the accumulate's");
+  if (sampled && !(c->in_frame && c->adaptive && c->cov_on)) return fail(c, PTC_E_STATE, "denoise_sampled: the frame is not an adaptive frame that keeps the sample covariance (ptc_set_sample_covariance before ptc_frame_set_adaptive)");
+  if (sampled && (!c->cov_resolved || c->pending)) return fail(c, PTC_E_STATE, "denoise_sampled: samples were added since the last ptc_frame_resolve");
   const size_t n = (size_t)c->rad_w * c->rad_h;
   int rc;
   if ((rc = ensure_buf(c, c->denoised, n)) || (rc = ensure_dn_events(c))) return rc;
+  if (sampled && ((rc = ensure_buf(c, c->sv_colour, n)) || (rc = ensure_buf(c, c->sv_var, n)))) return rc;
   if (p.iterations > 0 && ((rc = ensure_buf(c, c->dn_cv[0], n)) || (rc = ensure_buf(c, c->dn_cv[1], n)))) return rc;
   hipStream_t s0 = c->lanes[0].stream;      // behind the resolve, the reduce and the guide pass
   HIP_TRY(c, hipEventRecord(c->ev_dn[2], s0));
+  if (sampled)      // also with iterations = 0: ptc_read_sampled_variance serves what this call computed
+    pt_launch_ad_sampled_variance(s0, c->owned_n, c->owned.p, c->accum.p, dev_adaptive(c), c->g_albedo.p, c->radiance.p, p.demodulate ? 1 : 0, c->sv_colour.p, c->sv_var.p,
+                                  (uint32_t)n, (size_t)c->owned_n != n);
   if (p.iterations == 0) HIP_TRY(c, hipMemcpyAsync(c->denoised.p, accumulated ? c->tp_accum.p : c->radiance.p, n * sizeof(float4), hipMemcpyDeviceToDevice, s0));
   else {
     DenoiseArgs a{};
@@ -1634,7 +1653,11 @@ int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated
     a.pix = (2.0f * c->cam.sy) / (float)c->rad_h;
     a.radiance = c->radiance.p;
     a.g = GuideBufs{c->g_albedo.p, c->g_normal.p, c->g_pos.p, c->g_prim.p, c->g_uv.p};
-    if (accumulated) {      // D_new lies demodulated in the history; the iterations re-modulate it as they do ptc_denoise's, and pass the other classes' radiance through
+    if (sampled) {
+      DenoiseArgs ap = a;
+      ap.demodulate = 0;
+      pt_launch_denoise_prepare(s0, ap, c->sv_colour.p, c->sv_var.p, c->dn_cv[0].p);
+    } else if (accumulated) {      // D_new lies demodulated in the history; the iterations re-modulate it as they do ptc_denoise's, and pass the other classes' radiance through
       DenoiseArgs ap = a;
       ap.demodulate = 0;
       pt_launch_denoise_prepare(s0, ap, c->tp_dn[c->tp_cur].p, c->tp_mom[c->tp_cur].p, c->dn_cv[0].p);
@@ -1648,6 +1671,7 @@ int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated
   HIP_TRY(c, hipGetLastError());
   c->ev_dn_recorded[1] = true;
   c->denoised_valid = true;
+  if (sampled) c->sv_valid = true;
   return PTC_OK;
 }
 }  // namespace
@@ -1792,9 +1816,15 @@ int ptc_frame_set_adaptive(ptc_ctx* c, const ptc_adaptive_params* params) {
   for (int k = 0; k < 2; ++k) if ((rc = ensure_buf(c, c->ad_pix[k], n)) || (rc = ensure_buf(c, c->ad_slot[k], n))) return rc;
   if ((rc = ensure_buf(c, c->ad_mom, n)) || (rc = ensure_buf(c, c->ad_count, n)) || (rc = ensure_buf(c, c->ad_keep, n)) || (rc = ensure_buf(c, c->ad_flags, wh)) ||
       (rc = ensure_buf(c, c->ad_block, (size_t)pt_ad_blocks((uint32_t)n) + 1)) || (rc = ensure_buf(c, c->ad_n, 1))) return rc;
+  const bool cov = c->cov_setting;
+  if (cov && ((rc = ensure_buf(c, c->ad_cov4, n)) || (rc = ensure_buf(c, c->ad_cov2, n)))) return rc;
   for (hipEvent_t& e : c->ev_ad) if (!e) HIP_TRY(c, hipEventCreate(&e));
   hipStream_t s0 = c->lanes[0].stream;
   HIP_TRY(c, hipMemsetAsync(c->ad_mom.p, 0, (n ? n : 1) * sizeof(float2), s0));
+  if (cov) {
+    HIP_TRY(c, hipMemsetAsync(c->ad_cov4.p, 0, (n ? n : 1) * sizeof(float4), s0));
+    HIP_TRY(c, hipMemsetAsync(c->ad_cov2.p, 0, (n ? n : 1) * sizeof(float2), s0));
+  }
   HIP_TRY(c, hipMemsetAsync(c->ad_count.p, 0, (n ? n : 1) * sizeof(uint32_t), s0));
   HIP_TRY(c, hipMemsetAsync(c->ad_flags.p, 0, wh, s0));
   pt_launch_ad_init(s0, (uint32_t)n, c->owned.p, c->ad_pix[0].p, c->ad_slot[0].p);
@@ -1802,7 +1832,7 @@ int ptc_frame_set_adaptive(ptc_ctx* c, const ptc_adaptive_params* params) {
   HIP_TRY(c, hipStreamSynchronize(s0));      // the other lanes read these arrays too
   c->ad_cur = 0; c->ad_passes = 0; c->ad_seconds = 0.0; c->ad_params = p;
   c->fr.owned = c->ad_pix[0].p;              // n_owned is the frame's: everything is active
-  c->adaptive = true;
+  c->adaptive = true; c->cov_on = cov; c->cov_resolved = false; c->sv_valid = false;
   return PTC_OK;
 }
 
@@ -1866,6 +1896,48 @@ int ptc_get_adaptive_stats(ptc_ctx* c, ptc_adaptive_stats* out) {
   s.owned_pixels = c->owned_n; s.active_pixels = c->fr.n_owned; s.passes = c->ad_passes; s.seconds_adapt = c->ad_seconds;
   for (uint32_t v : cnt) { s.samples_total += v; if (v > s.max_count) s.max_count = v; }
   *out = s;
+  return PTC_OK;
+}
+
+int ptc_set_sample_covariance(ptc_ctx* c, int on) {
+  if (!c) return PTC_E_ARG;
+  if (on != 0 && on != 1) return fail(c, PTC_E_ARG, "set_sample_covariance: 0 or 1");
+  c->cov_setting = on == 1;
+  return PTC_OK;
+}
+
+int ptc_read_sample_covariance(ptc_ctx* c, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "read_sample_covariance: null pointer");
+  if (!c->in_frame || !c->adaptive || !c->cov_on) return fail(c, PTC_E_STATE, "read_sample_covariance: the frame is not an adaptive frame that keeps the sample covariance");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  const size_t n = c->owned_n;
+  std::vector<uint32_t> pix(n);
+  std::vector<float4> q4(n);
+  std::vector<float2> q2(n);
+  if (n) {
+    HIP_TRY(c, hipMemcpy(pix.data(), c->owned.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(q4.data(), c->ad_cov4.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(q2.data(), c->ad_cov2.p, n * sizeof(float2), hipMemcpyDeviceToHost));
+  }
+  std::memset(out, 0, (size_t)c->rad_w * (size_t)c->rad_h * 6 * sizeof(float));
+  for (size_t i = 0; i < n; ++i) {
+    float* o = out + (size_t)pix[i] * 6;
+    o[0] = q4[i].x; o[1] = q4[i].y; o[2] = q4[i].z; o[3] = q4[i].w; o[4] = q2[i].x; o[5] = q2[i].y;
+  }
+  return PTC_OK;
+}
+
+int ptc_read_sampled_variance(ptc_ctx* c, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "read_sampled_variance: null pointer");
+  if (!c->sv_valid) return fail(c, PTC_E_STATE, "read_sampled_variance: no ptc_denoise_sampled in this frame");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  const size_t n = (size_t)c->rad_w * (size_t)c->rad_h;
+  std::vector<float4> v(n);
+  HIP_TRY(c, hipMemcpy(v.data(), c->sv_var.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) { out[2 * i] = v[i].z; out[2 * i + 1] = v[i].w; }
   return PTC_OK;
 }
 

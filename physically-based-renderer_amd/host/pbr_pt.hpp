@@ -193,6 +193,32 @@ public:
     return out;
   }
   auto adaptiveStats() -> ptc_adaptive_stats { ptc_adaptive_stats s; ck(ptc_get_adaptive_stats(_ctx, &s)); return s; }
+  // ---- denoising from per-sample statistics (include/ptc.h): adaptive frames begun while the setting is on keep the RGB covariance of their samples ----
+  auto setSampleCovariance(bool on) -> void { ck(ptc_set_sample_covariance(_ctx, on ? 1 : 0)); }
+  // the raw sums (rr, gg, bb, rg, rb, gb) per pixel of the current frame
+  auto sampleCovariance() -> std::vector<float> {
+    std::vector<float> out((std::size_t)_w * _h * 6);
+    ck(ptc_read_sample_covariance(_ctx, out.data()));
+    return out;
+  }
+  // after ptc_frame_resolve and frameGuides(): the denoiser's iterations with the variance of the frame's own samples -> the denoised buffer (PTC_OUTPUT_DENOISED)
+  auto denoiseSampled(ptc_denoise_params const* params = nullptr) -> void { ck(ptc_denoise_sampled(_ctx, params)); }
+  // (Var_s, 1 / n) per pixel as the last denoiseSampled() computed them
+  auto sampledVariance() -> std::vector<float> {
+    std::vector<float> out((std::size_t)_w * _h * 2);
+    ck(ptc_read_sampled_variance(_ctx, out.data()));
+    return out;
+  }
+  // a uniform frame that keeps the statistics: an adaptive frame without a decision step, whose image is render()'s bit for bit
+  auto renderWithStatistics(int w, int h, int spp, std::uint64_t seed, int maxBounces) -> std::vector<float> {
+    setSampleCovariance(true);
+    ck(ptc_frame_begin(_ctx, w, h, spp, seed, maxBounces, PTC_INTEGRATOR_PATH, 0, 1));
+    ck(ptc_frame_set_adaptive(_ctx, nullptr));
+    ck(ptc_frame_add_samples(_ctx, spp));
+    ck(ptc_frame_resolve(_ctx));
+    ck(ptc_sync(_ctx));
+    return readRadiance(w, h);
+  }
   auto stats() -> ptc_stats { ptc_stats s; ck(ptc_get_stats(_ctx, &s)); return s; }
   auto handle() -> ptc_ctx* { return _ctx; }
 

@@ -1,11 +1,14 @@
 // ptc_render — dependency-free C++17 offline renderer over the C-ABI (include/ptc.h).
 //   ptc_render (--scene cornell|sphere | --gltf file.glb [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
 //              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
-//              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--guides PREFIX]
+//              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 // --denoise: first-hit guides + the variance-guided a-trous filter (ptc_frame_guides, ptc_denoise) after the render; every output is then the denoised
 // image.  --denoise-iters N: N iterations instead of the default 4 (implies --denoise).  --guides PREFIX: PREFIX_albedo.pfm, PREFIX_normal.pfm and
 // PREFIX_depth.pfm (the depth in all three channels) beside the image, for a denoiser outside the library.  With --gpus N device D denoises after the reduce.
+// --denoise-sampled (implies --denoise): the filter takes its variance from the per-sample RGB covariance of the frame's own samples (ptc_set_sample_covariance,
+// ptc_denoise_sampled) instead of the 7x7 window of the mean image.  With --adaptive the adaptive frame keeps the covariance; without, the frame runs as an
+// adaptive frame with no decision step, whose image is the uniform frame's bit for bit.  One context, path integrator.
 // --adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]: adaptive sampling (ptc_render_adaptive): --spp is then the
 // per-pixel maximum, a pixel stops when the relative standard error of its mean luminance is <= THRESH and no pixel within R of it (default 1) is above; N
 // samples before the first decision and between decisions (default 16 each).  --counts writes the per-pixel sample counts (all three channels).  One context
@@ -122,7 +125,7 @@ int main(int argc, char** argv) {
   float viewerFov = 0.0f;                    // --viewer-camera: the reference's fov in radians, passed on without a degree round trip
   int w = 256, h = 256, spp = 64, bounces = 8, device = 0, gpus = 0 /* 0: one plain context; N >= 1: a device group of N */, integrator = PTC_INTEGRATOR_PATH;
   std::string halfPath, guidesPrefix;
-  bool denoise = false;
+  bool denoise = false, denoiseSampled = false;
   int denoiseIters = -1;                     // -1: the library's default
   std::uint64_t seed = 1;
   bool adaptive = false;
@@ -137,6 +140,7 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = std::atoi(next()); else if (a == "--half") halfPath = next(); else if (a == "--raster16") integrator = PTC_INTEGRATOR_RASTER_GBUFFER16;
     else if (a == "--gltf") gltf = next();
     else if (a == "--denoise") denoise = true; else if (a == "--denoise-iters") { denoiseIters = std::atoi(next()); denoise = true; } else if (a == "--guides") guidesPrefix = next();
+    else if (a == "--denoise-sampled") { denoiseSampled = true; denoise = true; }
     else if (a == "--adaptive") { ap.threshold = (float)std::atof(next()); adaptive = true; } else if (a == "--min-spp") ap.min_samples = std::atoi(next());
     else if (a == "--spp-step") ap.step_samples = std::atoi(next()); else if (a == "--adaptive-radius") ap.radius = std::atoi(next()); else if (a == "--counts") countsPath = next();
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
@@ -158,6 +162,7 @@ int main(int argc, char** argv) {
   try {
     if (gpus < 0) throw std::runtime_error("--gpus must be >= 1");
     if (adaptive && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--adaptive renders on one context with the path integrator (not with --gpus / --raster)");
+    if (denoiseSampled && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--denoise-sampled renders on one context with the path integrator (not with --gpus / --raster)");
     if (!adaptive && !countsPath.empty()) throw std::runtime_error("--counts needs --adaptive");
     if (gltf.empty() && (!envPath.empty() || sky)) throw std::runtime_error("--env / --sky light a --gltf scene; the built-in scenes carry their own lights");
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
@@ -208,7 +213,9 @@ int main(int argc, char** argv) {
     if (gpus == 0) {
       single.reset(new pbr::PathTraceRenderSystem(device));
       buildScene(*single);
-      img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : single->render(w, h, spp, seed, bounces, integrator);
+      if (denoiseSampled) single->setSampleCovariance(true);
+      img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : denoiseSampled ? single->renderWithStatistics(w, h, spp, seed, bounces)
+                                                                                                : single->render(w, h, spp, seed, bounces, integrator);
     } else {
       std::vector<int> ids;
       for (int i = 0; i < gpus; ++i) ids.push_back(device + i);
@@ -246,7 +253,7 @@ int main(int argc, char** argv) {
       if (denoise) {
         ptc_denoise_params dp = pbr::PathTraceRenderSystem::denoiseDefaults();
         if (denoiseIters >= 0) dp.iterations = denoiseIters;
-        rs.denoise(&dp);
+        if (denoiseSampled) rs.denoiseSampled(&dp); else rs.denoise(&dp);
         rs.selectOutput(PTC_OUTPUT_DENOISED);
         img = rs.readRadiance(w, h);
       }

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "ptc_frame_guides", "ptc_read_guide_rgba32f", "ptc_read_guide_hit", "ptc_denoise_default_params", "ptc_denoise", "ptc_select_output", "ptc_get_denoise_seconds",
     "ptc_temporal_default_params", "ptc_temporal_accumulate", "ptc_temporal_reset", "ptc_read_temporal_rgba32f", "ptc_denoise_accumulated", "ptc_get_temporal_seconds",
     "ptc_adaptive_default_params", "ptc_frame_set_adaptive", "ptc_frame_adapt", "ptc_read_sample_counts", "ptc_render_adaptive", "ptc_get_adaptive_stats",
+    "ptc_set_sample_covariance", "ptc_read_sample_covariance", "ptc_denoise_sampled", "ptc_read_sampled_variance",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
@@ -197,6 +198,10 @@ def load_library():
     L.ptc_read_sample_counts.argtypes = [vp, u32p]
     L.ptc_render_adaptive.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(PtcAdaptiveParams)]
     L.ptc_get_adaptive_stats.argtypes = [vp, C.POINTER(PtcAdaptiveStats)]
+    L.ptc_set_sample_covariance.argtypes = [vp, C.c_int]
+    L.ptc_read_sample_covariance.argtypes = [vp, fp]
+    L.ptc_denoise_sampled.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
+    L.ptc_read_sampled_variance.argtypes = [vp, fp]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -516,6 +521,29 @@ class PathTracer:
         s = PtcAdaptiveStats()
         self._ck(self._L.ptc_get_adaptive_stats(self._h, C.byref(s)))
         return s.as_dict()
+
+    # ---- denoising from per-sample statistics ----------------------------------------------
+    def set_sample_covariance(self, on):
+        """ptc_set_sample_covariance: every adaptive frame begun (frame_set_adaptive, render_adaptive) while it is on keeps the per-pixel RGB covariance sums."""
+        self._ck(self._L.ptc_set_sample_covariance(self._h, int(on)))
+        return self
+
+    def read_sample_covariance(self):
+        """(h, w, 6) float32: the raw sums (rr, gg, bb, rg, rb, gb) of the current frame's samples, 0 where this context does not own the pixel."""
+        out = np.zeros((self._h_px, self._w, 6), np.float32)
+        self._ck(self._L.ptc_read_sample_covariance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise_sampled(self, **params):
+        """ptc_denoise_sampled: the denoiser's iterations over the resolved radiance with the variance of the frame's own samples where a pixel has four or
+        more (after frame_resolve and frame_guides).  Keywords as denoise()."""
+        self._ck(self._L.ptc_denoise_sampled(self._h, C.byref(self._denoise_params(params))))
+
+    def read_sampled_variance(self):
+        """(h, w, 2) float32: (Var_s, 1 / n) as the frame's last denoise_sampled() computed them, (0, 0) where the count is 0."""
+        out = np.zeros((self._h_px, self._w, 2), np.float32)
+        self._ck(self._L.ptc_read_sampled_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     # ---- multi-GPU (RCCL through the C-ABI) ---------------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, n_ranks: int):

@@ -8,7 +8,13 @@ the curve) — the speed-up at equal quality is uniform time at that spp / adapt
 
   python tools/adaptive_bench.py [atrium|textured|both] [--ref-spp N] [--max-spp N] [--reps N] [--size W H]
   python tools/adaptive_bench.py atrium --one THRESH      one warmed adaptive frame and nothing else: the run to put behind `rocprofv3 --kernel-trace --stats --`
-                                                          for the k_ad_* rows (per-launch times, share of the frame)"""
+                                                          for the k_ad_* rows (per-launch times, share of the frame)
+  python tools/adaptive_bench.py atrium --sampled [--max-spp N] [--reps N]
+                                                          what the per-sample covariance costs and ptc_denoise_sampled takes (-> profiles/sampled_variance_1080p.txt):
+                                                          the adaptive render at the default threshold with ptc_set_sample_covariance on against off, alternating, and
+                                                          the HIP-event time of ptc_denoise_sampled against ptc_denoise on the same frame.  With --one THRESH: one
+                                                          warmed frame with the covariance on + guides + ptc_denoise_sampled, the run to put behind rocprofv3 for the
+                                                          k_ad_accumulate<true> / k_ad_sampled_* rows"""
 import argparse
 import os
 import sys
@@ -28,6 +34,7 @@ ap.add_argument("--max-spp", type=int, default=1024)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--size", type=int, nargs=2, default=(1920, 1080))
 ap.add_argument("--one", type=float, default=None)
+ap.add_argument("--sampled", action="store_true")
 args = ap.parse_args()
 W, H = args.size
 SEED, REF_SEED, BOUNCES = 1, 99, 8
@@ -60,6 +67,46 @@ def adaptive_frame(pt, thr, mn, step):
     return st["seconds_render"] + ad["seconds_adapt"], wall, st, ad
 
 
+def run_sampled(pt, name):
+    """The adaptive render with the covariance on against off (alternating, same process), then ptc_denoise against ptc_denoise_sampled on the last frame."""
+    thr = 0.05 if args.one is None else args.one
+    if args.one is not None:
+        pt.set_sample_covariance(1)
+        adaptive_frame(pt, thr, 16, 16)
+        ev, wall, st, ad = adaptive_frame(pt, thr, 16, 16)
+        pt.frame_guides()
+        pt.denoise_sampled()
+        pt.sync()
+        print(f"one adaptive frame with the covariance, threshold {thr}: event {ev:.4f} s, wall {wall:.4f} s, mean count {ad['samples_total'] / ad['owned_pixels']:.2f}; "
+              f"ptc_denoise_sampled {pt.denoise_seconds()[1] * 1e3:.3f} ms", flush=True)
+        return
+    for on in (0, 1):                                                # warm-up: queues and both sets of buffers allocated, code loaded
+        pt.set_sample_covariance(on)
+        adaptive_frame(pt, thr, 16, 16)
+    rows = {0: [], 1: []}
+    for rep in range(args.reps):
+        for on in (0, 1):
+            pt.set_sample_covariance(on)
+            ev, wall, st, ad = adaptive_frame(pt, thr, 16, 16)
+            rows[on].append((ev, wall, ad["samples_total"] / ad["owned_pixels"], st["paths"]))
+    for on in (0, 1):
+        v = rows[on]
+        print(f"adaptive threshold {thr}, covariance {'on' if on else 'off'}: event s {[round(x[0], 4) for x in v]}, wall s {[round(x[1], 4) for x in v]}, mean count {v[-1][2]:.2f}, paths {v[-1][3]}", flush=True)
+    e0, e1 = np.median([x[0] for x in rows[0]]), np.median([x[0] for x in rows[1]])
+    w0, w1 = np.median([x[1] for x in rows[0]]), np.median([x[1] for x in rows[1]])
+    print(f"covariance on / off: event {e1 / e0:.4f}, wall {w1 / w0:.4f} (medians of {args.reps})", flush=True)
+    pt.frame_guides()                                                # the last frame keeps the covariance
+    plain, sampled = [], []
+    for rep in range(max(args.reps, 3) + 1):
+        pt.denoise()
+        plain.append(pt.denoise_seconds()[1])
+        pt.denoise_sampled()
+        sampled.append(pt.denoise_seconds()[1])
+    print(f"ptc_denoise ms {[round(t * 1e3, 3) for t in plain[1:]]}, ptc_denoise_sampled ms {[round(t * 1e3, 3) for t in sampled[1:]]} (4 iterations, the first pair dropped); "
+          f"sampled / plain {np.median(sampled[1:]) / np.median(plain[1:]):.3f}", flush=True)
+    pt.set_sample_covariance(0)
+
+
 def spp_for(curve, target):
     """the uniform spp whose relMSE is `target`: log-log interpolation between the measured levels (extrapolated with the last slope beyond them)"""
     lv = sorted(curve)
@@ -76,6 +123,10 @@ def run(name):
     desc = scenes.atrium() if name == "atrium" else scenes.textured_atrium()
     pt = pbr_amd.PathTracer(0).load_scene(desc)
     print(f"== {name} {W}x{H}, max_spp {args.max_spp}, max_bounces {BOUNCES}; {pbr_amd.load_library().ptc_build_info().decode()}", flush=True)
+    if args.sampled:
+        run_sampled(pt, name)
+        pt.close()
+        return
     if args.one is not None:
         adaptive_frame(pt, args.one, 16, 16)
         ev, wall, st, ad = adaptive_frame(pt, args.one, 16, 16)
