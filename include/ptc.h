@@ -188,6 +188,37 @@ int ptc_scene_refit(ptc_ctx*);
  * emitters falls back to a host build + upload (as ptc_scene_refit does).  ptc_stats.bvh_sa_cost / bvh_sa_cost_built say when it is worth calling. */
 int ptc_scene_rebuild(ptc_ctx*);
 
+/* ---- deforming meshes: morph targets and skinning, evaluated on the device (csrc/pt_deform.h is the definition) ----------------
+ * A mesh may carry T >= 0 morph targets — per vertex a position, a normal and a tangent delta — and a skin: per vertex 4 joint indices and 4 weights over
+ * n_joints >= 1 joints.  A POSE is T weights and n_joints joint matrices of 12 floats: rows 0..2 of a column-major 4x4, column by column
+ * (J[c * 3 + r] = M[c * 4 + r]); the default pose is weights 0 and identity matrices.  Per vertex, from the mesh's BASE vertex, in IEEE binary32 without
+ * contraction, in the order written:
+ *   morph   for k = 0 .. T-1 ascending: p_c = p_c + w_k dp_k,c; the same for the normal and for tangent.xyz (a missing delta array is zeros)
+ *   skin    S_e = ((a0 J[j0]_e + a1 J[j1]_e) + a2 J[j2]_e) + a3 J[j3]_e for the 12 entries, the weights as given (no renormalisation);
+ *           p'_r = ((S_r0 p_0 + S_r1 p_1) + S_r2 p_2) + S_r3; normal and tangent.xyz through the upper 3x3, a three-term sum in the same order
+ *   tangent.w and the texcoord are copied; nothing is normalised (the flatten normalises N, T, B after the normal matrix, as for every mesh).
+ * The instance transform applies afterwards, unchanged: a glTF joint matrix is inverse(global(mesh node)) global(joint) inverseBind.
+ *
+ * ptc_mesh_set_morph_targets / ptc_mesh_set_skin belong to the description: after ptc_add_mesh, before ptc_scene_commit (PTC_E_STATE once committed).
+ *   dpos, dnormal, dtangent: n_targets * n_verts * 3 floats each, TARGET-major ([target][vertex][3]); dnormal and dtangent may be NULL; n_targets = 0
+ *   removes the targets.  joints_u16x4 / weights_f32x4: n_verts * 4 each; a joint index >= n_joints gives PTC_E_ARG.  Both reset that half of the pose
+ *   to the default.
+ * ptc_update_mesh_pose (any time after the mesh exists): a non-NULL array must come with the mesh's count (T weights, n_joints matrices), otherwise
+ *   PTC_E_ARG and nothing changes; a NULL array leaves that half of the pose as it is.
+ * ptc_update_mesh_vertices: replaces the mesh's BASE vertices (same count, otherwise PTC_E_ARG) — for a caller who deforms on their own, e.g. a
+ *   simulation; works on any mesh.
+ * Both update calls only record.  ptc_scene_commit, ptc_scene_refit, ptc_scene_rebuild and ptc_group_scene_refit (the poses set on ptc_group_ctx(g, 0), as
+ * for transforms) apply them.  Where the refit runs on the device, the posed meshes are evaluated there by csrc/pt_deform.hip, into the object-space
+ * vertices the flatten reads: only the pose crosses the bus.  The host evaluates the same expressions for the vertices of emissive primitives (the emitter
+ * table is the host's), and whole meshes when a host path needs them (PTC_REFIT=host, PTC_REBUILD=host, a description-only context, a change of the
+ * emitter set, a host commit).  A commit of a posed description is byte for byte the commit of plain meshes that hold the posed vertices; a refit refused
+ * for a non-finite position leaves the scene in HBM, object-space vertices included, as it was; the temporal history survives a deformation as it
+ * survives a refit.  ptc_scene_begin drops all of it.  A context that never calls these computes what it always did. */
+int ptc_mesh_set_morph_targets(ptc_ctx*, int mesh, uint32_t n_targets, const float* dpos, const float* dnormal, const float* dtangent);
+int ptc_mesh_set_skin(ptc_ctx*, int mesh, uint32_t n_joints, const uint16_t* joints_u16x4, const float* weights_f32x4);
+int ptc_update_mesh_pose(ptc_ctx*, int mesh, const float* morph_weights, uint32_t n_weights, const float* joint_matrices, uint32_t n_joints);
+int ptc_update_mesh_vertices(ptc_ctx*, int mesh, const ptc_vertex* verts, uint32_t n_verts);
+
 /* pbr::makeCameraData (engine/pbr/CameraData.hpp:22-32): lookAtRH(pos,target,up=(0,-1,0)),
  * perspective fovY/aspect; y-down un-flipped viewport (PbrRenderSystem.cpp:425-430). */
 int ptc_set_camera(ptc_ctx*, const float pos[3], const float target[3], float fov_y,
@@ -494,6 +525,11 @@ int ptc_debug_trace_any(ptc_ctx*, const float* origins, const float* dirs, const
  * indices (n_tris*3 u32), per-triangle material.  Pass NULL to query sizes only. */
 int ptc_debug_get_flat_scene(ptc_ctx*, uint32_t* n_verts, uint32_t* n_tris, ptc_vertex* verts,
                              uint32_t* indices, int32_t* tri_material);
+/* The current posed object-space vertices of mesh `mesh` (n_verts of the mesh).  On a committed scene that is the LIVE pose, the one the
+ * last commit, refit or rebuild applied: a pose that is only recorded, or that a refit refused, does not show.  They are read from HBM
+ * when the kernel evaluated them there (ptc_debug_get_internals [7] bit 3 then says so); else the host evaluates them.  Before the first
+ * commit: the host's evaluation of the recorded pose. */
+int ptc_debug_get_mesh_vertices(ptc_ctx*, int mesh, ptc_vertex* out);
 
 /* The scene description as received (valid from ptc_scene_begin on, committed or not): number of materials and
  * textures; material i as 12 values (base rgba, metallic, roughness, emissive rgb as floats; tex_color, tex_normal,
@@ -521,7 +557,8 @@ uint64_t ptc_debug_host_build_id(const ptc_ctx*);
  * issued, [5] trace blocks per CU, [6] stack entries per lane kept in LDS, [7] bit 0: the last ptc_scene_refit ran on the
  * device (csrc/pt_refit.hip), not on the host; bit 1: the last ptc_scene_commit flattened and built on the device
  * (csrc/pt_refit.hip + csrc/pt_build.hip: the LBVH builder on a device context, or the SAH builder with the SAH device builder); bit 2: the
- * tree now in HBM was built on the device by the SAH front end (ptc_set_device_builder). */
+ * tree now in HBM was built on the device by the SAH front end (ptc_set_device_builder); bit 3: the last ptc_debug_get_mesh_vertices
+ * read the mesh's slice in HBM, where csrc/pt_deform.hip had written it. */
 int ptc_debug_get_internals(ptc_ctx*, uint64_t out[8]);
 
 /* The host's share of a commit ON THE DEVICE (the LBVH builder on a device context: indices and material per primitive, materials, the emitter table from the

@@ -25,6 +25,30 @@ extern "C" {
 long long ptc_gltf_load(ptc_ctx* ctx, const char* path, int scene_index, int compose_parents, float bbox6[6],
                         char* err, int err_len);
 
+/* ---- the asset as a handle: skins, morph targets and animations ---------------------------------------------------------------------
+ * ptc_gltf_load is stateless and reads the bind pose only.  A handle keeps the parsed file, so that the scene it loaded can be posed:
+ *   ptc_gltf_open          parse the file; NULL on failure (text in err)
+ *   ptc_gltf_asset_load    what ptc_gltf_load does (same arguments, same return value), plus: morph `targets` with the mesh's / node's default
+ *                          `weights` (ptc_mesh_set_morph_targets), JOINTS_0 (u8 / u16) + WEIGHTS_0 (float, normalised u8 / u16) and `skins` with their
+ *                          inverseBindMatrices (ptc_mesh_set_skin).  One ptc mesh per (primitive, skin) pair, and per node for a primitive that deforms:
+ *                          a pose belongs to a mesh.  The scene is left in the bind pose with the default weights.
+ *   ptc_gltf_asset_animations / ptc_gltf_asset_duration   the number of animations; the last key time of one, in seconds (-1: no such animation)
+ *   ptc_gltf_asset_pose    node transforms of `animation` at `time_seconds`, clamped to the animation's range: channels translation, rotation, scale and
+ *                          weights; samplers LINEAR and STEP, rotations by slerp along the shorter arc; a CUBICSPLINE sampler is sampled LINEARLY over
+ *                          its value entries (its tangents are not used).  Issues ptc_update_instance_matrix for every instance and
+ *                          ptc_update_mesh_pose for every deforming mesh, joint matrix = inverse(global(mesh node)) global(joint) inverseBind; the
+ *                          caller then calls ptc_scene_refit / ptc_scene_rebuild (or ptc_scene_commit, when the scene is not committed yet).
+ *   ptc_gltf_close         frees the handle (the context is not touched)
+ * Errors: a negative PTC_E_* code; ptc_gltf_asset_last_error has the text. */
+typedef struct ptc_gltf_asset ptc_gltf_asset;
+ptc_gltf_asset* ptc_gltf_open(const char* path, char* err, int err_len);
+long long ptc_gltf_asset_load(ptc_gltf_asset* asset, ptc_ctx* ctx, int scene_index, int compose_parents, float bbox6[6]);
+int ptc_gltf_asset_animations(const ptc_gltf_asset* asset);
+double ptc_gltf_asset_duration(const ptc_gltf_asset* asset, int animation);
+int ptc_gltf_asset_pose(ptc_gltf_asset* asset, ptc_ctx* ctx, int animation, double time_seconds);
+const char* ptc_gltf_asset_last_error(const ptc_gltf_asset* asset);
+void ptc_gltf_close(ptc_gltf_asset* asset);
+
 /* PNG file image (any colour type / bit depth / interlacing) → w*h*4 bytes RGBA8, row 0 on top; the decoder the loader
  * uses for glTF images (replaces stbi_load_from_memory(..., STBI_rgb_alpha), LoadImage.cpp:56-73).  out may be NULL to
  * query the size only.  Returns 0 or a negative PTC_E_* code with the text in err. */

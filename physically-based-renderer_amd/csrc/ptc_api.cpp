@@ -15,6 +15,7 @@
 #include "pt_denoise.h"
 #include "pt_adaptive.h"
 #include "pt_temporal.h"
+#include "pt_deform.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -78,6 +79,30 @@ struct CommittedScene {
   bool last_refit_on_device = false;
   bool commit_on_device = false;      // the last ptc_scene_commit flattened and built on the device (device_commit)
   bool tree_device_sah = false;       // the tree in HBM was built on the device by the SAH front end (pt_build_sah)
+  // deforming meshes (pt_deform.h): what ensure_refit_plan puts into HBM for every mesh with deformation state, by mesh index (n_verts = 0: none)
+  std::vector<DevDeform> deform;
+  std::vector<std::vector<float>> pose_stage;   // host side of the pose uploads in flight (alive until the pass that queued them has synchronised)
+  std::vector<uint32_t> mesh_first;   // first vertex of every mesh in the object-space vertex array
+  HostVertex* mesh_verts_rw = nullptr;   // drf.mesh_verts is const for the flatten: the deform kernel writes through this alias
+};
+
+// Deformation state of one mesh of the description (index = mesh id; a mesh that never saw one of the new calls has none: base == nullptr).
+// c->meshes[m].v holds the POSED vertices — that is what every host path reads — and is brought up to date lazily (deform_host_all / deform_host_emissive).
+// The pending pose is what the update calls recorded; the live pose is the one the mesh's slice in HBM was evaluated from (a refused refit re-evaluates from it,
+// as xf_live keeps the live transforms).  Vertex arrays and the fixed data are shared: the contexts of a group take context 0's.
+struct MeshPose {
+  std::shared_ptr<DeformMesh> data;
+  std::shared_ptr<std::vector<HostVertex>> base;        // base vertices as described (ptc_update_mesh_vertices replaces the vector)
+  std::vector<float> w, J;                              // pending: morph weights, joint matrices (12 floats each)
+  std::vector<float> pose_live;                         // live: weights then matrices
+  std::shared_ptr<std::vector<HostVertex>> base_live;   // live base
+  const void* base_on_device = nullptr;                 // identity of the vector DevDeform::base was uploaded from
+  bool host_fresh = false;      // meshes[m].v is the pending pose, every vertex
+  bool emis_fresh = false;      // ... at least the vertices of emissive primitives
+  bool dev_fresh = false;       // the slice in HBM is the pending pose (live == pending)
+  bool on_device = false;       // the slice in HBM was written by the kernel (ptc_debug_get_mesh_vertices reads it from there)
+  bool active() const { return base != nullptr; }
+  std::vector<float> pose() const { std::vector<float> p(w); p.insert(p.end(), J.begin(), J.end()); return p; }
 };
 
 // ---- RCCL, loaded on first use (a renderer that never reduces does not need librccl at load time) -------------------
@@ -143,7 +168,9 @@ struct ptc_ctx {
   bool committed = false;
   std::shared_ptr<HostBuilt> built = std::make_shared<HostBuilt>();   // the host build; the contexts of a ptc_group share one (ptc_group_scene_commit)
   CommittedScene scene;
+  std::vector<MeshPose> poses;      // deformation state by mesh id (may be shorter than meshes: plain meshes at the end have none)
   DevCamera cam{};
+  bool debug_verts_from_device = false;      // the last ptc_debug_get_mesh_vertices read the mesh's slice in HBM (ptc_debug_get_internals[7] bit 3)
   int refit_on_device = 1;          // PTC_REFIT=host: ptc_scene_refit recomputes on the host and uploads (the round-3a path, kept as the cross-check)
   int trace_rays_per_lane = 8;      // PTC_TRACE_RAYS_PER_LANE: rays per lane of the trace kernels' grid a batch should offer before the grid is made smaller (run_batch)
   int trace_overlap = 1;            // PTC_TRACE_OVERLAP: the shadow rays of bounce b are traced on the lane's second stream beside the closest-hit launch of bounce b + 1 (they are
@@ -281,6 +308,7 @@ void release_scene(ptc_ctx* c) {
   CommittedScene fresh;
   fresh.last_refit_on_device = s.last_refit_on_device; fresh.commit_on_device = s.commit_on_device; fresh.tree_device_sah = s.tree_device_sah;
   s = std::move(fresh);
+  for (MeshPose& P : c->poses) { P.base_on_device = nullptr; P.on_device = false; }
 }
 
 template <class T> int ensure_buf(ptc_ctx* c, DevBuf<T>& b, size_t n) {
@@ -766,6 +794,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   }
   c->mats.clear(); c->meshes.clear(); c->insts.clear(); c->texs.clear(); c->env = HostEnv{}; c->tex_linear = 0;
   c->bvh_builder = c->bvh_default;
+  c->poses.clear();
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   release_scene(c);
@@ -835,6 +864,158 @@ namespace {
 // what a commit_upload is for: a commit brings new primitive ids (the temporal history goes), a refit or rebuild that has to lay the arrays out anew keeps them
 enum class Upload { NewScene, SameScene };
 int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload what, bool skeleton = false);
+
+// ---- deforming meshes (pt_deform.h): the stage before the flatten ---------------------------------------------------------------------
+// Gives mesh `mesh` deformation state: its base vertices are the vertices as described, and so far they are what every copy holds.
+MeshPose* pose_make(ptc_ctx* c, int mesh) {
+  if (c->poses.size() <= (size_t)mesh) c->poses.resize((size_t)mesh + 1);
+  MeshPose& P = c->poses[(size_t)mesh];
+  if (!P.active()) {
+    P.base = std::make_shared<std::vector<HostVertex>>(c->meshes[(size_t)mesh].v);
+    P.data = std::make_shared<DeformMesh>();
+    P.data->n_verts = (uint32_t)P.base->size();
+    P.base_live = P.base; P.pose_live.clear();
+    P.host_fresh = P.emis_fresh = P.dev_fresh = true;      // a mesh without targets and skin evaluates to its base, bit for bit
+  }
+  return &P;
+}
+void pose_changed(MeshPose& P) { P.host_fresh = P.emis_fresh = P.dev_fresh = false; }
+bool any_pose(const ptc_ctx* c) { for (const MeshPose& P : c->poses) if (P.active()) return true; return false; }
+
+// The host evaluates whole meshes whenever a host path needs the description (a host commit, refit or rebuild, a description-only context)
+void deform_host_all(ptc_ctx* c) {
+  for (size_t m = 0; m < c->poses.size(); ++m) {
+    MeshPose& P = c->poses[m];
+    if (!P.active() || P.host_fresh) continue;
+    const std::vector<float> pose = P.pose();
+    pt_deform_eval_mesh(*P.data, P.base->data(), pose.data(), c->meshes[m].v.data());
+    P.host_fresh = P.emis_fresh = true;
+  }
+}
+// ... and the vertices of emissive primitives alone for a refit on the device: ptc_refit_emitters reads those from the description
+void deform_host_emissive(ptc_ctx* c) {
+  bool any = false;
+  for (const MeshPose& P : c->poses) any = any || (P.active() && !P.emis_fresh);
+  if (!any) return;
+  std::vector<std::vector<float>> pose(c->poses.size());
+  for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active() && !c->poses[m].emis_fresh) pose[m] = c->poses[m].pose();
+  const std::vector<int32_t>& E = c->scene.plan.emit_prims;
+  for (size_t j = 0; j * 5 < E.size(); ++j) {
+    const size_t m = (size_t)c->insts[(size_t)E[j * 5 + 1]].mesh;
+    if (m >= c->poses.size() || !c->poses[m].active() || c->poses[m].emis_fresh) continue;
+    const MeshPose& P = c->poses[m];
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t v = (uint32_t)E[j * 5 + 2 + k];
+      pt_deform_eval_vertex(*P.data, P.base->data(), pose[m].data(), v, c->meshes[m].v[v]);
+    }
+  }
+  for (MeshPose& P : c->poses) if (P.active()) P.emis_fresh = true;
+}
+bool deform_pending_finite(const ptc_ctx* c) {
+  for (const MeshPose& P : c->poses)
+    if (P.active() && !P.dev_fresh && !(pt_deform_pose_finite(P.w.data(), P.w.size()) && pt_deform_pose_finite(P.J.data(), P.J.size()))) return false;
+  return true;
+}
+// The scene in HBM was laid out from the description as it stands (a commit, a host refit or rebuild): what is pending is live now
+void deform_all_live(ptc_ctx* c) {
+  for (MeshPose& P : c->poses) if (P.active()) { P.pose_live = P.pose(); P.base_live = P.base; }
+}
+
+// Base vertices, deltas and skin records of every mesh with deformation state go to HBM with the refit plan and stay there
+int deform_upload_mesh(ptc_ctx* c, size_t m) {
+  CommittedScene& s = c->scene;
+  if (s.deform.size() < s.mesh_first.size()) { s.deform.resize(s.mesh_first.size(), DevDeform{}); s.pose_stage.resize(s.mesh_first.size()); }
+  {
+    MeshPose& P = c->poses[m];
+    const DeformMesh& D = *P.data;
+    DevDeform d{};
+    int rc = dev_upload(c, s.allocs, &d.base, *P.base);
+    if (!rc && D.n_targets) rc = dev_upload(c, s.allocs, &d.dp, D.dp);
+    if (!rc && !D.dn.empty()) rc = dev_upload(c, s.allocs, &d.dn, D.dn);
+    if (!rc && !D.dt.empty()) rc = dev_upload(c, s.allocs, &d.dt, D.dt);
+    if (!rc && !D.skin.empty()) rc = dev_upload(c, s.allocs, &d.skin, D.skin);
+    float* pose = nullptr;
+    if (!rc) rc = dev_alloc(c, s.allocs, &pose, pt_deform_pose_floats(D.n_targets, D.n_joints));
+    if (rc) return rc;
+    d.pose = pose; d.out = s.mesh_verts_rw + s.mesh_first[m];
+    d.n_verts = D.n_verts; d.n_targets = D.n_targets; d.n_joints = D.skin.empty() ? 0u : D.n_joints;
+    s.deform[m] = d;
+    P.base_on_device = P.base.get();
+    // the slice holds whatever the description's copy held when the plan was made: only a fully evaluated copy is the pending pose
+    P.dev_fresh = P.dev_fresh && P.host_fresh;
+    P.on_device = false;
+  }
+  return PTC_OK;
+}
+int deform_upload(ptc_ctx* c) {
+  for (size_t m = 0; m < c->poses.size() && m < c->scene.mesh_first.size(); ++m)
+    if (c->poses[m].active()) { int rc = deform_upload_mesh(c, m); if (rc) return rc; }
+  return PTC_OK;
+}
+// Evaluates, in HBM, every mesh whose slice is not the pending pose: from the pending pose, or (live) back from the live one after a refused refit
+int deform_device(ptc_ctx* c, hipStream_t st, bool live) {
+  CommittedScene& s = c->scene;
+  for (size_t m = 0; m < c->poses.size() && m < s.mesh_first.size(); ++m) {
+    MeshPose& P = c->poses[m];
+    if (!P.active() || P.dev_fresh) continue;
+    if (m >= s.deform.size() || !s.deform[m].n_verts) {      // the mesh got its state after the plan was made (ptc_update_mesh_vertices on a plain mesh)
+      int rc = deform_upload_mesh(c, m); if (rc) return rc;
+      P.dev_fresh = false;
+    }
+    const DevDeform& d = s.deform[m];
+    const std::shared_ptr<std::vector<HostVertex>>& base = live ? P.base_live : P.base;
+    if (P.base_on_device != base.get()) {
+      HIP_TRY(c, hipMemcpyAsync((void*)d.base, base->data(), base->size() * sizeof(HostVertex), hipMemcpyHostToDevice, st));
+      HIP_TRY(c, hipStreamSynchronize(st));      // the source is pageable memory that may go
+      P.base_on_device = base.get();
+    }
+    std::vector<float>& pose = s.pose_stage[m];      // the caller synchronises the stream before it returns
+    pose = live ? P.pose_live : P.pose();
+    if (pose.size() != pt_deform_pose_floats(d.n_targets, P.data->skin.empty() ? 0u : P.data->n_joints)) return fail(c, PTC_E_STATE, "deform: pose size does not match the mesh");
+    if (!pose.empty()) HIP_TRY(c, hipMemcpyAsync((void*)d.pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, st));
+    pt_launch_deform(st, d);
+    P.on_device = true;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return PTC_OK;
+}
+// the refit the device has completed used the pending poses: they are the live ones now
+void deform_applied(ptc_ctx* c) {
+  for (size_t m = 0; m < c->poses.size() && m < c->scene.deform.size(); ++m) {
+    MeshPose& P = c->poses[m];
+    if (!P.active() || P.dev_fresh || !c->scene.deform[m].n_verts) continue;
+    P.pose_live = P.pose(); P.base_live = P.base; P.dev_fresh = true;
+  }
+}
+// A host refit rewrote the scene's arrays in place from the fully evaluated description: the object-space vertices in HBM follow, so that a later refit on the
+// device starts from the same state
+int deform_after_host_refit(ptc_ctx* c) {
+  deform_all_live(c);
+  CommittedScene& s = c->scene;
+  if (c->device < 0 || !s.refit_ready) return PTC_OK;
+  for (size_t m = 0; m < c->poses.size() && m < s.deform.size(); ++m) {
+    MeshPose& P = c->poses[m];
+    if (!P.active() || P.dev_fresh || !s.deform[m].n_verts || !P.host_fresh) continue;
+    HIP_TRY(c, hipMemcpy(s.deform[m].out, c->meshes[m].v.data(), c->meshes[m].v.size() * sizeof(HostVertex), hipMemcpyHostToDevice));
+    P.dev_fresh = true; P.on_device = false;
+  }
+  return PTC_OK;
+}
+// A group member takes context 0's deformation state (shared arrays, its own flags); with_verts: and the evaluated vertices, for a host path
+void deform_take(ptc_ctx* c, const ptc_ctx* c0, bool with_verts) {
+  if (c == c0) return;
+  c->poses.resize(c0->poses.size());
+  for (size_t m = 0; m < c0->poses.size(); ++m) {
+    const MeshPose& Q = c0->poses[m];
+    MeshPose& P = c->poses[m];
+    if (!Q.active()) { P = MeshPose(); continue; }
+    const bool same = P.active() && P.data == Q.data && P.base == Q.base && P.w == Q.w && P.J == Q.J;
+    if (!P.active()) { P.pose_live = Q.pose_live; P.base_live = Q.base_live; }
+    P.data = Q.data; P.base = Q.base; P.w = Q.w; P.J = Q.J;
+    if (!same) pose_changed(P);
+    if (with_verts && Q.host_fresh && m < c->meshes.size()) { c->meshes[m].v = c0->meshes[m].v; P.host_fresh = P.emis_fresh = true; }
+  }
+}
 // Device half of a refit: c->built holds the refitted arrays.  same_sizes: overwrite in place what depends on the vertex positions (textures,
 // environment and materials stay where they are); else (an emitter appeared or vanished under a degenerate scale) upload everything.
 int refit_upload(ptc_ctx* c, bool same_sizes, std::chrono::steady_clock::time_point t0) {
@@ -886,7 +1067,13 @@ int ensure_refit_plan(ptc_ctx* c) {
   if (!rc) rc = dev_alloc(c, s.allocs, &d.bounds, 8);
   if (!rc) rc = dev_alloc(c, s.allocs, &d.cost, 1);
   if (!rc) { std::vector<uint32_t> cls; ptc_prim_classes(c->mats, B.tri_mat, cls); rc = dev_upload(c, s.allocs, &d.prim_cls, cls); }
-  if (rc) { free_all(tree); return rc; }
+  if (!rc) {      // the deformation data of the posed meshes, before the tree arrays join the live set: a failure here leaves as little behind as one above
+    s.mesh_verts_rw = const_cast<HostVertex*>(d.mesh_verts);
+    s.mesh_first.resize(c->meshes.size());
+    { uint32_t at = 0; for (size_t m = 0; m < c->meshes.size(); ++m) { s.mesh_first[m] = at; at += (uint32_t)c->meshes[m].v.size(); } }
+    if (any_pose(c)) rc = deform_upload(c);
+  }
+  if (rc) { free_all(tree); s.deform.clear(); s.pose_stage.clear(); s.mesh_verts_rw = nullptr; return rc; }
   s.live.levels = const_cast<uint32_t*>(d.level_nodes); s.live.levels_cap = P.level_nodes.size(); s.live.nbox = d.nbox; s.live.nbox_cap = nbox_cap;
   d.shade = const_cast<float4*>(s.dsc.shade);
   d.n_verts = P.n_verts; d.n_tris = P.n_tris; d.shade_stride = B.shade_stride;
@@ -913,6 +1100,8 @@ const char* const kNonFinite = "scene_commit: non-finite vertex position after t
 // A group member takes device 0's description: materials are counted from it, a later ptc_scene_commit on this context rebuilds from it
 void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   c->mats = c0->mats; c->meshes = c0->meshes; c->insts = c0->insts; c->texs = c0->texs; c->env = c0->env;
+  c->poses.clear(); deform_take(c, c0, /*with_verts=*/false);
+  for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active()) c->poses[m].host_fresh = c->poses[m].emis_fresh = c0->poses[m].host_fresh;
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
@@ -930,9 +1119,12 @@ struct Moved { std::vector<float> xf, lights, cdf; float lo[3], hi[3]; };
 int geometry_pass(ptc_ctx* c, Moved& m) {
   CommittedScene& s = c->scene;
   if (!ptc_refit_instance_transforms(c->insts, m.xf)) return fail(c, PTC_E_STATE, kNonFinite);
+  if (!deform_pending_finite(c)) return fail(c, PTC_E_STATE, kNonFinite);
+  deform_host_emissive(c);
   if (!ptc_refit_emitters(c->mats, c->meshes, c->insts, s.plan, *c->built, m.lights, m.cdf)) return 1;
   hipStream_t st = c->lanes[0].stream;
   const DevRefit& d = s.drf;
+  { int rc = deform_device(c, st, /*live=*/false); if (rc) return rc; }      // the posed meshes' object-space vertices, before the flatten reads them
   HIP_TRY(c, hipMemcpyAsync(d.inst_xf, m.xf.data(), m.xf.size() * 4, hipMemcpyHostToDevice, st));
   pt_launch_refit_geometry(st, d);
   uint32_t raw[8];
@@ -941,6 +1133,8 @@ int geometry_pass(ptc_ctx* c, Moved& m) {
   bool bad = false;
   pt_refit_decode_bounds(raw, m.lo, m.hi, &bad);
   if (bad) {     // nothing of the scene was written (k_refit_prims saw the flag); the scratch vertices go back to the state the scene in HBM was made from
+    { int rc = deform_device(c, st, /*live=*/true); if (rc) return rc; }      // object-space vertices included: back to the live poses
+    HIP_TRY(c, hipStreamSynchronize(st));
     if (!s.xf_live.empty()) {
       HIP_TRY(c, hipMemcpyAsync(d.inst_xf, s.xf_live.data(), s.xf_live.size() * 4, hipMemcpyHostToDevice, st));
       pt_launch_refit_geometry(st, d);
@@ -973,6 +1167,7 @@ int node_pass(ptc_ctx* c, Moved& m, bool publish) {
   B.sa_cost_fixed = cost_fixed;
   s.host_stale = true; s.last_refit_on_device = true;
   s.xf_live.swap(m.xf);
+  deform_applied(c);
   return PTC_OK;
 }
 
@@ -1058,6 +1253,7 @@ int refresh_host_copy(ptc_ctx* c) {
 // The tree: a rebuild's is the device builder's (the one device_rebuild would have made); a refit's is the scene's builder, or the SAH when the tree it replaces
 // is a device SAH build.
 int host_build_and_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, bool as_refit) {
+  deform_host_all(c);
   auto built = std::make_shared<HostBuilt>();
   const int builder = as_refit ? (c->scene.tree_device_sah ? PTC_BVH_SAH : c->bvh_builder) : c->device_builder;
   const std::string e = ptc_build_scene(c->mats, c->meshes, c->insts, c->texs, c->env, c->toplet_budget, builder, *built);
@@ -1090,6 +1286,104 @@ int ptc_update_instance(ptc_ctx* c, int instance, const float t[3], const float 
   return PTC_OK;
 }
 
+
+// ---- deforming meshes: description (before the commit) and pose updates (any time); DESIGN.md §7a --------------------------------------
+int ptc_mesh_set_morph_targets(ptc_ctx* c, int mesh, uint32_t n_targets, const float* dpos, const float* dnormal, const float* dtangent) {
+  if (!c) return PTC_E_ARG;
+  if (mesh < 0 || mesh >= (int)c->meshes.size()) return fail(c, PTC_E_ARG, "mesh_set_morph_targets: mesh out of range");
+  if (n_targets > 0 && !dpos) return fail(c, PTC_E_ARG, "mesh_set_morph_targets: null pointer");
+  if (n_targets > 65535u) return fail(c, PTC_E_ARG, "mesh_set_morph_targets: too many targets");
+  if (c->committed) return fail(c, PTC_E_STATE, "mesh_set_morph_targets: the scene is committed (targets belong to the description: ptc_scene_begin)");
+  MeshPose& P = *pose_make(c, mesh);
+  auto D = std::make_shared<DeformMesh>(*P.data);
+  const size_t n = (size_t)n_targets * D->n_verts * 3;
+  D->n_targets = n_targets;
+  D->dp.assign(dpos, dpos + (n_targets ? n : 0));
+  if (dnormal && n_targets) D->dn.assign(dnormal, dnormal + n); else D->dn.clear();
+  if (dtangent && n_targets) D->dt.assign(dtangent, dtangent + n); else D->dt.clear();
+  P.data = D;
+  P.w.assign(n_targets, 0.0f);      // the default pose
+  pose_changed(P);
+  return PTC_OK;
+}
+
+int ptc_mesh_set_skin(ptc_ctx* c, int mesh, uint32_t n_joints, const uint16_t* joints_u16x4, const float* weights_f32x4) {
+  if (!c) return PTC_E_ARG;
+  if (mesh < 0 || mesh >= (int)c->meshes.size()) return fail(c, PTC_E_ARG, "mesh_set_skin: mesh out of range");
+  if (!joints_u16x4 || !weights_f32x4) return fail(c, PTC_E_ARG, "mesh_set_skin: null pointer");
+  if (n_joints < 1u || n_joints > 65536u) return fail(c, PTC_E_ARG, "mesh_set_skin: n_joints out of range");
+  if (c->committed) return fail(c, PTC_E_STATE, "mesh_set_skin: the scene is committed (a skin belongs to the description: ptc_scene_begin)");
+  const size_t nv = c->meshes[(size_t)mesh].v.size();
+  for (size_t i = 0; i < nv * 4; ++i) if (joints_u16x4[i] >= n_joints) return fail(c, PTC_E_ARG, "mesh_set_skin: joint index out of range");
+  MeshPose& P = *pose_make(c, mesh);
+  auto D = std::make_shared<DeformMesh>(*P.data);
+  D->n_joints = n_joints;
+  D->skin.resize(nv);
+  for (size_t v = 0; v < nv; ++v)
+    for (int k = 0; k < 4; ++k) { D->skin[v].j[k] = joints_u16x4[v * 4 + k]; D->skin[v].w[k] = weights_f32x4[v * 4 + k]; }
+  P.data = D;
+  P.J.assign((size_t)n_joints * 12, 0.0f);      // the default pose: identity matrices
+  for (uint32_t j = 0; j < n_joints; ++j) P.J[(size_t)j * 12 + 0] = P.J[(size_t)j * 12 + 4] = P.J[(size_t)j * 12 + 8] = 1.0f;
+  pose_changed(P);
+  return PTC_OK;
+}
+
+int ptc_update_mesh_pose(ptc_ctx* c, int mesh, const float* morph_weights, uint32_t n_weights, const float* joint_matrices, uint32_t n_joints) {
+  if (!c) return PTC_E_ARG;
+  if (mesh < 0 || mesh >= (int)c->meshes.size()) return fail(c, PTC_E_ARG, "update_mesh_pose: mesh out of range");
+  const MeshPose* Q = (size_t)mesh < c->poses.size() && c->poses[(size_t)mesh].active() ? &c->poses[(size_t)mesh] : nullptr;
+  const uint32_t T = Q ? Q->data->n_targets : 0u, nj = Q && !Q->data->skin.empty() ? Q->data->n_joints : 0u;
+  if (morph_weights && n_weights != T) return fail(c, PTC_E_ARG, "update_mesh_pose: the number of weights is not the mesh's number of morph targets");
+  if (joint_matrices && n_joints != nj) return fail(c, PTC_E_ARG, "update_mesh_pose: the number of matrices is not the mesh's number of joints");
+  if (!Q) return PTC_OK;
+  MeshPose& P = c->poses[(size_t)mesh];
+  if (morph_weights && T) P.w.assign(morph_weights, morph_weights + T);
+  if (joint_matrices && nj) P.J.assign(joint_matrices, joint_matrices + (size_t)nj * 12);
+  if ((morph_weights && T) || (joint_matrices && nj)) pose_changed(P);
+  return PTC_OK;
+}
+
+int ptc_update_mesh_vertices(ptc_ctx* c, int mesh, const ptc_vertex* verts, uint32_t n_verts) {
+  if (!c) return PTC_E_ARG;
+  if (mesh < 0 || mesh >= (int)c->meshes.size()) return fail(c, PTC_E_ARG, "update_mesh_vertices: mesh out of range");
+  if (!verts) return fail(c, PTC_E_ARG, "update_mesh_vertices: null pointer");
+  if (n_verts != c->meshes[(size_t)mesh].v.size()) return fail(c, PTC_E_ARG, "update_mesh_vertices: the number of vertices is not the mesh's");
+  MeshPose& P = *pose_make(c, mesh);
+  auto base = std::make_shared<std::vector<HostVertex>>(n_verts);
+  std::memcpy(base->data(), verts, (size_t)n_verts * sizeof(ptc_vertex));
+  P.base = base;
+  pose_changed(P);
+  return PTC_OK;
+}
+
+int ptc_debug_get_mesh_vertices(ptc_ctx* c, int mesh, ptc_vertex* out) {
+  if (!c) return PTC_E_ARG;
+  if (mesh < 0 || mesh >= (int)c->meshes.size() || !out) return fail(c, PTC_E_ARG, "debug_get_mesh_vertices: bad argument");
+  const size_t m = (size_t)mesh;
+  const size_t bytes = c->meshes[m].v.size() * sizeof(ptc_vertex);
+  c->debug_verts_from_device = false;
+  if (m < c->poses.size() && c->poses[m].active()) {
+    const MeshPose& P = c->poses[m];
+    const CommittedScene& s = c->scene;
+    if (c->device >= 0 && s.refit_ready && P.on_device && m < s.deform.size() && s.deform[m].n_verts) {      // evaluated in HBM: from there
+      HIP_TRY(c, hipSetDevice(c->device));
+      { int rs = sync_all_lanes(c); if (rs) return rs; }
+      HIP_TRY(c, hipMemcpy(out, s.deform[m].out, bytes, hipMemcpyDeviceToHost));
+      c->debug_verts_from_device = true;
+      return PTC_OK;
+    }
+    // not evaluated in HBM: the host's evaluation of the LIVE pose, into `out` alone — a pending pose is only recorded, and one that a refit refused never shows
+    const size_t want = pt_deform_pose_floats(P.data->n_targets, P.data->skin.empty() ? 0u : P.data->n_joints);
+    if (c->committed && P.base_live && P.base_live->size() == c->meshes[m].v.size() && P.pose_live.size() == want) {
+      pt_deform_eval_mesh(*P.data, P.base_live->data(), P.pose_live.data(), reinterpret_cast<HostVertex*>(out));
+      return PTC_OK;
+    }
+    deform_host_all(c);      // before the first commit there is no live pose: the pending one
+  }
+  std::memcpy(out, c->meshes[m].v.data(), bytes);
+  return PTC_OK;
+}
+
 int ptc_scene_refit(ptc_ctx* c) {
   if (!c) return PTC_E_ARG;
   if (!c->committed) return fail(c, PTC_E_STATE, "scene_refit: scene not committed");
@@ -1109,6 +1403,7 @@ int ptc_scene_refit(ptc_ctx* c) {
   if (!c->built->topology) return host_build_and_upload(c, t0, /*as_refit=*/true);      // the tree in HBM was built on the device (ptc_scene_rebuild): the host has no topology to refit
   HostBuilt& B = *c->built;
   const size_t n_recs = B.recs.size(), n_shade = B.shade.size(), n_lights = B.lights.size(), n_cdf = B.cdf.size();
+  deform_host_all(c);
   const std::string e = ptc_refit_scene(c->mats, c->meshes, c->insts, c->texs, c->env, B);
   if (!e.empty()) return fail(c, PTC_E_STATE, e);
   c->in_frame = false; c->pending = 0; drop_guides(c);
@@ -1118,6 +1413,7 @@ int ptc_scene_refit(ptc_ctx* c) {
     int rc = refit_upload(c, B.recs.size() == n_recs && B.shade.size() == n_shade && B.lights.size() == n_lights && B.cdf.size() == n_cdf, t0);
     if (rc) return rc;
   }
+  { int rc = deform_after_host_refit(c); if (rc) return rc; }
   c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return PTC_OK;
 }
@@ -1211,6 +1507,8 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload w
   release_scene(c);
   CommittedScene& s = c->scene;
   s.insts = c->insts.size();
+  deform_all_live(c);      // every caller lays the scene out from the fully evaluated description
+  for (MeshPose& P : c->poses) if (P.active()) P.dev_fresh = P.host_fresh;
   if (c->device < 0) {   // description-only context: nothing to upload
     c->committed = true;
     commit_stats(c, t0);
@@ -1310,6 +1608,7 @@ int scene_commit(ptc_ctx* c, bool device_ok) {
     { int rs = sync_all_lanes(c); if (rs) return rs; }
   }
   const auto t0 = std::chrono::steady_clock::now();
+  deform_host_all(c);      // a commit of a posed description is the commit of plain meshes that hold the posed vertices
   // north_star's tree builds on the device, and so does the SAH tree with the SAH device builder: PTC_COMMIT=host keeps the host's build (the cross-check path)
   if (device_ok && c->device >= 0 && (c->bvh_builder == PTC_BVH_LBVH || c->device_builder == PTC_BVH_SAH)) {
     const char* how = std::getenv("PTC_COMMIT");
@@ -2099,7 +2398,7 @@ int ptc_group_scene_refit(ptc_group* g) {
     for (size_t i = 0; i < g->ctx.size() && !host_way; ++i) {
       ptc_ctx* c = g->ctx[i];
       if (hipSetDevice(c->device) != hipSuccess) { g->err = "ptc_group_scene_refit: hipSetDevice failed"; return PTC_E_DEVICE; }
-      if (i) c->insts = c0->insts;
+      if (i) { c->insts = c0->insts; deform_take(c, c0, /*with_verts=*/false); }
       c->built = mine;
       const int rc = device_refit(c, t0);
       if (rc > 0) { host_way = true; break; }      // decided from the description alone, before any kernel ran: all devices take the host path together
@@ -2113,16 +2412,18 @@ int ptc_group_scene_refit(ptc_group* g) {
   }
   auto built = std::make_shared<HostBuilt>(*c0->built);                 // the devices keep rendering from the old arrays until theirs are overwritten
   const size_t n_recs = built->recs.size(), n_shade = built->shade.size(), n_lights = built->lights.size(), n_cdf = built->cdf.size();
+  deform_host_all(c0);
   const std::string e = ptc_refit_scene(c0->mats, c0->meshes, c0->insts, c0->texs, c0->env, *built);
   if (!e.empty()) { g->err = e; return PTC_E_STATE; }
   const bool same = built->recs.size() == n_recs && built->shade.size() == n_shade && built->lights.size() == n_lights && built->cdf.size() == n_cdf;
   for (size_t i = 0; i < g->ctx.size(); ++i) {
     ptc_ctx* c = g->ctx[i];
     if (c->device >= 0 && hipSetDevice(c->device) != hipSuccess) { g->err = "ptc_group_scene_refit: hipSetDevice failed"; return PTC_E_DEVICE; }
-    if (i) c->insts = c0->insts;
+    if (i) { c->insts = c0->insts; deform_take(c, c0, /*with_verts=*/true); }
     c->built = built;
     c->in_frame = false; c->pending = 0; drop_guides(c);
-    const int rc = c->device >= 0 ? refit_upload(c, same, t0) : PTC_OK;
+    int rc = c->device >= 0 ? refit_upload(c, same, t0) : PTC_OK;
+    if (!rc) rc = deform_after_host_refit(c);
     if (rc) { g->err = "device " + std::to_string(i) + ": " + ptc_last_error(c); return rc; }
     c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
@@ -2286,7 +2587,7 @@ int ptc_debug_get_internals(ptc_ctx* c, uint64_t out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0;
   out[0] = c->events_created; out[1] = c->spans.size(); out[2] = c->lanes.empty() ? 0 : c->lanes[0].q.cap; out[3] = c->per_batch; out[4] = c->pending;
   out[5] = (uint64_t)c->cfg.trace_blocks_per_cu; out[6] = (uint64_t)c->cfg.stack_lds;
-  out[7] = (c->scene.last_refit_on_device ? 1u : 0u) | (c->scene.commit_on_device ? 2u : 0u) | (c->scene.tree_device_sah ? 4u : 0u);
+  out[7] = (c->scene.last_refit_on_device ? 1u : 0u) | (c->scene.commit_on_device ? 2u : 0u) | (c->scene.tree_device_sah ? 4u : 0u) | (c->debug_verts_from_device ? 8u : 0u);
   return PTC_OK;
 }
 

@@ -1,5 +1,6 @@
 // ptc_gltf.cpp — C-ABI wrapper of gltf_loader.hpp (include/ptc_gltf.h).
 #include "gltf_loader.hpp"
+#include "gltf_anim.hpp"
 #include "image_io.hpp"
 
 #include <ptc_gltf.h>
@@ -20,6 +21,36 @@ extern "C" long long ptc_gltf_load(ptc_ctx* ctx, const char* path, int scene_ind
     say(std::string("ptc_gltf_load: ") + e.what());
     return PTC_E_ARG;
   }
+}
+
+// ---- the asset as a handle: skins, morph targets, animations (host/gltf_anim.hpp) ----
+struct ptc_gltf_asset { pbr::gltf::Asset asset; std::string err; explicit ptc_gltf_asset(const char* path) : asset(path) {} };
+
+extern "C" ptc_gltf_asset* ptc_gltf_open(const char* path, char* err, int err_len) {
+  auto say = [&](const std::string& m) { if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str()); };
+  if (!path) { say("ptc_gltf_open: null argument"); return nullptr; }
+  try { return new ptc_gltf_asset(path); }
+  catch (std::exception const& e) { say(std::string("ptc_gltf_open: ") + e.what()); return nullptr; }
+}
+extern "C" void ptc_gltf_close(ptc_gltf_asset* a) { delete a; }
+extern "C" const char* ptc_gltf_asset_last_error(const ptc_gltf_asset* a) { return a ? a->err.c_str() : "null asset"; }
+extern "C" long long ptc_gltf_asset_load(ptc_gltf_asset* a, ptc_ctx* ctx, int scene_index, int compose_parents, float bbox6[6]) {
+  if (!a || !ctx) return PTC_E_ARG;
+  try {
+    const long long n = a->asset.load_into(ctx, scene_index, compose_parents != 0, bbox6);
+    if (n < 0) a->err = std::string("ptc_gltf_asset_load: ") + ptc_last_error(ctx);
+    return n;
+  } catch (std::exception const& e) { a->err = std::string("ptc_gltf_asset_load: ") + e.what(); return PTC_E_ARG; }
+}
+extern "C" int ptc_gltf_asset_animations(const ptc_gltf_asset* a) { return a ? a->asset.animations() : PTC_E_ARG; }
+extern "C" double ptc_gltf_asset_duration(const ptc_gltf_asset* a, int animation) { return a ? a->asset.duration(animation) : -1.0; }
+extern "C" int ptc_gltf_asset_pose(ptc_gltf_asset* a, ptc_ctx* ctx, int animation, double time_seconds) {
+  if (!a || !ctx) return PTC_E_ARG;
+  try {
+    const int rc = a->asset.pose(ctx, animation, time_seconds);
+    if (rc < 0) a->err = rc == PTC_E_ARG && (animation < 0 || animation >= a->asset.animations()) ? "ptc_gltf_asset_pose: animation out of range" : std::string("ptc_gltf_asset_pose: ") + ptc_last_error(ctx);
+    return rc;
+  } catch (std::exception const& e) { a->err = std::string("ptc_gltf_asset_pose: ") + e.what(); return PTC_E_ARG; }
 }
 
 namespace {

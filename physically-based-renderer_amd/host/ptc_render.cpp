@@ -1,5 +1,5 @@
 // ptc_render — dependency-free C++17 offline renderer over the C-ABI (include/ptc.h).
-//   ptc_render (--scene cornell|sphere | --gltf file.glb [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
+//   ptc_render (--scene cornell|sphere | --gltf file.glb [--animation N --time T] [--cam-pos x y z --cam-target x y z --fov deg | --viewer-camera]) --width W --height H
 //              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
@@ -18,8 +18,10 @@
 // --env: ordinary lat-long RGB environment map (PFM or Radiance .hdr, top row = up).  The reference's world is y-down (up = -y, CameraData.hpp:28) and
 // ptc_set_env_latlong_rgb32f takes row 0 = +y, so the rows are flipped on the way in.  --sky: a built-in gradient sky with a sun, for
 // assets that carry no emitters.
+// --animation N --time T: the glTF scene is loaded with its skins and morph targets (host/gltf_anim.hpp) and posed at T seconds of its animation N before the commit.
 // Without --cam-* a glTF scene is framed from its bounding box (the reference ignores glTF cameras and injects its own).
 // The scenes are the procedural stand-ins of BASELINE configs 1 and 2 (the reference's assets are stripped).
+#include "gltf_anim.hpp"
 #include "gltf_loader.hpp"
 #include "image_io.hpp"
 #include "pbr_pt.hpp"
@@ -131,6 +133,8 @@ int main(int argc, char** argv) {
   bool adaptive = false;
   ptc_adaptive_params ap = pbr::PathTraceRenderSystem::adaptiveDefaults();
   std::string countsPath;
+  int animation = -1;                        // --animation: pose the glTF scene along this animation ...
+  double animTime = 0.0;                     // ... at --time seconds, before the commit
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -139,6 +143,7 @@ int main(int argc, char** argv) {
     else if (a == "--bounces") bounces = std::atoi(next()); else if (a == "--device") device = std::atoi(next());
     else if (a == "--gpus") gpus = std::atoi(next()); else if (a == "--half") halfPath = next(); else if (a == "--raster16") integrator = PTC_INTEGRATOR_RASTER_GBUFFER16;
     else if (a == "--gltf") gltf = next();
+    else if (a == "--animation") animation = std::atoi(next()); else if (a == "--time") animTime = std::atof(next());
     else if (a == "--denoise") denoise = true; else if (a == "--denoise-iters") { denoiseIters = std::atoi(next()); denoise = true; } else if (a == "--guides") guidesPrefix = next();
     else if (a == "--denoise-sampled") { denoiseSampled = true; denoise = true; }
     else if (a == "--adaptive") { ap.threshold = (float)std::atof(next()); adaptive = true; } else if (a == "--min-spp") ap.min_samples = std::atoi(next());
@@ -164,13 +169,24 @@ int main(int argc, char** argv) {
     if (adaptive && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--adaptive renders on one context with the path integrator (not with --gpus / --raster)");
     if (denoiseSampled && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--denoise-sampled renders on one context with the path integrator (not with --gpus / --raster)");
     if (!adaptive && !countsPath.empty()) throw std::runtime_error("--counts needs --adaptive");
+    if (gltf.empty() && animation >= 0) throw std::runtime_error("--animation poses a --gltf scene");
     if (gltf.empty() && (!envPath.empty() || sky)) throw std::runtime_error("--env / --sky light a --gltf scene; the built-in scenes carry their own lights");
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
     if (deviceBvh >= 0) rs.setDeviceBuilder(deviceBvh);
     if (!gltf.empty()) {
-      const pbr::gltf::FlatScene fs = pbr::gltf::load(gltf);
-      rs.beginScene();
-      if (pbr::gltf::upload(rs.handle(), fs) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+      pbr::gltf::FlatScene fs;
+      if (animation >= 0) {      // the asset as a handle: targets, skins, and the pose of the animation at --time; the box that frames it is the bind pose's
+        pbr::gltf::Asset asset(gltf);
+        if (animation >= asset.animations()) throw std::runtime_error("--animation: the asset has " + std::to_string(asset.animations()) + " animation(s)");
+        rs.beginScene();
+        float box[6];
+        if (asset.load_into(rs.handle(), -1, true, box) < 0 || asset.pose(rs.handle(), animation, animTime) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+        for (int k = 0; k < 3; ++k) { fs.bbox_lo[k] = box[k]; fs.bbox_hi[k] = box[3 + k]; }
+      } else {
+        fs = pbr::gltf::load(gltf);
+        rs.beginScene();
+        if (pbr::gltf::upload(rs.handle(), fs) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+      }
       if (ptc_set_texture_filter(rs.handle(), filter) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
       if (bvh >= 0) rs.setBvhBuilder(bvh);
       if (!haveCam) {   // frame the bounding box from +z

@@ -32,8 +32,81 @@ def _load():
         L = C.CDLL(_LIB)
         L.ptc_gltf_load.restype = C.c_longlong
         L.ptc_gltf_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_char_p, C.c_int]
+        L.ptc_gltf_open.restype = C.c_void_p
+        L.ptc_gltf_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+        L.ptc_gltf_close.restype = None
+        L.ptc_gltf_close.argtypes = [C.c_void_p]
+        L.ptc_gltf_asset_load.restype = C.c_longlong
+        L.ptc_gltf_asset_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.ptc_gltf_asset_animations.argtypes = [C.c_void_p]
+        L.ptc_gltf_asset_duration.restype = C.c_double
+        L.ptc_gltf_asset_duration.argtypes = [C.c_void_p, C.c_int]
+        L.ptc_gltf_asset_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double]
+        L.ptc_gltf_asset_last_error.restype = C.c_char_p
+        L.ptc_gltf_asset_last_error.argtypes = [C.c_void_p]
         _lib = L
     return _lib
+
+
+class Asset:
+    """A glTF file kept open (ptc_gltf_open): load it into a PathTracer with its skins and morph targets, then pose it along its animations.
+
+        a = Asset(path); a.load_into(pt, camera); a.pose(pt, 0, 0.4); pt.scene_refit()"""
+
+    def __init__(self, path: str):
+        self._L = _load()
+        err = C.create_string_buffer(512)
+        self._a = self._L.ptc_gltf_open(os.fsencode(path), err, 512)
+        if not self._a:
+            raise _ptc.PtcError(err.value.decode() or "ptc_gltf_open failed")
+
+    def close(self):
+        if getattr(self, "_a", None):
+            self._L.ptc_gltf_close(self._a)
+            self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc < 0:
+            raise _ptc.PtcError(self._L.ptc_gltf_asset_last_error(self._a).decode() or f"glTF asset call failed ({rc})")
+        return rc
+
+    @property
+    def n_animations(self) -> int:
+        return int(self._L.ptc_gltf_asset_animations(self._a))
+
+    def duration(self, animation: int) -> float:
+        return float(self._L.ptc_gltf_asset_duration(self._a, int(animation)))
+
+    def load_into(self, pt, camera=None, scene_index: int = -1, compose_parents: bool = True, animation=None, time: float = 0.0):
+        """scene_begin -> the file's scene with targets and skins -> (the pose of `animation` at `time`) -> camera -> scene_commit.
+        Returns (n_triangles, bbox_lo, bbox_hi) of the bind pose."""
+        h = pt._h
+        pt._ck(pt._L.ptc_scene_begin(h))
+        bbox = (C.c_float * 6)()
+        n = self._ck(self._L.ptc_gltf_asset_load(self._a, h, scene_index, 1 if compose_parents else 0, bbox))
+        if animation is not None:
+            self._ck(self._L.ptc_gltf_asset_pose(self._a, h, int(animation), float(time)))
+        lo, hi = np.array(bbox[0:3], np.float32), np.array(bbox[3:6], np.float32)
+        if camera is None:
+            c = 0.5 * (lo + hi)
+            r = 0.5 * float(np.linalg.norm(hi - lo))
+            fov = np.radians(60.0)
+            pt.set_camera((c[0], c[1], c[2] + r / np.tan(0.5 * fov) + r), c, float(fov), 1.0)
+        else:
+            pt.set_camera(camera.position, camera.target, camera.fov_y, camera.aspect)
+        pt._ck(pt._L.ptc_scene_commit(h))
+        return int(n), lo, hi
+
+    def pose(self, pt, animation: int, time: float):
+        """ptc_gltf_asset_pose: instance matrices and mesh poses of `animation` at `time` (clamped); the caller refits or rebuilds."""
+        self._ck(self._L.ptc_gltf_asset_pose(self._a, pt._h, int(animation), float(time)))
+        return self
 
 
 def load_into(pt, path: str, camera=None, scene_index: int = -1, compose_parents: bool = True, env=None):
@@ -239,11 +312,16 @@ def _pad4(b: bytes, fill: bytes = b"\x00") -> bytes:
     return b + fill * ((4 - len(b) % 4) % 4)
 
 
-def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = False, nodes=None) -> None:
+def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = False, nodes=None, skins=None, animations=None,
+              joints_type: str = "u16", weights_type: str = "f32") -> None:
     """SceneDesc → GLB.  One glTF mesh per MeshDesc (one primitive each), one node per instance (TRS, or `matrix`
     when the instance carries one).  `nodes`: optional explicit node list (dicts with mesh/translation/rotation/
     scale/matrix/children) + root list, to exercise hierarchies: nodes=(node_dicts, root_indices).
-    index_type: "u16" | "u32" | "auto" (u16 when the mesh has < 65536 vertices, like the reference's indices)."""
+    index_type: "u16" | "u32" | "auto" (u16 when the mesh has < 65536 vertices, like the reference's indices).
+    Deformation: a MeshDesc with morph_dpos (/ morph_dnormal / morph_dtangent, morph_weights) gets `targets` (and `weights`), one with joints / weights gets
+    JOINTS_0 (joints_type "u8" | "u16") and WEIGHTS_0 (weights_type "f32", or normalised "u8" | "u16").  skins: [{"joints": [node, ...],
+    "inverseBindMatrices": (n, 16) column-major or None}] (a node dict names its skin with "skin").  animations: [{"channels": [{"node", "path"
+    ("translation" | "rotation" (x, y, z, w) | "scale" | "weights"), "times", "values", "interpolation" ("LINEAR" | "STEP" | "CUBICSPLINE")}]}]."""
     blob = bytearray()
     views, accessors, meshes = [], [], []
 
@@ -286,7 +364,32 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
         use16 = index_type == "u16" or (index_type == "auto" and n < 65536)
         ib = idx.astype("<u2").tobytes() if use16 else idx.astype("<u4").tobytes()
         ia = add_acc(add_view(ib, target=34963), 5123 if use16 else 5125, idx.size, "SCALAR")
-        meshes.append({"primitives": [{"attributes": attrs, "indices": ia, "material": int(m.material), "mode": 4}]})
+        prim = {"attributes": attrs, "indices": ia, "material": int(m.material), "mode": 4}
+        gm = {"primitives": [prim]}
+        if getattr(m, "joints", None) is not None:
+            j = np.ascontiguousarray(m.joints, "<u1" if joints_type == "u8" else "<u2")
+            attrs["JOINTS_0"] = add_acc(add_view(j.tobytes(), target=34962), 5121 if joints_type == "u8" else 5123, n, "VEC4")
+            w = np.asarray(m.weights, np.float32)
+            if weights_type == "f32":
+                attrs["WEIGHTS_0"] = add_acc(add_view(np.ascontiguousarray(w, "<f4").tobytes(), target=34962), 5126, n, "VEC4")
+            else:
+                top, dt, ct = (255, "<u1", 5121) if weights_type == "u8" else (65535, "<u2", 5123)
+                attrs["WEIGHTS_0"] = add_acc(add_view(np.ascontiguousarray(np.rint(w * top), dt).tobytes(), target=34962), ct, n, "VEC4")
+                accessors[attrs["WEIGHTS_0"]]["normalized"] = True
+        if getattr(m, "morph_dpos", None) is not None:
+            targets = []
+            for k in range(len(m.morph_dpos)):
+                t = {"POSITION": add_acc(add_view(np.ascontiguousarray(m.morph_dpos[k], "<f4").tobytes(), target=34962), 5126, n, "VEC3", 0,
+                                         (np.asarray(m.morph_dpos[k]).min(0), np.asarray(m.morph_dpos[k]).max(0)))}
+                if getattr(m, "morph_dnormal", None) is not None:
+                    t["NORMAL"] = add_acc(add_view(np.ascontiguousarray(m.morph_dnormal[k], "<f4").tobytes(), target=34962), 5126, n, "VEC3")
+                if getattr(m, "morph_dtangent", None) is not None:
+                    t["TANGENT"] = add_acc(add_view(np.ascontiguousarray(m.morph_dtangent[k], "<f4").tobytes(), target=34962), 5126, n, "VEC3")
+                targets.append(t)
+            prim["targets"] = targets
+            if getattr(m, "morph_weights", None) is not None:
+                gm["weights"] = [float(x) for x in m.morph_weights]
+        meshes.append(gm)
 
     images = []
     for t in getattr(desc, "textures", []) or []:   # RGBA8 images embedded as PNG bufferViews, one glTF texture per image
@@ -324,6 +427,28 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
         node_list, roots = nodes
     doc = {"asset": {"version": "2.0", "generator": "pbr_amd.gltf.write_glb"}, "scene": 0, "scenes": [{"nodes": list(roots)}], "nodes": node_list,
            "meshes": meshes, "materials": mats, "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(blob)}]}
+    if skins:
+        doc["skins"] = []
+        for sk in skins:
+            g = {"joints": [int(j) for j in sk["joints"]]}
+            if sk.get("inverseBindMatrices") is not None:
+                ibm = np.ascontiguousarray(sk["inverseBindMatrices"], "<f4").reshape(-1, 16)
+                g["inverseBindMatrices"] = add_acc(add_view(ibm.tobytes()), 5126, ibm.shape[0], "MAT4")
+            doc["skins"].append(g)
+    if animations:
+        doc["animations"] = []
+        for an in animations:
+            samplers, channels = [], []
+            for ch in an["channels"]:
+                times = np.ascontiguousarray(ch["times"], "<f4").reshape(-1)
+                vals = np.ascontiguousarray(ch["values"], "<f4")
+                typ = {"translation": "VEC3", "scale": "VEC3", "rotation": "VEC4", "weights": "SCALAR"}[ch["path"]]
+                per = {"VEC3": 3, "VEC4": 4, "SCALAR": 1}[typ]
+                samplers.append({"input": add_acc(add_view(times.tobytes()), 5126, times.size, "SCALAR", 0, ([times.min()], [times.max()])),
+                                 "output": add_acc(add_view(vals.tobytes()), 5126, vals.size // per, typ), "interpolation": ch.get("interpolation", "LINEAR")})
+                channels.append({"sampler": len(samplers) - 1, "target": {"node": int(ch["node"]), "path": ch["path"]}})
+            doc["animations"].append({"samplers": samplers, "channels": channels})
+    doc["buffers"] = [{"byteLength": len(blob)}]
     if images:
         doc["images"] = images
         doc["samplers"] = [{"magFilter": 9728, "minFilter": 9728, "wrapS": 10497, "wrapT": 10497}]   # NEAREST, REPEAT (what the reference uses regardless)

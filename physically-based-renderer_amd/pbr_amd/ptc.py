@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "ptc_adaptive_default_params", "ptc_frame_set_adaptive", "ptc_frame_adapt", "ptc_read_sample_counts", "ptc_render_adaptive", "ptc_get_adaptive_stats",
     "ptc_set_sample_covariance", "ptc_read_sample_covariance", "ptc_denoise_sampled", "ptc_read_sampled_variance",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
+    "ptc_mesh_set_morph_targets", "ptc_mesh_set_skin", "ptc_update_mesh_pose", "ptc_update_mesh_vertices", "ptc_debug_get_mesh_vertices",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
 
@@ -137,6 +138,11 @@ def load_library():
     L.ptc_update_instance.argtypes = [vp, C.c_int, fp, fp, fp]
     L.ptc_update_instance_matrix.argtypes = [vp, C.c_int, fp]
     L.ptc_scene_refit.argtypes = [vp]
+    L.ptc_mesh_set_morph_targets.argtypes = [vp, C.c_int, C.c_uint32, fp, fp, fp]
+    L.ptc_mesh_set_skin.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(C.c_uint16), fp]
+    L.ptc_update_mesh_pose.argtypes = [vp, C.c_int, fp, C.c_uint32, fp, C.c_uint32]
+    L.ptc_update_mesh_vertices.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.ptc_debug_get_mesh_vertices.argtypes = [vp, C.c_int, vp]
     L.ptc_scene_rebuild.argtypes = [vp]
     L.ptc_set_camera.argtypes = [vp, fp, fp, C.c_float, C.c_float]
     L.ptc_set_env_latlong_rgb32f.argtypes = [vp, fp, C.c_int, C.c_int]
@@ -286,7 +292,13 @@ class PathTracer:
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
-            self._ck(L.ptc_add_mesh(h, v.ctypes.data, v.size, i.ctypes.data_as(C.POINTER(C.c_uint32)), i.size, me.material))
+            mid = self._ck(L.ptc_add_mesh(h, v.ctypes.data, v.size, i.ctypes.data_as(C.POINTER(C.c_uint32)), i.size, me.material))
+            if getattr(me, "morph_dpos", None) is not None:
+                self.mesh_set_morph_targets(mid, me.morph_dpos, getattr(me, "morph_dnormal", None), getattr(me, "morph_dtangent", None))
+            if getattr(me, "joints", None) is not None:
+                self.mesh_set_skin(mid, me.n_joints, me.joints, me.weights)
+            if getattr(me, "morph_weights", None) is not None or getattr(me, "joint_matrices", None) is not None:
+                self.update_mesh_pose(mid, getattr(me, "morph_weights", None), getattr(me, "joint_matrices", None))
         for it in desc.instances:
             if getattr(it, "matrix", None) is not None:
                 self._ck(L.ptc_add_instance_matrix(h, it.mesh, _f(np.asarray(it.matrix, np.float32).reshape(16))[1]))
@@ -311,6 +323,60 @@ class PathTracer:
     def scene_refit(self):
         self._ck(self._L.ptc_scene_refit(self._h))
         return self
+
+    # ---- deforming meshes ----------------------------------------------------------------
+    def mesh_set_morph_targets(self, mesh, dpos, dnormal=None, dtangent=None):
+        """ptc_mesh_set_morph_targets, before the commit: dpos (and dnormal, dtangent, which may be None) are (n_targets, n_verts, 3) float32."""
+        dp = np.ascontiguousarray(dpos, np.float32)
+        assert dp.ndim == 3 and dp.shape[2] == 3, "morph deltas are (n_targets, n_verts, 3)"
+        keep = [dp]
+        ptrs = [dp.ctypes.data_as(C.POINTER(C.c_float))]
+        for a in (dnormal, dtangent):
+            if a is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float32)
+            assert a.shape == dp.shape, "every delta array has the shape of dpos"
+            keep.append(a)
+            ptrs.append(a.ctypes.data_as(C.POINTER(C.c_float)))
+        self._ck(self._L.ptc_mesh_set_morph_targets(self._h, int(mesh), dp.shape[0], *ptrs))
+        return self
+
+    def mesh_set_skin(self, mesh, n_joints, joints, weights):
+        """ptc_mesh_set_skin, before the commit: joints (n_verts, 4) uint16, weights (n_verts, 4) float32."""
+        j = np.ascontiguousarray(joints, np.uint16)
+        w = np.ascontiguousarray(weights, np.float32)
+        assert j.ndim == 2 and j.shape[1] == 4 and w.shape == j.shape, "joints and weights are (n_verts, 4)"
+        self._ck(self._L.ptc_mesh_set_skin(self._h, int(mesh), int(n_joints), j.ctypes.data_as(C.POINTER(C.c_uint16)), w.ctypes.data_as(C.POINTER(C.c_float))))
+        return self
+
+    def update_mesh_pose(self, mesh, morph_weights=None, joint_matrices=None):
+        """ptc_update_mesh_pose: morph_weights (n_targets,) and / or joint_matrices (n_joints, 12) — rows 0..2 of a column-major 4x4, column by column; None
+        leaves that half of the pose as it is.  scene_refit() / scene_rebuild() / a commit apply it."""
+        wp = jp = None
+        nw = nj = 0
+        if morph_weights is not None:
+            w = np.ascontiguousarray(morph_weights, np.float32).reshape(-1)
+            wp, nw = w.ctypes.data_as(C.POINTER(C.c_float)), w.size
+        if joint_matrices is not None:
+            jm = np.ascontiguousarray(joint_matrices, np.float32)
+            assert jm.size % 12 == 0, "joint matrices are 12 floats each"
+            jp, nj = jm.ctypes.data_as(C.POINTER(C.c_float)), jm.size // 12
+        self._ck(self._L.ptc_update_mesh_pose(self._h, int(mesh), wp, nw, jp, nj))
+        return self
+
+    def update_mesh_vertices(self, mesh, vertices):
+        """ptc_update_mesh_vertices: new BASE vertices (MESH_VERTEX, the mesh's count) for a caller who deforms on their own."""
+        v = np.ascontiguousarray(vertices)
+        assert v.dtype.itemsize == 48, "vertices are MESH_VERTEX records"
+        self._ck(self._L.ptc_update_mesh_vertices(self._h, int(mesh), v.ctypes.data, v.size))
+        return self
+
+    def mesh_vertices(self, mesh, n_verts):
+        """ptc_debug_get_mesh_vertices: the current posed object-space vertices of a mesh as (n_verts, 12) float32."""
+        out = np.zeros((int(n_verts), 12), np.float32)
+        self._ck(self._L.ptc_debug_get_mesh_vertices(self._h, int(mesh), out.ctypes.data))
+        return out
 
     def host_build_id(self):
         return int(self._L.ptc_debug_host_build_id(self._h))
@@ -632,6 +698,7 @@ class PathTracer:
         d = {k: int(buf[i]) for i, k in enumerate(keys)}
         d["commit_on_device"] = (d["refit_on_device"] >> 1) & 1
         d["device_build_sah"] = (d["refit_on_device"] >> 2) & 1
+        d["mesh_vertices_from_device"] = (d["refit_on_device"] >> 3) & 1
         d["refit_on_device"] &= 1
         return d
 

@@ -175,6 +175,15 @@ class MeshDesc:
     vertices: np.ndarray  # MESH_VERTEX[n]
     indices: np.ndarray  # uint32[3k], mesh-local
     material: int
+    # deformation (the arguments of ptc_mesh_set_morph_targets / ptc_mesh_set_skin / ptc_update_mesh_pose).  None: the mesh has none.
+    morph_dpos: Optional[np.ndarray] = None      # float32 (n_targets, n, 3), target-major
+    morph_dnormal: Optional[np.ndarray] = None   # the same shape, or None = zeros
+    morph_dtangent: Optional[np.ndarray] = None
+    n_joints: int = 0
+    joints: Optional[np.ndarray] = None          # uint16 (n, 4)
+    weights: Optional[np.ndarray] = None         # float32 (n, 4), used as given
+    morph_weights: Optional[np.ndarray] = None   # the pose the scene is committed in: float32 (n_targets,); None = zeros
+    joint_matrices: Optional[np.ndarray] = None  # float32 (n_joints, 12): rows 0..2 of a column-major 4x4, column by column; None = identities
 
 
 @dataclasses.dataclass
