@@ -45,28 +45,15 @@ def test_hit_records_golden(ora, pbr):
     assert np.array_equal(t.view(np.uint32), g["t"].view(np.uint32)) and np.array_equal(prim, g["prim"])
     assert np.array_equal(uv.view(np.uint32), g["uv"].view(np.uint32))
     assert np.array_equal(o.trace_any(org, dirs, tmax), g["occ"])
-    # brute force over all triangles agrees with the BVH answer (closest t, lowest prim id on ties)
+    # all 4096 golden records against the float64 search of all triangles (tests/trace_reference.py): primitive, t, u, v and occlusion
+    import trace_reference as tr
+
     verts, idx, _ = o.flat_scene()
-    P = verts[:, :3].astype(np.float64)
-    a, b, c = P[idx[:, 0]], P[idx[:, 1]], P[idx[:, 2]]
-    for k in range(0, 4096, 97):
-        oo, dd = org[k].astype(np.float64), dirs[k].astype(np.float64)
-        e1, e2 = b - a, c - a
-        pv = np.cross(dd, e2)
-        det = (e1 * pv).sum(1)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = 1.0 / det
-            tv = oo - a
-            u = (tv * pv).sum(1) * inv
-            qv = np.cross(tv, e1)
-            v = (qv * dd).sum(1) * inv
-            tt = (e2 * qv).sum(1) * inv
-        ok = (det != 0) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (tt > 0)
-        if not ok.any():
-            assert prim[k] == -1
-        else:
-            tmin = tt[ok].min()
-            assert prim[k] >= 0 and abs(t[k] - tmin) <= 1e-4 * max(1.0, tmin)
+    rays = (org, dirs, tmax, np.full(len(org), tr.MISS))               # none of them is aimed at a triangle
+    truth = tr.any_all(verts, idx, org, dirs, tmax)
+    e32 = tr.e32_of(verts, idx, org, dirs, truth)
+    assert e32[2] > 1000
+    tr.assert_true("golden sphere10k", verts, idx, rays, truth, e32[:2], g["t"], g["prim"], g["uv"], g["occ"])
 
 
 def test_hit_records_do_not_depend_on_the_builder(ora, pbr):
