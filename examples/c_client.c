@@ -41,6 +41,9 @@ int main(int argc, char** argv) {
   CHECK(ptc_add_instance(ctx, mesh_light, t1, q1, s1));
   const float eye[3] = {0, -0.5f, 0}, target[3] = {0, 0, -3};
   CHECK(ptc_set_camera(ctx, eye, target, 1.0f, 1.0f));
+  ptc_lens_params lens;                                /* the thin lens: the defaults are the pinhole, aperture_radius > 0 gives depth of field */
+  ptc_lens_default_params(&lens);
+  CHECK(ptc_set_camera_lens(ctx, &lens));
   CHECK(ptc_scene_commit(ctx));
   ptc_stats st;
   CHECK(ptc_get_stats(ctx, &st));

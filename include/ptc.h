@@ -224,6 +224,36 @@ int ptc_update_mesh_vertices(ptc_ctx*, int mesh, const ptc_vertex* verts, uint32
 int ptc_set_camera(ptc_ctx*, const float pos[3], const float target[3], float fov_y,
                    float aspect);
 
+/* ---- thin-lens camera: depth of field with a circular or a bladed aperture (no counterpart in the reference, whose camera is a pinhole) ----
+ * The lens belongs to the camera and lives in ray generation alone.  With aperture_radius R > 0 every sample of the path integrator starts at a point l of
+ * the aperture — a disk of radius R, or a regular polygon of `blades` sides with circumradius R and a vertex at `rotation` turns, in the camera's (right, up)
+ * plane through its position — and goes through the point that the pinhole ray of the same jittered pixel position meets at view depth focus_distance F
+ * (measured along the forward axis): surfaces at depth F are sharp, a point at depth z spreads over a disk of radius R |1 - z / F| on its own depth plane.
+ * Throughput 1, no cos^4 term and no vignetting, as for the pinhole.  The lens point is drawn from dimensions 2 and 3 of the path's RNG index 0, which
+ * nothing else uses; DESIGN.md 2a and csrc/pt_lens.h have the arithmetic (IEEE binary32 in the order written, as every value of the renderer).
+ * R = 0 (the default) is the pinhole: ray generation then runs as it always did, and a context that never calls these computes what it always did.
+ *
+ * ptc_set_camera_lens: params == NULL means the defaults (0, 1, 0, 0).  Needs no device.  PTC_E_ARG, and nothing changed, for a negative or non-finite
+ *   aperture_radius, a focus_distance that is not finite and > 0, blades other than 0 or 3..16, a rotation outside [0, 1) or non-finite.  The lens has the
+ *   lifetime of the camera: kept across ptc_set_camera, reset to the defaults by ptc_scene_begin, copied by ptc_group_scene_commit wherever the camera is; a
+ *   change during a frame applies to the batches queued afterwards, as a ptc_set_camera does.
+ * What ignores the lens: the raster integrators; ptc_frame_guides, the temporal reprojection and the denoisers, which keep the ray through the lens centre —
+ *   the pinhole ray — so setting the lens does not invalidate guides.  Known limit: the guides of an out-of-focus region are sharp, so the edge-stopping
+ *   filters smooth less there than the blur of the radiance would allow; lens-averaged guides are not provided.
+ * ptc_focus_distance_at_pixel: the view depth of what the pixel centre of (px, py) sees, for focusing on it: *out = Z / sqrt(fma(dvy, dvy, fma(dvx, dvx, 1)))
+ *   with Z the depth guide of the pixel and dvx, dvy the view-space slopes of its centre ray; 0 on a miss.  Needs valid guides of the current frame
+ *   (PTC_E_STATE otherwise) and a pixel inside it (PTC_E_ARG otherwise).  One 16-byte read-back: the call waits for the device. */
+typedef struct ptc_lens_params {
+  float aperture_radius;  /* R >= 0, world units; 0 = pinhole (default 0)                               */
+  float focus_distance;   /* F > 0, view depth of the plane of focus along the forward axis (default 1) */
+  int   blades;           /* 0 = disk, 3..16 = regular polygon with circumradius R (default 0)          */
+  float rotation;         /* of the polygon, in turns, [0, 1) (default 0)                               */
+} ptc_lens_params;
+void ptc_lens_default_params(ptc_lens_params*);
+int  ptc_set_camera_lens(ptc_ctx*, const ptc_lens_params*);    /* NULL: the defaults */
+int  ptc_get_camera_lens(const ptc_ctx*, ptc_lens_params*);
+int  ptc_focus_distance_at_pixel(ptc_ctx*, int px, int py, float* out);
+
 /* Lat-long environment light (BASELINE config 5; no counterpart in the reference, which has no lights): w*h RGB
  * fp32 texels, row 0 = +y, u = atan2(d.z, d.x)/(2 pi) + 1/2, piecewise-constant radiance, importance-sampled by
  * luminance x sin(theta).  rgb == NULL removes it.  Call before ptc_scene_commit. */
@@ -521,6 +551,16 @@ int ptc_debug_trace_closest(ptc_ctx*, const float* origins, const float* dirs, u
 /* Any-hit of n explicit rays with tmax each; out_occluded n uint8. */
 int ptc_debug_trace_any(ptc_ctx*, const float* origins, const float* dirs, const float* tmax,
                         uint32_t n, uint8_t* out_occluded);
+/* The aperture point (lx, ly) that the lens selects for the pair (u1, u2) in [0,1)^2: a pure host evaluation of csrc/pt_lens.h, no context.
+ * PTC_E_ARG for a null pointer, lens parameters ptc_set_camera_lens would refuse, or u outside [0, 1). */
+int ptc_debug_lens_sample(const ptc_lens_params*, float u1, float u2, float out_xy[2]);
+/* The camera rays of the path integrator for n_pixels pixels (indices y*w+x of a w x h frame) and the samples first_sample .. first_sample + n_samples - 1,
+ * with the context's camera and lens and the seed hashed as ptc_frame_begin hashes it: n_pixels * n_samples rays in path order, ray p = sample_local *
+ * n_pixels + j, origins and dirs 3 floats each.  On a device context the launcher a batch would choose — k_raygen for R = 0, the lens kernel otherwise —
+ * writes lane 0's ray queue, which is read back; same preconditions and side effects as ptc_debug_trace_closest (committed scene; ends the frame).  On a
+ * description-only context (a camera must have been set) the host evaluates csrc/pt_lens.h, which restates the pinhole ray for R = 0. */
+int ptc_debug_camera_rays(ptc_ctx*, int w, int h, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const uint32_t* pixels, uint32_t n_pixels,
+                          float* origins, float* dirs);
 /* World-space flattened geometry as committed: verts (n_verts*12 floats = ptc_vertex),
  * indices (n_tris*3 u32), per-triangle material.  Pass NULL to query sizes only. */
 int ptc_debug_get_flat_scene(ptc_ctx*, uint32_t* n_verts, uint32_t* n_tris, ptc_vertex* verts,

@@ -1,0 +1,33 @@
+// pt_lens.hip — ray generation through a thin lens (see pt_lens.h; the definition of every value is pt_lens_ray there, which the host evaluation calls too).
+//
+//   k_raygen_lens   one thread per path, k_raygen's path id -> (owned pixel j = p % n_owned, sample = first + p / n_owned) mapping, so adaptive frames (the
+//                   active-pixel list in DevFrame::owned), tile shares and sample ranges need nothing of their own here.  One 4-byte load of the pixel index,
+//                   four coalesced 16-byte stores: the ray record A = (o, d.x), B = (d.y, d.z, 1, 1), C = (1, 0, p, key) and the cleared path radiance.
+// A streaming kernel like k_raygen: 64 B written per path, every byte once.  Beside k_raygen's work it hashes two more RNG dimensions and evaluates a square
+// root and one (disk) or two (blades) sincos polynomials; profiles/lens_1080p.txt has the two kernels' times at equal path counts.
+#include "pt_lens.h"
+
+namespace {
+__global__ __launch_bounds__(256) void k_raygen_lens(DevCamera cam, ptc_lens_params lens, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_paths) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_paths) return;
+  const uint32_t j = p % fr.n_owned, sl = p / fr.n_owned;
+  const uint32_t pixel = fr.owned[j];
+  float o[3], d[3];
+  uint32_t key;
+  pt_lens_ray(cam, lens, fr.w, fr.h, fr.seed_hash, pixel, first_sample + sl, o, d, key);
+  const RayQ& r = q.ray[0];
+  r.A[p] = make_float4(o[0], o[1], o[2], d[0]);
+  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
+  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), __uint_as_float(key));
+  q.lpath[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+}  // namespace
+
+void pt_launch_raygen_lens(hipStream_t s, const DevCamera& cam, const ptc_lens_params& lens, const DevFrame& fr, const DevQueues& q, uint32_t first_sample,
+                           uint32_t n_samples) {
+  const uint32_t n_paths = fr.n_owned * n_samples;
+  if (!n_paths) return;
+  const dim3 grid((n_paths + 255u) / 256u);
+  hipLaunchKernelGGL(k_raygen_lens, grid, dim3(256), 0, s, cam, lens, fr, q, first_sample, n_paths);
+}

@@ -16,11 +16,13 @@
 #include "pt_adaptive.h"
 #include "pt_temporal.h"
 #include "pt_deform.h"
+#include "pt_lens.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -160,6 +162,7 @@ struct ptc_ctx {
   HostEnv env;
   float cam_pos[3]{}, cam_target[3]{}, cam_fov = 0, cam_aspect = 1;
   bool have_cam = false;
+  ptc_lens_params lens{0.0f, 1.0f, 0, 0.0f};   // the camera's lens (ptc_set_camera_lens): kept across ptc_set_camera, reset by ptc_scene_begin; R = 0: the pinhole, k_raygen
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -520,7 +523,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     { ScopedSpan t(c, st, 0); pt_launch_trace_closest(st, cfg, sc, q, 0, true); c->stats.launches_trace_closest++; }
     pt_launch_shade_raster(st, sc, c->cam, c->fr, q, c->accum.p, c->integrator == PTC_INTEGRATOR_RASTER_GBUFFER16);
   } else {
-    pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
+    if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(st, c->cam, c->lens, c->fr, q, first_sample, n_samples);      // the thin lens (pt_lens.hip); the raster integrators above ignore it
+    else pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
     const bool shadows = sc.n_lights > 0 || sc.env_ok;
     const bool small_batch = n_paths <= (1u << 26);
     const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2;
@@ -796,6 +800,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->bvh_builder = c->bvh_default;
   c->poses.clear();
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
+  ptc_lens_default_params(&c->lens);
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   release_scene(c);
   return PTC_OK;
@@ -1103,6 +1108,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   c->poses.clear(); deform_take(c, c0, /*with_verts=*/false);
   for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active()) c->poses[m].host_fresh = c->poses[m].emis_fresh = c0->poses[m].host_fresh;
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
+  c->lens = c0->lens;
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
 
@@ -1443,6 +1449,55 @@ int ptc_set_camera(ptc_ctx* c, const float pos[3], const float target[3], float 
   c->have_cam = true;
   c->guides_valid = false;      // the guides are those of the camera they were traced from
   if (c->committed) ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
+  return PTC_OK;
+}
+
+// ---- thin-lens camera (pt_lens.h) ---------------------------------------------------------------------------------------------------------
+void ptc_lens_default_params(ptc_lens_params* p) {
+  if (!p) return;
+  p->aperture_radius = 0.0f; p->focus_distance = 1.0f; p->blades = 0; p->rotation = 0.0f;
+}
+
+namespace {
+const char* lens_params_error(const ptc_lens_params& p) {
+  if (!(p.aperture_radius >= 0.0f) || !std::isfinite(p.aperture_radius)) return "aperture_radius must be finite and >= 0";
+  if (!(p.focus_distance > 0.0f) || !std::isfinite(p.focus_distance)) return "focus_distance must be finite and > 0";
+  if (p.blades != 0 && (p.blades < 3 || p.blades > 16)) return "blades must be 0 (disk) or 3..16";
+  if (!(p.rotation >= 0.0f && p.rotation < 1.0f)) return "rotation must be in [0, 1)";
+  return nullptr;
+}
+uint32_t frame_seed_hash(uint64_t seed) { return pt_lens_pcg((uint32_t)seed + pt_lens_pcg((uint32_t)(seed >> 32))); }   // as ptc_frame_begin
+}  // namespace
+
+int ptc_set_camera_lens(ptc_ctx* c, const ptc_lens_params* params) {
+  if (!c) return PTC_E_ARG;
+  ptc_lens_params p;
+  ptc_lens_default_params(&p);
+  if (params) p = *params;
+  if (const char* e = lens_params_error(p)) return fail(c, PTC_E_ARG, std::string("set_camera_lens: ") + e);
+  c->lens = p;      // the guides are traced through the lens centre: they stay valid
+  return PTC_OK;
+}
+
+int ptc_get_camera_lens(const ptc_ctx* c, ptc_lens_params* out) {
+  if (!c || !out) return PTC_E_ARG;
+  *out = c->lens;
+  return PTC_OK;
+}
+
+int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: null pointer");
+  if (!c->guides_valid) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: no guides (ptc_frame_guides)");
+  const int w = c->rad_w, h = c->rad_h;
+  if (px < 0 || py < 0 || px >= w || py >= h) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: pixel outside the frame");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  float4 nz;
+  HIP_TRY(c, hipMemcpy(&nz, c->g_normal.p + ((size_t)py * (size_t)w + (size_t)px), sizeof nz, hipMemcpyDeviceToHost));
+  // the pixel-centre ray of k_raygen_guides: Z is t along the unit ray, the view depth is t over the length of (dvx, dvy, 1)
+  const float fx = ((float)px + 0.5f) / (float)w, fy = ((float)py + 0.5f) / (float)h;
+  const float dvx = (2.0f * fx - 1.0f) * c->cam.sx, dvy = (2.0f * fy - 1.0f) * c->cam.sy;
+  *out = nz.w / std::sqrt(pt_lens_fma(dvy, dvy, pt_lens_fma(dvx, dvx, 1.0f)));
   return PTC_OK;
 }
 
@@ -2510,6 +2565,58 @@ int ptc_debug_trace_any(ptc_ctx* c, const float* origins, const float* dirs, con
   if (e == hipSuccess) e = hipMemcpy(out_occluded, d_out, n, hipMemcpyDeviceToHost);
   (void)hipFree(d_out);
   if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_trace_any: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+int ptc_debug_lens_sample(const ptc_lens_params* lens, float u1, float u2, float out_xy[2]) {
+  if (!lens || !out_xy || lens_params_error(*lens) || !(u1 >= 0.0f && u1 < 1.0f) || !(u2 >= 0.0f && u2 < 1.0f)) return PTC_E_ARG;
+  pt_lens_point(*lens, u1, u2, out_xy[0], out_xy[1]);
+  return PTC_OK;
+}
+
+int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const uint32_t* pixels, uint32_t n_pixels,
+                          float* origins, float* dirs) {
+  if (!c) return PTC_E_ARG;
+  if (!pixels || !origins || !dirs || w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull || n_samples == 0 || n_pixels == 0 ||
+      (uint64_t)n_pixels * (uint64_t)n_samples > 0x7fffffffull || (uint64_t)first_sample + n_samples > 0xffffffffull)
+    return fail(c, PTC_E_ARG, "debug_camera_rays: bad argument");
+  for (uint32_t j = 0; j < n_pixels; ++j)
+    if (pixels[j] >= (uint32_t)w * (uint32_t)h) return fail(c, PTC_E_ARG, "debug_camera_rays: pixel index outside the frame");
+  const uint32_t n = n_pixels * n_samples;
+  const uint32_t seed_hash = frame_seed_hash(seed);
+  if (c->device < 0) {      // the host evaluation of pt_lens.h
+    if (!c->have_cam) return fail(c, PTC_E_STATE, "debug_camera_rays: no camera (ptc_set_camera)");
+    DevCamera cam;
+    ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, cam);
+    for (uint32_t p = 0; p < n; ++p) {
+      uint32_t key;
+      pt_lens_ray(cam, c->lens, w, h, seed_hash, pixels[p % n_pixels], first_sample + p / n_pixels, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);
+    }
+    return PTC_OK;
+  }
+  { int rc = debug_prepare(c, n, "debug_camera_rays"); if (rc) return rc; }
+  const Lane& ln = c->lanes[0];
+  DevBuf<uint32_t> list;
+  { int rc = ensure_buf(c, list, n_pixels); if (rc) return rc; }
+  std::vector<float4> A(n), B(n);
+  hipError_t e = hipMemcpy(list.p, pixels, (size_t)n_pixels * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    DevFrame fr{};
+    fr.w = w; fr.h = h; fr.seed_hash = seed_hash; fr.max_bounces = 0; fr.n_owned = n_pixels; fr.owned = list.p;
+    const DevQueues q = batch_queues(c, 0, n);
+    if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(ln.stream, c->cam, c->lens, fr, q, first_sample, n_samples);      // run_batch's choice
+    else pt_launch_raygen(ln.stream, c->cam, fr, q, first_sample, n_samples, false);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
+  if (e == hipSuccess) e = hipMemcpy(A.data(), ln.q.ray[0].A, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(B.data(), ln.q.ray[0].B, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+  list.release();      // the pixel list lives for this call only
+  if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_camera_rays: ") + hipGetErrorString(e));
+  for (size_t p = 0; p < n; ++p) {
+    origins[p * 3] = A[p].x; origins[p * 3 + 1] = A[p].y; origins[p * 3 + 2] = A[p].z;
+    dirs[p * 3] = A[p].w; dirs[p * 3 + 1] = B[p].x; dirs[p * 3 + 2] = B[p].y;
+  }
   return PTC_OK;
 }
 

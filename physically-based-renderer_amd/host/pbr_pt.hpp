@@ -108,6 +108,17 @@ public:
   auto setCamera(std::array<float, 3> position, std::array<float, 3> target, float fov, float aspect) -> void {
     ck(ptc_set_camera(_ctx, position.data(), target.data(), fov, aspect));
   }
+  // ---- thin-lens camera (include/ptc.h; the reference's camera is a pinhole): depth of field for the path integrator ----
+  // apertureRadius 0 = pinhole; blades 0 = disk, 3..16 = regular polygon with a vertex at `rotation` turns; focusDistance = view depth of the plane of focus.
+  // Kept across setCamera, reset by beginScene; the raster integrators and the guides ignore it
+  static auto lensDefaults() -> ptc_lens_params { ptc_lens_params p; ptc_lens_default_params(&p); return p; }
+  auto setCameraLens(ptc_lens_params const& lens) -> void { ck(ptc_set_camera_lens(_ctx, &lens)); }
+  auto setCameraLens(float apertureRadius, float focusDistance, int blades = 0, float rotation = 0.0f) -> void {
+    setCameraLens(ptc_lens_params{apertureRadius, focusDistance, blades, rotation});
+  }
+  auto cameraLens() const -> ptc_lens_params { ptc_lens_params p; ptc_get_camera_lens(_ctx, &p); return p; }
+  // the view depth of what pixel (x, y)'s centre sees, 0 on a miss: needs frameGuides() of the current frame
+  auto focusDistanceAtPixel(int x, int y) -> float { float d = 0.0f; ck(ptc_focus_distance_at_pixel(_ctx, x, y, &d)); return d; }
   // PTC_BVH_SAH (default) or PTC_BVH_LBVH, for the scene being described
   auto setBvhBuilder(int builder) -> void { ck(ptc_set_bvh_builder(_ctx, builder)); }
   // the tree a build on the device makes (kept across beginScene): PTC_BVH_LBVH (default), or PTC_BVH_SAH — a SAH scene then commits on the device and

@@ -3,6 +3,11 @@
 //              --spp N --seed S --bounces B [--raster | --raster16] [--env latlong.pfm|latlong.hdr | --sky] [--filter nearest|linear] [--bvh sah|lbvh] [--device-bvh sah|lbvh] [--device D] [--gpus N]
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
+//              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
+// --aperture R: the thin lens (ptc_set_camera_lens) with aperture radius R in world units — depth of field, path integrator only.  --blades N: a regular polygon
+// of 3..16 sides instead of the disk, --aperture-rotation T: its rotation in turns, [0, 1).  --focus D: the view depth of the plane of focus (default 1);
+// --focus-pixel X,Y: focus on what that pixel's centre sees — the guides are traced once before the render and ptc_focus_distance_at_pixel is taken (a miss is
+// an error).  The two exclude each other.  Bad values are reported before any device work.
 // --denoise: first-hit guides + the variance-guided a-trous filter (ptc_frame_guides, ptc_denoise) after the render; every output is then the denoised
 // image.  --denoise-iters N: N iterations instead of the default 4 (implies --denoise).  --guides PREFIX: PREFIX_albedo.pfm, PREFIX_normal.pfm and
 // PREFIX_depth.pfm (the depth in all three channels) beside the image, for a denoiser outside the library.  With --gpus N device D denoises after the reduce.
@@ -133,6 +138,9 @@ int main(int argc, char** argv) {
   bool adaptive = false;
   ptc_adaptive_params ap = pbr::PathTraceRenderSystem::adaptiveDefaults();
   std::string countsPath;
+  ptc_lens_params lens = pbr::PathTraceRenderSystem::lensDefaults();      // --aperture / --blades / --aperture-rotation / --focus
+  bool haveFocus = false, haveFocusPixel = false, haveLensShape = false;
+  int focusX = 0, focusY = 0;
   int animation = -1;                        // --animation: pose the glTF scene along this animation ...
   double animTime = 0.0;                     // ... at --time seconds, before the commit
   for (int i = 1; i < argc; ++i) {
@@ -148,6 +156,10 @@ int main(int argc, char** argv) {
     else if (a == "--denoise-sampled") { denoiseSampled = true; denoise = true; }
     else if (a == "--adaptive") { ap.threshold = (float)std::atof(next()); adaptive = true; } else if (a == "--min-spp") ap.min_samples = std::atoi(next());
     else if (a == "--spp-step") ap.step_samples = std::atoi(next()); else if (a == "--adaptive-radius") ap.radius = std::atoi(next()); else if (a == "--counts") countsPath = next();
+    else if (a == "--aperture") lens.aperture_radius = (float)std::atof(next());
+    else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
+    else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
+    else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -169,6 +181,27 @@ int main(int argc, char** argv) {
     if (adaptive && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--adaptive renders on one context with the path integrator (not with --gpus / --raster)");
     if (denoiseSampled && (gpus != 0 || integrator != PTC_INTEGRATOR_PATH)) throw std::runtime_error("--denoise-sampled renders on one context with the path integrator (not with --gpus / --raster)");
     if (!adaptive && !countsPath.empty()) throw std::runtime_error("--counts needs --adaptive");
+    {   // the lens: everything that can be refused is refused here, before a device is touched
+      if (haveFocus && haveFocusPixel) throw std::runtime_error("--focus and --focus-pixel exclude each other");
+      const bool anyLens = lens.aperture_radius != 0.0f || haveFocus || haveFocusPixel || haveLensShape;
+      if (anyLens && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--aperture / --focus* / --blades apply to the path integrator (not with --raster / --raster16)");
+      if (!(lens.aperture_radius >= 0.0f) || !std::isfinite(lens.aperture_radius)) throw std::runtime_error("--aperture R: a finite radius >= 0");
+      if (!(lens.focus_distance > 0.0f) || !std::isfinite(lens.focus_distance)) throw std::runtime_error("--focus D: a finite distance > 0");
+      if (lens.blades != 0 && (lens.blades < 3 || lens.blades > 16)) throw std::runtime_error("--blades N: 0 (disk) or 3..16");
+      if (!(lens.rotation >= 0.0f && lens.rotation < 1.0f)) throw std::runtime_error("--aperture-rotation T: turns in [0, 1)");
+      if (haveFocusPixel && (focusX < 0 || focusY < 0 || focusX >= w || focusY >= h)) throw std::runtime_error("--focus-pixel X,Y: a pixel of the image");
+    }
+    // after the commit: the lens, focused on a pixel if asked (one guide pass of a one-sample frame; the render that follows begins its own frame)
+    auto applyLens = [&](pbr::PathTraceRenderSystem& rs) {
+      if (haveFocusPixel) {
+        if (ptc_frame_begin(rs.handle(), w, h, 1, seed, bounces, PTC_INTEGRATOR_PATH, 0, 1) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+        rs.frameGuides();
+        lens.focus_distance = rs.focusDistanceAtPixel(focusX, focusY);
+        if (!(lens.focus_distance > 0.0f)) throw std::runtime_error("--focus-pixel: the pixel sees nothing to focus on");
+        std::printf("{\"focus_pixel\": [%d, %d], \"focus_distance\": %.9g}\n", focusX, focusY, (double)lens.focus_distance);
+      }
+      rs.setCameraLens(lens);
+    };
     if (gltf.empty() && animation >= 0) throw std::runtime_error("--animation poses a --gltf scene");
     if (gltf.empty() && (!envPath.empty() || sky)) throw std::runtime_error("--env / --sky light a --gltf scene; the built-in scenes carry their own lights");
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
@@ -229,6 +262,7 @@ int main(int argc, char** argv) {
     if (gpus == 0) {
       single.reset(new pbr::PathTraceRenderSystem(device));
       buildScene(*single);
+      applyLens(*single);
       if (denoiseSampled) single->setSampleCovariance(true);
       img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : denoiseSampled ? single->renderWithStatistics(w, h, spp, seed, bounces)
                                                                                                 : single->render(w, h, spp, seed, bounces, integrator);
@@ -237,6 +271,7 @@ int main(int argc, char** argv) {
       for (int i = 0; i < gpus; ++i) ids.push_back(device + i);
       group.reset(new pbr::DeviceGroup(ids));
       buildScene(group->device(0));
+      applyLens(group->device(0));   // the group commit copies the lens with the camera
       group->commitScene();          // one flatten + BVH build on the host, uploaded to every device
       img = group->render(w, h, spp, seed, bounces, integrator);
     }

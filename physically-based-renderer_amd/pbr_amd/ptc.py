@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "ptc_set_sample_covariance", "ptc_read_sample_covariance", "ptc_denoise_sampled", "ptc_read_sampled_variance",
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_mesh_set_morph_targets", "ptc_mesh_set_skin", "ptc_update_mesh_pose", "ptc_update_mesh_vertices", "ptc_debug_get_mesh_vertices",
+    "ptc_lens_default_params", "ptc_set_camera_lens", "ptc_get_camera_lens", "ptc_focus_distance_at_pixel", "ptc_debug_lens_sample", "ptc_debug_camera_rays",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
 
@@ -96,6 +97,13 @@ class PtcAdaptiveParams(C.Structure):
 class PtcAdaptiveStats(C.Structure):
     _fields_ = [("owned_pixels", C.c_uint64), ("active_pixels", C.c_uint64), ("samples_total", C.c_uint64),
                 ("passes", C.c_uint32), ("max_count", C.c_uint32), ("seconds_adapt", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcLensParams(C.Structure):
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int), ("rotation", C.c_float)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -208,6 +216,13 @@ def load_library():
     L.ptc_read_sample_covariance.argtypes = [vp, fp]
     L.ptc_denoise_sampled.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
     L.ptc_read_sampled_variance.argtypes = [vp, fp]
+    L.ptc_lens_default_params.argtypes = [C.POINTER(PtcLensParams)]
+    L.ptc_lens_default_params.restype = None
+    L.ptc_set_camera_lens.argtypes = [vp, C.POINTER(PtcLensParams)]
+    L.ptc_get_camera_lens.argtypes = [vp, C.POINTER(PtcLensParams)]
+    L.ptc_focus_distance_at_pixel.argtypes = [vp, C.c_int, C.c_int, fp]
+    L.ptc_debug_lens_sample.argtypes = [C.POINTER(PtcLensParams), C.c_float, C.c_float, fp]
+    L.ptc_debug_camera_rays.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, u32p, C.c_uint32, fp, fp]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -231,6 +246,27 @@ def load_library():
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def lens_default_params():
+    p = PtcLensParams()
+    load_library().ptc_lens_default_params(C.byref(p))
+    return p.as_dict()
+
+
+def lens_sample(u1, u2, aperture_radius=1.0, blades=0, rotation=0.0):
+    """ptc_debug_lens_sample: the aperture point (lx, ly) of the pair (u1, u2) in [0,1)^2, the host's evaluation of csrc/pt_lens.h.  Scalars give a pair,
+    arrays an (n, 2) float32 array."""
+    L = load_library()
+    p = PtcLensParams(aperture_radius, 1.0, int(blades), rotation)
+    a, b = np.atleast_1d(np.asarray(u1, np.float32)), np.atleast_1d(np.asarray(u2, np.float32))
+    out = np.zeros((a.size, 2), np.float32)
+    xy = (C.c_float * 2)()
+    for i in range(a.size):
+        if L.ptc_debug_lens_sample(C.byref(p), float(a[i]), float(b[i]), xy) < 0:
+            raise PtcError(f"lens_sample: bad lens parameters or u outside [0, 1): {p.as_dict()}, ({a[i]}, {b[i]})")
+        out[i] = xy[0], xy[1]
+    return out if np.ndim(u1) else (float(out[0, 0]), float(out[0, 1]))
 
 
 def comm_unique_id() -> bytes:
@@ -306,11 +342,31 @@ class PathTracer:
                 self._ck(L.ptc_add_instance(h, it.mesh, _f(it.t)[1], _f(it.q_wxyz)[1], _f(it.s)[1]))
         c = desc.camera
         self._ck(L.ptc_set_camera(h, _f(c.position)[1], _f(c.target)[1], c.fov_y, c.aspect))
+        self.set_camera_lens(getattr(c, "aperture_radius", 0.0), getattr(c, "focus_distance", 1.0), getattr(c, "blades", 0), getattr(c, "aperture_rotation", 0.0))
         self._ck(L.ptc_scene_commit(h))
         return self
 
     def set_camera(self, position, target, fov_y, aspect):
         self._ck(self._L.ptc_set_camera(self._h, _f(position)[1], _f(target)[1], fov_y, aspect))
+
+    def set_camera_lens(self, aperture_radius=0.0, focus_distance=1.0, blades=0, rotation=0.0):
+        """ptc_set_camera_lens: the thin lens of the path integrator's camera.  aperture_radius 0 is the pinhole; blades 0 a disk, 3..16 a regular polygon with
+        a vertex at `rotation` turns; focus_distance the view depth of the plane of focus.  Kept across set_camera, reset by load_scene (which applies the
+        scene camera's lens fields)."""
+        p = PtcLensParams(aperture_radius, focus_distance, int(blades), rotation)
+        self._ck(self._L.ptc_set_camera_lens(self._h, C.byref(p)))
+        return self
+
+    def get_camera_lens(self):
+        p = PtcLensParams()
+        self._ck(self._L.ptc_get_camera_lens(self._h, C.byref(p)))
+        return p.as_dict()
+
+    def focus_distance_at_pixel(self, x, y):
+        """ptc_focus_distance_at_pixel: the view depth of what pixel (x, y)'s centre sees (0 on a miss), from the current frame's guides (frame_guides())."""
+        out = C.c_float(0)
+        self._ck(self._L.ptc_focus_distance_at_pixel(self._h, int(x), int(y), C.byref(out)))
+        return float(out.value)
 
     def update_instance(self, instance, t=None, q_wxyz=None, s=None, matrix=None):
         """New transform for a committed instance (ptc_update_instance / ptc_update_instance_matrix); scene_refit() applies it."""
@@ -652,6 +708,16 @@ class PathTracer:
         occ = np.zeros(n, np.uint8)
         self._ck(self._L.ptc_debug_trace_any(self._h, op, dp, tp, n, occ.ctypes.data_as(C.POINTER(C.c_uint8))))
         return occ
+
+    def debug_camera_rays(self, w, h, seed, first_sample, n_samples, pixels=None):
+        """ptc_debug_camera_rays: (origins, dirs), each (n_samples * n_pixels, 3) float32 in path order p = sample_local * n_pixels + j, of the path integrator's
+        camera rays for `pixels` (indices y * w + x; None: every pixel in order) with the context's camera and lens."""
+        px = np.arange(w * h, dtype=np.uint32) if pixels is None else np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+        n = px.size * int(n_samples)
+        o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        self._ck(self._L.ptc_debug_camera_rays(self._h, w, h, seed, first_sample, n_samples, px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size,
+                                               o.ctypes.data_as(C.POINTER(C.c_float)), d.ctypes.data_as(C.POINTER(C.c_float))))
+        return o, d
 
     def flat_scene(self):
         nv, nt = C.c_uint32(), C.c_uint32()

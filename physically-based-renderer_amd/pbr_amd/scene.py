@@ -201,6 +201,11 @@ class CameraDesc:
     target: Sequence[float]
     fov_y: float
     aspect: float
+    # the thin lens (ptc_set_camera_lens): aperture_radius 0 is the pinhole; blades 0 a disk, 3..16 a regular polygon; rotation in turns
+    aperture_radius: float = 0.0
+    focus_distance: float = 1.0
+    blades: int = 0
+    aperture_rotation: float = 0.0
 
 
 @dataclasses.dataclass
