@@ -44,6 +44,13 @@ int main(int argc, char** argv) {
   ptc_lens_params lens;                                /* the thin lens: the defaults are the pinhole, aperture_radius > 0 gives depth of field */
   ptc_lens_default_params(&lens);
   CHECK(ptc_set_camera_lens(ctx, &lens));
+  {
+    ptc_light_params lamp;                             /* a punctual light: no geometry, no commit; a frame sees the lights recorded when it begins */
+    ptc_light_default_params(&lamp);                   /* a white point light of intensity 1 at the origin */
+    lamp.position[0] = 0.8f; lamp.position[1] = -0.6f; lamp.position[2] = -2.5f;
+    lamp.intensity[0] = 2.0f; lamp.intensity[1] = 1.6f; lamp.intensity[2] = 1.2f;
+    CHECK(ptc_add_light(ctx, &lamp));
+  }
   CHECK(ptc_scene_commit(ctx));
   ptc_stats st;
   CHECK(ptc_get_stats(ctx, &st));

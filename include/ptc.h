@@ -254,6 +254,43 @@ int  ptc_set_camera_lens(ptc_ctx*, const ptc_lens_params*);    /* NULL: the defa
 int  ptc_get_camera_lens(const ptc_ctx*, ptc_lens_params*);
 int  ptc_focus_distance_at_pixel(ptc_ctx*, int px, int py, float* out);
 
+/* ---- punctual lights: point, spot and directional (glTF KHR_lights_punctual; no counterpart in the reference, which has no lights) ----
+ * A punctual light has no area.  The path integrator samples it by next-event estimation in a pass of its own behind the shading of every bounce
+ * b < max_bounces: one light per hit, chosen with probability sampling_weight / sum of the weights, a shadow ray, and the unoccluded contribution
+ * T f(wo, wi) Li cos / pmf added to the path.  No MIS weight: a BSDF sample cannot hit such a light, the term adds to emitters and environment.
+ * Radiance arriving at P from the unit direction wi (csrc/pt_lights.h and DESIGN.md 2b have the arithmetic, IEEE binary32 in the order written):
+ *   PTC_LIGHT_POINT        Li = intensity / d^2 (W/sr: glTF colour x candela), times the window clamp(1 - (d / range)^4, 0, 1) when range > 0
+ *   PTC_LIGHT_SPOT         the same times s^2, s = clamp((cd - cos_outer) / max(cos_inner - cos_outer, 0.001), 0, 1), cd = dot(direction, -wi): `direction` is
+ *                          the axis the light points along; 1 >= cos_inner > cos_outer >= -1
+ *   PTC_LIGHT_DIRECTIONAL  Li = intensity, the irradiance on a facing surface (glTF colour x lux); `direction` is the way the light travels
+ * At most PTC_MAX_LIGHTS lights.  A scene without them launches exactly the kernels it always launched.
+ *
+ * The calls need no device and only record; they are valid any time after ptc_scene_begin, which drops all lights.  Lights are not part of the tree: adding,
+ * changing or clearing them needs no commit and no refit.  ptc_frame_begin uploads a changed table, so a change during a frame applies from the next
+ * ptc_frame_begin.  ptc_group_scene_commit and ptc_group_render give every member the lights of ptc_group_ctx(g, 0).
+ * ptc_add_light returns the light's id (>= 0; ids count from 0 in the order added).  ptc_add_light / ptc_update_light: PTC_E_ARG, and nothing changed, for
+ *   an unknown type, a non-finite field, a negative intensity or range, a zero direction where one is needed (spot, directional), cone cosines out of order
+ *   (spot), a sampling_weight that is not finite and > 0, an id out of range, a light beyond PTC_MAX_LIGHTS.  The direction is stored normalised.
+ * What ignores the lights: the raster integrators, ptc_frame_guides, the denoisers and the temporal history. */
+enum { PTC_LIGHT_POINT = 0, PTC_LIGHT_SPOT = 1, PTC_LIGHT_DIRECTIONAL = 2 };
+#define PTC_MAX_LIGHTS 256
+typedef struct ptc_light_params {
+  int   type;             /* PTC_LIGHT_*                                                                  */
+  float position[3];      /* point, spot                                                                  */
+  float direction[3];     /* spot: the axis it points along; directional: the way the light travels      */
+  float intensity[3];     /* rgb >= 0: W/sr (point, spot) or irradiance (directional)                     */
+  float range;            /* >= 0; 0 = no range window (point, spot)                                      */
+  float cos_inner;        /* spot: full intensity inside this cosine ...                                  */
+  float cos_outer;        /* ... none outside this one                                                    */
+  float sampling_weight;  /* > 0: relative probability of being chosen for a hit (default 1)             */
+} ptc_light_params;
+void ptc_light_default_params(ptc_light_params*);   /* a white point light of intensity 1 at the origin, direction -z, no range, cone cosines 1 and cos(pi/4), weight 1 */
+int  ptc_add_light(ptc_ctx*, const ptc_light_params*);
+int  ptc_update_light(ptc_ctx*, int id, const ptc_light_params*);
+int  ptc_get_light(const ptc_ctx*, int id, ptc_light_params* out);
+int  ptc_light_count(const ptc_ctx*);
+int  ptc_clear_lights(ptc_ctx*);
+
 /* Lat-long environment light (BASELINE config 5; no counterpart in the reference, which has no lights): w*h RGB
  * fp32 texels, row 0 = +y, u = atan2(d.z, d.x)/(2 pi) + 1/2, piecewise-constant radiance, importance-sampled by
  * luminance x sin(theta).  rgb == NULL removes it.  Call before ptc_scene_commit. */
@@ -554,6 +591,21 @@ int ptc_debug_trace_any(ptc_ctx*, const float* origins, const float* dirs, const
 /* The aperture point (lx, ly) that the lens selects for the pair (u1, u2) in [0,1)^2: a pure host evaluation of csrc/pt_lens.h, no context.
  * PTC_E_ARG for a null pointer, lens parameters ptc_set_camera_lens would refuse, or u outside [0, 1). */
 int ptc_debug_lens_sample(const ptc_lens_params*, float u1, float u2, float out_xy[2]);
+/* Punctual lights (csrc/pt_lights.h).
+ * ptc_debug_light_sample: the host evaluation of pt_light_sample for one light and one point P, no context: unit direction towards the light, the distance
+ *   (3.0e38 for a directional light) and the arriving radiance.  Returns 1 when there is a sample, 0 when there is none (P on the light; outputs untouched),
+ *   PTC_E_ARG for a null pointer or parameters ptc_add_light would refuse.
+ * ptc_debug_get_light_table: the 64-byte records (16 floats per light: position, type as int bits | direction, range | intensity, pmf | spot scale, spot
+ *   offset, cos_inner, cos_outer) and the cdf (one float per light) as ptc_frame_begin uploads them for the lights recorded now.  Arrays may be NULL (count only).
+ *   Works on a description-only context.
+ * ptc_debug_punctual_nee: n explicit rays in identity layout with throughput 1, path id = index and the given RNG keys through k_trace_closest and then
+ *   k_shade_punctual at `bounce`, with the lights recorded now (at least one: PTC_E_STATE otherwise).  Per ray: out_valid 1 if it produced a shadow record, and
+ *   that record — origin (3), direction (3), tmax, contribution (3); records are matched by the path id they carry.  Preconditions and side effects as
+ *   ptc_debug_trace_closest. */
+int ptc_debug_light_sample(const ptc_light_params*, const float P[3], float out_wi[3], float* out_dist, float out_Li[3]);
+int ptc_debug_get_light_table(ptc_ctx*, uint32_t* n_lights, float* records, float* cdf);
+int ptc_debug_punctual_nee(ptc_ctx*, const float* origins, const float* dirs, const uint32_t* keys, uint32_t n, uint32_t bounce,
+                           uint8_t* out_valid, float* out_origin, float* out_dir, float* out_tmax, float* out_contrib);
 /* The camera rays of the path integrator for n_pixels pixels (indices y*w+x of a w x h frame) and the samples first_sample .. first_sample + n_samples - 1,
  * with the context's camera and lens and the seed hashed as ptc_frame_begin hashes it: n_pixels * n_samples rays in path order, ray p = sample_local *
  * n_pixels + j, origins and dirs 3 floats each.  On a device context the launcher a batch would choose — k_raygen for R = 0, the lens kernel otherwise —

@@ -8,6 +8,9 @@
  * and JPEG decoders (and BMP, TGA, PGM / PPM: ptc_image_decode_rgba8 below), which reproduce the output of the reference's vendored stb_image bit for bit (tests/test_jpeg.py,
  * tests/test_png.py against oracle/_ref).  Samplers are ignored: the reference creates
  * default samplers (NEAREST, REPEAT) whatever the asset says (Asset.cpp:116-117).
+ * KHR_lights_punctual: every light a node of the scene references is added with ptc_add_light, in the order the traversal first reaches the nodes — position = the
+ * node's origin, direction = its -Z axis after the composed transform, intensity = color x intensity (candela for point and spot, lux for directional), range,
+ * and the spot's cone angles as cosines; ptc_clear_lights afterwards drops them.
  * Call between ptc_scene_begin and ptc_scene_commit; the camera stays the caller's (the reference ignores glTF
  * cameras too and injects its own, Asset.cpp:262-265).  Host-only: works on a PTC_DEVICE_NONE context.
  */
@@ -38,6 +41,7 @@ long long ptc_gltf_load(ptc_ctx* ctx, const char* path, int scene_index, int com
  *                          its value entries (its tangents are not used).  Issues ptc_update_instance_matrix for every instance and
  *                          ptc_update_mesh_pose for every deforming mesh, joint matrix = inverse(global(mesh node)) global(joint) inverseBind; the
  *                          caller then calls ptc_scene_refit / ptc_scene_rebuild (or ptc_scene_commit, when the scene is not committed yet).
+ *                          The KHR_lights_punctual lights ptc_gltf_asset_load added move with their nodes (ptc_update_light; they need no refit).
  *   ptc_gltf_close         frees the handle (the context is not touched)
  * Errors: a negative PTC_E_* code; ptc_gltf_asset_last_error has the text. */
 typedef struct ptc_gltf_asset ptc_gltf_asset;

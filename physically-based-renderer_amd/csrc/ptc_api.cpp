@@ -17,6 +17,7 @@
 #include "pt_temporal.h"
 #include "pt_deform.h"
 #include "pt_lens.h"
+#include "pt_lights.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -163,6 +164,12 @@ struct ptc_ctx {
   float cam_pos[3]{}, cam_target[3]{}, cam_fov = 0, cam_aspect = 1;
   bool have_cam = false;
   ptc_lens_params lens{0.0f, 1.0f, 0, 0.0f};   // the camera's lens (ptc_set_camera_lens): kept across ptc_set_camera, reset by ptc_scene_begin; R = 0: the pinhole, k_raygen
+  // punctual lights (pt_lights.h): `lights` is what the calls recorded; the device table is what the last ptc_frame_begin uploaded of it, and what the frame's batches use
+  std::vector<ptc_light_params> lights;
+  bool lights_dirty = false;             // `lights` changed since the upload
+  DevBuf<pt_light_rec> d_lights;
+  DevBuf<float> d_light_cdf;
+  uint32_t n_lights_dev = 0;             // lights in the device table; 0: no punctual pass, nothing allocated
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -501,6 +508,23 @@ uint32_t batch_samples(const ptc_ctx* c, size_t n_pixels, size_t batch_paths) {
   return (uint32_t)per;
 }
 
+// The punctual lights' table as recorded -> device memory, when it changed (ptc_frame_begin, ptc_debug_punctual_nee: every lane is idle).  No light: nothing is allocated.
+int upload_lights(ptc_ctx* c) {
+  if (!c->lights_dirty) return PTC_OK;
+  std::vector<pt_light_rec> recs; std::vector<float> cdf;
+  pt_light_table(c->lights, recs, cdf);
+  if (!recs.empty()) {
+    int rc = ensure_buf(c, c->d_lights, recs.size());
+    if (!rc) rc = ensure_buf(c, c->d_light_cdf, cdf.size());
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(c->d_lights.p, recs.data(), recs.size() * sizeof(pt_light_rec), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_light_cdf.p, cdf.data(), cdf.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  c->n_lights_dev = (uint32_t)recs.size();
+  c->lights_dirty = false;
+  return PTC_OK;
+}
+
 // One wavefront batch of n samples per owned pixel (per active pixel of an adaptive frame) on lane `l`, fully asynchronous.
 int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
   const uint32_t n_paths = c->fr.n_owned * n_samples;
@@ -527,7 +551,10 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     else pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
     const bool shadows = sc.n_lights > 0 || sc.env_ok;
     const bool small_batch = n_paths <= (1u << 26);
-    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2;
+    // punctual lights (pt_lights.hip): a second next-event pass per bounce, on this stream alone — it needs hit and ray[b & 1] of bounce b intact and lpath to itself,
+    // so any(b) does not run beside closest(b + 1) while lights exist
+    const bool punctual = c->n_lights_dev > 0;
+    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
       while (ln.ev_scan.size() < need) { hipEvent_t e = nullptr; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ln.ev_scan.push_back(e); }
@@ -550,6 +577,11 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
         HIP_TRY(c, hipEventRecord(ln.ev_any[(size_t)b], ln.stream2));
       } else if (shadows) {
         ScopedSpan t(c, st, 1); pt_launch_trace_any(st, cfg, sc, q, nullptr); c->stats.launches_trace_any++;
+      }
+      if (punctual) {     // behind emission (k_shade) and the emitter / environment sample (any): the punctual sample, through the same shadow queue
+        { ScopedSpan t(c, st, 2); pt_launch_shade_punctual(st, sc, q, b & 1, (uint32_t)b, c->d_lights.p, c->d_light_cdf.p, c->n_lights_dev); }
+        pt_launch_scan(st, cfg, q, (b + 1) & 1);      // the same ray prefix again, the new shadow counts, the work counters zeroed: nothing runs beside it
+        { ScopedSpan t(c, st, 1); pt_launch_trace_any(st, cfg, sc, q, nullptr); c->stats.launches_trace_any++; }
       }
     }
     // sample-order accumulation: wait for the previous batch's accumulate (it ran on the previous lane)
@@ -777,6 +809,7 @@ void ptc_destroy(ptc_ctx* c) {
   c->owned.release(); c->accum.release(); c->radiance.release(); c->ldr.release(); c->half.release();
   c->g_albedo.release(); c->g_normal.release(); c->g_pos.release(); c->dn_cv[0].release(); c->dn_cv[1].release(); c->denoised.release();
   c->g_prim.release(); c->g_uv.release(); c->g_stats.release();
+  c->d_lights.release(); c->d_light_cdf.release();
   for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
   for (auto* b : {&c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_count, &c->ad_block, &c->ad_n}) b->release();
   c->ad_mom.release(); c->ad_flags.release(); c->ad_keep.release();
@@ -801,6 +834,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->poses.clear();
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
   ptc_lens_default_params(&c->lens);
+  c->lights_dirty = c->lights_dirty || !c->lights.empty(); c->lights.clear();
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   release_scene(c);
   return PTC_OK;
@@ -1100,6 +1134,12 @@ bool description_matches_commit(const ptc_ctx* c) {
   }
   return nv == c->built->n_wverts && nt == c->built->n_tris;
 }
+// a group member takes device 0's punctual lights (ptc_group_scene_commit, ptc_group_render)
+void take_lights(ptc_ctx* c, const ptc_ctx* c0) {
+  if (c == c0) return;
+  const bool same = c->lights.size() == c0->lights.size() && (c->lights.empty() || std::memcmp(c->lights.data(), c0->lights.data(), c->lights.size() * sizeof(ptc_light_params)) == 0);
+  if (!same) { c->lights = c0->lights; c->lights_dirty = true; }
+}
 const char* const kDescriptionChanged = "scene_refit: the scene's meshes or instances changed since the commit (only transforms may)";
 const char* const kNonFinite = "scene_commit: non-finite vertex position after the instance transform";
 // A group member takes device 0's description: materials are counted from it, a later ptc_scene_commit on this context rebuilds from it
@@ -1109,6 +1149,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active()) c->poses[m].host_fresh = c->poses[m].emis_fresh = c0->poses[m].host_fresh;
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
   c->lens = c0->lens;
+  take_lights(c, c0);
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
 
@@ -1485,6 +1526,54 @@ int ptc_get_camera_lens(const ptc_ctx* c, ptc_lens_params* out) {
   return PTC_OK;
 }
 
+// ---- punctual lights (pt_lights.h) ----------------------------------------------------------------------------------------------------------
+void ptc_light_default_params(ptc_light_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->type = PTC_LIGHT_POINT;
+  p->direction[2] = -1.0f;
+  p->intensity[0] = p->intensity[1] = p->intensity[2] = 1.0f;
+  p->cos_inner = 1.0f; p->cos_outer = 0.70710678f;      // glTF's default cone: inner 0, outer pi / 4
+  p->sampling_weight = 1.0f;
+}
+
+int ptc_add_light(ptc_ctx* c, const ptc_light_params* params) {
+  if (!c) return PTC_E_ARG;
+  if (!params) return fail(c, PTC_E_ARG, "add_light: null pointer");
+  if (const char* e = pt_light_params_error(*params)) return fail(c, PTC_E_ARG, std::string("add_light: ") + e);
+  if (c->lights.size() >= PTC_MAX_LIGHTS) return fail(c, PTC_E_ARG, "add_light: more than PTC_MAX_LIGHTS lights");
+  ptc_light_params p = *params;
+  pt_light_normalise(p);
+  c->lights.push_back(p);
+  c->lights_dirty = true;
+  return (int)c->lights.size() - 1;
+}
+
+int ptc_update_light(ptc_ctx* c, int id, const ptc_light_params* params) {
+  if (!c) return PTC_E_ARG;
+  if (!params || id < 0 || (size_t)id >= c->lights.size()) return fail(c, PTC_E_ARG, "update_light: null pointer or light id out of range");
+  if (const char* e = pt_light_params_error(*params)) return fail(c, PTC_E_ARG, std::string("update_light: ") + e);
+  ptc_light_params p = *params;
+  pt_light_normalise(p);
+  c->lights[(size_t)id] = p;
+  c->lights_dirty = true;
+  return PTC_OK;
+}
+
+int ptc_get_light(const ptc_ctx* c, int id, ptc_light_params* out) {
+  if (!c || !out || id < 0 || (size_t)id >= c->lights.size()) return PTC_E_ARG;
+  *out = c->lights[(size_t)id];
+  return PTC_OK;
+}
+
+int ptc_light_count(const ptc_ctx* c) { return c ? (int)c->lights.size() : PTC_E_ARG; }
+
+int ptc_clear_lights(ptc_ctx* c) {
+  if (!c) return PTC_E_ARG;
+  if (!c->lights.empty()) { c->lights.clear(); c->lights_dirty = true; }
+  return PTC_OK;
+}
+
 int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!out) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: null pointer");
@@ -1691,6 +1780,7 @@ int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int 
   if (tile_count < 1 || tile_rank < 0 || tile_rank >= tile_count) return fail(c, PTC_E_ARG, "frame_begin: bad tile rank/count");
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   int rc;
+  if ((rc = upload_lights(c))) return rc;      // a changed light table: nothing is queued any more that reads the old one
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
   if (!(c->owned_key_valid && c->owned_w == w && c->owned_h == h && c->owned_rank == tile_rank && c->owned_count == tile_count && c->owned.p)) {
@@ -2490,6 +2580,7 @@ int ptc_group_render(ptc_group* g, int w, int h, int spp, uint64_t seed, int max
   const int n = (int)g->ctx.size();
   auto bail = [&](int i, int rc) { g->err = std::string("device ") + std::to_string(i) + ": " + ptc_last_error(g->ctx[(size_t)i]); return rc; };
   // every device traces all samples of its tiles; all of it is queued before anything is waited for
+  for (int i = 1; i < n; ++i) take_lights(g->ctx[(size_t)i], g->ctx[0]);
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_begin(g->ctx[(size_t)i], w, h, spp, seed, max_bounces, integrator, i, n); if (rc) return bail(i, rc); }
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_add_samples(g->ctx[(size_t)i], spp); if (rc) return bail(i, rc); }
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_resolve(g->ctx[(size_t)i]); if (rc) return bail(i, rc); }
@@ -2571,6 +2662,80 @@ int ptc_debug_trace_any(ptc_ctx* c, const float* origins, const float* dirs, con
 int ptc_debug_lens_sample(const ptc_lens_params* lens, float u1, float u2, float out_xy[2]) {
   if (!lens || !out_xy || lens_params_error(*lens) || !(u1 >= 0.0f && u1 < 1.0f) || !(u2 >= 0.0f && u2 < 1.0f)) return PTC_E_ARG;
   pt_lens_point(*lens, u1, u2, out_xy[0], out_xy[1]);
+  return PTC_OK;
+}
+
+int ptc_debug_light_sample(const ptc_light_params* params, const float P[3], float out_wi[3], float* out_dist, float out_Li[3]) {
+  if (!params || !P || !out_wi || !out_dist || !out_Li || pt_light_params_error(*params)) return PTC_E_ARG;
+  ptc_light_params p = *params;
+  pt_light_normalise(p);
+  const pt_light_rec L = pt_light_make_rec(p, 1.0f);
+  float wi[3], Li[3], dist;
+  if (!pt_light_sample(L, P, wi, dist, Li)) return 0;
+  for (int k = 0; k < 3; ++k) { out_wi[k] = wi[k]; out_Li[k] = Li[k]; }
+  *out_dist = dist;
+  return 1;
+}
+
+int ptc_debug_get_light_table(ptc_ctx* c, uint32_t* n_lights, float* records, float* cdf) {
+  if (!c) return PTC_E_ARG;
+  std::vector<pt_light_rec> recs; std::vector<float> cd;
+  pt_light_table(c->lights, recs, cd);
+  if (n_lights) *n_lights = (uint32_t)recs.size();
+  if (records && !recs.empty()) std::memcpy(records, recs.data(), recs.size() * sizeof(pt_light_rec));
+  if (cdf && !cd.empty()) std::memcpy(cdf, cd.data(), cd.size() * sizeof(float));
+  return PTC_OK;
+}
+
+int ptc_debug_punctual_nee(ptc_ctx* c, const float* origins, const float* dirs, const uint32_t* keys, uint32_t n, uint32_t bounce,
+                           uint8_t* out_valid, float* out_origin, float* out_dir, float* out_tmax, float* out_contrib) {
+  if (!c) return PTC_E_ARG;
+  if (c->device >= 0 && (!origins || !dirs || !keys || !out_valid || !out_origin || !out_dir || !out_tmax || !out_contrib || n == 0 || bounce > 0x0fffffffu))
+    return fail(c, PTC_E_ARG, "debug_punctual_nee: bad argument");
+  { int rc = debug_prepare(c, n, "debug_punctual_nee"); if (rc) return rc; }
+  if (c->lights.empty()) return fail(c, PTC_E_STATE, "debug_punctual_nee: no punctual light (ptc_add_light)");
+  { int rc = upload_lights(c); if (rc) return rc; }
+  const Lane& ln = c->lanes[0];
+  std::vector<float4> A(n), B(n), C(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
+    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
+    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 1.0f, 1.0f);
+    C[i] = make_float4(1.0f, 0.0f, fi, fk);
+  }
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  const DevQueues q = batch_queues(c, 0, n);
+  const DevScene sc = lane_scene(c, 0);
+  pt_launch_set_counts(ln.stream, c->cfg, q, n, 0);
+  pt_launch_trace_closest(ln.stream, c->cfg, sc, q, 0, false);
+  pt_launch_shade_punctual(ln.stream, sc, q, 0, bounce, c->d_lights.p, c->d_light_cdf.p, c->n_lights_dev);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(ln.stream));
+  // the records lie at the front of each segment; a record says which ray it belongs to
+  std::vector<uint32_t> seg_sh(q.n_seg);
+  HIP_TRY(c, hipMemcpy(seg_sh.data(), q.seg_sh, (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
+  const size_t slots = (size_t)q.n_seg * q.seg_len;
+  std::vector<float4> SA(slots), SB(slots), SC(slots);
+  HIP_TRY(c, hipMemcpy(SA.data(), q.shadow.A, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(SB.data(), q.shadow.B, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(SC.data(), q.shadow.C, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  std::memset(out_valid, 0, n);
+  std::memset(out_origin, 0, (size_t)n * 12); std::memset(out_dir, 0, (size_t)n * 12); std::memset(out_tmax, 0, (size_t)n * 4); std::memset(out_contrib, 0, (size_t)n * 12);
+  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
+    if (seg_sh[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_punctual_nee: a segment holds more shadow records than slots");
+    for (uint32_t k = 0; k < seg_sh[sg]; ++k) {
+      const size_t at = (size_t)sg * q.seg_len + k;
+      uint32_t path; std::memcpy(&path, &SB[at].w, 4);
+      if (path >= n || out_valid[path]) return fail(c, PTC_E_DEVICE, "debug_punctual_nee: a shadow record carries a path id that is out of range or taken");
+      out_valid[path] = 1;
+      out_origin[path * 3] = SA[at].x; out_origin[path * 3 + 1] = SA[at].y; out_origin[path * 3 + 2] = SA[at].z;
+      out_dir[path * 3] = SA[at].w; out_dir[path * 3 + 1] = SB[at].x; out_dir[path * 3 + 2] = SB[at].y;
+      out_tmax[path] = SB[at].z;
+      out_contrib[path * 3] = SC[at].x; out_contrib[path * 3 + 1] = SC[at].y; out_contrib[path * 3 + 2] = SC[at].z;
+    }
+  }
   return PTC_OK;
 }
 

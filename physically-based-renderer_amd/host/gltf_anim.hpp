@@ -7,7 +7,8 @@
 //   pose        node transforms at time t of an animation (channels translation / rotation / scale / weights; samplers LINEAR and STEP, rotations by slerp;
 //               CUBICSPLINE is sampled LINEARLY over its value entries, its tangents are not used), t clamped to the animation's range; then
 //               ptc_update_instance_matrix for every instance and ptc_update_mesh_pose for every deforming mesh, with the joint matrices
-//               inverse(global(mesh node)) global(joint) inverseBind.  The caller refits or rebuilds (or commits).
+//               inverse(global(mesh node)) global(joint) inverseBind.  The caller refits or rebuilds (or commits).  KHR_lights_punctual lights follow their nodes
+//               through ptc_update_light.
 // Node matrices for the instances are composed in binary32 exactly as load() composes them; joint matrices are composed in binary64 and rounded once.
 #pragma once
 #include "gltf_loader.hpp"
@@ -39,7 +40,7 @@ public:
     using namespace detail;
     const FlatScene fs = load(path_, scene_index, compose_parents);
     compose_ = compose_parents;
-    insts_.clear(); meshes_.clear();
+    insts_.clear(); meshes_.clear(); lights_.clear();
     std::vector<int> tex_id, mat_id;
     for (const Texture& t : fs.textures) { const int id = ptc_add_texture_rgba8(ctx, t.rgba.data(), t.w, t.h); if (id < 0) return id; tex_id.push_back(id); }
     auto tex = [&](int k) { return k < 0 ? -1 : tex_id[(size_t)k]; };
@@ -139,6 +140,11 @@ public:
         insts_.push_back({n, id});
       }
     }
+    for (const Light& l : fs.lights) {      // KHR_lights_punctual: the lights move with their nodes (apply)
+      const int id = ptc_add_light(ctx, &l.params);
+      if (id < 0) return id;
+      lights_.push_back({l.node, id, l.params});
+    }
     { const int rc = apply(ctx, bind, /*instances=*/false); if (rc < 0) return rc; }      // the bind pose and the asset's default weights
     if (bbox6) for (int k = 0; k < 3; ++k) { bbox6[k] = fs.bbox_lo[k]; bbox6[3 + k] = fs.bbox_hi[k]; }
     return (long long)fs.n_triangles;
@@ -155,6 +161,7 @@ private:
   struct Anim { std::vector<Channel> ch; float t_min = 0, t_max = 0; };
   struct MeshRec { std::array<long, 3> key; long node = -1, skin = -1; int ptc_mesh = -1, n_targets = 0; std::vector<long> joints; std::vector<double> ibm; std::vector<float> weights0; };
   struct InstRec { long node; int ptc_inst; };
+  struct LightRec { long node; int ptc_light; ptc_light_params params; };
   struct Local { bool matrix = false; float m[16]; float t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}, s[3] = {1, 1, 1}; };
   struct Pose { std::vector<Local> local; std::map<long, std::vector<float>> weights; };      // weights: per node with an animated `weights` channel
 
@@ -164,6 +171,7 @@ private:
   std::vector<Anim> anims_;
   std::vector<MeshRec> meshes_;
   std::vector<InstRec> insts_;
+  std::vector<LightRec> lights_;
   bool compose_ = true;
 
   void walk(long n, int depth, std::vector<long>& out) const {
@@ -312,6 +320,13 @@ private:
       for (const InstRec& I : insts_) {
         const detail::Mat4 m = world32(P, I.node);
         const int rc = ptc_update_instance_matrix(ctx, I.ptc_inst, m.data());
+        if (rc < 0) return rc;
+      }
+    if (instances)
+      for (const LightRec& L : lights_) {
+        ptc_light_params p = L.params;
+        detail::place_light(world32(P, L.node), p);
+        const int rc = ptc_update_light(ctx, L.ptc_light, &p);
         if (rc < 0) return rc;
       }
     for (const MeshRec& M : meshes_) {

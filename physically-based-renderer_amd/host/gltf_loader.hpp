@@ -154,11 +154,15 @@ struct Material { float base_color[4] = {1, 1, 1, 1}; float metallic = 1.0f, rou
 struct Texture { int w = 0, h = 0; std::vector<std::uint8_t> rgba; };
 struct Primitive { std::vector<ptc_vertex> vertices; std::vector<std::uint32_t> indices; int material = 0; };
 struct Instance { int primitive; std::array<float, 16> model; };   // column-major
+// KHR_lights_punctual: `params` is the light in world space (position = the node's origin, direction = its -Z axis after the composed transform, not yet normalised:
+// ptc_add_light does that); intensity = color x intensity; the cone angles have become cosines through libm
+struct Light { long node; ptc_light_params params; };
 struct FlatScene {
   std::vector<Texture> textures;        // decoded images, one per glTF image that a material references (first-use order)
   std::vector<Material> materials;      // glTF materials in index order, plus a trailing default one if any primitive needs it
   std::vector<Primitive> primitives;    // one per glTF mesh primitive, mesh order then primitive order
   std::vector<Instance> instances;      // scene traversal order (depth-first, children before the node's own mesh — Scene.cpp:77-82)
+  std::vector<Light> lights;            // KHR_lights_punctual lights of the scene's nodes, in the order the traversal first reaches their nodes
   float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};   // world-space bounds of all instanced vertices
   std::uint64_t n_triangles = 0;
 };
@@ -237,6 +241,11 @@ inline Mat4 from_trs(const float t[3], const float q_wxyz[4], const float s[3]) 
   for (int c = 0; c < 3; ++c) { for (int k = 0; k < 3; ++k) m[c * 4 + k] = R[c * 3 + k] * s[c]; m[c * 4 + 3] = 0.0f; }
   m[12] = t[0]; m[13] = t[1]; m[14] = t[2]; m[15] = 1.0f;
   return m;
+}
+
+// a light's node transform -> its world-space position and direction (the node's -Z axis)
+inline void place_light(const Mat4& world, ptc_light_params& p) {
+  for (int k = 0; k < 3; ++k) { p.position[k] = world[12 + (size_t)k]; p.direction[k] = -world[8 + (size_t)k]; }
 }
 
 struct Doc {
@@ -583,6 +592,31 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
   long si = scene_index >= 0 ? scene_index : d.root.integer("scene", 0);
   if (scenes.empty()) throw std::runtime_error("asset has no scenes");
   if (si < 0 || (size_t)si >= scenes.size()) throw std::runtime_error("scene index out of range");
+  // ---- KHR_lights_punctual: the asset's lights, referenced by nodes ----
+  std::vector<ptc_light_params> light_defs;
+  if (const JValue* ext = d.root.get("extensions"))
+    if (const JValue* kl = ext->get("KHR_lights_punctual"))
+      for (const JValue& l : kl->array("lights")) {
+        ptc_light_params p;
+        ptc_light_default_params(&p);
+        const std::string type = l.string("type");
+        if (type == "point") p.type = PTC_LIGHT_POINT;
+        else if (type == "spot") p.type = PTC_LIGHT_SPOT;
+        else if (type == "directional") p.type = PTC_LIGHT_DIRECTIONAL;
+        else throw std::runtime_error("KHR_lights_punctual: unknown light type '" + type + "'");
+        float color[3] = {1, 1, 1};
+        const auto& col = l.array("color");
+        for (size_t k = 0; k < 3 && k < col.size(); ++k) color[k] = (float)col[k].num;
+        const float intensity = (float)l.number("intensity", 1.0);
+        for (int k = 0; k < 3; ++k) p.intensity[k] = intensity * color[k];
+        p.range = (float)l.number("range", 0.0);
+        if (p.type == PTC_LIGHT_SPOT) {
+          double inner = 0.0, outer = 0.78539816339744830962;
+          if (const JValue* sp = l.get("spot")) { inner = sp->number("innerConeAngle", inner); outer = sp->number("outerConeAngle", outer); }
+          p.cos_inner = (float)std::cos(inner); p.cos_outer = (float)std::cos(outer);
+        }
+        light_defs.push_back(p);
+      }
   bool first_vertex = true;
   struct Frame { long node; Mat4 parent; int depth; };
   for (const JValue& rootIdx : scenes[(size_t)si].array("nodes")) {
@@ -608,6 +642,14 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
       }
       const Mat4 world = compose_parents ? mul(fr.parent, local) : local;
       if (!expanded) {
+        if (const JValue* ext = n.get("extensions"))
+          if (const JValue* kl = ext->get("KHR_lights_punctual")) {
+            const long li = kl->integer("light", -1);
+            if (li < 0 || (size_t)li >= light_defs.size()) throw std::runtime_error("KHR_lights_punctual: light index out of range");
+            Light L{fr.node, light_defs[(size_t)li]};
+            place_light(world, L.params);
+            out.lights.push_back(L);
+          }
         stack.push_back({Frame{fr.node, fr.parent, fr.depth}, true});
         const auto& ch = n.array("children");
         for (size_t k = ch.size(); k-- > 0;) stack.push_back({Frame{(long)ch[k].num, world, fr.depth + 1}, false});
@@ -655,6 +697,10 @@ inline int upload(ptc_ctx* ctx, const FlatScene& s) {
   }
   for (const Instance& i : s.instances) {
     const int rc = ptc_add_instance_matrix(ctx, mesh_id[(size_t)i.primitive], i.model.data());
+    if (rc < 0) return rc;
+  }
+  for (const Light& l : s.lights) {
+    const int rc = ptc_add_light(ctx, &l.params);
     if (rc < 0) return rc;
   }
   return PTC_OK;

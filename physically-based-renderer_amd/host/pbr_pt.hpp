@@ -117,6 +117,14 @@ public:
     setCameraLens(ptc_lens_params{apertureRadius, focusDistance, blades, rotation});
   }
   auto cameraLens() const -> ptc_lens_params { ptc_lens_params p; ptc_get_camera_lens(_ctx, &p); return p; }
+  // punctual lights (ptc_add_light ...): point / spot / directional, sampled by the path integrator in a pass of its own.  They need no commit and no
+  // refit; a frame sees the lights recorded when it began.  Dropped by beginScene
+  static auto lightDefaults() -> ptc_light_params { ptc_light_params p; ptc_light_default_params(&p); return p; }
+  auto addLight(ptc_light_params const& light) -> int { return ck(ptc_add_light(_ctx, &light)); }
+  auto updateLight(int id, ptc_light_params const& light) -> void { ck(ptc_update_light(_ctx, id, &light)); }
+  auto light(int id) const -> ptc_light_params { ptc_light_params p = lightDefaults(); ptc_get_light(_ctx, id, &p); return p; }
+  auto lightCount() const -> int { return ptc_light_count(_ctx); }
+  auto clearLights() -> void { ck(ptc_clear_lights(_ctx)); }
   // the view depth of what pixel (x, y)'s centre sees, 0 on a miss: needs frameGuides() of the current frame
   auto focusDistanceAtPixel(int x, int y) -> float { float d = 0.0f; ck(ptc_focus_distance_at_pixel(_ctx, x, y, &d)); return d; }
   // PTC_BVH_SAH (default) or PTC_BVH_LBVH, for the scene being described

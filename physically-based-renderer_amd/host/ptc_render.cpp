@@ -4,6 +4,11 @@
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
+//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights]
+// --light (repeatable): a punctual light (ptc_add_light), path integrator only.  point / spot: position, intensity rgb in W/sr, an optional range; a spot points along
+// dx,dy,dz with full intensity inside inner_deg of the axis and none outside outer_deg.  sun: a directional light travelling along dx,dy,dz, rgb = the irradiance of a
+// facing surface.  A --gltf scene brings the KHR_lights_punctual lights of its nodes (with --animation they move with them); --no-gltf-lights drops those.
+// Bad values are reported before any device work.
 // --aperture R: the thin lens (ptc_set_camera_lens) with aperture radius R in world units — depth of field, path integrator only.  --blades N: a regular polygon
 // of 3..16 sides instead of the disk, --aperture-rotation T: its rotation in turns, [0, 1).  --focus D: the view depth of the plane of focus (default 1);
 // --focus-pixel X,Y: focus on what that pixel's centre sees — the guides are traced once before the render and ptc_focus_distance_at_pixel is taken (a miss is
@@ -40,6 +45,57 @@
 
 namespace {
 using V3 = std::array<float, 3>;
+
+// --light SPEC -> ptc_light_params; throws with the expected form on anything else
+ptc_light_params parseLight(const std::string& spec) {
+  std::vector<std::vector<float>> f;
+  std::string kind;
+  size_t at = 0;
+  for (int part = 0; at <= spec.size(); ++part) {
+    const size_t e = std::min(spec.find(':', at), spec.size());
+    const std::string tok = spec.substr(at, e - at);
+    if (part == 0) kind = tok;
+    else {
+      f.emplace_back();
+      size_t p = 0;
+      while (p <= tok.size()) {
+        const size_t c = std::min(tok.find(',', p), tok.size());
+        char* end = nullptr;
+        const std::string num = tok.substr(p, c - p);
+        const float v = std::strtof(num.c_str(), &end);
+        if (num.empty() || *end) throw std::runtime_error("--light " + spec + ": '" + num + "' is not a number");
+        f.back().push_back(v);
+        p = c + 1;
+      }
+    }
+    at = e + 1;
+  }
+  auto is = [&](size_t i, size_t n) { return i < f.size() && f[i].size() == n; };
+  ptc_light_params p;
+  ptc_light_default_params(&p);
+  const double deg = 3.14159265358979323846 / 180.0;
+  if (kind == "point" && (f.size() == 2 || f.size() == 3) && is(0, 3) && is(1, 3) && (f.size() == 2 || is(2, 1))) {
+    p.type = PTC_LIGHT_POINT;
+    for (int k = 0; k < 3; ++k) { p.position[k] = f[0][(size_t)k]; p.intensity[k] = f[1][(size_t)k]; }
+    if (f.size() == 3) p.range = f[2][0];
+  } else if (kind == "spot" && (f.size() == 4 || f.size() == 5) && is(0, 3) && is(1, 3) && is(2, 3) && is(3, 2) && (f.size() == 4 || is(4, 1))) {
+    p.type = PTC_LIGHT_SPOT;
+    for (int k = 0; k < 3; ++k) { p.position[k] = f[0][(size_t)k]; p.direction[k] = f[1][(size_t)k]; p.intensity[k] = f[2][(size_t)k]; }
+    p.cos_inner = (float)std::cos((double)f[3][0] * deg); p.cos_outer = (float)std::cos((double)f[3][1] * deg);
+    if (!(f[3][0] >= 0.0f && f[3][0] < f[3][1] && f[3][1] <= 180.0f)) throw std::runtime_error("--light " + spec + ": 0 <= inner_deg < outer_deg <= 180");
+    if (f.size() == 5) p.range = f[4][0];
+  } else if (kind == "sun" && f.size() == 2 && is(0, 3) && is(1, 3)) {
+    p.type = PTC_LIGHT_DIRECTIONAL;
+    for (int k = 0; k < 3; ++k) { p.direction[k] = f[0][(size_t)k]; p.intensity[k] = f[1][(size_t)k]; }
+  } else
+    throw std::runtime_error("--light " + spec + ": point:x,y,z:r,g,b[:range] | spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range] | sun:dx,dy,dz:r,g,b");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(p.position[k]) || !std::isfinite(p.direction[k]) || !(p.intensity[k] >= 0.0f) || !std::isfinite(p.intensity[k])) throw std::runtime_error("--light " + spec + ": finite values, intensity >= 0");
+  if (!(p.range >= 0.0f) || !std::isfinite(p.range)) throw std::runtime_error("--light " + spec + ": a finite range >= 0");
+  if (p.type != PTC_LIGHT_POINT && p.direction[0] == 0.0f && p.direction[1] == 0.0f && p.direction[2] == 0.0f) throw std::runtime_error("--light " + spec + ": the direction is zero");
+  if (p.type == PTC_LIGHT_SPOT && !(p.cos_inner > p.cos_outer)) throw std::runtime_error("--light " + spec + ": the cone angles are too close");
+  return p;
+}
 
 pbr::MeshBuilder::Primitive quad(V3 a, V3 b, V3 c, V3 d, int material) {   // CCW seen from the front
   V3 e1{b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2{c[0] - a[0], c[1] - a[1], c[2] - a[2]};
@@ -143,6 +199,9 @@ int main(int argc, char** argv) {
   int focusX = 0, focusY = 0;
   int animation = -1;                        // --animation: pose the glTF scene along this animation ...
   double animTime = 0.0;                     // ... at --time seconds, before the commit
+  std::vector<std::string> lightSpecs;       // --light, in order
+  std::vector<ptc_light_params> lights;
+  bool noGltfLights = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -160,6 +219,7 @@ int main(int argc, char** argv) {
     else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
+    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true;
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -191,6 +251,15 @@ int main(int argc, char** argv) {
       if (!(lens.rotation >= 0.0f && lens.rotation < 1.0f)) throw std::runtime_error("--aperture-rotation T: turns in [0, 1)");
       if (haveFocusPixel && (focusX < 0 || focusY < 0 || focusX >= w || focusY >= h)) throw std::runtime_error("--focus-pixel X,Y: a pixel of the image");
     }
+    for (const std::string& sp : lightSpecs) lights.push_back(parseLight(sp));
+    if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
+    if (noGltfLights && gltf.empty()) throw std::runtime_error("--no-gltf-lights drops the lights of a --gltf scene");
+    // after the scene: the punctual lights (they need no commit) — the asset's own unless dropped, then the command line's
+    auto applyLights = [&](pbr::PathTraceRenderSystem& rs) {
+      if (noGltfLights && ptc_clear_lights(rs.handle()) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+      for (const ptc_light_params& l : lights)
+        if (ptc_add_light(rs.handle(), &l) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+    };
     // after the commit: the lens, focused on a pixel if asked (one guide pass of a one-sample frame; the render that follows begins its own frame)
     auto applyLens = [&](pbr::PathTraceRenderSystem& rs) {
       if (haveFocusPixel) {
@@ -262,6 +331,7 @@ int main(int argc, char** argv) {
     if (gpus == 0) {
       single.reset(new pbr::PathTraceRenderSystem(device));
       buildScene(*single);
+      applyLights(*single);
       applyLens(*single);
       if (denoiseSampled) single->setSampleCovariance(true);
       img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : denoiseSampled ? single->renderWithStatistics(w, h, spp, seed, bounces)
@@ -271,6 +341,7 @@ int main(int argc, char** argv) {
       for (int i = 0; i < gpus; ++i) ids.push_back(device + i);
       group.reset(new pbr::DeviceGroup(ids));
       buildScene(group->device(0));
+      applyLights(group->device(0)); // the group commit and the group render give every member device 0's lights
       applyLens(group->device(0));   // the group commit copies the lens with the camera
       group->commitScene();          // one flatten + BVH build on the host, uploaded to every device
       img = group->render(w, h, spp, seed, bounces, integrator);

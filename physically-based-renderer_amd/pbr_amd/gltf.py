@@ -313,7 +313,7 @@ def _pad4(b: bytes, fill: bytes = b"\x00") -> bytes:
 
 
 def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = False, nodes=None, skins=None, animations=None,
-              joints_type: str = "u16", weights_type: str = "f32") -> None:
+              joints_type: str = "u16", weights_type: str = "f32", lights=None) -> None:
     """SceneDesc → GLB.  One glTF mesh per MeshDesc (one primitive each), one node per instance (TRS, or `matrix`
     when the instance carries one).  `nodes`: optional explicit node list (dicts with mesh/translation/rotation/
     scale/matrix/children) + root list, to exercise hierarchies: nodes=(node_dicts, root_indices).
@@ -321,7 +321,10 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
     Deformation: a MeshDesc with morph_dpos (/ morph_dnormal / morph_dtangent, morph_weights) gets `targets` (and `weights`), one with joints / weights gets
     JOINTS_0 (joints_type "u8" | "u16") and WEIGHTS_0 (weights_type "f32", or normalised "u8" | "u16").  skins: [{"joints": [node, ...],
     "inverseBindMatrices": (n, 16) column-major or None}] (a node dict names its skin with "skin").  animations: [{"channels": [{"node", "path"
-    ("translation" | "rotation" (x, y, z, w) | "scale" | "weights"), "times", "values", "interpolation" ("LINEAR" | "STEP" | "CUBICSPLINE")}]}]."""
+    ("translation" | "rotation" (x, y, z, w) | "scale" | "weights"), "times", "values", "interpolation" ("LINEAR" | "STEP" | "CUBICSPLINE")}]}].
+    lights: KHR_lights_punctual — [{"type" ("point" | "spot" | "directional"), "color", "intensity", "range", "inner", "outer" (cone angles, radians)}], each either on an
+    existing node ("node": its index) or on a node of its own, appended behind the others in list order, with "translation", "rotation" (w, x, y, z), "scale" and "parent"
+    (the index IN `lights` of the light whose node it hangs under; none: a root).  A light shines along its node's -Z."""
     blob = bytearray()
     views, accessors, meshes = [], [], []
 
@@ -425,6 +428,39 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
             roots.append(k)
     else:
         node_list, roots = nodes
+    light_defs = []
+    if lights:
+        node_list, roots = [dict(n) for n in node_list], list(roots)
+        own = {}      # index in `lights` -> its own node
+        for k, l in enumerate(lights):
+            g = {"type": l["type"]}
+            if "color" in l:
+                g["color"] = [float(x) for x in l["color"]]
+            if "intensity" in l:
+                g["intensity"] = float(l["intensity"])
+            if l.get("range"):
+                g["range"] = float(l["range"])
+            if l["type"] == "spot":
+                g["spot"] = {kk: float(l[src]) for kk, src in (("innerConeAngle", "inner"), ("outerConeAngle", "outer")) if src in l}
+            light_defs.append(g)
+            if "node" in l:
+                nd = node_list[int(l["node"])]
+            else:
+                nd = {"name": f"light{k}"}
+                if "translation" in l:
+                    nd["translation"] = [float(x) for x in l["translation"]]
+                if "rotation" in l:
+                    q = l["rotation"]
+                    nd["rotation"] = [float(q[1]), float(q[2]), float(q[3]), float(q[0])]
+                if "scale" in l:
+                    nd["scale"] = [float(x) for x in l["scale"]]
+                node_list.append(nd)
+                own[k] = len(node_list) - 1
+                if l.get("parent") is not None:
+                    node_list[own[int(l["parent"])]].setdefault("children", []).append(own[k])
+                else:
+                    roots.append(own[k])
+            nd.setdefault("extensions", {})["KHR_lights_punctual"] = {"light": k}
     doc = {"asset": {"version": "2.0", "generator": "pbr_amd.gltf.write_glb"}, "scene": 0, "scenes": [{"nodes": list(roots)}], "nodes": node_list,
            "meshes": meshes, "materials": mats, "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(blob)}]}
     if skins:
@@ -455,6 +491,9 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
         doc["textures"] = [{"source": k, "sampler": 0} for k in range(len(images))]
     if any("extensions" in g for g in mats):
         doc["extensionsUsed"] = ["KHR_materials_emissive_strength"]
+    if light_defs:
+        doc["extensions"] = {"KHR_lights_punctual": {"lights": light_defs}}
+        doc["extensionsUsed"] = doc.get("extensionsUsed", []) + ["KHR_lights_punctual"]
     js = _pad4(json.dumps(doc, separators=(",", ":")).encode(), b" ")
     bn = _pad4(bytes(blob))
     with open(path, "wb") as f:

@@ -26,6 +26,10 @@ INTEGRATOR_RASTER_COMPAT = 1
 INTEGRATOR_RASTER_GBUFFER16 = 2   # raster-compat lit from the reference's G-buffer formats (RGBA16F P/N, UNORM16 albedo)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
+LIGHT_POINT = 0
+LIGHT_SPOT = 1
+LIGHT_DIRECTIONAL = 2
+MAX_LIGHTS = 256
 GUIDE_ALBEDO = 0          # (albedo rgb, class: 0 miss, 1 surface, 2 emitter)
 GUIDE_NORMAL_DEPTH = 1    # (unit vertex normal, t along the unit camera ray)
 OUTPUT_RADIANCE = 0
@@ -53,6 +57,8 @@ ABI_SYMBOLS = [
     "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
     "ptc_mesh_set_morph_targets", "ptc_mesh_set_skin", "ptc_update_mesh_pose", "ptc_update_mesh_vertices", "ptc_debug_get_mesh_vertices",
     "ptc_lens_default_params", "ptc_set_camera_lens", "ptc_get_camera_lens", "ptc_focus_distance_at_pixel", "ptc_debug_lens_sample", "ptc_debug_camera_rays",
+    "ptc_light_default_params", "ptc_add_light", "ptc_update_light", "ptc_get_light", "ptc_light_count", "ptc_clear_lights",
+    "ptc_debug_light_sample", "ptc_debug_get_light_table", "ptc_debug_punctual_nee",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
 
@@ -107,6 +113,32 @@ class PtcLensParams(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PtcLightParams(C.Structure):
+    _fields_ = [("type", C.c_int), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3), ("range", C.c_float),
+                ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("sampling_weight", C.c_float)]
+
+    def as_dict(self):
+        return {k: (tuple(getattr(self, k)) if k in ("position", "direction", "intensity") else getattr(self, k)) for k, _ in self._fields_}
+
+
+_LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
+
+
+def light_params(type="point", position=(0, 0, 0), direction=(0, 0, -1), intensity=(1, 1, 1), range=0.0, cos_inner=1.0, cos_outer=0.70710678, sampling_weight=1.0):
+    """A ptc_light_params: `type` is a name (point, spot, directional) or a LIGHT_* value; an object with these attributes (scene.LightDesc) is taken by light_params_of."""
+    t = _LIGHT_TYPES[type] if isinstance(type, str) else int(type)
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    return PtcLightParams(t, f3(position), f3(direction), f3(intensity), float(range), float(cos_inner), float(cos_outer), float(sampling_weight))
+
+
+def light_params_of(l):
+    if isinstance(l, PtcLightParams):
+        return l
+    if isinstance(l, dict):
+        return light_params(**l)
+    return light_params(l.type, l.position, l.direction, l.intensity, l.range, l.cos_inner, l.cos_outer, l.sampling_weight)
 
 
 class PtcError(RuntimeError):
@@ -223,6 +255,17 @@ def load_library():
     L.ptc_focus_distance_at_pixel.argtypes = [vp, C.c_int, C.c_int, fp]
     L.ptc_debug_lens_sample.argtypes = [C.POINTER(PtcLensParams), C.c_float, C.c_float, fp]
     L.ptc_debug_camera_rays.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, u32p, C.c_uint32, fp, fp]
+    lp = C.POINTER(PtcLightParams)
+    L.ptc_light_default_params.argtypes = [lp]
+    L.ptc_light_default_params.restype = None
+    L.ptc_add_light.argtypes = [vp, lp]
+    L.ptc_update_light.argtypes = [vp, C.c_int, lp]
+    L.ptc_get_light.argtypes = [vp, C.c_int, lp]
+    L.ptc_light_count.argtypes = [vp]
+    L.ptc_clear_lights.argtypes = [vp]
+    L.ptc_debug_light_sample.argtypes = [lp, fp, fp, fp, fp]
+    L.ptc_debug_get_light_table.argtypes = [vp, u32p, fp, fp]
+    L.ptc_debug_punctual_nee.argtypes = [vp, fp, fp, u32p, C.c_uint32, C.c_uint32, u8p, fp, fp, fp, fp]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -267,6 +310,30 @@ def lens_sample(u1, u2, aperture_radius=1.0, blades=0, rotation=0.0):
             raise PtcError(f"lens_sample: bad lens parameters or u outside [0, 1): {p.as_dict()}, ({a[i]}, {b[i]})")
         out[i] = xy[0], xy[1]
     return out if np.ndim(u1) else (float(out[0, 0]), float(out[0, 1]))
+
+
+def light_default_params():
+    p = PtcLightParams()
+    load_library().ptc_light_default_params(C.byref(p))
+    return p.as_dict()
+
+
+def light_sample(light, P):
+    """ptc_debug_light_sample: the host's evaluation of csrc/pt_lights.h for one light (light_params / LightDesc / dict) and the points P (n, 3):
+    (has_sample (n,) bool, wi (n, 3), dist (n,), Li (n, 3)), float32; rows without a sample are 0."""
+    L = load_library()
+    p = light_params_of(light)
+    pts = np.ascontiguousarray(np.atleast_2d(np.asarray(P, np.float32)))
+    n = pts.shape[0]
+    ok, wi, dist, Li = np.zeros(n, bool), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+    w, li, d = (C.c_float * 3)(), (C.c_float * 3)(), C.c_float(0)
+    for i in range(n):
+        rc = L.ptc_debug_light_sample(C.byref(p), pts[i].ctypes.data_as(C.POINTER(C.c_float)), w, C.byref(d), li)
+        if rc < 0:
+            raise PtcError(f"light_sample: bad light parameters: {p.as_dict()}")
+        if rc:
+            ok[i], wi[i], dist[i], Li[i] = True, tuple(w), d.value, tuple(li)
+    return ok, wi, dist, Li
 
 
 def comm_unique_id() -> bytes:
@@ -343,8 +410,56 @@ class PathTracer:
         c = desc.camera
         self._ck(L.ptc_set_camera(h, _f(c.position)[1], _f(c.target)[1], c.fov_y, c.aspect))
         self.set_camera_lens(getattr(c, "aperture_radius", 0.0), getattr(c, "focus_distance", 1.0), getattr(c, "blades", 0), getattr(c, "aperture_rotation", 0.0))
+        for l in getattr(desc, "lights", []):
+            self.add_light(l)
         self._ck(L.ptc_scene_commit(h))
         return self
+
+    # ---- punctual lights (csrc/pt_lights.h) ---------------------------------------------------------------
+    def add_light(self, light=None, **kw):
+        """ptc_add_light: a light_params(...) / scene.LightDesc / dict, or the fields as keywords.  Returns the light's id.  Needs no commit; a frame sees the
+        lights recorded when it began."""
+        return self._ck(self._L.ptc_add_light(self._h, C.byref(light_params_of(light) if light is not None else light_params(**kw))))
+
+    def update_light(self, light_id, light=None, **kw):
+        self._ck(self._L.ptc_update_light(self._h, int(light_id), C.byref(light_params_of(light) if light is not None else light_params(**kw))))
+        return self
+
+    def get_light(self, light_id):
+        p = PtcLightParams()
+        self._ck(self._L.ptc_get_light(self._h, int(light_id), C.byref(p)))
+        return p.as_dict()
+
+    def light_count(self):
+        return self._ck(self._L.ptc_light_count(self._h))
+
+    def clear_lights(self):
+        self._ck(self._L.ptc_clear_lights(self._h))
+        return self
+
+    def light_table(self):
+        """ptc_debug_get_light_table: (records (n, 16) float32 — word 3 holds the type's int bits —, cdf (n,) float32) as a frame would upload them."""
+        n = C.c_uint32()
+        self._ck(self._L.ptc_debug_get_light_table(self._h, C.byref(n), None, None))
+        rec, cdf = np.zeros((n.value, 16), np.float32), np.zeros(n.value, np.float32)
+        if n.value:
+            self._ck(self._L.ptc_debug_get_light_table(self._h, None, rec.ctypes.data_as(C.POINTER(C.c_float)), cdf.ctypes.data_as(C.POINTER(C.c_float))))
+        return rec, cdf
+
+    def punctual_nee(self, origins, dirs, keys, bounce=0):
+        """ptc_debug_punctual_nee: explicit rays (throughput 1, path id = index, RNG key keys[i]) through k_trace_closest and k_shade_punctual at `bounce`:
+        (valid (n,) bool, origin (n, 3), dir (n, 3), tmax (n,), contrib (n, 3)) of the shadow record each ray produced."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = o.shape[0]
+        assert d.shape[0] == n and k.size == n
+        valid = np.zeros(n, np.uint8)
+        so, sd, tm, ct = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        fpt = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._ck(self._L.ptc_debug_punctual_nee(self._h, op, dp, k.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(bounce), valid.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                fpt(so), fpt(sd), fpt(tm), fpt(ct)))
+        return valid.astype(bool), so, sd, tm, ct
 
     def set_camera(self, position, target, fov_y, aspect):
         self._ck(self._L.ptc_set_camera(self._h, _f(position)[1], _f(target)[1], fov_y, aspect))

@@ -209,6 +209,21 @@ class CameraDesc:
 
 
 @dataclasses.dataclass
+class LightDesc:
+    """A punctual light (ptc_light_params; glTF KHR_lights_punctual).  type: "point", "spot" or "directional".  intensity: rgb, W/sr for point and spot (glTF
+    colour x candela), irradiance for directional (colour x lux).  direction: the axis a spot points along / the way a directional light travels.  The cone of a
+    spot is given by the cosines of its inner and outer angles.  range 0 = none."""
+    type: str = "point"
+    position: Sequence[float] = (0.0, 0.0, 0.0)
+    direction: Sequence[float] = (0.0, 0.0, -1.0)
+    intensity: Sequence[float] = (1.0, 1.0, 1.0)
+    range: float = 0.0
+    cos_inner: float = 1.0
+    cos_outer: float = 0.70710678
+    sampling_weight: float = 1.0
+
+
+@dataclasses.dataclass
 class SceneDesc:
     materials: List[Material]
     meshes: List[MeshDesc]
@@ -219,6 +234,7 @@ class SceneDesc:
     env: Optional[np.ndarray] = None  # lat-long RGB32F environment map, (h, w, 3) float32, row 0 = +y
     texture_filter: str = "nearest"  # "nearest" (the reference's default-constructed sampler) or "linear" (bilinear, REPEAT)
     bvh_builder: "str | None" = None  # "sah" (binned surface-area splits), "lbvh" (Morton-code radix tree) or None = the context's default
+    lights: List[LightDesc] = dataclasses.field(default_factory=list)  # punctual lights; loading the description adds them (ptc_add_light)
 
     @property
     def n_triangles(self) -> int:
