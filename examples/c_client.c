@@ -51,6 +51,7 @@ int main(int argc, char** argv) {
     lamp.intensity[0] = 2.0f; lamp.intensity[1] = 1.6f; lamp.intensity[2] = 1.2f;
     CHECK(ptc_add_light(ctx, &lamp));
   }
+  CHECK(ptc_set_display(ctx, NULL));                   /* the display transform's defaults: no exposure change, ACES, gamma 2.2 — what ptc_tonemap_rgba8 applies */
   CHECK(ptc_scene_commit(ctx));
   ptc_stats st;
   CHECK(ptc_get_stats(ctx, &st));

@@ -14,6 +14,9 @@
 // usage: viewer_shim DEVICE [frames [rebuild_ratio [temporal]]]    the word "temporal" opts in to the temporal path: every displayed frame is a frame of its own
 //                                       (1 spp, its own seed) whose result is blended into the reprojected history (ptc_temporal_accumulate) and filtered
 //                                       (ptc_denoise_accumulated) — for a scene or camera that moves every frame, where a progressive frame never gets past 1 spp.
+//                                       the word "exposure" (after it, or in its place) opts in to the display transform: every displayed frame is metered on the device
+//                                       (ptc_meter_exposure, the eye adapting at 0.1 per frame) and handed on exposed (ptc_display_rgba16f) — for a scene lit in
+//                                       physical units, whose radiance the HdrImage's halves cannot hold.
 //                                       DEVICE -1 = description only (PTC_DEVICE_NONE): the scene half runs, the render half reports
 //                                       "no device" and the program still exits 0 — that is what the CPU test runs.
 #include <pbr_pt.hpp>
@@ -57,8 +60,8 @@ inline std::vector<int> uploadNode(ptc_ctx* ctx, std::vector<int> const& meshIds
 // App::recordCommands: was `_pbrSystem.render(cmdBuffer, _scene, _gBuffer, _hdrImage.getImage(), extent);`
 class Frame {
 public:
-  Frame(ptc_ctx* ctx, int w, int h, int sppBudget, std::uint64_t seed, bool temporal = false)
-      : _ctx(ctx), _w(w), _h(h), _budget(sppBudget), _seed(seed), _temporal(temporal), _staging16((std::size_t)w * h * 4) {}
+  Frame(ptc_ctx* ctx, int w, int h, int sppBudget, std::uint64_t seed, bool temporal = false, bool exposure = false)
+      : _ctx(ctx), _w(w), _h(h), _budget(sppBudget), _seed(seed), _temporal(temporal), _exposure(exposure), _staging16((std::size_t)w * h * 4) {}
   // one displayed frame; returns false when the context has no device (description-only run)
   bool record(pbr::ViewerCamera const& cam, bool sceneOrCameraChanged) {
     if (_temporal) return recordTemporal(cam);
@@ -76,7 +79,7 @@ public:
     ck(_ctx, ptc_frame_resolve(_ctx));                        // sum / samples so far
     ck(_ctx, ptc_denoise(_ctx, nullptr));                     // the few-sample image is mostly noise: filter it along the guides (default parameters) ...
     ck(_ctx, ptc_select_output(_ctx, PTC_OUTPUT_DENOISED));   // ... and hand the denoised image on (ptc_frame_begin selects the plain radiance again)
-    ck(_ctx, ptc_read_radiance_rgba16f(_ctx, _staging16.data()));   // the HdrImage's own format (RGBA16F); the TransferStager copies it into _hdrImage
+    handOff();
     return true;
   }
   // App::update rotates every node a little each frame, without bound (App.cpp:306-313): new TRS for the instances, then a REFIT (0.5 ms at 250 k triangles) —
@@ -109,8 +112,15 @@ public:
     ck(_ctx, ptc_temporal_accumulate(_ctx, nullptr));          // reproject the history through this frame's guides and blend the sample in (default parameters)
     ck(_ctx, ptc_denoise_accumulated(_ctx, nullptr));          // the filter over the accumulated image, with the temporal variance where the history is long enough
     ck(_ctx, ptc_select_output(_ctx, PTC_OUTPUT_DENOISED));
-    ck(_ctx, ptc_read_radiance_rgba16f(_ctx, _staging16.data()));
+    handOff();
     return true;
+  }
+  // the HdrImage's own format (RGBA16F); the TransferStager copies it into _hdrImage.  With exposure: the served image is metered and converted at the metered
+  // scale, both queued behind the filter — the host waits once, for the copy
+  void handOff() {
+    if (!_exposure) { ck(_ctx, ptc_read_radiance_rgba16f(_ctx, _staging16.data())); return; }
+    ck(_ctx, ptc_meter_exposure(_ctx));
+    ck(_ctx, ptc_display_rgba16f(_ctx, _staging16.data()));
   }
   [[nodiscard]] auto staging() const -> std::vector<std::uint16_t> const& { return _staging16; }
   [[nodiscard]] auto rebuilds() const -> int { return _rebuilds; }
@@ -120,7 +130,7 @@ private:
   ptc_ctx* _ctx;
   int _w, _h, _budget;
   std::uint64_t _seed;
-  bool _temporal = false;
+  bool _temporal = false, _exposure = false;
   std::uint64_t _shown = 0;
   bool _begun = false;
   int _rebuilds = 0;
@@ -134,9 +144,17 @@ int main(int argc, char** argv) {
   const int frames = argc > 2 ? std::atoi(argv[2]) : 4;
   const double rebuildRatio = argc > 3 ? std::atof(argv[3]) : 1.2;
   const bool temporal = argc > 4 && std::strcmp(argv[4], "temporal") == 0;
+  bool exposure = false;
+  for (int i = 4; i < argc; ++i) exposure = exposure || std::strcmp(argv[i], "exposure") == 0;
   ptc_ctx* ctx = ptc_create(device);
   if (!ctx) { std::fprintf(stderr, "viewer_shim: %s\n", ptc_last_error(nullptr)); return 1; }
   try {
+    if (exposure) {                                            // a context setting: it needs no device and stays across ptc_scene_begin
+      ptc_display_params dp;
+      ptc_display_default_params(&dp);
+      dp.auto_exposure = 1; dp.adapt_rate = 0.1f;
+      shim::ck(ctx, ptc_set_display(ctx, &dp));
+    }
     // ---- App::loadAsset: ptc_scene_begin before Asset::loadScene, ptc_scene_commit after it (App.cpp:161-175) ----
     shim::ck(ctx, ptc_scene_begin(ctx));
     pbr::MaterialData wall; wall.color = {0.8f, 0.3f, 0.2f, 1.0f};
@@ -161,7 +179,7 @@ int main(int argc, char** argv) {
     ptc_stats st;
     shim::ck(ctx, ptc_get_stats(ctx, &st));
     // ---- App::run: displayed frames ----
-    shim::Frame frame(ctx, 160, 90, 64, 7, temporal);
+    shim::Frame frame(ctx, 160, 90, 64, 7, temporal, exposure);
     bool rendered = true;
     double sum = 0.0;
     for (int f = 0; f < frames && rendered; ++f) {
@@ -178,6 +196,11 @@ int main(int argc, char** argv) {
     std::printf("{\"device\": %d, \"triangles\": %u, \"rendered\": %s, \"frames\": %d, \"staging_sum\": %.0f, \"rebuilds\": %d}\n", device, st.n_triangles, rendered ? "true" : "false", frames, sum,
                 frame.rebuilds());
     if (temporal) std::printf("{\"temporal\": true, \"temporal_frames_begun\": %llu}\n", (unsigned long long)frame.shown());
+    if (exposure && rendered) {
+      float E = 0.0f, adapted = 0.0f;
+      shim::ck(ctx, ptc_get_exposure(ctx, &E, &adapted, nullptr, nullptr, nullptr));
+      std::printf("{\"exposure\": true, \"exposure_scale\": %.9g, \"adapted_luminance\": %.9g}\n", (double)E, (double)adapted);
+    }
     if (!rendered) std::printf("viewer_shim: no device (PTC_DEVICE_NONE): scene described and committed, render calls answered PTC_E_DEVICE\n");
   } catch (std::exception const& e) {
     std::fprintf(stderr, "viewer_shim: %s\n", e.what());

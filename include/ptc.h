@@ -544,6 +544,60 @@ int  ptc_read_temporal_rgba32f(ptc_ctx*, int which, float* out);      /* w*h*4 f
 int  ptc_denoise_accumulated(ptc_ctx*, const ptc_denoise_params*);    /* NULL: the defaults */
 int  ptc_get_temporal_seconds(ptc_ctx*, double* accumulate);
 
+/* ---- display transform: metered exposure, tone-mapping operators, transfer functions (csrc/pt_display.h) -----------
+ * The images above are scene-referred radiance in physical units: a sun of 100 000 lx is worth 100 000.  ptc_tonemap_rgba8 and the RGBA16F read-backs take that
+ * radiance as it is (they ignore everything here); these calls expose it first.  Nothing here changes what a context that never calls them computes, and nothing
+ * here writes the radiance, denoised or accumulated buffers, the frame's sums, its ptc_stats or the temporal history.
+ *
+ * ptc_set_display: a setting of the context (it needs no device), kept across ptc_scene_begin.  NULL: the defaults.  PTC_E_ARG, and nothing changed, for a value
+ *   outside the ranges in the struct's comments.
+ * ptc_meter_exposure: meters the image ptc_select_output serves — radiance, denoised or accumulated — on the context's stream behind whatever wrote it, and
+ *   returns without waiting.  A pixel's luminance is l = (0.2126 r + 0.7152 g) + 0.0722 b; pixels with alpha > 0 and a finite l > 0 are metered, pixels with
+ *   alpha > 0 and any other l are counted as rejected, the others are not counted.  The metered luminance is the trimmed mean, between the two percentiles, of a
+ *   piecewise-linear log2 of l over a histogram of 4096 bins, 16 per stop, in integers (csrc/pt_display.h has the definition): exact, whatever order the device
+ *   adds in.  The adaptation state then moves towards it by adapt_rate (1: follows at once; the first metering after a reset always does).  A metering without
+ *   metered pixels leaves the state alone.  The state survives ptc_frame_begin, ptc_set_camera, refit, rebuild and commit; ptc_exposure_reset and ptc_scene_begin
+ *   drop it.
+ * ptc_display_rgba8 / ptc_display_rgba16f: the served image times the exposure scale E — gain (key / clamp(adapted luminance, min_luminance, max_luminance))
+ *   with auto_exposure on and an adaptation state, gain otherwise — through the operator and the transfer function to RGBA8 (alpha: clamp and quantisation only),
+ *   or converted to RGBA16F as ptc_read_radiance_rgba16f converts (no operator, no transfer function: what a viewer's own tonemapper consumes; a NaN becomes
+ *   0x7e00).  The kernels read the adaptation state from device memory: ptc_meter_exposure followed by a display call needs no wait in between.  With the defaults
+ *   ptc_display_rgba8 writes ptc_tonemap_rgba8's bytes.  ptc_display_rgba16f_device_ptr: the device-pointer form, valid until the next RGBA16F display call.
+ * ptc_get_exposure: waits for the device; the scale E a display call would use now, the adapted luminance (the state as a float, before the clamp; 0: none), the
+ *   last metering's luminance, its metered and rejected pixel counts.  Any pointer may be NULL.
+ * ptc_read_luminance_histogram: the 4096 bins of the last metering (waits); bin k counts the pixels with bits(l) >> 19 == k.
+ * ptc_get_display_seconds: HIP-event times of the last metering and the last display kernel (0 when there was none); either pointer may be NULL.
+ * The device calls return PTC_E_DEVICE on a description-only context and PTC_E_STATE before anything is rendered. */
+enum { PTC_TONEMAP_ACES = 0,         /* the ACES fit of ptc_tonemap_rgba8 */
+       PTC_TONEMAP_PBR_NEUTRAL = 1,  /* Khronos PBR Neutral, the glTF sample viewer's operator */
+       PTC_TONEMAP_REINHARD = 2,     /* extended Reinhard on luminance, `white` maps to 1 */
+       PTC_TONEMAP_CLAMP = 3 };      /* none */
+enum { PTC_OETF_GAMMA22 = 0, PTC_OETF_SRGB = 1 };
+typedef struct ptc_display_params {
+  float gain;            /* linear exposure multiplier, finite, > 0 (1)            */
+  int   auto_exposure;   /* 0 | 1 (0)                                              */
+  float key;             /* metered luminance is mapped to this, > 0 (0.18)        */
+  float percentile_lo;   /* [0, 1), < percentile_hi (0.1)                          */
+  float percentile_hi;   /* (0, 1]  (0.9)                                          */
+  float adapt_rate;      /* [0, 1]; 1 = follow at once (1)                         */
+  float min_luminance;   /* clamp of the adapted luminance, > 0 (1e-4)             */
+  float max_luminance;   /* >= min_luminance (1e6)                                 */
+  int   tonemap;         /* PTC_TONEMAP_* (ACES)                                   */
+  float white;           /* REINHARD only, > 0 (4)                                 */
+  int   oetf;            /* PTC_OETF_* (GAMMA22)                                   */
+} ptc_display_params;
+void  ptc_display_default_params(ptc_display_params*);
+int   ptc_set_display(ptc_ctx*, const ptc_display_params*);   /* NULL: the defaults */
+int   ptc_get_display(const ptc_ctx*, ptc_display_params*);
+int   ptc_meter_exposure(ptc_ctx*);                            /* asynchronous */
+int   ptc_exposure_reset(ptc_ctx*);
+int   ptc_get_exposure(ptc_ctx*, float* scale_E, float* adapted_luminance, float* metered_luminance, uint64_t* metered, uint64_t* rejected);
+int   ptc_read_luminance_histogram(ptc_ctx*, uint32_t out[4096]);
+int   ptc_display_rgba8(ptc_ctx*, uint8_t* out);
+int   ptc_display_rgba16f(ptc_ctx*, uint16_t* out);
+void* ptc_display_rgba16f_device_ptr(ptc_ctx*);
+int   ptc_get_display_seconds(ptc_ctx*, double* meter, double* display);
+
 /* ---- multi-GPU: tiles shard over devices, one RCCL reduce brings the framebuffer to the root -----------
  * The reference has no multi-device path (one vk::Device, core/GpuHandle.cpp:94-101); this is BASELINE.json's
  * "independent pixel/sample tiles shard across the 8 GPUs of one node with an RCCL reduce onto rank 0".
@@ -606,6 +660,20 @@ int ptc_debug_light_sample(const ptc_light_params*, const float P[3], float out_
 int ptc_debug_get_light_table(ptc_ctx*, uint32_t* n_lights, float* records, float* cdf);
 int ptc_debug_punctual_nee(ptc_ctx*, const float* origins, const float* dirs, const uint32_t* keys, uint32_t n, uint32_t bounce,
                            uint8_t* out_valid, float* out_origin, float* out_dir, float* out_tmax, float* out_contrib);
+/* The display transform (csrc/pt_display.h).  The first two are pure host evaluations of the header and need no context.
+ * ptc_debug_display_pixel: one RGBA pixel at the exposure scale E through the operator and transfer function of params (NULL: the defaults): the four RGBA8
+ *   bytes and the four RGBA16F values.  Either output may be NULL.  PTC_E_ARG for a null input or parameters ptc_set_display would refuse.
+ * ptc_debug_meter: a metering of n_pixels RGBA pixels (at most 2^28) from the adaptation state state_in: the new state, Q, the metered pixels N, the pixels the
+ *   trim kept M, the rejected pixels and the histogram.  Every output may be NULL.
+ * ptc_debug_display_internals: [0] the pixels one pass of k_meter_hist's grid covers (an image with more takes a second pass of the grid-stride loop), [1] the
+ *   same for the display kernels, 0: they are not grid-stride, [2], [3] 0.
+ *   Works on a description-only context.
+ * ptc_debug_display_state: waits; the state record in device memory, out[0..4] = A, Q, N, M, rejected (zeros before the first metering). */
+int ptc_debug_display_pixel(const ptc_display_params*, float E, const float rgba_in[4], uint8_t out8[4], uint16_t out16[4]);
+int ptc_debug_meter(const ptc_display_params*, const float* rgba, uint64_t n_pixels, uint32_t state_in, uint32_t* state_out, uint32_t* Q, uint64_t* N, uint64_t* M,
+                    uint64_t* rejected, uint32_t hist[4096]);
+int ptc_debug_display_internals(ptc_ctx*, uint64_t out[4]);
+int ptc_debug_display_state(ptc_ctx*, uint32_t out[8]);
 /* The camera rays of the path integrator for n_pixels pixels (indices y*w+x of a w x h frame) and the samples first_sample .. first_sample + n_samples - 1,
  * with the context's camera and lens and the seed hashed as ptc_frame_begin hashes it: n_pixels * n_samples rays in path order, ray p = sample_local *
  * n_pixels + j, origins and dirs 3 floats each.  On a device context the launcher a batch would choose — k_raygen for R = 0, the lens kernel otherwise —

@@ -18,6 +18,7 @@
 #include "pt_deform.h"
 #include "pt_lens.h"
 #include "pt_lights.h"
+#include "pt_display.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -170,6 +171,14 @@ struct ptc_ctx {
   DevBuf<pt_light_rec> d_lights;
   DevBuf<float> d_light_cdf;
   uint32_t n_lights_dev = 0;             // lights in the device table; 0: no punctual pass, nothing allocated
+  // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
+  // allocated by the first call that needs them.  Nothing here is touched by a context that never calls the display functions
+  ptc_display_params display{1.0f, 0, 0.18f, 0.1f, 0.9f, 1.0f, 1e-4f, 1e6f, PTC_TONEMAP_ACES, 4.0f, PTC_OETF_GAMMA22};
+  DevBuf<uint32_t> dp_hist, dp_ldr;
+  DevBuf<pt_display_state> dp_state;
+  DevBuf<uint2> dp_half;
+  hipEvent_t ev_dp[4] = {nullptr, nullptr, nullptr, nullptr};   // start / stop of the last metering, start / stop of the last display kernel
+  bool ev_dp_recorded[2] = {false, false};
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -810,6 +819,8 @@ void ptc_destroy(ptc_ctx* c) {
   c->g_albedo.release(); c->g_normal.release(); c->g_pos.release(); c->dn_cv[0].release(); c->dn_cv[1].release(); c->denoised.release();
   c->g_prim.release(); c->g_uv.release(); c->g_stats.release();
   c->d_lights.release(); c->d_light_cdf.release();
+  c->dp_hist.release(); c->dp_ldr.release(); c->dp_state.release(); c->dp_half.release();
+  for (hipEvent_t e : c->ev_dp) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
   for (auto* b : {&c->ad_pix[0], &c->ad_pix[1], &c->ad_slot[0], &c->ad_slot[1], &c->ad_count, &c->ad_block, &c->ad_n}) b->release();
   c->ad_mom.release(); c->ad_flags.release(); c->ad_keep.release();
@@ -836,6 +847,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   ptc_lens_default_params(&c->lens);
   c->lights_dirty = c->lights_dirty || !c->lights.empty(); c->lights.clear();
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
+  if (c->dp_state.p) HIP_TRY(c, hipMemset(c->dp_state.p, 0, sizeof(pt_display_state)));      // the adaptation state goes with the scene; the display parameters stay
   release_scene(c);
   return PTC_OK;
 }
@@ -1571,6 +1583,205 @@ int ptc_light_count(const ptc_ctx* c) { return c ? (int)c->lights.size() : PTC_E
 int ptc_clear_lights(ptc_ctx* c) {
   if (!c) return PTC_E_ARG;
   if (!c->lights.empty()) { c->lights.clear(); c->lights_dirty = true; }
+  return PTC_OK;
+}
+
+// ---- display transform (pt_display.h, pt_display.hip) ----------------------------------------------------------------------------------------
+namespace {
+// the histogram, the state record (zeroed when it is made: no adaptation state) and the events; what the display calls need before they queue anything
+int ensure_display(ptc_ctx* c, const char* who) {
+  if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, std::string(who) + ": nothing rendered");
+  if ((size_t)c->rad_w * c->rad_h > PT_DISPLAY_MAX_PIXELS) return fail(c, PTC_E_ARG, std::string(who) + ": more than 2^28 pixels");
+  int rc;
+  if ((rc = ensure_buf(c, c->dp_hist, PT_DISPLAY_BINS + 4))) return rc;
+  if (!c->dp_state.p) {
+    if ((rc = ensure_buf(c, c->dp_state, 1))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->dp_state.p, 0, sizeof(pt_display_state), c->lanes[0].stream));
+    HIP_TRY(c, hipMemsetAsync(c->dp_hist.p, 0, (PT_DISPLAY_BINS + 4) * sizeof(uint32_t), c->lanes[0].stream));
+  }
+  for (hipEvent_t& e : c->ev_dp) if (!e) HIP_TRY(c, hipEventCreate(&e));
+  return PTC_OK;
+}
+int queue_display_half(ptc_ctx* c, const char* who) {
+  { int rd = need_device(c); if (rd) return rd; }
+  int rc;
+  if ((rc = ensure_display(c, who))) return rc;
+  const size_t n = (size_t)c->rad_w * c->rad_h;
+  if ((rc = ensure_buf(c, c->dp_half, n))) return rc;
+  hipStream_t s0 = c->lanes[0].stream;
+  HIP_TRY(c, hipEventRecord(c->ev_dp[2], s0));
+  pt_launch_display_half(s0, served_image(c), (uint32_t)n, c->dp_state.p, c->display, c->dp_half.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_dp[3], s0));
+  c->ev_dp_recorded[1] = true;
+  return PTC_OK;
+}
+}  // namespace
+
+void ptc_display_default_params(ptc_display_params* p) { if (p) pt_display_defaults(*p); }
+
+int ptc_set_display(ptc_ctx* c, const ptc_display_params* params) {
+  if (!c) return PTC_E_ARG;
+  ptc_display_params p;
+  pt_display_defaults(p);
+  if (params) p = *params;
+  if (const char* e = pt_display_params_error(p)) return fail(c, PTC_E_ARG, std::string("set_display: ") + e);
+  c->display = p;
+  return PTC_OK;
+}
+
+int ptc_get_display(const ptc_ctx* c, ptc_display_params* out) {
+  if (!c || !out) return PTC_E_ARG;
+  *out = c->display;
+  return PTC_OK;
+}
+
+int ptc_meter_exposure(ptc_ctx* c) {
+  { int rd = need_device(c); if (rd) return rd; }
+  int rc;
+  if ((rc = ensure_display(c, "meter_exposure"))) return rc;
+  hipStream_t s0 = c->lanes[0].stream;
+  HIP_TRY(c, hipEventRecord(c->ev_dp[0], s0));
+  pt_launch_meter(s0, served_image(c), (uint32_t)((size_t)c->rad_w * c->rad_h), c->dp_hist.p, c->dp_state.p, c->display);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_dp[1], s0));
+  c->ev_dp_recorded[0] = true;
+  return PTC_OK;
+}
+
+int ptc_exposure_reset(ptc_ctx* c) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (c->dp_state.p) HIP_TRY(c, hipMemsetAsync(c->dp_state.p, 0, sizeof(pt_display_state), c->lanes[0].stream));      // behind a metering still queued
+  return PTC_OK;
+}
+
+int ptc_debug_display_state(ptc_ctx* c, uint32_t out[8]) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "debug_display_state: null pointer");
+  std::memset(out, 0, 8 * sizeof(uint32_t));
+  if (!c->dp_state.p) return PTC_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  HIP_TRY(c, hipMemcpy(out, c->dp_state.p, sizeof(pt_display_state), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+int ptc_get_exposure(ptc_ctx* c, float* scale_E, float* adapted_luminance, float* metered_luminance, uint64_t* metered, uint64_t* rejected) {
+  uint32_t w[8];
+  { int rc = ptc_debug_display_state(c, w); if (rc) return rc; }
+  pt_display_state st;
+  std::memcpy(&st, w, sizeof st);
+  if (scale_E) *scale_E = pt_display_scale(c->display, st.A);
+  if (adapted_luminance) *adapted_luminance = pt_display_float(st.A);
+  if (metered_luminance) *metered_luminance = pt_display_float(st.Q);
+  if (metered) *metered = st.N;
+  if (rejected) *rejected = st.rejected;
+  return PTC_OK;
+}
+
+int ptc_read_luminance_histogram(ptc_ctx* c, uint32_t out[4096]) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "read_luminance_histogram: null pointer");
+  if (!c->dp_hist.p || !c->ev_dp_recorded[0]) return fail(c, PTC_E_STATE, "read_luminance_histogram: nothing metered (ptc_meter_exposure)");
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  HIP_TRY(c, hipMemcpy(out, c->dp_hist.p, PT_DISPLAY_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+int ptc_display_rgba8(ptc_ctx* c, uint8_t* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "display_rgba8: null pointer");
+  int rc;
+  if ((rc = ensure_display(c, "display_rgba8"))) return rc;
+  const size_t n = (size_t)c->rad_w * c->rad_h;
+  if ((rc = ensure_buf(c, c->dp_ldr, n))) return rc;
+  hipStream_t s0 = c->lanes[0].stream;
+  HIP_TRY(c, hipEventRecord(c->ev_dp[2], s0));
+  pt_launch_display_rgba8(s0, served_image(c), (uint32_t)n, c->dp_state.p, c->display, c->dp_ldr.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_dp[3], s0));
+  c->ev_dp_recorded[1] = true;
+  HIP_TRY(c, hipStreamSynchronize(s0));
+  HIP_TRY(c, hipMemcpy(out, c->dp_ldr.p, n * 4, hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+
+int ptc_display_rgba16f(ptc_ctx* c, uint16_t* out) {
+  if (c && c->device >= 0 && !out) return fail(c, PTC_E_ARG, "display_rgba16f: null pointer");
+  { int rc = queue_display_half(c, "display_rgba16f"); if (rc) return rc; }
+  HIP_TRY(c, hipStreamSynchronize(c->lanes[0].stream));
+  HIP_TRY(c, hipMemcpy(out, c->dp_half.p, (size_t)c->rad_w * c->rad_h * sizeof(uint2), hipMemcpyDeviceToHost));
+  return PTC_OK;
+}
+void* ptc_display_rgba16f_device_ptr(ptc_ctx* c) {
+  if (queue_display_half(c, "display_rgba16f_device_ptr")) return nullptr;
+  if (hipStreamSynchronize(c->lanes[0].stream) != hipSuccess) return nullptr;
+  return (void*)c->dp_half.p;
+}
+
+int ptc_get_display_seconds(ptc_ctx* c, double* meter, double* display) {
+  { int rd = need_device(c); if (rd) return rd; }
+  double* out[2] = {meter, display};
+  for (int k = 0; k < 2; ++k) {
+    if (!out[k]) continue;
+    *out[k] = 0.0;
+    if (!c->ev_dp_recorded[k]) continue;
+    HIP_TRY(c, hipEventSynchronize(c->ev_dp[2 * k + 1]));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_dp[2 * k], c->ev_dp[2 * k + 1]));
+    *out[k] = 1e-3 * (double)ms;
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_display_internals(ptc_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return PTC_E_ARG;
+  out[0] = pt_display_meter_grid_pixels(); out[1] = 0; out[2] = 0; out[3] = 0;
+  return PTC_OK;
+}
+
+int ptc_debug_display_pixel(const ptc_display_params* params, float E, const float rgba_in[4], uint8_t out8[4], uint16_t out16[4]) {
+  ptc_display_params p;
+  pt_display_defaults(p);
+  if (params) p = *params;
+  if (!rgba_in || pt_display_params_error(p)) return PTC_E_ARG;
+  if (out8) {
+    const uint32_t v = pt_display_host_pixel8(p, E, rgba_in);
+    for (int k = 0; k < 4; ++k) out8[k] = (uint8_t)(v >> (8 * k));
+  }
+  if (out16) {
+    uint32_t lo, hi;
+    pt_display_pixel16(rgba_in[0], rgba_in[1], rgba_in[2], rgba_in[3], E, lo, hi);
+    out16[0] = (uint16_t)lo; out16[1] = (uint16_t)(lo >> 16); out16[2] = (uint16_t)hi; out16[3] = (uint16_t)(hi >> 16);
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_meter(const ptc_display_params* params, const float* rgba, uint64_t n_pixels, uint32_t state_in, uint32_t* state_out, uint32_t* Q_out, uint64_t* N_out,
+                    uint64_t* M_out, uint64_t* rejected_out, uint32_t hist_out[4096]) {
+  ptc_display_params p;
+  pt_display_defaults(p);
+  if (params) p = *params;
+  if ((!rgba && n_pixels) || n_pixels > PT_DISPLAY_MAX_PIXELS || pt_display_params_error(p)) return PTC_E_ARG;
+  std::vector<uint32_t> hist(PT_DISPLAY_BINS, 0u);
+  uint64_t N = 0, rejected = 0;
+  for (uint64_t i = 0; i < n_pixels; ++i) {
+    uint32_t key = 0;
+    const int cls = pt_meter_classify(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3], key);
+    if (cls == 1) { hist[key]++; N++; } else if (cls == 2) rejected++;
+  }
+  uint64_t n_lo, n_hi, before = 0, S = 0, M = 0;
+  pt_meter_bounds((uint32_t)N, p.percentile_lo, p.percentile_hi, n_lo, n_hi);
+  for (uint32_t k = 0; k < PT_DISPLAY_BINS; ++k) {
+    const uint64_t kept = pt_meter_kept(before, hist[k], n_lo, n_hi);
+    S += kept * (uint64_t)(2u * k + 1u); M += kept; before += hist[k];
+  }
+  const uint32_t Q = pt_meter_mean(S, M);
+  if (state_out) *state_out = pt_meter_adapt(state_in, Q, M, p.adapt_rate);
+  if (Q_out) *Q_out = Q;
+  if (N_out) *N_out = N;
+  if (M_out) *M_out = M;
+  if (rejected_out) *rejected_out = rejected;
+  if (hist_out) std::memcpy(hist_out, hist.data(), PT_DISPLAY_BINS * sizeof(uint32_t));
   return PTC_OK;
 }
 

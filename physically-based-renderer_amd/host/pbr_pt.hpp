@@ -148,6 +148,31 @@ public:
     ck(ptc_tonemap_rgba8(_ctx, out.data()));
     return out;
   }
+  // ---- display transform (include/ptc.h): exposure (fixed, or metered on the device), tone-mapping operator, transfer function.  The radiance is in
+  // physical units; tonemap() and radianceHalf() take it as it is, these expose it first.  The parameters are a context setting, kept across beginScene
+  static auto displayDefaults() -> ptc_display_params { ptc_display_params p; ptc_display_default_params(&p); return p; }
+  auto setDisplay(ptc_display_params const& params) -> void { ck(ptc_set_display(_ctx, &params)); }
+  auto displayParams() const -> ptc_display_params { ptc_display_params p; ptc_get_display(_ctx, &p); return p; }
+  // meters the image selectOutput serves and moves the adaptation state; queued on the context's stream, does not wait: display() / displayHalf() behind it use it
+  auto meterExposure() -> void { ck(ptc_meter_exposure(_ctx)); }
+  auto exposureReset() -> void { ck(ptc_exposure_reset(_ctx)); }
+  struct Exposure { float scale = 1.0f, adaptedLuminance = 0.0f, meteredLuminance = 0.0f; std::uint64_t metered = 0, rejected = 0; };
+  auto exposure() -> Exposure { Exposure e; ck(ptc_get_exposure(_ctx, &e.scale, &e.adaptedLuminance, &e.meteredLuminance, &e.metered, &e.rejected)); return e; }
+  auto luminanceHistogram() -> std::vector<std::uint32_t> { std::vector<std::uint32_t> h(4096); ck(ptc_read_luminance_histogram(_ctx, h.data())); return h; }
+  auto display() -> std::vector<std::uint8_t> {
+    std::vector<std::uint8_t> out((std::size_t)_w * _h * 4);
+    ck(ptc_display_rgba8(_ctx, out.data()));
+    return out;
+  }
+  // the exposed image as RGBA16F, for a viewer's own tonemapper; displayHalfDevicePtr: the same in device memory (valid until the next of the two calls)
+  auto displayHalf() -> std::vector<std::uint16_t> {
+    std::vector<std::uint16_t> out((std::size_t)_w * _h * 4);
+    ck(ptc_display_rgba16f(_ctx, out.data()));
+    return out;
+  }
+  auto displayHalfDevicePtr() -> void* { return ptc_display_rgba16f_device_ptr(_ctx); }
+  // HIP-event seconds of the last meterExposure() and the last display kernel
+  auto displaySeconds() -> std::array<double, 2> { std::array<double, 2> t{0.0, 0.0}; ck(ptc_get_display_seconds(_ctx, &t[0], &t[1])); return t; }
   // the same image in the reference's HdrImage format, RGBA16F (PbrRenderSystem.hpp:21, HdrImage.cpp:20): what a viewer shim
   // copies into the image the tonemapper samples
   auto radianceHalf() -> std::vector<std::uint16_t> {

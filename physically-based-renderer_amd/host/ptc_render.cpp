@@ -5,6 +5,11 @@
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
 //              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights]
+//              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
+// --exposure EV / --auto-exposure / --tonemap / --srgb: the display transform (ptc_set_display) for --png, --ppm and --half.  --exposure multiplies the
+// radiance by 2^EV; --auto-exposure meters the image on the device (ptc_meter_exposure) and maps its metered luminance to the key K (default 0.18), times 2^EV;
+// --tonemap picks the operator (neutral: Khronos PBR Neutral) and --srgb the sRGB transfer function instead of gamma 2.2; --half then holds the exposed radiance.
+// With none of them the three files are what ptc_tonemap_rgba8 and ptc_read_radiance_rgba16f give.  Bad values are reported before any device work.
 // --light (repeatable): a punctual light (ptc_add_light), path integrator only.  point / spot: position, intensity rgb in W/sr, an optional range; a spot points along
 // dx,dy,dz with full intensity inside inner_deg of the axis and none outside outer_deg.  sun: a directional light travelling along dx,dy,dz, rgb = the irradiance of a
 // facing surface.  A --gltf scene brings the KHR_lights_punctual lights of its nodes (with --animation they move with them); --no-gltf-lights drops those.
@@ -202,6 +207,9 @@ int main(int argc, char** argv) {
   std::vector<std::string> lightSpecs;       // --light, in order
   std::vector<ptc_light_params> lights;
   bool noGltfLights = false;
+  ptc_display_params disp = pbr::PathTraceRenderSystem::displayDefaults();      // --exposure / --auto-exposure / --key / --tonemap / --srgb
+  bool useDisplay = false, haveKey = false;
+  double exposureEv = 0.0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -220,6 +228,14 @@ int main(int argc, char** argv) {
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
     else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true;
+    else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
+    else if (a == "--key") { disp.key = (float)std::atof(next()); haveKey = true; } else if (a == "--srgb") { disp.oetf = PTC_OETF_SRGB; useDisplay = true; }
+    else if (a == "--tonemap") {
+      const std::string f = next();
+      if (f == "aces") disp.tonemap = PTC_TONEMAP_ACES; else if (f == "neutral") disp.tonemap = PTC_TONEMAP_PBR_NEUTRAL; else if (f == "reinhard") disp.tonemap = PTC_TONEMAP_REINHARD;
+      else if (f == "clamp") disp.tonemap = PTC_TONEMAP_CLAMP; else { std::cerr << "--tonemap aces|neutral|reinhard|clamp\n"; return 2; }
+      useDisplay = true;
+    }
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -250,6 +266,12 @@ int main(int argc, char** argv) {
       if (lens.blades != 0 && (lens.blades < 3 || lens.blades > 16)) throw std::runtime_error("--blades N: 0 (disk) or 3..16");
       if (!(lens.rotation >= 0.0f && lens.rotation < 1.0f)) throw std::runtime_error("--aperture-rotation T: turns in [0, 1)");
       if (haveFocusPixel && (focusX < 0 || focusY < 0 || focusX >= w || focusY >= h)) throw std::runtime_error("--focus-pixel X,Y: a pixel of the image");
+    }
+    {   // the display transform
+      disp.gain = (float)std::exp2(exposureEv);
+      if (!std::isfinite(exposureEv) || !(disp.gain > 0.0f) || !std::isfinite(disp.gain)) throw std::runtime_error("--exposure EV: 2^EV must be a finite float > 0");
+      if (haveKey && !disp.auto_exposure) throw std::runtime_error("--key K sets the target of --auto-exposure");
+      if (!(disp.key > 0.0f) || !std::isfinite(disp.key)) throw std::runtime_error("--key K: a finite value > 0");
     }
     for (const std::string& sp : lightSpecs) lights.push_back(parseLight(sp));
     if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
@@ -380,15 +402,24 @@ int main(int argc, char** argv) {
         img = rs.readRadiance(w, h);
       }
     }
+    if (useDisplay) {      // behind the denoiser: the image the outputs serve is the one that is metered
+      rs.setDisplay(disp);
+      if (disp.auto_exposure) {
+        rs.meterExposure();
+        const pbr::PathTraceRenderSystem::Exposure e = rs.exposure();
+        std::printf("{\"metered_luminance\": %.9g, \"exposure_scale\": %.9g, \"metered_pixels\": %llu, \"rejected_pixels\": %llu}\n", (double)e.meteredLuminance, (double)e.scale,
+                    (unsigned long long)e.metered, (unsigned long long)e.rejected);
+      }
+    }
     if (!halfPath.empty()) {
-      const std::vector<std::uint16_t> hb = rs.radianceHalf();
+      const std::vector<std::uint16_t> hb = useDisplay ? rs.displayHalf() : rs.radianceHalf();
       std::ofstream g(halfPath, std::ios::binary);
       g.write(reinterpret_cast<const char*>(hb.data()), (std::streamsize)(hb.size() * 2));
     }
     pbr::image::write_pfm(out, img.data(), w, h);
-    if (!png.empty()) { const std::vector<std::uint8_t> ldr = rs.tonemap(); pbr::image::write_png(png, ldr.data(), w, h); }
+    if (!png.empty()) { const std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap(); pbr::image::write_png(png, ldr.data(), w, h); }
     if (!ppm.empty()) {
-      const std::vector<std::uint8_t> ldr = rs.tonemap();
+      const std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap();
       std::ofstream g(ppm, std::ios::binary);
       g << "P6\n" << w << " " << h << "\n255\n";
       for (std::size_t p = 0; p < (std::size_t)w * h; ++p) g.write(reinterpret_cast<const char*>(&ldr[p * 4]), 3);

@@ -30,6 +30,13 @@ LIGHT_POINT = 0
 LIGHT_SPOT = 1
 LIGHT_DIRECTIONAL = 2
 MAX_LIGHTS = 256
+TONEMAP_ACES = 0          # the ACES fit of tonemap()
+TONEMAP_PBR_NEUTRAL = 1   # Khronos PBR Neutral
+TONEMAP_REINHARD = 2      # extended Reinhard on luminance
+TONEMAP_CLAMP = 3
+OETF_GAMMA22 = 0
+OETF_SRGB = 1
+LUMINANCE_BINS = 4096
 GUIDE_ALBEDO = 0          # (albedo rgb, class: 0 miss, 1 surface, 2 emitter)
 GUIDE_NORMAL_DEPTH = 1    # (unit vertex normal, t along the unit camera ray)
 OUTPUT_RADIANCE = 0
@@ -59,6 +66,9 @@ ABI_SYMBOLS = [
     "ptc_lens_default_params", "ptc_set_camera_lens", "ptc_get_camera_lens", "ptc_focus_distance_at_pixel", "ptc_debug_lens_sample", "ptc_debug_camera_rays",
     "ptc_light_default_params", "ptc_add_light", "ptc_update_light", "ptc_get_light", "ptc_light_count", "ptc_clear_lights",
     "ptc_debug_light_sample", "ptc_debug_get_light_table", "ptc_debug_punctual_nee",
+    "ptc_display_default_params", "ptc_set_display", "ptc_get_display", "ptc_meter_exposure", "ptc_exposure_reset", "ptc_get_exposure", "ptc_read_luminance_histogram",
+    "ptc_display_rgba8", "ptc_display_rgba16f", "ptc_display_rgba16f_device_ptr", "ptc_get_display_seconds",
+    "ptc_debug_display_pixel", "ptc_debug_meter", "ptc_debug_display_internals", "ptc_debug_display_state",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
 
@@ -123,6 +133,16 @@ class PtcLightParams(C.Structure):
         return {k: (tuple(getattr(self, k)) if k in ("position", "direction", "intensity") else getattr(self, k)) for k, _ in self._fields_}
 
 
+class PtcDisplayParams(C.Structure):
+    _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_int), ("key", C.c_float), ("percentile_lo", C.c_float), ("percentile_hi", C.c_float),
+                ("adapt_rate", C.c_float), ("min_luminance", C.c_float), ("max_luminance", C.c_float), ("tonemap", C.c_int), ("white", C.c_float), ("oetf", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+_TONEMAPS = {"aces": TONEMAP_ACES, "neutral": TONEMAP_PBR_NEUTRAL, "pbr_neutral": TONEMAP_PBR_NEUTRAL, "reinhard": TONEMAP_REINHARD, "clamp": TONEMAP_CLAMP}
+_OETFS = {"gamma22": OETF_GAMMA22, "srgb": OETF_SRGB}
 _LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
 
 
@@ -266,6 +286,25 @@ def load_library():
     L.ptc_debug_light_sample.argtypes = [lp, fp, fp, fp, fp]
     L.ptc_debug_get_light_table.argtypes = [vp, u32p, fp, fp]
     L.ptc_debug_punctual_nee.argtypes = [vp, fp, fp, u32p, C.c_uint32, C.c_uint32, u8p, fp, fp, fp, fp]
+    dpp = C.POINTER(PtcDisplayParams)
+    u64p = C.POINTER(C.c_uint64)
+    L.ptc_display_default_params.argtypes = [dpp]
+    L.ptc_display_default_params.restype = None
+    L.ptc_set_display.argtypes = [vp, dpp]
+    L.ptc_get_display.argtypes = [vp, dpp]
+    L.ptc_meter_exposure.argtypes = [vp]
+    L.ptc_exposure_reset.argtypes = [vp]
+    L.ptc_get_exposure.argtypes = [vp, fp, fp, fp, u64p, u64p]
+    L.ptc_read_luminance_histogram.argtypes = [vp, u32p]
+    L.ptc_display_rgba8.argtypes = [vp, u8p]
+    L.ptc_display_rgba16f.argtypes = [vp, C.POINTER(C.c_uint16)]
+    L.ptc_display_rgba16f_device_ptr.argtypes = [vp]
+    L.ptc_display_rgba16f_device_ptr.restype = C.c_void_p
+    L.ptc_get_display_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.ptc_debug_display_pixel.argtypes = [dpp, C.c_float, fp, u8p, C.POINTER(C.c_uint16)]
+    L.ptc_debug_meter.argtypes = [dpp, fp, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p, u64p, u32p]
+    L.ptc_debug_display_internals.argtypes = [vp, u64p]
+    L.ptc_debug_display_state.argtypes = [vp, u32p]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -334,6 +373,69 @@ def light_sample(light, P):
         if rc:
             ok[i], wi[i], dist[i], Li[i] = True, tuple(w), d.value, tuple(li)
     return ok, wi, dist, Li
+
+
+def display_params(**fields):
+    """A ptc_display_params: the defaults with `fields` replaced.  `tonemap` takes a name (aces, neutral, reinhard, clamp) or a TONEMAP_* value, `oetf` a name
+    (gamma22, srgb) or an OETF_* value."""
+    p = PtcDisplayParams()
+    load_library().ptc_display_default_params(C.byref(p))
+    return _display_update(p, fields)
+
+
+def _display_update(p, fields):
+    names = dict(PtcDisplayParams._fields_)
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"display parameters: unknown field {k}")
+        if k == "tonemap" and isinstance(v, str):
+            v = _TONEMAPS[v]
+        if k == "oetf" and isinstance(v, str):
+            v = _OETFS[v]
+        setattr(p, k, int(v) if names[k] is C.c_int else float(v))
+    return p
+
+
+def display_default_params():
+    return display_params().as_dict()
+
+
+def ev_to_gain(ev):
+    """The linear exposure multiplier of `ev` stops: 2**ev in float64, rounded to float32."""
+    return float(np.float32(2.0 ** float(ev)))
+
+
+def display_pixels(rgba, E=1.0, **fields):
+    """ptc_debug_display_pixel: the host's evaluation of csrc/pt_display.h for the pixels rgba (n, 4) at the exposure scale E with display_params(**fields):
+    (RGBA8 (n, 4) uint8, RGBA16F (n, 4) uint16 bit patterns)."""
+    L = load_library()
+    p = fields.pop("params", None) or display_params(**fields)
+    px = np.ascontiguousarray(np.atleast_2d(np.asarray(rgba, np.float32)))
+    n = px.shape[0]
+    o8, o16 = np.zeros((n, 4), np.uint8), np.zeros((n, 4), np.uint16)
+    f, u8, u16 = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+    base, b8, b16 = px.ctypes.data, o8.ctypes.data, o16.ctypes.data
+    fn, pr, e = L.ptc_debug_display_pixel, C.byref(p), C.c_float(float(E))
+    for i in range(n):
+        if fn(pr, e, C.cast(base + 16 * i, f), C.cast(b8 + 4 * i, u8), C.cast(b16 + 8 * i, u16)) < 0:
+            raise PtcError(f"display_pixels: bad display parameters: {p.as_dict()}")
+    return o8, o16
+
+
+def meter(rgba, state=0, **fields):
+    """ptc_debug_meter: the host's metering of the pixels rgba (..., 4) from the adaptation state `state` with display_params(**fields): a dict with the new
+    state A, Q, N, M, rejected (integers) and hist (4096,) uint32."""
+    L = load_library()
+    p = fields.pop("params", None) or display_params(**fields)
+    px = np.ascontiguousarray(np.asarray(rgba, np.float32).reshape(-1, 4))
+    A, Q = C.c_uint32(0), C.c_uint32(0)
+    N, M, R = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    hist = np.zeros(LUMINANCE_BINS, np.uint32)
+    rc = L.ptc_debug_meter(C.byref(p), px.ctypes.data_as(C.POINTER(C.c_float)), px.shape[0], int(state), C.byref(A), C.byref(Q), C.byref(N), C.byref(M), C.byref(R),
+                           hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc < 0:
+        raise PtcError(f"meter: bad display parameters or too many pixels: {p.as_dict()}")
+    return {"A": A.value, "Q": Q.value, "N": N.value, "M": M.value, "rejected": R.value, "hist": hist}
 
 
 def comm_unique_id() -> bytes:
@@ -797,6 +899,76 @@ class PathTracer:
         out = np.empty((self._h_px, self._w, 4), np.uint8)
         self._ck(self._L.ptc_tonemap_rgba8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- display transform (csrc/pt_display.h) -----------------------------------------------
+    def set_display(self, **fields):
+        """ptc_set_display: the current display parameters with `fields` replaced (gain, auto_exposure, key, percentile_lo, percentile_hi, adapt_rate,
+        min_luminance, max_luminance, tonemap, white, oetf); no field: the defaults.  A context setting, kept across load_scene."""
+        if fields:
+            p = PtcDisplayParams()
+            self._ck(self._L.ptc_get_display(self._h, C.byref(p)))
+            self._ck(self._L.ptc_set_display(self._h, C.byref(_display_update(p, fields))))
+        else:
+            self._ck(self._L.ptc_set_display(self._h, None))
+        return self
+
+    def get_display(self):
+        p = PtcDisplayParams()
+        self._ck(self._L.ptc_get_display(self._h, C.byref(p)))
+        return p.as_dict()
+
+    def meter_exposure(self):
+        """ptc_meter_exposure: meter the image select_output serves and move the adaptation state; queued, does not wait."""
+        self._ck(self._L.ptc_meter_exposure(self._h))
+        return self
+
+    def exposure_reset(self):
+        self._ck(self._L.ptc_exposure_reset(self._h))
+        return self
+
+    def exposure(self):
+        """ptc_get_exposure (waits): the scale E a display call would use now, the adapted and the last metered luminance, the metered and rejected pixels."""
+        e, a, m = C.c_float(0), C.c_float(0), C.c_float(0)
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.ptc_get_exposure(self._h, C.byref(e), C.byref(a), C.byref(m), C.byref(n), C.byref(r)))
+        return {"scale": e.value, "adapted_luminance": a.value, "metered_luminance": m.value, "metered": n.value, "rejected": r.value}
+
+    def exposure_state(self):
+        """ptc_debug_display_state (waits): the integers of the state record, A (adaptation state), Q (last metering), N, M, rejected."""
+        w = (C.c_uint32 * 8)()
+        self._ck(self._L.ptc_debug_display_state(self._h, w))
+        return {"A": w[0], "Q": w[1], "N": w[2], "M": w[3], "rejected": w[4]}
+
+    def luminance_histogram(self):
+        out = np.zeros(LUMINANCE_BINS, np.uint32)
+        self._ck(self._L.ptc_read_luminance_histogram(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def display(self):
+        """ptc_display_rgba8: the served image through exposure, operator and transfer function: (h, w, 4) uint8."""
+        out = np.empty((self._h_px, self._w, 4), np.uint8)
+        self._ck(self._L.ptc_display_rgba8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def display_f16(self):
+        """ptc_display_rgba16f: the served image times the exposure scale as RGBA16F: (h, w, 4) float16."""
+        out = np.empty((self._h_px, self._w, 4), np.uint16)
+        self._ck(self._L.ptc_display_rgba16f(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out.view(np.float16)
+
+    def display_f16_device_ptr(self) -> int:
+        return int(self._L.ptc_display_rgba16f_device_ptr(self._h) or 0)
+
+    def display_seconds(self):
+        """(metering, display): HIP-event seconds of the last meter_exposure() and the last display() / display_f16()."""
+        m, d = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ptc_get_display_seconds(self._h, C.byref(m), C.byref(d)))
+        return m.value, d.value
+
+    def display_internals(self):
+        w = (C.c_uint64 * 4)()
+        self._ck(self._L.ptc_debug_display_internals(self._h, w))
+        return [int(v) for v in w]
 
     def stats(self):
         s = PtcStats()

@@ -9,7 +9,11 @@ With PTC_DEVICE_BVH=sah in the environment the rebuilt tree is the binned-SAH tr
 parameters) between the resolve and the RGBA16F hand-off, and reports that frame time beside the plain one, with the HIP-event times of the two passes.
 --temporal runs it once more with the temporal path: guides, ptc_temporal_accumulate (the history reprojected through the refit and blended with the frame),
 ptc_denoise_accumulated, hand-off; reported like --denoise's, against --denoise's frame time when both are given, with the accumulate's HIP-event time.
-usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h] [--denoise] [--temporal]"""
+--auto-exposure runs the plain loop once more with the display transform: one metering per displayed frame (ptc_meter_exposure, adapt_rate 0.1) and the exposed RGBA16F
+(ptc_display_rgba16f_device_ptr) instead of the raw one, queued behind the resolve without a wait in between.  The scene keeps turning and the refitted tree keeps getting
+slower, so this loop alternates plain and metered frames and reports the two medians of the same stretch, with the HIP-event times of the metering and of the display
+kernel and the exposure the loop ended at.
+usage: python3 tools/viewer_loop.py [atrium|textured] [spp] [frames] [w h] [--denoise] [--temporal] [--auto-exposure]"""
 import json, math, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))
@@ -18,7 +22,8 @@ import pbr_amd as pbr
 
 denoise = "--denoise" in sys.argv
 temporal = "--temporal" in sys.argv
-argv = [a for a in sys.argv if a not in ("--denoise", "--temporal")]
+auto_exposure = "--auto-exposure" in sys.argv
+argv = [a for a in sys.argv if a not in ("--denoise", "--temporal", "--auto-exposure")]
 name = argv[1] if len(argv) > 1 else "atrium"
 spp = int(argv[2]) if len(argv) > 2 else 1
 frames = int(argv[3]) if len(argv) > 3 else 60
@@ -114,4 +119,33 @@ if temporal:     # once more: the frame blended into the reprojected history, th
                        "mean_history_length": float(n_hist[n_hist > 0].mean())}
     if denoise:
         out["temporal"]["ms_added_to_denoise_frame"] = 1e3 * float(np.median(t_tp) - np.median(t_dn))
+if auto_exposure:      # plain and metered frames alternating: nothing waits between the resolve, the metering and the conversion of a metered frame
+    pt.set_display(auto_exposure=1, adapt_rate=0.1)
+    t_ae, t_pl, s_meter, s_disp = [], [], [], []
+    for k in range(3 * frames + 15, 5 * frames + 25):
+        metered = k % 2 == 1
+        t0 = time.perf_counter()
+        a = 0.01 * (k + 1)
+        for i in moving:
+            pt.update_instance(i, d.instances[i].t, (math.cos(a / 2), 0.0, math.sin(a / 2), 0.0), d.instances[i].s)
+        pt.scene_refit()
+        pt.frame_begin(w, h, spp, seed=k, max_bounces=8)
+        pt.frame_add_samples(spp)
+        pt.frame_resolve()
+        if metered:
+            pt.meter_exposure()
+            ptr = pt.display_f16_device_ptr()
+        else:
+            pt.sync()
+            pt.radiance_f16_device_ptr()
+        t2 = time.perf_counter()
+        if k >= 3 * frames + 25:
+            (t_ae if metered else t_pl).append(t2 - t0)
+            if metered:
+                m_s, d_s = pt.display_seconds()
+                s_meter.append(m_s); s_disp.append(d_s)
+    out["auto_exposure"] = {"params": pt.get_display(), "ms_per_frame": {"median": 1e3 * float(np.median(t_ae)), "min": 1e3 * float(np.min(t_ae)), "max": 1e3 * float(np.max(t_ae))},
+                            "ms_per_plain_frame_of_the_same_stretch": {"median": 1e3 * float(np.median(t_pl)), "min": 1e3 * float(np.min(t_pl)), "max": 1e3 * float(np.max(t_pl))},
+                            "ms_added_per_frame": 1e3 * float(np.median(t_ae) - np.median(t_pl)), "ms_meter_device": 1e3 * float(np.median(s_meter)),
+                            "ms_display_half_device": 1e3 * float(np.median(s_disp)), "exposure": pt.exposure(), "exposed_half_image_device_ptr": hex(ptr)}
 print(json.dumps(out))
