@@ -73,6 +73,14 @@ int main(int argc, char** argv) {
   CHECK(ptc_get_stats(ctx, &st));
   printf("rendered %llu paths, %llu segments; radiance sum %.6f, ldr sum %lu\n", (unsigned long long)st.paths, (unsigned long long)st.segments, sum, lsum);
   free(img); free(ldr);
+  {                                                    /* a light probe: the radiance arriving at a point as 9 SH coefficients per channel, and the irradiance it gives */
+    const float at[3] = {0.0f, 0.0f, -3.0f}, facing_light[3] = {0.0f, -1.0f, 0.0f};
+    float sh[27], E[3];
+    CHECK(ptc_render_probes(ctx, at, 1, 256, 1u, 4, sh));
+    CHECK(ptc_sh9_irradiance(sh, facing_light, E));
+    printf("probe at (0, 0, -3): irradiance towards the light %.4f %.4f %.4f\n", E[0], E[1], E[2]);
+    if (!(E[0] > 0.0f)) sum = 0.0;
+  }
   ptc_destroy(ctx);
   return sum > 0.0 ? 0 : 4;
 }

@@ -598,6 +598,37 @@ int   ptc_display_rgba16f(ptc_ctx*, uint16_t* out);
 void* ptc_display_rgba16f_device_ptr(ptc_ctx*);
 int   ptc_get_display_seconds(ptc_ctx*, double* meter, double* display);
 
+/* ---- light probes: path-traced radiance at arbitrary points as 9 spherical-harmonic coefficients per channel (csrc/pt_probes.h) ----
+ * A probe answers "what light arrives at this point, from every direction": the path integrator's radiance L(w) over the whole sphere of directions around the
+ * position, projected onto the real SH basis up to band 2 (world axes, no Condon-Shortley sign; k = 0 | y z x | xy yz 3z^2-1 xz x^2-y^2), so that
+ * L(w) ~ sum_k coef_k Y_k(w).  ptc_sh9_irradiance turns the 27 floats into the irradiance on a surface with a given normal: what a rasterizer's lighting pass
+ * multiplies by albedo / pi for baked diffuse global illumination.
+ *
+ * A probe frame is a frame of the path integrator with one "pixel" per probe: sample s of probe j leaves the probe's position in a direction uniform over the
+ * sphere, drawn from the two jitter dimensions of the key path_key(seed, probe_index_base + j, s), and is traced and shaded as a camera path is — an emitter or
+ * the environment seen directly counts in full.  ptc_probes_begin begins it and ends whatever frame was in progress; the next ptc_frame_begin leaves probe mode.
+ * ptc_frame_add_samples (with its deferred batching), ptc_frame_reserve, ptc_frame_set_sample_range, ptc_sync and ptc_get_stats work as in any frame, and after
+ * ptc_frame_resolve the radiance read-backs return an n_probes x 1 image: each probe's mean incoming radiance.  Every sum has one owner and runs in sample order:
+ * the coefficients do not depend on how the samples were cut into calls, batches or lanes, and the probes [a, b) of a set rendered with probe_index_base = a
+ * are bit for bit the probes [a, b) of the whole set.  Punctual lights are sampled at the bounces as always; the lens is ignored.
+ * What a probe does not see: the direct term of a punctual light (a delta that no ray hits — a real-time engine evaluates those lights itself; their bounced
+ *   light is in the probe), and whether it lies inside geometry.
+ * ptc_probes_begin: positions_xyz holds 3 floats per probe.  PTC_E_ARG, and nothing changed, for a NULL pointer, n_probes outside 1..2^26, probe indices beyond
+ *   32 bits, a non-finite position, spp_total < 1 or max_bounces < 0; then PTC_E_DEVICE on a description-only context, PTC_E_STATE before ptc_scene_commit.
+ * ptc_probes_read_sh: n_probes * 27 floats laid out [probe][k][rgb]: queues what ptc_frame_add_samples held back, waits, and returns sums * (4 pi / N), N the
+ *   samples accumulated or the resolve divisor of ptc_frame_set_sample_range (shards of a sample range then add up to the whole).  PTC_E_STATE outside a probe frame.
+ * ptc_render_probes == ptc_probes_begin(base 0) + ptc_frame_add_samples(spp) + ptc_probes_read_sh.
+ * Refused with PTC_E_STATE in a probe frame, which they leave untouched: ptc_frame_guides, ptc_set_sample_covariance(1) (the setting stays as it
+ *   was; 0 is accepted), ptc_frame_set_adaptive and ptc_frame_adapt, the denoisers, ptc_temporal_accumulate, ptc_frame_checkpoint / _restore, ptc_comm_reduce_radiance,
+ *   ptc_focus_distance_at_pixel, ptc_debug_camera_rays.
+ * ptc_sh9_eval / ptc_sh9_irradiance: pure functions, no context; sh = 27 floats [k][rgb], direction and normal of unit length.  Radiance sum_k sh_k Y_k(dir);
+ *   irradiance E(n) = sum_k A_l sh_k Y_k(n) with A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4 (Ramamoorthi and Hanrahan 2001).  PTC_E_ARG for a NULL pointer. */
+int ptc_probes_begin(ptc_ctx*, const float* positions_xyz, int n_probes, uint32_t probe_index_base, int spp_total, uint64_t seed, int max_bounces);
+int ptc_probes_read_sh(ptc_ctx*, float* out);
+int ptc_render_probes(ptc_ctx*, const float* positions_xyz, int n_probes, int spp, uint64_t seed, int max_bounces, float* out);
+int ptc_sh9_eval(const float sh[27], const float dir[3], float out[3]);
+int ptc_sh9_irradiance(const float sh[27], const float normal[3], float out[3]);
+
 /* ---- multi-GPU: tiles shard over devices, one RCCL reduce brings the framebuffer to the root -----------
  * The reference has no multi-device path (one vk::Device, core/GpuHandle.cpp:94-101); this is BASELINE.json's
  * "independent pixel/sample tiles shard across the 8 GPUs of one node with an RCCL reduce onto rank 0".
@@ -681,6 +712,18 @@ int ptc_debug_display_state(ptc_ctx*, uint32_t out[8]);
  * description-only context (a camera must have been set) the host evaluates csrc/pt_lens.h, which restates the pinhole ray for R = 0. */
 int ptc_debug_camera_rays(ptc_ctx*, int w, int h, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const uint32_t* pixels, uint32_t n_pixels,
                           float* origins, float* dirs);
+/* Light probes (csrc/pt_probes.h).  On a description-only context the host evaluates the header; on a device context the kernels run on lane 0's queues
+ * (any frame in progress ends; no scene is needed).  Paths are in batch order: path p = sample_local * n_probes + j.
+ * ptc_debug_probe_rays: the rays k_raygen_probe writes for the samples first_sample .. first_sample + n_samples - 1: 6 floats per path (origin, direction) and
+ *   the path's RNG key.
+ * ptc_debug_probe_project: k_accumulate_sh's step: acc_inout (n_probes * 27 running sums) += the projection of lpath_rgba (4 floats per path, alpha unused).
+ * ptc_debug_probe_resolve: the resolve of ptc_probes_read_sh, out = acc * (4 pi / n_samples); no context.
+ * PTC_E_ARG for a NULL pointer, n_probes outside 1..2^26, n_samples = 0, more than 2^31 - 1 paths, sample or probe indices beyond 32 bits. */
+int ptc_debug_probe_rays(ptc_ctx*, const float* positions_xyz, int n_probes, uint32_t probe_index_base, uint64_t seed, uint32_t first_sample, uint32_t n_samples,
+                         float* out_o_d, uint32_t* out_key);
+int ptc_debug_probe_project(ptc_ctx*, int n_probes, uint32_t probe_index_base, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const float* lpath_rgba,
+                            float* acc_inout);
+int ptc_debug_probe_resolve(const float* acc, int n_probes, uint32_t n_samples, float* out);
 /* World-space flattened geometry as committed: verts (n_verts*12 floats = ptc_vertex),
  * indices (n_tris*3 u32), per-triangle material.  Pass NULL to query sizes only. */
 int ptc_debug_get_flat_scene(ptc_ctx*, uint32_t* n_verts, uint32_t* n_tris, ptc_vertex* verts,

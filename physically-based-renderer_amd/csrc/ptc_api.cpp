@@ -19,6 +19,7 @@
 #include "pt_lens.h"
 #include "pt_lights.h"
 #include "pt_display.h"
+#include "pt_probes.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -259,6 +260,12 @@ struct ptc_ctx {
   bool tp_accum_valid = false;      // the current frame has been accumulated: tp_accum holds its accumulated image
   hipEvent_t ev_tp[2] = {nullptr, nullptr};
   bool ev_tp_recorded = false;
+  // light probes (pt_probes.h).  A probe frame is a frame of n x 1 "pixels" — `fr`, accum, radiance, the batching and the sample range are the frame's own — whose
+  // batches start at k_raygen_probe and end with k_accumulate_sh beside k_accumulate.  The flag lives as long as the frame does (drop_guides ends it).
+  bool probe = false;
+  uint32_t probe_base = 0;          // index of probe 0 in the RNG key (ptc_probes_begin: probe_index_base)
+  DevBuf<float4> probe_pos;         // (x, y, z, -) per probe
+  DevBuf<float> probe_acc;          // 27 running sums per probe, [probe][k][rgb]
   // multi-GPU
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_size = 0;
@@ -285,7 +292,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; re
 // the temporal history is about the primitive ids of one committed scene: whatever brings another scene (ptc_scene_begin; every kind of commit, through
 // commit_upload(Upload::NewScene)) ends it, and with it the position snapshot's claim to be current.  Refits and rebuilds keep the ids and the history.
 void drop_history(ptc_ctx* c) { c->tp_live = false; c->tp_snap_current = false; }
-void drop_guides(ptc_ctx* c) { c->guides_valid = false; c->denoised_valid = false; c->tp_accum_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
+void drop_guides(ptc_ctx* c) { c->probe = false; c->guides_valid = false; c->denoised_valid = false; c->tp_accum_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
 // the image ptc_read_radiance_rgba32f / _rgba16f / ptc_tonemap_rgba8 serve (ptc_select_output)
 const float4* served_image(const ptc_ctx* c) { return c->output == PTC_OUTPUT_DENOISED ? c->denoised.p : c->output == PTC_OUTPUT_ACCUMULATED ? c->tp_accum.p : c->radiance.p; }
 const char* const kNoDevice = "this context has no device (PTC_DEVICE_NONE): the call needs a gfx950 GPU; there is no CPU path";
@@ -556,7 +563,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     { ScopedSpan t(c, st, 0); pt_launch_trace_closest(st, cfg, sc, q, 0, true); c->stats.launches_trace_closest++; }
     pt_launch_shade_raster(st, sc, c->cam, c->fr, q, c->accum.p, c->integrator == PTC_INTEGRATOR_RASTER_GBUFFER16);
   } else {
-    if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(st, c->cam, c->lens, c->fr, q, first_sample, n_samples);      // the thin lens (pt_lens.hip); the raster integrators above ignore it
+    if (c->probe) pt_launch_raygen_probe(st, c->probe_pos.p, c->fr.n_owned, c->probe_base, c->fr.seed_hash, q, first_sample, n_samples);      // a probe frame (pt_probes.hip) has no camera and no lens
+    else if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(st, c->cam, c->lens, c->fr, q, first_sample, n_samples);      // the thin lens (pt_lens.hip); the raster integrators above ignore it
     else pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
     const bool shadows = sc.n_lights > 0 || sc.env_ok;
     const bool small_batch = n_paths <= (1u << 26);
@@ -600,6 +608,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     }
     if (c->adaptive) pt_launch_ad_accumulate(st, c->fr.n_owned, c->ad_slot[c->ad_cur].p, q.lpath, c->accum.p, dev_adaptive(c), n_samples);
     else pt_launch_accumulate(st, c->fr, q, c->accum.p, n_samples);
+    // a probe frame: the SH projection of the same path radiance, inside the same sample-order bracket (it has its own sums, so the two do not order each other)
+    if (c->probe) pt_launch_accumulate_sh(st, c->fr.n_owned, c->probe_base, c->fr.seed_hash, q.lpath, c->probe_acc.p, first_sample, n_samples);
     if (c->n_lanes > 1) HIP_TRY(c, hipEventRecord(ln.acc_done, st));
   }
   c->batches_issued++;
@@ -819,6 +829,7 @@ void ptc_destroy(ptc_ctx* c) {
   c->g_albedo.release(); c->g_normal.release(); c->g_pos.release(); c->dn_cv[0].release(); c->dn_cv[1].release(); c->denoised.release();
   c->g_prim.release(); c->g_uv.release(); c->g_stats.release();
   c->d_lights.release(); c->d_light_cdf.release();
+  c->probe_pos.release(); c->probe_acc.release();
   c->dp_hist.release(); c->dp_ldr.release(); c->dp_state.release(); c->dp_half.release();
   for (hipEvent_t e : c->ev_dp) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_dn) if (e) (void)hipEventDestroy(e);
@@ -1788,6 +1799,7 @@ int ptc_debug_meter(const ptc_display_params* params, const float* rgba, uint64_
 int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!out) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: null pointer");
+  if (c->probe) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: a probe frame has no camera image");
   if (!c->guides_valid) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: no guides (ptc_frame_guides)");
   const int w = c->rad_w, h = c->rad_h;
   if (px < 0 || py < 0 || px >= w || py >= h) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: pixel outside the frame");
@@ -1982,19 +1994,34 @@ int scene_commit(ptc_ctx* c, bool device_ok) {
 
 int ptc_scene_commit(ptc_ctx* c) { return scene_commit(c, true); }
 
-int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
+namespace {
+// ptc_frame_begin, and ptc_probes_begin's share of it: probe_pos != nullptr begins a probe frame of w probes (h = 1, the path integrator, no tiles) — the "owned
+// pixels" are the probes in their own order, the positions go to the device, the 27 w sums are cleared and the probe flag is set
+int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const float* probe_pos,
+                uint32_t probe_base) {
   { int rd = need_device(c); if (rd) return rd; }
   c->in_frame = false; c->pending = 0; c->adaptive = false; c->cov_on = false; c->cov_resolved = false; c->sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
-  if (!c->committed) return fail(c, PTC_E_STATE, "frame_begin: scene not committed");
-  if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, "frame_begin: bad size");
-  if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, "frame_begin: unknown integrator");
-  if (tile_count < 1 || tile_rank < 0 || tile_rank >= tile_count) return fail(c, PTC_E_ARG, "frame_begin: bad tile rank/count");
+  const std::string who = probe_pos ? "probes_begin" : "frame_begin";      // the entry the caller used, for ptc_last_error
+  if (!c->committed) return fail(c, PTC_E_STATE, who + ": scene not committed");
+  if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, who + ": bad size");
+  if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, who + ": unknown integrator");
+  if (tile_count < 1 || tile_rank < 0 || tile_rank >= tile_count) return fail(c, PTC_E_ARG, who + ": bad tile rank/count");
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   int rc;
   if ((rc = upload_lights(c))) return rc;      // a changed light table: nothing is queued any more that reads the old one
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
-  if (!(c->owned_key_valid && c->owned_w == w && c->owned_h == h && c->owned_rank == tile_rank && c->owned_count == tile_count && c->owned.p)) {
+  if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
+    std::vector<uint32_t> owned((size_t)w);
+    std::vector<float4> pos((size_t)w);
+    for (int j = 0; j < w; ++j) { owned[(size_t)j] = (uint32_t)j; pos[(size_t)j] = make_float4(probe_pos[j * 3], probe_pos[j * 3 + 1], probe_pos[j * 3 + 2], 0.0f); }
+    c->owned_key_valid = false;
+    if ((rc = ensure_buf(c, c->owned, owned.size())) || (rc = ensure_buf(c, c->probe_pos, pos.size())) || (rc = ensure_buf(c, c->probe_acc, (size_t)PT_SH9_FLOATS * (size_t)w))) return rc;
+    HIP_TRY(c, hipMemcpy(c->owned.p, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->probe_pos.p, pos.data(), pos.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(c->probe_acc.p, 0, (size_t)PT_SH9_FLOATS * (size_t)w * sizeof(float), c->lanes[0].stream));
+    c->owned_n = (uint32_t)w;
+  } else if (!(c->owned_key_valid && c->owned_w == w && c->owned_h == h && c->owned_rank == tile_rank && c->owned_count == tile_count && c->owned.p)) {
     std::vector<uint32_t> owned;
     ptc_owned_pixels(w, h, tile_rank, tile_count, owned);
     c->owned_key_valid = false;
@@ -2046,6 +2073,59 @@ int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int 
   c->stats.n_emitters = keep.n_emitters; c->stats.bvh_max_depth = keep.bvh_max_depth;
   c->stats.bvh_sa_cost = keep.bvh_sa_cost; c->stats.bvh_sa_cost_built = keep.bvh_sa_cost_built; c->stats.seconds_rebuild = keep.seconds_rebuild;
   c->in_frame = true;
+  c->probe = probe_pos != nullptr; c->probe_base = probe_base;
+  return PTC_OK;
+}
+}  // namespace
+
+int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
+  return frame_begin(c, w, h, spp_total, seed, max_bounces, integrator, tile_rank, tile_count, nullptr, 0);
+}
+
+// ---- light probes (pt_probes.h) ------------------------------------------------------------------------------------------------
+#define PTC_MAX_PROBES (1 << 26)      // 9 lanes per probe and 27 sums per probe stay inside 32-bit indices
+int ptc_probes_begin(ptc_ctx* c, const float* positions_xyz, int n_probes, uint32_t probe_index_base, int spp_total, uint64_t seed, int max_bounces) {
+  if (!c) return PTC_E_ARG;
+  if (!positions_xyz) return fail(c, PTC_E_ARG, "probes_begin: null pointer");
+  if (n_probes < 1 || n_probes > PTC_MAX_PROBES) return fail(c, PTC_E_ARG, "probes_begin: n_probes outside 1..2^26");
+  if (spp_total < 1 || max_bounces < 0) return fail(c, PTC_E_ARG, "probes_begin: spp_total < 1 or max_bounces < 0");
+  if ((uint64_t)probe_index_base + (uint64_t)n_probes > 0x100000000ull) return fail(c, PTC_E_ARG, "probes_begin: probe indices exceed 32 bits");
+  for (size_t i = 0; i < (size_t)n_probes * 3; ++i)
+    if (!std::isfinite(positions_xyz[i])) return fail(c, PTC_E_ARG, "probes_begin: a position is not finite");
+  return frame_begin(c, n_probes, 1, spp_total, seed, max_bounces, PTC_INTEGRATOR_PATH, 0, 1, positions_xyz, probe_index_base);
+}
+
+int ptc_probes_read_sh(ptc_ctx* c, float* out) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!out) return fail(c, PTC_E_ARG, "probes_read_sh: null pointer");
+  if (!c->in_frame || !c->probe) return fail(c, PTC_E_STATE, "probes_read_sh: no probe frame (ptc_probes_begin)");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  const size_t n = (size_t)c->fr.n_owned * PT_SH9_FLOATS;
+  HIP_TRY(c, hipMemcpy(out, c->probe_acc.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  const uint32_t N = c->resolve_divisor ? c->resolve_divisor : c->samples_done;
+  if (N == 0) return PTC_OK;      // no sample yet: the sums are zero, and so are the coefficients
+  const float scale = pt_sh9_resolve_scale(N);
+  for (size_t i = 0; i < n; ++i) out[i] = out[i] * scale;
+  return PTC_OK;
+}
+
+int ptc_render_probes(ptc_ctx* c, const float* positions_xyz, int n_probes, int spp, uint64_t seed, int max_bounces, float* out) {
+  if (c && !out) return fail(c, PTC_E_ARG, "render_probes: null pointer");
+  int rc = ptc_probes_begin(c, positions_xyz, n_probes, 0, spp, seed, max_bounces);
+  if (rc) return rc;
+  if ((rc = ptc_frame_add_samples(c, spp))) return rc;
+  return ptc_probes_read_sh(c, out);
+}
+
+int ptc_sh9_eval(const float sh[27], const float dir[3], float out[3]) {
+  if (!sh || !dir || !out) return PTC_E_ARG;
+  pt_sh9_eval(sh, dir, out);
+  return PTC_OK;
+}
+int ptc_sh9_irradiance(const float sh[27], const float normal[3], float out[3]) {
+  if (!sh || !normal || !out) return PTC_E_ARG;
+  pt_sh9_irradiance(sh, normal, out);
   return PTC_OK;
 }
 
@@ -2107,6 +2187,7 @@ int ptc_frame_checkpoint(ptc_ctx* c, float* accum_rgba, uint64_t* n_owned_pixels
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_checkpoint: no frame");
   if (is_raster(c->integrator)) return fail(c, PTC_E_ARG, "frame_checkpoint: the raster integrators have nothing to resume");
   if (c->adaptive) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in an adaptive frame");
+  if (c->probe) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in a probe frame");
   { int rf = flush(c); if (rf) return rf; }
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   if (n_owned_pixels) *n_owned_pixels = c->fr.n_owned;
@@ -2118,6 +2199,7 @@ int ptc_frame_checkpoint(ptc_ctx* c, float* accum_rgba, uint64_t* n_owned_pixels
 int ptc_frame_restore(ptc_ctx* c, const float* accum_rgba, uint64_t n_owned_pixels, uint32_t samples_done) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_restore: no frame (ptc_frame_begin with the checkpointed frame's parameters first)");
+  if (c->probe) return fail(c, PTC_E_STATE, "frame_restore: not available in a probe frame");
   if (!accum_rgba) return fail(c, PTC_E_ARG, "frame_restore: null pointer");
   if (c->adaptive) return fail(c, PTC_E_STATE, "frame_restore: not available in an adaptive frame");
   if (c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_restore: call it right after ptc_frame_begin, before any sample");
@@ -2204,6 +2286,7 @@ int ensure_dn_events(ptc_ctx* c) {
 int ptc_frame_guides(ptc_ctx* c) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_guides: no frame");
+  if (c->probe) return fail(c, PTC_E_STATE, "frame_guides: a probe frame has no camera image to guide");
   if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_guides: the frame is not a PTC_INTEGRATOR_PATH frame (the raster integrators are noise-free)");
   const uint32_t n = (uint32_t)c->fr.w * (uint32_t)c->fr.h;      // every pixel, whatever the frame's tile share: the root of a sharded frame denoises the whole image
   int rc;
@@ -2279,6 +2362,7 @@ namespace {
 // sampled: the input is the radiance, demodulated by k_ad_sampled_variance, with the variance of the frame's own samples (§8d) where a pixel has four or more
 int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated, bool sampled) {
   { int rd = need_device(c); if (rd) return rd; }
+  if (c->probe) return fail(c, PTC_E_STATE, "denoise: a probe frame has no image to denoise");
   ptc_denoise_params p;
   ptc_denoise_default_params(&p);
   if (params) p = *params;
@@ -2339,6 +2423,7 @@ void ptc_temporal_default_params(ptc_temporal_params* p) {
 
 int ptc_temporal_accumulate(ptc_ctx* c, const ptc_temporal_params* params) {
   { int rd = need_device(c); if (rd) return rd; }
+  if (c->probe) return fail(c, PTC_E_STATE, "temporal_accumulate: a probe frame has no image to accumulate");
   ptc_temporal_params p;
   ptc_temporal_default_params(&p);
   if (params) p = *params;
@@ -2459,6 +2544,7 @@ int need_adaptive_frame(ptc_ctx* c, const char* who) {
 int ptc_frame_set_adaptive(ptc_ctx* c, const ptc_adaptive_params* params) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_set_adaptive: no frame");
+  if (c->probe) return fail(c, PTC_E_STATE, "frame_set_adaptive: not available in a probe frame");
   if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame is not a PTC_INTEGRATOR_PATH frame");
   if (c->adaptive || c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_set_adaptive: call it once, right after ptc_frame_begin, before any sample");
   if (c->resolve_divisor) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame has a resolve divisor (ptc_frame_set_sample_range)");
@@ -2557,6 +2643,7 @@ int ptc_get_adaptive_stats(ptc_ctx* c, ptc_adaptive_stats* out) {
 int ptc_set_sample_covariance(ptc_ctx* c, int on) {
   if (!c) return PTC_E_ARG;
   if (on != 0 && on != 1) return fail(c, PTC_E_ARG, "set_sample_covariance: 0 or 1");
+  if (on == 1 && c->probe) return fail(c, PTC_E_STATE, "set_sample_covariance: a probe frame keeps no per-sample covariance (the setting is unchanged)");
   c->cov_setting = on == 1;
   return PTC_OK;
 }
@@ -2664,6 +2751,7 @@ int ptc_comm_init(ptc_ctx* c, const uint8_t id[PTC_COMM_ID_BYTES], int rank, int
 
 int ptc_comm_reduce_radiance(ptc_ctx* c, int root) {
   { int rd = need_device(c); if (rd) return rd; }
+  if (c->probe) return fail(c, PTC_E_STATE, "comm_reduce_radiance: a probe frame is not a tile share of an image (shard probes by probe_index_base)");
   if (!c->comm) return fail(c, PTC_E_STATE, "comm_reduce_radiance: no communicator (ptc_comm_init / ptc_group_create)");
   if (root < 0 || root >= c->comm_size) return fail(c, PTC_E_ARG, "comm_reduce_radiance: bad root");
   if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "comm_reduce_radiance: nothing rendered");
@@ -2958,6 +3046,7 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     return fail(c, PTC_E_ARG, "debug_camera_rays: bad argument");
   for (uint32_t j = 0; j < n_pixels; ++j)
     if (pixels[j] >= (uint32_t)w * (uint32_t)h) return fail(c, PTC_E_ARG, "debug_camera_rays: pixel index outside the frame");
+  if (c->probe) return fail(c, PTC_E_STATE, "debug_camera_rays: a probe frame is in progress (its rays: ptc_debug_probe_rays)");
   const uint32_t n = n_pixels * n_samples;
   const uint32_t seed_hash = frame_seed_hash(seed);
   if (c->device < 0) {      // the host evaluation of pt_lens.h
@@ -2993,6 +3082,106 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     origins[p * 3] = A[p].x; origins[p * 3 + 1] = A[p].y; origins[p * 3 + 2] = A[p].z;
     dirs[p * 3] = A[p].w; dirs[p * 3 + 1] = B[p].x; dirs[p * 3 + 2] = B[p].y;
   }
+  return PTC_OK;
+}
+
+namespace {
+// what the two probe hooks need of debug_prepare: a device, idle lanes, the frame ended, lane 0's queues for n paths.  No scene: neither kernel reads one.
+int probe_debug_prepare(ptc_ctx* c, uint32_t n) {
+  { int rd = need_device(c); if (rd) return rd; }
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  c->in_frame = false; c->pending = 0; drop_guides(c);
+  return ensure_lane_queues(c, n);
+}
+bool probe_debug_args_bad(int n, uint32_t base, uint32_t first_sample, uint32_t n_samples) {
+  return n < 1 || n > PTC_MAX_PROBES || n_samples == 0 || (uint64_t)n * (uint64_t)n_samples > 0x7fffffffull || (uint64_t)first_sample + n_samples > 0x100000000ull ||
+         (uint64_t)base + (uint64_t)n > 0x100000000ull;
+}
+}  // namespace
+
+int ptc_debug_probe_rays(ptc_ctx* c, const float* positions_xyz, int n_probes, uint32_t probe_index_base, uint64_t seed, uint32_t first_sample, uint32_t n_samples,
+                         float* out_o_d, uint32_t* out_key) {
+  if (!c) return PTC_E_ARG;
+  if (!positions_xyz || !out_o_d || !out_key || probe_debug_args_bad(n_probes, probe_index_base, first_sample, n_samples)) return fail(c, PTC_E_ARG, "debug_probe_rays: bad argument");
+  const uint32_t np = (uint32_t)n_probes, n = np * n_samples;
+  const uint32_t seed_hash = frame_seed_hash(seed);
+  if (c->device < 0) {      // the host evaluation of pt_probes.h
+    for (uint32_t p = 0; p < n; ++p) {
+      const uint32_t j = p % np;
+      float* o = out_o_d + (size_t)p * 6;
+      for (int k = 0; k < 3; ++k) o[k] = positions_xyz[(size_t)j * 3 + k];
+      pt_probe_dir(seed_hash, probe_index_base + j, first_sample + p / np, o + 3, out_key[p]);
+    }
+    return PTC_OK;
+  }
+  { int rc = probe_debug_prepare(c, n); if (rc) return rc; }
+  const Lane& ln = c->lanes[0];
+  DevBuf<float4> pos;
+  { int rc = ensure_buf(c, pos, np); if (rc) return rc; }
+  std::vector<float4> P(np), A(n), B(n), C(n);
+  for (uint32_t j = 0; j < np; ++j) P[j] = make_float4(positions_xyz[(size_t)j * 3], positions_xyz[(size_t)j * 3 + 1], positions_xyz[(size_t)j * 3 + 2], 0.0f);
+  hipError_t e = hipMemcpy(pos.p, P.data(), (size_t)np * sizeof(float4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    pt_launch_raygen_probe(ln.stream, pos.p, np, probe_index_base, seed_hash, batch_queues(c, 0, n), first_sample, n_samples);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
+  if (e == hipSuccess) e = hipMemcpy(A.data(), ln.q.ray[0].A, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(B.data(), ln.q.ray[0].B, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(C.data(), ln.q.ray[0].C, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+  pos.release();      // the positions live for this call only
+  if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_probe_rays: ") + hipGetErrorString(e));
+  for (size_t p = 0; p < n; ++p) {
+    float* o = out_o_d + p * 6;
+    o[0] = A[p].x; o[1] = A[p].y; o[2] = A[p].z; o[3] = A[p].w; o[4] = B[p].x; o[5] = B[p].y;
+    std::memcpy(&out_key[p], &C[p].w, 4);
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_probe_project(ptc_ctx* c, int n_probes, uint32_t probe_index_base, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const float* lpath_rgba,
+                            float* acc_inout) {
+  if (!c) return PTC_E_ARG;
+  if (!lpath_rgba || !acc_inout || probe_debug_args_bad(n_probes, probe_index_base, first_sample, n_samples)) return fail(c, PTC_E_ARG, "debug_probe_project: bad argument");
+  const uint32_t np = (uint32_t)n_probes, n = np * n_samples;
+  const uint32_t seed_hash = frame_seed_hash(seed);
+  if (c->device < 0) {      // the host evaluation of pt_probes.h: k_accumulate_sh's sums, sample by sample
+    for (uint32_t j = 0; j < np; ++j)
+      for (uint32_t s = 0; s < n_samples; ++s) {
+        const float* L = lpath_rgba + ((size_t)s * np + j) * 4;
+        float d[3]; uint32_t key;
+        pt_probe_dir(seed_hash, probe_index_base + j, first_sample + s, d, key);
+        for (int k = 0; k < PT_SH9; ++k) {
+          const float b = pt_sh9_basis(k, d[0], d[1], d[2]);
+          float* a = acc_inout + (size_t)j * PT_SH9_FLOATS + (size_t)k * 3;
+          for (int ch = 0; ch < 3; ++ch) a[ch] = a[ch] + L[ch] * b;
+        }
+      }
+    return PTC_OK;
+  }
+  { int rc = probe_debug_prepare(c, n); if (rc) return rc; }
+  const Lane& ln = c->lanes[0];
+  DevBuf<float> acc;
+  const size_t na = (size_t)np * PT_SH9_FLOATS;
+  { int rc = ensure_buf(c, acc, na); if (rc) return rc; }
+  hipError_t e = hipMemcpy(acc.p, acc_inout, na * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ln.q.lpath, lpath_rgba, (size_t)n * sizeof(float4), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    pt_launch_accumulate_sh(ln.stream, np, probe_index_base, seed_hash, ln.q.lpath, acc.p, first_sample, n_samples);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
+  if (e == hipSuccess) e = hipMemcpy(acc_inout, acc.p, na * sizeof(float), hipMemcpyDeviceToHost);
+  acc.release();
+  if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_probe_project: ") + hipGetErrorString(e));
+  return PTC_OK;
+}
+
+int ptc_debug_probe_resolve(const float* acc, int n_probes, uint32_t n_samples, float* out) {
+  if (!acc || !out || n_probes < 1 || n_probes > PTC_MAX_PROBES || n_samples == 0) return PTC_E_ARG;
+  const float scale = pt_sh9_resolve_scale(n_samples);
+  for (size_t i = 0; i < (size_t)n_probes * PT_SH9_FLOATS; ++i) out[i] = acc[i] * scale;
   return PTC_OK;
 }
 

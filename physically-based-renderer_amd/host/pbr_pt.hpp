@@ -263,6 +263,26 @@ public:
     ck(ptc_sync(_ctx));
     return readRadiance(w, h);
   }
+  // light probes (ptc_probes_begin ...): positions = 3 floats per probe; 27 floats per probe come back, laid out [probe][k][rgb]
+  auto renderProbes(std::vector<float> const& positions, int spp, std::uint64_t seed = 0, int maxBounces = 8) -> std::vector<float> {
+    std::vector<float> out(positions.size() / 3 * 27);
+    ck(ptc_render_probes(_ctx, positions.data(), (int)(positions.size() / 3), spp, seed, maxBounces, out.data()));
+    _probes = positions.size() / 3;      // the probe frame stays in progress: readProbesSh() may follow
+    return out;
+  }
+  // the caller-driven form: beginProbes(), ptc_frame_add_samples as in any frame, readProbesSh() whenever coefficients are wanted; indexBase shards a probe set
+  auto beginProbes(std::vector<float> const& positions, int sppTotal, std::uint64_t seed = 0, int maxBounces = 8, std::uint32_t indexBase = 0) -> void {
+    ck(ptc_probes_begin(_ctx, positions.data(), (int)(positions.size() / 3), indexBase, sppTotal, seed, maxBounces));
+    _probes = positions.size() / 3;
+  }
+  auto readProbesSh() -> std::vector<float> {
+    if (!_probes) throw std::runtime_error("readProbesSh: no probe frame was begun through this object (beginProbes / renderProbes)");
+    std::vector<float> out(_probes * 27);      // ptc_probes_read_sh writes 27 floats per probe of the frame in progress
+    ck(ptc_probes_read_sh(_ctx, out.data()));
+    return out;
+  }
+  static auto sh9Eval(float const* sh27, std::array<float, 3> const& dir) -> std::array<float, 3> { std::array<float, 3> o{}; ptc_sh9_eval(sh27, dir.data(), o.data()); return o; }
+  static auto sh9Irradiance(float const* sh27, std::array<float, 3> const& normal) -> std::array<float, 3> { std::array<float, 3> o{}; ptc_sh9_irradiance(sh27, normal.data(), o.data()); return o; }
   auto stats() -> ptc_stats { ptc_stats s; ck(ptc_get_stats(_ctx, &s)); return s; }
   auto handle() -> ptc_ctx* { return _ctx; }
 
@@ -271,6 +291,7 @@ private:
   ptc_ctx* _ctx;
   bool _owned = true;
   int _w = 0, _h = 0;
+  std::size_t _probes = 0;
 };
 
 // Several GPUs driven by one process (ptc_group: one context per device + an RCCL communicator): the scene described on device(0) is

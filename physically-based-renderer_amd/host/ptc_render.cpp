@@ -6,6 +6,10 @@
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
 //              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
+//              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
+// --probe-grid NX,NY,NZ / --probes FILE with --probes-out sh.pfm: bake light probes instead of an image (ptc_render_probes) — the centres of the
+// NX x NY x NZ cells of the scene's bounding box (x fastest, then y, then z; the grid's origin and cell size are printed), or the `x y z` lines of a text file —
+// at --spp samples each, --seed, --bounces.  sh.pfm is a 9 x n RGB image: row j holds the nine SH coefficients of probe j.  One context, path integrator.
 // --exposure EV / --auto-exposure / --tonemap / --srgb: the display transform (ptc_set_display) for --png, --ppm and --half.  --exposure multiplies the
 // radiance by 2^EV; --auto-exposure meters the image on the device (ptc_meter_exposure) and maps its metered luminance to the key K (default 0.18), times 2^EV;
 // --tonemap picks the operator (neutral: Khronos PBR Neutral) and --srgb the sRGB transfer function instead of gamma 2.2; --half then holds the exposed radiance.
@@ -210,6 +214,8 @@ int main(int argc, char** argv) {
   ptc_display_params disp = pbr::PathTraceRenderSystem::displayDefaults();      // --exposure / --auto-exposure / --key / --tonemap / --srgb
   bool useDisplay = false, haveKey = false;
   double exposureEv = 0.0;
+  int probeGrid[3] = {0, 0, 0};              // --probe-grid
+  std::string probesFile, probesOut;         // --probes, --probes-out
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -236,6 +242,8 @@ int main(int argc, char** argv) {
       else if (f == "clamp") disp.tonemap = PTC_TONEMAP_CLAMP; else { std::cerr << "--tonemap aces|neutral|reinhard|clamp\n"; return 2; }
       useDisplay = true;
     }
+    else if (a == "--probe-grid") { if (std::sscanf(next(), "%d,%d,%d", &probeGrid[0], &probeGrid[1], &probeGrid[2]) != 3) { std::cerr << "--probe-grid NX,NY,NZ\n"; return 2; } }
+    else if (a == "--probes") probesFile = next(); else if (a == "--probes-out") probesOut = next();
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -272,6 +280,23 @@ int main(int argc, char** argv) {
       if (!std::isfinite(exposureEv) || !(disp.gain > 0.0f) || !std::isfinite(disp.gain)) throw std::runtime_error("--exposure EV: 2^EV must be a finite float > 0");
       if (haveKey && !disp.auto_exposure) throw std::runtime_error("--key K sets the target of --auto-exposure");
       if (!(disp.key > 0.0f) || !std::isfinite(disp.key)) throw std::runtime_error("--key K: a finite value > 0");
+    }
+    const bool haveGrid = probeGrid[0] || probeGrid[1] || probeGrid[2], bakeProbes = haveGrid || !probesFile.empty() || !probesOut.empty();
+    std::vector<float> probePos;
+    if (bakeProbes) {      // light probes: refused here, before a device is touched
+      if (probesOut.empty()) throw std::runtime_error("--probe-grid / --probes need --probes-out sh.pfm");
+      if (haveGrid == !probesFile.empty()) throw std::runtime_error("--probes-out needs either --probe-grid NX,NY,NZ or --probes FILE");
+      if (gpus != 0 || integrator != PTC_INTEGRATOR_PATH || adaptive || denoise) throw std::runtime_error("probes are baked on one context with the path integrator (not with --gpus / --raster / --adaptive / --denoise)");
+      if (haveGrid && (probeGrid[0] < 1 || probeGrid[1] < 1 || probeGrid[2] < 1 || (long long)probeGrid[0] * probeGrid[1] * probeGrid[2] > (1ll << 26)))
+        throw std::runtime_error("--probe-grid NX,NY,NZ: three counts >= 1, at most 2^26 probes");
+      if (spp < 1) throw std::runtime_error("--spp N: at least one sample per probe");
+      if (!probesFile.empty()) {
+        std::ifstream f(probesFile);
+        if (!f) throw std::runtime_error("--probes: cannot read " + probesFile);
+        float x, y, z;
+        while (f >> x >> y >> z) { probePos.push_back(x); probePos.push_back(y); probePos.push_back(z); }
+        if (!f.eof() || probePos.empty()) throw std::runtime_error("--probes FILE: lines of `x y z`, at least one");
+      }
     }
     for (const std::string& sp : lightSpecs) lights.push_back(parseLight(sp));
     if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
@@ -354,6 +379,35 @@ int main(int argc, char** argv) {
       single.reset(new pbr::PathTraceRenderSystem(device));
       buildScene(*single);
       applyLights(*single);
+      if (bakeProbes) {
+        pbr::PathTraceRenderSystem& rs = *single;
+        if (haveGrid) {      // the cell centres of the committed scene's bounding box
+          std::uint32_t nv = 0, nt = 0;
+          if (ptc_debug_get_flat_scene(rs.handle(), &nv, &nt, nullptr, nullptr, nullptr) < 0 || nv == 0) throw std::runtime_error("--probe-grid: the scene has no geometry");
+          std::vector<ptc_vertex> verts(nv);
+          if (ptc_debug_get_flat_scene(rs.handle(), &nv, &nt, verts.data(), nullptr, nullptr) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+          float lo[3] = {verts[0].position[0], verts[0].position[1], verts[0].position[2]}, hi[3] = {lo[0], lo[1], lo[2]}, cell[3];
+          for (const ptc_vertex& v : verts)
+            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], v.position[k]); hi[k] = std::max(hi[k], v.position[k]); }
+          for (int k = 0; k < 3; ++k) cell[k] = (hi[k] - lo[k]) / (float)probeGrid[k];
+          for (int z = 0; z < probeGrid[2]; ++z)
+            for (int y = 0; y < probeGrid[1]; ++y)
+              for (int x = 0; x < probeGrid[0]; ++x) {
+                probePos.push_back(lo[0] + ((float)x + 0.5f) * cell[0]); probePos.push_back(lo[1] + ((float)y + 0.5f) * cell[1]); probePos.push_back(lo[2] + ((float)z + 0.5f) * cell[2]);
+              }
+          std::printf("{\"probe_grid\": [%d, %d, %d], \"origin\": [%.9g, %.9g, %.9g], \"cell\": [%.9g, %.9g, %.9g]}\n", probeGrid[0], probeGrid[1], probeGrid[2], (double)lo[0], (double)lo[1],
+                      (double)lo[2], (double)cell[0], (double)cell[1], (double)cell[2]);
+        }
+        const std::size_t n = probePos.size() / 3;
+        const std::vector<float> sh = rs.renderProbes(probePos, spp, seed, bounces);
+        std::vector<float> rows(n * 9 * 4);      // the writer takes RGBA: 9 pixels per probe
+        for (std::size_t p = 0; p < n * 9; ++p) { rows[p * 4] = sh[p * 3]; rows[p * 4 + 1] = sh[p * 3 + 1]; rows[p * 4 + 2] = sh[p * 3 + 2]; rows[p * 4 + 3] = 1.0f; }
+        pbr::image::write_pfm(probesOut, rows.data(), 9, (int)n);
+        const ptc_stats st = rs.stats();
+        std::printf("{\"scene\": \"%s\", \"probes\": %zu, \"spp\": %d, \"paths\": %llu, \"seconds_render\": %.6f, \"mpaths_per_s\": %.2f}\n", (gltf.empty() ? scene : gltf).c_str(), n, spp,
+                    (unsigned long long)st.paths, st.seconds_render, st.seconds_render > 0 ? st.paths / st.seconds_render / 1e6 : 0.0);
+        return 0;
+      }
       applyLens(*single);
       if (denoiseSampled) single->setSampleCovariance(true);
       img = adaptive ? single->renderAdaptive(w, h, spp, seed, bounces, &ap) : denoiseSampled ? single->renderWithStatistics(w, h, spp, seed, bounces)

@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "ptc_display_default_params", "ptc_set_display", "ptc_get_display", "ptc_meter_exposure", "ptc_exposure_reset", "ptc_get_exposure", "ptc_read_luminance_histogram",
     "ptc_display_rgba8", "ptc_display_rgba16f", "ptc_display_rgba16f_device_ptr", "ptc_get_display_seconds",
     "ptc_debug_display_pixel", "ptc_debug_meter", "ptc_debug_display_internals", "ptc_debug_display_state",
+    "ptc_probes_begin", "ptc_probes_read_sh", "ptc_render_probes", "ptc_sh9_eval", "ptc_sh9_irradiance",
+    "ptc_debug_probe_rays", "ptc_debug_probe_project", "ptc_debug_probe_resolve",
     "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
 ]
 
@@ -305,6 +307,14 @@ def load_library():
     L.ptc_debug_meter.argtypes = [dpp, fp, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p, u64p, u32p]
     L.ptc_debug_display_internals.argtypes = [vp, u64p]
     L.ptc_debug_display_state.argtypes = [vp, u32p]
+    L.ptc_probes_begin.argtypes = [vp, fp, C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_int]
+    L.ptc_probes_read_sh.argtypes = [vp, fp]
+    L.ptc_render_probes.argtypes = [vp, fp, C.c_int, C.c_int, C.c_uint64, C.c_int, fp]
+    L.ptc_sh9_eval.argtypes = [fp, fp, fp]
+    L.ptc_sh9_irradiance.argtypes = [fp, fp, fp]
+    L.ptc_debug_probe_rays.argtypes = [vp, fp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, fp, u32p]
+    L.ptc_debug_probe_project.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, fp, fp]
+    L.ptc_debug_probe_resolve.argtypes = [fp, C.c_int, C.c_uint32, fp]
     L.ptc_comm_unique_id.argtypes = [u8p]
     L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
     L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
@@ -349,6 +359,44 @@ def lens_sample(u1, u2, aperture_radius=1.0, blades=0, rotation=0.0):
             raise PtcError(f"lens_sample: bad lens parameters or u outside [0, 1): {p.as_dict()}, ({a[i]}, {b[i]})")
         out[i] = xy[0], xy[1]
     return out if np.ndim(u1) else (float(out[0, 0]), float(out[0, 1]))
+
+
+def _sh9_apply(fn, name, sh, vecs):
+    sh = np.ascontiguousarray(sh, np.float32)
+    v = np.ascontiguousarray(vecs, np.float32)
+    if sh.shape[-2:] != (9, 3) or v.shape[-1:] != (3,):
+        raise PtcError(f"{name}: sh must end in (9, 3) and the directions in (3,), got {sh.shape} and {v.shape}")
+    lead = np.broadcast_shapes(sh.shape[:-2], v.shape[:-1])
+    shb = np.ascontiguousarray(np.broadcast_to(sh, lead + (9, 3))).reshape(-1, 27)
+    vb = np.ascontiguousarray(np.broadcast_to(v, lead + (3,))).reshape(-1, 3)
+    out = np.zeros((shb.shape[0], 3), np.float32)
+    P = C.POINTER(C.c_float)
+    for i in range(shb.shape[0]):
+        if fn(shb[i].ctypes.data_as(P), vb[i].ctypes.data_as(P), out[i].ctypes.data_as(P)) < 0:
+            raise PtcError(f"{name}: bad argument")
+    return out.reshape(lead + (3,))
+
+
+def sh9_eval(sh, dirs):
+    """ptc_sh9_eval: the radiance sum_k sh_k Y_k(dir) of SH9 coefficients sh (..., 9, 3) from the unit directions dirs (..., 3); leading shapes broadcast;
+    (..., 3) float32.  The host's evaluation of csrc/pt_probes.h."""
+    return _sh9_apply(load_library().ptc_sh9_eval, "sh9_eval", sh, dirs)
+
+
+def sh9_irradiance(sh, normals):
+    """ptc_sh9_irradiance: the irradiance on a surface with the unit normals (..., 3) under the radiance the SH9 coefficients sh (..., 9, 3) describe
+    (Ramamoorthi-Hanrahan: A = pi, 2 pi / 3, pi / 4 per band); (..., 3) float32."""
+    return _sh9_apply(load_library().ptc_sh9_irradiance, "sh9_irradiance", sh, normals)
+
+
+def probe_resolve(acc, n_samples):
+    """ptc_debug_probe_resolve: running sums (n, 9, 3) -> coefficients, acc * (4 pi / n_samples) in float32."""
+    a = np.ascontiguousarray(acc, np.float32).reshape(-1, 9, 3)
+    out = np.zeros_like(a)
+    P = C.POINTER(C.c_float)
+    if load_library().ptc_debug_probe_resolve(a.ctypes.data_as(P), a.shape[0], int(n_samples), out.ctypes.data_as(P)) < 0:
+        raise PtcError("probe_resolve: bad argument")
+    return out
 
 
 def light_default_params():
@@ -678,6 +726,62 @@ class PathTracer:
     def frame_begin(self, w, h, spp_total, seed=1, max_bounces=8, integrator=INTEGRATOR_PATH, tile_rank=0, tile_count=1):
         self._ck(self._L.ptc_frame_begin(self._h, w, h, spp_total, seed, max_bounces, integrator, tile_rank, tile_count))
         self._w, self._h_px = w, h
+
+    # ---- light probes (csrc/pt_probes.h) ----------------------------------------------------------------
+    @staticmethod
+    def _probe_positions(positions):
+        p = np.ascontiguousarray(positions, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise PtcError(f"probe positions must be (n, 3), got {p.shape}")
+        return p
+
+    def probes_begin(self, positions, spp_total, seed=0, max_bounces=8, index_base=0):
+        """ptc_probes_begin: a probe frame of len(positions) probes; frame_add_samples / frame_set_sample_range / sync work as in any frame, and after
+        frame_resolve read_radiance returns the (1, n, 4) image of each probe's mean incoming radiance."""
+        p = self._probe_positions(positions)
+        self._ck(self._L.ptc_probes_begin(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], index_base, spp_total, seed, max_bounces))
+        self._w, self._h_px = p.shape[0], 1
+        self._n_probes = p.shape[0]
+
+    def read_probes_sh(self):
+        """ptc_probes_read_sh: the SH9 coefficients of the probe frame in progress, (n, 9, 3) float32 laid out [probe][k][rgb]."""
+        out = np.zeros((getattr(self, "_n_probes", 0) or 1, 9, 3), np.float32)
+        self._ck(self._L.ptc_probes_read_sh(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_probes(self, positions, spp, seed=0, max_bounces=8, index_base=0):
+        """Bake the probes at `positions` (n, 3) with spp samples each: (n, 9, 3) float32 SH9 coefficients of the incoming radiance (sh9_irradiance turns them
+        into the irradiance for a normal).  ptc_render_probes when index_base is 0; index_base shards a probe set: the probes [a, b) with index_base = a are
+        bit for bit those of the whole set."""
+        p = self._probe_positions(positions)
+        if index_base == 0:
+            out = np.zeros((p.shape[0], 9, 3), np.float32)
+            self._ck(self._L.ptc_render_probes(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], spp, seed, max_bounces, out.ctypes.data_as(C.POINTER(C.c_float))))
+            self._w, self._h_px, self._n_probes = p.shape[0], 1, p.shape[0]
+            return out
+        self.probes_begin(p, spp, seed, max_bounces, index_base)
+        self.frame_add_samples(spp)
+        return self.read_probes_sh()
+
+    def debug_probe_rays(self, positions, seed, first_sample, n_samples, index_base=0):
+        """ptc_debug_probe_rays: (origins, dirs, keys) of the probe rays in path order p = sample_local * n + j: (n_samples * n, 3) float32 twice and uint32."""
+        p = self._probe_positions(positions)
+        n = p.shape[0] * int(n_samples)
+        od, key = np.zeros((n, 6), np.float32), np.zeros(n, np.uint32)
+        self._ck(self._L.ptc_debug_probe_rays(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], index_base, seed, first_sample, n_samples,
+                                              od.ctypes.data_as(C.POINTER(C.c_float)), key.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return od[:, :3].copy(), od[:, 3:].copy(), key
+
+    def debug_probe_project(self, n_probes, seed, first_sample, n_samples, lpath, acc=None, index_base=0):
+        """ptc_debug_probe_project: the running sums (n, 9, 3) after adding the projection of lpath (n_samples * n, 4) to acc (zeros when None)."""
+        L = np.ascontiguousarray(lpath, np.float32).reshape(-1, 4)
+        if L.shape[0] != int(n_probes) * int(n_samples):
+            raise PtcError(f"debug_probe_project: lpath has {L.shape[0]} paths, expected {int(n_probes) * int(n_samples)}")
+        a = np.zeros((n_probes, 9, 3), np.float32) if acc is None else np.array(acc, np.float32).reshape(n_probes, 9, 3)
+        a = np.ascontiguousarray(a)
+        self._ck(self._L.ptc_debug_probe_project(self._h, n_probes, index_base, seed, first_sample, n_samples, L.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 a.ctypes.data_as(C.POINTER(C.c_float))))
+        return a
 
     def frame_checkpoint(self):
         """(per-pixel sums as an opaque (n_owned, 4) float32 array, samples in them) of the frame in progress (ptc_frame_checkpoint)."""
