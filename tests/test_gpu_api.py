@@ -458,3 +458,34 @@ def test_checkpoint_resume_and_sample_ranges(gpu):
     pt.frame_add_samples(1)
     with pytest.raises(gpu.PtcError):
         pt.frame_set_sample_range(4, spp)                            # only before the first sample
+
+
+def test_destroy_after_every_image_space_feature(gpu):
+    """One context bakes probes, renders an adaptive frame, traces guides, accumulates, denoises, meters and displays, and is then destroyed: each feature's device
+    memory and events are owned by its member of the context (csrc/ptc_ctx.h) and go with it.  Every stage timer has recorded, closing twice is harmless, and a
+    context made afterwards renders, bit for bit, what one that used none of the features renders."""
+    d = gpu.scenes.cornell_box()
+    w, h = 32, 24
+    plain = gpu.PathTracer(0).load_scene(d)
+    want = plain.render(w, h, 2, seed=3, max_bounces=2)
+    plain.close()
+    pt = gpu.PathTracer(0).load_scene(d)
+    sh = pt.render_probes(np.array([[0.0, 0.0, 0.0], [0.2, -0.1, 0.1]], np.float32), 4, seed=1, max_bounces=2)
+    assert sh.shape == (2, 9, 3) and np.isfinite(sh).all()
+    pt.render_adaptive(w, h, 8, seed=3, max_bounces=2, min_samples=4, step_samples=4)
+    assert pt.adaptive_stats()["passes"] >= 1
+    pt.frame_guides()
+    pt.frame_resolve()
+    pt.temporal_accumulate()
+    pt.denoise()
+    pt.select_output(gpu.ptc.OUTPUT_DENOISED)
+    pt.meter_exposure()
+    assert pt.display().shape[:2] == (h, w)
+    assert np.isfinite(pt.read_radiance()).all()
+    for seconds in (*pt.denoise_seconds(), pt.temporal_seconds(), *pt.display_seconds()):
+        assert seconds > 0.0
+    pt.close()
+    pt.close()
+    after = gpu.PathTracer(0).load_scene(d)
+    assert _bits_equal(after.render(w, h, 2, seed=3, max_bounces=2), want)
+    after.close()

@@ -717,7 +717,7 @@ def _coincident_scene(gpu):
 @pytest.mark.parametrize("name,kw", [("cornell", {}), ("sphere10k", {}), ("atrium", {"scale": 0.05}), ("textured_atrium", {"scale": 0.05, "tex_size": 64, "env_size": (64, 32)}),
                                      ("textured_objects", {}), ("coincident", {}), ("atrium", {})])
 def test_commit_on_the_device_writes_the_bytes_of_the_host_lbvh_commit(gpu, ora, name, kw):
-    """ptc_scene_commit with the LBVH builder on a device context (csrc/ptc_api.cpp device_commit): the host only describes — indices, materials, the emitter table from
+    """ptc_scene_commit with the LBVH builder on a device context (csrc/ptc_api_scene.cpp device_commit): the host only describes — indices, materials, the emitter table from
     the emissive primitives, textures —, the device flattens the vertices, writes the shading records around their two seeded indices and builds the tree.  What then lies in
     HBM — unit array, origin grid, shading records (padding included), emitters, cdf, world vertices — is byte for byte what the host's commit of the same description
     (PTC_COMMIT=host on the same device, and a description-only context) computes; statistics, launch configuration, image and traversal counters agree, the counters with the

@@ -385,7 +385,7 @@ def test_host_share_of_the_device_refit(pbr, name, kw, builder):
 
 @pytest.mark.parametrize("name,kw", [("cornell", {}), ("sphere10k", {}), ("atrium", {"scale": 0.05}), ("textured_objects", {}), ("textured_atrium", {"scale": 0.03, "tex_size": 32, "env_size": (32, 16)})])
 def test_host_share_of_the_device_commit(pbr, name, kw):
-    """ptc_scene_commit with the LBVH builder on a device context lets the device flatten and build (csrc/ptc_api.cpp device_commit, tested on the GPU); what the host
+    """ptc_scene_commit with the LBVH builder on a device context lets the device flatten and build (csrc/ptc_api_scene.cpp device_commit, tested on the GPU); what the host
     contributes needs none: ptc_build_skeleton — world vertex indices and material per primitive, the material table, the emitter index of every primitive with the emitter table
     and its cdf from the emissive primitives ALONE (each vertex through its instance's matrix, no flatten), textures, texture sets, environment tables — must be, bit for bit, what
     the full host build of the same description holds; also after the instances have moved and the scene was committed again, and with an emitter collapsed to zero area."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ptc_scene_commit with the LBVH builder ON THE DEVICE (flatten, shading records, tree: csrc/ptc_api.cpp device_commit), n times on fresh contexts of one process, next to the host's
+"""ptc_scene_commit with the LBVH builder ON THE DEVICE (flatten, shading records, tree: csrc/ptc_api_scene.cpp device_commit), n times on fresh contexts of one process, next to the host's
 commit of the same description (PTC_COMMIT=host) and the default SAH commit.  Under `rocprofv3 --kernel-trace --stats` the k_refit_* / k_bld_* / k_sort_* rows are the device's share.
 usage: python3 tools/commit_bench.py [atrium|textured] [n]"""
 import copy, json, os, sys, time
