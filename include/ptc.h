@@ -742,7 +742,7 @@ int ptc_debug_get_material(ptc_ctx*, int index, float out_factors[9], int out_te
 int ptc_debug_get_texture(ptc_ctx*, int index, int* w, int* h, uint8_t* rgba);
 
 /* Raw device counter array of the current frame (segments, shadow rays, hits, node/triangle counts, then the
- * loop-iteration diagnostics a -DPT_DIAG build fills).  Returns the number of counters the library keeps. */
+ * loop-iteration diagnostics that only an instrumented build fills: profiles/instr_diag.patch, built with EXTRA=-DPT_DIAG).  Returns the number of counters the library keeps. */
 int ptc_debug_get_counters(ptc_ctx*, uint64_t* out, int n);
 
 /* The flattened 8-wide BVH as committed: ONE array of n_units 16-byte units (n_units*4 32-bit words) holding 64-byte nodes

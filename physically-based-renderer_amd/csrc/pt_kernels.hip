@@ -281,11 +281,7 @@ PT_DEV uint32_t node_visit(const DevScene& sc, uint32_t node_addr, int cur, cons
     for (int i = 3; i >= 0; --i) {      // slot 4h+i; descending, so that shifting the results in leaves slot s in bit s
       const float tn = hw_max(hw_max(hw_max(pt_fma(ubyte_f(nqx, i), ax, bx), pt_fma(ubyte_f(nqy, i), ay, by)), pt_fma(ubyte_f(nqz, i), az, bz)), tmin);
       const float tf = hw_min(hw_min(hw_min(pt_fma(ubyte_f(fqx, i), ax, bx), pt_fma(ubyte_f(fqy, i), ay, by)), pt_fma(ubyte_f(fqz, i), az, bz)), tlimit);
-#ifndef PT_NO_ADDC
       asm("v_cmp_le_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(hits) : "v"(tn), "v"(tf) : "vcc");   // hits = 2·hits + (tn <= tf)
-#else
-      hits = hits + hits + (tn <= tf ? 1u : 0u);
-#endif
     }
   }
   masks = w2 >> 8;
@@ -326,36 +322,6 @@ PT_DEV uint32_t next_triangle(uint32_t tbase, uint32_t& tmask) {
   const bool more = second == 0u && ((tmask >> (16u + sl)) & 1u) != 0u;
   tmask = more ? (tmask | (1u << 24)) : ((tmask & 0x00ffffffu) & ~(1u << sl));
   return k;
-}
-
-// triangles still pending in a lane's set (after next_triangle took some)
-PT_DEV uint32_t pending_triangles(uint32_t tmask) {
-  const uint32_t lh = tmask & 255u;
-  return (uint32_t)__builtin_popcount(lh) + (uint32_t)__builtin_popcount((tmask >> 16) & lh) - (tmask >> 24);
-}
-#ifndef LEAF_EXTRA
-#define LEAF_EXTRA 1     // triangles a lane may hand to free lanes per leaf pass
-#endif
-// Leaf pass, work distribution: every lane at a leaf tests one triangle itself and hands up to LEAF_EXTRA more to lanes that are not at a leaf.
-// `extra` (0..LEAF_EXTRA) is what the lane would hand out; tasks are numbered by the exclusive prefix of `extra` over the lanes (ballot per bit of
-// `extra` + mbcnt) and the first `ntask` = min(total, free lanes) of them find a helper: task i goes to the i-th free lane.
-struct LeafDeal { uint32_t off, take, ntask, rank_free; bool helper; };
-PT_DEV LeafDeal leaf_deal(uint32_t extra, bool leaf, uint64_t m_leaf) {
-  LeafDeal d;
-  uint32_t off = 0, total = 0;
-#pragma unroll
-  for (int b = 0; (1 << b) <= LEAF_EXTRA; ++b) {
-    const uint64_t m = __ballot(((extra >> b) & 1u) != 0u);
-    off += mbcnt64(m) << b; total += (uint32_t)__popcll(m) << b;
-  }
-  const uint64_t m_free = ~m_leaf;
-  const uint32_t n_free = (uint32_t)__popcll(m_free);
-  d.rank_free = mbcnt64(m_free);
-  d.ntask = total < n_free ? total : n_free;
-  d.helper = !leaf && d.rank_free < d.ntask;
-  d.off = off;
-  d.take = off >= d.ntask ? 0u : (d.ntask - off < extra ? d.ntask - off : extra);
-  return d;
 }
 
 // Wave-private reservoir of input slots: idle lanes are refilled from a chunk of consecutive rays of one queue segment (ballot +
@@ -454,12 +420,6 @@ struct RayRing {
   }
 };
 
-#ifdef PT_DIAG
-#define DIAG_ITER(var) do { const uint64_t m_ = __ballot(true); if ((int)lane == __ffsll((unsigned long long)m_) - 1) ++(var); } while (0)
-#else
-#define DIAG_ITER(var) do { } while (0)
-#endif
-
 // LDS of a trace block: [n_lds_units × 16 B: the top of the tree][waves × L × 64 stack entries of 8 B][2 KiB slot-order table (closest hit only)][waves × RING_FIELDS × TRACE_RING words: the prepared rays]
 struct TraceLds { uint32_t top_addr; uint2* stack; uint8_t* order_tab; uint32_t* ring; };
 PT_DEV TraceLds trace_lds(float4* lds_raw, const DevScene& sc, int stack_lds, bool closest) {
@@ -504,14 +464,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
   const RayQ rq = q.ray[qi];
   unsigned long long nv = 0, nr = 0, nh = 0;   // wave totals, only updated at wave-uniform points: they live in SGPRs
   uint32_t nt = 0;                               // per lane (updated inside the divergent leaf phase)
-  uint32_t d_node = 0, d_tri = 0, d_round = 0, d_leftpass = 0, d_left = 0;
-  (void)d_node; (void)d_tri; (void)d_round; (void)d_leftpass; (void)d_left;
-#ifdef PT_STAMP
-  unsigned long long t_refill = 0, t_node = 0, t_leaf = 0, t_fin = 0, t_mark = __builtin_amdgcn_s_memtime();
-#define STAMP(acc) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - t_mark; t_mark = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STAMP(acc) do { } while (0)
-#endif
   Reservoir res; res.init(&q.cnt[CNT_RAY_TOTAL], (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave)));
   const uint32_t* seg_cnt = q.seg_ray[qi];
   WStack st;
@@ -553,10 +505,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
         }
       }
     }
-    STAMP(t_refill);
     if (!__ballot(cur != CUR_DONE)) break;        // nothing in flight, nothing prepared, the queue exhausted
     // ---- one cycle: node visits while enough lanes walk, one leaf pass, publish ----
-    DIAG_ITER(d_round);
     {
       for (;;) {
         const uint64_t mn = __ballot(cur >= 0);
@@ -564,7 +514,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
         if (__popcll(mn) < TRACE_NODE_MIN && __ballot(cur == CUR_LEAF)) break;   // few walkers, triangles waiting
         nv += (unsigned long long)__popcll(mn);
         if (cur >= 0) {
-          DIAG_ITER(d_node);
           uint32_t nb, masks;
           const uint32_t node_addr = L.top_addr + 16u * (uint32_t)cur;
           const uint32_t hits = node_visit(sc, node_addr, cur, r, oct, tmin, best_t, nb, masks);
@@ -575,115 +524,15 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
           cur = lhits ? CUR_LEAF : advance<true>(gbase, gmask, st, order_tab, oct);
         }
       }
-      STAMP(t_node);
       // ---- leaf phase: every lane with pending triangles tests one; a lane that then still has triangles pending hands its next
       // one to a lane that is not at a leaf (the k-th such owner to the k-th free lane, through two 64-byte LDS tables; the helper
       // fetches the owner's ray through ds_bpermute and returns its result the same way).  Same tests, same results and counters
-      // as one triangle per pass — closest hit is an order-independent minimum — in fewer passes.
-#if LEAF_EXTRA == 0    // no hand-outs: every lane at a leaf tests its own next triangle (no cross-lane traffic at all)
-      {
-        const bool leaf = cur == CUR_LEAF;
-        if (__ballot(leaf)) {
-          DIAG_ITER(d_tri);
-          if (leaf) {
-            const uint32_t k = next_triangle(tbase, tmask);
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            float t, u, v;
-            const bool hit = tri_test<CULL>(r, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v);
-            const int pid = __float_as_int(a.w);
-            ++nt;
-            if (hit && t > tmin && (t < best_t || (t == best_t && pid < best_prim))) {
-              best_t = t; best_u = u; best_v = v; best_prim = pid; best_cls = __float_as_int(b.w); found = true;
-            }
-            if ((tmask & 255u) == 0u) cur = advance<true>(gbase, gmask, st, order_tab, oct);
-          }
-        }
-      }
-#elif LEAF_EXTRA > 1
+      // as one triangle per pass — closest hit is an order-independent minimum — in fewer passes.  (No hand-outs, and two or more per lane, both lost:
+      // profiles/r03_leaf_extra.txt; the code of both is profiles/exp_leaf_extra.patch.)
       {
         const bool leaf = cur == CUR_LEAF;
         const uint64_t m_leaf = __ballot(leaf);
         if (m_leaf) {
-          DIAG_ITER(d_tri);
-          uint32_t k1 = 0, pend = 0;
-          if (leaf) { k1 = next_triangle(tbase, tmask); pend = pending_triangles(tmask); }
-          const LeafDeal dl = leaf_deal(pend < LEAF_EXTRA ? pend : LEAF_EXTRA, leaf, m_leaf);
-          typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-          lds_u8* tab_task = (lds_u8*)s_pair[0][wave];      // task -> owner lane | which of its extras << 6
-          lds_u8* tab_helper = (lds_u8*)s_pair[1][wave];    // task -> helper lane
-          uint32_t kx[LEAF_EXTRA];
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            kx[j] = 0;
-            if (j < dl.take) { kx[j] = next_triangle(tbase, tmask); tab_task[dl.off + j] = (uint8_t)(lane | (j << 6)); }
-          }
-          if (dl.helper) tab_helper[dl.rank_free] = (uint8_t)lane;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const uint32_t task = dl.helper ? (uint32_t)tab_task[dl.rank_free] : lane;
-          const int src = (int)(task & 63u);
-          ray_t rr;
-          rr.o = V3(__shfl(r.o.x, src), __shfl(r.o.y, src), __shfl(r.o.z, src));
-          rr.d = V3(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src));
-          uint32_t k = k1;
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            const uint32_t kj = (uint32_t)__shfl((int)kx[j], src);       // unconditional: a shuffle inside ?: would run with the owners masked off
-            if (dl.helper && (task >> 6) == j) k = kj;
-          }
-          bool hit = false; float t = 0.0f, u = 0.0f, v = 0.0f; int pid = 0, cls = 0;
-          if (leaf || dl.helper) {
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            hit = tri_test<CULL>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v);
-            pid = __float_as_int(a.w); cls = __float_as_int(b.w);
-          }
-          if (leaf) {
-            ++nt;
-            if (hit && t > tmin && (t < best_t || (t == best_t && pid < best_prim))) {
-              best_t = t; best_u = u; best_v = v; best_prim = pid; best_cls = cls; found = true;
-            }
-          }
-          // results of the handed-out triangles: (t, prim | class) of each, then (u, v) of the best of them only
-          const float tt = hit ? t : -INFINITY;
-          const int pw = pid | (cls << HIT_CLASS_SHIFT);
-          float bt = 0.0f; int bp = 0, bl = (int)lane; bool have = false;
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            const int hl = j < dl.take ? (int)tab_helper[dl.off + j] : (int)lane;
-            const float tj = __shfl(tt, hl);
-            const int pj = __shfl(pw, hl);
-            if (j < dl.take) {
-              ++nt;
-              const int prim_j = pj & ((1 << HIT_CLASS_SHIFT) - 1);
-              if (tj > tmin && (!have || tj < bt || (tj == bt && prim_j < (bp & ((1 << HIT_CLASS_SHIFT) - 1))))) { bt = tj; bp = pj; bl = hl; have = true; }
-            }
-          }
-          const float ub = __shfl(u, bl), vb = __shfl(v, bl);
-          if (have) {
-            const int prim_b = bp & ((1 << HIT_CLASS_SHIFT) - 1);
-            if (bt < best_t || (bt == best_t && prim_b < best_prim)) {
-              best_t = bt; best_u = ub; best_v = vb; best_prim = prim_b; best_cls = (int)((uint32_t)bp >> HIT_CLASS_SHIFT); found = true;
-            }
-          }
-          if (leaf && (tmask & 255u) == 0u) cur = advance<true>(gbase, gmask, st, order_tab, oct);
-#ifdef PT_DIAG
-          {
-            const uint32_t left = (cur == CUR_LEAF) ? pending_triangles(tmask) : 0u;
-            const uint64_t m_left = __ballot(left != 0u);
-            if (m_left) { if ((int)lane == __ffsll((unsigned long long)m_left) - 1) ++d_leftpass; d_left += left; }
-          }
-#endif
-        }
-      }
-#else
-      {
-        const bool leaf = cur == CUR_LEAF;
-        const uint64_t m_leaf = __ballot(leaf);
-        if (m_leaf) {
-          DIAG_ITER(d_tri);
           uint32_t k1 = 0, k2 = 0;
           bool more = false;
           if (leaf) { k1 = next_triangle(tbase, tmask); more = (tmask & 255u) != 0u; }
@@ -729,23 +578,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
             }
           }
           if (leaf && (tmask & 255u) == 0u) cur = advance<true>(gbase, gmask, st, order_tab, oct);
-#ifdef PT_DIAG     // what a pass leaves behind: passes after which some lane still has triangles pending, and how many triangles those are
-          {
-            const uint32_t left = (cur == CUR_LEAF) ? (uint32_t)__builtin_popcount(tmask & 255u) + (uint32_t)__builtin_popcount((tmask >> 16) & tmask & 255u) - (tmask >> 24) : 0u;
-            const uint64_t m_left = __ballot(left != 0u);
-            if (m_left) { if ((int)lane == __ffsll((unsigned long long)m_left) - 1) ++d_leftpass; d_left += left; }
-          }
-#endif
         }
       }
-#endif
-      STAMP(t_leaf);
       nh += (unsigned long long)__popcll(__ballot(cur == CUR_FINISHED && found));
       if (cur == CUR_FINISHED) {                                       // this lane's ray is finished: publish in place
         q.hit[ri] = make_float4(found ? best_t : -1.0f, __int_as_float(found ? (best_prim | (best_cls << HIT_CLASS_SHIFT)) : -1), best_u, best_v);
         cur = CUR_DONE;
       }
-      STAMP(t_fin);
     }
   }
   {   // counters: summed over the block first, then one atomic per counter, each counter on its own line (ptc_internal.h, ST_STRIDE)
@@ -760,16 +599,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
       if (v) atomicAdd(&q.stats[at * ST_STRIDE], v);
     }
   }
-#ifdef PT_STAMP
-  if (lane == 0) { atomicAdd(&q.stats[ST_DIAG_NODE_ITERS * ST_STRIDE], t_node); atomicAdd(&q.stats[ST_DIAG_TRI_ITERS * ST_STRIDE], t_leaf); atomicAdd(&q.stats[ST_DIAG_LEAF_VISITS * ST_STRIDE], t_fin); atomicAdd(&q.stats[ST_DIAG_ROUNDS * ST_STRIDE], t_refill); }
-#endif
-#ifdef PT_DIAG
-  {
-    unsigned long long a0 = wave_sum(d_node), a1 = wave_sum(d_tri), a3 = wave_sum(d_round), a4 = wave_sum(d_leftpass), a5 = wave_sum(d_left);
-    if (lane == 0) { atomicAdd(&q.stats[ST_DIAG_NODE_ITERS * ST_STRIDE], a0); atomicAdd(&q.stats[ST_DIAG_TRI_ITERS * ST_STRIDE], a1); atomicAdd(&q.stats[ST_DIAG_ROUNDS * ST_STRIDE], a3);
-                     atomicAdd(&q.stats[ST_DIAG_LEAF_VISITS * ST_STRIDE], a4); atomicAdd(&q.stats[ST_DIAG_REFILLED * ST_STRIDE], a5); }
-  }
-#endif
 }
 
 // =================================================================================================
@@ -844,76 +673,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_any(DevS
           cur = lhits ? CUR_LEAF : advance<false>(gbase, gmask, st, nullptr, 0u);
         }
       }
-#if LEAF_EXTRA == 0
-      {
-        const bool leaf = cur == CUR_LEAF;
-        if (__ballot(leaf)) {
-          if (leaf) {
-            const uint32_t k = next_triangle(tbase, tmask);
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            float t, u, v;
-            const bool hit = tri_test<false>(r, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v) && t > 0.0f && t < tmax;
-            ++nt;
-            if (hit) { occluded = true; cur = CUR_FINISHED; }
-            else if ((tmask & 255u) == 0u) cur = advance<false>(gbase, gmask, st, nullptr, 0u);
-          }
-        }
-      }
-#elif LEAF_EXTRA > 1
-      {
-        // ---- leaf phase: as in k_trace_closest, up to LEAF_EXTRA more of a lane's pending triangles are tested in the same pass by free lanes.
-        // The counter stays the sequential one: a test is counted (and used) only when all tests before it missed.
-        const bool leaf = cur == CUR_LEAF;
-        const uint64_t m_leaf = __ballot(leaf);
-        if (m_leaf) {
-          uint32_t k1 = 0, pend = 0;
-          if (leaf) { k1 = next_triangle(tbase, tmask); pend = pending_triangles(tmask); }
-          const LeafDeal dl = leaf_deal(pend < LEAF_EXTRA ? pend : LEAF_EXTRA, leaf, m_leaf);
-          typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-          lds_u8* tab_task = (lds_u8*)s_pair[0][wave];
-          lds_u8* tab_helper = (lds_u8*)s_pair[1][wave];
-          uint32_t kx[LEAF_EXTRA];
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            kx[j] = 0;
-            if (j < dl.take) { kx[j] = next_triangle(tbase, tmask); tab_task[dl.off + j] = (uint8_t)(lane | (j << 6)); }
-          }
-          if (dl.helper) tab_helper[dl.rank_free] = (uint8_t)lane;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const uint32_t task = dl.helper ? (uint32_t)tab_task[dl.rank_free] : lane;
-          const int src = (int)(task & 63u);
-          ray_t rr;
-          rr.o = V3(__shfl(r.o.x, src), __shfl(r.o.y, src), __shfl(r.o.z, src));
-          rr.d = V3(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src));
-          const float tmax_src = __shfl(tmax, src);
-          uint32_t k = k1;
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            const uint32_t kj = (uint32_t)__shfl((int)kx[j], src);
-            if (dl.helper && (task >> 6) == j) k = kj;
-          }
-          bool hit = false;
-          if (leaf || dl.helper) {
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            float t, u, v;
-            hit = tri_test<false>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v) && t > 0.0f && t < tmax_src;
-          }
-          bool done = false;
-          if (leaf) { ++nt; if (hit) { occluded = true; cur = CUR_FINISHED; done = true; } }
-#pragma unroll
-          for (uint32_t j = 0; j < LEAF_EXTRA; ++j) {
-            const int hl = j < dl.take ? (int)tab_helper[dl.off + j] : (int)lane;
-            const int hj = __shfl(hit ? 1 : 0, hl);
-            if (j < dl.take && !done) { ++nt; if (hj) { occluded = true; cur = CUR_FINISHED; done = true; } }
-          }
-          if (cur == CUR_LEAF && (tmask & 255u) == 0u) cur = advance<false>(gbase, gmask, st, nullptr, 0u);
-        }
-      }
-#else
       {
         // ---- leaf phase: as in k_trace_closest, a lane's second pending triangle is tested in the same pass by a free lane.  The
         // counter stays the sequential one: the second test is counted (and used) only when the first one missed.
@@ -963,7 +722,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_any(DevS
           }
         }
       }
-#endif
       if (cur == CUR_FINISHED) {
         if (DEBUG_OUT) debug_out[ri] = occluded ? 1 : 0;
         else if (!occluded) {
@@ -1241,14 +999,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
   const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.seg_ray[qi][seg]);
   typedef __attribute__((address_space(3))) volatile uint32_t lds_u32;
   lds_u32* ring = (lds_u32*)&s_ring[SORT ? wave : 0][0][0];
-#ifdef PT_STAMP_SHADE   // wave-cycles per phase (tools/stamp_shade.py)
-  unsigned long long t_front = 0, t_load = 0, t_math = 0, t_back = 0, t_mark = __builtin_amdgcn_s_memtime();
-#define SSTAMP(acc) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - t_mark; t_mark = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define SSTAMP_LOADS(acc) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SSTAMP(acc); } while (0)
-#else
-#define SSTAMP(acc) do { } while (0)
-#define SSTAMP_LOADS(acc) do { } while (0)
-#endif
   uint32_t out_a = 0, out_s = 0;          // wave cursors: continuation / shadow rays written so far
   uint32_t fillv = 0;                     // lane c holds the number of slots waiting in ring c
   uint32_t ready = 0, nonempty = 0;       // class masks: ring holds >= 64 / > 0 slots
@@ -1267,9 +1017,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
         const uint32_t i = i0 + lane;
         int cls = -1;
         if (i < n) cls = w_pref >= 0 ? ((w_pref >> HIT_CLASS_SHIFT) & (PTC_MATERIAL_CLASSES - 1)) : (has_env ? PTC_MATERIAL_CLASSES - 1 : -1);
-#ifdef SHADE_TWO_RING     // experiment (profiles/r04_shade_variants.txt): two rings only — textured hits / everything else — the split the hit word's class >= 2 gives
-        if (cls >= 0) cls = (cls >= 2 && cls != PTC_MATERIAL_CLASSES - 1) ? 1 : 0;
-#endif
         i0 += 64u;
         w_pref = i0 + lane < n ? __float_as_int(q.hit[base + i0 + lane].y) : -1;
         uint64_t rem = __ballot(cls >= 0);
@@ -1284,7 +1031,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
           if (f >= 64u) ready |= 1u << c;
           rem &= ~m;
         }
-        SSTAMP(t_front);
         continue;
       }
       if (!nonempty) break;
@@ -1317,7 +1063,6 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
     }
     }   // SORT
     const uint32_t slot = base + item;
-    SSTAMP(t_front);
 
     bool alive = false, has_shadow = false;
     float4 oA, oB, oC, sA, sB, sC;
@@ -1353,12 +1098,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
       bool use_env = false;
       if ((int)b < fr.max_bounces && env_nee) use_env = sc.n_lights == 0u || rng_f(key, rb, 7) < p_env;
       v3 wi_env = V3(0, 0, 0);
-#ifdef SHADE_ENV_ALWAYS    // experiment (profiles/r04_shade_variants.txt): the environment sample's chain of loads issued by every lane, so that the env / area choice diverges in arithmetic only
-      if ((int)b < fr.max_bounces && env_nee) wi_env = env_sample(sc, env_marg, env_marg_guide, rng_f(key, rb, 1), rng_f(key, rb, 2));
-#else
       if (use_env) wi_env = env_sample(sc, env_marg, env_marg_guide, rng_f(key, rb, 1), rng_f(key, rb, 2));
-#endif
-      SSTAMP_LOADS(t_load);
       const v3 Pa = V3(r0.x, r0.y, r0.z), Pb = V3(r1.x, r1.y, r1.z), Pc = V3(r2.x, r2.y, r2.z);
       const v3 Na = V3(r2.w, r3.x, r3.y), Nb = V3(r3.z, r3.w, r4.x), Nc = V3(r4.y, r4.z, r4.w);
       const float hw = 1.0f - hu - hv;
@@ -1484,19 +1224,13 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
       }
       }   // hit
     }
-    SSTAMP(t_math);
     // ---- P9 back end: compaction into the wave's own segment of the output arrays ----
     const uint64_t ms = __ballot(has_shadow), ma = __ballot(alive);
     if (has_shadow) { const uint32_t o = base + out_s + mbcnt64(ms); q.shadow.A[o] = sA; q.shadow.B[o] = sB; q.shadow.C[o] = sC; }
     if (alive) { const uint32_t o = base + out_a + mbcnt64(ma); rout.A[o] = oA; rout.B[o] = oB; rout.C[o] = oC; }
     out_s += (uint32_t)__popcll(ms); out_a += (uint32_t)__popcll(ma);
-    SSTAMP(t_back);
   }
   if (lane == 0) { q.seg_ray[qi ^ 1][seg] = out_a; q.seg_sh[seg] = out_s; }
-#ifdef PT_STAMP_SHADE
-  if (lane == 0) { atomicAdd(&q.stats[ST_DIAG_NODE_ITERS * ST_STRIDE], t_front); atomicAdd(&q.stats[ST_DIAG_TRI_ITERS * ST_STRIDE], t_load); atomicAdd(&q.stats[ST_DIAG_LEAF_VISITS * ST_STRIDE], t_math);
-                   atomicAdd(&q.stats[ST_DIAG_ROUNDS * ST_STRIDE], t_back); }
-#endif
 }
 
 // =================================================================================================
@@ -1629,7 +1363,7 @@ int pt_trace_block_threads() { return TRACE_BLOCK; }
 // the compile-time half of the launch policy (ptc_launch_policy)
 const char* pt_kernel_policy() {
   return "trace_block=" PT_STR(TRACE_BLOCK) " trace_min_waves=" PT_STR(TRACE_MIN_WAVES) " chunk=" PT_STR(TRACE_CHUNK) " ring=" PT_STR(TRACE_RING) " refill_idle=" PT_STR(TRACE_REFILL_IDLE)
-         " node_min=" PT_STR(TRACE_NODE_MIN) " leaf_extra=" PT_STR(LEAF_EXTRA) " shade_block=" PT_STR(SHADE_BLOCK) " shade_min_waves=" PT_STR(SHADE_MIN_WAVES);
+         " node_min=" PT_STR(TRACE_NODE_MIN) " leaf_extra=1 shade_block=" PT_STR(SHADE_BLOCK) " shade_min_waves=" PT_STR(SHADE_MIN_WAVES);   // leaf_extra: one hand-out per lane and leaf pass, the only leaf phase in this file
 }
 
 size_t pt_trace_lds_bytes(const LaunchCfg& cfg, const DevScene& sc) { return trace_lds_bytes(cfg, sc, true); }

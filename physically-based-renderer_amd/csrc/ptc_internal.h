@@ -96,7 +96,8 @@ enum { CNT_RAY_TOTAL = 0, CNT_RAY_CHUNK, CNT_RAY_NCHUNKS, CNT_SH_TOTAL, CNT_SH_C
 // (tools/viewer_loop.py).  Now: one per counter and BLOCK, four lines.
 #define ST_STRIDE 16
 enum { ST_SEGMENTS = 0, ST_SHADOW, ST_HITS, ST_NODES_C, ST_TRIS_C, ST_NODES_A, ST_TRIS_A,
-       // wave-level iteration counts of the trace kernels' loops (filled only by a -DPT_DIAG build): lane
+       // wave-level iteration counts of the trace kernels' loops (filled only by an instrumented build: apply profiles/instr_diag.patch or
+       // profiles/instr_stamp*.patch, build with EXTRA=-DPT_DIAG / -DPT_STAMP / -DPT_STAMP_SHADE, select it with PTC_LIB): lane
        // utilisation of a phase = lane-level count / (64 x wave-level count)
        ST_DIAG_NODE_ITERS, ST_DIAG_TRI_ITERS, ST_DIAG_LEAF_VISITS, ST_DIAG_ROUNDS, ST_DIAG_REFILLED, ST_N };
 

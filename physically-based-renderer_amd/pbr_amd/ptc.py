@@ -17,7 +17,8 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PTC_LIB selects another build of the same library (the -DPT_STAMP / -DPT_DIAG diagnostic builds of tools/)
+# PTC_LIB selects another build of the same library (the instrumented builds tools/diag.py and tools/stamp*.py read: profiles/instr_*.patch
+# applied, built with EXTRA=-DPT_DIAG / -DPT_STAMP / -DPT_STAMP_SHADE)
 LIB_PATH = os.environ.get("PTC_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libptc.so")
 
 DEVICE_NONE = -1  # PTC_DEVICE_NONE: description-only context (host flatten + BVH build; renders nothing)

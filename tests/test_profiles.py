@@ -79,3 +79,50 @@ def test_bench_line_of_the_committed_run_has_the_contract_fields():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
     assert abs(d["value"] - d["config"]["paths"] / (d["ms_per_step"] * 1e-3 * d["steps"]) / 1e6) / d["value"] < 1e-6
     ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+
+
+KERNEL_SRC = [os.path.join("physically-based-renderer_amd", "csrc", f) for f in "pt_kernels.hip pt_device.h ptc_internal.h pt_refit.hip pt_refit.h pt_build.hip pt_build.h".split()]
+STRIPPED_PATCHES = ("instr_diag", "instr_stamp", "instr_stamp_shade", "exp_leaf_extra", "exp_shade_variants", "exp_misc", "exp_oracle_fp16_slab")
+
+
+def _foreign_conditionals(path):
+    """Preprocessor conditionals of a file that are neither a tunable's default (`#ifndef NAME`, `#define NAME ...`, `#endif` and nothing else but
+    comments between them) nor the file's include guard, as (line number, text)."""
+    import re
+    code = [(i + 1, ln.strip()) for i, ln in enumerate(open(os.path.join(ROOT, path), encoding="utf-8")) if ln.strip() and not ln.strip().startswith("//")]
+    directive = re.compile(r"#\s*(ifndef|ifdef|if|elif|else|endif)\b\s*(\w*)")
+    bad, k, seen_directive = [], 0, False
+    while k < len(code):
+        no, ln = code[k]
+        m = directive.match(ln)
+        if m:
+            kind, name = m.groups()
+            define = re.match(r"#\s*define\s+%s\b" % re.escape(name), code[k + 1][1]) if kind == "ifndef" and k + 2 < len(code) else None
+            if define and re.match(r"#\s*endif\b", code[k + 2][1]):
+                k += 3          # a tunable's default
+                continue
+            if define and not seen_directive and re.match(r"#\s*endif\b", code[-1][1]):
+                code.pop()      # the include guard: first directive of the file, closed by its last line
+                k += 2
+                continue
+            bad.append((no, ln))
+        seen_directive = seen_directive or ln.startswith("#")
+        k += 1
+    return bad
+
+
+def test_kernel_and_oracle_sources_hold_no_experiment_conditionals():
+    """The hashed kernel sources and the oracle are what ships and what specifies: every conditional in them is a tunable's `#ifndef` default (the sweeps
+    set those with EXTRA=-D..., the policy string reports them) or an include guard; no #ifdef / #if / #elif / #else.  Instrumentation and rejected variants are
+    kept as profiles/instr_*.patch and profiles/exp_*.patch."""
+    assert _foreign_conditionals(KERNEL_SRC[0]) == [] and "#ifndef TRACE_BLOCK" in open(os.path.join(ROOT, KERNEL_SRC[0]), encoding="utf-8").read()
+    for f in KERNEL_SRC + [os.path.join("oracle", "ptc_oracle.c")]:
+        assert _foreign_conditionals(f) == [], f
+
+
+def test_stripped_instrumentation_and_experiments_apply_as_patches():
+    """What left the sources stays usable: each patch applies to the tree as it stands (git apply needs no repository)."""
+    import subprocess
+    for name in STRIPPED_PATCHES:
+        r = subprocess.run(["git", "apply", "--check", os.path.join("profiles", name + ".patch")], cwd=ROOT, capture_output=True, text=True)
+        assert r.returncode == 0, (name, r.stderr)

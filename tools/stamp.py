@@ -1,4 +1,7 @@
-"""Where a k_trace_closest wave spends its cycles (needs libptc built with EXTRA=-DPT_STAMP)."""
+"""Where a k_trace_closest wave spends its cycles .
+
+The cycle stamps are instrumentation that the product's source does not carry: apply profiles/instr_stamp.patch, build that
+tree with EXTRA=-DPT_STAMP into a library of its own and select it with PTC_LIB (the patch's head has the commands)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))

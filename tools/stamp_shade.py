@@ -1,4 +1,7 @@
-"""Where a k_shade wave spends its cycles, per phase of a 64-slot batch (needs libptc built with -DPT_STAMP_SHADE)."""
+"""Where a k_shade wave spends its cycles, per phase of a 64-slot batch.
+
+The cycle stamps are instrumentation that the product's source does not carry: apply profiles/instr_stamp_shade.patch, build that
+tree with EXTRA=-DPT_STAMP_SHADE into a library of its own and select it with PTC_LIB (the patch's head has the commands)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "physically-based-renderer_amd"))
