@@ -27,6 +27,54 @@ class OraStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+def _prototypes():
+    """name -> (restype, argtypes) of every function oracle/ptc_oracle.h declares, in the header's order."""
+    i, f, u16, u32, u64 = C.c_int, C.c_float, C.c_uint16, C.c_uint32, C.c_uint64
+    vp, fp, u8p, u32p, i32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    return {
+        "ora_create": (vp, []),
+        "ora_destroy": (None, [vp]),
+        "ora_last_error": (C.c_char_p, [vp]),
+        # scene
+        "ora_scene_begin": (i, [vp]),
+        "ora_add_material": (i, [vp, fp, f, f, fp, i, i, i]),
+        "ora_add_texture_rgba8": (i, [vp, u8p, i, i]),
+        "ora_add_mesh": (i, [vp, vp, u32, u32p, u32, i]),
+        "ora_add_instance": (i, [vp, i, fp, fp, fp]),
+        "ora_add_instance_matrix": (i, [vp, i, fp]),
+        "ora_set_camera": (i, [vp, fp, fp, f, f]),
+        "ora_set_env_latlong_rgb32f": (i, [vp, fp, i, i]),
+        "ora_set_texture_filter": (i, [vp, i]),
+        "ora_set_bvh_builder": (i, [vp, i]),
+        "ora_scene_commit": (i, [vp]),
+        "ora_update_instance": (i, [vp, i, fp, fp, fp]),
+        "ora_update_instance_matrix": (i, [vp, i, fp]),
+        "ora_scene_refit": (i, [vp]),
+        # rendering and single stages
+        "ora_render": (i, [vp, i, i, i, u64, i, i, i, i, i, fp]),
+        "ora_get_stats": (i, [vp, C.POINTER(OraStats)]),
+        "ora_trace_closest": (i, [vp, fp, fp, u32, fp, i32p, fp]),
+        "ora_trace_any": (i, [vp, fp, fp, fp, u32, u8p]),
+        "ora_get_flat_scene": (i, [vp, u32p, u32p, vp, u32p, i32p]),
+        "ora_get_bvh": (i, [vp, u32p, u32p, fp, fp]),
+        # stand-alone pieces for known-answer tests
+        "ora_make_model": (None, [fp, fp, fp, fp, fp]),
+        "ora_make_camera": (None, [fp, fp, f, f, fp, fp]),
+        "ora_tonemap_rgba8": (None, [fp, u32, u8p]),
+        "ora_sincos2pi": (None, [f, fp, fp]),
+        "ora_powf": (f, [f, f]),
+        "ora_atan2f": (f, [f, f]),
+        "ora_f32_to_f16": (u16, [f]),
+        "ora_f16_to_f32": (f, [u16]),
+        "ora_rng_u32": (u32, [u64, u32, u32, u32, u32]),
+        "ora_tile_owner": (i, [i, i, i, i, i]),
+        "ora_hw_threads": (i, []),
+    }
+
+
+_PROTOTYPES = _prototypes()
+
+
 def build(force: bool = False) -> str:
     src = os.path.join(_HERE, "ptc_oracle.c")
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
@@ -44,58 +92,24 @@ def lib():
         if path == _LIB_PATH and not os.path.exists(_LIB_PATH):
             build()
         L = C.CDLL(path)
-        vp, fp, u32p, i32p, u8p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-        L.ora_create.restype = vp
-        L.ora_destroy.argtypes = [vp]
-        L.ora_last_error.restype = C.c_char_p
-        L.ora_last_error.argtypes = [vp]
-        L.ora_scene_begin.argtypes = [vp]
-        L.ora_add_material.argtypes = [vp, fp, C.c_float, C.c_float, fp, C.c_int, C.c_int, C.c_int]
-        L.ora_add_mesh.argtypes = [vp, vp, C.c_uint32, u32p, C.c_uint32, C.c_int]
-        L.ora_add_texture_rgba8.argtypes = [vp, u8p, C.c_int, C.c_int]
-        L.ora_set_env_latlong_rgb32f.argtypes = [vp, fp, C.c_int, C.c_int]
-        L.ora_set_texture_filter.argtypes = [vp, C.c_int]
-        L.ora_set_bvh_builder.argtypes = [vp, C.c_int]
-        L.ora_atan2f.argtypes = [C.c_float, C.c_float]
-        L.ora_atan2f.restype = C.c_float
-        L.ora_add_instance.argtypes = [vp, C.c_int, fp, fp, fp]
-        L.ora_update_instance.argtypes = [vp, C.c_int, fp, fp, fp]
-        L.ora_update_instance_matrix.argtypes = [vp, C.c_int, fp]
-        L.ora_scene_refit.argtypes = [vp]
-        L.ora_add_instance_matrix.argtypes = [vp, C.c_int, fp]
-        L.ora_set_camera.argtypes = [vp, fp, fp, C.c_float, C.c_float]
-        L.ora_scene_commit.argtypes = [vp]
-        L.ora_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp]
-        L.ora_get_stats.argtypes = [vp, C.POINTER(OraStats)]
-        L.ora_trace_closest.argtypes = [vp, fp, fp, C.c_uint32, fp, i32p, fp]
-        L.ora_trace_any.argtypes = [vp, fp, fp, fp, C.c_uint32, u8p]
-        L.ora_get_flat_scene.argtypes = [vp, u32p, u32p, vp, u32p, i32p]
-        L.ora_get_bvh.argtypes = [vp, u32p, u32p, fp, fp]
-        L.ora_make_model.argtypes = [fp, fp, fp, fp, fp]
-        L.ora_make_model.restype = None
-        L.ora_make_camera.argtypes = [fp, fp, C.c_float, C.c_float, fp, fp]
-        L.ora_make_camera.restype = None
-        L.ora_tonemap_rgba8.argtypes = [fp, C.c_uint32, u8p]
-        L.ora_tonemap_rgba8.restype = None
-        L.ora_sincos2pi.argtypes = [C.c_float, fp, fp]
-        L.ora_sincos2pi.restype = None
-        L.ora_powf.argtypes = [C.c_float, C.c_float]
-        L.ora_powf.restype = C.c_float
-        L.ora_f32_to_f16.argtypes = [C.c_float]
-        L.ora_f32_to_f16.restype = C.c_uint16
-        L.ora_f16_to_f32.argtypes = [C.c_uint16]
-        L.ora_f16_to_f32.restype = C.c_float
-        L.ora_rng_u32.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
-        L.ora_rng_u32.restype = C.c_uint32
-        L.ora_tile_owner.argtypes = [C.c_int] * 5
-        L.ora_hw_threads.restype = C.c_int
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
+# the pointer type of an array's elements; anything else (48-byte vertex records) goes as void*
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.float32, C.c_float), (np.uint8, C.c_uint8), (np.uint32, C.c_uint32), (np.int32, C.c_int32))}
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_POINTERS.get(a.dtype, C.c_void_p))
+
+
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
-    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+    return a, _ptr(a)
 
 
 class Oracle:
@@ -128,21 +142,19 @@ class Oracle:
         self._ck(L.ora_scene_begin(h))
         for t in getattr(desc, "textures", []):
             t = np.ascontiguousarray(t, np.uint8)
-            self._ck(L.ora_add_texture_rgba8(h, t.ctypes.data_as(C.POINTER(C.c_uint8)), t.shape[1], t.shape[0]))
+            self._ck(L.ora_add_texture_rgba8(h, _ptr(t), t.shape[1], t.shape[0]))
         self._ck(L.ora_set_texture_filter(h, 1 if getattr(desc, "texture_filter", "nearest") == "linear" else 0))
         self._ck(L.ora_set_bvh_builder(h, 1 if getattr(desc, "bvh_builder", None) == "lbvh" else 0))
         env = getattr(desc, "env", None)
         if env is not None:
             e = np.ascontiguousarray(env, np.float32)
-            self._ck(L.ora_set_env_latlong_rgb32f(h, e.ctypes.data_as(C.POINTER(C.c_float)), e.shape[1], e.shape[0]))
+            self._ck(L.ora_set_env_latlong_rgb32f(h, _ptr(e), e.shape[1], e.shape[0]))
         for m in desc.materials:
-            _, b = _f(m.base_color)
-            _, e = _f(m.emissive)
-            self._ck(L.ora_add_material(h, b, m.metallic, m.roughness, e, m.tex_color, m.tex_normal, m.tex_mr))
+            self._ck(L.ora_add_material(h, _f(m.base_color)[1], m.metallic, m.roughness, _f(m.emissive)[1], m.tex_color, m.tex_normal, m.tex_mr))
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
-            self._ck(L.ora_add_mesh(h, v.ctypes.data, v.size, i.ctypes.data_as(C.POINTER(C.c_uint32)), i.size, me.material))
+            self._ck(L.ora_add_mesh(h, v.ctypes.data, v.size, _ptr(i), i.size, me.material))
         for it in desc.instances:
             if getattr(it, "matrix", None) is not None:
                 self._ck(L.ora_add_instance_matrix(h, it.mesh, _f(np.asarray(it.matrix, np.float32).reshape(16))[1]))
@@ -166,8 +178,7 @@ class Oracle:
 
     def render(self, w, h, spp, seed=1, max_bounces=8, integrator=0, tile_rank=0, tile_count=1, n_threads=0):
         out = np.zeros((h, w, 4), np.float32)
-        self._ck(self._L.ora_render(self._h, w, h, spp, seed, max_bounces, integrator, tile_rank, tile_count, n_threads,
-                                    out.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ora_render(self._h, w, h, spp, seed, max_bounces, integrator, tile_rank, tile_count, n_threads, _ptr(out)))
         return out
 
     def stats(self):
@@ -182,8 +193,7 @@ class Oracle:
         t = np.zeros(n, np.float32)
         prim = np.zeros(n, np.int32)
         uv = np.zeros((n, 2), np.float32)
-        self._ck(self._L.ora_trace_closest(self._h, op, dp, n, t.ctypes.data_as(C.POINTER(C.c_float)),
-                                           prim.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ora_trace_closest(self._h, op, dp, n, _ptr(t), _ptr(prim), _ptr(uv)))
         return t, prim, uv
 
     def trace_any(self, origins, dirs, tmax):
@@ -192,44 +202,38 @@ class Oracle:
         tm, tp = _f(tmax)
         n = o.shape[0]
         occ = np.zeros(n, np.uint8)
-        self._ck(self._L.ora_trace_any(self._h, op, dp, tp, n, occ.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._ck(self._L.ora_trace_any(self._h, op, dp, tp, n, _ptr(occ)))
         return occ
 
     def flat_scene(self):
-        from numpy import dtype
         nv, nt = C.c_uint32(), C.c_uint32()
         self._ck(self._L.ora_get_flat_scene(self._h, C.byref(nv), C.byref(nt), None, None, None))
         verts = np.zeros((nv.value, 12), np.float32)
         idx = np.zeros((nt.value, 3), np.uint32)
         tm = np.zeros(nt.value, np.int32)
-        self._ck(self._L.ora_get_flat_scene(self._h, None, None, verts.ctypes.data, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                            tm.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self._L.ora_get_flat_scene(self._h, None, None, verts.ctypes.data, _ptr(idx), _ptr(tm)))
         return verts, idx, tm
 
-
-def _bvh(self):
-    nn, nt = C.c_uint32(), C.c_uint32()
-    self._ck(self._L.ora_get_bvh(self._h, C.byref(nn), C.byref(nt), None, None))
-    nodes = np.zeros((nn.value, 65), np.float32)
-    tris = np.zeros((nt.value, 12), np.float32)
-    self._ck(self._L.ora_get_bvh(self._h, None, None, nodes.ctypes.data_as(C.POINTER(C.c_float)), tris.ctypes.data_as(C.POINTER(C.c_float))))
-    return nodes, tris
-
-
-Oracle.bvh = _bvh
+    def bvh(self):
+        nn, nt = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.ora_get_bvh(self._h, C.byref(nn), C.byref(nt), None, None))
+        nodes = np.zeros((nn.value, 65), np.float32)
+        tris = np.zeros((nt.value, 12), np.float32)
+        self._ck(self._L.ora_get_bvh(self._h, None, None, _ptr(nodes), _ptr(tris)))
+        return nodes, tris
 
 
 def make_model(t, q, s):
     M = np.zeros(16, np.float32)
     N = np.zeros(9, np.float32)
-    lib().ora_make_model(_f(t)[1], _f(q)[1], _f(s)[1], M.ctypes.data_as(C.POINTER(C.c_float)), N.ctypes.data_as(C.POINTER(C.c_float)))
+    lib().ora_make_model(_f(t)[1], _f(q)[1], _f(s)[1], _ptr(M), _ptr(N))
     return M.reshape(4, 4), N.reshape(3, 3)  # [col][row]
 
 
 def make_camera(pos, target, fov, aspect):
     V = np.zeros(16, np.float32)
     P = np.zeros(16, np.float32)
-    lib().ora_make_camera(_f(pos)[1], _f(target)[1], fov, aspect, V.ctypes.data_as(C.POINTER(C.c_float)), P.ctypes.data_as(C.POINTER(C.c_float)))
+    lib().ora_make_camera(_f(pos)[1], _f(target)[1], fov, aspect, _ptr(V), _ptr(P))
     return V.reshape(4, 4), P.reshape(4, 4)
 
 
@@ -237,7 +241,7 @@ def tonemap_rgba8(rgba):
     a, ap = _f(rgba)
     n = a.size // 4
     out = np.zeros((n, 4), np.uint8)
-    lib().ora_tonemap_rgba8(ap, n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    lib().ora_tonemap_rgba8(ap, n, _ptr(out))
     return out.reshape(a.shape[:-1] + (4,))
 
 

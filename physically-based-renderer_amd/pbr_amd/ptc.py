@@ -8,6 +8,10 @@
 
 HIP only.  There is no CPU fallback: if libptc.so is missing or no gfx950 device is usable this
 module raises — loudly — instead of computing anything on the host.
+
+A new entry point of include/ptc.h is declared here in three places at most: its prototype in `_prototypes()` (the only place that says what a
+call passes; tests/test_binding_matches_header.py holds the table, the struct mirrors and the constants to the header), a `_Struct` mirror when it
+brings a struct, and the method that calls it.
 """
 from __future__ import annotations
 
@@ -49,34 +53,46 @@ TEMPORAL_MOTION = 2       # (x_prev, y_prev, W, reprojected n)
 TEMPORAL_NORMAL_DEPTH = 3     # the history's copy of its frame's (N, Z)
 TEMPORAL_POSITION_CLASS = 4   # the history's copy of its frame's (P, K)
 
-# every symbol include/ptc.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = [
-    "ptc_create", "ptc_destroy", "ptc_last_error", "ptc_abi_version", "ptc_build_info", "ptc_launch_policy", "ptc_scene_begin", "ptc_add_material",
-    "ptc_add_texture_rgba8", "ptc_add_mesh", "ptc_add_instance", "ptc_add_instance_matrix", "ptc_update_instance", "ptc_update_instance_matrix", "ptc_scene_refit", "ptc_scene_rebuild", "ptc_set_camera", "ptc_set_env_latlong_rgb32f", "ptc_set_texture_filter", "ptc_set_bvh_builder", "ptc_set_device_builder", "ptc_scene_commit", "ptc_render",
-    "ptc_frame_begin", "ptc_frame_add_samples", "ptc_frame_reserve", "ptc_frame_resolve", "ptc_frame_checkpoint", "ptc_frame_restore", "ptc_frame_set_sample_range", "ptc_sync", "ptc_read_radiance_rgba32f",
-    "ptc_radiance_device_ptr", "ptc_write_radiance_rgba32f", "ptc_tonemap_rgba8", "ptc_get_stats",
-    "ptc_debug_trace_closest", "ptc_debug_trace_any", "ptc_debug_get_flat_scene", "ptc_debug_get_bvh", "ptc_debug_get_counters",
-    "ptc_debug_get_description", "ptc_debug_get_material", "ptc_debug_get_texture", "ptc_debug_get_internals", "ptc_debug_host_build_id", "ptc_debug_get_shading_tables", "ptc_debug_refit_host_parts", "ptc_debug_commit_host_parts",
-    "ptc_read_radiance_rgba16f", "ptc_radiance_rgba16f_device_ptr",
-    "ptc_frame_guides", "ptc_read_guide_rgba32f", "ptc_read_guide_hit", "ptc_denoise_default_params", "ptc_denoise", "ptc_select_output", "ptc_get_denoise_seconds",
-    "ptc_temporal_default_params", "ptc_temporal_accumulate", "ptc_temporal_reset", "ptc_read_temporal_rgba32f", "ptc_denoise_accumulated", "ptc_get_temporal_seconds",
-    "ptc_adaptive_default_params", "ptc_frame_set_adaptive", "ptc_frame_adapt", "ptc_read_sample_counts", "ptc_render_adaptive", "ptc_get_adaptive_stats",
-    "ptc_set_sample_covariance", "ptc_read_sample_covariance", "ptc_denoise_sampled", "ptc_read_sampled_variance",
-    "ptc_comm_unique_id", "ptc_comm_init", "ptc_comm_reduce_radiance", "ptc_comm_destroy",
-    "ptc_mesh_set_morph_targets", "ptc_mesh_set_skin", "ptc_update_mesh_pose", "ptc_update_mesh_vertices", "ptc_debug_get_mesh_vertices",
-    "ptc_lens_default_params", "ptc_set_camera_lens", "ptc_get_camera_lens", "ptc_focus_distance_at_pixel", "ptc_debug_lens_sample", "ptc_debug_camera_rays",
-    "ptc_light_default_params", "ptc_add_light", "ptc_update_light", "ptc_get_light", "ptc_light_count", "ptc_clear_lights",
-    "ptc_debug_light_sample", "ptc_debug_get_light_table", "ptc_debug_punctual_nee",
-    "ptc_display_default_params", "ptc_set_display", "ptc_get_display", "ptc_meter_exposure", "ptc_exposure_reset", "ptc_get_exposure", "ptc_read_luminance_histogram",
-    "ptc_display_rgba8", "ptc_display_rgba16f", "ptc_display_rgba16f_device_ptr", "ptc_get_display_seconds",
-    "ptc_debug_display_pixel", "ptc_debug_meter", "ptc_debug_display_internals", "ptc_debug_display_state",
-    "ptc_probes_begin", "ptc_probes_read_sh", "ptc_render_probes", "ptc_sh9_eval", "ptc_sh9_irradiance",
-    "ptc_debug_probe_rays", "ptc_debug_probe_project", "ptc_debug_probe_resolve",
-    "ptc_group_create", "ptc_group_size", "ptc_group_scene_commit", "ptc_group_scene_refit", "ptc_group_ctx", "ptc_group_render", "ptc_group_last_error", "ptc_group_destroy",
-]
+
+class PtcError(RuntimeError):
+    pass
 
 
-class PtcStats(C.Structure):
+class _Struct(C.Structure):
+    """Base of the mirrors of include/ptc.h's structs.  A parameter struct names its ptc_*_default_params in `_defaults_`, says in `_unknown_` how it
+    refuses a key that is no field, and lists in `_names_` the fields that also take a name for a value."""
+    _defaults_ = None
+    _unknown_ = "unknown field {}"
+    _names_ = {}
+
+    def as_dict(self):
+        return {k: tuple(getattr(self, k)) if issubclass(t, C.Array) else getattr(self, k) for k, t in self._fields_}
+
+    @classmethod
+    def defaults(cls, **fields):
+        """A new struct holding the library's defaults, with `fields` set on it."""
+        if cls._defaults_ is None:
+            raise TypeError(f"{cls.__name__} has no ptc_*_default_params")
+        p = cls()
+        getattr(load_library(), cls._defaults_)(C.byref(p))
+        return p.update(**fields) if fields else p
+
+    def update(self, **fields):
+        """Set `fields` on this struct, in place, each converted by its field's ctype; TypeError for a key that is no field.  Returns self."""
+        types = dict(self._fields_)
+        for k, v in fields.items():
+            if k not in types:
+                raise TypeError(self._unknown_.format(k))
+            if isinstance(v, str):
+                if v not in self._names_.get(k, ()):
+                    raise ValueError(f"{k}: {v!r} is not one of {sorted(self._names_.get(k, ()))}")
+                v = self._names_[k][v]
+            t = types[k]
+            setattr(self, k, t(*[float(x) for x in v]) if issubclass(t, C.Array) else float(v) if t in (C.c_float, C.c_double) else int(v))
+        return self
+
+
+class PtcStats(_Struct):
     _fields_ = [
         ("paths", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64), ("hits", C.c_uint64),
         ("node_visits_closest", C.c_uint64), ("tri_tests_closest", C.c_uint64),
@@ -88,85 +104,217 @@ class PtcStats(C.Structure):
         ("bvh_sa_cost", C.c_double), ("bvh_sa_cost_built", C.c_double), ("seconds_rebuild", C.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+
+class PtcLensParams(_Struct):
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int), ("rotation", C.c_float)]
+    _defaults_ = "ptc_lens_default_params"
 
 
-class PtcDenoiseParams(C.Structure):
+_LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
+
+
+class PtcLightParams(_Struct):
+    _fields_ = [("type", C.c_int), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3), ("range", C.c_float),
+                ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("sampling_weight", C.c_float)]
+    _defaults_ = "ptc_light_default_params"
+    _names_ = {"type": _LIGHT_TYPES}
+
+
+class PtcDenoiseParams(_Struct):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class PtcTemporalParams(C.Structure):
-    _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("demodulate", C.c_int)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+    _defaults_ = "ptc_denoise_default_params"
+    _unknown_ = "denoise: unknown parameter {}"
 
 
-class PtcAdaptiveParams(C.Structure):
+class PtcAdaptiveParams(_Struct):
     _fields_ = [("threshold", C.c_float), ("radius", C.c_int), ("min_samples", C.c_int), ("step_samples", C.c_int)]
+    _defaults_ = "ptc_adaptive_default_params"
+    _unknown_ = "adaptive sampling: unknown parameter {}"
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class PtcAdaptiveStats(C.Structure):
+class PtcAdaptiveStats(_Struct):
     _fields_ = [("owned_pixels", C.c_uint64), ("active_pixels", C.c_uint64), ("samples_total", C.c_uint64),
                 ("passes", C.c_uint32), ("max_count", C.c_uint32), ("seconds_adapt", C.c_double)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class PtcLensParams(C.Structure):
-    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int), ("rotation", C.c_float)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class PtcLightParams(C.Structure):
-    _fields_ = [("type", C.c_int), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3), ("range", C.c_float),
-                ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("sampling_weight", C.c_float)]
-
-    def as_dict(self):
-        return {k: (tuple(getattr(self, k)) if k in ("position", "direction", "intensity") else getattr(self, k)) for k, _ in self._fields_}
-
-
-class PtcDisplayParams(C.Structure):
-    _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_int), ("key", C.c_float), ("percentile_lo", C.c_float), ("percentile_hi", C.c_float),
-                ("adapt_rate", C.c_float), ("min_luminance", C.c_float), ("max_luminance", C.c_float), ("tonemap", C.c_int), ("white", C.c_float), ("oetf", C.c_int)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
+class PtcTemporalParams(_Struct):
+    _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("demodulate", C.c_int)]
+    _defaults_ = "ptc_temporal_default_params"
+    _unknown_ = "temporal_accumulate: unknown parameter {}"
 
 
 _TONEMAPS = {"aces": TONEMAP_ACES, "neutral": TONEMAP_PBR_NEUTRAL, "pbr_neutral": TONEMAP_PBR_NEUTRAL, "reinhard": TONEMAP_REINHARD, "clamp": TONEMAP_CLAMP}
 _OETFS = {"gamma22": OETF_GAMMA22, "srgb": OETF_SRGB}
-_LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
 
 
-def light_params(type="point", position=(0, 0, 0), direction=(0, 0, -1), intensity=(1, 1, 1), range=0.0, cos_inner=1.0, cos_outer=0.70710678, sampling_weight=1.0):
-    """A ptc_light_params: `type` is a name (point, spot, directional) or a LIGHT_* value; an object with these attributes (scene.LightDesc) is taken by light_params_of."""
-    t = _LIGHT_TYPES[type] if isinstance(type, str) else int(type)
-    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
-    return PtcLightParams(t, f3(position), f3(direction), f3(intensity), float(range), float(cos_inner), float(cos_outer), float(sampling_weight))
+class PtcDisplayParams(_Struct):
+    _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_int), ("key", C.c_float), ("percentile_lo", C.c_float), ("percentile_hi", C.c_float),
+                ("adapt_rate", C.c_float), ("min_luminance", C.c_float), ("max_luminance", C.c_float), ("tonemap", C.c_int), ("white", C.c_float), ("oetf", C.c_int)]
+    _defaults_ = "ptc_display_default_params"
+    _unknown_ = "display parameters: unknown field {}"
+    _names_ = {"tonemap": _TONEMAPS, "oetf": _OETFS}
 
 
-def light_params_of(l):
-    if isinstance(l, PtcLightParams):
-        return l
-    if isinstance(l, dict):
-        return light_params(**l)
-    return light_params(l.type, l.position, l.direction, l.intensity, l.range, l.cos_inner, l.cos_outer, l.sampling_weight)
+def _prototypes():
+    """name -> (restype, argtypes) of every function include/ptc.h declares, section by section in the header's order."""
+    i, f, u32, u64, s = C.c_int, C.c_float, C.c_uint32, C.c_uint64, C.c_char_p
+    vp, ip, fp, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double)
+    u8p, u16p, u32p, u64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    lens, light, display = C.POINTER(PtcLensParams), C.POINTER(PtcLightParams), C.POINTER(PtcDisplayParams)
+    denoise, adaptive, temporal = C.POINTER(PtcDenoiseParams), C.POINTER(PtcAdaptiveParams), C.POINTER(PtcTemporalParams)
+    return {
+        # context
+        "ptc_create": (vp, [i]),
+        "ptc_destroy": (None, [vp]),
+        "ptc_last_error": (s, [vp]),
+        "ptc_abi_version": (i, []),
+        "ptc_build_info": (s, []),
+        "ptc_launch_policy": (s, [vp]),
+        # scene description
+        "ptc_scene_begin": (i, [vp]),
+        "ptc_add_material": (i, [vp, fp, f, f, fp, i, i, i]),
+        "ptc_add_texture_rgba8": (i, [vp, u8p, i, i]),
+        "ptc_add_mesh": (i, [vp, vp, u32, u32p, u32, i]),
+        "ptc_add_instance": (i, [vp, i, fp, fp, fp]),
+        "ptc_add_instance_matrix": (i, [vp, i, fp]),
+        "ptc_update_instance": (i, [vp, i, fp, fp, fp]),
+        "ptc_update_instance_matrix": (i, [vp, i, fp]),
+        "ptc_scene_refit": (i, [vp]),
+        "ptc_scene_rebuild": (i, [vp]),
+        # deforming meshes
+        "ptc_mesh_set_morph_targets": (i, [vp, i, u32, fp, fp, fp]),
+        "ptc_mesh_set_skin": (i, [vp, i, u32, u16p, fp]),
+        "ptc_update_mesh_pose": (i, [vp, i, fp, u32, fp, u32]),
+        "ptc_update_mesh_vertices": (i, [vp, i, vp, u32]),
+        # camera and thin lens
+        "ptc_set_camera": (i, [vp, fp, fp, f, f]),
+        "ptc_lens_default_params": (None, [lens]),
+        "ptc_set_camera_lens": (i, [vp, lens]),
+        "ptc_get_camera_lens": (i, [vp, lens]),
+        "ptc_focus_distance_at_pixel": (i, [vp, i, i, fp]),
+        # punctual lights
+        "ptc_light_default_params": (None, [light]),
+        "ptc_add_light": (i, [vp, light]),
+        "ptc_update_light": (i, [vp, i, light]),
+        "ptc_get_light": (i, [vp, i, light]),
+        "ptc_light_count": (i, [vp]),
+        "ptc_clear_lights": (i, [vp]),
+        # environment, texture filter, builders, commit
+        "ptc_set_env_latlong_rgb32f": (i, [vp, fp, i, i]),
+        "ptc_set_texture_filter": (i, [vp, i]),
+        "ptc_set_bvh_builder": (i, [vp, i]),
+        "ptc_set_device_builder": (i, [vp, i]),
+        "ptc_scene_commit": (i, [vp]),
+        # rendering
+        "ptc_render": (i, [vp, i, i, i, u64, i, i]),
+        "ptc_frame_begin": (i, [vp, i, i, i, u64, i, i, i, i]),
+        "ptc_frame_add_samples": (i, [vp, i]),
+        "ptc_frame_reserve": (i, [vp]),
+        "ptc_frame_resolve": (i, [vp]),
+        "ptc_sync": (i, [vp]),
+        "ptc_read_radiance_rgba32f": (i, [vp, fp]),
+        "ptc_radiance_device_ptr": (vp, [vp]),
+        "ptc_write_radiance_rgba32f": (i, [vp, fp]),
+        "ptc_read_radiance_rgba16f": (i, [vp, u16p]),
+        "ptc_radiance_rgba16f_device_ptr": (vp, [vp]),
+        "ptc_tonemap_rgba8": (i, [vp, u8p]),
+        # checkpoint / resume, sample ranges, counters
+        "ptc_frame_checkpoint": (i, [vp, fp, u64p, u32p]),
+        "ptc_frame_restore": (i, [vp, fp, u64, u32]),
+        "ptc_frame_set_sample_range": (i, [vp, u32, u32]),
+        "ptc_get_stats": (i, [vp, C.POINTER(PtcStats)]),
+        # guide buffers, denoiser, output selection
+        "ptc_frame_guides": (i, [vp]),
+        "ptc_read_guide_rgba32f": (i, [vp, i, fp]),
+        "ptc_read_guide_hit": (i, [vp, i32p, fp]),
+        "ptc_denoise_default_params": (None, [denoise]),
+        "ptc_denoise": (i, [vp, denoise]),
+        "ptc_select_output": (i, [vp, i]),
+        "ptc_get_denoise_seconds": (i, [vp, dp, dp]),
+        # adaptive sampling
+        "ptc_adaptive_default_params": (None, [adaptive]),
+        "ptc_frame_set_adaptive": (i, [vp, adaptive]),
+        "ptc_frame_adapt": (i, [vp, u64p]),
+        "ptc_read_sample_counts": (i, [vp, u32p]),
+        "ptc_render_adaptive": (i, [vp, i, i, i, u64, i, adaptive]),
+        "ptc_get_adaptive_stats": (i, [vp, C.POINTER(PtcAdaptiveStats)]),
+        # denoising from per-sample statistics
+        "ptc_set_sample_covariance": (i, [vp, i]),
+        "ptc_read_sample_covariance": (i, [vp, fp]),
+        "ptc_denoise_sampled": (i, [vp, denoise]),
+        "ptc_read_sampled_variance": (i, [vp, fp]),
+        # temporal accumulation
+        "ptc_temporal_default_params": (None, [temporal]),
+        "ptc_temporal_accumulate": (i, [vp, temporal]),
+        "ptc_temporal_reset": (i, [vp]),
+        "ptc_read_temporal_rgba32f": (i, [vp, i, fp]),
+        "ptc_denoise_accumulated": (i, [vp, denoise]),
+        "ptc_get_temporal_seconds": (i, [vp, dp]),
+        # display transform
+        "ptc_display_default_params": (None, [display]),
+        "ptc_set_display": (i, [vp, display]),
+        "ptc_get_display": (i, [vp, display]),
+        "ptc_meter_exposure": (i, [vp]),
+        "ptc_exposure_reset": (i, [vp]),
+        "ptc_get_exposure": (i, [vp, fp, fp, fp, u64p, u64p]),
+        "ptc_read_luminance_histogram": (i, [vp, u32p]),
+        "ptc_display_rgba8": (i, [vp, u8p]),
+        "ptc_display_rgba16f": (i, [vp, u16p]),
+        "ptc_display_rgba16f_device_ptr": (vp, [vp]),
+        "ptc_get_display_seconds": (i, [vp, dp, dp]),
+        # light probes
+        "ptc_probes_begin": (i, [vp, fp, i, u32, i, u64, i]),
+        "ptc_probes_read_sh": (i, [vp, fp]),
+        "ptc_render_probes": (i, [vp, fp, i, i, u64, i, fp]),
+        "ptc_sh9_eval": (i, [fp, fp, fp]),
+        "ptc_sh9_irradiance": (i, [fp, fp, fp]),
+        # multi-GPU: one process per GPU
+        "ptc_comm_unique_id": (i, [u8p]),
+        "ptc_comm_init": (i, [vp, u8p, i, i]),
+        "ptc_comm_reduce_radiance": (i, [vp, i]),
+        "ptc_comm_destroy": (i, [vp]),
+        # multi-GPU: one process driving several GPUs
+        "ptc_group_create": (vp, [ip, i]),
+        "ptc_group_size": (i, [vp]),
+        "ptc_group_scene_commit": (i, [vp]),
+        "ptc_group_scene_refit": (i, [vp]),
+        "ptc_group_ctx": (vp, [vp, i]),
+        "ptc_group_render": (i, [vp, i, i, i, u64, i, i]),
+        "ptc_group_last_error": (s, [vp]),
+        "ptc_group_destroy": (None, [vp]),
+        # test hooks
+        "ptc_debug_trace_closest": (i, [vp, fp, fp, u32, fp, i32p, fp]),
+        "ptc_debug_trace_any": (i, [vp, fp, fp, fp, u32, u8p]),
+        "ptc_debug_lens_sample": (i, [lens, f, f, fp]),
+        "ptc_debug_light_sample": (i, [light, fp, fp, fp, fp]),
+        "ptc_debug_get_light_table": (i, [vp, u32p, fp, fp]),
+        "ptc_debug_punctual_nee": (i, [vp, fp, fp, u32p, u32, u32, u8p, fp, fp, fp, fp]),
+        "ptc_debug_display_pixel": (i, [display, f, fp, u8p, u16p]),
+        "ptc_debug_meter": (i, [display, fp, u64, u32, u32p, u32p, u64p, u64p, u64p, u32p]),
+        "ptc_debug_display_internals": (i, [vp, u64p]),
+        "ptc_debug_display_state": (i, [vp, u32p]),
+        "ptc_debug_camera_rays": (i, [vp, i, i, u64, u32, u32, u32p, u32, fp, fp]),
+        "ptc_debug_probe_rays": (i, [vp, fp, i, u32, u64, u32, u32, fp, u32p]),
+        "ptc_debug_probe_project": (i, [vp, i, u32, u64, u32, u32, fp, fp]),
+        "ptc_debug_probe_resolve": (i, [fp, i, u32, fp]),
+        "ptc_debug_get_flat_scene": (i, [vp, u32p, u32p, vp, u32p, i32p]),
+        "ptc_debug_get_mesh_vertices": (i, [vp, i, vp]),
+        "ptc_debug_get_description": (i, [vp, ip, ip]),
+        "ptc_debug_get_material": (i, [vp, i, fp, ip]),
+        "ptc_debug_get_texture": (i, [vp, i, ip, ip, vp]),
+        "ptc_debug_get_counters": (i, [vp, u64p, i]),
+        "ptc_debug_get_bvh": (i, [vp, u32p, u32p, u32p, fp, fp]),
+        "ptc_debug_host_build_id": (u64, [vp]),
+        "ptc_debug_get_internals": (i, [vp, u64p]),
+        "ptc_debug_commit_host_parts": (i, [vp, u64p]),
+        "ptc_debug_get_shading_tables": (i, [vp, u32p, fp, u32p, fp, fp]),
+        "ptc_debug_refit_host_parts": (i, [vp, u64p]),
+    }
 
 
-class PtcError(RuntimeError):
-    pass
-
+_PROTOTYPES = _prototypes()
+# every symbol include/ptc.h declares (tests check the library exports all of them)
+ABI_SYMBOLS = list(_PROTOTYPES)
 
 _lib = None
 
@@ -180,171 +328,29 @@ def load_library():
         raise PtcError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, fp = C.c_void_p, C.POINTER(C.c_float)
-    u32p, i32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-    L.ptc_create.restype = vp
-    L.ptc_create.argtypes = [C.c_int]
-    L.ptc_destroy.argtypes = [vp]
-    L.ptc_destroy.restype = None
-    L.ptc_last_error.restype = C.c_char_p
-    L.ptc_last_error.argtypes = [vp]
-    L.ptc_abi_version.restype = C.c_int
-    L.ptc_build_info.restype = C.c_char_p
-    L.ptc_launch_policy.restype = C.c_char_p
-    L.ptc_launch_policy.argtypes = [vp]
-    L.ptc_scene_begin.argtypes = [vp]
-    L.ptc_add_material.argtypes = [vp, fp, C.c_float, C.c_float, fp, C.c_int, C.c_int, C.c_int]
-    L.ptc_add_texture_rgba8.argtypes = [vp, u8p, C.c_int, C.c_int]
-    L.ptc_add_mesh.argtypes = [vp, vp, C.c_uint32, u32p, C.c_uint32, C.c_int]
-    L.ptc_add_instance.argtypes = [vp, C.c_int, fp, fp, fp]
-    L.ptc_add_instance_matrix.argtypes = [vp, C.c_int, fp]
-    L.ptc_update_instance.argtypes = [vp, C.c_int, fp, fp, fp]
-    L.ptc_update_instance_matrix.argtypes = [vp, C.c_int, fp]
-    L.ptc_scene_refit.argtypes = [vp]
-    L.ptc_mesh_set_morph_targets.argtypes = [vp, C.c_int, C.c_uint32, fp, fp, fp]
-    L.ptc_mesh_set_skin.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(C.c_uint16), fp]
-    L.ptc_update_mesh_pose.argtypes = [vp, C.c_int, fp, C.c_uint32, fp, C.c_uint32]
-    L.ptc_update_mesh_vertices.argtypes = [vp, C.c_int, vp, C.c_uint32]
-    L.ptc_debug_get_mesh_vertices.argtypes = [vp, C.c_int, vp]
-    L.ptc_scene_rebuild.argtypes = [vp]
-    L.ptc_set_camera.argtypes = [vp, fp, fp, C.c_float, C.c_float]
-    L.ptc_set_env_latlong_rgb32f.argtypes = [vp, fp, C.c_int, C.c_int]
-    L.ptc_set_texture_filter.argtypes = [vp, C.c_int]
-    L.ptc_set_bvh_builder.argtypes = [vp, C.c_int]
-    L.ptc_set_device_builder.argtypes = [vp, C.c_int]
-    L.ptc_scene_commit.argtypes = [vp]
-    L.ptc_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int]
-    L.ptc_frame_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.ptc_frame_add_samples.argtypes = [vp, C.c_int]
-    L.ptc_frame_resolve.argtypes = [vp]
-    L.ptc_frame_reserve.argtypes = [vp]
-    L.ptc_frame_checkpoint.argtypes = [vp, fp, C.POINTER(C.c_uint64), u32p]
-    L.ptc_frame_restore.argtypes = [vp, fp, C.c_uint64, C.c_uint32]
-    L.ptc_frame_set_sample_range.argtypes = [vp, C.c_uint32, C.c_uint32]
-    L.ptc_sync.argtypes = [vp]
-    L.ptc_read_radiance_rgba32f.argtypes = [vp, fp]
-    L.ptc_radiance_device_ptr.argtypes = [vp]
-    L.ptc_radiance_device_ptr.restype = vp
-    L.ptc_write_radiance_rgba32f.argtypes = [vp, fp]
-    L.ptc_tonemap_rgba8.argtypes = [vp, u8p]
-    L.ptc_get_stats.argtypes = [vp, C.POINTER(PtcStats)]
-    L.ptc_debug_trace_closest.argtypes = [vp, fp, fp, C.c_uint32, fp, i32p, fp]
-    L.ptc_debug_trace_any.argtypes = [vp, fp, fp, fp, C.c_uint32, u8p]
-    L.ptc_debug_get_flat_scene.argtypes = [vp, u32p, u32p, vp, u32p, i32p]
-    L.ptc_debug_get_bvh.argtypes = [vp, u32p, u32p, u32p, fp, fp]
-    L.ptc_debug_get_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
-    L.ptc_debug_get_description.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.ptc_debug_get_material.argtypes = [vp, C.c_int, fp, C.POINTER(C.c_int)]
-    L.ptc_debug_get_texture.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
-    L.ptc_debug_get_internals.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.ptc_debug_host_build_id.argtypes = [vp]
-    L.ptc_debug_host_build_id.restype = C.c_uint64
-    L.ptc_debug_get_shading_tables.argtypes = [vp, u32p, fp, u32p, fp, fp]
-    L.ptc_debug_refit_host_parts.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.ptc_debug_commit_host_parts.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.ptc_read_radiance_rgba16f.argtypes = [vp, C.POINTER(C.c_uint16)]
-    L.ptc_radiance_rgba16f_device_ptr.argtypes = [vp]
-    L.ptc_radiance_rgba16f_device_ptr.restype = vp
-    L.ptc_frame_guides.argtypes = [vp]
-    L.ptc_read_guide_rgba32f.argtypes = [vp, C.c_int, fp]
-    L.ptc_read_guide_hit.argtypes = [vp, i32p, fp]
-    L.ptc_denoise_default_params.argtypes = [C.POINTER(PtcDenoiseParams)]
-    L.ptc_denoise_default_params.restype = None
-    L.ptc_denoise.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
-    L.ptc_select_output.argtypes = [vp, C.c_int]
-    L.ptc_get_denoise_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.ptc_temporal_default_params.argtypes = [C.POINTER(PtcTemporalParams)]
-    L.ptc_temporal_default_params.restype = None
-    L.ptc_temporal_accumulate.argtypes = [vp, C.POINTER(PtcTemporalParams)]
-    L.ptc_temporal_reset.argtypes = [vp]
-    L.ptc_read_temporal_rgba32f.argtypes = [vp, C.c_int, fp]
-    L.ptc_denoise_accumulated.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
-    L.ptc_get_temporal_seconds.argtypes = [vp, C.POINTER(C.c_double)]
-    L.ptc_adaptive_default_params.argtypes = [C.POINTER(PtcAdaptiveParams)]
-    L.ptc_adaptive_default_params.restype = None
-    L.ptc_frame_set_adaptive.argtypes = [vp, C.POINTER(PtcAdaptiveParams)]
-    L.ptc_frame_adapt.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.ptc_read_sample_counts.argtypes = [vp, u32p]
-    L.ptc_render_adaptive.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(PtcAdaptiveParams)]
-    L.ptc_get_adaptive_stats.argtypes = [vp, C.POINTER(PtcAdaptiveStats)]
-    L.ptc_set_sample_covariance.argtypes = [vp, C.c_int]
-    L.ptc_read_sample_covariance.argtypes = [vp, fp]
-    L.ptc_denoise_sampled.argtypes = [vp, C.POINTER(PtcDenoiseParams)]
-    L.ptc_read_sampled_variance.argtypes = [vp, fp]
-    L.ptc_lens_default_params.argtypes = [C.POINTER(PtcLensParams)]
-    L.ptc_lens_default_params.restype = None
-    L.ptc_set_camera_lens.argtypes = [vp, C.POINTER(PtcLensParams)]
-    L.ptc_get_camera_lens.argtypes = [vp, C.POINTER(PtcLensParams)]
-    L.ptc_focus_distance_at_pixel.argtypes = [vp, C.c_int, C.c_int, fp]
-    L.ptc_debug_lens_sample.argtypes = [C.POINTER(PtcLensParams), C.c_float, C.c_float, fp]
-    L.ptc_debug_camera_rays.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, u32p, C.c_uint32, fp, fp]
-    lp = C.POINTER(PtcLightParams)
-    L.ptc_light_default_params.argtypes = [lp]
-    L.ptc_light_default_params.restype = None
-    L.ptc_add_light.argtypes = [vp, lp]
-    L.ptc_update_light.argtypes = [vp, C.c_int, lp]
-    L.ptc_get_light.argtypes = [vp, C.c_int, lp]
-    L.ptc_light_count.argtypes = [vp]
-    L.ptc_clear_lights.argtypes = [vp]
-    L.ptc_debug_light_sample.argtypes = [lp, fp, fp, fp, fp]
-    L.ptc_debug_get_light_table.argtypes = [vp, u32p, fp, fp]
-    L.ptc_debug_punctual_nee.argtypes = [vp, fp, fp, u32p, C.c_uint32, C.c_uint32, u8p, fp, fp, fp, fp]
-    dpp = C.POINTER(PtcDisplayParams)
-    u64p = C.POINTER(C.c_uint64)
-    L.ptc_display_default_params.argtypes = [dpp]
-    L.ptc_display_default_params.restype = None
-    L.ptc_set_display.argtypes = [vp, dpp]
-    L.ptc_get_display.argtypes = [vp, dpp]
-    L.ptc_meter_exposure.argtypes = [vp]
-    L.ptc_exposure_reset.argtypes = [vp]
-    L.ptc_get_exposure.argtypes = [vp, fp, fp, fp, u64p, u64p]
-    L.ptc_read_luminance_histogram.argtypes = [vp, u32p]
-    L.ptc_display_rgba8.argtypes = [vp, u8p]
-    L.ptc_display_rgba16f.argtypes = [vp, C.POINTER(C.c_uint16)]
-    L.ptc_display_rgba16f_device_ptr.argtypes = [vp]
-    L.ptc_display_rgba16f_device_ptr.restype = C.c_void_p
-    L.ptc_get_display_seconds.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.ptc_debug_display_pixel.argtypes = [dpp, C.c_float, fp, u8p, C.POINTER(C.c_uint16)]
-    L.ptc_debug_meter.argtypes = [dpp, fp, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p, u64p, u32p]
-    L.ptc_debug_display_internals.argtypes = [vp, u64p]
-    L.ptc_debug_display_state.argtypes = [vp, u32p]
-    L.ptc_probes_begin.argtypes = [vp, fp, C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_int]
-    L.ptc_probes_read_sh.argtypes = [vp, fp]
-    L.ptc_render_probes.argtypes = [vp, fp, C.c_int, C.c_int, C.c_uint64, C.c_int, fp]
-    L.ptc_sh9_eval.argtypes = [fp, fp, fp]
-    L.ptc_sh9_irradiance.argtypes = [fp, fp, fp]
-    L.ptc_debug_probe_rays.argtypes = [vp, fp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, fp, u32p]
-    L.ptc_debug_probe_project.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, fp, fp]
-    L.ptc_debug_probe_resolve.argtypes = [fp, C.c_int, C.c_uint32, fp]
-    L.ptc_comm_unique_id.argtypes = [u8p]
-    L.ptc_comm_init.argtypes = [vp, u8p, C.c_int, C.c_int]
-    L.ptc_comm_reduce_radiance.argtypes = [vp, C.c_int]
-    L.ptc_comm_destroy.argtypes = [vp]
-    L.ptc_group_create.argtypes = [C.POINTER(C.c_int), C.c_int]
-    L.ptc_group_create.restype = vp
-    L.ptc_group_size.argtypes = [vp]
-    L.ptc_group_scene_commit.argtypes = [vp]
-    L.ptc_group_scene_refit.argtypes = [vp]
-    L.ptc_group_ctx.argtypes = [vp, C.c_int]
-    L.ptc_group_ctx.restype = vp
-    L.ptc_group_render.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int]
-    L.ptc_group_last_error.argtypes = [vp]
-    L.ptc_group_last_error.restype = C.c_char_p
-    L.ptc_group_destroy.argtypes = [vp]
-    L.ptc_group_destroy.restype = None
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
 
+# the pointer type of an array's elements; anything else (MESH_VERTEX records) goes as void*
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.float32, C.c_float), (np.uint8, C.c_uint8), (np.uint16, C.c_uint16), (np.uint32, C.c_uint32),
+                                                    (np.int32, C.c_int32), (np.uint64, C.c_uint64))}
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_POINTERS.get(a.dtype, C.c_void_p))
+
+
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
-    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+    return a, _ptr(a)
 
 
 def lens_default_params():
-    p = PtcLensParams()
-    load_library().ptc_lens_default_params(C.byref(p))
-    return p.as_dict()
+    return PtcLensParams.defaults().as_dict()
 
 
 def lens_sample(u1, u2, aperture_radius=1.0, blades=0, rotation=0.0):
@@ -371,9 +377,8 @@ def _sh9_apply(fn, name, sh, vecs):
     shb = np.ascontiguousarray(np.broadcast_to(sh, lead + (9, 3))).reshape(-1, 27)
     vb = np.ascontiguousarray(np.broadcast_to(v, lead + (3,))).reshape(-1, 3)
     out = np.zeros((shb.shape[0], 3), np.float32)
-    P = C.POINTER(C.c_float)
     for i in range(shb.shape[0]):
-        if fn(shb[i].ctypes.data_as(P), vb[i].ctypes.data_as(P), out[i].ctypes.data_as(P)) < 0:
+        if fn(_ptr(shb[i]), _ptr(vb[i]), _ptr(out[i])) < 0:
             raise PtcError(f"{name}: bad argument")
     return out.reshape(lead + (3,))
 
@@ -394,16 +399,27 @@ def probe_resolve(acc, n_samples):
     """ptc_debug_probe_resolve: running sums (n, 9, 3) -> coefficients, acc * (4 pi / n_samples) in float32."""
     a = np.ascontiguousarray(acc, np.float32).reshape(-1, 9, 3)
     out = np.zeros_like(a)
-    P = C.POINTER(C.c_float)
-    if load_library().ptc_debug_probe_resolve(a.ctypes.data_as(P), a.shape[0], int(n_samples), out.ctypes.data_as(P)) < 0:
+    if load_library().ptc_debug_probe_resolve(_ptr(a), a.shape[0], int(n_samples), _ptr(out)) < 0:
         raise PtcError("probe_resolve: bad argument")
     return out
 
 
+def light_params(type="point", position=(0, 0, 0), direction=(0, 0, -1), intensity=(1, 1, 1), range=0.0, cos_inner=1.0, cos_outer=0.70710678, sampling_weight=1.0):
+    """A ptc_light_params: `type` is a name (point, spot, directional) or a LIGHT_* value; an object with these attributes (scene.LightDesc) is taken by light_params_of."""
+    return PtcLightParams().update(type=type, position=position, direction=direction, intensity=intensity, range=range, cos_inner=cos_inner,
+                                    cos_outer=cos_outer, sampling_weight=sampling_weight)
+
+
+def light_params_of(l):
+    if isinstance(l, PtcLightParams):
+        return l
+    if isinstance(l, dict):
+        return light_params(**l)
+    return light_params(l.type, l.position, l.direction, l.intensity, l.range, l.cos_inner, l.cos_outer, l.sampling_weight)
+
+
 def light_default_params():
-    p = PtcLightParams()
-    load_library().ptc_light_default_params(C.byref(p))
-    return p.as_dict()
+    return PtcLightParams.defaults().as_dict()
 
 
 def light_sample(light, P):
@@ -416,7 +432,7 @@ def light_sample(light, P):
     ok, wi, dist, Li = np.zeros(n, bool), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
     w, li, d = (C.c_float * 3)(), (C.c_float * 3)(), C.c_float(0)
     for i in range(n):
-        rc = L.ptc_debug_light_sample(C.byref(p), pts[i].ctypes.data_as(C.POINTER(C.c_float)), w, C.byref(d), li)
+        rc = L.ptc_debug_light_sample(C.byref(p), _ptr(pts[i]), w, C.byref(d), li)
         if rc < 0:
             raise PtcError(f"light_sample: bad light parameters: {p.as_dict()}")
         if rc:
@@ -427,22 +443,7 @@ def light_sample(light, P):
 def display_params(**fields):
     """A ptc_display_params: the defaults with `fields` replaced.  `tonemap` takes a name (aces, neutral, reinhard, clamp) or a TONEMAP_* value, `oetf` a name
     (gamma22, srgb) or an OETF_* value."""
-    p = PtcDisplayParams()
-    load_library().ptc_display_default_params(C.byref(p))
-    return _display_update(p, fields)
-
-
-def _display_update(p, fields):
-    names = dict(PtcDisplayParams._fields_)
-    for k, v in fields.items():
-        if k not in names:
-            raise TypeError(f"display parameters: unknown field {k}")
-        if k == "tonemap" and isinstance(v, str):
-            v = _TONEMAPS[v]
-        if k == "oetf" and isinstance(v, str):
-            v = _OETFS[v]
-        setattr(p, k, int(v) if names[k] is C.c_int else float(v))
-    return p
+    return PtcDisplayParams.defaults(**fields)
 
 
 def display_default_params():
@@ -462,7 +463,7 @@ def display_pixels(rgba, E=1.0, **fields):
     px = np.ascontiguousarray(np.atleast_2d(np.asarray(rgba, np.float32)))
     n = px.shape[0]
     o8, o16 = np.zeros((n, 4), np.uint8), np.zeros((n, 4), np.uint16)
-    f, u8, u16 = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+    f, u8, u16 = _POINTERS[px.dtype], _POINTERS[o8.dtype], _POINTERS[o16.dtype]
     base, b8, b16 = px.ctypes.data, o8.ctypes.data, o16.ctypes.data
     fn, pr, e = L.ptc_debug_display_pixel, C.byref(p), C.c_float(float(E))
     for i in range(n):
@@ -480,8 +481,7 @@ def meter(rgba, state=0, **fields):
     A, Q = C.c_uint32(0), C.c_uint32(0)
     N, M, R = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     hist = np.zeros(LUMINANCE_BINS, np.uint32)
-    rc = L.ptc_debug_meter(C.byref(p), px.ctypes.data_as(C.POINTER(C.c_float)), px.shape[0], int(state), C.byref(A), C.byref(Q), C.byref(N), C.byref(M), C.byref(R),
-                           hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+    rc = L.ptc_debug_meter(C.byref(p), _ptr(px), px.shape[0], int(state), C.byref(A), C.byref(Q), C.byref(N), C.byref(M), C.byref(R), _ptr(hist))
     if rc < 0:
         raise PtcError(f"meter: bad display parameters or too many pixels: {p.as_dict()}")
     return {"A": A.value, "Q": Q.value, "N": N.value, "M": M.value, "rejected": R.value, "hist": hist}
@@ -523,6 +523,18 @@ class PathTracer:
             raise PtcError(f"ptc error {rc}: {self._L.ptc_last_error(self._h).decode()}")
         return rc
 
+    def _read(self, fn, shape, dtype, *args, alloc=np.empty):
+        """The read-back fn(ctx, *args, out) into a new array; alloc is np.zeros where the library does not write every element."""
+        out = alloc(shape, dtype)
+        self._ck(fn(self._h, *args, _ptr(out)))
+        return out
+
+    def _get(self, fn, struct, *args):
+        """fn(ctx, *args, &s) for a new `struct` s, as a dict."""
+        s = struct()
+        self._ck(fn(self._h, *args, C.byref(s)))
+        return s.as_dict()
+
     # ---- scene ------------------------------------------------------------------------------------
     def load_scene(self, desc):
         """Describe `desc` and commit it (ptc_scene_commit): on the host, or on the device for an LBVH scene — and for a SAH scene when the device builder is
@@ -532,7 +544,7 @@ class PathTracer:
         for t in getattr(desc, "textures", []):
             t = np.ascontiguousarray(t, np.uint8)
             assert t.ndim == 3 and t.shape[2] == 4, "textures are (h, w, 4) uint8"
-            self._ck(L.ptc_add_texture_rgba8(h, t.ctypes.data_as(C.POINTER(C.c_uint8)), t.shape[1], t.shape[0]))
+            self._ck(L.ptc_add_texture_rgba8(h, _ptr(t), t.shape[1], t.shape[0]))
         self._ck(L.ptc_set_texture_filter(h, 1 if getattr(desc, "texture_filter", "nearest") == "linear" else 0))
         if getattr(desc, "bvh_builder", None) is not None:      # None: the context's default (SAH, or what PTC_BVH says)
             self._ck(L.ptc_set_bvh_builder(h, {"sah": 0, "lbvh": 1}[desc.bvh_builder]))
@@ -540,13 +552,13 @@ class PathTracer:
         if env is not None:
             e = np.ascontiguousarray(env, np.float32)
             assert e.ndim == 3 and e.shape[2] == 3, "env is (h, w, 3) float32"
-            self._ck(L.ptc_set_env_latlong_rgb32f(h, e.ctypes.data_as(C.POINTER(C.c_float)), e.shape[1], e.shape[0]))
+            self._ck(L.ptc_set_env_latlong_rgb32f(h, _ptr(e), e.shape[1], e.shape[0]))
         for m in desc.materials:
             self._ck(L.ptc_add_material(h, _f(m.base_color)[1], m.metallic, m.roughness, _f(m.emissive)[1], m.tex_color, m.tex_normal, m.tex_mr))
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
-            mid = self._ck(L.ptc_add_mesh(h, v.ctypes.data, v.size, i.ctypes.data_as(C.POINTER(C.c_uint32)), i.size, me.material))
+            mid = self._ck(L.ptc_add_mesh(h, v.ctypes.data, v.size, _ptr(i), i.size, me.material))
             if getattr(me, "morph_dpos", None) is not None:
                 self.mesh_set_morph_targets(mid, me.morph_dpos, getattr(me, "morph_dnormal", None), getattr(me, "morph_dtangent", None))
             if getattr(me, "joints", None) is not None:
@@ -577,9 +589,7 @@ class PathTracer:
         return self
 
     def get_light(self, light_id):
-        p = PtcLightParams()
-        self._ck(self._L.ptc_get_light(self._h, int(light_id), C.byref(p)))
-        return p.as_dict()
+        return self._get(self._L.ptc_get_light, PtcLightParams, int(light_id))
 
     def light_count(self):
         return self._ck(self._L.ptc_light_count(self._h))
@@ -594,7 +604,7 @@ class PathTracer:
         self._ck(self._L.ptc_debug_get_light_table(self._h, C.byref(n), None, None))
         rec, cdf = np.zeros((n.value, 16), np.float32), np.zeros(n.value, np.float32)
         if n.value:
-            self._ck(self._L.ptc_debug_get_light_table(self._h, None, rec.ctypes.data_as(C.POINTER(C.c_float)), cdf.ctypes.data_as(C.POINTER(C.c_float))))
+            self._ck(self._L.ptc_debug_get_light_table(self._h, None, _ptr(rec), _ptr(cdf)))
         return rec, cdf
 
     def punctual_nee(self, origins, dirs, keys, bounce=0):
@@ -607,9 +617,7 @@ class PathTracer:
         assert d.shape[0] == n and k.size == n
         valid = np.zeros(n, np.uint8)
         so, sd, tm, ct = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
-        fpt = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._ck(self._L.ptc_debug_punctual_nee(self._h, op, dp, k.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(bounce), valid.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                fpt(so), fpt(sd), fpt(tm), fpt(ct)))
+        self._ck(self._L.ptc_debug_punctual_nee(self._h, op, dp, _ptr(k), n, int(bounce), _ptr(valid), _ptr(so), _ptr(sd), _ptr(tm), _ptr(ct)))
         return valid.astype(bool), so, sd, tm, ct
 
     def set_camera(self, position, target, fov_y, aspect):
@@ -624,9 +632,7 @@ class PathTracer:
         return self
 
     def get_camera_lens(self):
-        p = PtcLensParams()
-        self._ck(self._L.ptc_get_camera_lens(self._h, C.byref(p)))
-        return p.as_dict()
+        return self._get(self._L.ptc_get_camera_lens, PtcLensParams)
 
     def focus_distance_at_pixel(self, x, y):
         """ptc_focus_distance_at_pixel: the view depth of what pixel (x, y)'s centre sees (0 on a miss), from the current frame's guides (frame_guides())."""
@@ -651,16 +657,14 @@ class PathTracer:
         """ptc_mesh_set_morph_targets, before the commit: dpos (and dnormal, dtangent, which may be None) are (n_targets, n_verts, 3) float32."""
         dp = np.ascontiguousarray(dpos, np.float32)
         assert dp.ndim == 3 and dp.shape[2] == 3, "morph deltas are (n_targets, n_verts, 3)"
-        keep = [dp]
-        ptrs = [dp.ctypes.data_as(C.POINTER(C.c_float))]
+        ptrs = [_ptr(dp)]
         for a in (dnormal, dtangent):
             if a is None:
                 ptrs.append(None)
                 continue
             a = np.ascontiguousarray(a, np.float32)
             assert a.shape == dp.shape, "every delta array has the shape of dpos"
-            keep.append(a)
-            ptrs.append(a.ctypes.data_as(C.POINTER(C.c_float)))
+            ptrs.append(_ptr(a))
         self._ck(self._L.ptc_mesh_set_morph_targets(self._h, int(mesh), dp.shape[0], *ptrs))
         return self
 
@@ -669,7 +673,7 @@ class PathTracer:
         j = np.ascontiguousarray(joints, np.uint16)
         w = np.ascontiguousarray(weights, np.float32)
         assert j.ndim == 2 and j.shape[1] == 4 and w.shape == j.shape, "joints and weights are (n_verts, 4)"
-        self._ck(self._L.ptc_mesh_set_skin(self._h, int(mesh), int(n_joints), j.ctypes.data_as(C.POINTER(C.c_uint16)), w.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_mesh_set_skin(self._h, int(mesh), int(n_joints), _ptr(j), _ptr(w)))
         return self
 
     def update_mesh_pose(self, mesh, morph_weights=None, joint_matrices=None):
@@ -679,11 +683,11 @@ class PathTracer:
         nw = nj = 0
         if morph_weights is not None:
             w = np.ascontiguousarray(morph_weights, np.float32).reshape(-1)
-            wp, nw = w.ctypes.data_as(C.POINTER(C.c_float)), w.size
+            wp, nw = _ptr(w), w.size
         if joint_matrices is not None:
             jm = np.ascontiguousarray(joint_matrices, np.float32)
             assert jm.size % 12 == 0, "joint matrices are 12 floats each"
-            jp, nj = jm.ctypes.data_as(C.POINTER(C.c_float)), jm.size // 12
+            jp, nj = _ptr(jm), jm.size // 12
         self._ck(self._L.ptc_update_mesh_pose(self._h, int(mesh), wp, nw, jp, nj))
         return self
 
@@ -696,9 +700,7 @@ class PathTracer:
 
     def mesh_vertices(self, mesh, n_verts):
         """ptc_debug_get_mesh_vertices: the current posed object-space vertices of a mesh as (n_verts, 12) float32."""
-        out = np.zeros((int(n_verts), 12), np.float32)
-        self._ck(self._L.ptc_debug_get_mesh_vertices(self._h, int(mesh), out.ctypes.data))
-        return out
+        return self._read(self._L.ptc_debug_get_mesh_vertices, (int(n_verts), 12), np.float32, int(mesh), alloc=np.zeros)
 
     def host_build_id(self):
         return int(self._L.ptc_debug_host_build_id(self._h))
@@ -740,15 +742,13 @@ class PathTracer:
         """ptc_probes_begin: a probe frame of len(positions) probes; frame_add_samples / frame_set_sample_range / sync work as in any frame, and after
         frame_resolve read_radiance returns the (1, n, 4) image of each probe's mean incoming radiance."""
         p = self._probe_positions(positions)
-        self._ck(self._L.ptc_probes_begin(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], index_base, spp_total, seed, max_bounces))
+        self._ck(self._L.ptc_probes_begin(self._h, _ptr(p), p.shape[0], index_base, spp_total, seed, max_bounces))
         self._w, self._h_px = p.shape[0], 1
         self._n_probes = p.shape[0]
 
     def read_probes_sh(self):
         """ptc_probes_read_sh: the SH9 coefficients of the probe frame in progress, (n, 9, 3) float32 laid out [probe][k][rgb]."""
-        out = np.zeros((getattr(self, "_n_probes", 0) or 1, 9, 3), np.float32)
-        self._ck(self._L.ptc_probes_read_sh(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_probes_read_sh, (getattr(self, "_n_probes", 0) or 1, 9, 3), np.float32, alloc=np.zeros)
 
     def render_probes(self, positions, spp, seed=0, max_bounces=8, index_base=0):
         """Bake the probes at `positions` (n, 3) with spp samples each: (n, 9, 3) float32 SH9 coefficients of the incoming radiance (sh9_irradiance turns them
@@ -756,8 +756,7 @@ class PathTracer:
         bit for bit those of the whole set."""
         p = self._probe_positions(positions)
         if index_base == 0:
-            out = np.zeros((p.shape[0], 9, 3), np.float32)
-            self._ck(self._L.ptc_render_probes(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], spp, seed, max_bounces, out.ctypes.data_as(C.POINTER(C.c_float))))
+            out = self._read(self._L.ptc_render_probes, (p.shape[0], 9, 3), np.float32, _ptr(p), p.shape[0], spp, seed, max_bounces, alloc=np.zeros)
             self._w, self._h_px, self._n_probes = p.shape[0], 1, p.shape[0]
             return out
         self.probes_begin(p, spp, seed, max_bounces, index_base)
@@ -769,8 +768,7 @@ class PathTracer:
         p = self._probe_positions(positions)
         n = p.shape[0] * int(n_samples)
         od, key = np.zeros((n, 6), np.float32), np.zeros(n, np.uint32)
-        self._ck(self._L.ptc_debug_probe_rays(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0], index_base, seed, first_sample, n_samples,
-                                              od.ctypes.data_as(C.POINTER(C.c_float)), key.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._ck(self._L.ptc_debug_probe_rays(self._h, _ptr(p), p.shape[0], index_base, seed, first_sample, n_samples, _ptr(od), _ptr(key)))
         return od[:, :3].copy(), od[:, 3:].copy(), key
 
     def debug_probe_project(self, n_probes, seed, first_sample, n_samples, lpath, acc=None, index_base=0):
@@ -780,8 +778,7 @@ class PathTracer:
             raise PtcError(f"debug_probe_project: lpath has {L.shape[0]} paths, expected {int(n_probes) * int(n_samples)}")
         a = np.zeros((n_probes, 9, 3), np.float32) if acc is None else np.array(acc, np.float32).reshape(n_probes, 9, 3)
         a = np.ascontiguousarray(a)
-        self._ck(self._L.ptc_debug_probe_project(self._h, n_probes, index_base, seed, first_sample, n_samples, L.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 a.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_debug_probe_project(self._h, n_probes, index_base, seed, first_sample, n_samples, _ptr(L), _ptr(a)))
         return a
 
     def frame_checkpoint(self):
@@ -789,12 +786,12 @@ class PathTracer:
         n, k = C.c_uint64(0), C.c_uint32(0)
         self._ck(self._L.ptc_frame_checkpoint(self._h, None, C.byref(n), C.byref(k)))
         acc = np.zeros((n.value, 4), np.float32)
-        self._ck(self._L.ptc_frame_checkpoint(self._h, acc.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n), C.byref(k)))
+        self._ck(self._L.ptc_frame_checkpoint(self._h, _ptr(acc), C.byref(n), C.byref(k)))
         return acc, int(k.value)
 
     def frame_restore(self, accum, samples_done):
         a = np.ascontiguousarray(accum, np.float32)
-        self._ck(self._L.ptc_frame_restore(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], samples_done))
+        self._ck(self._L.ptc_frame_restore(self._h, _ptr(a), a.shape[0], samples_done))
 
     def frame_set_sample_range(self, first_sample, resolve_divisor=0):
         self._ck(self._L.ptc_frame_set_sample_range(self._h, first_sample, resolve_divisor))
@@ -813,9 +810,7 @@ class PathTracer:
         self._ck(self._L.ptc_sync(self._h))
 
     def read_radiance(self):
-        out = np.empty((self._h_px, self._w, 4), np.float32)
-        self._ck(self._L.ptc_read_radiance_rgba32f(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_read_radiance_rgba32f, (self._h_px, self._w, 4), np.float32)
 
     def write_radiance(self, img):
         a, p = _f(img)
@@ -827,9 +822,7 @@ class PathTracer:
 
     def read_radiance_f16(self):
         """The radiance buffer as the reference's RGBA16F HdrImage holds it: (h, w, 4) float16."""
-        out = np.empty((self._h_px, self._w, 4), np.uint16)
-        self._ck(self._L.ptc_read_radiance_rgba16f(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
-        return out.view(np.float16)
+        return self._read(self._L.ptc_read_radiance_rgba16f, (self._h_px, self._w, 4), np.uint16).view(np.float16)
 
     def radiance_f16_device_ptr(self) -> int:
         return int(self._L.ptc_radiance_rgba16f_device_ptr(self._h) or 0)
@@ -841,35 +834,22 @@ class PathTracer:
 
     def read_guide(self, which):
         """(h, w, 4) float32: GUIDE_ALBEDO = (albedo rgb, class), GUIDE_NORMAL_DEPTH = (normal, depth)."""
-        out = np.empty((self._h_px, self._w, 4), np.float32)
-        self._ck(self._L.ptc_read_guide_rgba32f(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_read_guide_rgba32f, (self._h_px, self._w, 4), np.float32, int(which))
 
     def read_guide_hit(self):
         """(prim (h, w) int32 with -1 = miss, uv (h, w, 2) float32) of the guide rays' hits."""
         prim = np.empty((self._h_px, self._w), np.int32)
         uv = np.empty((self._h_px, self._w, 2), np.float32)
-        self._ck(self._L.ptc_read_guide_hit(self._h, prim.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_read_guide_hit(self._h, _ptr(prim), _ptr(uv)))
         return prim, uv
 
     @staticmethod
     def denoise_default_params():
-        p = PtcDenoiseParams()
-        load_library().ptc_denoise_default_params(C.byref(p))
-        return p.as_dict()
-
-    def _denoise_params(self, params):
-        p = PtcDenoiseParams()
-        self._L.ptc_denoise_default_params(C.byref(p))
-        for k, v in params.items():
-            if k not in dict(PtcDenoiseParams._fields_):
-                raise TypeError(f"denoise: unknown parameter {k}")
-            setattr(p, k, v)
-        return p
+        return PtcDenoiseParams.defaults().as_dict()
 
     def denoise(self, **params):
         """ptc_denoise: radiance buffer + guides -> the denoised buffer.  Keywords (iterations, sigma_l, sigma_n, sigma_p, demodulate) replace the defaults."""
-        self._ck(self._L.ptc_denoise(self._h, C.byref(self._denoise_params(params))))
+        self._ck(self._L.ptc_denoise(self._h, C.byref(PtcDenoiseParams.defaults(**params))))
 
     def select_output(self, which):
         """ptc_select_output: OUTPUT_RADIANCE or OUTPUT_DENOISED is what read_radiance / read_radiance_f16 / tonemap serve."""
@@ -884,20 +864,12 @@ class PathTracer:
     # ---- temporal accumulation ----------------------------------------------------------------------------
     @staticmethod
     def temporal_default_params():
-        p = PtcTemporalParams()
-        load_library().ptc_temporal_default_params(C.byref(p))
-        return p.as_dict()
+        return PtcTemporalParams.defaults().as_dict()
 
     def temporal_accumulate(self, **params):
         """ptc_temporal_accumulate: reproject the history through the frame's guides and blend the radiance buffer in; the accumulated image is
         OUTPUT_ACCUMULATED.  Keywords (max_history, sigma_z, demodulate) replace the defaults."""
-        p = PtcTemporalParams()
-        self._L.ptc_temporal_default_params(C.byref(p))
-        for k, v in params.items():
-            if k not in dict(PtcTemporalParams._fields_):
-                raise TypeError(f"temporal_accumulate: unknown parameter {k}")
-            setattr(p, k, v)
-        self._ck(self._L.ptc_temporal_accumulate(self._h, C.byref(p)))
+        self._ck(self._L.ptc_temporal_accumulate(self._h, C.byref(PtcTemporalParams.defaults(**params))))
 
     def temporal_reset(self):
         """ptc_temporal_reset: drop the history; the next temporal_accumulate() starts from nothing."""
@@ -908,13 +880,11 @@ class PathTracer:
         (x_prev, y_prev, W, reprojected n), and the history's copies of its frame's guides, TEMPORAL_NORMAL_DEPTH (N, Z) and TEMPORAL_POSITION_CLASS (P, K).
         (h, w) is the current frame's, which the library holds the history's size to: after a frame_begin with another size it raises (ptc error -2) until
         the next temporal_accumulate()."""
-        out = np.empty((self._h_px, self._w, 4), np.float32)
-        self._ck(self._L.ptc_read_temporal_rgba32f(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_read_temporal_rgba32f, (self._h_px, self._w, 4), np.float32, int(which))
 
     def denoise_accumulated(self, **params):
         """ptc_denoise_accumulated: the denoiser's iterations over the accumulated image, with the temporal variance where the history is long enough."""
-        self._ck(self._L.ptc_denoise_accumulated(self._h, C.byref(self._denoise_params(params))))
+        self._ck(self._L.ptc_denoise_accumulated(self._h, C.byref(PtcDenoiseParams.defaults(**params))))
 
     def temporal_seconds(self):
         """HIP-event seconds of the last temporal_accumulate()."""
@@ -925,23 +895,12 @@ class PathTracer:
     # ---- adaptive sampling ------------------------------------------------------------------------------
     @staticmethod
     def adaptive_default_params():
-        p = PtcAdaptiveParams()
-        load_library().ptc_adaptive_default_params(C.byref(p))
-        return p.as_dict()
-
-    def _adaptive_params(self, params):
-        p = PtcAdaptiveParams()
-        self._L.ptc_adaptive_default_params(C.byref(p))
-        for k, v in params.items():
-            if k not in dict(PtcAdaptiveParams._fields_):
-                raise TypeError(f"adaptive sampling: unknown parameter {k}")
-            setattr(p, k, v)
-        return p
+        return PtcAdaptiveParams.defaults().as_dict()
 
     def frame_set_adaptive(self, **params):
         """ptc_frame_set_adaptive, right after frame_begin: add_samples then feeds the active pixels only.  Keywords (threshold, radius, min_samples,
         step_samples) replace the defaults."""
-        self._ck(self._L.ptc_frame_set_adaptive(self._h, C.byref(self._adaptive_params(params))))
+        self._ck(self._L.ptc_frame_set_adaptive(self._h, C.byref(PtcAdaptiveParams.defaults(**params))))
 
     def frame_adapt(self):
         """ptc_frame_adapt: one decision step; returns the number of pixels still active."""
@@ -951,20 +910,16 @@ class PathTracer:
 
     def read_sample_counts(self):
         """(h, w) uint32: samples every pixel of the adaptive frame has received, 0 where this context does not own the pixel."""
-        out = np.zeros((self._h_px, self._w), np.uint32)
-        self._ck(self._L.ptc_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out
+        return self._read(self._L.ptc_read_sample_counts, (self._h_px, self._w), np.uint32, alloc=np.zeros)
 
     def render_adaptive(self, w, h, max_spp, seed=1, max_bounces=8, **params):
         """ptc_render_adaptive: at most max_spp samples per pixel, fewer where the estimate has converged; returns the image (read_sample_counts has the counts)."""
-        self._ck(self._L.ptc_render_adaptive(self._h, w, h, max_spp, seed, max_bounces, C.byref(self._adaptive_params(params))))
+        self._ck(self._L.ptc_render_adaptive(self._h, w, h, max_spp, seed, max_bounces, C.byref(PtcAdaptiveParams.defaults(**params))))
         self._w, self._h_px = w, h
         return self.read_radiance()
 
     def adaptive_stats(self):
-        s = PtcAdaptiveStats()
-        self._ck(self._L.ptc_get_adaptive_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        return self._get(self._L.ptc_get_adaptive_stats, PtcAdaptiveStats)
 
     # ---- denoising from per-sample statistics (DESIGN.md §8d) ----------------------------------------------
     def set_sample_covariance(self, on):
@@ -974,20 +929,16 @@ class PathTracer:
 
     def read_sample_covariance(self):
         """(h, w, 6) float32: the raw sums (rr, gg, bb, rg, rb, gb) of the current frame's samples, 0 where this context does not own the pixel."""
-        out = np.zeros((self._h_px, self._w, 6), np.float32)
-        self._ck(self._L.ptc_read_sample_covariance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_read_sample_covariance, (self._h_px, self._w, 6), np.float32, alloc=np.zeros)
 
     def denoise_sampled(self, **params):
         """ptc_denoise_sampled: the denoiser's iterations over the resolved radiance with the variance of the frame's own samples where a pixel has four or
         more (after frame_resolve and frame_guides).  Keywords as denoise()."""
-        self._ck(self._L.ptc_denoise_sampled(self._h, C.byref(self._denoise_params(params))))
+        self._ck(self._L.ptc_denoise_sampled(self._h, C.byref(PtcDenoiseParams.defaults(**params))))
 
     def read_sampled_variance(self):
         """(h, w, 2) float32: (Var_s, 1 / n) as the frame's last denoise_sampled() computed them, (0, 0) where the count is 0."""
-        out = np.zeros((self._h_px, self._w, 2), np.float32)
-        self._ck(self._L.ptc_read_sampled_variance(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
-        return out
+        return self._read(self._L.ptc_read_sampled_variance, (self._h_px, self._w, 2), np.float32, alloc=np.zeros)
 
     # ---- multi-GPU (RCCL through the C-ABI) ---------------------------------------------------------
     def comm_init(self, unique_id: bytes, rank: int, n_ranks: int):
@@ -1001,9 +952,7 @@ class PathTracer:
         self._ck(self._L.ptc_comm_destroy(self._h))
 
     def tonemap(self):
-        out = np.empty((self._h_px, self._w, 4), np.uint8)
-        self._ck(self._L.ptc_tonemap_rgba8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out
+        return self._read(self._L.ptc_tonemap_rgba8, (self._h_px, self._w, 4), np.uint8)
 
     # ---- display transform (csrc/pt_display.h) -----------------------------------------------
     def set_display(self, **fields):
@@ -1012,15 +961,13 @@ class PathTracer:
         if fields:
             p = PtcDisplayParams()
             self._ck(self._L.ptc_get_display(self._h, C.byref(p)))
-            self._ck(self._L.ptc_set_display(self._h, C.byref(_display_update(p, fields))))
+            self._ck(self._L.ptc_set_display(self._h, C.byref(p.update(**fields))))
         else:
             self._ck(self._L.ptc_set_display(self._h, None))
         return self
 
     def get_display(self):
-        p = PtcDisplayParams()
-        self._ck(self._L.ptc_get_display(self._h, C.byref(p)))
-        return p.as_dict()
+        return self._get(self._L.ptc_get_display, PtcDisplayParams)
 
     def meter_exposure(self):
         """ptc_meter_exposure: meter the image select_output serves and move the adaptation state; queued, does not wait."""
@@ -1040,26 +987,18 @@ class PathTracer:
 
     def exposure_state(self):
         """ptc_debug_display_state (waits): the integers of the state record, A (adaptation state), Q (last metering), N, M, rejected."""
-        w = (C.c_uint32 * 8)()
-        self._ck(self._L.ptc_debug_display_state(self._h, w))
-        return {"A": w[0], "Q": w[1], "N": w[2], "M": w[3], "rejected": w[4]}
+        return dict(zip(("A", "Q", "N", "M", "rejected"), self._read(self._L.ptc_debug_display_state, 8, np.uint32, alloc=np.zeros).tolist()))
 
     def luminance_histogram(self):
-        out = np.zeros(LUMINANCE_BINS, np.uint32)
-        self._ck(self._L.ptc_read_luminance_histogram(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out
+        return self._read(self._L.ptc_read_luminance_histogram, LUMINANCE_BINS, np.uint32, alloc=np.zeros)
 
     def display(self):
         """ptc_display_rgba8: the served image through exposure, operator and transfer function: (h, w, 4) uint8."""
-        out = np.empty((self._h_px, self._w, 4), np.uint8)
-        self._ck(self._L.ptc_display_rgba8(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return out
+        return self._read(self._L.ptc_display_rgba8, (self._h_px, self._w, 4), np.uint8)
 
     def display_f16(self):
         """ptc_display_rgba16f: the served image times the exposure scale as RGBA16F: (h, w, 4) float16."""
-        out = np.empty((self._h_px, self._w, 4), np.uint16)
-        self._ck(self._L.ptc_display_rgba16f(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
-        return out.view(np.float16)
+        return self._read(self._L.ptc_display_rgba16f, (self._h_px, self._w, 4), np.uint16).view(np.float16)
 
     def display_f16_device_ptr(self) -> int:
         return int(self._L.ptc_display_rgba16f_device_ptr(self._h) or 0)
@@ -1071,14 +1010,10 @@ class PathTracer:
         return m.value, d.value
 
     def display_internals(self):
-        w = (C.c_uint64 * 4)()
-        self._ck(self._L.ptc_debug_display_internals(self._h, w))
-        return [int(v) for v in w]
+        return self._read(self._L.ptc_debug_display_internals, 4, np.uint64, alloc=np.zeros).tolist()
 
     def stats(self):
-        s = PtcStats()
-        self._ck(self._L.ptc_get_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        return self._get(self._L.ptc_get_stats, PtcStats)
 
     # ---- test hooks -------------------------------------------------------------------------------
     def trace_closest(self, origins, dirs):
@@ -1088,18 +1023,14 @@ class PathTracer:
         t = np.zeros(n, np.float32)
         prim = np.zeros(n, np.int32)
         uv = np.zeros((n, 2), np.float32)
-        self._ck(self._L.ptc_debug_trace_closest(self._h, op, dp, n, t.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 prim.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_debug_trace_closest(self._h, op, dp, n, _ptr(t), _ptr(prim), _ptr(uv)))
         return t, prim, uv
 
     def trace_any(self, origins, dirs, tmax):
         o, op = _f(origins)
         d, dp = _f(dirs)
         tm, tp = _f(tmax)
-        n = o.shape[0]
-        occ = np.zeros(n, np.uint8)
-        self._ck(self._L.ptc_debug_trace_any(self._h, op, dp, tp, n, occ.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return occ
+        return self._read(self._L.ptc_debug_trace_any, o.shape[0], np.uint8, op, dp, tp, o.shape[0], alloc=np.zeros)
 
     def debug_camera_rays(self, w, h, seed, first_sample, n_samples, pixels=None):
         """ptc_debug_camera_rays: (origins, dirs), each (n_samples * n_pixels, 3) float32 in path order p = sample_local * n_pixels + j, of the path integrator's
@@ -1107,8 +1038,7 @@ class PathTracer:
         px = np.arange(w * h, dtype=np.uint32) if pixels is None else np.ascontiguousarray(pixels, np.uint32).reshape(-1)
         n = px.size * int(n_samples)
         o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
-        self._ck(self._L.ptc_debug_camera_rays(self._h, w, h, seed, first_sample, n_samples, px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size,
-                                               o.ctypes.data_as(C.POINTER(C.c_float)), d.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_debug_camera_rays(self._h, w, h, seed, first_sample, n_samples, _ptr(px), px.size, _ptr(o), _ptr(d)))
         return o, d
 
     def flat_scene(self):
@@ -1117,8 +1047,7 @@ class PathTracer:
         verts = np.zeros((nv.value, 12), np.float32)
         idx = np.zeros((nt.value, 3), np.uint32)
         tm = np.zeros(nt.value, np.int32)
-        self._ck(self._L.ptc_debug_get_flat_scene(self._h, None, None, verts.ctypes.data, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  tm.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self._L.ptc_debug_get_flat_scene(self._h, None, None, verts.ctypes.data, _ptr(idx), _ptr(tm)))
         return verts, idx, tm
 
     def description(self):
@@ -1129,7 +1058,7 @@ class PathTracer:
         for i in range(nm.value):
             f = np.zeros(9, np.float32)
             t = (C.c_int * 3)()
-            self._ck(self._L.ptc_debug_get_material(self._h, i, f.ctypes.data_as(C.POINTER(C.c_float)), t))
+            self._ck(self._L.ptc_debug_get_material(self._h, i, _ptr(f), t))
             mats.append((f, tuple(t)))
         for i in range(nt.value):
             w, h = C.c_int(0), C.c_int(0)
@@ -1146,12 +1075,11 @@ class PathTracer:
         self._ck(self._L.ptc_debug_get_bvh(self._h, C.byref(nn), C.byref(nt), C.byref(nu), None, None))
         units = np.zeros((nu.value, 4), np.float32)
         grid = np.zeros(6, np.float32)
-        self._ck(self._L.ptc_debug_get_bvh(self._h, None, None, None, units.ctypes.data_as(C.POINTER(C.c_float)), grid.ctypes.data_as(C.POINTER(C.c_float))))
+        self._ck(self._L.ptc_debug_get_bvh(self._h, None, None, None, _ptr(units), _ptr(grid)))
         return units, nn.value, nt.value, grid
 
     def internals(self):
-        buf = (C.c_uint64 * 8)()
-        self._ck(self._L.ptc_debug_get_internals(self._h, buf))
+        buf = self._read(self._L.ptc_debug_get_internals, 8, np.uint64, alloc=np.zeros)
         keys = ("events_created", "spans_waiting", "queue_cap", "per_batch", "pending", "trace_blocks_per_cu", "stack_lds", "refit_on_device")
         d = {k: int(buf[i]) for i, k in enumerate(keys)}
         d["commit_on_device"] = (d["refit_on_device"] >> 1) & 1
@@ -1162,15 +1090,13 @@ class PathTracer:
 
     def commit_host_parts(self):
         """The host's share of a commit on the device, checked against the host build (ptc_debug_commit_host_parts)."""
-        buf = (C.c_uint64 * 8)()
-        self._ck(self._L.ptc_debug_commit_host_parts(self._h, buf))
+        buf = self._read(self._L.ptc_debug_commit_host_parts, 8, np.uint64, alloc=np.zeros)
         keys = ("n_tris", "n_lights", "indices_ok", "emitters_ok", "materials_ok", "tables_ok", "sizes_ok")
         return {k: int(buf[i]) for i, k in enumerate(keys)}
 
     def refit_host_parts(self):
         """The host's share of a refit on the device, checked against the host build (ptc_debug_refit_host_parts)."""
-        buf = (C.c_uint64 * 8)()
-        self._ck(self._L.ptc_debug_refit_host_parts(self._h, buf))
+        buf = self._read(self._L.ptc_debug_refit_host_parts, 8, np.uint64, alloc=np.zeros)
         keys = ("n_verts", "n_tris", "nodes_listed", "levels", "emissive_prims", "levels_ok", "emitters_equal", "transforms_finite")
         return {k: int(buf[i]) for i, k in enumerate(keys)}
 
@@ -1183,8 +1109,7 @@ class PathTracer:
         shade = np.zeros((n, 4 * stride.value), np.float32)
         lights = np.zeros((max(nl.value, 1), 20), np.float32)
         cdf = np.zeros(max(nl.value, 1), np.float32)
-        f = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._ck(self._L.ptc_debug_get_shading_tables(self._h, None, f(shade), None, f(lights), f(cdf)))
+        self._ck(self._L.ptc_debug_get_shading_tables(self._h, None, _ptr(shade), None, _ptr(lights), _ptr(cdf)))
         return shade, lights[:max(nl.value, 1)], cdf
 
     def raw_counters(self):
@@ -1209,28 +1134,27 @@ class Group:
     def __len__(self):
         return int(self._L.ptc_group_size(self._g))
 
+    def _ck(self, rc):
+        if rc < 0:
+            raise PtcError(f"ptc error {rc}: {self._L.ptc_group_last_error(self._g).decode()}")
+        return rc
+
     def ctx(self, i) -> PathTracer:
         return self._ctx[i]
 
     def load_scene(self, desc):
         """Describe the scene on device 0 and commit it to every device with ONE host build (ptc_group_scene_commit)."""
         self._ctx[0].load_scene(desc)
-        rc = self._L.ptc_group_scene_commit(self._g)
-        if rc < 0:
-            raise PtcError(f"ptc error {rc}: {self._L.ptc_group_last_error(self._g).decode()}")
+        self._ck(self._L.ptc_group_scene_commit(self._g))
         return self
 
     def scene_refit(self):
         """After ctx(0).update_instance(...): one host refit, uploaded to every device (ptc_group_scene_refit)."""
-        rc = self._L.ptc_group_scene_refit(self._g)
-        if rc < 0:
-            raise PtcError(f"ptc error {rc}: {self._L.ptc_group_last_error(self._g).decode()}")
+        self._ck(self._L.ptc_group_scene_refit(self._g))
         return self
 
     def render(self, w, h, spp, seed=1, max_bounces=8, integrator=INTEGRATOR_PATH):
-        rc = self._L.ptc_group_render(self._g, w, h, spp, seed, max_bounces, integrator)
-        if rc < 0:
-            raise PtcError(f"ptc error {rc}: {self._L.ptc_group_last_error(self._g).decode()}")
+        self._ck(self._L.ptc_group_render(self._g, w, h, spp, seed, max_bounces, integrator))
         for c in self._ctx:
             c._w, c._h_px = w, h
         return self._ctx[0].read_radiance()

@@ -1,0 +1,105 @@
+"""The ctypes bindings say what the C headers say: pbr_amd/ptc.py's prototype table, struct mirrors and constants against include/ptc.h, and
+oracle/ora.py's table and struct against oracle/ptc_oracle.h.  A function missing from a table is called with ctypes' defaults (every argument a C int,
+the result a C int), which truncates a 64-bit seed or a pointer without a word; these tests are what notices.  tests/c_header.py reads the headers."""
+import ctypes as C
+import os
+
+import pytest
+
+import c_header
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def ptc_h():
+    return c_header.Header(os.path.join(ROOT, "include", "ptc.h"), "ptc_")
+
+
+@pytest.fixture(scope="module")
+def oracle_h():
+    return c_header.Header(os.path.join(ROOT, "oracle", "ptc_oracle.h"), "ora_")
+
+
+def test_the_reader_finds_what_the_library_exports(pbr, ptc_h):
+    """The reader is held to the library: it finds a prototype for every ptc_* symbol libptc.so exports, and nothing else."""
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", pbr.ptc.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("ptc_") and line.split()[-2] in "TW")
+    assert sorted(ptc_h.prototypes) == exported
+    assert len(exported) == 129
+
+
+def test_prototype_table_matches_the_header(pbr, ptc_h):
+    table = pbr.ptc._PROTOTYPES
+    assert c_header.check_prototypes(ptc_h, table) == []
+    assert pbr.ptc.ABI_SYMBOLS == list(table)
+    L = pbr.load_library()
+    for name, (restype, argtypes) in table.items():       # the loaded library carries the table, not ctypes' defaults
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_prototype_table_is_in_the_headers_order(pbr, ptc_h):
+    """The table lists the functions in exactly the order the header declares them: that keeps a feature's prototypes together, section by section, and
+    leaves one place for a new row.  Exact order is meant: moving a declaration inside a header section means moving its row too."""
+    assert list(pbr.ptc._PROTOTYPES) == list(ptc_h.prototypes)
+
+
+def test_struct_mirrors_match_the_header(pbr, ptc_h):
+    assert len(ptc_h.structs) == 9 and "ptc_ctx" not in ptc_h.structs and "ptc_group" not in ptc_h.structs
+    bad = []
+    for name, fields in ptc_h.structs.items():
+        if name == "ptc_vertex":
+            continue
+        mirror = getattr(pbr.ptc, c_header.mirror_name(name), None)
+        assert mirror is not None and issubclass(mirror, C.Structure), f"{name} has no mirror {c_header.mirror_name(name)}"
+        bad += c_header.check_struct(fields, mirror)
+    assert bad == []
+    assert C.sizeof(pbr.ptc.PtcStats) == 9 * 8 + 7 * 8 + 6 * 4 + 3 * 8
+
+
+def test_mesh_vertex_dtype_matches_ptc_vertex(pbr, ptc_h):
+    """ptc_vertex's mirror is the numpy dtype scene.MESH_VERTEX: same fields at the same offsets, 48 bytes.  The dtype keeps the reference's spelling of its
+    last member (pbr::MeshVertex::texCoords), the header says texcoord: the one name that differs, and it is pinned here."""
+    spelling = {"texcoord": "texCoords"}
+    dt = pbr.scene.MESH_VERTEX
+    fields = ptc_h.structs["ptc_vertex"]
+    assert list(dt.names) == [spelling.get(k, k) for k, _, _ in fields]
+    offset = 0
+    for k, kind, n in fields:
+        sub, at = dt.fields[spelling.get(k, k)]
+        assert kind == "float" and sub.base == "<f4" and sub.shape == (n,) and at == offset, k
+        offset += 4 * n
+    assert dt.itemsize == offset == 48
+
+
+def test_constants_match_the_header(pbr, ptc_h):
+    mod = pbr.ptc
+    public = {k: v for k, v in vars(mod).items() if k.isupper() and not k.startswith("_") and isinstance(v, int)}
+    held = {k: v for k, v in public.items() if "PTC_" + k in ptc_h.constants}
+    assert {k: ptc_h.constants["PTC_" + k] for k in held} == held
+    # the rule above must not quietly hold nothing: these are in the header by name
+    for k in ("ABI_VERSION", "DEVICE_NONE", "COMM_ID_BYTES", "MAX_LIGHTS", "INTEGRATOR_PATH", "INTEGRATOR_RASTER_COMPAT", "INTEGRATOR_RASTER_GBUFFER16",
+              "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "TONEMAP_ACES", "TONEMAP_PBR_NEUTRAL", "TONEMAP_REINHARD", "TONEMAP_CLAMP", "OETF_GAMMA22", "OETF_SRGB",
+              "GUIDE_ALBEDO", "GUIDE_NORMAL_DEPTH", "OUTPUT_RADIANCE", "OUTPUT_DENOISED", "OUTPUT_ACCUMULATED", "TEMPORAL_HISTORY", "TEMPORAL_MOMENTS",
+              "TEMPORAL_MOTION", "TEMPORAL_NORMAL_DEPTH", "TEMPORAL_POSITION_CLASS"):
+        assert k in held, k
+    # the histogram's size has no name in the header: it is the declared length of the two arrays that hold one
+    assert mod.LUMINANCE_BINS == ptc_h.array_length("ptc_read_luminance_histogram", 1) == ptc_h.array_length("ptc_debug_meter", 9)
+    assert mod.COMM_ID_BYTES == ptc_h.array_length("ptc_comm_unique_id", 0)
+    # every public integer constant of the binding is held by one of the two rules
+    assert sorted(set(public) - set(held)) == ["LUMINANCE_BINS"]
+
+
+def test_oracle_binding_matches_its_header(ora, oracle_h):
+    table = ora._PROTOTYPES
+    assert len(oracle_h.prototypes) == 34
+    assert c_header.check_prototypes(oracle_h, table) == []
+    L = ora.lib()
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert list(oracle_h.structs) == ["ora_stats"]
+    assert c_header.check_struct(oracle_h.structs["ora_stats"], ora.OraStats) == []

@@ -60,7 +60,7 @@ def uniform_frame(pt, spp):
 def adaptive_frame(pt, thr, mn, step):
     t0 = time.perf_counter()
     L, h = pt._L, pt._h
-    pt._ck(L.ptc_render_adaptive(h, W, H, args.max_spp, SEED, BOUNCES, pbr_amd.ptc.C.byref(pt._adaptive_params(dict(threshold=thr, min_samples=mn, step_samples=step)))))
+    pt._ck(L.ptc_render_adaptive(h, W, H, args.max_spp, SEED, BOUNCES, pbr_amd.ptc.C.byref(pbr_amd.ptc.PtcAdaptiveParams.defaults(threshold=thr, min_samples=mn, step_samples=step))))
     wall = time.perf_counter() - t0
     pt._w, pt._h_px = W, H
     st, ad = pt.stats(), pt.adaptive_stats()
