@@ -398,7 +398,7 @@ struct RayRing {
       const ray_t r = make_ray(V3(A.x, A.y, A.z), V3(A.w, B.x, B.y));
       f[lane] = ri;
       f[TRACE_RING + lane] = __float_as_uint(r.inv.x); f[2 * TRACE_RING + lane] = __float_as_uint(r.inv.y); f[3 * TRACE_RING + lane] = __float_as_uint(r.inv.z);
-      f[4 * TRACE_RING + lane] = (r.inv.x >= 0.0f ? 1u : 0u) | (r.inv.y >= 0.0f ? 2u : 0u) | (r.inv.z >= 0.0f ? 4u : 0u);
+      f[4 * TRACE_RING + lane] = ray_octant(r);
     }
     n = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -442,42 +442,107 @@ PT_DEV void load_triangle(const DevScene& sc, uint32_t top_addr, uint32_t k, flo
   a = make_float4(x.x, x.y, x.z, x.w); b = make_float4(y.x, y.y, y.z, y.w); c = make_float4(z.x, z.y, z.z, z.w);
 }
 
-// =================================================================================================
-// P3 closest-hit traversal + triangle intersection: persistent waves, dynamic lane refill, 8-wide BVH.
-// Per node: the 8 slots are tested against [tmin, best_t]; the triangles of the hit leaf slots are intersected (slot
-// order) before the ray descends into the hit interior children, nearest octant first.
-// Closest hit = lexicographic minimum of (t, original primitive id).
-// The hit record (t, prim | class<<28, u, v) is written IN PLACE at the ray's slot (miss: prim = -1).
-// CULL: R6 back-face culling + per-ray [tmin,tmax] from B.zw (raster-compat primary rays).
-template <bool CULL>
-__global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(DevScene sc, DevQueues q, int qi, int stack_lds) {
+// Leaf phase, the part both kernels share: every lane with pending triangles tests one; a lane that then still has triangles pending hands its next
+// one to a lane that is not at a leaf (the k-th such owner to the k-th free lane, through two 64-byte LDS tables; the helper
+// fetches the owner's ray through ds_bpermute and returns its result the same way).  What is done with the two results is the kernel's (leaf_pass below).
+// (No hand-outs, and two or more per lane, both lost: profiles/r03_leaf_extra.txt; the code of both is profiles/exp_leaf_extra.patch.)
+struct LeafPair {
+  typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
+  bool leaf, paired, helper;      // at a leaf · an owner whose second triangle found a free lane · a free lane that tests such a triangle
+  uint32_t k1, k2, tmask_after;   // unit addresses of the lane's first and second triangle; its pending set with the second taken as well (`tmask` of open: the first only)
+  uint32_t rank_more, rank_free;
+  lds_u8 *tab_owner, *tab_helper;
+  // m_leaf: the lanes at a leaf, not empty.  Takes the triangles, makes the pairs and leaves both tables visible to the wave.
+  PT_DEV void open(uint64_t m_leaf, int cur, uint32_t tbase, uint32_t& tmask, uint32_t wave, uint32_t lane) {
+    __shared__ uint8_t s_pair[2][TRACE_WAVES][64];   // k-th owner with a second triangle <-> k-th free lane
+    leaf = cur == CUR_LEAF;
+    k1 = 0; k2 = 0;
+    bool more = false;
+    if (leaf) { k1 = next_triangle(tbase, tmask); more = (tmask & 255u) != 0u; }
+    const uint64_t m_more = __ballot(more), m_free = ~m_leaf;
+    const uint32_t n_more = (uint32_t)__popcll(m_more), n_free = (uint32_t)__popcll(m_free);
+    rank_more = mbcnt64(m_more); rank_free = mbcnt64(m_free);
+    paired = more && rank_more < n_free; helper = !leaf && rank_free < n_more;
+    tab_owner = (lds_u8*)s_pair[0][wave];
+    tab_helper = (lds_u8*)s_pair[1][wave];
+    tmask_after = tmask;
+    if (paired) { k2 = next_triangle(tbase, tmask_after); tab_owner[rank_more] = (uint8_t)lane; }
+    if (helper) tab_helper[rank_free] = (uint8_t)lane;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  PT_DEV int src(uint32_t lane) const { return helper ? (int)tab_owner[rank_free] : (int)lane; }      // whose ray this lane tests with
+  PT_DEV int hsrc(uint32_t lane) const { return paired ? (int)tab_helper[rank_more] : (int)lane; }    // the lane that tested this owner's second triangle
+  // the ray of lane `src` (origin and direction) and the unit address of the triangle this lane tests with it
+  PT_DEV uint32_t fetch(const ray_t& r, int src, ray_t& rr) const {
+    rr.o = V3(__shfl(r.o.x, src), __shfl(r.o.y, src), __shfl(r.o.z, src));
+    rr.d = V3(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src));
+    const uint32_t k2_src = (uint32_t)__shfl((int)k2, src);                 // unconditional: a shuffle inside ?: would run with the owners masked off
+    return helper ? k2_src : k1;
+  }
+  PT_DEV bool tests() const { return leaf || helper; }      // this lane has a triangle to test in this pass
+};
+
+// counters: the wave totals are summed over the block first, then one atomic per counter (total[i] goes to the statistic AT[i]), each counter on its own line (ptc_internal.h, ST_STRIDE)
+template <int... AT>
+PT_DEV void flush_trace_stats(unsigned long long* stats, const unsigned long long (&total)[sizeof...(AT)]) {
+  constexpr int N = (int)sizeof...(AT);
+  __shared__ unsigned long long s_stat[TRACE_WAVES][N];
+  const uint32_t wave = threadIdx.x >> 6;
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) s_stat[wave][i] = total[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)N) {
+    unsigned long long v = 0;
+    for (int w = 0; w < TRACE_WAVES; ++w) v += s_stat[w][threadIdx.x];
+    int at = 0; uint32_t i = 0;
+    ((at = threadIdx.x == i++ ? AT : at), ...);
+    if (v) atomicAdd(&stats[at * ST_STRIDE], v);
+  }
+}
+
+// The skeleton both trace kernels run: persistent waves, dynamic lane refill, 8-wide BVH.  RAY is what a kernel keeps per ray and does with it (ClosestRay, AnyRay below):
+//   start(B)                       the ray's own fields from the B word of its queue record
+//   tmin(), tfar()                 the interval of the node visits
+//   leaf_pass(lp, ...)             tests this lane's triangle of the pass (LeafPair) and consumes the results; true: the ray ends here
+//   hit()                          counted as a hit when the ray is finished (wave-uniform count)
+//   publish(q, ri, debug_out)      the finished ray's result
+//   flush(stats, nv, nt, nr, nh)   the kernel's counters (flush_trace_stats)
+// ORDERED: interior children nearest octant first (the slot-order table) instead of ascending; NODE_MIN: the kernel's TRACE_NODE_MIN.
+// The queue is (hdr, pre, seg_cnt, ctr) with its rays in (QA, QB).
+// Why ONE function with the phases as its sections, and not a function per phase: the compiler simplifies a callee before it inlines it.  A phase with a loop of
+// its own that reaches the lane's state through references or a struct came out with that state in another shape (pairs of words fused into 64-bit registers, flags
+// as bytes) — 2 to 32 VGPR spills, or twelve v_mov per node iteration (profiles/trace_skeleton.txt).  With the state as plain locals of the function that holds the
+// loops, and only loop-free pieces behind calls (LeafPair, RAY, flush_trace_stats), the machine code is the hand-copied one to within a few instructions.
+template <class RAY, bool ORDERED, int NODE_MIN>
+PT_DEV void trace_queue(const DevScene& sc, const DevQueues& q, int stack_lds, const uint32_t* hdr, const uint32_t* pre, const uint32_t* seg_cnt, uint32_t* ctr,
+                        const float4* QA, const float4* QB, uint8_t* debug_out) {
   extern __shared__ float4 lds_raw[];
-  __shared__ uint8_t s_pair[2][TRACE_WAVES][64];   // leaf phase: k-th owner with a second triangle <-> k-th free lane
+  // ---- block and wave setup ----
   const uint32_t lane = lane_id();
   const uint32_t wave = threadIdx.x >> 6;
-  if (Reservoir::block_has_no_work(&q.cnt[CNT_RAY_TOTAL])) return;     // a short queue: most blocks of the persistent grid leave before staging anything
-  const TraceLds L = trace_lds(lds_raw, sc, stack_lds, true);
+  if (Reservoir::block_has_no_work(hdr)) return;     // a short queue: most blocks of the persistent grid leave before staging anything
+  const TraceLds L = trace_lds(lds_raw, sc, stack_lds, ORDERED);
   uint8_t* order_tab = L.order_tab;
   for (uint32_t i = threadIdx.x; i < sc.n_lds_units; i += TRACE_BLOCK) lds_raw[i] = sc.recs[i];
-  build_order_table(order_tab);
+  if (ORDERED) build_order_table(order_tab);
   __syncthreads();
-  const RayQ rq = q.ray[qi];
   unsigned long long nv = 0, nr = 0, nh = 0;   // wave totals, only updated at wave-uniform points: they live in SGPRs
   uint32_t nt = 0;                               // per lane (updated inside the divergent leaf phase)
-  Reservoir res; res.init(&q.cnt[CNT_RAY_TOTAL], (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave)));
-  const uint32_t* seg_cnt = q.seg_ray[qi];
+  const uint32_t wave_in_grid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave));
+  Reservoir res; res.init(hdr, wave_in_grid);
   WStack st;
-  st.init(L.stack + (size_t)wave * (size_t)stack_lds * 64u + lane,
-          sc.stack_ovf + ((size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave)) * sc.ovf_depth) * 64u, stack_lds);
+  st.init(L.stack + (size_t)wave * (size_t)stack_lds * 64u + lane, sc.stack_ovf + ((size_t)(int)wave_in_grid * sc.ovf_depth) * 64u, stack_lds);
+  RayRing ring; ring.init(L.ring + (size_t)wave * RING_FIELDS * TRACE_RING);
   int cur = CUR_DONE;
   uint32_t ri = 0, oct = 0, gbase = 0, gmask = 0, tbase = 0, tmask = 0;
   ray_t r = make_ray(V3(0, 0, 0), V3(0, 0, 1));
-  float tmin = 0.0f, best_t = PT_T_INF, best_u = 0.0f, best_v = 0.0f;
-  int best_prim = 0x7fffffff, best_cls = 0;
-  bool found = false;
-  RayRing ring; ring.init(L.ring + (size_t)wave * RING_FIELDS * TRACE_RING);
+  RAY ray;
   for (;;) {
-    // ---- hand prepared rays to the idle lanes (RayRing) ----
+    // ---- refill: hand prepared rays to the idle lanes (RayRing) ----
     {
       bool idle = cur == CUR_DONE;
       uint64_t mi = __ballot(idle);
@@ -485,18 +550,17 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
         while (mi) {
           if (ring.n == 0u) {
             if (res.exhausted) break;
-            ring.stage(res, q, q.pre_ray, seg_cnt, &q.cnt[CNT_WORK_TRACE], rq.A, rq.B, lane);
+            ring.stage(res, q, pre, seg_cnt, ctr, QA, QB, lane);
             if (ring.n == 0u) break;
           }
           v3 inv = V3(0, 0, 0); uint32_t oc = 0;
           const bool got = ring.pop(idle, ri, inv, oc);
           nr += (unsigned long long)__popcll(__ballot(got));
           if (got) {
-            const float4 A = rq.A[ri], Bq = rq.B[ri];
+            const float4 A = QA[ri], Bq = QB[ri];
             r.o = V3(A.x, A.y, A.z); r.d = V3(A.w, Bq.x, Bq.y); r.inv = inv;
             oct = oc;
-            tmin = CULL ? Bq.z : 0.0f;
-            best_t = CULL ? Bq.w : PT_T_INF; best_u = 0.0f; best_v = 0.0f; best_prim = 0x7fffffff; best_cls = 0; found = false;
+            ray.start(Bq);
             st.reset();
             gmask = 0; tmask = 0;
             cur = 0;
@@ -507,245 +571,152 @@ __global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(
     }
     if (!__ballot(cur != CUR_DONE)) break;        // nothing in flight, nothing prepared, the queue exhausted
     // ---- one cycle: node visits while enough lanes walk, one leaf pass, publish ----
-    {
-      for (;;) {
-        const uint64_t mn = __ballot(cur >= 0);
-        if (!mn) break;
-        if (__popcll(mn) < TRACE_NODE_MIN && __ballot(cur == CUR_LEAF)) break;   // few walkers, triangles waiting
-        nv += (unsigned long long)__popcll(mn);
-        if (cur >= 0) {
-          uint32_t nb, masks;
-          const uint32_t node_addr = L.top_addr + 16u * (uint32_t)cur;
-          const uint32_t hits = node_visit(sc, node_addr, cur, r, oct, tmin, best_t, nb, masks);
-          const uint32_t imask = masks & 255u, lhits = hits & (masks >> 8);
-          enter_group(gbase, gmask, st, nb, hits & imask, imask);
-          tbase = nb + 4u * (uint32_t)__builtin_popcount(imask);
-          tmask = lhits | (masks & 0x00ffff00u);
-          cur = lhits ? CUR_LEAF : advance<true>(gbase, gmask, st, order_tab, oct);
-        }
-      }
-      // ---- leaf phase: every lane with pending triangles tests one; a lane that then still has triangles pending hands its next
-      // one to a lane that is not at a leaf (the k-th such owner to the k-th free lane, through two 64-byte LDS tables; the helper
-      // fetches the owner's ray through ds_bpermute and returns its result the same way).  Same tests, same results and counters
-      // as one triangle per pass — closest hit is an order-independent minimum — in fewer passes.  (No hand-outs, and two or more per lane, both lost:
-      // profiles/r03_leaf_extra.txt; the code of both is profiles/exp_leaf_extra.patch.)
-      {
-        const bool leaf = cur == CUR_LEAF;
-        const uint64_t m_leaf = __ballot(leaf);
-        if (m_leaf) {
-          uint32_t k1 = 0, k2 = 0;
-          bool more = false;
-          if (leaf) { k1 = next_triangle(tbase, tmask); more = (tmask & 255u) != 0u; }
-          const uint64_t m_more = __ballot(more), m_free = ~m_leaf;
-          const uint32_t n_more = (uint32_t)__popcll(m_more), n_free = (uint32_t)__popcll(m_free);
-          const uint32_t rank_more = mbcnt64(m_more), rank_free = mbcnt64(m_free);
-          const bool paired = more && rank_more < n_free, helper = !leaf && rank_free < n_more;
-          typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-          lds_u8* tab_owner = (lds_u8*)s_pair[0][wave];
-          lds_u8* tab_helper = (lds_u8*)s_pair[1][wave];
-          if (paired) { k2 = next_triangle(tbase, tmask); tab_owner[rank_more] = (uint8_t)lane; }
-          if (helper) tab_helper[rank_free] = (uint8_t)lane;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const int src = helper ? (int)tab_owner[rank_free] : (int)lane;        // whose ray this lane tests with
-          ray_t rr;
-          rr.o = V3(__shfl(r.o.x, src), __shfl(r.o.y, src), __shfl(r.o.z, src));
-          rr.d = V3(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src));
-          const uint32_t k2_src = (uint32_t)__shfl((int)k2, src);                 // unconditional: a shuffle inside ?: would run with the owners masked off
-          const uint32_t k = helper ? k2_src : k1;
-          bool hit = false; float t = 0.0f, u = 0.0f, v = 0.0f; int pid = 0, cls = 0;
-          if (leaf || helper) {
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            hit = tri_test<CULL>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v);
-            pid = __float_as_int(a.w); cls = __float_as_int(b.w);
-          }
-          if (leaf) {
-            ++nt;
-            if (hit && t > tmin && (t < best_t || (t == best_t && pid < best_prim))) {
-              best_t = t; best_u = u; best_v = v; best_prim = pid; best_cls = cls; found = true;
-            }
-          }
-          const int hsrc = paired ? (int)tab_helper[rank_more] : (int)lane;      // the lane that tested this owner's second triangle
-          const int h2 = __shfl(hit ? 1 : 0, hsrc);
-          const float t2 = __shfl(t, hsrc), u2 = __shfl(u, hsrc), v2 = __shfl(v, hsrc);
-          const int pid2 = __shfl(pid, hsrc), cls2 = __shfl(cls, hsrc);
-          if (paired) {
-            ++nt;
-            if (h2 && t2 > tmin && (t2 < best_t || (t2 == best_t && pid2 < best_prim))) {
-              best_t = t2; best_u = u2; best_v = v2; best_prim = pid2; best_cls = cls2; found = true;
-            }
-          }
-          if (leaf && (tmask & 255u) == 0u) cur = advance<true>(gbase, gmask, st, order_tab, oct);
-        }
-      }
-      nh += (unsigned long long)__popcll(__ballot(cur == CUR_FINISHED && found));
-      if (cur == CUR_FINISHED) {                                       // this lane's ray is finished: publish in place
-        q.hit[ri] = make_float4(found ? best_t : -1.0f, __int_as_float(found ? (best_prim | (best_cls << HIT_CLASS_SHIFT)) : -1), best_u, best_v);
-        cur = CUR_DONE;
+    for (;;) {                                      // node phase
+      const uint64_t mn = __ballot(cur >= 0);
+      if (!mn) break;
+      if (__popcll(mn) < NODE_MIN && __ballot(cur == CUR_LEAF)) break;   // few walkers, triangles waiting
+      nv += (unsigned long long)__popcll(mn);
+      if (cur >= 0) {
+        uint32_t nb, masks;
+        const uint32_t node_addr = L.top_addr + 16u * (uint32_t)cur;
+        const uint32_t hits = node_visit(sc, node_addr, cur, r, oct, ray.tmin(), ray.tfar(), nb, masks);
+        const uint32_t imask = masks & 255u, lhits = hits & (masks >> 8);
+        enter_group(gbase, gmask, st, nb, hits & imask, imask);
+        tbase = nb + 4u * (uint32_t)__builtin_popcount(imask);
+        tmask = lhits | (masks & 0x00ffff00u);
+        cur = lhits ? CUR_LEAF : advance<ORDERED>(gbase, gmask, st, order_tab, oct);
       }
     }
-  }
-  {   // counters: summed over the block first, then one atomic per counter, each counter on its own line (ptc_internal.h, ST_STRIDE)
-    __shared__ unsigned long long s_stat[TRACE_WAVES][4];
-    const unsigned long long c_tris = wave_sum(nt);
-    if (lane == 0) { s_stat[wave][0] = nv; s_stat[wave][1] = c_tris; s_stat[wave][2] = nr; s_stat[wave][3] = nh; }
-    __syncthreads();
-    if (threadIdx.x < 4u) {
-      unsigned long long v = 0;
-      for (int w = 0; w < TRACE_WAVES; ++w) v += s_stat[w][threadIdx.x];
-      const int at = threadIdx.x == 0u ? ST_NODES_C : threadIdx.x == 1u ? ST_TRIS_C : threadIdx.x == 2u ? ST_SEGMENTS : ST_HITS;
-      if (v) atomicAdd(&q.stats[at * ST_STRIDE], v);
+    // ---- leaf phase: the pairing is LeafPair's, the tests and what becomes of their results RAY's ----
+    if (const uint64_t m_leaf = __ballot(cur == CUR_LEAF)) {
+      LeafPair lp;
+      lp.open(m_leaf, cur, tbase, tmask, wave, lane);
+      if (ray.leaf_pass(lp, sc, L.top_addr, r, lane, tmask, nt)) cur = CUR_FINISHED;
+      if (cur == CUR_LEAF && (tmask & 255u) == 0u) cur = advance<ORDERED>(gbase, gmask, st, order_tab, oct);
+    }
+    nh += (unsigned long long)__popcll(__ballot(cur == CUR_FINISHED && ray.hit()));
+    if (cur == CUR_FINISHED) {                      // this lane's ray is finished
+      ray.publish(q, ri, debug_out);
+      cur = CUR_DONE;
     }
   }
+  RAY::flush(q.stats, nv, wave_sum(nt), nr, nh);
 }
 
 // =================================================================================================
-// P4 any-hit traversal for the NEE shadow rays: same nodes and machinery, the interval is fixed, hit slots are taken in
+// P3 closest-hit traversal + triangle intersection (trace_queue, ORDERED).
+// Per node: the 8 slots are tested against [tmin, best_t]; the triangles of the hit leaf slots are intersected (slot
+// order) before the ray descends into the hit interior children, nearest octant first.
+// Closest hit = lexicographic minimum of (t, original primitive id).
+// The hit record (t, prim | class<<28, u, v) is written IN PLACE at the ray's slot (miss: prim = -1).
+// CULL: R6 back-face culling + per-ray [tmin,tmax] from B.zw (raster-compat primary rays).
+template <bool CULL>
+struct ClosestRay {
+  float t0 = 0.0f, best_t = PT_T_INF, best_u = 0.0f, best_v = 0.0f;
+  int best_prim = 0x7fffffff, best_cls = 0;
+  bool found = false;
+  PT_DEV void start(const float4& B) {
+    t0 = CULL ? B.z : 0.0f;
+    best_t = CULL ? B.w : PT_T_INF; best_u = 0.0f; best_v = 0.0f; best_prim = 0x7fffffff; best_cls = 0; found = false;
+  }
+  PT_DEV float tmin() const { return t0; }
+  PT_DEV float tfar() const { return best_t; }
+  PT_DEV void take(bool hit, float t, float u, float v, int pid, int cls) {
+    if (hit && t > t0 && (t < best_t || (t == best_t && pid < best_prim))) {
+      best_t = t; best_u = u; best_v = v; best_prim = pid; best_cls = cls; found = true;
+    }
+  }
+  // Same tests, same results and counters as one triangle per pass — closest hit is an order-independent minimum, so an owner's second
+  // triangle is consumed whatever its first gives — in fewer passes.
+  PT_DEV bool leaf_pass(const LeafPair& lp, const DevScene& sc, uint32_t top_addr, const ray_t& r, uint32_t lane, uint32_t& tmask, uint32_t& nt) {
+    tmask = lp.tmask_after;
+    ray_t rr;
+    const uint32_t k = lp.fetch(r, lp.src(lane), rr);
+    bool hit = false; float t = 0.0f, u = 0.0f, v = 0.0f; int pid = 0, cls = 0;
+    if (lp.tests()) {
+      float4 a, b, c;
+      load_triangle(sc, top_addr, k, a, b, c);
+      hit = tri_test<CULL>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v);
+      pid = __float_as_int(a.w); cls = __float_as_int(b.w);
+    }
+    if (lp.leaf) { ++nt; take(hit, t, u, v, pid, cls); }
+    const int hsrc = lp.hsrc(lane);
+    const int h2 = __shfl(hit ? 1 : 0, hsrc);
+    const float t2 = __shfl(t, hsrc), u2 = __shfl(u, hsrc), v2 = __shfl(v, hsrc);
+    const int pid2 = __shfl(pid, hsrc), cls2 = __shfl(cls, hsrc);
+    if (lp.paired) { ++nt; take(h2 != 0, t2, u2, v2, pid2, cls2); }
+    return false;
+  }
+  PT_DEV bool hit() const { return found; }
+  PT_DEV void publish(const DevQueues& q, uint32_t ri, uint8_t*) const {       // in place
+    q.hit[ri] = make_float4(found ? best_t : -1.0f, __int_as_float(found ? (best_prim | (best_cls << HIT_CLASS_SHIFT)) : -1), best_u, best_v);
+  }
+  static PT_DEV void flush(unsigned long long* stats, unsigned long long nv, unsigned long long nt, unsigned long long nr, unsigned long long nh) {
+    flush_trace_stats<ST_NODES_C, ST_TRIS_C, ST_SEGMENTS, ST_HITS>(stats, {nv, nt, nr, nh});
+  }
+};
+template <bool CULL>
+__global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_closest(DevScene sc, DevQueues q, int qi, int stack_lds) {
+  const RayQ rq = q.ray[qi];
+  trace_queue<ClosestRay<CULL>, true, TRACE_NODE_MIN>(sc, q, stack_lds, &q.cnt[CNT_RAY_TOTAL], q.pre_ray, q.seg_ray[qi], &q.cnt[CNT_WORK_TRACE], rq.A, rq.B, nullptr);
+}
+
+// =================================================================================================
+// P4 any-hit traversal for the NEE shadow rays (trace_queue, not ORDERED): same nodes and machinery, the interval is fixed, hit slots are taken in
 // ascending slot order (occlusion needs no front-to-back order) and the first triangle hit inside (0, tmax) ends the ray.
 // An unoccluded ray adds its contribution to the path's radiance word (single owner: one shadow ray per path per bounce).
 template <bool DEBUG_OUT>
-__global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_any(DevScene sc, DevQueues q, int stack_lds, uint8_t* debug_out) {
-  extern __shared__ float4 lds_raw[];
-  __shared__ uint8_t s_pair[2][TRACE_WAVES][64];   // leaf phase: k-th owner with a second triangle <-> k-th free lane
-  const uint32_t lane = lane_id();
-  const uint32_t wave = threadIdx.x >> 6;
-  if (Reservoir::block_has_no_work(&q.cnt[CNT_SH_TOTAL])) return;
-  const TraceLds L = trace_lds(lds_raw, sc, stack_lds, false);
-  for (uint32_t i = threadIdx.x; i < sc.n_lds_units; i += TRACE_BLOCK) lds_raw[i] = sc.recs[i];
-  __syncthreads();
-  unsigned long long nv = 0, nr = 0;
-  uint32_t nt = 0;
-  Reservoir res; res.init(&q.cnt[CNT_SH_TOTAL], (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave)));
-  WStack st;
-  st.init(L.stack + (size_t)wave * (size_t)stack_lds * 64u + lane,
-          sc.stack_ovf + ((size_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * TRACE_WAVES + wave)) * sc.ovf_depth) * 64u, stack_lds);
-  int cur = CUR_DONE;
-  uint32_t ri = 0, path = 0, oct = 0, gbase = 0, gmask = 0, tbase = 0, tmask = 0;
-  ray_t r = make_ray(V3(0, 0, 0), V3(0, 0, 1));
-  float tmax = 0.0f;
+struct AnyRay {
+  float tmax = 0.0f; uint32_t path = 0;
   bool occluded = false;
-  RayRing ring; ring.init(L.ring + (size_t)wave * RING_FIELDS * TRACE_RING);
-  for (;;) {
-    {
-      bool idle = cur == CUR_DONE;
-      uint64_t mi = __ballot(idle);
-      if ((uint32_t)__popcll(mi) >= TRACE_REFILL_IDLE || !__ballot(cur != CUR_DONE)) {
-        while (mi) {
-          if (ring.n == 0u) {
-            if (res.exhausted) break;
-            ring.stage(res, q, q.pre_sh, q.seg_sh, &q.cnt[CNT_WORK_SHADOW], q.shadow.A, q.shadow.B, lane);
-            if (ring.n == 0u) break;
-          }
-          v3 inv = V3(0, 0, 0); uint32_t oc = 0;
-          const bool got = ring.pop(idle, ri, inv, oc);
-          nr += (unsigned long long)__popcll(__ballot(got));
-          if (got) {
-            const float4 A = q.shadow.A[ri], Bq = q.shadow.B[ri];
-            r.o = V3(A.x, A.y, A.z); r.d = V3(A.w, Bq.x, Bq.y); r.inv = inv;
-            oct = oc;
-            tmax = Bq.z; path = __float_as_uint(Bq.w);
-            occluded = false;
-            st.reset();
-            gmask = 0; tmask = 0;
-            cur = 0;
-          }
-          idle = cur == CUR_DONE; mi = __ballot(idle);
-        }
+  PT_DEV void start(const float4& B) {
+    tmax = B.z; path = __float_as_uint(B.w);
+    occluded = false;
+  }
+  PT_DEV float tmin() const { return 0.0f; }
+  PT_DEV float tfar() const { return tmax; }
+  // As in ClosestRay, a lane's second pending triangle is tested in the same pass by a free lane.  The counter stays the sequential
+  // one: the second test is counted (and used, and its triangle consumed) only when the first one missed.
+  PT_DEV bool leaf_pass(const LeafPair& lp, const DevScene& sc, uint32_t top_addr, const ray_t& r, uint32_t lane, uint32_t& tmask, uint32_t& nt) {
+    const int src = lp.src(lane);
+    ray_t rr;
+    const uint32_t k = lp.fetch(r, src, rr);
+    const float tmax_src = __shfl(tmax, src);
+    bool hit = false;
+    if (lp.tests()) {
+      float4 a, b, c;
+      load_triangle(sc, top_addr, k, a, b, c);
+      float t, u, v;
+      hit = tri_test<false>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v) && t > 0.0f && t < tmax_src;
+    }
+    const int h2 = __shfl(hit ? 1 : 0, lp.hsrc(lane));
+    if (lp.leaf) {
+      ++nt;
+      if (hit) occluded = true;
+      else if (lp.paired) {
+        ++nt; tmask = lp.tmask_after;
+        if (h2) occluded = true;
       }
     }
-    if (!__ballot(cur != CUR_DONE)) break;
-    {
-      for (;;) {
-        const uint64_t mn = __ballot(cur >= 0);
-        if (!mn) break;
-        if (__popcll(mn) < TRACE_NODE_MIN_ANY && __ballot(cur == CUR_LEAF)) break;
-        nv += (unsigned long long)__popcll(mn);
-        if (cur >= 0) {
-          uint32_t nb, masks;
-          const uint32_t node_addr = L.top_addr + 16u * (uint32_t)cur;
-          const uint32_t hits = node_visit(sc, node_addr, cur, r, oct, 0.0f, tmax, nb, masks);
-          const uint32_t imask = masks & 255u, lhits = hits & (masks >> 8);
-          enter_group(gbase, gmask, st, nb, hits & imask, imask);
-          tbase = nb + 4u * (uint32_t)__builtin_popcount(imask);
-          tmask = lhits | (masks & 0x00ffff00u);
-          cur = lhits ? CUR_LEAF : advance<false>(gbase, gmask, st, nullptr, 0u);
-        }
-      }
-      {
-        // ---- leaf phase: as in k_trace_closest, a lane's second pending triangle is tested in the same pass by a free lane.  The
-        // counter stays the sequential one: the second test is counted (and used) only when the first one missed.
-        const bool leaf = cur == CUR_LEAF;
-        const uint64_t m_leaf = __ballot(leaf);
-        if (m_leaf) {
-          uint32_t k1 = 0, k2 = 0;
-          bool more = false;
-          if (leaf) { k1 = next_triangle(tbase, tmask); more = (tmask & 255u) != 0u; }
-          const uint64_t m_more = __ballot(more), m_free = ~m_leaf;
-          const uint32_t n_more = (uint32_t)__popcll(m_more), n_free = (uint32_t)__popcll(m_free);
-          const uint32_t rank_more = mbcnt64(m_more), rank_free = mbcnt64(m_free);
-          const bool paired = more && rank_more < n_free, helper = !leaf && rank_free < n_more;
-          typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-          lds_u8* tab_owner = (lds_u8*)s_pair[0][wave];
-          lds_u8* tab_helper = (lds_u8*)s_pair[1][wave];
-          uint32_t tmask_after = tmask;
-          if (paired) { k2 = next_triangle(tbase, tmask_after); tab_owner[rank_more] = (uint8_t)lane; }
-          if (helper) tab_helper[rank_free] = (uint8_t)lane;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const int src = helper ? (int)tab_owner[rank_free] : (int)lane;
-          ray_t rr;
-          rr.o = V3(__shfl(r.o.x, src), __shfl(r.o.y, src), __shfl(r.o.z, src));
-          rr.d = V3(__shfl(r.d.x, src), __shfl(r.d.y, src), __shfl(r.d.z, src));
-          const float tmax_src = __shfl(tmax, src);
-          const uint32_t k2_src = (uint32_t)__shfl((int)k2, src);
-          const uint32_t k = helper ? k2_src : k1;
-          bool hit = false;
-          if (leaf || helper) {
-            float4 a, b, c;
-            load_triangle(sc, L.top_addr, k, a, b, c);
-            float t, u, v;
-            hit = tri_test<false>(rr, V3(a.x, a.y, a.z), V3(b.x, b.y, b.z), V3(c.x, c.y, c.z), t, u, v) && t > 0.0f && t < tmax_src;
-          }
-          const int hsrc = paired ? (int)tab_helper[rank_more] : (int)lane;
-          const int h2 = __shfl(hit ? 1 : 0, hsrc);
-          if (leaf) {
-            ++nt;
-            if (hit) { occluded = true; cur = CUR_FINISHED; }
-            else if (paired) {
-              ++nt; tmask = tmask_after;
-              if (h2) { occluded = true; cur = CUR_FINISHED; }
-            }
-            if (cur == CUR_LEAF && (tmask & 255u) == 0u) cur = advance<false>(gbase, gmask, st, nullptr, 0u);
-          }
-        }
-      }
-      if (cur == CUR_FINISHED) {
-        if (DEBUG_OUT) debug_out[ri] = occluded ? 1 : 0;
-        else if (!occluded) {
-          const float4 Cq = q.shadow.C[ri];
-          float4 L = q.lpath[path];
-          L.x = L.x + Cq.x; L.y = L.y + Cq.y; L.z = L.z + Cq.z;
-          q.lpath[path] = L;
-        }
-        cur = CUR_DONE;
-      }
+    return lp.leaf && occluded;
+  }
+  PT_DEV bool hit() const { return false; }       // shadow rays are not counted as hits
+  PT_DEV void publish(const DevQueues& q, uint32_t ri, uint8_t* debug_out) const {
+    if (DEBUG_OUT) debug_out[ri] = occluded ? 1 : 0;
+    else if (!occluded) {
+      const float4 Cq = q.shadow.C[ri];
+      float4 L = q.lpath[path];
+      L.x = L.x + Cq.x; L.y = L.y + Cq.y; L.z = L.z + Cq.z;
+      q.lpath[path] = L;
     }
   }
-  {
-    __shared__ unsigned long long s_stat[TRACE_WAVES][3];
-    const unsigned long long c_tris = wave_sum(nt);
-    if (lane == 0) { s_stat[wave][0] = nv; s_stat[wave][1] = c_tris; s_stat[wave][2] = nr; }
-    __syncthreads();
-    if (threadIdx.x < 3u) {
-      unsigned long long v = 0;
-      for (int w = 0; w < TRACE_WAVES; ++w) v += s_stat[w][threadIdx.x];
-      const int at = threadIdx.x == 0u ? ST_NODES_A : threadIdx.x == 1u ? ST_TRIS_A : ST_SHADOW;
-      if (v) atomicAdd(&q.stats[at * ST_STRIDE], v);
-    }
+  static PT_DEV void flush(unsigned long long* stats, unsigned long long nv, unsigned long long nt, unsigned long long nr, unsigned long long) {
+    flush_trace_stats<ST_NODES_A, ST_TRIS_A, ST_SHADOW>(stats, {nv, nt, nr});
   }
+};
+template <bool DEBUG_OUT>
+__global__ __launch_bounds__(TRACE_BLOCK, TRACE_MIN_WAVES) void k_trace_any(DevScene sc, DevQueues q, int stack_lds, uint8_t* debug_out) {
+  trace_queue<AnyRay<DEBUG_OUT>, false, TRACE_NODE_MIN_ANY>(sc, q, stack_lds, &q.cnt[CNT_SH_TOTAL], q.pre_sh, q.seg_sh, &q.cnt[CNT_WORK_SHADOW], q.shadow.A, q.shadow.B, debug_out);
 }
 
 // =================================================================================================
@@ -1371,10 +1342,10 @@ size_t pt_trace_lds_bytes(const LaunchCfg& cfg, const DevScene& sc) { return tra
 // Resident blocks per CU of the trace kernels with `lds` bytes of dynamic LDS (registers, static LDS and the launch bounds
 // included: the runtime's own occupancy calculation), minimum over the closest-hit and any-hit kernels; <= 0 on error.
 // Dynamic LDS above the default 64 KiB limit is enabled on every variant first.
+static const void* const TRACE_KERNELS[] = {(const void*)k_trace_closest<false>, (const void*)k_trace_closest<true>, (const void*)k_trace_any<false>, (const void*)k_trace_any<true>};
 int pt_trace_blocks_per_cu(size_t lds) {
-  const void* fns[] = {(const void*)k_trace_closest<false>, (const void*)k_trace_closest<true>, (const void*)k_trace_any<false>, (const void*)k_trace_any<true>};
   int best = 1 << 30;
-  for (const void* f : fns) {
+  for (const void* f : TRACE_KERNELS) {
     if (lds > 64u * 1024u && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, TRACE_BLOCK, lds) != hipSuccess) return -1;
@@ -1383,7 +1354,8 @@ int pt_trace_blocks_per_cu(size_t lds) {
   return best;
 }
 
-static uint32_t trace_waves(const LaunchCfg& cfg) { return (uint32_t)(cfg.n_cu * cfg.trace_blocks_per_cu) * TRACE_WAVES; }
+static unsigned trace_grid(const LaunchCfg& cfg) { return (unsigned)(cfg.n_cu * cfg.trace_blocks_per_cu); }      // blocks of the persistent grid
+static uint32_t trace_waves(const LaunchCfg& cfg) { return trace_grid(cfg) * TRACE_WAVES; }
 void pt_launch_set_counts(hipStream_t s, const LaunchCfg& cfg, const DevQueues& q, uint32_t n_rays, uint32_t n_shadow) {
   hipLaunchKernelGGL(k_set_counts, dim3(1), dim3(SCAN_BLOCK), 0, s, q, n_rays, n_shadow, trace_waves(cfg));
 }
@@ -1400,14 +1372,14 @@ void pt_launch_raygen(hipStream_t s, const DevCamera& cam, const DevFrame& fr, c
 }
 
 void pt_launch_trace_closest(hipStream_t s, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, bool cull) {
-  const dim3 grid((unsigned)(cfg.n_cu * cfg.trace_blocks_per_cu));
+  const dim3 grid(trace_grid(cfg));
   const size_t lds = trace_lds_bytes(cfg, sc, true);
   if (cull) hipLaunchKernelGGL(k_trace_closest<true>, grid, dim3(TRACE_BLOCK), lds, s, sc, q, qi, cfg.stack_lds);
   else hipLaunchKernelGGL(k_trace_closest<false>, grid, dim3(TRACE_BLOCK), lds, s, sc, q, qi, cfg.stack_lds);
 }
 
 void pt_launch_trace_any(hipStream_t s, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, uint8_t* debug_out) {
-  const dim3 grid((unsigned)(cfg.n_cu * cfg.trace_blocks_per_cu));
+  const dim3 grid(trace_grid(cfg));
   const size_t lds = trace_lds_bytes(cfg, sc, false);
   if (debug_out) hipLaunchKernelGGL(k_trace_any<true>, grid, dim3(TRACE_BLOCK), lds, s, sc, q, cfg.stack_lds, debug_out);
   else hipLaunchKernelGGL(k_trace_any<false>, grid, dim3(TRACE_BLOCK), lds, s, sc, q, cfg.stack_lds, debug_out);

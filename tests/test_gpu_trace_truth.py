@@ -3,7 +3,8 @@ of tests/trace_reference.py — for every path that puts a tree into HBM: the ho
 builder, the refit and the rebuild on the device after instance updates (rotation, non-uniform scale, a sheared matrix), and a pose followed by a
 refit or a rebuild on the deforming scene.  Per path: 0 lost, 0 ghost, any-hit never wrong, the caps held, every solid hit within 16 x E32 of float64;
 and on the same rays — aimed at interiors, edges and vertices, starting inside boxes and on box planes, with zero, negative-zero and tiny direction
-components, which tests/test_gpu_parity.py::test_hit_records never sends — the oracle's bits.  Launches are ragged: 1, 63, 65 and 2048 + 37 rays.
+components, which tests/test_gpu_parity.py::test_hit_records never sends — the oracle's bits.  Launches are ragged: 1, 63, 65 and 2048 + 37 rays; the Cornell box
+adds the edges of a wave's ray ring and of a chunk, and one launch long enough for chunks of 512 handed out through the work counter.
 Small scenes (at most 5,904 triangles): a test is a few launches and a numpy reference of a second or less."""
 import dataclasses
 import functools
@@ -24,6 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_RAYS = 2048 + 37
 RAGGED = (1, 63, 65)
+RAGGED_RING = (64, 128, 129, 511, 512, 513)      # one scene more: the ring of prepared rays (64), twice it, and the edges of a TRACE_CHUNK
 SCENES = ("cornell", "sphere", "atrium")
 
 
@@ -81,7 +83,7 @@ def _answers(ctx, rays, n=None):
     return t, prim, uv, ctx.trace_any(o, d, tm)
 
 
-def _hold(tag, pt, c, oracle):
+def _hold(tag, pt, c, oracle, ragged=RAGGED):
     """The device's answers for the case's rays: the truth, the oracle's bits (when there is an oracle with that tree), and ragged launches."""
     ans = _answers(pt, c["rays"])
     tr.assert_true(tag, c["verts"], c["idx"], c["rays"], c["truth"], c["e32"], *ans)
@@ -90,7 +92,7 @@ def _hold(tag, pt, c, oracle):
     if oracle is not None:
         for name, got, want in zip(("t", "prim", "uv", "occluded"), ans, _answers(oracle, c["rays"])):
             assert _bits(got, want) if got.dtype == np.float32 else np.array_equal(got, want), "%s: %s differs from the oracle's" % (tag, name)
-    for n in RAGGED:
+    for n in ragged:
         for name, got, want in zip(("t", "prim", "uv", "occluded"), _answers(pt, c["rays"], n), ans):
             assert _bits(got, want[:n]) if got.dtype == np.float32 else np.array_equal(got, want[:n]), "%s: %s of a launch of %d rays" % (tag, name, n)
 
@@ -118,7 +120,7 @@ def test_commit_paths(gpu, ora, scene, path):
     builder = path.split("-")[1]
     c = _case(scene, "commit")
     pt = _commit(gpu, _desc(gpu, scene, builder), path)
-    _hold("%s %s" % (scene, path), pt, c, c["own"][builder])
+    _hold("%s %s" % (scene, path), pt, c, c["own"][builder], RAGGED + RAGGED_RING if scene == "cornell" else RAGGED)
     pt.close()
 
 
@@ -203,6 +205,38 @@ def test_two_stack_entries_in_lds(gpu, ora, tmp_path):
     tr.assert_true("atrium lbvh refit, 2 stack entries in LDS", c["verts"], c["idx"], c["rays"], c["truth"], c["e32"], *ans)
     for name, a, b in zip(("t", "prim", "uv", "occluded"), ans, _answers(c["own"]["lbvh"], c["rays"])):
         assert _bits(a, b) if a.dtype == np.float32 else np.array_equal(a, b), name
+
+
+# ---- a long queue: chunks of TRACE_CHUNK rays, the later ones handed out through the work counter -------------------------------------------
+def test_long_queue_hands_chunks_out_through_the_work_counter(gpu, tmp_path):
+    """Every launch above is a short queue (fewer than 512 rays per wave of the grid): chunks of 64 dealt round-robin, no atomic.  Here the Cornell box is committed
+    with PTC_TRACE_BLOCKS_PER_CU=1 (read at the commit; a process of its own), a grid of W = 4 waves per CU, and the case's rays are tiled to 2 * 512 * W + 37:
+    at least 2 W + 1 chunks of 512 for W waves, so every wave's first chunk is its static one and the rest go through the work counter.  Every answer of both kernels
+    is, bit for bit, the one this process's default-policy context gives for the same ray (test_commit_paths holds those to the truth)."""
+    c = _case("cornell", "commit")
+    pt = gpu.PathTracer(0).load_scene(_desc(gpu, "cornell", "sah"))
+    base = _answers(pt, c["rays"])
+    pt.close()
+    rays_file, out = str(tmp_path / "rays.npz"), str(tmp_path / "child.npz")
+    np.savez(rays_file, org=c["rays"][0], dirs=c["rays"][1], tmax=c["rays"][2])
+    code = ("import sys, numpy as np, torch; sys.path[:0] = [%r, %r, %r]\n"
+            "import pbr_amd\nfrom test_gpu_trace_truth import _desc\n"
+            "pt = pbr_amd.PathTracer(0).load_scene(_desc(pbr_amd, 'cornell', 'sah'))\n"
+            "waves = 4 * torch.cuda.get_device_properties(0).multi_processor_count\n"
+            "r = np.load(%r)\nsel = np.arange(2 * 512 * waves + 37) %% len(r['org'])\n"
+            "o, d, tm = (np.ascontiguousarray(r[k][sel]) for k in ('org', 'dirs', 'tmax'))\n"
+            "t, prim, uv = pt.trace_closest(o, d)\nocc = pt.trace_any(o, d, tm)\n"
+            "np.savez(%r, t=t, prim=prim, uv=uv, occ=occ, sel=sel, waves=waves, policy=pt.launch_policy())\n"
+            % (ROOT, os.path.join(ROOT, "physically-based-renderer_amd"), os.path.join(ROOT, "tests"), rays_file, out))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PTC_TRACE_BLOCKS_PER_CU="1"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = np.load(out)
+    assert " trace_blocks_per_cu=1 " in str(got["policy"]) and " chunk=512u " in str(got["policy"]), str(got["policy"])
+    sel, waves = got["sel"], int(got["waves"])
+    assert len(sel) == 2 * 512 * waves + 37 and -(-len(sel) // 512) > waves >= 4         # more chunks of 512 than waves: the hand-out through the counter runs
+    for name, a, b in zip(("t", "prim", "uv", "occluded"), (got["t"], got["prim"], got["uv"], got["occ"]), base):
+        assert len(a) == len(sel)
+        assert _bits(a, b[sel]) if a.dtype == np.float32 else np.array_equal(a, b[sel]), name
 
 
 # ---- the guide buffers: a full frame's camera rays -------------------------------------------------------------------------------------------
