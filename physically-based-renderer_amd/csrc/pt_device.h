@@ -1,4 +1,4 @@
-// pt_device.h — device-side arithmetic of the path-tracing core (gfx950).
+// pt_device.h — the arithmetic of the path-tracing core (gfx950), written once for host and device.
 //
 // Arithmetic contract (DESIGN.md §"Arithmetic contract"): IEEE binary32, correctly rounded
 // + - * / sqrt (-fhip-fp32-correctly-rounded-divide-sqrt), NO implicit contraction
@@ -6,11 +6,19 @@
 // No libm / ocml transcendental on the render path: sin/cos/pow are the polynomials below.
 // These rules make every value reproducible on any IEEE machine, which is what lets the parity
 // tests demand (near) bit-equality instead of a statistical comparison.
+//
+// Two parts.  PT_HD (host + device): v3 and its operators, the scalar helpers, the RNG hash, the polynomials and the ACES
+// fit — plain IEEE expressions that need no GPU.  The feature headers (pt_lens.h, pt_probes.h, pt_lights.h, pt_display.h)
+// define their values through these, and the library's host evaluations (ptc_debug_*, ptc_frame_begin's seed hash) call the
+// same functions the kernels call: a value has ONE expression in the product, and the host computes the bytes the device
+// writes because it runs the same text under the same contract.  PT_DEV (device only): the BSDF, the ray / box / triangle
+// code and the wave helpers, which only kernels use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define PT_DEV __device__ __forceinline__
+#define PT_HD __host__ __device__ __forceinline__
 
 #define PT_LEAF_MAX 2
 #define PT_RR_START 3u
@@ -25,40 +33,42 @@
 
 struct v3 { float x, y, z; };
 
-PT_DEV v3 V3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-PT_DEV v3 operator+(v3 a, v3 b) { return V3(a.x + b.x, a.y + b.y, a.z + b.z); }
-PT_DEV v3 operator-(v3 a, v3 b) { return V3(a.x - b.x, a.y - b.y, a.z - b.z); }
-PT_DEV v3 operator-(v3 a) { return V3(-a.x, -a.y, -a.z); }
-PT_DEV v3 operator*(v3 a, float s) { return V3(a.x * s, a.y * s, a.z * s); }
-PT_DEV float pt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-PT_DEV float dot3(v3 a, v3 b) { return pt_fma(a.z, b.z, pt_fma(a.y, b.y, a.x * b.x)); }
-PT_DEV v3 cross3(v3 a, v3 b) {
+PT_HD v3 V3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
+PT_HD v3 V3(const float a[3]) { return V3(a[0], a[1], a[2]); }
+PT_HD v3 operator+(v3 a, v3 b) { return V3(a.x + b.x, a.y + b.y, a.z + b.z); }
+PT_HD v3 operator-(v3 a, v3 b) { return V3(a.x - b.x, a.y - b.y, a.z - b.z); }
+PT_HD v3 operator-(v3 a) { return V3(-a.x, -a.y, -a.z); }
+PT_HD v3 operator*(v3 a, float s) { return V3(a.x * s, a.y * s, a.z * s); }
+PT_HD float pt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+PT_HD float dot3(v3 a, v3 b) { return pt_fma(a.z, b.z, pt_fma(a.y, b.y, a.x * b.x)); }
+PT_HD v3 cross3(v3 a, v3 b) {
   return V3(pt_fma(a.y, b.z, -(a.z * b.y)), pt_fma(a.z, b.x, -(a.x * b.z)), pt_fma(a.x, b.y, -(a.y * b.x)));
 }
-PT_DEV float pt_sqrt(float x) { return __builtin_sqrtf(x); }
-PT_DEV v3 normalize3(v3 a) { float inv = 1.0f / pt_sqrt(dot3(a, a)); return a * inv; }
-PT_DEV v3 vfma(v3 a, float s, v3 b) { return V3(pt_fma(a.x, s, b.x), pt_fma(a.y, s, b.y), pt_fma(a.z, s, b.z)); }
-PT_DEV float fmin2(float a, float b) { return a < b ? a : b; }
-PT_DEV float fmax2(float a, float b) { return a > b ? a : b; }
-PT_DEV float max3c(v3 a) { return fmax2(fmax2(a.x, a.y), a.z); }
-PT_DEV float luminance(v3 c) { return pt_fma(c.z, 0.0722f, pt_fma(c.y, 0.7152f, c.x * 0.2126f)); }
+PT_HD float pt_sqrt(float x) { return __builtin_sqrtf(x); }
+PT_HD v3 normalize3(v3 a) { float inv = 1.0f / pt_sqrt(dot3(a, a)); return a * inv; }
+PT_HD v3 vfma(v3 a, float s, v3 b) { return V3(pt_fma(a.x, s, b.x), pt_fma(a.y, s, b.y), pt_fma(a.z, s, b.z)); }
+PT_HD float fmin2(float a, float b) { return a < b ? a : b; }
+PT_HD float fmax2(float a, float b) { return a > b ? a : b; }
+PT_HD float max3c(v3 a) { return fmax2(fmax2(a.x, a.y), a.z); }
+PT_HD float luminance(v3 c) { return pt_fma(c.z, 0.0722f, pt_fma(c.y, 0.7152f, c.x * 0.2126f)); }
 
 // ---- RNG: counter-based hash keyed (seed, pixel, sample) then (bounce, dim) -------------------
-PT_DEV uint32_t pcg(uint32_t v) {
+PT_HD uint32_t pcg(uint32_t v) {
   uint32_t s = v * 747796405u + 2891336453u;
   uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
   return (w >> 22) ^ w;
 }
-PT_DEV uint32_t path_key(uint32_t seed_hash, uint32_t pixel, uint32_t sample) {
-  return pcg(pixel + pcg(sample + seed_hash));   // seed_hash = pcg(seed_lo + pcg(seed_hi)), host-side
+PT_HD uint32_t path_key(uint32_t seed_hash, uint32_t pixel, uint32_t sample) {
+  return pcg(pixel + pcg(sample + seed_hash));
 }
-PT_DEV float rng_f(uint32_t key, uint32_t bounce, uint32_t dim) {
+PT_HD uint32_t seed_hash(uint64_t seed) { return pcg((uint32_t)seed + pcg((uint32_t)(seed >> 32))); }   // what DevFrame.seed_hash holds
+PT_HD float rng_f(uint32_t key, uint32_t bounce, uint32_t dim) {
   uint32_t x = pcg(pcg(bounce * 8u + dim) ^ key);
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
 
 // ---- sin(2πu), cos(2πu), u ∈ [0,1): quadrant + octant reduction, Taylor on [0, π/4] ------------
-PT_DEV void sincos2pi(float u, float& so, float& co) {
+PT_HD void sincos2pi(float u, float& so, float& co) {
   float x4 = u * 4.0f;
   int q = (int)x4;
   if (q > 3) q = 3;
@@ -80,31 +90,31 @@ PT_DEV void sincos2pi(float u, float& so, float& co) {
 }
 
 // ---- x^y for x > 0 (else 0): exp2(y·log2 x) by polynomial --------------------------------------
-PT_DEV float pt_log2(float x) {
-  uint32_t u = __float_as_uint(x);
+PT_HD float pt_log2(float x) {
+  uint32_t u = __builtin_bit_cast(uint32_t, x);
   int e = (int)((u >> 23) & 0xffu) - 127;
-  float m = __uint_as_float((u & 0x007fffffu) | 0x3f800000u);
+  float m = __builtin_bit_cast(float, (u & 0x007fffffu) | 0x3f800000u);
   if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
   float z = (m - 1.0f) / (m + 1.0f);
   float z2 = z * z;
   float p = pt_fma(z2, pt_fma(z2, pt_fma(z2, pt_fma(z2, 0.3205989f, 0.4121984f), 0.5770780f), 0.9617967f), 2.8853901f);
   return pt_fma(z, p, (float)e);
 }
-PT_DEV float pt_exp2(float x) {
+PT_HD float pt_exp2(float x) {
   if (x < -126.0f) return 0.0f;
   if (x > 127.0f) x = 127.0f;
   float fl = __builtin_floorf(x);
   float f = x - fl;
   float p = pt_fma(f, pt_fma(f, pt_fma(f, pt_fma(f, pt_fma(f, 1.8775767e-3f, 8.9893397e-3f), 5.5826318e-2f), 2.4015361e-1f), 6.9315308e-1f), 9.9999994e-1f);
-  return p * __uint_as_float((uint32_t)((int)fl + 127) << 23);
+  return p * __builtin_bit_cast(float, (uint32_t)((int)fl + 127) << 23);
 }
-PT_DEV float pt_pow(float x, float y) {
+PT_HD float pt_pow(float x, float y) {
   if (!(x > 0.0f)) return 0.0f;
   return pt_exp2(y * pt_log2(x));
 }
 
 // ---- atan2(y, x) in (-pi, pi]: octant reduction + odd minimax polynomial on [0,1] (max error ~1e-5 rad) --------
-PT_DEV float pt_atan2(float y, float x) {
+PT_HD float pt_atan2(float y, float x) {
   const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
   const float mx = fmax2(ax, ay), mn = fmin2(ax, ay);
   if (!(mx > 0.0f)) return 0.0f;
@@ -117,6 +127,21 @@ PT_DEV float pt_atan2(float y, float x) {
   return r;
 }
 
+// ---- R9 tonemap: ACES fit (matrices as GLSL reads them: column-major, i.e. transposed — SURVEY §3.4) ------------
+PT_HD float rrt_odt(float c) {
+  const float num = c * (c + 0.0245786f) - 0.000090537f;
+  const float den = c * (0.983729f * c + 0.4329510f) + 0.238081f;
+  return num / den;
+}
+PT_HD v3 aces_input(v3 c) {
+  return V3(0.59719f * c.x + 0.07600f * c.y + 0.02840f * c.z, 0.35458f * c.x + 0.90834f * c.y + 0.13383f * c.z, 0.04823f * c.x + 0.01566f * c.y + 0.83777f * c.z);
+}
+PT_HD v3 aces_output(v3 f) {
+  return V3(1.60475f * f.x + -0.10208f * f.y + -0.00327f * f.z, -0.53108f * f.x + 1.10813f * f.y + -0.07276f * f.z, -0.07367f * f.x + -0.00605f * f.y + 1.07602f * f.z);
+}
+PT_HD v3 aces_fit(v3 c) { const v3 i = aces_input(c); return aces_output(V3(rrt_odt(i.x), rrt_odt(i.y), rrt_odt(i.z))); }
+
+// ==== device only =================================================================================
 // ---- P6: BSDF in the local frame of the shading normal (z = n) ---------------------------------
 struct bsdf_t { v3 cd, f0; float alpha; int ggx; };
 

@@ -2,8 +2,8 @@
 //
 // The renderer's images are scene-referred radiance in physical units; this file defines how one becomes a displayable RGBA8 (or an exposed RGBA16F for a viewer's
 // own tonemapper).  It is compiled for host and device: the kernels (pt_display.hip) and the host evaluations (ptc_debug_display_pixel, ptc_debug_meter) call the
-// same functions, and tests/display_reference.py restates them in numpy.  IEEE binary32, no contraction (-ffp-contract=off), in the order written; pt_display_fma
-// = one rounding.  pt_device.h is device-only, so pt_pow / pt_log2 / pt_exp2, fmin2 / fmax2, rrt_odt and the ACES matrices are restated here operation for operation.
+// same functions, and tests/display_reference.py restates them in numpy.  IEEE binary32, no contraction (-ffp-contract=off), in the order written; pt_fma
+// = one rounding.  pt_pow, fmin2 / fmax2 and the ACES fit (aces_fit) are pt_device.h's host + device functions, the ones k_tonemap calls.
 //
 // Metering is exact in integers — no logarithm, no floating-point sum — so the device's result does not depend on the order it adds in:
 //   luminance  l = (0.2126 r + 0.7152 g) + 0.0722 b                                   (pt_adaptive's unfused order)
@@ -32,10 +32,8 @@
 // RGBA16F: half(rgb * E), alpha copied, round to nearest even, overflow to inf, half denormals kept (k_to_half's conversion); a NaN becomes 0x7e00.
 #pragma once
 #include "../../include/ptc.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "pt_device.h"
 
-#define PT_DISPLAY_HD __host__ __device__ inline
 #define PT_DISPLAY_BINS 4096u
 #define PT_DISPLAY_MAX_PIXELS (1u << 28)     // counts are uint32; S << 18 stays below 2^64
 
@@ -49,40 +47,13 @@ struct pt_display_state {
 };
 static_assert(sizeof(pt_display_state) == 32, "pt_display_state is 32 bytes");
 
-PT_DISPLAY_HD float pt_display_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-PT_DISPLAY_HD float pt_display_min(float a, float b) { return a < b ? a : b; }      // fmin2
-PT_DISPLAY_HD float pt_display_max(float a, float b) { return a > b ? a : b; }      // fmax2
-PT_DISPLAY_HD uint32_t pt_display_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
-PT_DISPLAY_HD float pt_display_float(uint32_t u) { return __builtin_bit_cast(float, u); }
-PT_DISPLAY_HD float pt_display_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// pt_log2 / pt_exp2 / pt_pow of pt_device.h
-PT_DISPLAY_HD float pt_display_log2(float x) {
-  const uint32_t u = pt_display_bits(x);
-  int e = (int)((u >> 23) & 0xffu) - 127;
-  float m = pt_display_float((u & 0x007fffffu) | 0x3f800000u);
-  if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
-  const float z = (m - 1.0f) / (m + 1.0f);
-  const float z2 = z * z;
-  const float p = pt_display_fma(z2, pt_display_fma(z2, pt_display_fma(z2, pt_display_fma(z2, 0.3205989f, 0.4121984f), 0.5770780f), 0.9617967f), 2.8853901f);
-  return pt_display_fma(z, p, (float)e);
-}
-PT_DISPLAY_HD float pt_display_exp2(float x) {
-  if (x < -126.0f) return 0.0f;
-  if (x > 127.0f) x = 127.0f;
-  const float fl = __builtin_floorf(x);
-  const float f = x - fl;
-  const float p = pt_display_fma(f, pt_display_fma(f, pt_display_fma(f, pt_display_fma(f, pt_display_fma(f, 1.8775767e-3f, 8.9893397e-3f), 5.5826318e-2f), 2.4015361e-1f), 6.9315308e-1f), 9.9999994e-1f);
-  return p * pt_display_float((uint32_t)((int)fl + 127) << 23);
-}
-PT_DISPLAY_HD float pt_display_pow(float x, float y) {
-  if (!(x > 0.0f)) return 0.0f;
-  return pt_display_exp2(y * pt_display_log2(x));
-}
+PT_HD uint32_t pt_display_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+PT_HD float pt_display_float(uint32_t u) { return __builtin_bit_cast(float, u); }
+PT_HD float pt_display_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 // ---- metering -------------------------------------------------------------------------------------------------------------------------------------
 // 0: not counted, 1: metered (key set), 2: rejected
-PT_DISPLAY_HD int pt_meter_classify(float r, float g, float b, float a, uint32_t& key) {
+PT_HD int pt_meter_classify(float r, float g, float b, float a, uint32_t& key) {
   if (!(a > 0.0f)) return 0;
   const float l = pt_display_lum(r, g, b);
   const uint32_t u = pt_display_bits(l);
@@ -90,19 +61,19 @@ PT_DISPLAY_HD int pt_meter_classify(float r, float g, float b, float a, uint32_t
   key = u >> 19;
   return 1;
 }
-PT_DISPLAY_HD void pt_meter_bounds(uint32_t N, float percentile_lo, float percentile_hi, uint64_t& n_lo, uint64_t& n_hi) {
+PT_HD void pt_meter_bounds(uint32_t N, float percentile_lo, float percentile_hi, uint64_t& n_lo, uint64_t& n_hi) {
   const uint32_t lo_q = (uint32_t)(percentile_lo * 65536.0f), hi_q = (uint32_t)(percentile_hi * 65536.0f);
   n_lo = ((uint64_t)N * lo_q) >> 16;
   n_hi = ((uint64_t)N * hi_q) >> 16;
   if (n_hi <= n_lo) { n_lo = 0; n_hi = N; }
 }
 // of a bin with `count` samples whose first has rank `before`: the samples with a rank in [n_lo, n_hi)
-PT_DISPLAY_HD uint64_t pt_meter_kept(uint64_t before, uint64_t count, uint64_t n_lo, uint64_t n_hi) {
+PT_HD uint64_t pt_meter_kept(uint64_t before, uint64_t count, uint64_t n_lo, uint64_t n_hi) {
   const uint64_t a = before > n_lo ? before : n_lo, b = before + count < n_hi ? before + count : n_hi;
   return b > a ? b - a : 0;
 }
-PT_DISPLAY_HD uint32_t pt_meter_mean(uint64_t S, uint64_t M) { return M ? (uint32_t)((S << 18) / M) : 0u; }
-PT_DISPLAY_HD uint32_t pt_meter_adapt(uint32_t A, uint32_t Q, uint64_t M, float adapt_rate) {
+PT_HD uint32_t pt_meter_mean(uint64_t S, uint64_t M) { return M ? (uint32_t)((S << 18) / M) : 0u; }
+PT_HD uint32_t pt_meter_adapt(uint32_t A, uint32_t Q, uint64_t M, float adapt_rate) {
   if (M == 0) return A;
   const uint32_t rate_q = (uint32_t)(adapt_rate * 65536.0f);
   if (A == 0u || rate_q == 65536u) return Q;
@@ -110,32 +81,22 @@ PT_DISPLAY_HD uint32_t pt_meter_adapt(uint32_t A, uint32_t Q, uint64_t M, float 
   const int64_t step = d >= 0 ? d / 65536 : -((-d + 65535) / 65536);     // floor
   return (uint32_t)((int64_t)A + step);
 }
-PT_DISPLAY_HD float pt_display_scale(const ptc_display_params& p, uint32_t A) {
+PT_HD float pt_display_scale(const ptc_display_params& p, uint32_t A) {
   if (!p.auto_exposure || A == 0u) return p.gain;
-  const float La = pt_display_min(pt_display_max(pt_display_float(A), p.min_luminance), p.max_luminance);
+  const float La = fmin2(fmax2(pt_display_float(A), p.min_luminance), p.max_luminance);
   return p.gain * (p.key / La);
 }
 
 // ---- operators ------------------------------------------------------------------------------------------------------------------------------------
-PT_DISPLAY_HD float pt_display_rrt_odt(float c) {     // rrt_odt (pt_kernels.hip)
-  const float num = c * (c + 0.0245786f) - 0.000090537f;
-  const float den = c * (0.983729f * c + 0.4329510f) + 0.238081f;
-  return num / den;
-}
-template <int OP> PT_DISPLAY_HD void pt_display_operator(float& r, float& g, float& b, float white) {
-  if (OP == PTC_TONEMAP_ACES) {     // k_tonemap
-    const float ir = 0.59719f * r + 0.07600f * g + 0.02840f * b;
-    const float ig = 0.35458f * r + 0.90834f * g + 0.13383f * b;
-    const float ib = 0.04823f * r + 0.01566f * g + 0.83777f * b;
-    const float fr = pt_display_rrt_odt(ir), fg = pt_display_rrt_odt(ig), fb = pt_display_rrt_odt(ib);
-    r = 1.60475f * fr + -0.10208f * fg + -0.00327f * fb;
-    g = -0.53108f * fr + 1.10813f * fg + -0.07276f * fb;
-    b = -0.07367f * fr + -0.00605f * fg + 1.07602f * fb;
+template <int OP> PT_HD void pt_display_operator(float& r, float& g, float& b, float white) {
+  if (OP == PTC_TONEMAP_ACES) {     // k_tonemap's
+    const v3 o = aces_fit(V3(r, g, b));
+    r = o.x; g = o.y; b = o.z;
   } else if (OP == PTC_TONEMAP_PBR_NEUTRAL) {     // Khronos PBR Neutral: startCompression 0.8 - 0.04 = 0.76, desaturation 0.15
-    const float x = pt_display_min(r, pt_display_min(g, b));
+    const float x = fmin2(r, fmin2(g, b));
     const float off = x < 0.08f ? x - 6.25f * (x * x) : 0.04f;
     r = r - off; g = g - off; b = b - off;
-    const float peak = pt_display_max(r, pt_display_max(g, b));
+    const float peak = fmax2(r, fmax2(g, b));
     if (peak >= 0.76f) {
       const float np = 1.0f - (0.24f * 0.24f) / ((peak + 0.24f) - 0.76f);
       const float k = np / peak;
@@ -145,30 +106,30 @@ template <int OP> PT_DISPLAY_HD void pt_display_operator(float& r, float& g, flo
       r = r * iq + nq; g = g * iq + nq; b = b * iq + nq;
     }
   } else if (OP == PTC_TONEMAP_REINHARD) {     // extended Reinhard on luminance
-    const float l = pt_display_max(pt_display_lum(r, g, b), 0.0f);
+    const float l = fmax2(pt_display_lum(r, g, b), 0.0f);
     const float s = (1.0f + l / (white * white)) / (1.0f + l);
     r = r * s; g = g * s; b = b * s;
   }
 }
-template <int OETF> PT_DISPLAY_HD float pt_display_oetf(float v) {
-  if (OETF == PTC_OETF_SRGB) return v <= 0.0031308f ? 12.92f * v : 1.055f * pt_display_pow(v, 1.0f / 2.4f) - 0.055f;
-  return pt_display_pow(v, 1.0f / 2.2f);
+template <int OETF> PT_HD float pt_display_oetf(float v) {
+  if (OETF == PTC_OETF_SRGB) return v <= 0.0031308f ? 12.92f * v : 1.055f * pt_pow(v, 1.0f / 2.4f) - 0.055f;
+  return pt_pow(v, 1.0f / 2.2f);
 }
-PT_DISPLAY_HD uint32_t pt_display_unorm8(float v) {
-  v = pt_display_min(pt_display_max(v, 0.0f), 1.0f);
+PT_HD uint32_t pt_display_unorm8(float v) {
+  v = fmin2(fmax2(v, 0.0f), 1.0f);
   return (uint32_t)(int)(v * 255.0f + 0.5f);
 }
-template <int OP, int OETF> PT_DISPLAY_HD uint32_t pt_display_pixel8(float r, float g, float b, float a, float E, float white) {
+template <int OP, int OETF> PT_HD uint32_t pt_display_pixel8(float r, float g, float b, float a, float E, float white) {
   r = r * E; g = g * E; b = b * E;
   pt_display_operator<OP>(r, g, b, white);
-  return pt_display_unorm8(pt_display_oetf<OETF>(pt_display_max(r, 0.0f))) | (pt_display_unorm8(pt_display_oetf<OETF>(pt_display_max(g, 0.0f))) << 8) |
-         (pt_display_unorm8(pt_display_oetf<OETF>(pt_display_max(b, 0.0f))) << 16) | (pt_display_unorm8(a) << 24);
+  return pt_display_unorm8(pt_display_oetf<OETF>(fmax2(r, 0.0f))) | (pt_display_unorm8(pt_display_oetf<OETF>(fmax2(g, 0.0f))) << 8) |
+         (pt_display_unorm8(pt_display_oetf<OETF>(fmax2(b, 0.0f))) << 16) | (pt_display_unorm8(a) << 24);
 }
-PT_DISPLAY_HD uint32_t pt_display_half_bits(float v) {
+PT_HD uint32_t pt_display_half_bits(float v) {
   if (v != v) return 0x7e00u;
   return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)v);
 }
-PT_DISPLAY_HD void pt_display_pixel16(float r, float g, float b, float a, float E, uint32_t& lo, uint32_t& hi) {
+PT_HD void pt_display_pixel16(float r, float g, float b, float a, float E, uint32_t& lo, uint32_t& hi) {
   lo = pt_display_half_bits(r * E) | (pt_display_half_bits(g * E) << 16);
   hi = pt_display_half_bits(b * E) | (pt_display_half_bits(a) << 16);
 }

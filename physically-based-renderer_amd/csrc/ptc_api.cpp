@@ -331,10 +331,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   HIP_TRY(c, hipMemsetAsync(c->radiance.p, 0, (size_t)w * h * sizeof(float4), s0));
   c->rad_w = w; c->rad_h = h;
   c->fr.w = w; c->fr.h = h; c->fr.max_bounces = max_bounces; c->fr.n_owned = (uint32_t)n_owned; c->fr.owned = c->owned.p;
-  {  // seed_hash = pcg(seed_lo + pcg(seed_hi)), same hash as pt_device.h
-    auto pcg = [](uint32_t v) { uint32_t s = v * 747796405u + 2891336453u; uint32_t x = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u; return (x >> 22) ^ x; };
-    c->fr.seed_hash = pcg((uint32_t)seed + pcg((uint32_t)(seed >> 32)));
-  }
+  c->fr.seed_hash = seed_hash(seed);
   c->spp_total = is_raster(integrator) ? 1 : spp_total;
   c->integrator = integrator; c->samples_done = 0; c->sample_base = 0; c->resolve_divisor = 0;
   // samples of one full batch: as many as fit max_batch_paths split over the lanes.  The queues themselves are sized by the

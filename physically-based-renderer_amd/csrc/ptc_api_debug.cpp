@@ -46,7 +46,6 @@ bool probe_debug_args_bad(int n, uint32_t base, uint32_t first_sample, uint32_t 
          (uint64_t)base + (uint64_t)n > 0x100000000ull;
 }
 
-uint32_t frame_seed_hash(uint64_t seed) { return pt_lens_pcg((uint32_t)seed + pt_lens_pcg((uint32_t)(seed >> 32))); }   // as ptc_frame_begin
 }  // namespace
 
 extern "C" {
@@ -113,10 +112,10 @@ int ptc_debug_light_sample(const ptc_light_params* params, const float P[3], flo
   ptc_light_params p = *params;
   pt_light_normalise(p);
   const pt_light_rec L = pt_light_make_rec(p, 1.0f);
-  float wi[3], Li[3], dist;
-  if (!pt_light_sample(L, P, wi, dist, Li)) return 0;
-  for (int k = 0; k < 3; ++k) { out_wi[k] = wi[k]; out_Li[k] = Li[k]; }
-  *out_dist = dist;
+  v3 wi, Li;
+  if (!pt_light_sample(L, V3(P), wi, *out_dist, Li)) return 0;
+  out_wi[0] = wi.x; out_wi[1] = wi.y; out_wi[2] = wi.z;
+  out_Li[0] = Li.x; out_Li[1] = Li.y; out_Li[2] = Li.z;
   return 1;
 }
 
@@ -192,7 +191,7 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     if (pixels[j] >= (uint32_t)w * (uint32_t)h) return fail(c, PTC_E_ARG, "debug_camera_rays: pixel index outside the frame");
   if (c->probes.on) return fail(c, PTC_E_STATE, "debug_camera_rays: a probe frame is in progress (its rays: ptc_debug_probe_rays)");
   const uint32_t n = n_pixels * n_samples;
-  const uint32_t seed_hash = frame_seed_hash(seed);
+  const uint32_t seed_hash = ::seed_hash(seed);
   if (c->device < 0) {      // the host evaluation of pt_lens.h
     if (!c->have_cam) return fail(c, PTC_E_STATE, "debug_camera_rays: no camera (ptc_set_camera)");
     DevCamera cam;
@@ -234,7 +233,7 @@ int ptc_debug_probe_rays(ptc_ctx* c, const float* positions_xyz, int n_probes, u
   if (!c) return PTC_E_ARG;
   if (!positions_xyz || !out_o_d || !out_key || probe_debug_args_bad(n_probes, probe_index_base, first_sample, n_samples)) return fail(c, PTC_E_ARG, "debug_probe_rays: bad argument");
   const uint32_t np = (uint32_t)n_probes, n = np * n_samples;
-  const uint32_t seed_hash = frame_seed_hash(seed);
+  const uint32_t seed_hash = ::seed_hash(seed);
   if (c->device < 0) {      // the host evaluation of pt_probes.h
     for (uint32_t p = 0; p < n; ++p) {
       const uint32_t j = p % np;
@@ -274,7 +273,7 @@ int ptc_debug_probe_project(ptc_ctx* c, int n_probes, uint32_t probe_index_base,
   if (!c) return PTC_E_ARG;
   if (!lpath_rgba || !acc_inout || probe_debug_args_bad(n_probes, probe_index_base, first_sample, n_samples)) return fail(c, PTC_E_ARG, "debug_probe_project: bad argument");
   const uint32_t np = (uint32_t)n_probes, n = np * n_samples;
-  const uint32_t seed_hash = frame_seed_hash(seed);
+  const uint32_t seed_hash = ::seed_hash(seed);
   if (c->device < 0) {      // the host evaluation of pt_probes.h: k_accumulate_sh's sums, sample by sample
     for (uint32_t j = 0; j < np; ++j)
       for (uint32_t s = 0; s < n_samples; ++s) {

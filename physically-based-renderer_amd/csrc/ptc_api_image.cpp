@@ -100,7 +100,7 @@ int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
   // the pixel-centre ray of k_raygen_guides: Z is t along the unit ray, the view depth is t over the length of (dvx, dvy, 1)
   const float fx = ((float)px + 0.5f) / (float)w, fy = ((float)py + 0.5f) / (float)h;
   const float dvx = (2.0f * fx - 1.0f) * c->cam.sx, dvy = (2.0f * fy - 1.0f) * c->cam.sy;
-  *out = nz.w / std::sqrt(pt_lens_fma(dvy, dvy, pt_lens_fma(dvx, dvx, 1.0f)));
+  *out = nz.w / std::sqrt(pt_fma(dvy, dvy, pt_fma(dvx, dvx, 1.0f)));
   return PTC_OK;
 }
 

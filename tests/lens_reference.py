@@ -51,7 +51,7 @@ def rng_f(key, bounce, dim):
 
 
 def sincos2pi(u, dt=F32):
-    """(sin, cos) of 2 pi u by the polynomial of pt_lens_sincos2pi."""
+    """(sin, cos) of 2 pi u by the polynomial of sincos2pi (csrc/pt_device.h)."""
     u = np.asarray(u, dt)
     x4 = u * dt(4.0)
     q = np.minimum(x4.astype(np.int32), 3)

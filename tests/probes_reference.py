@@ -1,7 +1,7 @@
 """numpy restatement of the light probes (csrc/pt_probes.h), for tests/test_probes_host.py and tests/test_gpu_probes.py.
 
 Everything is float32 in the order the header writes it (numpy's + - * / sqrt on float32 arrays are correctly rounded; `_fma` of lens_reference.py is the
-single rounding).  pcg, seed_hash, path_key, rng_f and sincos2pi are lens_reference.py's: the header uses pt_lens.h's copies."""
+single rounding).  pcg, seed_hash, path_key, rng_f and sincos2pi are lens_reference.py's: the header calls csrc/pt_device.h's, as the lens does."""
 import numpy as np
 
 from lens_reference import F32, F64, U64, _fma, path_key, rng_f, seed_hash, sincos2pi  # noqa: F401

@@ -4,16 +4,20 @@ import ast
 import hashlib
 import json
 import os
+import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROF = os.path.join(ROOT, "profiles")
+CSRC = os.path.join("physically-based-renderer_amd", "csrc")
+# the hashed kernel sources: the one list is csrc/Makefile's KERNEL_SRC
+KERNEL_SRC = [os.path.join(CSRC, f) for f in re.search(r"^KERNEL_SRC = (.*)$", open(os.path.join(ROOT, CSRC, "Makefile")).read(), re.M).group(1).split()]
 
 
 def _kernel_source_sha256():
     """csrc/Makefile's KERNEL_SHA: sha256 over its KERNEL_SRC list in that order — every file that holds device code (what ptc_build_info reports)."""
     h = hashlib.sha256()
-    for f in "pt_kernels.hip pt_device.h ptc_internal.h pt_refit.hip pt_refit.h pt_build.hip pt_build.h".split():
-        h.update(open(os.path.join(ROOT, "physically-based-renderer_amd", "csrc", f), "rb").read())
+    for f in KERNEL_SRC:
+        h.update(open(os.path.join(ROOT, f), "rb").read())
     return h.hexdigest()
 
 
@@ -81,7 +85,6 @@ def test_bench_line_of_the_committed_run_has_the_contract_fields():
     ast.parse(open(os.path.join(ROOT, "bench.py")).read())
 
 
-KERNEL_SRC = [os.path.join("physically-based-renderer_amd", "csrc", f) for f in "pt_kernels.hip pt_device.h ptc_internal.h pt_refit.hip pt_refit.h pt_build.hip pt_build.h".split()]
 STRIPPED_PATCHES = ("instr_diag", "instr_stamp", "instr_stamp_shade", "exp_leaf_extra", "exp_shade_variants", "exp_misc", "exp_oracle_fp16_slab")
 
 
@@ -126,3 +129,16 @@ def test_stripped_instrumentation_and_experiments_apply_as_patches():
     for name in STRIPPED_PATCHES:
         r = subprocess.run(["git", "apply", "--check", os.path.join("profiles", name + ".patch")], cwd=ROOT, capture_output=True, text=True)
         assert r.returncode == 0, (name, r.stderr)
+
+
+def test_render_arithmetic_has_one_definition():
+    """DESIGN.md's arithmetic contract: an expression is written once in the product (csrc/pt_device.h, host + device) and once in the oracle.  Four literals that
+    only the RNG hash, sincos2pi, pt_log2 and rrt_odt hold each occur in exactly one file under csrc/; no header has a device part behind a macro any more; and the
+    list of hashed sources this file uses is the Makefile's, with the shared device header on it."""
+    src = {f: open(os.path.join(ROOT, CSRC, f), encoding="utf-8").read() for f in sorted(os.listdir(os.path.join(ROOT, CSRC)))}
+    for literal in ("747796405", "2.7557319e-6", "0.3205989", "0.983729f"):
+        assert [f for f, text in src.items() if literal in text] == ["pt_device.h"], literal
+    assert not [f for f, text in src.items() if "PT_LIGHTS_DEVICE_PART" in text]
+    make = re.search(r"^KERNEL_SRC = (.*)$", src["Makefile"], re.M).group(1).split()
+    assert [os.path.basename(f) for f in KERNEL_SRC] == make and {"pt_kernels.hip", "pt_device.h", "pt_shading.h"} <= set(make)
+    assert set(f for f in make if f.endswith(".h")) <= set(re.search(r"^HDR = (.*)$", src["Makefile"], re.M).group(1).split())
