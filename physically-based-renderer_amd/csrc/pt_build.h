@@ -1,7 +1,7 @@
 // pt_build.h — the BVH build ON THE DEVICE (pt_build.hip): SURVEY §8a P2 "host build first, GPU build later", north_star's "flattened LBVH".
 //
-// The definition of every value is the host's LBVH build (ptc_scene.cpp, build_or_refit with bvh_builder == PTC_BVH_LBVH), which the oracle pins
-// (oracle/ptc_oracle.c: morton_order, morton_split, dp_compute, widen): 63-bit Morton codes of the triangle-box centres, order (code, primitive id),
+// The tree is the host's LBVH build (ptc_scene.cpp, build_or_refit with bvh_builder == PTC_BVH_LBVH), which the oracle pins (oracle/ptc_oracle.c:
+// morton_order, morton_split, dp_compute, widen); the value rules both builds call are written once, in pt_scene_rules.h: 63-bit Morton codes of the triangle-box centres, order (code, primitive id),
 // the radix tree of the keys (code, sorted position), bottom-up boxes and collapse-cost tables, the cost-optimal 8-wide collapse, octant slots, and the
 // unit layout (breadth-first top, depth-first rest).  The device build writes THE SAME BYTES (tests/test_gpu_parity.py compares the unit arrays),
 // from the world-space vertices a refit keeps in HBM (DevRefit::wverts / widx) — so a scene that has moved far from its commit is rebuilt where it

@@ -1,30 +1,28 @@
-// pt_build.hip — the LBVH and binned-SAH builds on the device (see pt_build.h; the definition of every value is the host build in ptc_scene.cpp).
+// pt_build.hip — the LBVH and binned-SAH builds on the device (see pt_build.h).
 //
 // Everything here is integer / byte work with a few float comparisons per node: HBM- and latency-bound, nothing for MFMA.  The arithmetic that decides
-// the tree — centres, Morton quantisation, box unions, half areas, the collapse-cost sums, the slot scores — is written with the host's expressions in
-// the host's order (-ffp-contract=off on both sides), because the contract is byte equality of the result, not a tree "as good as" the host's.
+// the tree — centres, Morton quantisation, box unions, half areas, bin indices, cut costs, the collapse tables, the slot scores — is pt_scene_rules.h's, the
+// text the host build (ptc_scene.cpp) runs too, because the contract is byte equality of the result, not a tree "as good as" the host's.  What is written
+// here is how the work is spread: sorts, scans, levels, and the layout (which the host numbers by another algorithm to the same addresses).
 #include "pt_build.h"
+#include "pt_scene_rules.h"
+using namespace scene_rules;
 
 #include <string>
 #include <vector>
 
 namespace {
 constexpr int kBlock = 256;
-constexpr int kWideB = 8;
-constexpr uint32_t kLeafMaxB = 2;
 constexpr uint32_t kEmptyLink = 0x80000000u;
 constexpr uint32_t kUnset = 0xffffffffu;
 constexpr uint32_t kSortTile = 512;       // keys per wave of a sort pass: 8 steps of 64, in order (the sort is stable)
 
-struct Box6 { float lo[3], hi[3]; };
-struct DpT { uint32_t bits; float c[7]; };   // c[i - 1] = C(n, i), i = 1..7; bits: 0 leaf1, i (2..7) same[i], 8 + 3 (j - 2) .. : k[j], j = 2..8
-
 struct Bld {
   const HostVertex* wverts; const uint32_t* widx; const uint32_t* prim_cls; uint32_t n, budget;
-  Box6* tbox; uint32_t* cb;
+  Box* tbox; uint32_t* cb;
   unsigned long long *key_a, *key_b; uint32_t *val_a, *val_b; uint32_t* hist; uint32_t* digit_total;
   int32_t *r_left, *r_right; uint32_t *r_lo, *r_hi, *r_parent, *leaf_parent, *r_flag;
-  Box6* r_box; DpT* dp;
+  Box* r_box; DpT* dp;
   int32_t* w_radix; uint32_t* w_parent; int32_t* w_link; uint32_t* w_child; uint32_t *w_own, *w_sub, *w_baddr, *w_naddr;
   uint32_t* counters;    // [0] 8-wide nodes so far, [1] units of the array, [2] entries of top_order
   uint32_t* top_order;
@@ -33,34 +31,19 @@ struct Bld {
   float4* ctr; struct SahRange *s_list[2], *s_big[2]; uint32_t *s_cnt, *s_bigcnt; struct SahSlot* s_slot; uint32_t *s_blk, *s_root;   // s_root[1]: error bits
 };
 
-__device__ inline uint32_t ordered_u(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ inline float unordered_f(uint32_t enc) { return __uint_as_float((enc & 0x80000000u) ? (enc ^ 0x80000000u) : ~enc); }
-__device__ inline void grow6(Box6& b, const Box6& o) {
-  for (int k = 0; k < 3; ++k) { b.lo[k] = o.lo[k] < b.lo[k] ? o.lo[k] : b.lo[k]; b.hi[k] = o.hi[k] > b.hi[k] ? o.hi[k] : b.hi[k]; }
-}
-__device__ inline float half_area6(const Box6& b) {
-  const float ex = b.hi[0] - b.lo[0], ey = b.hi[1] - b.lo[1], ez = b.hi[2] - b.lo[2];
-  return ex * ey + ey * ez + ez * ex;
-}
-
 __global__ void k_bld_init(Bld b) {
   const uint32_t i = threadIdx.x;
   if (i < 6) b.cb[i] = i < 3 ? 0xffffffffu : 0u;
   if (i == 0) { b.counters[0] = 1u; b.counters[1] = 0u; b.counters[2] = 0u; b.w_radix[0] = 0; b.w_parent[0] = kUnset; }
 }
 
-// ---- triangle boxes (the host's tbox: < and > from +-inf over the vertices in order) and the bounds of their centres -------------------------
+// ---- triangle boxes and the bounds of their centres -------------------------
 __global__ __launch_bounds__(kBlock) void k_bld_prims(Bld b) {
   float cl[3] = {INFINITY, INFINITY, INFINITY}, ch[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < b.n; p += gridDim.x * kBlock) {
-    Box6 t;
-    for (int k = 0; k < 3; ++k) { t.lo[k] = INFINITY; t.hi[k] = -INFINITY; }
-    for (int c = 0; c < 3; ++c) {
-      const float* P = b.wverts[b.widx[(size_t)p * 3 + c]].position;
-      for (int k = 0; k < 3; ++k) { t.lo[k] = P[k] < t.lo[k] ? P[k] : t.lo[k]; t.hi[k] = P[k] > t.hi[k] ? P[k] : t.hi[k]; }
-    }
+    const Box t = triangle_box(b.wverts[b.widx[(size_t)p * 3]].position, b.wverts[b.widx[(size_t)p * 3 + 1]].position, b.wverts[b.widx[(size_t)p * 3 + 2]].position);
     b.tbox[p] = t;
-    for (int k = 0; k < 3; ++k) { const float c = 0.5f * (t.lo[k] + t.hi[k]); cl[k] = fminf(cl[k], c); ch[k] = fmaxf(ch[k], c); }
+    for (int k = 0; k < 3; ++k) { const float c = centre(t, k); cl[k] = fminf(cl[k], c); ch[k] = fmaxf(ch[k], c); }
   }
   __shared__ float red[6][kBlock / 64];
   for (int k = 0; k < 3; ++k) {
@@ -76,26 +59,14 @@ __global__ __launch_bounds__(kBlock) void k_bld_prims(Bld b) {
   }
 }
 
-__device__ inline unsigned long long spread21(uint32_t v) {       // bit i of v -> bit 3 i
-  unsigned long long x = v & 0x1fffffu;
-  x = (x | x << 32) & 0x1f00000000ffffull;
-  x = (x | x << 16) & 0x1f0000ff0000ffull;
-  x = (x | x << 8) & 0x100f00f00f00f00full;
-  x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-  x = (x | x << 2) & 0x1249249249249249ull;
-  return x;
-}
 __global__ __launch_bounds__(kBlock) void k_bld_codes(Bld b) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= b.n) return;
-  const Box6 t = b.tbox[p];
+  const Box t = b.tbox[p];
   unsigned long long code = 0;
   for (int k = 0; k < 3; ++k) {
-    const float cl = unordered_f(b.cb[k]), ch = unordered_f(b.cb[3 + k]);
-    const float scale = ch > cl ? 2097152.0f / (ch - cl) : 0.0f;
-    const float f = (0.5f * (t.lo[k] + t.hi[k]) - cl) * scale;
-    const uint32_t q = f >= 2097151.0f ? 2097151u : (uint32_t)f;
-    code |= spread21(q) << k;
+    const float cl = unordered_f(b.cb[k]);
+    code |= morton_axis(centre(t, k), cl, cell_scale(cl, unordered_f(b.cb[3 + k]), kMortonCells)) << k;
   }
   b.key_a[p] = code; b.val_a[p] = p;
 }
@@ -233,12 +204,11 @@ __global__ __launch_bounds__(kBlock) void k_bld_radix(Bld b) {
 // ---- the binned-SAH binary tree (ptc_scene.cpp: build_split_tree, split_range, split_range_parallel), top down, one LEVEL of open ranges per launch.  Per range:
 // the bounds of its centres come with it (its parent's partition reduced them); on every axis with ch > cl, 32 bins of j = min((int)((c - cl) * (32 / (ch - cl))), 31)
 // hold a count and a box union (integer atomics: counts add, boxes take min / max of the order-preserving encoding — exact in any order); the suffix and prefix
-// sweeps are lane scans of the same min / max and integer sums; each boundary's cost is the host's expression; the cut is the first strict minimum in (axis, bin)
+// sweeps are lane scans of the same min / max and integer sums; each boundary's cost is sah_cut_cost; the cut is the first strict minimum in (axis, bin)
 // order, or the middle when no axis has a candidate; the partition of ord[lo..hi] is stable on both sides.  So the tree is the host's, node for node.
 // Node ids: an internal node is named by its cut (the last position of its left part), the root's cut swapped with 0 so that the root is node 0 — every id in
 // [0, n - 2], no allocation; a child writes its own id into its parent's link when it is cut.
 struct SahRange { uint32_t lo, hi, parent, bnd[6]; };     // parent: node id | side << 31 (kUnset for the root); bnd: ordered_u of the centre bounds lo[3], hi[3]
-constexpr int kSahBins = 32;
 constexpr int kBinWords = 7 * 3 * kSahBins;               // [field][axis * 32 + bin]: field 0 the count, 1..3 box lo, 4..6 box hi (ordered_u)
 constexpr uint32_t kSahBig = 1024;                        // ranges of at least this many triangles are cut by several workgroups (k_sah_big_*)
 constexpr uint32_t kSahChunk = 4096;                      // triangles per workgroup of the big-range kernels
@@ -248,26 +218,24 @@ struct SahCut { int axis, bin; };
 
 __device__ inline uint32_t sah_bin_init(uint32_t w) { return w < 3u * kSahBins ? 0u : (w < 12u * kSahBins ? kOrdPosInf : kOrdNegInf); }
 __device__ inline uint32_t sah_cbnd_init(uint32_t w) { return (w % 6u) < 3u ? kOrdPosInf : kOrdNegInf; }
-__device__ inline int sah_bin(float c, float cl, float scale) {
-  const int j = (int)((c - cl) * scale);
-  return j > kSahBins - 1 ? kSahBins - 1 : (j < 0 ? 0 : j);
-}
+// the bin index addresses LDS and global atomics: a centre below its range's bounds (it cannot be: the bounds are the minima of these centres) stays in bin 0
+__device__ inline int sah_bin_guarded(float c, float cl, float scale) { const int j = sah_bin(c, cl, scale); return j < 0 ? 0 : j; }
 struct SahAxes {
   float cl[3], ch[3], scale[3];
   __device__ explicit SahAxes(const uint32_t* bnd) {
     for (int k = 0; k < 3; ++k) {
       cl[k] = unordered_f(bnd[k]); ch[k] = unordered_f(bnd[3 + k]);
-      scale[k] = ch[k] > cl[k] ? (float)kSahBins / (ch[k] - cl[k]) : 0.0f;
+      scale[k] = cell_scale(cl[k], ch[k], (float)kSahBins);
     }
   }
   __device__ bool on(int k) const { return ch[k] > cl[k]; }
 };
 // adds triangle p to the bins (LDS or global)
-__device__ inline void sah_bin_add(uint32_t* bins, const SahAxes& ax, const float4& c, const Box6& t) {
+__device__ inline void sah_bin_add(uint32_t* bins, const SahAxes& ax, const float4& c, const Box& t) {
   const float cc[3] = {c.x, c.y, c.z};
   for (int k = 0; k < 3; ++k) {
     if (!ax.on(k)) continue;
-    const uint32_t w = (uint32_t)k * kSahBins + (uint32_t)sah_bin(cc[k], ax.cl[k], ax.scale[k]);
+    const uint32_t w = (uint32_t)k * kSahBins + (uint32_t)sah_bin_guarded(cc[k], ax.cl[k], ax.scale[k]);
     atomicAdd(&bins[w], 1u);
     for (int d = 0; d < 3; ++d) { atomicMin(&bins[(1 + d) * 3 * kSahBins + w], ordered_u(t.lo[d])); atomicMax(&bins[(4 + d) * 3 * kSahBins + w], ordered_u(t.hi[d])); }
   }
@@ -278,30 +246,29 @@ __device__ SahCut sah_choose(const uint32_t* bins, const SahAxes& ax) {
   float best = INFINITY; SahCut cut{-1, 0};
   for (int k = 0; k < 3; ++k) {
     if (!ax.on(k)) continue;
-    uint32_t cnt = 0; Box6 bx;
-    for (int d = 0; d < 3; ++d) { bx.lo[d] = INFINITY; bx.hi[d] = -INFINITY; }
+    uint32_t cnt = 0; Box bx = empty_box();
     if (lane < (uint32_t)kSahBins) {
       const uint32_t w = (uint32_t)k * kSahBins + lane;
       cnt = bins[w];
       for (int d = 0; d < 3; ++d) { bx.lo[d] = unordered_f(bins[(1 + d) * 3 * kSahBins + w]); bx.hi[d] = unordered_f(bins[(4 + d) * 3 * kSahBins + w]); }
     }
-    uint32_t sc = cnt, pc = cnt; Box6 sb = bx, pb = bx;
+    uint32_t sc = cnt, pc = cnt; Box sb = bx, pb = bx;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const uint32_t osc = __shfl_down(sc, o), opc = __shfl_up(pc, o);
-      Box6 os, op;
+      Box os, op;
       for (int d = 0; d < 3; ++d) {
         os.lo[d] = __shfl_down(sb.lo[d], o); os.hi[d] = __shfl_down(sb.hi[d], o);
         op.lo[d] = __shfl_up(pb.lo[d], o); op.hi[d] = __shfl_up(pb.hi[d], o);
       }
-      if (lane + (uint32_t)o < 64u) { sc += osc; grow6(sb, os); }
-      if (lane >= (uint32_t)o) { pc += opc; grow6(pb, op); }
+      if (lane + (uint32_t)o < 64u) { sc += osc; grow(sb, os); }
+      if (lane >= (uint32_t)o) { pc += opc; grow(pb, op); }
     }
-    const float sa = sc ? half_area6(sb) : 0.0f;                   // suffix_area[lane]
+    const float sa = sah_suffix_area(sb, sc);                   // suffix_area[lane]
     const uint32_t nsc = __shfl_down(sc, 1);
     const float nsa = __shfl_down(sa, 1);
     float cost = INFINITY;
-    if (lane + 1u < (uint32_t)kSahBins && pc != 0u && nsc != 0u) cost = half_area6(pb) * (float)pc + nsa * (float)nsc;
+    if (lane + 1u < (uint32_t)kSahBins && pc != 0u && nsc != 0u) cost = sah_cut_cost(pb, pc, nsa, nsc);
     if (!(cost < INFINITY)) cost = INFINITY;                        // +inf and NaN never win
     int bj = (int)lane;
 #pragma unroll
@@ -316,7 +283,7 @@ __device__ SahCut sah_choose(const uint32_t* bins, const SahAxes& ax) {
 __device__ inline bool sah_left(const SahCut& cut, const SahAxes& ax, const float4& c, uint32_t i, uint32_t mid) {
   if (cut.axis < 0) return i <= mid;
   const float cc = cut.axis == 0 ? c.x : (cut.axis == 1 ? c.y : c.z);
-  return sah_bin(cc, ax.cl[cut.axis], ax.scale[cut.axis]) <= cut.bin;
+  return sah_bin_guarded(cc, ax.cl[cut.axis], ax.scale[cut.axis]) <= cut.bin;
 }
 __device__ inline void bnd_add(float* bd, const float4& c) {
   bd[0] = fminf(bd[0], c.x); bd[1] = fminf(bd[1], c.y); bd[2] = fminf(bd[2], c.z);
@@ -352,8 +319,8 @@ __device__ void sah_finish(const Bld& b, const SahRange& r, uint32_t g, const fl
 __global__ __launch_bounds__(kBlock) void k_sah_init(Bld b) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= b.n) return;
-  const Box6 t = b.tbox[p];
-  b.ctr[p] = make_float4(0.5f * (t.lo[0] + t.hi[0]), 0.5f * (t.lo[1] + t.hi[1]), 0.5f * (t.lo[2] + t.hi[2]), 0.0f);
+  const Box t = b.tbox[p];
+  b.ctr[p] = make_float4(centre(t, 0), centre(t, 1), centre(t, 2), 0.0f);
   b.val_a[p] = p;
   if (p == 0) {
     SahRange e;
@@ -549,8 +516,7 @@ __global__ __launch_bounds__(kBlock) void k_sah_big_finish(Bld b, uint32_t level
 // everything a node reads was written by an earlier launch and no fence is needed.  (The textbook form — one thread per triangle walks up, the second arrival at
 // a node proceeds — needs a release / acquire pair of agent-scope fences per step, and on a chip of 8 XCDs with an L2 each those are L2 write-backs and
 // invalidations: 1.6 ms for the 249,936-triangle atrium against 0.4 ms for the ~60 rounds of this one.)
-__device__ inline Box6 link_box(const Bld& b, int32_t link) { return link < 0 ? b.tbox[b.val_a[(size_t)~link]] : b.r_box[(size_t)link]; }
-__device__ inline int min7(int k) { return k > 7 ? 7 : k; }
+__device__ inline Box link_box(const Bld& b, int32_t link) { return link < 0 ? b.tbox[b.val_a[(size_t)~link]] : b.r_box[(size_t)link]; }
 __global__ __launch_bounds__(kBlock) void k_bld_up(Bld b, uint32_t round) {
   const uint32_t cur = blockIdx.x * kBlock + threadIdx.x;
   if (cur + 1u >= b.n || b.r_flag[cur]) return;
@@ -558,59 +524,38 @@ __global__ __launch_bounds__(kBlock) void k_bld_up(Bld b, uint32_t round) {
   if (left >= 0) { const uint32_t f = b.r_flag[left]; if (f == 0u || f >= round) return; }
   if (right >= 0) { const uint32_t f = b.r_flag[right]; if (f == 0u || f >= round) return; }
   {
-    const Box6 bl = link_box(b, left), br = link_box(b, right);
-    Box6 nb = bl;
-    grow6(nb, br);
+    const Box bl = link_box(b, left), br = link_box(b, right);
+    Box nb = bl;
+    grow(nb, br);
     float cl[8], cr[8];
-    if (left < 0) { const float a = half_area6(bl) * 1.0f * 1.0f; for (int i = 1; i <= 7; ++i) cl[i] = a; }
-    else { const DpT dl = b.dp[(size_t)left]; for (int i = 1; i <= 7; ++i) cl[i] = dl.c[i - 1]; }
-    if (right < 0) { const float a = half_area6(br) * 1.0f * 1.0f; for (int i = 1; i <= 7; ++i) cr[i] = a; }
-    else { const DpT dr = b.dp[(size_t)right]; for (int i = 1; i <= 7; ++i) cr[i] = dr.c[i - 1]; }
-    DpT d;
-    d.bits = 0u;
+    if (left < 0) dp_row(half_area(bl), cl); else dp_row(b.dp[(size_t)left], cl);
+    if (right < 0) dp_row(half_area(br), cr); else dp_row(b.dp[(size_t)right], cr);
     float dist[9];
-    for (int j = 2; j <= 8; ++j) {
-      float best = INFINITY; int bk = 1;
-      for (int k = 1; k < j; ++k) {
-        const float v = cl[min7(k)] + cr[min7(j - k)];
-        if (v < best) { best = v; bk = k; }
-      }
-      dist[j] = best; d.bits |= (uint32_t)bk << (8 + 3 * (j - 2));
-    }
-    const uint32_t P = b.r_hi[cur] - b.r_lo[cur] + 1u;
-    const float area = half_area6(nb);
-    const float cleaf = P <= kLeafMaxB ? area * (float)P * 1.0f : INFINITY;
-    const float cint = dist[8] + area * 1.0f;
-    const bool leaf1 = cleaf <= cint;
-    if (leaf1) d.bits |= 1u;
-    d.c[0] = leaf1 ? cleaf : cint;
-    for (int i = 2; i <= 7; ++i) {
-      if (dist[i] < d.c[i - 2]) d.c[i - 1] = dist[i]; else { d.c[i - 1] = d.c[i - 2]; d.bits |= 1u << i; }
-    }
+    const uint32_t kbits = collapse_dist(cl, cr, dist);
+    const DpT d = collapse_table(kbits, dist, b.r_hi[cur] - b.r_lo[cur] + 1u, half_area(nb));
     b.r_box[cur] = nb;
     b.dp[cur] = d;
     b.r_flag[cur] = round;
   }
 }
 
-// ---- 8-wide collapse, one level of the wide tree per launch (ptc_scene.cpp: expand = forest + make_wide / assign_slots).  A link of a slot: >= 0 the radix node
+// ---- 8-wide collapse, one level of the wide tree per launch (ptc_scene.cpp: expand = forest + make_wide; the decision step and the slots are pt_scene_rules.h's).  A link of a slot: >= 0 the radix node
 // of an interior child, kEmptyLink an unused slot, else ~(first sorted position | (triangles - 1) << 28) of a leaf.
-struct Kid { int32_t link; bool leaf; uint32_t lo, hi; Box6 box; };
+struct Kid { int32_t link; bool leaf; uint32_t lo, hi; Box box; };
 __device__ inline void forest(const Bld& b, int32_t link0, int i0, Kid* kid, int& n) {
   int32_t sl[16]; int si[16]; int sp = 0;
   sl[sp] = link0; si[sp] = i0; ++sp;
   while (sp > 0) {
     --sp;
-    const int32_t link = sl[sp]; int i = si[sp];
+    const int32_t link = sl[sp];
     Kid c;
     c.box = link_box(b, link);
     if (link < 0) { c.leaf = true; c.lo = c.hi = (uint32_t)~link; c.link = -1; kid[n++] = c; continue; }
     const uint32_t bits = b.dp[(size_t)link].bits;
-    while (i > 1 && ((bits >> i) & 1u)) --i;
-    if (i == 1) { c.leaf = (bits & 1u) != 0u; c.lo = b.r_lo[link]; c.hi = b.r_hi[link]; c.link = link; kid[n++] = c; continue; }
-    const int kk = (int)((bits >> (8 + 3 * (i - 2))) & 7u);
-    sl[sp] = b.r_right[link]; si[sp] = min7(i - kk); ++sp;       // left first
-    sl[sp] = b.r_left[link]; si[sp] = min7(kk); ++sp;
+    int il, ir;
+    if (!forest_split(bits, si[sp], il, ir)) { c.leaf = dp_leaf1(bits); c.lo = b.r_lo[link]; c.hi = b.r_hi[link]; c.link = link; kid[n++] = c; continue; }
+    sl[sp] = b.r_right[link]; si[sp] = ir; ++sp;       // left first
+    sl[sp] = b.r_left[link]; si[sp] = il; ++sp;
   }
 }
 __global__ __launch_bounds__(64) void k_bld_widen(Bld b, uint32_t first, uint32_t count) {
@@ -618,40 +563,21 @@ __global__ __launch_bounds__(64) void k_bld_widen(Bld b, uint32_t first, uint32_
   if (t >= count) return;
   const uint32_t idx = first + t;
   const int32_t r = b.w_radix[idx];
-  Kid kid[kWideB];
+  Kid kid[kWide];
   int n = 0;
   {
-    const int kk = (int)((b.dp[(size_t)r].bits >> (8 + 3 * 6)) & 7u);       // k[8]
+    const int kk = dp_k(b.dp[(size_t)r].bits, 8);
     forest(b, b.r_left[r], min7(kk), kid, n);
     forest(b, b.r_right[r], min7(8 - kk), kid, n);
   }
-  // slots: repeatedly the (child, free slot) pair with the largest +-dx +-dy +-dz, d = child centre - node centre; ties: lowest child, then lowest slot
-  Box6 nb;
-  for (int k = 0; k < 3; ++k) { nb.lo[k] = INFINITY; nb.hi[k] = -INFINITY; }
-  for (int i = 0; i < n; ++i) grow6(nb, kid[i].box);
-  float d[kWideB][3];
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < 3; ++k) d[i][k] = 0.5f * (kid[i].box.lo[k] + kid[i].box.hi[k]) - 0.5f * (nb.lo[k] + nb.hi[k]);
-  uint32_t child_done = 0, slot_used = 0;
-  int slot_of[kWideB];
-  for (int round = 0; round < n; ++round) {
-    int bi = -1, bs = -1; float bsc = 0.0f;
-    for (int i = 0; i < n; ++i) {
-      if ((child_done >> i) & 1u) continue;
-      for (int sl = 0; sl < kWideB; ++sl) {
-        if ((slot_used >> sl) & 1u) continue;
-        const float sc = ((sl & 1) ? d[i][0] : -d[i][0]) + ((sl & 2) ? d[i][1] : -d[i][1]) + ((sl & 4) ? d[i][2] : -d[i][2]);
-        if (bi < 0 || sc > bsc) { bi = i; bs = sl; bsc = sc; }
-      }
-    }
-    child_done |= 1u << bi; slot_used |= 1u << bs; slot_of[bi] = bs;
-  }
-  int32_t links[kWideB]; uint32_t childs[kWideB];
-  for (int sl = 0; sl < kWideB; ++sl) { links[sl] = (int32_t)kEmptyLink; childs[sl] = kUnset; }
+  int slot_of[kWide];
+  assign_slots(kid, n, slot_of);
+  int32_t links[kWide]; uint32_t childs[kWide];
+  for (int sl = 0; sl < kWide; ++sl) { links[sl] = (int32_t)kEmptyLink; childs[sl] = kUnset; }
   uint32_t ni = 0, nt = 0;
   for (int i = 0; i < n; ++i) {
     const int sl = slot_of[i];
-    if (kid[i].leaf) { links[sl] = (int32_t)~(kid[i].lo | ((kid[i].hi - kid[i].lo) << 28)); nt += kid[i].hi - kid[i].lo + 1u; }
+    if (kid[i].leaf) { links[sl] = (int32_t)leaf_code(kid[i].lo, kid[i].hi - kid[i].lo + 1u); nt += kid[i].hi - kid[i].lo + 1u; }
     else {
       links[sl] = kid[i].link;
       const uint32_t c = atomicAdd(&b.counters[0], 1u);
@@ -659,8 +585,8 @@ __global__ __launch_bounds__(64) void k_bld_widen(Bld b, uint32_t first, uint32_
       childs[sl] = c; ++ni;
     }
   }
-  for (int sl = 0; sl < kWideB; ++sl) { b.w_link[(size_t)idx * 8 + sl] = links[sl]; b.w_child[(size_t)idx * 8 + sl] = childs[sl]; }
-  b.w_own[idx] = (4u * ni + 3u * nt + 3u) & ~3u;
+  for (int sl = 0; sl < kWide; ++sl) { b.w_link[(size_t)idx * 8 + sl] = links[sl]; b.w_child[(size_t)idx * 8 + sl] = childs[sl]; }
+  b.w_own[idx] = block_units(ni, nt);
   b.w_baddr[idx] = kUnset;
 }
 
@@ -670,7 +596,7 @@ __global__ __launch_bounds__(kBlock) void k_bld_sizes(Bld b, uint32_t first, uin
   if (t >= count) return;
   const uint32_t idx = first + t;
   uint32_t s = b.w_own[idx];
-  for (int sl = 0; sl < kWideB; ++sl) { const uint32_t c = b.w_child[(size_t)idx * 8 + sl]; if (c != kUnset) s += b.w_sub[c]; }
+  for (int sl = 0; sl < kWide; ++sl) { const uint32_t c = b.w_child[(size_t)idx * 8 + sl]; if (c != kUnset) s += b.w_sub[c]; }
   b.w_sub[idx] = s;
 }
 
@@ -686,7 +612,7 @@ __global__ void k_bld_top(Bld b) {
     const uint32_t idx = order[head];
     b.w_baddr[idx] = next_unit;
     next_unit += b.w_own[idx];
-    for (int sl = 0; sl < kWideB; ++sl) { const uint32_t c = b.w_child[(size_t)idx * 8 + sl]; if (c != kUnset) order[cnt++] = c; }
+    for (int sl = 0; sl < kWide; ++sl) { const uint32_t c = b.w_child[(size_t)idx * 8 + sl]; if (c != kUnset) order[cnt++] = c; }
   }
   for (uint32_t i = head; i < cnt; ++i) { const uint32_t idx = order[i]; b.w_baddr[idx] = next_unit; next_unit += b.w_sub[idx]; }
   b.counters[1] = next_unit; b.counters[2] = cnt;
@@ -712,24 +638,26 @@ __global__ __launch_bounds__(kBlock) void k_bld_emit(Bld b, uint32_t first, uint
   if (t >= count) return;
   const uint32_t idx = first + t;
   uint32_t imask = 0, lmask = 0, two = 0, ni = 0;
-  for (int sl = 0; sl < kWideB; ++sl) {
+  for (int sl = 0; sl < kWide; ++sl) {
     const uint32_t l = (uint32_t)b.w_link[(size_t)idx * 8 + sl];
     if (l == kEmptyLink) continue;
     if ((int32_t)l >= 0) { imask |= 1u << sl; ++ni; }
     else { lmask |= 1u << sl; if (((~l) >> 28) == 1u) two |= 1u << sl; }
   }
   const uint32_t block = b.w_baddr[idx], at = b.w_naddr[idx];
-  reinterpret_cast<uint4*>(recs)[at] = make_uint4(0u, 0u, (imask << 8) | (lmask << 16) | (two << 24), block);
+  const uint32_t none[3] = {0u, 0u, 0u};      // origin, exponents and planes are the refit kernels'
+  uint32_t w[3];
+  node_header(none, none, node_masks(imask, lmask, two), w);
+  reinterpret_cast<uint4*>(recs)[at] = make_uint4(w[0], w[1], w[2], block);
   uint32_t tri = block + 4u * ni;
-  for (int sl = 0; sl < kWideB; ++sl) {
+  for (int sl = 0; sl < kWide; ++sl) {
     if (!((lmask >> sl) & 1u)) continue;
     const uint32_t code = ~(uint32_t)b.w_link[(size_t)idx * 8 + sl];
     const uint32_t lo = code & 0x0fffffffu, cntt = (code >> 28) + 1u;
     for (uint32_t k = 0; k < cntt; ++k) {
       const uint32_t prim = b.val_a[lo + k];
-      recs[tri] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(prim));
-      recs[tri + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(b.prim_cls[prim]));
-      recs[tri + 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      const float zero[3] = {0.0f, 0.0f, 0.0f};
+      tri_record(recs + tri, zero, zero, zero, prim, b.prim_cls[prim]);
       tri += 3u;
     }
   }
@@ -758,12 +686,12 @@ std::string build_tree(hipStream_t st, const HostVertex* wverts, const uint32_t*
   b.wverts = wverts; b.widx = widx; b.prim_cls = prim_cls; b.n = n; b.budget = toplet_budget;
   auto layout = [&](char* base) {
     char* p = base;
-    b.tbox = carve<Box6>(p, n); b.cb = carve<uint32_t>(p, 8);
+    b.tbox = carve<Box>(p, n); b.cb = carve<uint32_t>(p, 8);
     b.key_a = carve<unsigned long long>(p, n); b.key_b = carve<unsigned long long>(p, n); b.val_a = carve<uint32_t>(p, n); b.val_b = carve<uint32_t>(p, n);
     b.hist = carve<uint32_t>(p, (size_t)(tiles + 4u) * 256u); b.digit_total = carve<uint32_t>(p, 256);
     b.r_left = carve<int32_t>(p, n); b.r_right = carve<int32_t>(p, n); b.r_lo = carve<uint32_t>(p, n); b.r_hi = carve<uint32_t>(p, n);
     b.r_parent = carve<uint32_t>(p, n); b.leaf_parent = carve<uint32_t>(p, n); b.r_flag = carve<uint32_t>(p, n);
-    b.r_box = carve<Box6>(p, n); b.dp = carve<DpT>(p, n);
+    b.r_box = carve<Box>(p, n); b.dp = carve<DpT>(p, n);
     b.w_radix = carve<int32_t>(p, n); b.w_parent = carve<uint32_t>(p, n); b.w_link = carve<int32_t>(p, (size_t)n * 8); b.w_child = carve<uint32_t>(p, (size_t)n * 8);
     b.w_own = carve<uint32_t>(p, n); b.w_sub = carve<uint32_t>(p, n); b.w_baddr = carve<uint32_t>(p, n); b.w_naddr = carve<uint32_t>(p, n);
     b.counters = carve<uint32_t>(p, 8); b.top_order = carve<uint32_t>(p, budget + 16);

@@ -1,7 +1,7 @@
 // pt_refit.h — refit of a committed scene ON THE DEVICE (pt_refit.hip), declarations shared with ptc_api.cpp / ptc_scene.cpp.
 //
-// ptc_refit_scene (ptc_scene.cpp) is the definition: same tree, same slots, same unit layout; everything that depends on vertex positions
-// is recomputed.  The device path does the same arithmetic (same expressions, -ffp-contract=off, correctly rounded / and sqrt) element-parallel
+// Same tree, same slots, same unit layout; everything that depends on vertex positions is recomputed.  ptc_refit_scene (ptc_scene.cpp) and the
+// device path call the same functions (pt_scene_rules.h: one text under -ffp-contract=off, correctly rounded / and sqrt); the device runs them element-parallel
 // and IN PLACE on the scene's arrays in HBM, so a moved instance costs three kernel families and a 32-byte read-back instead of a host pass
 // over every vertex plus an upload of the whole BVH.  What stays on the host: the instances' normal matrices (a handful of 3x3 inverses) and
 // the emitter table (the emissive primitives only).  tests/test_gpu_parity.py holds the device result byte for byte against the host refit
@@ -55,5 +55,3 @@ void pt_refit_decode_bounds(const uint32_t raw[8], float lo[3], float hi[3], boo
 // nodes and triangle records, level by level from the leaves up
 // scene_half_area: half area of the scene box (the denominator of the cost sum; <= 0: no sum)
 void pt_launch_refit_nodes(hipStream_t, const DevRefit&, const std::vector<uint32_t>& level_first, const float grid_lo[3], const float grid_step[3], float scene_half_area);
-// the cost term of one child slot in units of 2^-20 (shared by the host build, which sums the same terms)
-#define PTC_SA_COST_ONE 1048576.0f

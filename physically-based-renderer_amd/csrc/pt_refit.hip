@@ -1,4 +1,5 @@
-// pt_refit.hip — the refit of a committed scene on the device (see pt_refit.h; the definition of every value is ptc_refit_scene in ptc_scene.cpp).
+// pt_refit.hip — the refit of a committed scene on the device (see pt_refit.h).  The definition of every value is pt_scene_rules.h, which the host refit
+// (ptc_refit_scene in ptc_scene.cpp) calls too; what is written here is who computes which value: threads, octets, reductions.
 //
 //   k_refit_flatten   one thread per world vertex: instance transform of position / normal / tangent / bitangent           (R1, vertex.glsl:28-40)
 //   k_refit_prims     grid-stride over the primitives: the shading record of each, and the scene box by block reduction + 6 atomics per block
@@ -9,28 +10,12 @@
 // primitive, 64 B + its triangles read and written per node.  No LDS tiling applies (every record is touched once), so the only layout rule is
 // the one the arrays already obey: whole records per thread, threads in record order.
 #include "pt_refit.h"
+#include "pt_scene_rules.h"
+using namespace scene_rules;
 
 namespace {
 constexpr int kBlock = 256;
 constexpr int kNodeBlock = 64;
-
-__device__ inline float dot3(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
-__device__ inline void cross3(const float a[3], const float b[3], float o[3]) {
-  o[0] = fmaf(a[1], b[2], -(a[2] * b[1]));
-  o[1] = fmaf(a[2], b[0], -(a[0] * b[2]));
-  o[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
-}
-__device__ inline void normalize3(float v[3]) {
-  const float inv = 1.0f / sqrtf(dot3(v, v));
-  v[0] *= inv; v[1] *= inv; v[2] *= inv;
-}
-__device__ inline void mul_n(const float* N, const float v[3], float o[3]) {
-  o[0] = N[0] * v[0] + N[3] * v[1] + N[6] * v[2];
-  o[1] = N[1] * v[0] + N[4] * v[1] + N[7] * v[2];
-  o[2] = N[2] * v[0] + N[5] * v[1] + N[8] * v[2];
-}
-// order-preserving map float → uint32 (negative values below positive ones), for atomicMin / atomicMax
-__device__ inline uint32_t ordered(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
 __global__ void k_refit_init(uint32_t* bounds) {
   const uint32_t i = threadIdx.x;
@@ -41,23 +26,9 @@ __global__ __launch_bounds__(kBlock) void k_refit_flatten(const DevRefit r) {
   const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
   if (v >= r.n_verts) return;
   const uint32_t inst = r.vert_inst[v];
-  const float* m = r.inst_xf + (size_t)inst * 21;      // m[c*3 + row] = model[c*4 + row]
-  const float* N = m + 12;
-  const HostVertex s = r.mesh_verts[r.inst_src[inst] + (v - r.inst_first[inst])];
-  HostVertex d;
-  for (int k = 0; k < 3; ++k) d.position[k] = m[0 + k] * s.position[0] + m[3 + k] * s.position[1] + m[6 + k] * s.position[2] + m[9 + k];
-  mul_n(N, s.normal, d.normal);
-  normalize3(d.normal);
-  float t3[3];
-  mul_n(N, s.tangent, t3);
-  normalize3(t3);
-  d.tangent[0] = t3[0]; d.tangent[1] = t3[1]; d.tangent[2] = t3[2]; d.tangent[3] = s.tangent[3];
-  float cr[3], sc[3], bt[3];
-  cross3(s.normal, s.tangent, cr);
-  sc[0] = cr[0] * s.tangent[3]; sc[1] = cr[1] * s.tangent[3]; sc[2] = cr[2] * s.tangent[3];
-  mul_n(N, sc, bt);
-  normalize3(bt);
-  d.texcoord[0] = s.texcoord[0]; d.texcoord[1] = s.texcoord[1];
+  const float* m = r.inst_xf + (size_t)inst * 21;      // rows 0..2 of the model matrix column by column, then the normal matrix
+  float bt[3];
+  const HostVertex d = world_vertex(m, 3, m + 12, r.mesh_verts[r.inst_src[inst] + (v - r.inst_first[inst])], bt);
   r.wverts[v] = d;
   r.wbt[(size_t)v * 3 + 0] = bt[0]; r.wbt[(size_t)v * 3 + 1] = bt[1]; r.wbt[(size_t)v * 3 + 2] = bt[2];
   if (!(isfinite(d.position[0]) && isfinite(d.position[1]) && isfinite(d.position[2]))) atomicOr(&r.bounds[6], 1u);
@@ -75,21 +46,8 @@ __global__ __launch_bounds__(kBlock) void k_refit_prims(const DevRefit r) {
       hi[k] = fmaxf(hi[k], fmaxf(a.position[k], fmaxf(b.position[k], c.position[k])));
     }
     float4* o = r.shade + (size_t)p * r.shade_stride;
-    const float mat = o[0].w, light = o[1].w;        // material and emitter index of the primitive: not a refit's business
-    o[0] = make_float4(a.position[0], a.position[1], a.position[2], mat);
-    o[1] = make_float4(b.position[0], b.position[1], b.position[2], light);
-    o[2] = make_float4(c.position[0], c.position[1], c.position[2], a.normal[0]);
-    o[3] = make_float4(a.normal[1], a.normal[2], b.normal[0], b.normal[1]);
-    o[4] = make_float4(b.normal[2], c.normal[0], c.normal[1], c.normal[2]);
-    if (tex) {
-      const float* ba = r.wbt + (size_t)vi[0] * 3; const float* bb = r.wbt + (size_t)vi[1] * 3; const float* bc = r.wbt + (size_t)vi[2] * 3;
-      o[5] = make_float4(a.texcoord[0], a.texcoord[1], b.texcoord[0], b.texcoord[1]);
-      o[6] = make_float4(c.texcoord[0], c.texcoord[1], a.tangent[0], a.tangent[1]);
-      o[7] = make_float4(a.tangent[2], b.tangent[0], b.tangent[1], b.tangent[2]);
-      o[8] = make_float4(c.tangent[0], c.tangent[1], c.tangent[2], ba[0]);
-      o[9] = make_float4(ba[1], ba[2], bb[0], bb[1]);
-      o[10] = make_float4(bb[2], bc[0], bc[1], bc[2]);
-    }
+    // material and emitter index of the primitive: not a refit's business
+    shading_record(o, tex, a, b, c, r.wbt + (size_t)vi[0] * 3, r.wbt + (size_t)vi[1] * 3, r.wbt + (size_t)vi[2] * 3, __float_as_int(o[0].w), __float_as_int(o[1].w));
   }
   // scene box: min / max over finite values is the same number in any order (only the sign of a zero can differ, which nothing downstream reads)
   __shared__ float red[6][kBlock / 64];
@@ -101,34 +59,20 @@ __global__ __launch_bounds__(kBlock) void k_refit_prims(const DevRefit r) {
   if (threadIdx.x < 6) {
     float v = red[threadIdx.x][0];
     for (int w = 1; w < kBlock / 64; ++w) v = threadIdx.x < 3 ? fminf(v, red[threadIdx.x][w]) : fmaxf(v, red[threadIdx.x][w]);
-    if (threadIdx.x < 3) { if (v != INFINITY) atomicMin(&r.bounds[threadIdx.x], ordered(v)); }
-    else if (v != -INFINITY) atomicMax(&r.bounds[threadIdx.x], ordered(v));
+    if (threadIdx.x < 3) { if (v != INFINITY) atomicMin(&r.bounds[threadIdx.x], ordered_u(v)); }
+    else if (v != -INFINITY) atomicMax(&r.bounds[threadIdx.x], ordered_u(v));
   }
 }
 
-struct Box3 { float lo[3], hi[3]; };
-
-// box of the triangle whose record starts at unit `at` (the record's word 3 is its primitive id), as the host's tbox: < and > from +-inf over the vertices in order
-__device__ inline Box3 triangle_box(const DevRefit& r, uint32_t at, const float*& pa, const float*& pb, const float*& pc) {
+// the triangle whose record starts at unit `at` (the record's word 3 is its primitive id, word 7 its class: kept): its record rewritten, its box returned
+__device__ inline Box refit_triangle(const DevRefit& r, uint32_t at) {
   const uint32_t prim = __float_as_uint(r.recs[at].w);
-  pa = r.wverts[r.widx[(size_t)prim * 3 + 0]].position;
-  pb = r.wverts[r.widx[(size_t)prim * 3 + 1]].position;
-  pc = r.wverts[r.widx[(size_t)prim * 3 + 2]].position;
-  Box3 b;
-  for (int k = 0; k < 3; ++k) {
-    float l = INFINITY, h = -INFINITY;
-    l = pa[k] < l ? pa[k] : l; h = pa[k] > h ? pa[k] : h;
-    l = pb[k] < l ? pb[k] : l; h = pb[k] > h ? pb[k] : h;
-    l = pc[k] < l ? pc[k] : l; h = pc[k] > h ? pc[k] : h;
-    b.lo[k] = l; b.hi[k] = h;
-  }
-  return b;
-}
-__device__ inline void write_triangle(const DevRefit& r, uint32_t at, const float* a, const float* b, const float* c) {
-  const float w0 = r.recs[at].w, w1 = r.recs[at + 1].w;      // primitive id, material class
-  r.recs[at] = make_float4(a[0], a[1], a[2], w0);
-  r.recs[at + 1] = make_float4(b[0] - a[0], b[1] - a[1], b[2] - a[2], w1);
-  r.recs[at + 2] = make_float4(c[0] - a[0], c[1] - a[1], c[2] - a[2], 0.0f);
+  const float* a = r.wverts[r.widx[(size_t)prim * 3 + 0]].position;
+  const float* b = r.wverts[r.widx[(size_t)prim * 3 + 1]].position;
+  const float* c = r.wverts[r.widx[(size_t)prim * 3 + 2]].position;
+  const Box t = triangle_box(a, b, c);
+  tri_record(r.recs + at, a, b, c, prim, __float_as_uint(r.recs[at + 1].w));
+  return t;
 }
 
 // EIGHT lanes per node, one per child slot (round 4, second session).  One thread per node walked its eight slots one after the other: up to 16 triangles behind three dependent
@@ -142,16 +86,15 @@ __global__ __launch_bounds__(kNodeBlock) void k_refit_nodes(const DevRefit r, ui
   const int oct0 = (int)(threadIdx.x & 63u & ~7u);          // first lane of this octet inside the wave
   const bool live = i < count;                             // uniform over an octet
   unsigned long long my_cost = 0ull;
-  uint32_t addr = 0, imask = 0, lmask = 0, two = 0, block = 0, headz = 0;
+  uint32_t addr = 0, imask = 0, lmask = 0, two = 0, block = 0, masks = 0;
   if (live) {
     addr = r.level_nodes[first + i];
     const uint4 head = reinterpret_cast<const uint4*>(r.recs)[addr];
-    imask = (head.z >> 8) & 255u; lmask = (head.z >> 16) & 255u; two = (head.z >> 24) & 255u; block = head.w; headz = head.z;
+    imask = (head.z >> 8) & 255u; lmask = (head.z >> 16) & 255u; two = (head.z >> 24) & 255u; block = head.w; masks = node_masks_of(head.z);
   }
   const uint32_t used = imask | lmask;
   const bool mine = ((used >> sl) & 1u) != 0u;
-  Box3 b;
-  for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+  Box b = empty_box();
   if ((imask >> sl) & 1u) {
     const uint32_t child = block + 4u * (uint32_t)__popc(imask & ((1u << sl) - 1u));
     const float* nb = r.nbox + (size_t)(child >> 2) * 6;
@@ -160,14 +103,8 @@ __global__ __launch_bounds__(kNodeBlock) void k_refit_nodes(const DevRefit r, ui
     const uint32_t below = (1u << sl) - 1u;
     const uint32_t tris_below = (uint32_t)__popc(lmask & below) + (uint32_t)__popc(two & lmask & below);
     const uint32_t at = block + 4u * (uint32_t)__popc(imask) + 3u * tris_below;
-    const float *pa, *pb, *pc;
-    b = triangle_box(r, at, pa, pb, pc);
-    write_triangle(r, at, pa, pb, pc);
-    if ((two >> sl) & 1u) {
-      const Box3 b2 = triangle_box(r, at + 3u, pa, pb, pc);
-      write_triangle(r, at + 3u, pa, pb, pc);
-      for (int k = 0; k < 3; ++k) { b.lo[k] = b2.lo[k] < b.lo[k] ? b2.lo[k] : b.lo[k]; b.hi[k] = b2.hi[k] > b.hi[k] ? b2.hi[k] : b.hi[k]; }
-    }
+    b = refit_triangle(r, at);
+    if ((two >> sl) & 1u) grow(b, refit_triangle(r, at + 3u));
   }
   // the eight boxes of the node, in every lane of its octet
   float clo[3][8], chi[3][8];
@@ -189,69 +126,41 @@ __global__ __launch_bounds__(kNodeBlock) void k_refit_nodes(const DevRefit r, ui
       else { nlo = clo[k][j] < nlo ? clo[k][j] : nlo; nhi = chi[k][j] > nhi ? chi[k][j] : nhi; }
     }
     nbx[k] = nlo; nbx[3 + k] = nhi;
-    // origin on the 16-bit scene grid, rounded down
-    float fq = floorf((nlo - glo[k]) / gstep[k]);
-    if (fq < 0.0f) fq = 0.0f;
-    if (fq > 65535.0f) fq = 65535.0f;
-    uint32_t q16 = (uint32_t)fq;
-    while (q16 > 0u && fmaf((float)q16, gstep[k], glo[k]) > nlo) --q16;
-    oq[k] = q16;
-    const float org = fmaf((float)q16, gstep[k], glo[k]);
-    // 8-bit planes: the smallest power-of-two scale that covers the node, lower planes floored, upper planes ceiled, nudged until they bracket
-    const float f = (nhi - org) / 255.0f;
-    const uint32_t u = __float_as_uint(f);
-    uint32_t e = (u >> 23) & 255u;
-    if (u & 0x007fffffu) e += 1u;
-    if (e < 1u) e = 1u;
+    oq[k] = grid_origin(nlo, glo[k], gstep[k]);
+    const float org = grid_point(oq[k], glo[k], gstep[k]);
+    uint32_t e = first_plane_exponent(nhi, org);
     bool done = !live;
     uint32_t ql = 255u, qh = 0u;           // an empty slot
     for (;;) {
       bool ok = true;
       if (!done && mine) {
-        const float sc = __uint_as_float(e << 23);
-        float fl = floorf((b.lo[k] - org) / sc);
-        if (fl < 0.0f) fl = 0.0f;
-        if (fl > 255.0f) fl = 255.0f;
-        int q = (int)fl;
-        while (q > 0 && org + (float)q * sc > b.lo[k]) --q;
-        ql = (uint32_t)q;
-        float ce = ceilf((b.hi[k] - org) / sc);
-        if (ce < 0.0f) ce = 0.0f;
-        if (ce > 255.0f) { ok = false; ce = 255.0f; }
-        int q2 = (int)ce;
-        while (q2 < 255 && org + (float)q2 * sc < b.hi[k]) ++q2;
-        if (org + (float)q2 * sc < b.hi[k]) ok = false;
-        qh = (uint32_t)q2;
+        const Planes q = quantize_planes(b.lo[k], b.hi[k], org, e);
+        ql = q.ql; qh = q.qh; ok = q.fits;
       }
       const unsigned long long verdict = __ballot(done || ok);
       if (!done) { if (((verdict >> oct0) & 0xffull) == 0xffull) done = true; else ++e; }
       if (!__ballot(!done)) break;
     }
     e3[k] = e;
-    uint32_t pl[2] = {0u, 0u}, ph[2] = {0u, 0u};
+    uint32_t pl[8], ph[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t a = (uint32_t)__shfl((int)ql, oct0 + j), c = (uint32_t)__shfl((int)qh, oct0 + j);
-      pl[j >> 2] |= a << (8 * (j & 3));
-      ph[j >> 2] |= c << (8 * (j & 3));
-    }
-    wlo[k][0] = pl[0]; wlo[k][1] = pl[1]; whi[k][0] = ph[0]; whi[k][1] = ph[1];
+    for (int j = 0; j < 8; ++j) { pl[j] = (uint32_t)__shfl((int)ql, oct0 + j); ph[j] = (uint32_t)__shfl((int)qh, oct0 + j); }
+    wlo[k][0] = pack4(pl[0], pl[1], pl[2], pl[3]); wlo[k][1] = pack4(pl[4], pl[5], pl[6], pl[7]);
+    whi[k][0] = pack4(ph[0], ph[1], ph[2], ph[3]); whi[k][1] = pack4(ph[4], ph[5], ph[6], ph[7]);
   }
   if (live && sl == 0u) {
     uint4* out = reinterpret_cast<uint4*>(r.recs) + addr;
-    out[0] = make_uint4(oq[0] | (oq[1] << 16), oq[2] | (e3[0] << 16) | (e3[1] << 24), e3[2] | (headz & 0xffffff00u), block);
+    uint32_t w[3];
+    node_header(oq, e3, masks, w);
+    out[0] = make_uint4(w[0], w[1], w[2], block);
     out[1] = make_uint4(wlo[0][0], wlo[0][1], wlo[1][0], wlo[1][1]);
     out[2] = make_uint4(wlo[2][0], wlo[2][1], whi[0][0], whi[0][1]);
     out[3] = make_uint4(whi[1][0], whi[1][1], whi[2][0], whi[2][1]);
     float* nb = r.nbox + (size_t)(addr >> 2) * 6;
     for (int k = 0; k < 6; ++k) nb[k] = nbx[k];
   }
-  // surface-area cost of this node's children (ptc_stats.bvh_sa_cost): half_area(child) / half_area(scene) per used slot, a two-triangle leaf twice
-  if (live && mine && scene_area > 0.0f) {
-    const float ex = b.hi[0] - b.lo[0], ey = b.hi[1] - b.lo[1], ez = b.hi[2] - b.lo[2];
-    const unsigned long long term = (unsigned long long)(((ex * ey + ey * ez + ez * ex) / scene_area) * PTC_SA_COST_ONE);
-    my_cost = ((two >> sl) & 1u) ? 2ull * term : term;
-  }
+  // surface-area cost of this node's children (ptc_stats.bvh_sa_cost): one term per used slot
+  if (live && mine && scene_area > 0.0f) my_cost = sa_cost_term(b, scene_area, ((two >> sl) & 1u) != 0u);
   // one atomic per wave (a block is one wave): integer sum, the same bits in any order
   for (int d = 32; d >= 1; d >>= 1) my_cost += __shfl_xor(my_cost, d);
   if ((threadIdx.x & 63) == 0 && my_cost) atomicAdd(r.cost, my_cost);
@@ -281,13 +190,7 @@ void pt_launch_refit_geometry(hipStream_t st, const DevRefit& r) {
 }
 
 void pt_refit_decode_bounds(const uint32_t raw[8], float lo[3], float hi[3], bool* non_finite) {
-  for (int k = 0; k < 6; ++k) {
-    const uint32_t enc = raw[k];
-    const uint32_t u = (enc & 0x80000000u) ? (enc ^ 0x80000000u) : ~enc;
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    (k < 3 ? lo[k] : hi[k - 3]) = f;
-  }
+  for (int k = 0; k < 6; ++k) (k < 3 ? lo[k] : hi[k - 3]) = unordered_f(raw[k]);
   *non_finite = raw[6] != 0u;
 }
 

@@ -2,6 +2,7 @@
 //
 // Three parts: the helpers of this file, what the other ptc_api*.cpp files call of it (declared in ptc_ctx.h), the C-ABI.
 #include "ptc_ctx.h"
+#include "pt_scene_rules.h"
 
 #include <map>
 #include <mutex>
@@ -239,11 +240,6 @@ int ensure_refit_plan(ptc_ctx* c) {
 
 const char* const kNonFinite = "scene_commit: non-finite vertex position after the instance transform";
 
-float scene_half_area(const float lo[3], const float hi[3]) {      // the host's box_half_area of the scene box
-  const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-  return ex * ey + ey * ez + ez * ex;
-}
-
 // What the geometry pass hands on: the instance transforms, the emitter table of the moved scene, the scene box
 struct Moved { std::vector<float> xf, lights, cdf; float lo[3], hi[3]; };
 
@@ -327,7 +323,7 @@ int device_build(ptc_ctx* c, int builder, const Moved& m) {
   use_live_tree(c);
   s.plan.level_first = out.level_first; s.plan.level_nodes.clear();
   HostBuilt& B = *c->built;
-  B.sa_unit = scene_half_area(m.lo, m.hi);                  // a new topology: a new unit of its cost
+  B.sa_unit = scene_rules::half_area(m.lo, m.hi);                  // a new topology: a new unit of its cost
   B.n_nodes = out.n_nodes; B.n_units = out.n_units; B.max_depth = out.max_depth; B.n_tri_records = out.n_tri_records;
   B.n_lds_units = B.n_units < c->toplet_budget * 4u ? B.n_units : c->toplet_budget * 4u;
   B.recs.clear();                       // refresh_host_copy sizes and fills them when somebody asks

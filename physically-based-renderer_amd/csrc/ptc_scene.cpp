@@ -9,9 +9,12 @@
 //   R4  world-space N/T                assets/shaders/geometry_pass/vertex.glsl:25-36
 //   R5  camera basis                   src/pbr_engine/engine/pbr/CameraData.hpp:22-32
 // Everything is plain IEEE binary32 without contraction (this file is compiled -ffp-contract=off),
-// so the flattened scene is reproducible bit for bit.
+// so the flattened scene is reproducible bit for bit.  Every value that the device builders compute too (pt_refit.hip, pt_build.hip) is a function of
+// pt_scene_rules.h, called from both sides; what stands here is the host's order of work: containers, stages, the pool.
 #include "ptc_internal.h"
 #include "pt_refit.h"
+#include "pt_scene_rules.h"
+using namespace scene_rules;
 
 #include <algorithm>
 #include <atomic>
@@ -152,10 +155,10 @@ template <class F> void parallel_for(size_t n, size_t min_chunk, F&& fn) {
   });
 }
 
-constexpr int kLeafMax = 2;
-constexpr int kWide = 8;      // child slots per BVH node
 constexpr int kNodeWords = 16; // 64-byte node = 4 units of 16 bytes
-constexpr float kCostNode = 1.0f, kCostPrim = 1.0f;   // surface-area cost of one node visit / one triangle test (collapse)
+// tri_record and shading_record write whole float4 units into HostBuilt::recs / ::shade (vectors of float, every record at a multiple of 4 floats): the vectors' storage
+// comes from operator new, which must be aligned for a float4
+static_assert(alignof(float4) <= __STDCPP_DEFAULT_NEW_ALIGNMENT__, "std::vector<float> storage is not aligned for float4 records");
 constexpr int kTile = 32;
 
 struct Mat34 { float m[16]; float n[9]; };  // column-major model (glm layout) + normal matrix
@@ -186,32 +189,6 @@ Mat34 from_matrix(const float m[16]) {
   return r;
 }
 
-inline float fdot(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
-inline void fcross(const float a[3], const float b[3], float o[3]) {
-  o[0] = fmaf(a[1], b[2], -(a[2] * b[1]));
-  o[1] = fmaf(a[2], b[0], -(a[0] * b[2]));
-  o[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
-}
-inline void fnormalize(float v[3]) {
-  const float inv = 1.0f / sqrtf(fdot(v, v));
-  v[0] *= inv; v[1] *= inv; v[2] *= inv;
-}
-inline void mul_n(const float N[9], const float v[3], float o[3]) {
-  o[0] = N[0] * v[0] + N[3] * v[1] + N[6] * v[2];
-  o[1] = N[1] * v[0] + N[4] * v[1] + N[7] * v[2];
-  o[2] = N[2] * v[0] + N[5] * v[1] + N[8] * v[2];
-}
-
-struct Box { float lo[3], hi[3]; };
-inline Box empty_box() {
-  Box b;
-  for (int k = 0; k < 3; ++k) { b.lo[k] = std::numeric_limits<float>::infinity(); b.hi[k] = -std::numeric_limits<float>::infinity(); }
-  return b;
-}
-inline void grow(Box& b, const Box& o) {
-  for (int k = 0; k < 3; ++k) { b.lo[k] = o.lo[k] < b.lo[k] ? o.lo[k] : b.lo[k]; b.hi[k] = o.hi[k] > b.hi[k] ? o.hi[k] : b.hi[k]; }
-}
-
 // ---- binary tree by top-down binned surface-area splits -------------------------------------------------
 // SplitNode covers positions [lo,hi] of `ord`; child >= 0: node index; < 0: ~position of a single triangle.
 // Per range: kSahBins equal bins over the centroid bounds on each axis, cost = half_area(L)·nL + half_area(R)·nR,
@@ -219,38 +196,22 @@ inline void grow(Box& b, const Box& o) {
 // centroids → cut at the middle index.  The binary tree goes down to single triangles; which subtrees become the
 // wide tree's leaves is decided by the collapse (ptc_build_scene).
 struct SplitNode { uint32_t lo, hi; int32_t left, right; };
-constexpr int kSahBins = 32;
-
-inline float box_half_area(const Box& b) {
-  const float ex = b.hi[0] - b.lo[0], ey = b.hi[1] - b.lo[1], ez = b.hi[2] - b.lo[2];
-  return ex * ey + ey * ez + ez * ex;
-}
-
 // ---- LBVH option (BASELINE north_star's "flattened LBVH"): the binary tree is the radix tree of 63-bit Morton codes ------------
 // Per axis q = (uint32)((centre - cl) * (2^21 / (ch - cl))) clamped to 2^21 - 1 over the bounds cl..ch of all box centres (0 on a
 // degenerate axis); x in bit 0, y in bit 1, z in bit 2 of each triple.  Positions are ordered by (code, primitive id); the tree is the radix
 // tree of the keys (code, sorted position): a range splits where the highest bit in which its end KEYS differ turns 1 — a bit of the code or,
 // in a range of one code, of the position — so that every internal node can be found on its own (the device build, pt_build.hip).
-inline uint64_t spread_bits_3(uint32_t v) {
-  uint64_t r = 0;
-  for (int b = 0; b < 21; ++b) r |= (uint64_t)((v >> b) & 1u) << (3 * b);
-  return r;
-}
 std::vector<uint64_t> sort_by_morton_code(const std::vector<float>& ctr, std::vector<uint32_t>& ord) {
   const uint32_t n = (uint32_t)ord.size();
   float cl[3], ch[3], scale[3];
   for (int k = 0; k < 3; ++k) { cl[k] = std::numeric_limits<float>::infinity(); ch[k] = -cl[k]; }
   for (uint32_t p = 0; p < n; ++p)
     for (int k = 0; k < 3; ++k) { const float c = ctr[(size_t)p * 3 + k]; cl[k] = cl[k] < c ? cl[k] : c; ch[k] = ch[k] > c ? ch[k] : c; }
-  for (int k = 0; k < 3; ++k) scale[k] = ch[k] > cl[k] ? 2097152.0f / (ch[k] - cl[k]) : 0.0f;
+  for (int k = 0; k < 3; ++k) scale[k] = cell_scale(cl[k], ch[k], kMortonCells);
   std::vector<std::pair<uint64_t, uint32_t>> keyed(n);
   for (uint32_t p = 0; p < n; ++p) {
     uint64_t code = 0;
-    for (int k = 0; k < 3; ++k) {
-      const float f = (ctr[(size_t)p * 3 + k] - cl[k]) * scale[k];
-      const uint32_t q = f >= 2097151.0f ? 2097151u : (uint32_t)f;
-      code |= spread_bits_3(q) << k;
-    }
+    for (int k = 0; k < 3; ++k) code |= morton_axis(ctr[(size_t)p * 3 + k], cl[k], scale[k]) << k;
     keyed[p] = {code, p};
   }
   std::sort(keyed.begin(), keyed.end());
@@ -270,139 +231,122 @@ inline uint32_t morton_last_left(const std::vector<uint64_t>& codes, uint32_t lo
   return (uint32_t)(first_set - codes.begin()) - 1u;
 }
 
+// The bounds of a range's centres with the bin scale of every axis, and the sweep that finds the cheapest cut of one axis from its complete bins: what split_range
+// makes in one go and split_range_parallel per chunk, merged (minima, maxima and counts: the same in any order, only the sign of a zero can differ, which no area
+// and no comparison reads).
+struct SahAxes {
+  float cl[3], ch[3], scale[3];
+  SahAxes() { for (int k = 0; k < 3; ++k) { cl[k] = std::numeric_limits<float>::infinity(); ch[k] = -cl[k]; scale[k] = 0.0f; } }
+  void add(const float* lo, const float* hi) { for (int k = 0; k < 3; ++k) { cl[k] = cl[k] < lo[k] ? cl[k] : lo[k]; ch[k] = ch[k] > hi[k] ? ch[k] : hi[k]; } }
+  void close() { for (int k = 0; k < 3; ++k) scale[k] = cell_scale(cl[k], ch[k], (float)kSahBins); }
+  bool on(int k) const { return ch[k] > cl[k]; }
+  int bin(int k, const float* c) const { return sah_bin(c[k], cl[k], scale[k]); }
+};
+struct Bin { Box box; uint32_t count; };
+inline void clear_bins(Bin* bins, int n) { for (int j = 0; j < n; ++j) { bins[j].box = empty_box(); bins[j].count = 0; } }
+struct SahCut { int axis = -1, bin = 0; float cost = std::numeric_limits<float>::infinity(); };      // axis < 0: no axis has a candidate (coincident centres)
+// the cuts of axis k: strictly cheaper wins, so ties go to the lowest axis, then the lowest boundary
+void sweep_axis(const Bin* bins, int k, SahCut& best) {
+  float best_cost = best.cost;
+  float suffix_area[kSahBins];
+  uint32_t suffix_count[kSahBins];
+  Box acc = empty_box();
+  uint32_t cnt = 0;
+  for (int j = kSahBins - 1; j >= 1; --j) {
+    cnt += bins[j].count;
+    grow(acc, bins[j].box);
+    suffix_count[j] = cnt;
+    suffix_area[j] = sah_suffix_area(acc, cnt);
+  }
+  acc = empty_box();
+  cnt = 0;
+  for (int j = 0; j + 1 < kSahBins; ++j) {
+    cnt += bins[j].count;
+    grow(acc, bins[j].box);
+    if (cnt == 0 || suffix_count[j + 1] == 0) continue;
+    const float cost = sah_cut_cost(acc, cnt, suffix_area[j + 1], suffix_count[j + 1]);
+    if (cost < best_cost) { best_cost = cost; best.axis = k; best.bin = j; }
+  }
+  best.cost = best_cost;
+}
+
 // Where the range [lo, hi] of `ord` is cut: returns the last position of the left part (the SAH path partitions ord[lo..hi] in place, stably; `scratch`
 // holds hi - lo + 1 entries).  A pure function of the range's content, so disjoint ranges can be cut by different threads.
 uint32_t split_range(const std::vector<Box>& tbox, const std::vector<float>& ctr, const std::vector<uint64_t>& codes, bool lbvh, std::vector<uint32_t>& ord,
                      uint32_t* scratch, uint32_t lo, uint32_t hi) {
   if (lbvh) return morton_last_left(codes, lo, hi);
-  struct Bin { Box box; uint32_t count; };
-  float cl[3], ch[3];
-  for (int k = 0; k < 3; ++k) { cl[k] = std::numeric_limits<float>::infinity(); ch[k] = -cl[k]; }
-  for (uint32_t i = lo; i <= hi; ++i) {
-    const float* c = &ctr[(size_t)ord[i] * 3];
-    for (int k = 0; k < 3; ++k) { cl[k] = cl[k] < c[k] ? cl[k] : c[k]; ch[k] = ch[k] > c[k] ? ch[k] : c[k]; }
-  }
-  float best_cost = std::numeric_limits<float>::infinity();
-  int best_axis = -1, best_bin = 0;
+  SahAxes ax;
+  for (uint32_t i = lo; i <= hi; ++i) { const float* c = &ctr[(size_t)ord[i] * 3]; ax.add(c, c); }
+  ax.close();
+  SahCut cut;
   for (int k = 0; k < 3; ++k) {
-    if (!(ch[k] > cl[k])) continue;
-    const float scale = (float)kSahBins / (ch[k] - cl[k]);
+    if (!ax.on(k)) continue;
     Bin bins[kSahBins];
-    for (Bin& bn : bins) { bn.box = empty_box(); bn.count = 0; }
+    clear_bins(bins, kSahBins);
+    const float c0 = ax.cl[k], sc = ax.scale[k];
     for (uint32_t i = lo; i <= hi; ++i) {
       const uint32_t p = ord[i];
-      int j = (int)((ctr[(size_t)p * 3 + k] - cl[k]) * scale);
-      j = j > kSahBins - 1 ? kSahBins - 1 : j;
-      bins[j].count++;
-      grow(bins[j].box, tbox[p]);
+      Bin& b = bins[sah_bin(ctr[(size_t)p * 3 + k], c0, sc)];
+      b.count++;
+      grow(b.box, tbox[p]);
     }
-    float suffix_area[kSahBins];
-    uint32_t suffix_count[kSahBins];
-    Box acc = empty_box();
-    uint32_t cnt = 0;
-    for (int j = kSahBins - 1; j >= 1; --j) {
-      cnt += bins[j].count;
-      grow(acc, bins[j].box);
-      suffix_count[j] = cnt;
-      suffix_area[j] = cnt ? box_half_area(acc) : 0.0f;
-    }
-    acc = empty_box();
-    cnt = 0;
-    for (int j = 0; j + 1 < kSahBins; ++j) {
-      cnt += bins[j].count;
-      grow(acc, bins[j].box);
-      if (cnt == 0 || suffix_count[j + 1] == 0) continue;
-      const float cost = box_half_area(acc) * (float)cnt + suffix_area[j + 1] * (float)suffix_count[j + 1];
-      if (cost < best_cost) { best_cost = cost; best_axis = k; best_bin = j; }
-    }
+    sweep_axis(bins, k, cut);
   }
-  if (best_axis < 0) return lo + (hi - lo) / 2;
-  const float scale = (float)kSahBins / (ch[best_axis] - cl[best_axis]);
+  if (cut.axis < 0) return lo + (hi - lo) / 2;
+  const float c0 = ax.cl[cut.axis], sc = ax.scale[cut.axis];
   uint32_t nl = 0, nr = 0;
   for (uint32_t i = lo; i <= hi; ++i) {
     const uint32_t p = ord[i];
-    int j = (int)((ctr[(size_t)p * 3 + best_axis] - cl[best_axis]) * scale);
-    j = j > kSahBins - 1 ? kSahBins - 1 : j;
-    if (j <= best_bin) ord[lo + nl++] = p; else scratch[nr++] = p;
+    if (sah_bin(ctr[(size_t)p * 3 + cut.axis], c0, sc) <= cut.bin) ord[lo + nl++] = p; else scratch[nr++] = p;
   }
   std::copy(scratch, scratch + nr, ord.begin() + lo + nl);
   return lo + nl - 1;
 }
 
 // split_range for a LARGE range, its passes spread over the pool (the top of the tree is a handful of such ranges and everything else waits for them).
-// Same cut: bounds and bins are minima / maxima / counts — the same in any order (only the sign of a zero can differ, and areas and comparisons do not read
-// it) — and the partition keeps the order of both parts (per-chunk counts, exclusive prefix, every chunk writes its own stretch of the scratch buffer).
+// Same cut: the chunks' bounds and bins merge to the range's, and the partition keeps the order of both parts (per-chunk counts, exclusive prefix, every chunk
+// writes its own stretch of the scratch buffer).
 uint32_t split_range_parallel(const std::vector<Box>& tbox, const std::vector<float>& ctr, std::vector<uint32_t>& ord, uint32_t* scratch, uint32_t lo, uint32_t hi) {
-  struct Bin { Box box; uint32_t count; };
   const size_t n = (size_t)hi - lo + 1;
   const size_t nc = std::min<size_t>((size_t)HostPool::get().size() * 2, n / 8192);
   const size_t per = (n + nc - 1) / nc;
   auto chunk = [&](size_t c, size_t& a, size_t& b) { a = lo + c * per; b = std::min<size_t>(a + per, (size_t)hi + 1); };
-  struct Bounds { float cl[3], ch[3]; };
-  std::vector<Bounds> cb(nc);
+  std::vector<SahAxes> cb(nc);
   HostPool::get().run(nc, [&](size_t c) {
     size_t a, b; chunk(c, a, b);
-    Bounds r;
-    for (int k = 0; k < 3; ++k) { r.cl[k] = std::numeric_limits<float>::infinity(); r.ch[k] = -r.cl[k]; }
-    for (size_t i = a; i < b; ++i) {
-      const float* q = &ctr[(size_t)ord[i] * 3];
-      for (int k = 0; k < 3; ++k) { r.cl[k] = r.cl[k] < q[k] ? r.cl[k] : q[k]; r.ch[k] = r.ch[k] > q[k] ? r.ch[k] : q[k]; }
-    }
+    SahAxes r;
+    for (size_t i = a; i < b; ++i) { const float* q = &ctr[(size_t)ord[i] * 3]; r.add(q, q); }
     cb[c] = r;
   });
-  float cl[3], ch[3];
-  for (int k = 0; k < 3; ++k) { cl[k] = std::numeric_limits<float>::infinity(); ch[k] = -cl[k]; }
-  for (const Bounds& r : cb)
-    for (int k = 0; k < 3; ++k) { cl[k] = cl[k] < r.cl[k] ? cl[k] : r.cl[k]; ch[k] = ch[k] > r.ch[k] ? ch[k] : r.ch[k]; }
-  float scale[3];
-  for (int k = 0; k < 3; ++k) scale[k] = ch[k] > cl[k] ? (float)kSahBins / (ch[k] - cl[k]) : 0.0f;
+  SahAxes ax;
+  for (const SahAxes& r : cb) ax.add(r.cl, r.ch);
+  ax.close();
   std::vector<Bin> part(nc * 3 * kSahBins);
   HostPool::get().run(nc, [&](size_t c) {
     size_t a, b; chunk(c, a, b);
     Bin* bins = &part[c * 3 * kSahBins];
-    for (int j = 0; j < 3 * kSahBins; ++j) { bins[j].box = empty_box(); bins[j].count = 0; }
+    clear_bins(bins, 3 * kSahBins);
     for (size_t i = a; i < b; ++i) {
       const uint32_t p = ord[i];
       for (int k = 0; k < 3; ++k) {
-        if (!(ch[k] > cl[k])) continue;
-        int j = (int)((ctr[(size_t)p * 3 + (size_t)k] - cl[k]) * scale[k]);
-        j = j > kSahBins - 1 ? kSahBins - 1 : j;
-        bins[k * kSahBins + j].count++;
-        grow(bins[k * kSahBins + j].box, tbox[p]);
+        if (!ax.on(k)) continue;
+        Bin& bn = bins[k * kSahBins + ax.bin(k, &ctr[(size_t)p * 3])];
+        bn.count++;
+        grow(bn.box, tbox[p]);
       }
     }
   });
-  float best_cost = std::numeric_limits<float>::infinity();
-  int best_axis = -1, best_bin = 0;
+  SahCut cut;
   for (int k = 0; k < 3; ++k) {
-    if (!(ch[k] > cl[k])) continue;
+    if (!ax.on(k)) continue;
     Bin bins[kSahBins];
-    for (Bin& bn : bins) { bn.box = empty_box(); bn.count = 0; }
+    clear_bins(bins, kSahBins);
     for (size_t c = 0; c < nc; ++c)
       for (int j = 0; j < kSahBins; ++j) { const Bin& o = part[(c * 3 + (size_t)k) * kSahBins + (size_t)j]; if (o.count) { bins[j].count += o.count; grow(bins[j].box, o.box); } }
-    float suffix_area[kSahBins];
-    uint32_t suffix_count[kSahBins];
-    Box acc = empty_box();
-    uint32_t cnt = 0;
-    for (int j = kSahBins - 1; j >= 1; --j) {
-      cnt += bins[j].count;
-      grow(acc, bins[j].box);
-      suffix_count[j] = cnt;
-      suffix_area[j] = cnt ? box_half_area(acc) : 0.0f;
-    }
-    acc = empty_box();
-    cnt = 0;
-    for (int j = 0; j + 1 < kSahBins; ++j) {
-      cnt += bins[j].count;
-      grow(acc, bins[j].box);
-      if (cnt == 0 || suffix_count[j + 1] == 0) continue;
-      const float cost = box_half_area(acc) * (float)cnt + suffix_area[j + 1] * (float)suffix_count[j + 1];
-      if (cost < best_cost) { best_cost = cost; best_axis = k; best_bin = j; }
-    }
+    sweep_axis(bins, k, cut);
   }
-  if (best_axis < 0) return lo + (hi - lo) / 2;
-  const float sc = scale[best_axis], c0 = cl[best_axis];
-  auto goes_left = [&](uint32_t p) { int j = (int)((ctr[(size_t)p * 3 + (size_t)best_axis] - c0) * sc); j = j > kSahBins - 1 ? kSahBins - 1 : j; return j <= best_bin; };
+  if (cut.axis < 0) return lo + (hi - lo) / 2;
+  auto goes_left = [&](uint32_t p) { return ax.bin(cut.axis, &ctr[(size_t)p * 3]) <= cut.bin; };
   std::vector<uint32_t> nleft(nc + 1, 0u);
   HostPool::get().run(nc, [&](size_t c) {
     size_t a, b; chunk(c, a, b);
@@ -459,7 +403,7 @@ void build_split_tree(const std::vector<Box>& tbox, std::vector<uint32_t>& ord, 
   std::vector<float> ctr((size_t)n * 3);
   parallel_for(n, 16384, [&](size_t p0, size_t p1) {
     for (size_t p = p0; p < p1; ++p)
-      for (int k = 0; k < 3; ++k) ctr[p * 3 + (size_t)k] = 0.5f * (tbox[p].lo[k] + tbox[p].hi[k]);
+      for (int k = 0; k < 3; ++k) ctr[p * 3 + (size_t)k] = centre(tbox[p], k);
   });
   std::vector<uint64_t> codes;
   if (lbvh) codes = sort_by_morton_code(ctr, ord);
@@ -508,8 +452,6 @@ void build_split_tree(const std::vector<Box>& tbox, std::vector<uint32_t>& ord, 
   }
 }
 
-inline int32_t leaf_code(uint32_t first, uint32_t count) { return (int32_t) ~(first | ((count - 1u) << 28)); }
-
 // ---- what a refit keeps (HostBuilt::topology): the order of the triangles, the binary tree they were split into, which of its
 // subtrees the 8-wide nodes took as children and in which slots, and where every node and children block lies in the unit array.
 // ptc_refit_scene recomputes everything that depends on vertex positions — boxes, quantised planes, triangle and shading records, emitters —
@@ -550,14 +492,9 @@ void ptc_trs_to_matrix(const float t[3], const float q[4], const float s[3], flo
 
 void ptc_make_camera(const float pos[3], const float target[3], float fov, float aspect, DevCamera& cam) {
   // glm::lookAtRH(pos, target, up = (0,-1,0)): f = normalize(target-pos), s = normalize(f × up), u = s × f
-  float f[3] = {target[0] - pos[0], target[1] - pos[1], target[2] - pos[2]};
-  fnormalize(f);
-  const float up[3] = {0.0f, -1.0f, 0.0f};
-  float s[3], u[3];
-  fcross(f, up, s);
-  fnormalize(s);
-  fcross(s, f, u);
-  for (int k = 0; k < 3; ++k) { cam.pos[k] = pos[k]; cam.f[k] = f[k]; cam.s[k] = s[k]; cam.u[k] = u[k]; }
+  const v3 f = normalize3(V3(target[0] - pos[0], target[1] - pos[1], target[2] - pos[2]));
+  const v3 s = normalize3(cross3(f, V3(0.0f, -1.0f, 0.0f)));
+  store3(cam.pos, V3(pos)); store3(cam.f, f); store3(cam.s, s); store3(cam.u, cross3(s, f));
   const float th = (float)std::tan((double)fov * 0.5);   // 1/proj[1][1] of glm::perspectiveRH_NO
   cam.sy = th;
   cam.sx = aspect * th;
@@ -612,11 +549,6 @@ uint32_t shade_stride_for(const std::vector<HostMaterial>& mats) {
   for (const auto& m : mats) any_tex = any_tex || m.tex_color >= 0 || m.tex_normal >= 0 || m.tex_mr >= 0;
   return any_tex ? 12u : 5u;
 }
-// model matrix times (position, 1): m[0]*x + m[1]*y + m[2]*z + m[3] — the flatten's expression, which the emitter table and the device flatten repeat bit for bit
-inline void transform_point(const Mat34& M, const float s[3], float o[3]) {
-  for (int r = 0; r < 3; ++r) o[r] = M.m[0 + r] * s[0] + M.m[4 + r] * s[1] + M.m[8 + r] * s[2] + M.m[12 + r];
-}
-constexpr float kGridCells = 65535.0f;      // node origins are 16 bits per axis on a grid over the scene box (ptc_refit_grid, grid_origin)
 void fill_materials(const std::vector<HostMaterial>& mats, const std::vector<int32_t>& mat_set, HostBuilt& B) {
   B.mats.assign(mats.size() * 16, 0.0f);
   for (size_t i = 0; i < mats.size(); ++i) {
@@ -791,12 +723,12 @@ int emitters_from_prims(const std::vector<HostMaterial>& mats, const std::vector
     const HostMaterial& m = mats[(size_t)mesh.material];
     if (e[1] != cached_inst) { M = from_matrix(insts[(size_t)e[1]].m); cached_inst = e[1]; }
     float w[3][3];
-    for (int c = 0; c < 3; ++c) transform_point(M, mesh.v[(size_t)e[2 + c]].position, w[c]);
+    for (int c = 0; c < 3; ++c) store3(w[c], transform_point(M.m, 4, V3(mesh.v[(size_t)e[2 + c]].position)));      // the flatten's expression
     const float *a = w[0], *b = w[1], *c = w[2];
     const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
     float cr[3];
-    fcross(e1, e2, cr);
-    const float len = sqrtf(fdot(cr, cr));
+    store3(cr, cross3(V3(e1), V3(e2)));
+    const float len = pt_sqrt(dot3(V3(cr), V3(cr)));
     const float area = 0.5f * len;
     const float lum = fmaf(m.emissive[2], 0.0722f, fmaf(m.emissive[1], 0.7152f, m.emissive[0] * 0.2126f));
     const float wgt = area * lum;
@@ -863,27 +795,6 @@ void fill_emitters(const std::vector<HostMaterial>& mats, const std::vector<Host
 // Layout: blocks breadth-first until `toplet_budget` 64-byte records exist (the trace kernels stage that prefix in LDS),
 // then depth-first.
 
-// slot_of[i]: the slot of child i of n (see above)
-void assign_slots(const WChild* kid, int n, int* slot_of) {
-  Box nb = empty_box();
-  for (int i = 0; i < n; ++i) grow(nb, kid[i].box);
-  float d[kWide][3];
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < 3; ++k) d[i][k] = 0.5f * (kid[i].box.lo[k] + kid[i].box.hi[k]) - 0.5f * (nb.lo[k] + nb.hi[k]);
-  bool child_done[kWide] = {false}, slot_used[kWide] = {false};
-  for (int round = 0; round < n; ++round) {
-    int bi = -1, bs = -1; float bsc = 0.0f;
-    for (int i = 0; i < n; ++i) {
-      if (child_done[i]) continue;
-      for (int sl = 0; sl < kWide; ++sl) {
-        if (slot_used[sl]) continue;
-        const float sc = ((sl & 1) ? d[i][0] : -d[i][0]) + ((sl & 2) ? d[i][1] : -d[i][1]) + ((sl & 4) ? d[i][2] : -d[i][2]);
-        if (bi < 0 || sc > bsc) { bi = i; bs = sl; bsc = sc; }
-      }
-    }
-    child_done[bi] = true; slot_used[bs] = true; slot_of[bi] = bs;
-  }
-}
 Wide make_wide(const WChild* kid, int n) {
   int slot_of[kWide];
   assign_slots(kid, n, slot_of);
@@ -893,62 +804,25 @@ Wide make_wide(const WChild* kid, int n) {
   for (int i = 0; i < n; ++i) { w.slot[slot_of[i]] = kid[i]; w.used[slot_of[i]] = true; }
   return w;
 }
-// 8-bit quantisation of the children's [lo,hi] on one axis against the node's [org, nhi]: scale 2^(e-127)
-// is the smallest power of two with (nhi-org)/scale <= 255; lower planes floor, upper planes ceil, each
-// nudged until the float expression org + q*scale brackets the exact plane.
-inline float pow2_biased(uint32_t e) { const uint32_t u = e << 23; float f; std::memcpy(&f, &u, 4); return f; }
+// 8-bit quantisation of the children's [lo,hi] on one axis against the node's [org, nhi]: the first exponent at which every child fits
 void quantize_axis(const float* clo, const float* chi, int nk, float org, float nhi, uint32_t& e_out, uint32_t* qlo, uint32_t* qhi) {
-  const float f = (nhi - org) / 255.0f;
-  uint32_t u; std::memcpy(&u, &f, 4);
-  uint32_t e = (u >> 23) & 255u;
-  if (u & 0x007fffffu) e += 1u;
-  if (e < 1u) e = 1u;
-  for (;; ++e) {
-    const float sc = pow2_biased(e);
+  for (uint32_t e = first_plane_exponent(nhi, org);; ++e) {
     bool ok = true;
     for (int i = 0; i < nk && ok; ++i) {
-      float fl = std::floor((clo[i] - org) / sc);
-      if (fl < 0.0f) fl = 0.0f;
-      if (fl > 255.0f) fl = 255.0f;
-      int q = (int)fl;
-      while (q > 0 && org + (float)q * sc > clo[i]) --q;
-      qlo[i] = (uint32_t)q;
-      float ce = std::ceil((chi[i] - org) / sc);
-      if (ce < 0.0f) ce = 0.0f;
-      if (ce > 255.0f) { ok = false; break; }
-      int q2 = (int)ce;
-      while (q2 < 255 && org + (float)q2 * sc < chi[i]) ++q2;
-      if (org + (float)q2 * sc < chi[i]) { ok = false; break; }
-      qhi[i] = (uint32_t)q2;
+      const Planes q = quantize_planes(clo[i], chi[i], org, e);
+      qlo[i] = q.ql; qhi[i] = q.qh; ok = q.fits;
     }
-    if (ok) break;
+    if (ok) { e_out = e; return; }
   }
-  e_out = e;
 }
-// a node's origin on the 16-bit scene grid, rounded down: the largest q with fmaf(q, step, lo) <= the node's lower bound
-uint32_t grid_origin(float nlo, float lo, float step) {
-  float fq = std::floor((nlo - lo) / step);
-  if (fq < 0.0f) fq = 0.0f;
-  if (fq > kGridCells) fq = kGridCells;
-  uint32_t q16 = (uint32_t)fq;
-  while (q16 > 0u && fmaf((float)q16, step, lo) > nlo) --q16;
-  return q16;
-}
-// surface-area cost of a node (ptc_stats.bvh_sa_cost): per used child slot half_area(child) / half_area(scene box at build time), a two-triangle leaf twice, each term
-// truncated to 2^-20 and summed as an integer — the terms and the sum k_refit_nodes forms on the device (pt_refit.hip)
+// surface-area cost of a node (ptc_stats.bvh_sa_cost): one term per used child slot, the terms and the sum k_refit_nodes forms on the device (pt_refit.hip)
 uint64_t sa_cost_of(const Wide& w, float scene_area) {
   uint64_t cost = 0;
   if (scene_area > 0.0f)
-    for (int sl = 0; sl < kWide; ++sl) {
-      if (!w.used[sl]) continue;
-      const uint64_t term = (uint64_t)((box_half_area(w.slot[sl].box) / scene_area) * PTC_SA_COST_ONE);
-      cost += (w.slot[sl].leaf && w.slot[sl].hi - w.slot[sl].lo + 1u == 2u) ? 2u * term : term;
-    }
+    for (int sl = 0; sl < kWide; ++sl)
+      if (w.used[sl]) cost += sa_cost_term(w.slot[sl].box, scene_area, w.slot[sl].leaf && w.slot[sl].hi - w.slot[sl].lo + 1u == 2u);
   return cost;
 }
-
-struct Dp { float c[8]; uint8_t leaf1, same[8], k[9]; };   // collapse cost table of a binary node.  c[i], same[i]: i = 1..7; k[j]: j = 2..8
-inline int min7(int k) { return k > 7 ? 7 : k; }
 
 // The state of one host build or refit; its member functions are the stages build_or_refit runs, in the order they stand here.
 struct SceneBuild {
@@ -962,7 +836,7 @@ struct SceneBuild {
   std::vector<Box> tbox;                     // box of every primitive
   Box sb;                                    // scene box
   std::vector<Box> radix_box;                // box of every binary node
-  std::vector<Dp> dp;
+  std::vector<DpT> dp;
 
   // ---- flatten: world position / normal / tangent (R3, R4) and bitangent (vertex.glsl:35) of every vertex ---------------------------
   void flatten(std::vector<HostVertex>& wverts, std::vector<float>& wbt) const {
@@ -976,22 +850,7 @@ struct SceneBuild {
         const Mat34 M = from_matrix(in.m);
         const uint32_t vb = L.vb[slices[si].inst];
         for (size_t k = slices[si].lo; k < slices[si].hi; ++k) {
-          const HostVertex& s = m.v[k];
-          HostVertex& d = wverts[vb + k];
-          transform_point(M, s.position, d.position);
-          mul_n(M.n, s.normal, d.normal);
-          fnormalize(d.normal);
-          mul_n(M.n, s.tangent, d.tangent);
-          fnormalize(d.tangent);
-          d.tangent[3] = s.tangent[3];
-          float cr[3], sc3[3], bt[3];
-          fcross(s.normal, s.tangent, cr);
-          sc3[0] = cr[0] * s.tangent[3]; sc3[1] = cr[1] * s.tangent[3]; sc3[2] = cr[2] * s.tangent[3];
-          mul_n(M.n, sc3, bt);
-          fnormalize(bt);
-          wbt[(size_t)(vb + k) * 3 + 0] = bt[0]; wbt[(size_t)(vb + k) * 3 + 1] = bt[1]; wbt[(size_t)(vb + k) * 3 + 2] = bt[2];
-          d.texcoord[0] = s.texcoord[0];
-          d.texcoord[1] = s.texcoord[1];
+          wverts[vb + k] = world_vertex(M.m, 4, M.n, m.v[k], &wbt[(size_t)(vb + k) * 3]);
         }
       }
     });
@@ -1006,13 +865,8 @@ struct SceneBuild {
     parallel_for(B.n_tris, 16384, [&](size_t p0, size_t p1) {
       Box mine = empty_box();
       for (size_t p = p0; p < p1; ++p) {
-        Box b = empty_box();
-        for (int c = 0; c < 3; ++c) {
-          const float* P = B.wverts[B.widx[p * 3 + c]].position;
-          for (int k = 0; k < 3; ++k) { b.lo[k] = P[k] < b.lo[k] ? P[k] : b.lo[k]; b.hi[k] = P[k] > b.hi[k] ? P[k] : b.hi[k]; }
-        }
-        tbox[p] = b;
-        grow(mine, b);
+        tbox[p] = triangle_box(B.wverts[B.widx[p * 3]].position, B.wverts[B.widx[p * 3 + 1]].position, B.wverts[B.widx[p * 3 + 2]].position);
+        grow(mine, tbox[p]);
       }
       part[next_part.fetch_add(1) % 64u] = mine;
     });
@@ -1057,29 +911,15 @@ struct SceneBuild {
   }
 
   // ---- cost tables, bottom-up ---------------------------------------------------------------------------
-  float dp_cost(int32_t link, int i) const { return link < 0 ? box_half_area(link_box(link)) * 1.0f * kCostPrim : dp[(size_t)link].c[i]; }
+  void cost_row(int32_t link, float row[8]) const { if (link < 0) dp_row(half_area(link_box(link)), row); else dp_row(dp[(size_t)link], row); }
   void cost_tables() {
-    dp.assign(T.radix.size(), Dp());
+    dp.assign(T.radix.size(), DpT());
     bottom_up([&](size_t idx) {
       const SplitNode& r = T.radix[idx];
-      Dp& d = dp[idx];
-      float dist[9];
-      for (int j = 2; j <= 8; ++j) {
-        float best = std::numeric_limits<float>::infinity(); int bk = 1;
-        for (int k = 1; k < j; ++k) {
-          const float v = dp_cost(r.left, min7(k)) + dp_cost(r.right, min7(j - k));
-          if (v < best) { best = v; bk = k; }
-        }
-        dist[j] = best; d.k[j] = (uint8_t)bk;
-      }
-      const uint32_t P = r.hi - r.lo + 1u;
-      const float area = box_half_area(radix_box[idx]);
-      const float cleaf = P <= (uint32_t)kLeafMax ? area * (float)P * kCostPrim : std::numeric_limits<float>::infinity();
-      const float cint = dist[8] + area * kCostNode;
-      d.leaf1 = cleaf <= cint; d.c[1] = d.leaf1 ? cleaf : cint;
-      for (int i = 2; i <= 7; ++i) {
-        if (dist[i] < d.c[i - 1]) { d.c[i] = dist[i]; d.same[i] = 0; } else { d.c[i] = d.c[i - 1]; d.same[i] = 1; }
-      }
+      float cl[8], cr[8], dist[9];
+      cost_row(r.left, cl); cost_row(r.right, cr);
+      const uint32_t kbits = collapse_dist(cl, cr, dist);
+      dp[idx] = collapse_table(kbits, dist, r.hi - r.lo + 1u, half_area(radix_box[idx]));
     });
   }
 
@@ -1094,19 +934,17 @@ struct SceneBuild {
       WChild c;
       c.box = link_box(j.link);
       if (j.link < 0) { c.leaf = true; c.lo = c.hi = (uint32_t)~j.link; c.radix = -1; kid[n++] = c; continue; }
-      const SplitNode& r = T.radix[(size_t)j.link]; const Dp& d = dp[(size_t)j.link];
-      int i = j.i;
-      while (i > 1 && d.same[i]) --i;
-      if (i == 1) { c.leaf = d.leaf1 != 0; c.lo = r.lo; c.hi = r.hi; c.radix = j.link; kid[n++] = c; continue; }
-      const int kk = d.k[i];
-      stk[sp++] = {r.right, min7(i - kk)};      // left first
-      stk[sp++] = {r.left, min7(kk)};
+      const SplitNode& r = T.radix[(size_t)j.link]; const uint32_t bits = dp[(size_t)j.link].bits;
+      int il, ir;
+      if (!forest_split(bits, j.i, il, ir)) { c.leaf = dp_leaf1(bits); c.lo = r.lo; c.hi = r.hi; c.radix = j.link; kid[n++] = c; continue; }
+      stk[sp++] = {r.right, ir};      // left first
+      stk[sp++] = {r.left, il};
     }
   }
   Wide expand(int32_t r) const {
     WChild kid[kWide];
     int n = 0;
-    const int kk = dp[(size_t)r].k[8];
+    const int kk = dp_k(dp[(size_t)r].bits, 8);
     forest(T.radix[(size_t)r].left, min7(kk), kid, n);
     forest(T.radix[(size_t)r].right, min7(8 - kk), kid, n);
     return make_wide(kid, n);
@@ -1161,7 +999,7 @@ struct SceneBuild {
       }
       T.block_addr[idx] = (uint32_t)T.next_unit;
       for (uint32_t i = 0; i < ni; ++i) T.node_addr[T.child_base[idx] + i] = (uint32_t)T.next_unit + 4u * i;
-      T.next_unit += ((uint64_t)4 * ni + (uint64_t)3 * nt + 3u) & ~(uint64_t)3;
+      T.next_unit += block_units(ni, nt);
       T.n_tri_records += nt;
       if (T.next_unit >= (1ull << 31)) return false;
     }
@@ -1170,17 +1008,12 @@ struct SceneBuild {
   }
 
   // ---- emit nodes and triangles -----------------------------------------------------------------------------------------
-  // triangle record of sorted position i: (v0, prim id) (e1, class) (e2, 0)
-  void tri_record(uint32_t i, float* o) const {
+  // triangle record of sorted position i
+  void tri_record_at(uint32_t i, float4* o) const {
     const uint32_t p = T.ord[i];
-    const float* a = B.wverts[B.widx[p * 3 + 0]].position;
-    const float* b = B.wverts[B.widx[p * 3 + 1]].position;
-    const float* c = B.wverts[B.widx[p * 3 + 2]].position;
     const int32_t mi = B.tri_mat[p];
-    const uint32_t cls = material_class(mats[(size_t)mi], mat_set[(size_t)mi]);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; std::memcpy(&o[3], &p, 4);
-    o[4] = b[0] - a[0]; o[5] = b[1] - a[1]; o[6] = b[2] - a[2]; std::memcpy(&o[7], &cls, 4);
-    o[8] = c[0] - a[0]; o[9] = c[1] - a[1]; o[10] = c[2] - a[2]; o[11] = 0.0f;
+    tri_record(o, B.wverts[B.widx[p * 3 + 0]].position, B.wverts[B.widx[p * 3 + 1]].position, B.wverts[B.widx[p * 3 + 2]].position, p,
+               material_class(mats[(size_t)mi], mat_set[(size_t)mi]));
   }
   void emit_node(uint32_t idx) {
     const Wide& w = T.wide[idx];
@@ -1196,7 +1029,7 @@ struct SceneBuild {
       }
       // quantised against the node's origin on the scene grid
       oq[k] = grid_origin(nlo, B.grid_lo[k], B.grid_step[k]);
-      const float org = fmaf((float)oq[k], B.grid_step[k], B.grid_lo[k]);
+      const float org = grid_point(oq[k], B.grid_lo[k], B.grid_step[k]);
       uint32_t ql[kWide], qh[kWide];
       quantize_axis(clo, chi, nk, org, nhi, e[k], ql, qh);
       for (int sl = 0; sl < kWide; ++sl) { qlo[k][sl] = 255; qhi[k][sl] = 0; }
@@ -1211,21 +1044,19 @@ struct SceneBuild {
       if (w.slot[sl].hi - w.slot[sl].lo + 1u == 2u) two |= 1u << sl;
     }
     uint32_t word[kNodeWords];
-    word[0] = oq[0] | (oq[1] << 16);
-    word[1] = oq[2] | (e[0] << 16) | (e[1] << 24);
-    word[2] = e[2] | (imask << 8) | (lmask << 16) | (two << 24);
+    node_header(oq, e, node_masks(imask, lmask, two), word);
     word[3] = T.block_addr[idx];
-    auto pack4 = [](const uint32_t* q) { return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24); };
     for (int k = 0; k < 3; ++k) {
-      word[4 + 2 * k] = pack4(&qlo[k][0]); word[5 + 2 * k] = pack4(&qlo[k][4]);
-      word[10 + 2 * k] = pack4(&qhi[k][0]); word[11 + 2 * k] = pack4(&qhi[k][4]);
+      const uint32_t *l = qlo[k], *h = qhi[k];
+      word[4 + 2 * k] = pack4(l[0], l[1], l[2], l[3]); word[5 + 2 * k] = pack4(l[4], l[5], l[6], l[7]);
+      word[10 + 2 * k] = pack4(h[0], h[1], h[2], h[3]); word[11 + 2 * k] = pack4(h[4], h[5], h[6], h[7]);
     }
     std::memcpy(&B.recs[(size_t)T.node_addr[idx] * 4], word, sizeof word);
     // the triangles of its leaf children, behind the interior children in its block
-    float* tri_out = &B.recs[((size_t)T.block_addr[idx] + 4u * ni) * 4];
+    float4* tri_out = reinterpret_cast<float4*>(B.recs.data()) + (size_t)T.block_addr[idx] + 4u * ni;
     for (int sl = 0; sl < kWide; ++sl) {
       if (!w.used[sl] || !w.slot[sl].leaf) continue;
-      for (uint32_t t = w.slot[sl].lo; t <= w.slot[sl].hi; ++t) { tri_record(t, tri_out); tri_out += 12; }
+      for (uint32_t t = w.slot[sl].lo; t <= w.slot[sl].hi; ++t) { tri_record_at(t, tri_out); tri_out += 3; }
     }
   }
   void emit_nodes() {
@@ -1252,28 +1083,12 @@ struct SceneBuild {
   void shading_records() {
     B.shade_stride = shade_stride_for(mats);
     const bool any_tex = B.shade_stride > 5u;
-    const size_t fl = (size_t)B.shade_stride * 4;
-    B.shade.assign((size_t)B.n_tris * fl, 0.0f);
+    B.shade.assign((size_t)B.n_tris * B.shade_stride * 4, 0.0f);
     parallel_for(B.n_tris, 8192, [&](size_t p0, size_t p1) {
       for (uint32_t p = (uint32_t)p0; p < (uint32_t)p1; ++p) {
-        const HostVertex& a = B.wverts[B.widx[p * 3 + 0]];
-        const HostVertex& b = B.wverts[B.widx[p * 3 + 1]];
-        const HostVertex& c = B.wverts[B.widx[p * 3 + 2]];
-        float* o = &B.shade[(size_t)p * fl];
-        o[0] = a.position[0]; o[1] = a.position[1]; o[2] = a.position[2]; std::memcpy(&o[3], &B.tri_mat[p], 4);
-        o[4] = b.position[0]; o[5] = b.position[1]; o[6] = b.position[2]; std::memcpy(&o[7], &B.prim_light[p], 4);
-        o[8] = c.position[0]; o[9] = c.position[1]; o[10] = c.position[2]; o[11] = a.normal[0];
-        o[12] = a.normal[1]; o[13] = a.normal[2]; o[14] = b.normal[0]; o[15] = b.normal[1];
-        o[16] = b.normal[2]; o[17] = c.normal[0]; o[18] = c.normal[1]; o[19] = c.normal[2];
-        if (any_tex) {
-          float* t = o + 20;
-          for (int k = 0; k < 3; ++k) {
-            const uint32_t vi = B.widx[p * 3 + (uint32_t)k];
-            const HostVertex& v = B.wverts[vi];
-            t[k * 2 + 0] = v.texcoord[0]; t[k * 2 + 1] = v.texcoord[1];
-            for (int j = 0; j < 3; ++j) { t[6 + k * 3 + j] = v.tangent[j]; t[15 + k * 3 + j] = T.wbt[(size_t)vi * 3 + (size_t)j]; }
-          }
-        }
+        const uint32_t* vi = &B.widx[(size_t)p * 3];
+        shading_record(reinterpret_cast<float4*>(B.shade.data()) + (size_t)p * B.shade_stride, any_tex, B.wverts[vi[0]], B.wverts[vi[1]], B.wverts[vi[2]],
+                       &T.wbt[(size_t)vi[0] * 3], &T.wbt[(size_t)vi[1] * 3], &T.wbt[(size_t)vi[2] * 3], B.tri_mat[p], B.prim_light[p]);
       }
     });
   }
@@ -1330,7 +1145,7 @@ std::string build_or_refit(const std::vector<HostMaterial>& mats, const std::vec
     S.refit_child_boxes();
     lap("refit boxes");
   } else {
-    B.sa_unit = box_half_area(S.sb);      // the unit of the surface-area cost: a refit keeps the commit's
+    B.sa_unit = half_area(S.sb);      // the unit of the surface-area cost: a refit keeps the commit's
     T.ord.resize(B.n_tris);
     for (uint32_t p = 0; p < B.n_tris; ++p) T.ord[p] = p;
     if (B.n_tris == 1) {

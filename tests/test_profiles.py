@@ -142,3 +142,19 @@ def test_render_arithmetic_has_one_definition():
     make = re.search(r"^KERNEL_SRC = (.*)$", src["Makefile"], re.M).group(1).split()
     assert [os.path.basename(f) for f in KERNEL_SRC] == make and {"pt_kernels.hip", "pt_device.h", "pt_shading.h"} <= set(make)
     assert set(f for f in make if f.endswith(".h")) <= set(re.search(r"^HDR = (.*)$", src["Makefile"], re.M).group(1).split())
+
+
+def test_scene_build_rules_have_one_definition():
+    """The rules that turn a scene description into the bytes in HBM are written once (csrc/pt_scene_rules.h, host + device) and once in the oracle: the host
+    builder and the device builders call them.  Six expressions that only a build rule holds and that stood in two or more files before — the Morton scale, the cost
+    term's fixed point, the nudge of an upper plane, the z term of the slot score, the half area of a box, the order-preserving map — each occur in exactly one file
+    under csrc/, that header;
+    it is on the hashed list; and the device files no longer point at ptc_scene.cpp for their definitions."""
+    src = {f: open(os.path.join(ROOT, CSRC, f), encoding="utf-8").read() for f in sorted(os.listdir(os.path.join(ROOT, CSRC)))}
+    for expr in ("2097152.0f", "* PTC_SA_COST_ONE", "(float)q2 * sc", "(sl & 4) ? d[i][2]", "ex * ey + ey * ez + ez * ex", "? ~u : (u | 0x80000000u)"):
+        assert [f for f, text in src.items() if expr in text] == ["pt_scene_rules.h"], expr
+    assert "pt_scene_rules.h" in [os.path.basename(f) for f in KERNEL_SRC]
+    for f in ("pt_refit.hip", "pt_build.hip", "ptc_scene.cpp", "ptc_api_scene.cpp"):
+        assert '#include "pt_scene_rules.h"' in src[f], f
+    for f in ("pt_refit.hip", "pt_build.hip"):
+        assert "pt_scene_rules.h" in src[f].split("#include")[0] and "in the host's order" not in src[f] and "ptc_scene.cpp)." not in src[f].split("#include")[0], f
