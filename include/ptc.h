@@ -291,6 +291,10 @@ int  ptc_get_light(const ptc_ctx*, int id, ptc_light_params* out);
 int  ptc_light_count(const ptc_ctx*);
 int  ptc_clear_lights(ptc_ctx*);
 
+/* Alpha coverage: the glTF alphaMode of a material (OPAQUE is the default).  The calls that set it, the statistics and the test hooks are declared in ptc_alpha.h,
+ * which this header includes at its end; DESIGN.md 2d has the specification. */
+enum { PTC_ALPHA_OPAQUE = 0, PTC_ALPHA_MASK = 1, PTC_ALPHA_BLEND = 2 };
+
 /* Lat-long environment light (BASELINE config 5; no counterpart in the reference, which has no lights): w*h RGB
  * fp32 texels, row 0 = +y, u = atan2(d.z, d.x)/(2 pi) + 1/2, piecewise-constant radiance, importance-sampled by
  * luminance x sin(theta).  rgb == NULL removes it.  Call before ptc_scene_commit. */
@@ -786,4 +790,5 @@ int ptc_debug_refit_host_parts(ptc_ctx*, uint64_t out[8]);
 #ifdef __cplusplus
 }
 #endif
+#include "ptc_alpha.h"   /* alpha coverage: an extension with a header and a symbol prefix of its own */
 #endif /* PTC_H */

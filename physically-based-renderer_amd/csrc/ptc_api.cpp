@@ -20,6 +20,7 @@ using namespace ptc_detail;
 
 namespace {
 constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray ping-pong) + 48 (shadow) + 16 (hit) + 16 (path radiance)
+constexpr size_t kAlphaBytesPerPath = 65;    // ensure_alpha_queues: 48 (continuation) + 16 (its hit record) + 1 (k_trace_any's flag)
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 
 // the timing spans that have completed (all_done: every one) go into the statistics, their events back to the pool
@@ -35,6 +36,7 @@ void collect_times(ptc_ctx* c, bool all_done) {
       else if (s.kind == 1) c->stats.seconds_trace_any += sec;
       else if (s.kind == 2) c->stats.seconds_shade += sec;
       else if (s.kind == 4) c->stats.seconds_reduce += sec;
+      else if (s.kind == 5) c->alpha.seconds += sec;
       else c->stats.seconds_render += sec;
     }
     c->free_events.push_back(s.a); c->free_events.push_back(s.b);
@@ -74,7 +76,16 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     // punctual lights (pt_lights.hip): a second next-event pass per bounce, on this stream alone — it needs hit and ray[b & 1] of bounce b intact and lpath to itself,
     // so any(b) does not run beside closest(b + 1) while lights exist
     const bool punctual = c->lights.n_dev > 0;
-    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual;
+    // alpha coverage (pt_alpha.hip): the hit records of bounce b are resolved between closest(b) and shade(b), every shadow queue to a transmittance per record instead of
+    // a flag — rounds of filter, scan and closest-hit launches on this stream alone, so any(b) does not run beside closest(b + 1) while alpha materials exist either
+    const bool alpha = alpha_on(c);
+    auto trace_shadows = [&]() {
+      ScopedSpan t(c, st, 1);
+      if (alpha) alpha_resolve_shadow(c, l, st, cfg, sc, q, nullptr);
+      else pt_launch_trace_any(st, cfg, sc, q, nullptr);
+      c->stats.launches_trace_any++;
+    };
+    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
       while (ln.ev_scan.size() < need) { hipEvent_t e = nullptr; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ln.ev_scan.push_back(e); }
@@ -85,6 +96,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     const bool per_kernel = !overlap || c->timing >= 2;       // overlapped launches: the batch's span only (ptc_stats.seconds_render); seconds_trace_* / seconds_shade stay 0
     for (int b = 0; b <= c->fr.max_bounces; ++b) {
       { ScopedSpan t(c, st, 0, per_kernel); pt_launch_trace_closest(st, cfg, sc, q, b & 1, false); c->stats.launches_trace_closest++; }
+      if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, PT_ALPHA_FORM_CLOSEST, nullptr);
       // k_shade(b) overwrites the shadow queue any(b - 1) reads and adds to the path radiance it adds to
       if (overlap && b > 0) HIP_TRY(c, hipStreamWaitEvent(st, ln.ev_any[(size_t)b - 1], 0));
       { ScopedSpan t(c, st, 2, per_kernel); pt_launch_shade(st, cfg, ln.d_scene, c->fr, q, b & 1, (uint32_t)b); }
@@ -95,13 +107,11 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
         HIP_TRY(c, hipStreamWaitEvent(ln.stream2, ln.ev_scan[(size_t)b], 0));
         { ScopedSpan t(c, ln.stream2, 1, per_kernel); pt_launch_trace_any(ln.stream2, cfg, sc_any, q, nullptr); c->stats.launches_trace_any++; }
         HIP_TRY(c, hipEventRecord(ln.ev_any[(size_t)b], ln.stream2));
-      } else if (shadows) {
-        ScopedSpan t(c, st, 1); pt_launch_trace_any(st, cfg, sc, q, nullptr); c->stats.launches_trace_any++;
-      }
+      } else if (shadows) trace_shadows();
       if (punctual) {     // behind emission (k_shade) and the emitter / environment sample (any): the punctual sample, through the same shadow queue
         { ScopedSpan t(c, st, 2); pt_launch_shade_punctual(st, sc, q, b & 1, (uint32_t)b, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev); }
         pt_launch_scan(st, cfg, q, (b + 1) & 1);      // the same ray prefix again, the new shadow counts, the work counters zeroed: nothing runs beside it
-        { ScopedSpan t(c, st, 1); pt_launch_trace_any(st, cfg, sc, q, nullptr); c->stats.launches_trace_any++; }
+        trace_shadows();
       }
     }
     // sample-order accumulation: wait for the previous batch's accumulate (it ran on the previous lane)
@@ -135,6 +145,7 @@ int issue(ptc_ctx* c, uint32_t k) {
   const uint64_t cap = (uint64_t)c->fr.n_owned * k;
   int rc = ensure_lane_queues(c, (uint32_t)cap);
   if (rc) return rc;
+  if (alpha_on(c) && (rc = ensure_alpha_queues(c))) return rc;
   if ((rc = run_batch(c, (int)(c->batches_issued % (uint64_t)c->n_lanes), c->sample_base + c->samples_done, k))) return rc;
   c->samples_done += k;
   c->stats.paths += cap;
@@ -277,6 +288,7 @@ int sum_lane_stats(ptc_ctx* c, unsigned long long st[ST_N]) {
 void Lane::teardown() {
   if (acc_done) (void)hipEventDestroy(acc_done);
   free_all(allocs);
+  free_all(aq_allocs);
   if (q.cnt) (void)hipFree(q.cnt);
   if (q.stats) (void)hipFree(q.stats);
   if (q.seg_ray[0]) (void)hipFree(q.seg_ray[0]);
@@ -302,6 +314,8 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   int rc;
   if ((rc = upload_lights(c))) return rc;      // a changed light table: nothing is queued any more that reads the old one
+  if ((rc = alpha_upload(c))) return rc;       // the alpha tables of a scene committed since the last frame
+  if (c->alpha.counters.p) HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
   if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
@@ -345,9 +359,10 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
     // no need to ask the driver how much memory is free (a call of 0.1-0.2 ms, every frame of a viewer's loop)
   } else {   // no more than 60 % of the device memory that is free now (plus what the lanes' queues already hold) goes into queues
     size_t free_b = 0, total_b = 0, held = 0;
-    for (const auto& ln : c->lanes) held += (size_t)ln.q.cap * kQueueBytesPerPath;
+    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0);
+    for (const auto& ln : c->lanes) held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / kQueueBytesPerPath;
+      const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / per_path;
       if (fit < batch_paths) batch_paths = fit;
     }
   }
@@ -362,6 +377,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->stats.seconds_commit = keep.seconds_commit; c->stats.seconds_refit = keep.seconds_refit; c->stats.n_triangles = keep.n_triangles; c->stats.n_bvh_nodes = keep.n_bvh_nodes;
   c->stats.n_emitters = keep.n_emitters; c->stats.bvh_max_depth = keep.bvh_max_depth;
   c->stats.bvh_sa_cost = keep.bvh_sa_cost; c->stats.bvh_sa_cost_built = keep.bvh_sa_cost_built; c->stats.seconds_rebuild = keep.seconds_rebuild;
+  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
   c->in_frame = true;
   c->probes.on = probe_pos != nullptr; c->probes.base = probe_base;
   return PTC_OK;
@@ -477,7 +493,8 @@ int ptc_frame_reserve(ptc_ctx* c) {
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_reserve: no frame");
   if (c->fr.n_owned == 0) return PTC_OK;
   const uint32_t k = is_raster(c->integrator) ? 1u : (c->per_batch < (uint32_t)c->spp_total ? c->per_batch : (uint32_t)c->spp_total);
-  return ensure_lane_queues(c, c->fr.n_owned * k);     // n_owned * per_batch fits 32 bits by construction (frame_begin)
+  { int rc = ensure_lane_queues(c, c->fr.n_owned * k); if (rc) return rc; }     // n_owned * per_batch fits 32 bits by construction (frame_begin)
+  return alpha_on(c) ? ensure_alpha_queues(c) : PTC_OK;
 }
 
 int ptc_frame_add_samples(ptc_ctx* c, int n_samples) {

@@ -45,6 +45,7 @@ int ptc_frame_guides(ptc_ctx* c) {
   {
     const uint32_t want = n < (1u << 21) ? n : (1u << 21);
     if (c->lanes[0].q.cap < want && (rc = ensure_lane_queues(c, want))) return rc;
+    if (alpha_on(c) && (rc = ensure_alpha_queues(c))) return rc;
   }
   Lane& ln = c->lanes[0];
   hipStream_t st = ln.stream;
@@ -60,6 +61,7 @@ int ptc_frame_guides(ptc_ctx* c) {
     pt_launch_set_counts(st, cfg, q, m, 0);
     pt_launch_raygen_guides(st, c->cam, c->fr.w, c->fr.h, first, m, q);
     pt_launch_trace_closest(st, cfg, sc, q, 0, false);
+    if (alpha_on(c)) alpha_resolve_closest(c, 0, st, cfg, sc, q, 0, 0, PT_ALPHA_FORM_GUIDE, nullptr);      // the first COVERING surface, decided without random numbers
     pt_launch_guides(st, sc, c->cam, c->fr.w, c->fr.h, first, m, q, g);
   }
   if ((rc = c->guides.timer.end(c, st))) return rc;

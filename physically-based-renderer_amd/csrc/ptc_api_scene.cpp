@@ -554,6 +554,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active()) c->poses[m].host_fresh = c->poses[m].emis_fresh = c0->poses[m].host_fresh;
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
   c->lens = c0->lens;
+  c->alpha.mode = c0->alpha.mode; c->alpha.cutoff = c0->alpha.cutoff;      // every member builds context 0's alpha tables
   take_lights(c, c0);
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
@@ -587,6 +588,7 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload w
   c->in_frame = false; c->pending = 0; drop_guides(c);
   c->committed = false;
   release_scene(c);
+  c->alpha.dirty = true; c->alpha.n_prims = 0;      // the alpha tables follow the primitive ids of the build being laid out: the next ptc_frame_begin uploads them (alpha_upload)
   CommittedScene& s = c->scene;
   s.insts = c->insts.size();
   deform_all_live(c);      // every caller lays the scene out from the fully evaluated description
@@ -679,6 +681,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
   ptc_lens_default_params(&c->lens);
   c->lights.dirty = c->lights.dirty || !c->lights.list.empty(); c->lights.list.clear();
+  c->alpha.mode.clear(); c->alpha.cutoff.clear(); c->alpha.dirty = true; c->alpha.n_prims = 0;      // every material of the next description starts OPAQUE; max_layers stays
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   if (c->display.state.p) HIP_TRY(c, hipMemset(c->display.state.p, 0, sizeof(pt_display_state)));      // the adaptation state goes with the scene; the display parameters stay
   release_scene(c);

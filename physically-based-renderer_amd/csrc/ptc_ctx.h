@@ -18,6 +18,7 @@
 #include "pt_deform.h"
 #include "pt_lens.h"
 #include "pt_lights.h"
+#include "pt_alpha.h"
 #include "pt_display.h"
 #include "pt_probes.h"
 
@@ -50,7 +51,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg);
     if (r_ != ncclSuccess) return fail((c), PTC_E_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
   } while (0)
 
-struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce
+struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution
 
 // An array in HBM and its owner: freed when the owner goes (with the context: after ptc_destroy made the device current), or early by release()
 template <class T> struct DevBuf {
@@ -91,6 +92,11 @@ struct Lane {
   hipStream_t stream2 = nullptr;
   uint2* stack_ovf2 = nullptr;      // the any-hit launches' own overflow slab (concurrent kernels must not share one)
   std::vector<hipEvent_t> ev_scan, ev_any;
+  // alpha coverage (pt_alpha.h): the lane's alpha queue as a DevQueues view — continuation records in ray[0], their hit records, header words, segment counts and
+  // statistics of its own — and the flags k_trace_any writes for the shadow queue.  Allocated only while the committed scene has an alpha material (ensure_alpha_queues)
+  DevQueues aq{};
+  uint8_t* aq_flags = nullptr;
+  std::vector<void*> aq_allocs;
   void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
   void teardown();                  // ptc_destroy: everything but the overflow slabs (release_scene's), the streams after what ran on them
 };
@@ -162,6 +168,21 @@ struct Lights {
   DevBuf<pt_light_rec> recs;
   DevBuf<float> cdf;
   uint32_t n_dev = 0;               // lights in the device table; 0: no punctual pass, nothing allocated
+};
+
+// alpha coverage (pt_alpha.h): mode / cutoff are what the calls recorded, by material id (shorter than the material list: the rest is OPAQUE); the device tables are
+// those of the committed scene, built from its per-primitive material ids and uploaded by the first ptc_frame_begin (or ray hook) after the commit
+struct Alpha {
+  std::vector<int32_t> mode;
+  std::vector<float> cutoff;
+  int max_layers = PT_ALPHA_DEFAULT_LAYERS;   // a context setting: kept across ptc_scene_begin
+  int frame_layers = PT_ALPHA_DEFAULT_LAYERS; // what the frame in progress (or the last ray hook) was begun with: a frame's batches all queue the same rounds
+  bool dirty = true;                // the committed scene's tables are not on the device yet
+  uint32_t n_prims = 0;             // primitives of the committed scene whose material is not OPAQUE, as of the last upload; 0: no pass, no queue, nothing allocated
+  DevBuf<uint32_t> bits;
+  DevBuf<float2> mode_cutoff;
+  DevBuf<unsigned long long> counters;
+  double seconds = 0.0;             // the frame's alpha resolutions (spans of kind 5)
 };
 
 // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
@@ -281,6 +302,7 @@ struct ptc_ctx {
   bool have_cam = false;
   ptc_lens_params lens{0.0f, 1.0f, 0, 0.0f};   // the camera's lens (ptc_set_camera_lens): kept across ptc_set_camera, reset by ptc_scene_begin; R = 0: the pinhole, k_raygen
   ptc_detail::Lights lights;
+  ptc_detail::Alpha alpha;
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -488,6 +510,13 @@ int refit_upload(ptc_ctx* c, bool same_sizes, std::chrono::steady_clock::time_po
 int device_refit(ptc_ctx* c, std::chrono::steady_clock::time_point t0);
 int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload what, bool skeleton = false);
 int scene_commit(ptc_ctx* c, bool device_ok);
+
+// ---- ptc_api_alpha.cpp: alpha coverage (pt_alpha.h) ------------------------------------------------------------------------------------------------
+int alpha_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
+inline bool alpha_on(const ptc_ctx* c) { return c->alpha.n_prims > 0; }
+int ensure_alpha_queues(ptc_ctx* c);                   // every lane: an alpha queue as large as its queues (grow only; waits for the work in flight first)
+void alpha_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, int form, uint32_t* layers_out);
+void alpha_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out);
 
 // ---- ptc_api_image.cpp ---------------------------------------------------------------------------------------------------------------------------
 DevAdaptive dev_adaptive(const ptc_ctx* c);

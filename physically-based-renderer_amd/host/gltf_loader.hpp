@@ -150,7 +150,8 @@ private:
 };
 
 // ---- flat result ------------------------------------------------------------------------------------
-struct Material { float base_color[4] = {1, 1, 1, 1}; float metallic = 1.0f, roughness = 1.0f; float emissive[3] = {0, 0, 0}; int tex_color = -1, tex_normal = -1, tex_mr = -1; };   // tex_*: index into FlatScene::textures
+struct Material { float base_color[4] = {1, 1, 1, 1}; float metallic = 1.0f, roughness = 1.0f; float emissive[3] = {0, 0, 0}; int tex_color = -1, tex_normal = -1, tex_mr = -1;      // tex_*: index into FlatScene::textures
+                  int alpha_mode = PTC_ALPHA_OPAQUE; float alpha_cutoff = 0.5f; };   // glTF alphaMode / alphaCutoff (an emissive material stays OPAQUE: ptc_set_material_alpha's rule)
 struct Texture { int w = 0, h = 0; std::vector<std::uint8_t> rgba; };
 struct Primitive { std::vector<ptc_vertex> vertices; std::vector<std::uint32_t> indices; int material = 0; };
 struct Instance { int primitive; std::array<float, 16> model; };   // column-major
@@ -512,6 +513,17 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
       o.tex_mr = texture_of(pbr->get("metallicRoughnessTexture"));
     }
     o.tex_normal = texture_of(m.get("normalTexture"));
+    {
+      const std::string am = m.string("alphaMode", "OPAQUE");
+      if (am == "OPAQUE") o.alpha_mode = PTC_ALPHA_OPAQUE;
+      else if (am == "MASK") o.alpha_mode = PTC_ALPHA_MASK;
+      else if (am == "BLEND") o.alpha_mode = PTC_ALPHA_BLEND;
+      else throw std::runtime_error("material " + std::to_string(out.materials.size()) + ": alphaMode \"" + am + "\" is not OPAQUE, MASK or BLEND");
+      o.alpha_cutoff = (float)m.number("alphaCutoff", 0.5);
+      if (!(o.alpha_cutoff >= 0.0f)) o.alpha_cutoff = 0.0f;      // glTF asks for >= 0; above 1 nothing passes the mask, which a cutoff of 1 with alpha <= 1 already says
+      if (o.alpha_cutoff > 1.0f) o.alpha_cutoff = 1.0f;
+      if (o.emissive[0] != 0.0f || o.emissive[1] != 0.0f || o.emissive[2] != 0.0f) o.alpha_mode = PTC_ALPHA_OPAQUE;      // emitters are sampled by area: they stay opaque
+    }
     out.materials.push_back(o);
   }
   int default_material = -1;
@@ -688,6 +700,7 @@ inline int upload(ptc_ctx* ctx, const FlatScene& s) {
   for (const Material& m : s.materials) {
     const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
     if (id < 0) return id;
+    if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
     mat_id.push_back(id);
   }
   for (const Primitive& p : s.primitives) {

@@ -39,6 +39,8 @@ struct MaterialData {
   std::array<float, 4> color{1, 1, 1, 1};
   float metallic = 0.0f, roughness = 1.0f;
   std::array<float, 3> emissive{0, 0, 0};
+  int alphaMode = PTC_ALPHA_OPAQUE;      // glTF alphaMode: PTC_ALPHA_OPAQUE / _MASK / _BLEND (ptc_set_material_alpha; an emissive material must stay opaque)
+  float alphaCutoff = 0.5f;
 };
 
 // The viewer's start-up camera: app::CameraController's defaults (src/gltf_viewer/CameraController.hpp:25-40: position 0, pitch 0,
@@ -93,7 +95,9 @@ public:
 
   auto beginScene() -> void { ck(ptc_scene_begin(_ctx)); }
   auto addMaterial(MaterialData const& m) -> int {
-    return ck(ptc_add_material(_ctx, m.color.data(), m.metallic, m.roughness, m.emissive.data(), -1, -1, -1));
+    const int id = ck(ptc_add_material(_ctx, m.color.data(), m.metallic, m.roughness, m.emissive.data(), -1, -1, -1));
+    if (m.alphaMode != PTC_ALPHA_OPAQUE) ck(ptc_set_material_alpha(_ctx, id, m.alphaMode, m.alphaCutoff));
+    return id;
   }
   // one ptc mesh per PrimitiveSpan, firstVertex applied like drawIndexed's vertexOffset (PbrRenderSystem.cpp:454-460)
   auto addMesh(MeshBuilder::BuiltMesh const& b) -> std::vector<int> {

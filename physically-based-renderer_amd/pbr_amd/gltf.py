@@ -411,6 +411,11 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
             g["normalTexture"] = {"index": int(m.tex_normal)}
         if strength > 1.0:
             g["extensions"] = {"KHR_materials_emissive_strength": {"emissiveStrength": strength}}
+        mode = getattr(m, "alpha_mode", None)      # None: the key is left out (glTF's default, OPAQUE); any string is written as given
+        if mode is not None and not (mode == "opaque" and getattr(m, "alpha_cutoff", 0.5) == 0.5):
+            g["alphaMode"] = str(mode).upper() if str(mode).lower() in ("opaque", "mask", "blend") else str(mode)
+            if str(mode).lower() == "mask":
+                g["alphaCutoff"] = float(getattr(m, "alpha_cutoff", 0.5))
         mats.append(g)
 
     if nodes is None:

@@ -35,6 +35,9 @@ LIGHT_POINT = 0
 LIGHT_SPOT = 1
 LIGHT_DIRECTIONAL = 2
 MAX_LIGHTS = 256
+ALPHA_OPAQUE = 0          # glTF alphaMode (set_material_alpha)
+ALPHA_MASK = 1
+ALPHA_BLEND = 2
 TONEMAP_ACES = 0          # the ACES fit of tonemap()
 TONEMAP_PBR_NEUTRAL = 1   # Khronos PBR Neutral
 TONEMAP_REINHARD = 2      # extended Reinhard on luminance
@@ -110,6 +113,7 @@ class PtcLensParams(_Struct):
     _defaults_ = "ptc_lens_default_params"
 
 
+_ALPHA_MODES = {"opaque": ALPHA_OPAQUE, "mask": ALPHA_MASK, "blend": ALPHA_BLEND}
 _LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
 
 
@@ -118,6 +122,10 @@ class PtcLightParams(_Struct):
                 ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("sampling_weight", C.c_float)]
     _defaults_ = "ptc_light_default_params"
     _names_ = {"type": _LIGHT_TYPES}
+
+
+class PtcAlphaStats(_Struct):
+    _fields_ = [("closest_passes", C.c_uint64), ("shadow_walked", C.c_uint64), ("shadow_passes", C.c_uint64), ("exhausted", C.c_uint64), ("seconds_alpha", C.c_double)]
 
 
 class PtcDenoiseParams(_Struct):
@@ -312,7 +320,28 @@ def _prototypes():
     }
 
 
+def _alpha_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_alpha.h declares, in the header's order.  The library exports them under the prefix ptcx_ (the
+    header maps the names by macros): load_library looks them up there and hangs them on the library object under the names the header gives them."""
+    i, f, u32 = C.c_int, C.c_float, C.c_uint32
+    vp, ip, fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
+    u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    return {
+        "ptc_set_material_alpha": (i, [vp, i, i, f]),
+        "ptc_get_material_alpha": (i, [vp, i, ip, fp]),
+        "ptc_set_alpha_max_layers": (i, [vp, i]),
+        "ptc_get_alpha_stats": (i, [vp, C.POINTER(PtcAlphaStats)]),
+        "ptc_debug_alpha_closest": (i, [vp, fp, fp, u32p, u32, u32, i, fp, i32p, fp, u32p]),
+        "ptc_debug_alpha_any": (i, [vp, fp, fp, fp, u32, fp]),
+        "ptc_debug_alpha_decide": (i, [i, f, f, f, ip, fp]),
+        "ptc_debug_get_alpha_tables": (i, [vp, u32p, u32p, u32p, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
+_ALPHA_PROTOTYPES = _alpha_prototypes()
+# every function include/ptc_alpha.h declares, by the header's names
+ALPHA_SYMBOLS = list(_ALPHA_PROTOTYPES)
 # every symbol include/ptc.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = list(_PROTOTYPES)
 
@@ -331,6 +360,10 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
+    for name, (restype, argtypes) in _ALPHA_PROTOTYPES.items():
+        fn = getattr(L, "ptcx_" + name[len("ptc_"):])
+        fn.restype, fn.argtypes = restype, argtypes
+        setattr(L, name, fn)
     _lib = L
     return L
 
@@ -438,6 +471,15 @@ def light_sample(light, P):
         if rc:
             ok[i], wi[i], dist[i], Li[i] = True, tuple(w), d.value, tuple(li)
     return ok, wi, dist, Li
+
+
+def alpha_decide(mode, cutoff, a, u):
+    """ptc_debug_alpha_decide: the host's evaluation of csrc/pt_alpha.h: (accept bool, transmit float32) of one hit of coverage a."""
+    acc, tr = C.c_int(0), C.c_float(0)
+    rc = load_library().ptc_debug_alpha_decide(_ALPHA_MODES[mode] if isinstance(mode, str) else int(mode), float(cutoff), float(a), float(u), C.byref(acc), C.byref(tr))
+    if rc < 0:
+        raise PtcError(f"alpha_decide: unknown mode {mode!r}")
+    return bool(acc.value), np.float32(tr.value)
 
 
 def display_params(**fields):
@@ -554,7 +596,9 @@ class PathTracer:
             assert e.ndim == 3 and e.shape[2] == 3, "env is (h, w, 3) float32"
             self._ck(L.ptc_set_env_latlong_rgb32f(h, _ptr(e), e.shape[1], e.shape[0]))
         for m in desc.materials:
-            self._ck(L.ptc_add_material(h, _f(m.base_color)[1], m.metallic, m.roughness, _f(m.emissive)[1], m.tex_color, m.tex_normal, m.tex_mr))
+            mid = self._ck(L.ptc_add_material(h, _f(m.base_color)[1], m.metallic, m.roughness, _f(m.emissive)[1], m.tex_color, m.tex_normal, m.tex_mr))
+            if str(getattr(m, "alpha_mode", "opaque")).lower() not in ("opaque", str(ALPHA_OPAQUE)):
+                self.set_material_alpha(mid, m.alpha_mode, getattr(m, "alpha_cutoff", 0.5))
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
@@ -619,6 +663,55 @@ class PathTracer:
         so, sd, tm, ct = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
         self._ck(self._L.ptc_debug_punctual_nee(self._h, op, dp, _ptr(k), n, int(bounce), _ptr(valid), _ptr(so), _ptr(sd), _ptr(tm), _ptr(ct)))
         return valid.astype(bool), so, sd, tm, ct
+
+    # ---- alpha coverage (csrc/pt_alpha.h) -------------------------------------------------------------------
+    def set_material_alpha(self, material, mode, cutoff=0.5):
+        """ptc_set_material_alpha, between add_material and the commit: mode "opaque" / "mask" / "blend" (or ALPHA_*), cutoff in [0, 1] (MASK)."""
+        self._ck(self._L.ptc_set_material_alpha(self._h, int(material), _ALPHA_MODES[mode.lower()] if isinstance(mode, str) else int(mode), float(cutoff)))
+        return self
+
+    def get_material_alpha(self, material):
+        """(mode, cutoff) of a material of the description."""
+        m, c = C.c_int(0), C.c_float(0)
+        self._ck(self._L.ptc_get_material_alpha(self._h, int(material), C.byref(m), C.byref(c)))
+        return int(m.value), float(c.value)
+
+    def set_alpha_max_layers(self, n):
+        self._ck(self._L.ptc_set_alpha_max_layers(self._h, int(n)))
+        return self
+
+    def alpha_stats(self):
+        return self._get(self._L.ptc_get_alpha_stats, PtcAlphaStats)
+
+    def alpha_closest(self, origins, dirs, keys, bounce=0, deterministic=False):
+        """ptc_debug_alpha_closest: explicit rays through k_trace_closest and the closest-hit alpha resolution: (t, prim, uv, layers)."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = o.shape[0]
+        assert d.shape[0] == n and k.size == n
+        t, prim, uv, layers = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint32)
+        self._ck(self._L.ptc_debug_alpha_closest(self._h, op, dp, _ptr(k), n, int(bounce), 1 if deterministic else 0, _ptr(t), _ptr(prim), _ptr(uv), _ptr(layers)))
+        return t, prim, uv, layers
+
+    def alpha_any(self, origins, dirs, tmax):
+        """ptc_debug_alpha_any: explicit shadow rays through the shadow resolution: the transmittance per ray (0: occluded)."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        tm, tp = _f(tmax)
+        n = o.shape[0]
+        assert d.shape[0] == n and tm.size == n
+        out = np.zeros(n, np.float32)
+        self._ck(self._L.ptc_debug_alpha_any(self._h, op, dp, tp, n, _ptr(out)))
+        return out
+
+    def alpha_tables(self):
+        """ptc_debug_get_alpha_tables: (bits (ceil(n_prims / 32),) uint32, mode (n_mats,) int32, cutoff (n_mats,) float32, n_prims, whether an alpha queue is allocated)."""
+        npr, nm = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.ptc_debug_get_alpha_tables(self._h, C.byref(npr), None, C.byref(nm), None))
+        bits, mc = np.zeros((npr.value + 31) // 32, np.uint32), np.zeros((nm.value, 2), np.float32)
+        rc = self._ck(self._L.ptc_debug_get_alpha_tables(self._h, None, _ptr(bits), None, _ptr(mc)))
+        return bits, mc[:, 0].copy().view(np.int32), mc[:, 1].copy(), int(npr.value), bool(rc)
 
     def set_camera(self, position, target, fov_y, aspect):
         self._ck(self._L.ptc_set_camera(self._h, _f(position)[1], _f(target)[1], fov_y, aspect))

@@ -40,6 +40,8 @@ class Material:
     tex_color: int = -1
     tex_normal: int = -1
     tex_mr: int = -1
+    alpha_mode: str = "opaque"      # glTF alphaMode: "opaque", "mask" or "blend" (ptc_set_material_alpha); an emissive material stays opaque
+    alpha_cutoff: float = 0.5       # MASK: the surface counts where its alpha reaches this
 
 
 @dataclasses.dataclass

@@ -378,6 +378,41 @@ def textured_objects() -> SceneDesc:
     d.env = analytic_sky(64, 32)
     return d
 
+def alpha_layers(n_mask: int = 3, n_blend: int = 2, texture_filter: str = "nearest", spacing: float = 0.25, mask_alpha=None, blend_alpha=None,
+                 emitter: bool = True) -> SceneDesc:
+    """The alpha-coverage test scene (csrc/pt_alpha.h): n_mask + n_blend parallel quads of two triangles each, `spacing` apart (thousands of ray epsilons in this
+    unit-scale scene), above a Lambert floor, seen from far above through a narrow lens: the rays are within 5 degrees of the quads' normal and all of them cross
+    every quad well inside its outline.  That is on purpose: a ray that passes a surface goes on from a point one ray epsilon off the surface ALONG ITS NORMAL, which moves
+    a slanted ray sideways by epsilon x sin(angle); here that is under 1e-5 of a texture per layer, so which texel a later layer is met in does not depend on it.  Each quad has an 8x8 RGBA texture of its own: a MASK layer alpha 0 / 255 in a checker of 2x2-texel
+    cells shifted by one texel per layer, a BLEND layer alpha in {0, 64, 128, 192, 255}; mask_alpha / blend_alpha (0..255) make a kind's alpha constant instead.
+    The MASK layers lie below the BLEND layers.  The quads are added LAST, so the floor's (and the emitter's) primitive ids are those of the scene without them:
+    floor 0-1, emitter 2-3 (a small quad above the layers, facing down, outside the camera's view; emitter=False leaves it out), layer k at 4 + 2k (2 + 2k without the emitter)."""
+    mats = [Material((0.7, 0.7, 0.7, 1.0), 0.0, 1.0)]
+    meshes = [MeshDesc(*_quad((-2, 0, 2), (2, 0, 2), (2, 0, -2), (-2, 0, -2)), 0)]                       # floor, normal +y
+    if emitter:
+        mats.append(Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (20.0, 20.0, 20.0)))
+        meshes.append(MeshDesc(*_quad((1.6, 4.0, -0.2), (2.0, 4.0, -0.2), (2.0, 4.0, 0.2), (1.6, 4.0, 0.2)), 1))     # normal -y; beside the camera's view
+    textures = []
+    yy, xx = np.mgrid[0:8, 0:8]
+    for k in range(n_mask + n_blend):
+        mask = k < n_mask
+        if mask:
+            alpha = np.where((((xx + k) // 2 + yy // 2) % 2) == 0, 255, 0) if mask_alpha is None else np.full((8, 8), int(mask_alpha))
+        else:
+            alpha = np.asarray([0, 64, 128, 192, 255])[(xx + 2 * yy + k) % 5] if blend_alpha is None else np.full((8, 8), int(blend_alpha))
+        rgb = np.stack([(37 * xx + 11 * k) % 200 + 40, (53 * yy + 29 * k) % 200 + 40, (17 * (xx + yy) + 71 * k) % 200 + 40], -1)
+        textures.append(np.concatenate([rgb, alpha[..., None]], -1).astype(np.uint8))
+        mats.append(Material((1.0, 1.0, 1.0, 1.0), 0.0, 1.0, (0, 0, 0), k, -1, -1, "mask" if mask else "blend", 0.5))
+        y = 0.5 + spacing * k
+        meshes.append(MeshDesc(*_quad((-2, y, 2), (2, y, 2), (2, y, -2), (-2, y, -2)), len(mats) - 1))   # normal +y
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    cam = CameraDesc((1.2, 40.0, 1.0), (0.0, 0.0, 0.0), math.radians(2.9), 1.0)      # a square of side 2 of the quads, turned about y, corners within 1.55 of the axis: four texels across
+    d = SceneDesc(mats, meshes, inst, cam, "alpha_layers")
+    d.textures = textures
+    d.texture_filter = texture_filter
+    return d
+
+
 def by_name(name: str, **kw) -> SceneDesc:
     return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
-            "textured_objects": textured_objects, "textured_atrium": textured_atrium}[name](**kw)
+            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers}[name](**kw)
