@@ -1,0 +1,117 @@
+// pt_glass.hip — the dielectric-transmission pass (see pt_glass.h).
+//
+//   k_glass_filter   one round of a resolution.  Round 0 reads the batch's own queue (the rays of ray[qi] and their hit records); a later round reads the glass queue
+//                    and the hit records k_trace_closest wrote for it.  A ray whose hit stands (or that is exhausted) after at least one event is written to its
+//                    SOURCE slot (the hit record and the ray record: single owner, one continuation per source ray); a ray with an event is compacted to the front
+//                    of the same segment of the glass queue, to be traced again by the unchanged k_trace_closest.
+// Layout: k_alpha_filter_closest's.  Blocks of 256 threads, one WAVE owns one queue segment (seg = blockIdx.x * 4 + wave), takes its slots 64 at a time in queue order,
+// and compacts what it produces with a ballot and mbcnt64: no atomic on the data path, no block barrier, and a wave never writes more records than it read — which is
+// also why a later round can compact IN PLACE: a batch of 64 is loaded whole before anything is stored, and what it stores lies at or before its own slots.
+// An empty round (every segment count 0) is a launch whose waves read one word each.
+// Memory per hit that needs a decision: the 80 B (192 B in a textured scene) of the shading record, the texel taps, 48 B of material and 32 B of glass record; a hit on
+// anything else costs the 4-byte load of its bit from a table that stays in L2.  The surface comes from the pt_shading.h helpers: k_shade's texels and arithmetic.
+#include "pt_shading.h"
+#include "pt_glass.h"
+
+#define GLASS_BLOCK 256
+#define GLASS_WAVES (GLASS_BLOCK / 64)
+
+namespace {
+PT_DEV bool glass_bit(const DevGlass& gl, uint32_t prim) { return (gl.bits[prim >> 5] >> (prim & 31u)) & 1u; }
+PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
+
+template <bool FIRST>
+__global__ __launch_bounds__(GLASS_BLOCK) void k_glass_filter(DevScene sc, DevQueues q, DevQueues gq, int qi, uint32_t b, DevGlass gl, uint32_t* j_out) {
+  const uint32_t lane = lane_id();
+  const uint32_t seg = blockIdx.x * GLASS_WAVES + (threadIdx.x >> 6);
+  if (seg >= q.n_seg) return;
+  const RayQ rsrc = q.ray[qi];
+  const RayQ rin = FIRST ? q.ray[qi] : gq.ray[0];
+  const float4* hin = FIRST ? q.hit : gq.hit;
+  const RayQ rout = gq.ray[0];
+  const uint32_t base = seg * q.seg_len;
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)(FIRST ? q.seg_ray[qi][seg] : gq.seg_ray[0][seg]));
+  uint32_t out = 0;
+  unsigned long long n_refl = 0, n_refr = 0, n_stand = 0, n_exh = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+    const uint32_t slot = base + i0 + lane;
+    bool go_on = false, reflected = false, exhausted = false, stood = false;
+    float4 cA, cB, cC;
+    cA = cB = cC = make_float4(0, 0, 0, 0);
+    if (i0 + lane < n) {
+      float4 H = hin[slot];
+      const int pw = __float_as_int(H.y);
+      const bool decide = pw >= 0 && glass_bit(gl, (uint32_t)pw & ((1u << HIT_CLASS_SHIFT) - 1u));
+      if (!FIRST || decide) {
+        const float4 A = rin.A[slot], Bq = rin.B[slot], Cq = rin.C[slot];
+        v3 o = V3(A.x, A.y, A.z), d = V3(A.w, Bq.x, Bq.y), T = V3(Bq.z, Bq.w, Cq.x);
+        const uint32_t key = __float_as_uint(Cq.w);
+        const uint32_t j = FIRST ? 0u : __float_as_uint(Cq.y), src = FIRST ? slot : __float_as_uint(Cq.z);
+        int outcome = PT_GLASS_STANDS;
+        bool beer = false;
+        if (decide) {
+          // ---- the surface: k_shade's loads and its P5 (pt_shading.h) ----
+          const uint32_t prim = (uint32_t)pw & ((1u << HIT_CLASS_SHIFT) - 1u);
+          const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
+          const size_t rec = (size_t)prim * sc.shade_stride;
+          const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2], r3 = sc.shade[rec + 3], r4 = sc.shade[rec + 4];
+          float4 x0, x1, x2, x3, x4, x5;
+          x0 = x1 = x2 = x3 = x4 = x5 = make_float4(0, 0, 0, 0);
+          if (((uint32_t)pw >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; x2 = sc.shade[rec + 7]; x3 = sc.shade[rec + 8]; x4 = sc.shade[rec + 9]; x5 = sc.shade[rec + 10]; }
+          const int mat = __float_as_int(r0.w);
+          const float4 g0 = gl.mats[(size_t)mat * 2u], g1 = gl.mats[(size_t)mat * 2u + 1u];
+          const v3 P = record_position(r0, r1, r2, hu, hv, hw);
+          v3 ng = record_face_normal(r0, r1, r2);
+          const v3 ni = record_normal(r2, r3, r4, hu, hv, hw);
+          v3 ns = normalize3(ni);
+          float base_c[4], metallic, roughness;
+          bool lambert;
+          record_material(sc, sc.mats, mat, x0, x1, x2, x3, x4, x5, hu, hv, hw, ni, base_c, metallic, roughness, lambert, ns);
+          const bool front = orient_normals(-d, ng, ns);
+          pt_glass_mat m;
+          m.tau = g0.x; m.ior = g0.y; m.thin = __float_as_int(g0.z); m.pad0 = 0.0f; m.sigma2[0] = g1.x; m.sigma2[1] = g1.y; m.sigma2[2] = g1.z; m.pad1 = 0.0f;
+          beer = pt_glass_beer(m, front, H.x, T);
+          const uint32_t idx = PT_GLASS_RNG_BASE + (b + 1u) * 64u + j;
+          float F;
+          outcome = pt_glass_interact(m, P, ng, ns, front, V3(base_c[0], base_c[1], base_c[2]), metallic, sc.ray_eps, rng_f(key, idx, 0), rng_f(key, idx, 1), j, gl.max_interactions, o, d, T, F);
+        }
+        if (outcome >= PT_GLASS_REFLECT) {
+          go_on = true; reflected = outcome == PT_GLASS_REFLECT;
+          cA = make_float4(o.x, o.y, o.z, d.x);
+          cB = make_float4(d.y, d.z, T.x, T.y);
+          cC = make_float4(T.z, __uint_as_float(j + 1u), __uint_as_float(src), __uint_as_float(key));
+        } else if (!FIRST) {      // j >= 1: the standing hit (or the miss record) and the rewritten ray, at the source ray's own slot
+          if (outcome == PT_GLASS_EXHAUSTED) { exhausted = true; H = make_float4(-1.0f, __int_as_float(-1), 0.0f, 0.0f); T = V3(0.0f, 0.0f, 0.0f); }
+          else stood = true;      // counted as standing: the ray leaves the pass with a result for k_shade, a hit that stood or the trace's miss (pw < 0) alike
+          q.hit[src] = H;
+          rsrc.A[src] = make_float4(o.x, o.y, o.z, d.x);
+          rsrc.B[src] = make_float4(d.y, d.z, T.x, T.y);
+          *reinterpret_cast<float2*>(&rsrc.C[src]) = make_float2(T.z, PT_GLASS_DELTA_PDF);      // path and key stay
+          if (j_out) j_out[src] = j;
+        } else if (beer) {        // j = 0 and the hit stands: T alone
+          rsrc.B[slot] = make_float4(Bq.x, Bq.y, T.x, T.y);
+          rsrc.C[slot] = make_float4(T.z, Cq.y, Cq.z, Cq.w);
+        }
+      }
+    }
+    const uint64_t mp = __ballot(go_on);
+    if (go_on) { const uint32_t o = base + out + mbcnt64(mp); rout.A[o] = cA; rout.B[o] = cB; rout.C[o] = cC; }
+    out += (uint32_t)__popcll(mp);
+    const unsigned long long nr = (unsigned long long)__popcll(__ballot(reflected));
+    n_refl += nr; n_refr += (unsigned long long)__popcll(mp) - nr;
+    n_stand += (unsigned long long)__popcll(__ballot(stood));
+    n_exh += (unsigned long long)__popcll(__ballot(exhausted));
+  }
+  if (lane == 0) gq.seg_ray[0][seg] = out;
+  wave_count(&gl.counters[PT_GLASS_REFLECTIONS], n_refl, lane);
+  wave_count(&gl.counters[PT_GLASS_REFRACTIONS], n_refr, lane);
+  wave_count(&gl.counters[PT_GLASS_STANDING], n_stand, lane);
+  wave_count(&gl.counters[PT_GLASS_EXHAUSTED_N], n_exh, lane);
+}
+}  // namespace
+
+void pt_launch_glass_filter(hipStream_t s, const DevScene& sc, const DevQueues& q, const DevQueues& gq, int qi, uint32_t bounce, const DevGlass& gl, bool first, uint32_t* j_out) {
+  const dim3 grid((q.n_seg + GLASS_WAVES - 1u) / GLASS_WAVES), block(GLASS_BLOCK);      // one wave per segment
+  if (first) hipLaunchKernelGGL((k_glass_filter<true>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+  else hipLaunchKernelGGL((k_glass_filter<false>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+}

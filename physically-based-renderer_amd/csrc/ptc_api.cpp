@@ -21,6 +21,7 @@ using namespace ptc_detail;
 namespace {
 constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray ping-pong) + 48 (shadow) + 16 (hit) + 16 (path radiance)
 constexpr size_t kAlphaBytesPerPath = 65;    // ensure_alpha_queues: 48 (continuation) + 16 (its hit record) + 1 (k_trace_any's flag)
+constexpr size_t kGlassBytesPerPath = 64;    // ensure_glass_queues: 48 (continuation) + 16 (its hit record)
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 
 // the timing spans that have completed (all_done: every one) go into the statistics, their events back to the pool
@@ -37,6 +38,7 @@ void collect_times(ptc_ctx* c, bool all_done) {
       else if (s.kind == 2) c->stats.seconds_shade += sec;
       else if (s.kind == 4) c->stats.seconds_reduce += sec;
       else if (s.kind == 5) c->alpha.seconds += sec;
+      else if (s.kind == 6) c->glass.seconds += sec;
       else c->stats.seconds_render += sec;
     }
     c->free_events.push_back(s.a); c->free_events.push_back(s.b);
@@ -79,13 +81,15 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     // alpha coverage (pt_alpha.hip): the hit records of bounce b are resolved between closest(b) and shade(b), every shadow queue to a transmittance per record instead of
     // a flag — rounds of filter, scan and closest-hit launches on this stream alone, so any(b) does not run beside closest(b + 1) while alpha materials exist either
     const bool alpha = alpha_on(c);
+    // dielectric transmission (pt_glass.hip): behind the alpha resolution of bounce b, before shade(b), rounds of launches on this stream alone as well
+    const bool glass = glass_on(c);
     auto trace_shadows = [&]() {
       ScopedSpan t(c, st, 1);
       if (alpha) alpha_resolve_shadow(c, l, st, cfg, sc, q, nullptr);
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
-    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha;
+    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
       while (ln.ev_scan.size() < need) { hipEvent_t e = nullptr; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ln.ev_scan.push_back(e); }
@@ -97,6 +101,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     for (int b = 0; b <= c->fr.max_bounces; ++b) {
       { ScopedSpan t(c, st, 0, per_kernel); pt_launch_trace_closest(st, cfg, sc, q, b & 1, false); c->stats.launches_trace_closest++; }
       if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, PT_ALPHA_FORM_CLOSEST, nullptr);
+      if (glass) glass_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, nullptr);
       // k_shade(b) overwrites the shadow queue any(b - 1) reads and adds to the path radiance it adds to
       if (overlap && b > 0) HIP_TRY(c, hipStreamWaitEvent(st, ln.ev_any[(size_t)b - 1], 0));
       { ScopedSpan t(c, st, 2, per_kernel); pt_launch_shade(st, cfg, ln.d_scene, c->fr, q, b & 1, (uint32_t)b); }
@@ -146,6 +151,7 @@ int issue(ptc_ctx* c, uint32_t k) {
   int rc = ensure_lane_queues(c, (uint32_t)cap);
   if (rc) return rc;
   if (alpha_on(c) && (rc = ensure_alpha_queues(c))) return rc;
+  if (glass_on(c) && (rc = ensure_glass_queues(c))) return rc;
   if ((rc = run_batch(c, (int)(c->batches_issued % (uint64_t)c->n_lanes), c->sample_base + c->samples_done, k))) return rc;
   c->samples_done += k;
   c->stats.paths += cap;
@@ -289,6 +295,7 @@ void Lane::teardown() {
   if (acc_done) (void)hipEventDestroy(acc_done);
   free_all(allocs);
   free_all(aq_allocs);
+  free_all(gq_allocs);
   if (q.cnt) (void)hipFree(q.cnt);
   if (q.stats) (void)hipFree(q.stats);
   if (q.seg_ray[0]) (void)hipFree(q.seg_ray[0]);
@@ -316,6 +323,8 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   if ((rc = upload_lights(c))) return rc;      // a changed light table: nothing is queued any more that reads the old one
   if ((rc = alpha_upload(c))) return rc;       // the alpha tables of a scene committed since the last frame
   if (c->alpha.counters.p) HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
+  if ((rc = glass_upload(c))) return rc;       // the glass tables likewise
+  if (c->glass.counters.p) HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
   if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
@@ -359,8 +368,8 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
     // no need to ask the driver how much memory is free (a call of 0.1-0.2 ms, every frame of a viewer's loop)
   } else {   // no more than 60 % of the device memory that is free now (plus what the lanes' queues already hold) goes into queues
     size_t free_b = 0, total_b = 0, held = 0;
-    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0);
-    for (const auto& ln : c->lanes) held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath;
+    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0);
+    for (const auto& ln : c->lanes) held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath + (size_t)ln.gq.cap * kGlassBytesPerPath;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
       const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / per_path;
       if (fit < batch_paths) batch_paths = fit;
@@ -378,6 +387,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->stats.n_emitters = keep.n_emitters; c->stats.bvh_max_depth = keep.bvh_max_depth;
   c->stats.bvh_sa_cost = keep.bvh_sa_cost; c->stats.bvh_sa_cost_built = keep.bvh_sa_cost_built; c->stats.seconds_rebuild = keep.seconds_rebuild;
   c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
+  c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions;
   c->in_frame = true;
   c->probes.on = probe_pos != nullptr; c->probes.base = probe_base;
   return PTC_OK;
@@ -494,7 +504,8 @@ int ptc_frame_reserve(ptc_ctx* c) {
   if (c->fr.n_owned == 0) return PTC_OK;
   const uint32_t k = is_raster(c->integrator) ? 1u : (c->per_batch < (uint32_t)c->spp_total ? c->per_batch : (uint32_t)c->spp_total);
   { int rc = ensure_lane_queues(c, c->fr.n_owned * k); if (rc) return rc; }     // n_owned * per_batch fits 32 bits by construction (frame_begin)
-  return alpha_on(c) ? ensure_alpha_queues(c) : PTC_OK;
+  if (alpha_on(c)) { int rc = ensure_alpha_queues(c); if (rc) return rc; }
+  return glass_on(c) ? ensure_glass_queues(c) : PTC_OK;
 }
 
 int ptc_frame_add_samples(ptc_ctx* c, int n_samples) {

@@ -56,39 +56,44 @@ int alpha_upload(ptc_ctx* c) {
   return PTC_OK;
 }
 
-// 64 B of continuation and hit record and one flag byte per slot, beside the lane's queues; the small arrays (header words, per-segment counts, statistics) once
-int ensure_alpha_queues(ptc_ctx* c) {
+// A side queue per lane, as large as the lane's queues (grow only; waits for the work in flight first): 64 B of continuation and hit record per slot and, where
+// `flags` names a member, one flag byte per slot; the small arrays (header words, per-segment counts, statistics) once.  The alpha and the glass pass each keep one.
+int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags) {
   bool grow = false;
-  for (auto& ln : c->lanes) grow = grow || ln.aq.cap < ln.q.cap;
+  for (auto& ln : c->lanes) grow = grow || (ln.*queue).cap < ln.q.cap;
   if (!grow) return PTC_OK;
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   for (auto& ln : c->lanes) {
-    if (ln.aq.cap >= ln.q.cap) continue;
-    free_all(ln.aq_allocs);
-    ln.aq = DevQueues{}; ln.aq_flags = nullptr;
-    DevQueues aq{};
+    if ((ln.*queue).cap >= ln.q.cap) continue;
+    std::vector<void*>& allocs = ln.*owner;
+    free_all(allocs);
+    ln.*queue = DevQueues{};
+    if (flags) ln.*flags = nullptr;
+    DevQueues sq{};
     const size_t slots = ptc_seg_slots(ln.q.cap, (uint32_t)c->cfg.shade_waves);
     const size_t per = PTC_MAX_SEGMENTS + 64;
     uint32_t* segs = nullptr;
-    int rc = dev_alloc(c, ln.aq_allocs, &aq.ray[0].A, slots);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &aq.ray[0].B, slots);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &aq.ray[0].C, slots);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &aq.hit, slots);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &ln.aq_flags, slots);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &aq.cnt, (size_t)CNT_N);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &aq.stats, (size_t)ST_N * ST_STRIDE);
-    if (!rc) rc = dev_alloc(c, ln.aq_allocs, &segs, 5 * per);
-    if (rc) { free_all(ln.aq_allocs); ln.aq_flags = nullptr; return rc; }
-    HIP_TRY(c, hipMemset(aq.cnt, 0, CNT_N * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemset(aq.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
+    int rc = dev_alloc(c, allocs, &sq.ray[0].A, slots);
+    if (!rc) rc = dev_alloc(c, allocs, &sq.ray[0].B, slots);
+    if (!rc) rc = dev_alloc(c, allocs, &sq.ray[0].C, slots);
+    if (!rc) rc = dev_alloc(c, allocs, &sq.hit, slots);
+    if (!rc && flags) rc = dev_alloc(c, allocs, &(ln.*flags), slots);
+    if (!rc) rc = dev_alloc(c, allocs, &sq.cnt, (size_t)CNT_N);
+    if (!rc) rc = dev_alloc(c, allocs, &sq.stats, (size_t)ST_N * ST_STRIDE);
+    if (!rc) rc = dev_alloc(c, allocs, &segs, 5 * per);
+    if (rc) { free_all(allocs); if (flags) ln.*flags = nullptr; return rc; }
+    HIP_TRY(c, hipMemset(sq.cnt, 0, CNT_N * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(sq.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(segs, 0, 5 * per * sizeof(uint32_t)));
-    aq.ray[1] = aq.ray[0];
-    aq.seg_ray[0] = segs; aq.seg_ray[1] = segs + per; aq.seg_sh = segs + 2 * per; aq.pre_ray = segs + 3 * per; aq.pre_sh = segs + 4 * per;      // seg_sh stays zero: the view has no shadow queue
-    aq.cap = ln.q.cap;
-    ln.aq = aq;
+    sq.ray[1] = sq.ray[0];
+    sq.seg_ray[0] = segs; sq.seg_ray[1] = segs + per; sq.seg_sh = segs + 2 * per; sq.pre_ray = segs + 3 * per; sq.pre_sh = segs + 4 * per;      // seg_sh stays zero: the view has no shadow queue
+    sq.cap = ln.q.cap;
+    ln.*queue = sq;
   }
   return PTC_OK;
 }
+
+int ensure_alpha_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::aq, &Lane::aq_allocs, &Lane::aq_flags); }
 
 // The host cannot know how many rays pass without a read-back, so a resolution queues every round it may need: filter, then max_layers x (scan, trace, filter).  A round
 // with nothing left is three launches that find their queue empty.
@@ -131,6 +136,7 @@ int ptc_set_material_alpha(ptc_ctx* c, int material, int mode, float cutoff) {
   const HostMaterial& m = c->mats[(size_t)material];
   if (m.emissive[0] != 0.0f || m.emissive[1] != 0.0f || m.emissive[2] != 0.0f)
     return fail(c, PTC_E_ARG, "set_material_alpha: the material is emissive (emitters are sampled by area without regard to coverage: they stay opaque)");
+  if (glass_tau(c, material) > 0.0f) return fail(c, PTC_E_ARG, "set_material_alpha: the material is transmissive (ptc_set_material_transmission: such a material stays OPAQUE)");
   if (c->alpha.mode.size() < c->mats.size()) { c->alpha.mode.resize(c->mats.size(), PTC_ALPHA_OPAQUE); c->alpha.cutoff.resize(c->mats.size(), 0.5f); }
   c->alpha.mode[(size_t)material] = mode; c->alpha.cutoff[(size_t)material] = cutoff;
   return PTC_OK;

@@ -1,0 +1,221 @@
+// ptc_api_glass.cpp — dielectric transmission over the C-ABI (pt_glass.h): the material calls, the tables of the committed scene, the lanes' glass
+// queues, the rounds of a resolution as run_batch and the debug hook queue them, the statistics and the ptc_debug_glass_* hooks.
+#include "ptc_ctx.h"
+
+#include <cmath>
+
+using namespace ptc_detail;
+
+namespace {
+DevGlass dev_glass(const ptc_ctx* c) { return DevGlass{c->glass.bits.p, c->glass.mats.p, (uint32_t)c->glass.frame_interactions, c->glass.counters.p}; }
+
+// the lane's glass queue with the segment layout of the batch whose queues are q
+DevQueues glass_view(const ptc_ctx* c, int l, const DevQueues& q) {
+  DevQueues gq = c->lanes[(size_t)l].gq;
+  gq.lpath = q.lpath;
+  gq.n_seg = q.n_seg; gq.seg_len = q.seg_len;
+  return gq;
+}
+
+void glass_tables(const ptc_ctx* c, std::vector<uint32_t>& bits, std::vector<pt_glass_mat>& mats, uint32_t& n) {
+  n = pt_glass_tables(c->built->tri_mat, c->mats.size(), c->glass.params, bits, mats);
+}
+}  // namespace
+
+namespace ptc_detail {
+int glass_upload(ptc_ctx* c) {
+  if (!c->glass.dirty) return PTC_OK;
+  std::vector<uint32_t> bits; std::vector<pt_glass_mat> mats;
+  uint32_t n = 0;
+  glass_tables(c, bits, mats, n);
+  if (n) {
+    static_assert(sizeof(pt_glass_mat) == 32, "two 16-byte units per material");
+    int rc = ensure_buf(c, c->glass.bits, bits.size());
+    if (!rc) rc = ensure_buf(c, c->glass.mats, mats.size() * 2u);
+    if (!rc) rc = ensure_buf(c, c->glass.counters, (size_t)PT_GLASS_COUNTERS);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(c->glass.bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->glass.mats.p, mats.data(), mats.size() * sizeof(pt_glass_mat), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+  }
+  c->glass.n_prims = n;
+  c->glass.dirty = false;
+  return PTC_OK;
+}
+
+int ensure_glass_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::gq, &Lane::gq_allocs, nullptr); }      // no flag bytes: the glass pass has no shadow walk
+
+// The host cannot know how many rays go on without a read-back, so a resolution queues every round it may need: filter, then max_interactions x (scan, trace, [alpha],
+// filter).  A round with nothing left is launches that find their queue empty.  In round r the continuations' hits are first resolved by the alpha pass on the glass
+// view; its bounce argument only enters alpha's RNG index, and the value gives fresh numbers per interaction.
+void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, uint32_t* j_out) {
+  ScopedSpan t(c, st, 6);
+  const DevQueues gq = glass_view(c, l, q);
+  const DevGlass gl = dev_glass(c);
+  const bool alpha = alpha_on(c);
+  pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/true, j_out);
+  for (uint32_t r = 0; r < gl.max_interactions; ++r) {
+    pt_launch_scan(st, cfg, gq, 0);
+    pt_launch_trace_closest(st, cfg, sc, gq, 0, false);
+    if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, gq, 0, 0x01000000u + (bounce + 1u) * 64u + r, PT_ALPHA_FORM_CLOSEST, nullptr);
+    pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/false, j_out);
+  }
+}
+}  // namespace ptc_detail
+
+extern "C" {
+void ptc_transmission_default_params(ptc_transmission_params* out) {
+  if (!out) return;
+  out->transmission = 0.0f; out->ior = 1.5f; out->thin_walled = 1;
+  out->attenuation_color[0] = out->attenuation_color[1] = out->attenuation_color[2] = 1.0f;
+  out->attenuation_distance = 0.0f;
+}
+
+int ptc_set_material_transmission(ptc_ctx* c, int material, const ptc_transmission_params* p) {
+  if (!c) return PTC_E_ARG;
+  if (c->committed) return fail(c, PTC_E_STATE, "set_material_transmission: the scene is committed (transmission belongs to the description: before ptc_scene_commit)");
+  if (!p) return fail(c, PTC_E_ARG, "set_material_transmission: null pointer");
+  if (material < 0 || (size_t)material >= c->mats.size()) return fail(c, PTC_E_ARG, "set_material_transmission: material out of range");
+  if (!(p->transmission >= 0.0f && p->transmission <= 1.0f)) return fail(c, PTC_E_ARG, "set_material_transmission: transmission is not a number in [0, 1]");
+  if (!(p->ior >= 1.0f) || !std::isfinite(p->ior)) return fail(c, PTC_E_ARG, "set_material_transmission: ior is not a finite number >= 1");
+  if (p->thin_walled != 0 && p->thin_walled != 1) return fail(c, PTC_E_ARG, "set_material_transmission: thin_walled is 0 or 1");
+  for (int k = 0; k < 3; ++k)
+    if (!(p->attenuation_color[k] > 0.0f && p->attenuation_color[k] <= 1.0f)) return fail(c, PTC_E_ARG, "set_material_transmission: attenuation_color is not in (0, 1]");
+  if (!(p->attenuation_distance >= 0.0f) || !std::isfinite(p->attenuation_distance)) return fail(c, PTC_E_ARG, "set_material_transmission: attenuation_distance is not a finite number >= 0");
+  const HostMaterial& m = c->mats[(size_t)material];
+  if (m.emissive[0] != 0.0f || m.emissive[1] != 0.0f || m.emissive[2] != 0.0f)
+    return fail(c, PTC_E_ARG, "set_material_transmission: the material is emissive (emitters are sampled by area as opaque surfaces)");
+  if ((size_t)material < c->alpha.mode.size() && c->alpha.mode[(size_t)material] != PTC_ALPHA_OPAQUE)
+    return fail(c, PTC_E_ARG, "set_material_transmission: the material's alpha mode is not OPAQUE");
+  if (c->glass.params.size() < c->mats.size()) {
+    ptc_transmission_params def;
+    ptc_transmission_default_params(&def);
+    c->glass.params.resize(c->mats.size(), def);
+  }
+  c->glass.params[(size_t)material] = *p;
+  return PTC_OK;
+}
+
+int ptc_get_material_transmission(const ptc_ctx* c, int material, ptc_transmission_params* out) {
+  if (!c || !out || material < 0 || (size_t)material >= c->mats.size()) return PTC_E_ARG;
+  if ((size_t)material < c->glass.params.size()) *out = c->glass.params[(size_t)material];
+  else ptc_transmission_default_params(out);
+  return PTC_OK;
+}
+
+int ptc_set_glass_max_interactions(ptc_ctx* c, int n) {
+  if (!c) return PTC_E_ARG;
+  if (n < 1 || n > PT_GLASS_MAX_INTERACTIONS) return fail(c, PTC_E_ARG, "set_glass_max_interactions: 1 .. 32");
+  c->glass.max_interactions = n;
+  return PTC_OK;
+}
+
+int ptc_get_glass_stats(ptc_ctx* c, ptc_glass_stats* out) {
+  if (!c) return PTC_E_ARG;
+  if (!out) return fail(c, PTC_E_ARG, "get_glass_stats: null pointer");
+  std::memset(out, 0, sizeof *out);
+  if (c->device < 0) return PTC_OK;
+  ptc_stats unused;
+  { int rc = ptc_get_stats(c, &unused); if (rc) return rc; }      // flushes, waits and collects the timing spans
+  if (c->glass.counters.p) {
+    unsigned long long v[PT_GLASS_COUNTERS];
+    HIP_TRY(c, hipMemcpy(v, c->glass.counters.p, sizeof v, hipMemcpyDeviceToHost));
+    out->reflections = v[PT_GLASS_REFLECTIONS]; out->refractions = v[PT_GLASS_REFRACTIONS]; out->standing = v[PT_GLASS_STANDING]; out->exhausted = v[PT_GLASS_EXHAUSTED_N];
+  }
+  out->seconds_glass = c->glass.seconds;
+  return PTC_OK;
+}
+
+// ---- test hooks -------------------------------------------------------------------------------------------------------------------------------------
+int ptc_debug_glass_closest(ptc_ctx* c, const float* origins, const float* dirs, const uint32_t* keys, uint32_t n, uint32_t bounce,
+                            float* out_t, int32_t* out_prim, float* out_uv, float* out_ray10, uint32_t* out_j) {
+  if (!c) return PTC_E_ARG;
+  if (c->device >= 0 && (!origins || !dirs || !keys || !out_t || !out_prim || !out_uv || !out_ray10 || !out_j || n == 0 || bounce > 0x0000ffffu)) return fail(c, PTC_E_ARG, "debug_glass_closest: bad argument");
+  // what ptc_api_debug.cpp's ray hooks need — a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared — and the
+  // alpha and glass tables, queues and counters of the committed scene
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->committed) return fail(c, PTC_E_STATE, "debug_glass_closest: scene not committed");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  c->in_frame = false; c->pending = 0; drop_guides(c);
+  int rc = ensure_lane_queues(c, n);
+  if (rc) return rc;
+  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
+  if ((rc = alpha_upload(c))) return rc;
+  if ((rc = glass_upload(c))) return rc;
+  if (alpha_on(c)) {
+    if ((rc = ensure_alpha_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
+  }
+  if (glass_on(c)) {
+    if ((rc = ensure_glass_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+  }
+  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
+  c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions;
+  const Lane& ln = c->lanes[0];
+  std::vector<float4> A(n), B(n), C(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
+    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
+    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 1.0f, 1.0f);
+    C[i] = make_float4(1.0f, 1.0f, fi, fk);
+  }
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  DevBuf<uint32_t> jn;
+  if ((rc = ensure_buf(c, jn, n))) return rc;
+  HIP_TRY(c, hipMemset(jn.p, 0, (size_t)n * 4));
+  const DevQueues q = batch_queues(c, 0, n);
+  const DevScene sc = lane_scene(c, 0);
+  pt_launch_set_counts(ln.stream, c->cfg, q, n, 0);
+  pt_launch_trace_closest(ln.stream, c->cfg, sc, q, 0, false);
+  if (alpha_on(c)) alpha_resolve_closest(c, 0, ln.stream, c->cfg, sc, q, 0, bounce, PT_ALPHA_FORM_CLOSEST, nullptr);
+  if (glass_on(c)) glass_resolve_closest(c, 0, ln.stream, c->cfg, sc, q, 0, bounce, jn.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(ln.stream));
+  std::vector<float4> H(n);
+  HIP_TRY(c, hipMemcpy(H.data(), ln.q.hit, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(A.data(), ln.q.ray[0].A, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.data(), ln.q.ray[0].B, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(C.data(), ln.q.ray[0].C, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(out_j, jn.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i) {
+    int32_t pc; std::memcpy(&pc, &H[i].y, 4);
+    out_t[i] = H[i].x; out_prim[i] = pc < 0 ? -1 : (pc & 0x0fffffff); out_uv[i * 2] = H[i].z; out_uv[i * 2 + 1] = H[i].w;
+    float* r = out_ray10 + (size_t)i * 10;
+    r[0] = A[i].x; r[1] = A[i].y; r[2] = A[i].z; r[3] = A[i].w; r[4] = B[i].x; r[5] = B[i].y; r[6] = B[i].z; r[7] = B[i].w; r[8] = C[i].x; r[9] = C[i].y;
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_glass_interact(const ptc_transmission_params* p, ptc_glass_interaction* io) {
+  if (!p || !io || !std::isfinite(io->t)) return PTC_E_ARG;      // a hit record's t is finite
+  const pt_glass_mat m = pt_glass_make_mat(*p);
+  v3 o = V3(0.0f, 0.0f, 0.0f), d = V3(io->d), T = V3(io->T);
+  const bool front = io->front != 0;
+  pt_glass_beer(m, front, io->t, T);
+  float F = 0.0f;
+  io->outcome = pt_glass_interact(m, V3(io->P), V3(io->ng), V3(io->ns), front, V3(io->base), io->metallic, io->ray_eps, io->u_s, io->u_e, io->j, io->max_interactions, o, d, T, F);
+  io->o_out[0] = o.x; io->o_out[1] = o.y; io->o_out[2] = o.z;
+  io->d_out[0] = d.x; io->d_out[1] = d.y; io->d_out[2] = d.z;
+  io->T_out[0] = T.x; io->T_out[1] = T.y; io->T_out[2] = T.z;
+  io->F = F;
+  return PTC_OK;
+}
+
+int ptc_debug_get_glass_tables(ptc_ctx* c, uint32_t* n_prims, uint32_t* bits, uint32_t* n_mats, float* mats8) {
+  if (!c) return PTC_E_ARG;
+  if (!c->committed) return fail(c, PTC_E_STATE, "debug_get_glass_tables: scene not committed");
+  std::vector<uint32_t> b; std::vector<pt_glass_mat> m;
+  uint32_t n = 0;
+  glass_tables(c, b, m, n);
+  if (n_prims) *n_prims = (uint32_t)c->built->tri_mat.size();
+  if (n_mats) *n_mats = (uint32_t)c->mats.size();
+  if (bits && !b.empty()) std::memcpy(bits, b.data(), b.size() * sizeof(uint32_t));
+  if (mats8 && !m.empty()) std::memcpy(mats8, m.data(), m.size() * sizeof(pt_glass_mat));
+  for (const Lane& ln : c->lanes) if (ln.gq.cap) return 1;
+  return PTC_OK;
+}
+}  // extern "C"

@@ -19,6 +19,7 @@
 #include "pt_lens.h"
 #include "pt_lights.h"
 #include "pt_alpha.h"
+#include "pt_glass.h"
 #include "pt_display.h"
 #include "pt_probes.h"
 
@@ -51,7 +52,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg);
     if (r_ != ncclSuccess) return fail((c), PTC_E_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
   } while (0)
 
-struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution
+struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution, 6 a glass resolution
 
 // An array in HBM and its owner: freed when the owner goes (with the context: after ptc_destroy made the device current), or early by release()
 template <class T> struct DevBuf {
@@ -97,6 +98,9 @@ struct Lane {
   DevQueues aq{};
   uint8_t* aq_flags = nullptr;
   std::vector<void*> aq_allocs;
+  // dielectric transmission (pt_glass.h): the lane's glass queue, a DevQueues view like aq.  Allocated only while the committed scene has a transmissive material
+  DevQueues gq{};
+  std::vector<void*> gq_allocs;
   void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
   void teardown();                  // ptc_destroy: everything but the overflow slabs (release_scene's), the streams after what ran on them
 };
@@ -183,6 +187,20 @@ struct Alpha {
   DevBuf<float2> mode_cutoff;
   DevBuf<unsigned long long> counters;
   double seconds = 0.0;             // the frame's alpha resolutions (spans of kind 5)
+};
+
+// dielectric transmission (pt_glass.h): params are what the calls recorded, by material id (shorter than the material list: the rest is not transmissive); the device
+// tables are those of the committed scene, built from its per-primitive material ids and uploaded by the first ptc_frame_begin (or ray hook) after the commit
+struct Glass {
+  std::vector<ptc_transmission_params> params;
+  int max_interactions = PT_GLASS_DEFAULT_INTERACTIONS;     // a context setting: kept across ptc_scene_begin
+  int frame_interactions = PT_GLASS_DEFAULT_INTERACTIONS;   // what the frame in progress (or the last ray hook) was begun with
+  bool dirty = true;                // the committed scene's tables are not on the device yet
+  uint32_t n_prims = 0;             // primitives of the committed scene whose material has tau > 0, as of the last upload; 0: no pass, no queue, nothing allocated
+  DevBuf<uint32_t> bits;
+  DevBuf<float4> mats;
+  DevBuf<unsigned long long> counters;
+  double seconds = 0.0;             // the frame's glass resolutions (spans of kind 6)
 };
 
 // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
@@ -303,6 +321,7 @@ struct ptc_ctx {
   ptc_lens_params lens{0.0f, 1.0f, 0, 0.0f};   // the camera's lens (ptc_set_camera_lens): kept across ptc_set_camera, reset by ptc_scene_begin; R = 0: the pinhole, k_raygen
   ptc_detail::Lights lights;
   ptc_detail::Alpha alpha;
+  ptc_detail::Glass glass;
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -514,9 +533,17 @@ int scene_commit(ptc_ctx* c, bool device_ok);
 // ---- ptc_api_alpha.cpp: alpha coverage (pt_alpha.h) ------------------------------------------------------------------------------------------------
 int alpha_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
 inline bool alpha_on(const ptc_ctx* c) { return c->alpha.n_prims > 0; }
+int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags);      // ptc_api_alpha.cpp: what the two below share
 int ensure_alpha_queues(ptc_ctx* c);                   // every lane: an alpha queue as large as its queues (grow only; waits for the work in flight first)
 void alpha_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, int form, uint32_t* layers_out);
 void alpha_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out);
+
+// ---- ptc_api_glass.cpp: dielectric transmission (pt_glass.h) ---------------------------------------------------------------------------------------
+int glass_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
+inline bool glass_on(const ptc_ctx* c) { return c->glass.n_prims > 0; }
+inline float glass_tau(const ptc_ctx* c, int material) { return (size_t)material < c->glass.params.size() ? c->glass.params[(size_t)material].transmission : 0.0f; }
+int ensure_glass_queues(ptc_ctx* c);                   // every lane: a glass queue as large as its queues (grow only; waits for the work in flight first)
+void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, uint32_t* j_out);
 
 // ---- ptc_api_image.cpp ---------------------------------------------------------------------------------------------------------------------------
 DevAdaptive dev_adaptive(const ptc_ctx* c);

@@ -48,6 +48,7 @@ public:
       const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
       if (id < 0) return id;
       if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
+      if (m.transmission.transmission > 0.0f) { const int rc = ptc_set_material_transmission(ctx, id, &m.transmission); if (rc < 0) return rc; }
       mat_id.push_back(id);
     }
     // primitive index (FlatScene order: mesh order, then primitive order) -> its JSON

@@ -151,7 +151,9 @@ private:
 
 // ---- flat result ------------------------------------------------------------------------------------
 struct Material { float base_color[4] = {1, 1, 1, 1}; float metallic = 1.0f, roughness = 1.0f; float emissive[3] = {0, 0, 0}; int tex_color = -1, tex_normal = -1, tex_mr = -1;      // tex_*: index into FlatScene::textures
-                  int alpha_mode = PTC_ALPHA_OPAQUE; float alpha_cutoff = 0.5f; };   // glTF alphaMode / alphaCutoff (an emissive material stays OPAQUE: ptc_set_material_alpha's rule)
+                  int alpha_mode = PTC_ALPHA_OPAQUE; float alpha_cutoff = 0.5f;
+                  // KHR_materials_transmission / _ior / _volume (ptc_set_material_transmission): transmission 0 unless the material is OPAQUE and not emissive
+                  ptc_transmission_params transmission = {0.0f, 1.5f, 1, {1.0f, 1.0f, 1.0f}, 0.0f}; };   // glTF alphaMode / alphaCutoff (an emissive material stays OPAQUE: ptc_set_material_alpha's rule)
 struct Texture { int w = 0, h = 0; std::vector<std::uint8_t> rgba; };
 struct Primitive { std::vector<ptc_vertex> vertices; std::vector<std::uint32_t> indices; int material = 0; };
 struct Instance { int primitive; std::array<float, 16> model; };   // column-major
@@ -524,6 +526,20 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
       if (o.alpha_cutoff > 1.0f) o.alpha_cutoff = 1.0f;
       if (o.emissive[0] != 0.0f || o.emissive[1] != 0.0f || o.emissive[2] != 0.0f) o.alpha_mode = PTC_ALPHA_OPAQUE;      // emitters are sampled by area: they stay opaque
     }
+    if (const JValue* ext = m.get("extensions")) {      // transmissionFactor (its texture is ignored), ior, and a volume: thicknessFactor > 0 means a solid
+      auto clampf = [](double v, double lo, double hi) { return (float)(v < lo || !(v == v) ? lo : v > hi ? hi : v); };
+      ptc_transmission_params& t = o.transmission;
+      if (const JValue* tr = ext->get("KHR_materials_transmission")) t.transmission = clampf(tr->number("transmissionFactor", 0.0), 0.0, 1.0);
+      if (const JValue* io = ext->get("KHR_materials_ior")) t.ior = clampf(io->number("ior", 1.5), 1.0, 1.0e6);      // glTF also allows 0 ("specular-glossiness"): read as 1
+      if (const JValue* vo = ext->get("KHR_materials_volume")) {
+        t.thin_walled = vo->number("thicknessFactor", 0.0) > 0.0 ? 0 : 1;
+        const auto& ac = vo->array("attenuationColor");
+        for (size_t k = 0; k < 3 && k < ac.size(); ++k) t.attenuation_color[k] = clampf(ac[k].num, 9.5367431640625e-7, 1.0);
+        const double ad = vo->number("attenuationDistance", 0.0);      // glTF's default is +infinity: no attenuation, which 0 says here
+        t.attenuation_distance = (ad > 0.0 && ad < 3.0e38) ? (float)ad : 0.0f;
+      }
+      if (o.alpha_mode != PTC_ALPHA_OPAQUE || o.emissive[0] != 0.0f || o.emissive[1] != 0.0f || o.emissive[2] != 0.0f) t.transmission = 0.0f;
+    }
     out.materials.push_back(o);
   }
   int default_material = -1;
@@ -701,6 +717,7 @@ inline int upload(ptc_ctx* ctx, const FlatScene& s) {
     const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
     if (id < 0) return id;
     if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
+    if (m.transmission.transmission > 0.0f) { const int rc = ptc_set_material_transmission(ctx, id, &m.transmission); if (rc < 0) return rc; }
     mat_id.push_back(id);
   }
   for (const Primitive& p : s.primitives) {

@@ -41,6 +41,11 @@ struct MaterialData {
   std::array<float, 3> emissive{0, 0, 0};
   int alphaMode = PTC_ALPHA_OPAQUE;      // glTF alphaMode: PTC_ALPHA_OPAQUE / _MASK / _BLEND (ptc_set_material_alpha; an emissive material must stay opaque)
   float alphaCutoff = 0.5f;
+  // KHR_materials_transmission / _ior / _volume (ptc_set_material_transmission): an emissive or non-opaque material must stay at transmission 0
+  float transmission = 0.0f, ior = 1.5f;
+  bool thinWalled = true;
+  std::array<float, 3> attenuationColor{1, 1, 1};
+  float attenuationDistance = 0.0f;
 };
 
 // The viewer's start-up camera: app::CameraController's defaults (src/gltf_viewer/CameraController.hpp:25-40: position 0, pitch 0,
@@ -97,6 +102,10 @@ public:
   auto addMaterial(MaterialData const& m) -> int {
     const int id = ck(ptc_add_material(_ctx, m.color.data(), m.metallic, m.roughness, m.emissive.data(), -1, -1, -1));
     if (m.alphaMode != PTC_ALPHA_OPAQUE) ck(ptc_set_material_alpha(_ctx, id, m.alphaMode, m.alphaCutoff));
+    if (m.transmission > 0.0f) {
+      const ptc_transmission_params t{m.transmission, m.ior, m.thinWalled ? 1 : 0, {m.attenuationColor[0], m.attenuationColor[1], m.attenuationColor[2]}, m.attenuationDistance};
+      ck(ptc_set_material_transmission(_ctx, id, &t));
+    }
     return id;
   }
   // one ptc mesh per PrimitiveSpan, firstVertex applied like drawIndexed's vertexOffset (PbrRenderSystem.cpp:454-460)

@@ -4,7 +4,7 @@
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
-//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha]
+//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
 //              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
 // --probe-grid NX,NY,NZ / --probes FILE with --probes-out sh.pfm: bake light probes instead of an image (ptc_render_probes) — the centres of the
@@ -20,6 +20,8 @@
 // Bad values are reported before any device work.
 // --no-alpha: a --gltf scene is rendered with the alphaMode of its materials (MASK: holes where the alpha lies below alphaCutoff, BLEND: stochastic coverage and
 // attenuated shadows; ptc_set_material_alpha), path integrator only; --no-alpha renders every material opaque, as the raster integrators always do.
+// --no-transmission: a --gltf scene is rendered with KHR_materials_transmission, KHR_materials_ior and KHR_materials_volume of its materials (glass and thin panes;
+// ptc_set_material_transmission), path integrator only; --no-transmission renders them as the opaque surfaces they were before.
 // --aperture R: the thin lens (ptc_set_camera_lens) with aperture radius R in world units — depth of field, path integrator only.  --blades N: a regular polygon
 // of 3..16 sides instead of the disk, --aperture-rotation T: its rotation in turns, [0, 1).  --focus D: the view depth of the plane of focus (default 1);
 // --focus-pixel X,Y: focus on what that pixel's centre sees — the guides are traced once before the render and ptc_focus_distance_at_pixel is taken (a miss is
@@ -214,6 +216,7 @@ int main(int argc, char** argv) {
   std::vector<ptc_light_params> lights;
   bool noGltfLights = false;
   bool noAlpha = false;                      // --no-alpha: ignore the asset's alpha modes
+  bool noTransmission = false;               // --no-transmission: ignore the asset's transmission extensions
   ptc_display_params disp = pbr::PathTraceRenderSystem::displayDefaults();      // --exposure / --auto-exposure / --key / --tonemap / --srgb
   bool useDisplay = false, haveKey = false;
   double exposureEv = 0.0;
@@ -236,7 +239,7 @@ int main(int argc, char** argv) {
     else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
-    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true;
+    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true;
     else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
     else if (a == "--key") { disp.key = (float)std::atof(next()); haveKey = true; } else if (a == "--srgb") { disp.oetf = PTC_OETF_SRGB; useDisplay = true; }
     else if (a == "--tonemap") {
@@ -338,6 +341,13 @@ int main(int argc, char** argv) {
         fs = pbr::gltf::load(gltf);
         rs.beginScene();
         if (pbr::gltf::upload(rs.handle(), fs) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+      }
+      if (noTransmission) {      // every material back to transmission 0
+        int nMats = 0;
+        if (ptc_debug_get_description(rs.handle(), &nMats, nullptr) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+        ptc_transmission_params off;
+        ptc_transmission_default_params(&off);
+        for (int m = 0; m < nMats; ++m) (void)ptc_set_material_transmission(rs.handle(), m, &off);
       }
       if (noAlpha) {      // every material back to OPAQUE (an emissive one is refused: it is opaque anyway)
         int nMats = 0;

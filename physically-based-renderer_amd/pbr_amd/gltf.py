@@ -416,6 +416,15 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
             g["alphaMode"] = str(mode).upper() if str(mode).lower() in ("opaque", "mask", "blend") else str(mode)
             if str(mode).lower() == "mask":
                 g["alphaCutoff"] = float(getattr(m, "alpha_cutoff", 0.5))
+        if getattr(m, "transmission", 0.0) > 0.0:      # KHR_materials_transmission, _ior and, for a solid, _volume (thicknessFactor 1: "has a volume")
+            ext = g.setdefault("extensions", {})
+            ext["KHR_materials_transmission"] = {"transmissionFactor": float(m.transmission)}
+            ext["KHR_materials_ior"] = {"ior": float(getattr(m, "ior", 1.5))}
+            if not getattr(m, "thin_walled", True):
+                vol = {"thicknessFactor": 1.0, "attenuationColor": [float(x) for x in getattr(m, "attenuation_color", (1.0, 1.0, 1.0))]}
+                if getattr(m, "attenuation_distance", 0.0) > 0.0:
+                    vol["attenuationDistance"] = float(m.attenuation_distance)
+                ext["KHR_materials_volume"] = vol
         mats.append(g)
 
     if nodes is None:
@@ -494,8 +503,9 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
         doc["images"] = images
         doc["samplers"] = [{"magFilter": 9728, "minFilter": 9728, "wrapS": 10497, "wrapT": 10497}]   # NEAREST, REPEAT (what the reference uses regardless)
         doc["textures"] = [{"source": k, "sampler": 0} for k in range(len(images))]
-    if any("extensions" in g for g in mats):
-        doc["extensionsUsed"] = ["KHR_materials_emissive_strength"]
+    used = sorted({k for g in mats for k in g.get("extensions", {})})
+    if used:
+        doc["extensionsUsed"] = used
     if light_defs:
         doc["extensions"] = {"KHR_lights_punctual": {"lights": light_defs}}
         doc["extensionsUsed"] = doc.get("extensionsUsed", []) + ["KHR_lights_punctual"]

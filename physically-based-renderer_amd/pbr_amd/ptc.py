@@ -128,6 +128,22 @@ class PtcAlphaStats(_Struct):
     _fields_ = [("closest_passes", C.c_uint64), ("shadow_walked", C.c_uint64), ("shadow_passes", C.c_uint64), ("exhausted", C.c_uint64), ("seconds_alpha", C.c_double)]
 
 
+class PtcTransmissionParams(_Struct):
+    _fields_ = [("transmission", C.c_float), ("ior", C.c_float), ("thin_walled", C.c_int), ("attenuation_color", C.c_float * 3), ("attenuation_distance", C.c_float)]
+    _defaults_ = "ptc_transmission_default_params"
+    _unknown_ = "unknown transmission field {}"
+
+
+class PtcGlassStats(_Struct):
+    _fields_ = [("reflections", C.c_uint64), ("refractions", C.c_uint64), ("standing", C.c_uint64), ("exhausted", C.c_uint64), ("seconds_glass", C.c_double)]
+
+
+class PtcGlassInteraction(_Struct):
+    _fields_ = [("P", C.c_float * 3), ("ng", C.c_float * 3), ("ns", C.c_float * 3), ("front", C.c_int), ("d", C.c_float * 3), ("T", C.c_float * 3), ("t", C.c_float),
+                ("base", C.c_float * 3), ("metallic", C.c_float), ("u_s", C.c_float), ("u_e", C.c_float), ("j", C.c_uint32), ("max_interactions", C.c_uint32),
+                ("ray_eps", C.c_float), ("outcome", C.c_int), ("o_out", C.c_float * 3), ("d_out", C.c_float * 3), ("T_out", C.c_float * 3), ("F", C.c_float)]
+
+
 class PtcDenoiseParams(_Struct):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
     _defaults_ = "ptc_denoise_default_params"
@@ -338,8 +354,29 @@ def _alpha_prototypes():
     }
 
 
+def _glass_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_glass.h declares, in the header's order; exported under ptcx_ like ptc_alpha.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, fp = C.c_void_p, C.POINTER(C.c_float)
+    u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    tp = C.POINTER(PtcTransmissionParams)
+    return {
+        "ptc_transmission_default_params": (None, [tp]),
+        "ptc_set_material_transmission": (i, [vp, i, tp]),
+        "ptc_get_material_transmission": (i, [vp, i, tp]),
+        "ptc_set_glass_max_interactions": (i, [vp, i]),
+        "ptc_get_glass_stats": (i, [vp, C.POINTER(PtcGlassStats)]),
+        "ptc_debug_glass_closest": (i, [vp, fp, fp, u32p, u32, u32, fp, i32p, fp, fp, u32p]),
+        "ptc_debug_glass_interact": (i, [tp, C.POINTER(PtcGlassInteraction)]),
+        "ptc_debug_get_glass_tables": (i, [vp, u32p, u32p, u32p, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
+_GLASS_PROTOTYPES = _glass_prototypes()
+# every function include/ptc_glass.h declares, by the header's names
+GLASS_SYMBOLS = list(_GLASS_PROTOTYPES)
 # every function include/ptc_alpha.h declares, by the header's names
 ALPHA_SYMBOLS = list(_ALPHA_PROTOTYPES)
 # every symbol include/ptc.h declares (tests check the library exports all of them)
@@ -360,7 +397,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in _ALPHA_PROTOTYPES.items():
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -482,6 +519,26 @@ def alpha_decide(mode, cutoff, a, u):
     return bool(acc.value), np.float32(tr.value)
 
 
+def transmission_params(**fields):
+    """A ptc_transmission_params: the defaults (transmission 0, ior 1.5, thin-walled, no attenuation) with `fields` replaced."""
+    return PtcTransmissionParams.defaults(**fields)
+
+
+def _material_transmission(m):
+    """The ptc_transmission_params of a scene.Material (or anything with its fields)."""
+    return transmission_params(transmission=getattr(m, "transmission", 0.0), ior=getattr(m, "ior", 1.5), thin_walled=1 if getattr(m, "thin_walled", True) else 0,
+                               attenuation_color=getattr(m, "attenuation_color", (1.0, 1.0, 1.0)), attenuation_distance=getattr(m, "attenuation_distance", 0.0))
+
+
+def glass_interact(params, **fields):
+    """ptc_debug_glass_interact: the host's evaluation of steps 2 to 4 of csrc/pt_glass.h for one hit.  Returns the struct as a dict (outcome, o_out, d_out, T_out, F, ..)."""
+    io = PtcGlassInteraction().update(**fields)
+    rc = load_library().ptc_debug_glass_interact(C.byref(params), C.byref(io))
+    if rc < 0:
+        raise PtcError("glass_interact: bad argument")
+    return io.as_dict()
+
+
 def display_params(**fields):
     """A ptc_display_params: the defaults with `fields` replaced.  `tonemap` takes a name (aces, neutral, reinhard, clamp) or a TONEMAP_* value, `oetf` a name
     (gamma22, srgb) or an OETF_* value."""
@@ -599,6 +656,8 @@ class PathTracer:
             mid = self._ck(L.ptc_add_material(h, _f(m.base_color)[1], m.metallic, m.roughness, _f(m.emissive)[1], m.tex_color, m.tex_normal, m.tex_mr))
             if str(getattr(m, "alpha_mode", "opaque")).lower() not in ("opaque", str(ALPHA_OPAQUE)):
                 self.set_material_alpha(mid, m.alpha_mode, getattr(m, "alpha_cutoff", 0.5))
+            if getattr(m, "transmission", 0.0) > 0.0:
+                self.set_material_transmission(mid, _material_transmission(m))
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
@@ -712,6 +771,43 @@ class PathTracer:
         bits, mc = np.zeros((npr.value + 31) // 32, np.uint32), np.zeros((nm.value, 2), np.float32)
         rc = self._ck(self._L.ptc_debug_get_alpha_tables(self._h, None, _ptr(bits), None, _ptr(mc)))
         return bits, mc[:, 0].copy().view(np.int32), mc[:, 1].copy(), int(npr.value), bool(rc)
+
+    # ---- dielectric transmission (csrc/pt_glass.h) ----------------------------------------------------------
+    def set_material_transmission(self, material, params=None, **fields):
+        """ptc_set_material_transmission, between add_material and the commit: a transmission_params(...) or its fields (transmission, ior, thin_walled,
+        attenuation_color, attenuation_distance) as keywords."""
+        self._ck(self._L.ptc_set_material_transmission(self._h, int(material), C.byref(params if params is not None else transmission_params(**fields))))
+        return self
+
+    def get_material_transmission(self, material):
+        return self._get(self._L.ptc_get_material_transmission, PtcTransmissionParams, int(material))
+
+    def set_glass_max_interactions(self, n):
+        self._ck(self._L.ptc_set_glass_max_interactions(self._h, int(n)))
+        return self
+
+    def glass_stats(self):
+        return self._get(self._L.ptc_get_glass_stats, PtcGlassStats)
+
+    def glass_closest(self, origins, dirs, keys, bounce=0):
+        """ptc_debug_glass_closest: explicit rays of throughput 1 through k_trace_closest, the alpha resolution and the glass resolution:
+        (t, prim, uv, o (n, 3), d (n, 3), T (n, 3), pdf word (n,), j)."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = o.shape[0]
+        assert d.shape[0] == n and k.size == n
+        t, prim, uv, ray, j = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros((n, 10), np.float32), np.zeros(n, np.uint32)
+        self._ck(self._L.ptc_debug_glass_closest(self._h, op, dp, _ptr(k), n, int(bounce), _ptr(t), _ptr(prim), _ptr(uv), _ptr(ray), _ptr(j)))
+        return t, prim, uv, ray[:, 0:3].copy(), ray[:, 3:6].copy(), ray[:, 6:9].copy(), ray[:, 9].copy(), j
+
+    def glass_tables(self):
+        """ptc_debug_get_glass_tables: (bits (ceil(n_prims / 32),) uint32, mats (n_mats, 8) float32 — word 2 holds thin's int bits —, n_prims, whether a glass queue is allocated)."""
+        npr, nm = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.ptc_debug_get_glass_tables(self._h, C.byref(npr), None, C.byref(nm), None))
+        bits, mats = np.zeros((npr.value + 31) // 32, np.uint32), np.zeros((nm.value, 8), np.float32)
+        rc = self._ck(self._L.ptc_debug_get_glass_tables(self._h, None, _ptr(bits), None, _ptr(mats)))
+        return bits, mats, int(npr.value), bool(rc)
 
     def set_camera(self, position, target, fov_y, aspect):
         self._ck(self._L.ptc_set_camera(self._h, _f(position)[1], _f(target)[1], fov_y, aspect))

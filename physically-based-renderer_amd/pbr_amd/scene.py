@@ -42,6 +42,11 @@ class Material:
     tex_mr: int = -1
     alpha_mode: str = "opaque"      # glTF alphaMode: "opaque", "mask" or "blend" (ptc_set_material_alpha); an emissive material stays opaque
     alpha_cutoff: float = 0.5       # MASK: the surface counts where its alpha reaches this
+    transmission: float = 0.0       # KHR_materials_transmission (ptc_set_material_transmission); an emissive or non-opaque material stays at 0
+    ior: float = 1.5                # KHR_materials_ior
+    thin_walled: bool = True        # glTF's "no volume"; False: a solid (KHR_materials_volume)
+    attenuation_color: tuple = (1.0, 1.0, 1.0)
+    attenuation_distance: float = 0.0   # 0: no attenuation
 
 
 @dataclasses.dataclass

@@ -413,6 +413,60 @@ def alpha_layers(n_mask: int = 3, n_blend: int = 2, texture_filter: str = "neare
     return d
 
 
+def glass_slab(thin: bool = False, thickness: float = 0.5, transmission: float = 1.0, ior: float = 1.5, base=(1.0, 1.0, 1.0), metallic: float = 0.0,
+               attenuation_color=(1.0, 1.0, 1.0), attenuation_distance: float = 0.0, sheet_alpha=None, emitter: bool = False, pane: bool = True,
+               texture_filter: str = "nearest", textured: bool = False) -> SceneDesc:
+    """The transmission test scene (csrc/pt_glass.h): a Lambert floor at y = 0 (primitives 0-1), an optional emissive quad facing down at y = 4 beside the view
+    (emitter=True: primitives 2-3), then the glass over x, z in [-2, 2]: a box slab from y = 1 to y = 1 + thickness (solid, six quads, outward normals, top first then
+    bottom) or a single pane at y = 1 (thin=True, normal +y); pane=False leaves the glass out.  sheet_alpha (0..1): a BLEND sheet of that constant alpha at y = 0.5,
+    added last.  textured=True gives the glass a 4x4 base-colour texture, so that the tint depends on the texel and the filter.  Seen from above, slanted."""
+    mats = [Material((0.7, 0.7, 0.7, 1.0), 0.0, 1.0)]
+    meshes = [MeshDesc(*_quad((-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4)), 0)]
+    if emitter:
+        mats.append(Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (20.0, 20.0, 20.0)))
+        meshes.append(MeshDesc(*_quad((-1.0, 4.0, -1.0), (1.0, 4.0, -1.0), (1.0, 4.0, 1.0), (-1.0, 4.0, 1.0)), len(mats) - 1))     # normal -y
+    textures = []
+    if pane:
+        if textured:
+            yy, xx = np.mgrid[0:4, 0:4]
+            textures.append(np.stack([(37 * xx + 90) % 200 + 55, (53 * yy + 60) % 200 + 55, (17 * (xx + yy)) % 200 + 55, np.full((4, 4), 255)], -1).astype(np.uint8))
+        mats.append(Material(tuple(base) + (1.0,), metallic, 0.2, (0, 0, 0), 0 if textured else -1, -1, -1, "opaque", 0.5, transmission, ior, thin,
+                             tuple(attenuation_color), attenuation_distance))
+        g = len(mats) - 1
+        y0, y1, a = 1.0, 1.0 + thickness, 2.0
+        if thin:
+            meshes.append(MeshDesc(*_quad((-a, y0, a), (a, y0, a), (a, y0, -a), (-a, y0, -a)), g))
+        else:
+            meshes.append(MeshDesc(*_quad((-a, y1, a), (a, y1, a), (a, y1, -a), (-a, y1, -a)), g))        # top, +y
+            meshes.append(MeshDesc(*_quad((-a, y0, -a), (a, y0, -a), (a, y0, a), (-a, y0, a)), g))        # bottom, -y
+            meshes.append(MeshDesc(*_quad((-a, y0, a), (a, y0, a), (a, y1, a), (-a, y1, a)), g))          # +z
+            meshes.append(MeshDesc(*_quad((a, y0, -a), (-a, y0, -a), (-a, y1, -a), (a, y1, -a)), g))      # -z
+            meshes.append(MeshDesc(*_quad((a, y0, a), (a, y0, -a), (a, y1, -a), (a, y1, a)), g))          # +x
+            meshes.append(MeshDesc(*_quad((-a, y0, -a), (-a, y0, a), (-a, y1, a), (-a, y1, -a)), g))      # -x
+    if sheet_alpha is not None:
+        mats.append(Material((0.9, 0.5, 0.3, float(sheet_alpha)), 0.0, 1.0, (0, 0, 0), -1, -1, -1, "blend", 0.5))
+        meshes.append(MeshDesc(*_quad((-3, 0.5, 3), (3, 0.5, 3), (3, 0.5, -3), (-3, 0.5, -3)), len(mats) - 1))
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    cam = CameraDesc((1.5, 6.0, 2.5), (0.0, 1.0, 0.0), math.radians(20.0), 1.0)
+    d = SceneDesc(mats, meshes, inst, cam, "glass_slab")
+    d.textures = textures
+    d.texture_filter = texture_filter
+    return d
+
+
+def glass_ball(nu: int = 24, nv: int = 12, ior: float = 1.5, transmission: float = 1.0, base=(1.0, 1.0, 1.0), env: float = 1.0, attenuation_color=(1.0, 1.0, 1.0),
+               attenuation_distance: float = 0.0) -> SceneDesc:
+    """A closed solid glass ball of radius 1 (smooth normals, 2 nu (nv - 1) triangles) in a constant environment of radiance `env`, and nothing else: with base 1
+    and no attenuation a white furnace — every path that is not exhausted carries throughput 1 into the environment."""
+    mats = [Material(tuple(base) + (1.0,), 0.0, 0.2, (0, 0, 0), -1, -1, -1, "opaque", 0.5, transmission, ior, False, tuple(attenuation_color), attenuation_distance)]
+    meshes = [MeshDesc(*uv_sphere(nu, nv, 1.0), 0)]
+    inst = [InstanceDesc(0, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0))]
+    cam = CameraDesc((0.0, 0.6, 3.2), (0.0, 0.0, 0.0), math.radians(40.0), 1.0)
+    d = SceneDesc(mats, meshes, inst, cam, "glass_ball")
+    d.env = np.full((4, 8, 3), env, np.float32)
+    return d
+
+
 def by_name(name: str, **kw) -> SceneDesc:
     return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
-            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers}[name](**kw)
+            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_ball": glass_ball}[name](**kw)

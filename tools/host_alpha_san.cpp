@@ -19,6 +19,7 @@ extern "C" {
 int ptc_add_texture_rgba8(ptc_ctx*, const uint8_t*, int, int) { return -1; }
 int ptc_add_material(ptc_ctx*, const float*, float, float, const float*, int, int, int) { return -1; }
 int ptc_set_material_alpha(ptc_ctx*, int, int, float) { return -1; }
+int ptc_set_material_transmission(ptc_ctx*, int, const ptc_transmission_params*) { return -1; }
 int ptc_add_mesh(ptc_ctx*, const ptc_vertex*, uint32_t, const uint32_t*, uint32_t, int) { return -1; }
 int ptc_add_instance_matrix(ptc_ctx*, int, const float*) { return -1; }
 int ptc_add_light(ptc_ctx*, const ptc_light_params*) { return -1; }

@@ -1,0 +1,127 @@
+// The host side of dielectric transmission (csrc/pt_glass.h: pt_glass_sigma2, pt_glass_beer, pt_glass_event, pt_glass_interact, pt_glass_tables) and the glTF loader's
+// KHR_materials_transmission / _ior / _volume parsing (host/gltf_loader.hpp) under AddressSanitizer and UndefinedBehaviorSanitizer: a stand-alone program, no GPU, no
+// library.  It evaluates the definition over a grid with special values (grazing and normal incidence, total internal reflection, NaN and infinite inputs), builds the
+// tables for primitive counts on and around a word of the bit table (material ids out of range and negative among them, parameter lists shorter than the material
+// list), loads a small glTF document whose materials carry every form of the three extensions, and prints a checksum.
+//   hipcc -std=c++17 -O1 -g -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//         -Iinclude -Iphysically-based-renderer_amd/csrc -Iphysically-based-renderer_amd/host tools/host_glass_san.cpp -o /tmp/host_glass_san && /tmp/host_glass_san
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <limits>
+#include <string>
+#include <vector>
+#include "pt_glass.h"
+#include "gltf_loader.hpp"
+
+// the loader's upload() names the C-ABI; this program has no library behind it and never calls upload()
+extern "C" {
+int ptc_add_texture_rgba8(ptc_ctx*, const uint8_t*, int, int) { return -1; }
+int ptc_add_material(ptc_ctx*, const float*, float, float, const float*, int, int, int) { return -1; }
+int ptc_set_material_alpha(ptc_ctx*, int, int, float) { return -1; }
+int ptc_set_material_transmission(ptc_ctx*, int, const ptc_transmission_params*) { return -1; }
+int ptc_add_mesh(ptc_ctx*, const ptc_vertex*, uint32_t, const uint32_t*, uint32_t, int) { return -1; }
+int ptc_add_instance_matrix(ptc_ctx*, int, const float*) { return -1; }
+int ptc_add_light(ptc_ctx*, const ptc_light_params*) { return -1; }
+void ptc_light_default_params(ptc_light_params* p) { std::memset(p, 0, sizeof *p); }
+}
+
+int main(int argc, char** argv) {
+  uint64_t sum = 0;
+  auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) sum = sum * 1099511628211ull + ((const unsigned char*)p)[i]; };
+  const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+  // sigma2 and Beer
+  // (the values ptc_set_material_transmission lets through, and the finite t of a hit record: pt_exp2 converts its argument's floor to an integer)
+  const float cols[] = {1e-30f, 9.5367431640625e-7f, 0.25f, 0.5f, std::nextafter(1.0f, 0.0f), 1.0f};
+  const float dists[] = {0.0f, 1e-30f, 0.5f, 2.0f, 1e30f};
+  for (float c : cols)
+    for (float dd : dists) {
+      ptc_transmission_params p{1.0f, 1.5f, 0, {c, c, c}, dd};
+      const pt_glass_mat m = pt_glass_make_mat(p);
+      for (float t : {0.0f, 1e-3f, 1.0f, 1e6f, 3.0e38f})
+        for (int front = 0; front < 2; ++front) {
+          v3 T = V3(1.0f, 0.5f, 2.0f);
+          const int ch = pt_glass_beer(m, front != 0, t, T) ? 1 : 0;
+          mix(&ch, sizeof ch); mix(&T, sizeof T);
+        }
+    }
+  // the event and the interaction: normals and directions around a circle, plus degenerate ones
+  const float iors[] = {1.0f, 1.0000001f, 1.33f, 1.5f, 3.0f, 1e6f};
+  const float us[] = {0.0f, 0.25f, 0.999999f, nan};
+  std::vector<v3> dirs;
+  for (int k = 0; k < 24; ++k) { const float a = 6.2831853f * (float)k / 24.0f; dirs.push_back(V3(std::sin(a), -std::cos(a), 0.02f * (float)(k % 3))); }
+  dirs.push_back(V3(0.0f, 0.0f, 0.0f)); dirs.push_back(V3(nan, 0.0f, 1.0f)); dirs.push_back(V3(inf, 0.0f, 0.0f));
+  const v3 ng = V3(0.0f, 1.0f, 0.0f);
+  const v3 nss[] = {V3(0.0f, 1.0f, 0.0f), V3(0.6f, 0.8f, 0.0f), V3(-0.8f, 0.6f, 0.0f), V3(0.0f, 0.0f, 0.0f)};
+  int outcomes[4] = {0, 0, 0, 0};
+  for (float ior : iors)
+    for (int thin = 0; thin < 2; ++thin)
+      for (int front = 0; front < 2; ++front)
+        for (const v3& ns : nss)
+          for (const v3& d0 : dirs)
+            for (float us_ : us)
+              for (float ue : us)
+                for (uint32_t j : {0u, 3u}) {
+                  ptc_transmission_params p{0.7f, ior, thin, {1.0f, 1.0f, 1.0f}, 0.0f};
+                  const pt_glass_mat m = pt_glass_make_mat(p);
+                  v3 o = V3(0.0f, 0.0f, 0.0f), d = d0, T = V3(1.0f, 1.0f, 1.0f);
+                  float F = 0.0f;
+                  const int oc = pt_glass_interact(m, V3(0.1f, 0.2f, 0.3f), ng, ns, front != 0, V3(0.9f, 0.8f, 0.7f), 0.25f, 1e-4f, us_, ue, j, 3u, o, d, T, F);
+                  if (oc < 0 || oc > 3) { std::fprintf(stderr, "outcome %d\n", oc); return 1; }
+                  ++outcomes[oc];
+                  mix(&oc, sizeof oc); mix(&o, sizeof o); mix(&d, sizeof d); mix(&T, sizeof T); mix(&F, sizeof F);
+                }
+  for (int k = 0; k < 4; ++k) if (!outcomes[k]) { std::fprintf(stderr, "outcome %d never seen\n", k); return 1; }
+  // the tables
+  for (size_t n_prims : {(size_t)0, (size_t)1, (size_t)31, (size_t)32, (size_t)33, (size_t)64, (size_t)1000}) {
+    for (size_t n_params : {(size_t)0, (size_t)2, (size_t)5, (size_t)9}) {
+      const size_t n_mats = 5;
+      std::vector<int32_t> tri_mat(n_prims);
+      std::vector<ptc_transmission_params> params(n_params);
+      for (size_t p = 0; p < n_prims; ++p) tri_mat[p] = (int32_t)(p % 7) - 1;      // -1 and 5 lie outside the material list
+      for (size_t m = 0; m < n_params; ++m) params[m] = ptc_transmission_params{(float)(m % 2), 1.0f + 0.25f * (float)m, (int)(m % 2), {0.5f, 0.25f, 1.0f}, (float)m};
+      std::vector<uint32_t> bits; std::vector<pt_glass_mat> mats;
+      const uint32_t n = pt_glass_tables(tri_mat, n_mats, params, bits, mats);
+      if (bits.size() != (n_prims + 31) / 32 || mats.size() != n_mats) { std::fprintf(stderr, "table sizes\n"); return 1; }
+      uint32_t set = 0;
+      for (uint32_t wd : bits) set += (uint32_t)__builtin_popcount(wd);
+      if (set != n) { std::fprintf(stderr, "bit count\n"); return 1; }
+      mix(bits.data(), bits.size() * 4); mix(mats.data(), mats.size() * sizeof(pt_glass_mat));
+    }
+  }
+  // the loader: one triangle; a thin pane, a solid with attenuation, out-of-range values, a BLEND and an emissive material with the extension, none
+  const std::string dir = argc > 1 ? argv[1] : "/tmp";
+  const std::string doc =
+      "{\"asset\":{\"version\":\"2.0\"},\"scene\":0,\"scenes\":[{\"nodes\":[0]}],\"nodes\":[{\"mesh\":0}],"
+      "\"meshes\":[{\"primitives\":[{\"attributes\":{\"POSITION\":0},\"material\":0}]}],"
+      "\"materials\":[{\"extensions\":{\"KHR_materials_transmission\":{\"transmissionFactor\":0.75,\"transmissionTexture\":{\"index\":0}},\"KHR_materials_ior\":{\"ior\":1.25}}},"
+      "{\"extensions\":{\"KHR_materials_transmission\":{\"transmissionFactor\":1},\"KHR_materials_volume\":{\"thicknessFactor\":0.5,\"attenuationColor\":[0.5,0.25,1],\"attenuationDistance\":2}}},"
+      "{\"extensions\":{\"KHR_materials_transmission\":{\"transmissionFactor\":7},\"KHR_materials_ior\":{\"ior\":0},\"KHR_materials_volume\":{\"thicknessFactor\":0,\"attenuationColor\":[0,2,-1]}}},"
+      "{\"alphaMode\":\"BLEND\",\"extensions\":{\"KHR_materials_transmission\":{\"transmissionFactor\":0.5}}},"
+      "{\"emissiveFactor\":[1,0,0],\"extensions\":{\"KHR_materials_transmission\":{\"transmissionFactor\":0.5}}},{},{\"extensions\":{}}],"
+      "\"accessors\":[{\"bufferView\":0,\"componentType\":5126,\"count\":3,\"type\":\"VEC3\",\"min\":[0,0,0],\"max\":[1,1,0]}],"
+      "\"bufferViews\":[{\"buffer\":0,\"byteLength\":36}],"
+      "\"buffers\":[{\"byteLength\":36,\"uri\":\"data:application/octet-stream;base64,AAAAAAAAAAAAAAAAAACAPwAAAAAAAAAAAAAAAAAAgD8AAAAA\"}]}";
+  const std::string path = dir + "/host_glass_san.gltf";
+  { std::ofstream f(path); f << doc; }
+  try {
+    const pbr::gltf::FlatScene fs = pbr::gltf::load(path);
+    if (fs.materials.size() != 7) { std::fprintf(stderr, "materials: %zu\n", fs.materials.size()); return 1; }
+    const float want_tau[7] = {0.75f, 1.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (size_t m = 0; m < 7; ++m) {
+      const ptc_transmission_params& t = fs.materials[m].transmission;
+      if (t.transmission != want_tau[m]) { std::fprintf(stderr, "material %zu: transmission %g\n", m, t.transmission); return 1; }
+      if (!(t.ior >= 1.0f) || !(t.attenuation_distance >= 0.0f)) { std::fprintf(stderr, "material %zu: out of range\n", m); return 1; }
+      for (int k = 0; k < 3; ++k) if (!(t.attenuation_color[k] > 0.0f && t.attenuation_color[k] <= 1.0f)) { std::fprintf(stderr, "material %zu: colour\n", m); return 1; }
+      mix(&t, sizeof t);
+    }
+    const ptc_transmission_params &a = fs.materials[0].transmission, &b = fs.materials[1].transmission, &c = fs.materials[2].transmission;
+    if (a.ior != 1.25f || a.thin_walled != 1 || b.thin_walled != 0 || b.ior != 1.5f || b.attenuation_color[1] != 0.25f || b.attenuation_distance != 2.0f || c.ior != 1.0f || c.thin_walled != 1) {
+      std::fprintf(stderr, "fields\n");
+      return 1;
+    }
+  } catch (const std::exception& e) { std::fprintf(stderr, "load: %s\n", e.what()); return 1; }
+  std::printf("host_glass_san ok, checksum %016llx\n", (unsigned long long)sum);
+  return 0;
+}
