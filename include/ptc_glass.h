@@ -43,8 +43,8 @@ extern "C" {
  *   hits, node visits, triangle tests and launches_trace_closest count the batch's own trace per bounce and leave out the continuation segments of the glass
  *   pass, as they leave out those of the alpha pass.  Where the scene also has alpha materials, the alpha resolutions of the continuations run inside this
  *   pass and their time is part of seconds_glass AND of ptc_alpha_stats' seconds_alpha: the two are not to be added.
- * Limits: no eta^2 radiance scaling; roughness is ignored for the interface; shadow rays of every kind see a transmissive surface as an occluder, so light
- * reaches things behind glass only along sampled paths that hit an emitter or the environment; ptc_frame_guides, the denoisers, the temporal reprojection and
+ * Limits: no eta^2 radiance scaling; roughness is ignored for the interface; shadow rays of every kind see a transmissive surface as an occluder unless
+ * ptc_set_glass_shadows (ptc_glass_shadows.h) lets them pass thin panes, so light otherwise reaches things behind glass only along sampled paths that hit an emitter or the environment; ptc_frame_guides, the denoisers, the temporal reprojection and
  * ptc_focus_distance_at_pixel see glass as the surface; the raster integrators and the other debug hooks ignore transmission. */
 typedef struct ptc_transmission_params {
   float transmission, ior;

@@ -10,43 +10,13 @@
 // An empty round (every segment count 0) is a launch whose waves read one word each.
 // Memory per hit that needs a decision: 48 B of shading record (positions, material), 32 B more (the uv units) and the texel taps when the class is textured,
 // 8 B of (mode, cutoff); an opaque hit costs the 4-byte load of its bit.  The surface's alpha comes from record_material itself (pt_shading.h): the same texels and
-// the same arithmetic as k_shade's base[3].
-#include "pt_shading.h"
-#include "pt_alpha.h"
+// the same arithmetic as k_shade's base[3] (alpha_surface: pt_walk_surfaces.h, which the shadow walk through thin glass shares).
+#include "pt_walk_surfaces.h"
 
 #define ALPHA_BLOCK 256
 #define ALPHA_WAVES (ALPHA_BLOCK / 64)
 
 namespace {
-PT_DEV bool alpha_bit(const DevAlpha& al, uint32_t prim) { return (al.bits[prim >> 5] >> (prim & 31u)) & 1u; }
-
-// the alpha-mapped surface of a hit: its material's (mode, cutoff), its coverage a, and where a ray (.., d) that passes through it goes on from
-PT_DEV void alpha_surface(const DevScene& sc, const DevAlpha& al, float4 H, v3 d, int& mode, float& cutoff, float& a, v3& onward) {
-  const uint32_t hw_word = (uint32_t)__float_as_int(H.y);
-  const uint32_t prim = hw_word & ((1u << HIT_CLASS_SHIFT) - 1u);
-  const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
-  const size_t rec = (size_t)prim * sc.shade_stride;
-  const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2];
-  float4 x0, x1;
-  const float4 z = make_float4(0, 0, 0, 0);
-  x0 = x1 = z;
-  if ((hw_word >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; }      // a textured class: the uv units (the tangent units only feed the normal map)
-  const int mat = __float_as_int(r0.w);
-  float base[4], metallic, roughness;
-  bool lambert;
-  v3 ns = V3(0.0f, 0.0f, 1.0f);
-  record_material(sc, sc.mats, mat, x0, x1, z, z, z, z, hu, hv, hw, V3(0.0f, 0.0f, 1.0f), base, metallic, roughness, lambert, ns);
-  a = base[3];
-  const float2 mc = al.mode_cutoff[mat];
-  mode = __float_as_int(mc.x); cutoff = mc.y;
-  const v3 P = record_position(r0, r1, r2, hu, hv, hw);
-  const v3 ng = record_face_normal(r0, r1, r2);
-  const v3 n = dot3(ng, d) > 0.0f ? ng : -ng;
-  onward = vfma(n, sc.ray_eps, P);
-}
-
-PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
-
 // ---- closest hit ------------------------------------------------------------------------------------------------------------------------------------
 template <bool DET, bool FIRST>
 __global__ __launch_bounds__(ALPHA_BLOCK) void k_alpha_filter_closest(DevScene sc, DevQueues q, DevQueues aq, int qi, uint32_t b, DevAlpha al, uint32_t* layers_out) {

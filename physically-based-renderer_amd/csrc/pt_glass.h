@@ -26,14 +26,15 @@
 // q.hit — (t of the last segment, prim | class << 28, u, v), or the trace's miss record — and its own slot of ray[qi] becomes A = (o', d'.x), B = (d'.yz, T.xy),
 // C = (T.z, PT_GLASS_DELTA_PDF, path, key).  A j = 0 ray whose T step 2 attenuated gets T rewritten in ray[qi] only.
 // PT_GLASS_DELTA_PDF: its square is finite, and in k_shade's pb2 / fma(pl, pl, pb2) it gives the weight 1 for any realistic pl — the correct MIS weight, because
-// next-event estimation cannot reach a light through a delta interface.
+// next-event estimation cannot reach a light through a delta interface.  In a frame with transparent shadows (pt_glass_shadow.h) it can, through thin panes: there a
+// ray all of whose events were thin transmissions keeps the pdf word, o and d of its source record instead, and its hit's t counts from the source origin.
 //
 // RNG: rng_f forms index * 8 + dim in uint32, so the pass draws at the counters 0x40000000 + ..: disjoint from k_shade (small), the punctual pass (0x80000000 + ..)
 // and alpha.
 //
 // Limits.  No eta^2 radiance scaling; roughness is ignored for the interface.  Shadow rays (k_trace_any, alpha's shadow walk, the punctual pass) see a transmissive
-// surface as an occluder: light reaches things behind glass only along sampled paths that hit an emitter or the environment (transparent shadows through thin
-// panes are the named follow-up).  ptc_frame_guides, the denoisers, the temporal reprojection and ptc_focus_distance_at_pixel see glass as the surface.  The raster
+// surface as an occluder unless ptc_set_glass_shadows lets them pass thin panes (pt_glass_shadow.h; solid glass bends light and stays an occluder): otherwise
+// light reaches things behind glass only along sampled paths that hit an emitter or the environment.  ptc_frame_guides, the denoisers, the temporal reprojection and ptc_focus_distance_at_pixel see glass as the surface.  The raster
 // integrators and the existing debug hooks ignore transmission.  Probe frames go through run_batch and honour it.  An emissive material and a material whose alpha
 // mode is not OPAQUE are never transmissive.
 #pragma once
@@ -144,5 +145,6 @@ inline uint32_t pt_glass_tables(const std::vector<int32_t>& tri_mat, size_t n_ma
 // A = (o', d'.x), B = (d'.yz, T.xy), C = (T.z, j, source slot, key).
 // first = true: the batch's rays ray[qi] and their hit records -> the rays with an event, compacted to the front of each segment of gq.
 // first = false: gq's records and THEIR hit records -> standing results scattered to the source slots of q.hit and q.ray[qi], the rays with an event compacted in place.
+// shadows: the frame's shadow records pass thin panes (pt_glass_shadow.h), so a ray that only went straight through thin panes keeps its pdf word, o and d.
 // j_out (or null): per source slot, the events of a ray whose result was written (debug hook).
-void pt_launch_glass_filter(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& gq, int qi, uint32_t bounce, const DevGlass&, bool first, uint32_t* j_out);
+void pt_launch_glass_filter(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& gq, int qi, uint32_t bounce, const DevGlass&, bool first, bool shadows, uint32_t* j_out);

@@ -8,19 +8,20 @@
 // and compacts what it produces with a ballot and mbcnt64: no atomic on the data path, no block barrier, and a wave never writes more records than it read — which is
 // also why a later round can compact IN PLACE: a batch of 64 is loaded whole before anything is stored, and what it stores lies at or before its own slots.
 // An empty round (every segment count 0) is a launch whose waves read one word each.
+// The kernel is templated on transparent shadows (pt_glass_shadow.h): in such a frame a ray that only went straight through thin panes leaves the pass as a ray
+// next-event estimation could have sampled — one more 16-byte load of the source origin at stand time.  The other instantiation does none of it.
 // Memory per hit that needs a decision: the 80 B (192 B in a textured scene) of the shading record, the texel taps, 48 B of material and 32 B of glass record; a hit on
 // anything else costs the 4-byte load of its bit from a table that stays in L2.  The surface comes from the pt_shading.h helpers: k_shade's texels and arithmetic.
-#include "pt_shading.h"
-#include "pt_glass.h"
+#include "pt_walk_surfaces.h"
 
 #define GLASS_BLOCK 256
 #define GLASS_WAVES (GLASS_BLOCK / 64)
+#define GLASS_BENT (1u << 16)      // SHADOWS: beside j in a continuation's C.y, set once the ray was reflected or refracted by a solid (j <= PT_GLASS_MAX_INTERACTIONS)
 
 namespace {
-PT_DEV bool glass_bit(const DevGlass& gl, uint32_t prim) { return (gl.bits[prim >> 5] >> (prim & 31u)) & 1u; }
-PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
-
-template <bool FIRST>
+// SHADOWS: the frame walks its shadow records through thin panes (pt_glass_shadow.h), so a ray all of whose events were thin transmissions leaves the pass as
+// the straight ray it is: the pdf word, o and d of its source record, T rewritten, the standing hit's t measured from the source origin.  false: none of that.
+template <bool FIRST, bool SHADOWS>
 __global__ __launch_bounds__(GLASS_BLOCK) void k_glass_filter(DevScene sc, DevQueues q, DevQueues gq, int qi, uint32_t b, DevGlass gl, uint32_t* j_out) {
   const uint32_t lane = lane_id();
   const uint32_t seg = blockIdx.x * GLASS_WAVES + (threadIdx.x >> 6);
@@ -46,47 +47,41 @@ __global__ __launch_bounds__(GLASS_BLOCK) void k_glass_filter(DevScene sc, DevQu
         const float4 A = rin.A[slot], Bq = rin.B[slot], Cq = rin.C[slot];
         v3 o = V3(A.x, A.y, A.z), d = V3(A.w, Bq.x, Bq.y), T = V3(Bq.z, Bq.w, Cq.x);
         const uint32_t key = __float_as_uint(Cq.w);
-        const uint32_t j = FIRST ? 0u : __float_as_uint(Cq.y), src = FIRST ? slot : __float_as_uint(Cq.z);
+        const uint32_t jw = FIRST ? 0u : __float_as_uint(Cq.y), src = FIRST ? slot : __float_as_uint(Cq.z);
+        const uint32_t j = SHADOWS ? jw & (GLASS_BENT - 1u) : jw;
+        bool bent = SHADOWS && (jw & GLASS_BENT) != 0u;
         int outcome = PT_GLASS_STANDS;
         bool beer = false;
         if (decide) {
-          // ---- the surface: k_shade's loads and its P5 (pt_shading.h) ----
-          const uint32_t prim = (uint32_t)pw & ((1u << HIT_CLASS_SHIFT) - 1u);
-          const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
-          const size_t rec = (size_t)prim * sc.shade_stride;
-          const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2], r3 = sc.shade[rec + 3], r4 = sc.shade[rec + 4];
-          float4 x0, x1, x2, x3, x4, x5;
-          x0 = x1 = x2 = x3 = x4 = x5 = make_float4(0, 0, 0, 0);
-          if (((uint32_t)pw >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; x2 = sc.shade[rec + 7]; x3 = sc.shade[rec + 8]; x4 = sc.shade[rec + 9]; x5 = sc.shade[rec + 10]; }
-          const int mat = __float_as_int(r0.w);
-          const float4 g0 = gl.mats[(size_t)mat * 2u], g1 = gl.mats[(size_t)mat * 2u + 1u];
-          const v3 P = record_position(r0, r1, r2, hu, hv, hw);
-          v3 ng = record_face_normal(r0, r1, r2);
-          const v3 ni = record_normal(r2, r3, r4, hu, hv, hw);
-          v3 ns = normalize3(ni);
-          float base_c[4], metallic, roughness;
-          bool lambert;
-          record_material(sc, sc.mats, mat, x0, x1, x2, x3, x4, x5, hu, hv, hw, ni, base_c, metallic, roughness, lambert, ns);
-          const bool front = orient_normals(-d, ng, ns);
-          pt_glass_mat m;
-          m.tau = g0.x; m.ior = g0.y; m.thin = __float_as_int(g0.z); m.pad0 = 0.0f; m.sigma2[0] = g1.x; m.sigma2[1] = g1.y; m.sigma2[2] = g1.z; m.pad1 = 0.0f;
-          beer = pt_glass_beer(m, front, H.x, T);
+          const GlassSurface s = glass_surface(sc, gl, H, d);
+          beer = pt_glass_beer(s.m, s.front, H.x, T);
           const uint32_t idx = PT_GLASS_RNG_BASE + (b + 1u) * 64u + j;
           float F;
-          outcome = pt_glass_interact(m, P, ng, ns, front, V3(base_c[0], base_c[1], base_c[2]), metallic, sc.ray_eps, rng_f(key, idx, 0), rng_f(key, idx, 1), j, gl.max_interactions, o, d, T, F);
+          outcome = pt_glass_interact(s.m, s.P, s.ng, s.ns, s.front, s.base, s.metallic, sc.ray_eps, rng_f(key, idx, 0), rng_f(key, idx, 1), j, gl.max_interactions, o, d, T, F);
+          if (SHADOWS && (outcome == PT_GLASS_REFLECT || (outcome == PT_GLASS_TRANSMIT && s.m.thin == 0))) bent = true;
         }
         if (outcome >= PT_GLASS_REFLECT) {
           go_on = true; reflected = outcome == PT_GLASS_REFLECT;
           cA = make_float4(o.x, o.y, o.z, d.x);
           cB = make_float4(d.y, d.z, T.x, T.y);
-          cC = make_float4(T.z, __uint_as_float(j + 1u), __uint_as_float(src), __uint_as_float(key));
+          cC = make_float4(T.z, __uint_as_float((j + 1u) | (bent ? GLASS_BENT : 0u)), __uint_as_float(src), __uint_as_float(key));
         } else if (!FIRST) {      // j >= 1: the standing hit (or the miss record) and the rewritten ray, at the source ray's own slot
           if (outcome == PT_GLASS_EXHAUSTED) { exhausted = true; H = make_float4(-1.0f, __int_as_float(-1), 0.0f, 0.0f); T = V3(0.0f, 0.0f, 0.0f); }
           else stood = true;      // counted as standing: the ray leaves the pass with a result for k_shade, a hit that stood or the trace's miss (pw < 0) alike
-          q.hit[src] = H;
-          rsrc.A[src] = make_float4(o.x, o.y, o.z, d.x);
-          rsrc.B[src] = make_float4(d.y, d.z, T.x, T.y);
-          *reinterpret_cast<float2*>(&rsrc.C[src]) = make_float2(T.z, PT_GLASS_DELTA_PDF);      // path and key stay
+          if (SHADOWS && !bent) {      // it went straight on: d is the source record's, bit for bit; o and the pdf word stay, t counts from the source origin
+            if (__float_as_int(H.y) >= 0) {
+              const float4 As = rsrc.A[src];
+              H.x = dot3(o - V3(As.x, As.y, As.z), d) + H.x;
+            }
+            q.hit[src] = H;
+            *reinterpret_cast<float2*>(&rsrc.B[src].z) = make_float2(T.x, T.y);
+            rsrc.C[src].x = T.z;
+          } else {
+            q.hit[src] = H;
+            rsrc.A[src] = make_float4(o.x, o.y, o.z, d.x);
+            rsrc.B[src] = make_float4(d.y, d.z, T.x, T.y);
+            *reinterpret_cast<float2*>(&rsrc.C[src]) = make_float2(T.z, PT_GLASS_DELTA_PDF);      // path and key stay
+          }
           if (j_out) j_out[src] = j;
         } else if (beer) {        // j = 0 and the hit stands: T alone
           rsrc.B[slot] = make_float4(Bq.x, Bq.y, T.x, T.y);
@@ -110,8 +105,10 @@ __global__ __launch_bounds__(GLASS_BLOCK) void k_glass_filter(DevScene sc, DevQu
 }
 }  // namespace
 
-void pt_launch_glass_filter(hipStream_t s, const DevScene& sc, const DevQueues& q, const DevQueues& gq, int qi, uint32_t bounce, const DevGlass& gl, bool first, uint32_t* j_out) {
+void pt_launch_glass_filter(hipStream_t s, const DevScene& sc, const DevQueues& q, const DevQueues& gq, int qi, uint32_t bounce, const DevGlass& gl, bool first, bool shadows, uint32_t* j_out) {
   const dim3 grid((q.n_seg + GLASS_WAVES - 1u) / GLASS_WAVES), block(GLASS_BLOCK);      // one wave per segment
-  if (first) hipLaunchKernelGGL((k_glass_filter<true>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
-  else hipLaunchKernelGGL((k_glass_filter<false>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+  if (first && shadows) hipLaunchKernelGGL((k_glass_filter<true, true>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+  else if (shadows) hipLaunchKernelGGL((k_glass_filter<false, true>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+  else if (first) hipLaunchKernelGGL((k_glass_filter<true, false>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
+  else hipLaunchKernelGGL((k_glass_filter<false, false>), grid, block, 0, s, sc, q, gq, qi, bounce, gl, j_out);
 }

@@ -1,0 +1,63 @@
+// pt_walk_surfaces.h — what the alpha pass, the glass pass and the shadow walk through thin glass need of a hit (device only): the bit of a primitive, the
+// alpha-mapped surface and the transmissive surface, each from the pt_shading.h helpers — k_shade's loads, texels and arithmetic.
+#pragma once
+#include "pt_shading.h"
+#include "pt_alpha.h"
+#include "pt_glass.h"
+
+PT_DEV bool alpha_bit(const DevAlpha& al, uint32_t prim) { return (al.bits[prim >> 5] >> (prim & 31u)) & 1u; }
+PT_DEV bool glass_bit(const DevGlass& gl, uint32_t prim) { return (gl.bits[prim >> 5] >> (prim & 31u)) & 1u; }
+PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
+
+// the alpha-mapped surface of a hit: its material's (mode, cutoff), its coverage a, and where a ray (.., d) that passes through it goes on from
+PT_DEV void alpha_surface(const DevScene& sc, const DevAlpha& al, float4 H, v3 d, int& mode, float& cutoff, float& a, v3& onward) {
+  const uint32_t hw_word = (uint32_t)__float_as_int(H.y);
+  const uint32_t prim = hw_word & ((1u << HIT_CLASS_SHIFT) - 1u);
+  const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
+  const size_t rec = (size_t)prim * sc.shade_stride;
+  const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2];
+  float4 x0, x1;
+  const float4 z = make_float4(0, 0, 0, 0);
+  x0 = x1 = z;
+  if ((hw_word >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; }      // a textured class: the uv units (the tangent units only feed the normal map)
+  const int mat = __float_as_int(r0.w);
+  float base[4], metallic, roughness;
+  bool lambert;
+  v3 ns = V3(0.0f, 0.0f, 1.0f);
+  record_material(sc, sc.mats, mat, x0, x1, z, z, z, z, hu, hv, hw, V3(0.0f, 0.0f, 1.0f), base, metallic, roughness, lambert, ns);
+  a = base[3];
+  const float2 mc = al.mode_cutoff[mat];
+  mode = __float_as_int(mc.x); cutoff = mc.y;
+  const v3 P = record_position(r0, r1, r2, hu, hv, hw);
+  const v3 ng = record_face_normal(r0, r1, r2);
+  const v3 n = dot3(ng, d) > 0.0f ? ng : -ng;
+  onward = vfma(n, sc.ray_eps, P);
+}
+
+// the transmissive surface of a hit H of a ray of direction d: k_shade's loads and its P5 — P, ng and ns after record_material and orient_normals(-d, ..), base,
+// metallic — and the glass record of its material
+struct GlassSurface { v3 P, ng, ns, base; float metallic; bool front; pt_glass_mat m; };
+PT_DEV GlassSurface glass_surface(const DevScene& sc, const DevGlass& gl, float4 H, v3 d) {
+  const int pw = __float_as_int(H.y);
+  const uint32_t prim = (uint32_t)pw & ((1u << HIT_CLASS_SHIFT) - 1u);
+  const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
+  const size_t rec = (size_t)prim * sc.shade_stride;
+  const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2], r3 = sc.shade[rec + 3], r4 = sc.shade[rec + 4];
+  float4 x0, x1, x2, x3, x4, x5;
+  x0 = x1 = x2 = x3 = x4 = x5 = make_float4(0, 0, 0, 0);
+  if (((uint32_t)pw >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; x2 = sc.shade[rec + 7]; x3 = sc.shade[rec + 8]; x4 = sc.shade[rec + 9]; x5 = sc.shade[rec + 10]; }
+  const int mat = __float_as_int(r0.w);
+  const float4 g0 = gl.mats[(size_t)mat * 2u], g1 = gl.mats[(size_t)mat * 2u + 1u];
+  GlassSurface s;
+  s.P = record_position(r0, r1, r2, hu, hv, hw);
+  s.ng = record_face_normal(r0, r1, r2);
+  const v3 ni = record_normal(r2, r3, r4, hu, hv, hw);
+  s.ns = normalize3(ni);
+  float base_c[4], roughness;
+  bool lambert;
+  record_material(sc, sc.mats, mat, x0, x1, x2, x3, x4, x5, hu, hv, hw, ni, base_c, s.metallic, roughness, lambert, s.ns);
+  s.front = orient_normals(-d, s.ng, s.ns);
+  s.base = V3(base_c[0], base_c[1], base_c[2]);
+  s.m.tau = g0.x; s.m.ior = g0.y; s.m.thin = __float_as_int(g0.z); s.m.pad0 = 0.0f; s.m.sigma2[0] = g1.x; s.m.sigma2[1] = g1.y; s.m.sigma2[2] = g1.z; s.m.pad1 = 0.0f;
+  return s;
+}

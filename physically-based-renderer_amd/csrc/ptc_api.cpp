@@ -22,6 +22,7 @@ namespace {
 constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray ping-pong) + 48 (shadow) + 16 (hit) + 16 (path radiance)
 constexpr size_t kAlphaBytesPerPath = 65;    // ensure_alpha_queues: 48 (continuation) + 16 (its hit record) + 1 (k_trace_any's flag)
 constexpr size_t kGlassBytesPerPath = 64;    // ensure_glass_queues: 48 (continuation) + 16 (its hit record)
+constexpr size_t kGlassFlagBytesPerPath = 1; // ... + 1 (k_trace_any's flag) in a frame with transparent shadows
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 
 // the timing spans that have completed (all_done: every one) go into the statistics, their events back to the pool
@@ -83,9 +84,12 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     const bool alpha = alpha_on(c);
     // dielectric transmission (pt_glass.hip): behind the alpha resolution of bounce b, before shade(b), rounds of launches on this stream alone as well
     const bool glass = glass_on(c);
+    // transparent shadows (pt_glass_shadow.hip): every shadow queue to an RGB transmittance per record, one walk for alpha surfaces and thin panes
+    const bool glass_shadows = glass_shadows_on(c);
     auto trace_shadows = [&]() {
       ScopedSpan t(c, st, 1);
-      if (alpha) alpha_resolve_shadow(c, l, st, cfg, sc, q, nullptr);
+      if (glass_shadows) glass_resolve_shadow(c, l, st, cfg, sc, q, nullptr, nullptr);
+      else if (alpha) alpha_resolve_shadow(c, l, st, cfg, sc, q, nullptr);
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
@@ -325,6 +329,8 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   if (c->alpha.counters.p) HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
   if ((rc = glass_upload(c))) return rc;       // the glass tables likewise
   if (c->glass.counters.p) HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+  if (c->glass.shadow_counters.p) HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
+  c->glass.frame_shadows = c->glass.shadows;      // before the queues are sized: a frame with transparent shadows keeps a flag byte per path
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
   if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
@@ -368,8 +374,9 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
     // no need to ask the driver how much memory is free (a call of 0.1-0.2 ms, every frame of a viewer's loop)
   } else {   // no more than 60 % of the device memory that is free now (plus what the lanes' queues already hold) goes into queues
     size_t free_b = 0, total_b = 0, held = 0;
-    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0);
-    for (const auto& ln : c->lanes) held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath + (size_t)ln.gq.cap * kGlassBytesPerPath;
+    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0) + (glass_shadows_on(c) ? kGlassFlagBytesPerPath : 0);
+    for (const auto& ln : c->lanes)
+      held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath + (size_t)ln.gq.cap * (kGlassBytesPerPath + (ln.gq_flags ? kGlassFlagBytesPerPath : 0));
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
       const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / per_path;
       if (fit < batch_paths) batch_paths = fit;

@@ -57,14 +57,16 @@ int alpha_upload(ptc_ctx* c) {
 }
 
 // A side queue per lane, as large as the lane's queues (grow only; waits for the work in flight first): 64 B of continuation and hit record per slot and, where
-// `flags` names a member, one flag byte per slot; the small arrays (header words, per-segment counts, statistics) once.  The alpha and the glass pass each keep one.
-int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags) {
+// `with_flags` says so, one flag byte per slot in the member `flags` (a queue that lacks them is allocated anew); the small arrays (header words, per-segment counts, statistics) once.  The alpha and the glass pass each keep one.
+int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags, bool with_flags) {
+  with_flags = with_flags && flags;
   bool grow = false;
-  for (auto& ln : c->lanes) grow = grow || (ln.*queue).cap < ln.q.cap;
+  auto enough = [&](const Lane& ln) { return (ln.*queue).cap >= ln.q.cap && !(with_flags && ln.q.cap && !(ln.*flags)); };      // flag bytes may be asked for later than the queue
+  for (auto& ln : c->lanes) grow = grow || !enough(ln);
   if (!grow) return PTC_OK;
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   for (auto& ln : c->lanes) {
-    if ((ln.*queue).cap >= ln.q.cap) continue;
+    if (enough(ln)) continue;
     std::vector<void*>& allocs = ln.*owner;
     free_all(allocs);
     ln.*queue = DevQueues{};
@@ -77,7 +79,7 @@ int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> La
     if (!rc) rc = dev_alloc(c, allocs, &sq.ray[0].B, slots);
     if (!rc) rc = dev_alloc(c, allocs, &sq.ray[0].C, slots);
     if (!rc) rc = dev_alloc(c, allocs, &sq.hit, slots);
-    if (!rc && flags) rc = dev_alloc(c, allocs, &(ln.*flags), slots);
+    if (!rc && with_flags) rc = dev_alloc(c, allocs, &(ln.*flags), slots);
     if (!rc) rc = dev_alloc(c, allocs, &sq.cnt, (size_t)CNT_N);
     if (!rc) rc = dev_alloc(c, allocs, &sq.stats, (size_t)ST_N * ST_STRIDE);
     if (!rc) rc = dev_alloc(c, allocs, &segs, 5 * per);

@@ -1,5 +1,6 @@
 // ptc_api_glass.cpp — dielectric transmission over the C-ABI (pt_glass.h): the material calls, the tables of the committed scene, the lanes' glass
-// queues, the rounds of a resolution as run_batch and the debug hook queue them, the statistics and the ptc_debug_glass_* hooks.
+// queues, the rounds of a resolution as run_batch and the debug hooks queue them, the statistics and the ptc_debug_glass_* hooks; and transparent shadows
+// (pt_glass_shadow.h, include/ptc_glass_shadows.h): the setting, the rounds of the shadow walk, its statistics and hooks.
 #include "ptc_ctx.h"
 
 #include <cmath>
@@ -20,6 +21,33 @@ DevQueues glass_view(const ptc_ctx* c, int l, const DevQueues& q) {
 void glass_tables(const ptc_ctx* c, std::vector<uint32_t>& bits, std::vector<pt_glass_mat>& mats, uint32_t& n) {
   n = pt_glass_tables(c->built->tri_mat, c->mats.size(), c->glass.params, bits, mats);
 }
+
+// ptc_debug_glass_*: what ptc_api_debug.cpp's ray hooks need — a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters
+// cleared — and the alpha and glass tables, queues and counters of the committed scene
+int glass_debug_prepare(ptc_ctx* c, uint32_t n, const char* who) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  c->in_frame = false; c->pending = 0; drop_guides(c);
+  int rc = ensure_lane_queues(c, n);
+  if (rc) return rc;
+  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
+  if ((rc = alpha_upload(c))) return rc;
+  if ((rc = glass_upload(c))) return rc;
+  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
+  c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions; c->glass.frame_shadows = c->glass.shadows;
+  if (alpha_on(c)) {
+    if ((rc = ensure_alpha_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
+  }
+  if (glass_on(c)) {
+    if ((rc = ensure_glass_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
+  }
+  return PTC_OK;
+}
 }  // namespace
 
 namespace ptc_detail {
@@ -33,17 +61,23 @@ int glass_upload(ptc_ctx* c) {
     int rc = ensure_buf(c, c->glass.bits, bits.size());
     if (!rc) rc = ensure_buf(c, c->glass.mats, mats.size() * 2u);
     if (!rc) rc = ensure_buf(c, c->glass.counters, (size_t)PT_GLASS_COUNTERS);
+    if (!rc) rc = ensure_buf(c, c->glass.shadow_counters, (size_t)PT_GLASS_SHADOW_COUNTERS);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpy(c->glass.bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->glass.mats.p, mats.data(), mats.size() * sizeof(pt_glass_mat), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
   }
+  uint32_t n_thin = 0;
+  for (const int32_t m : c->built->tri_mat) n_thin += m >= 0 && (size_t)m < mats.size() && mats[(size_t)m].tau > 0.0f && mats[(size_t)m].thin != 0;
+  c->glass.n_thin = n_thin;
   c->glass.n_prims = n;
   c->glass.dirty = false;
   return PTC_OK;
 }
 
-int ensure_glass_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::gq, &Lane::gq_allocs, nullptr); }      // no flag bytes: the glass pass has no shadow walk
+// flag bytes only for a frame (or ray hook) that walks its shadow records through thin panes: turning the feature on after frames have run allocates the queue anew
+int ensure_glass_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::gq, &Lane::gq_allocs, &Lane::gq_flags, glass_shadows_on(c)); }
 
 // The host cannot know how many rays go on without a read-back, so a resolution queues every round it may need: filter, then max_interactions x (scan, trace, [alpha],
 // filter).  A round with nothing left is launches that find their queue empty.  In round r the continuations' hits are first resolved by the alpha pass on the glass
@@ -52,13 +86,34 @@ void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& c
   ScopedSpan t(c, st, 6);
   const DevQueues gq = glass_view(c, l, q);
   const DevGlass gl = dev_glass(c);
-  const bool alpha = alpha_on(c);
-  pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/true, j_out);
+  const bool alpha = alpha_on(c), shadows = glass_shadows_on(c);
+  pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/true, shadows, j_out);
   for (uint32_t r = 0; r < gl.max_interactions; ++r) {
     pt_launch_scan(st, cfg, gq, 0);
     pt_launch_trace_closest(st, cfg, sc, gq, 0, false);
     if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, gq, 0, 0x01000000u + (bounce + 1u) * 64u + r, PT_ALPHA_FORM_CLOSEST, nullptr);
-    pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/false, j_out);
+    pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/false, shadows, j_out);
+  }
+}
+
+// the shadow queue of q, counted and scanned, resolved to an RGB transmittance per record (pt_glass_shadow.h): the coarse flags by k_trace_any, then the walk through
+// the glass queue — a record that starts at k = 0 may be traced L + 1 times before it is exhausted, L the larger of the frame's max_interactions and, in a scene
+// with alpha materials, its max_layers
+void glass_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out, uint32_t* layers_out) {
+  ScopedSpan t(c, st, 6);
+  const DevQueues gq = glass_view(c, l, q);
+  const DevGlass gl = dev_glass(c);
+  const bool alpha = alpha_on(c);
+  const DevAlpha al = alpha ? DevAlpha{c->alpha.bits.p, c->alpha.mode_cutoff.p, (uint32_t)c->alpha.frame_layers, c->alpha.counters.p} : DevAlpha{nullptr, nullptr, 0u, nullptr};
+  const uint32_t L = alpha && al.max_layers > gl.max_interactions ? al.max_layers : gl.max_interactions;
+  const uint8_t* flags = c->lanes[(size_t)l].gq_flags;
+  unsigned long long* ctr = c->glass.shadow_counters.p;
+  pt_launch_trace_any(st, cfg, sc, q, c->lanes[(size_t)l].gq_flags);
+  pt_launch_glass_filter_shadow(st, sc, q, gq, al, gl, L, ctr, flags, /*first=*/true, tr_out, layers_out);
+  for (uint32_t r = 0; r <= L; ++r) {
+    pt_launch_scan(st, cfg, gq, 0);
+    pt_launch_trace_closest(st, cfg, sc, gq, 0, false);
+    pt_launch_glass_filter_shadow(st, sc, q, gq, al, gl, L, ctr, flags, /*first=*/false, tr_out, layers_out);
   }
 }
 }  // namespace ptc_detail
@@ -110,6 +165,34 @@ int ptc_set_glass_max_interactions(ptc_ctx* c, int n) {
   return PTC_OK;
 }
 
+int ptc_set_glass_shadows(ptc_ctx* c, int on) {
+  if (!c) return PTC_E_ARG;
+  if (on != 0 && on != 1) return fail(c, PTC_E_ARG, "set_glass_shadows: 0 or 1");
+  c->glass.shadows = on;
+  return PTC_OK;
+}
+
+int ptc_get_glass_shadows(const ptc_ctx* c, int* on) {
+  if (!c || !on) return PTC_E_ARG;
+  *on = c->glass.shadows;
+  return PTC_OK;
+}
+
+int ptc_get_glass_shadow_stats(ptc_ctx* c, ptc_glass_shadow_stats* out) {
+  if (!c) return PTC_E_ARG;
+  if (!out) return fail(c, PTC_E_ARG, "get_glass_shadow_stats: null pointer");
+  std::memset(out, 0, sizeof *out);
+  if (c->device < 0) return PTC_OK;
+  ptc_stats unused;
+  { int rc = ptc_get_stats(c, &unused); if (rc) return rc; }      // flushes and waits
+  if (c->glass.shadow_counters.p) {
+    unsigned long long v[PT_GLASS_SHADOW_COUNTERS];
+    HIP_TRY(c, hipMemcpy(v, c->glass.shadow_counters.p, sizeof v, hipMemcpyDeviceToHost));
+    out->walked = v[PT_GLASS_SHADOW_WALKED]; out->passes = v[PT_GLASS_SHADOW_PASSES]; out->visible = v[PT_GLASS_SHADOW_VISIBLE]; out->exhausted = v[PT_GLASS_SHADOW_EXHAUSTED];
+  }
+  return PTC_OK;
+}
+
 int ptc_get_glass_stats(ptc_ctx* c, ptc_glass_stats* out) {
   if (!c) return PTC_E_ARG;
   if (!out) return fail(c, PTC_E_ARG, "get_glass_stats: null pointer");
@@ -131,28 +214,8 @@ int ptc_debug_glass_closest(ptc_ctx* c, const float* origins, const float* dirs,
                             float* out_t, int32_t* out_prim, float* out_uv, float* out_ray10, uint32_t* out_j) {
   if (!c) return PTC_E_ARG;
   if (c->device >= 0 && (!origins || !dirs || !keys || !out_t || !out_prim || !out_uv || !out_ray10 || !out_j || n == 0 || bounce > 0x0000ffffu)) return fail(c, PTC_E_ARG, "debug_glass_closest: bad argument");
-  // what ptc_api_debug.cpp's ray hooks need — a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared — and the
-  // alpha and glass tables, queues and counters of the committed scene
-  { int rd = need_device(c); if (rd) return rd; }
-  if (!c->committed) return fail(c, PTC_E_STATE, "debug_glass_closest: scene not committed");
-  { int rf = flush(c); if (rf) return rf; }
-  { int rs = sync_all_lanes(c); if (rs) return rs; }
-  c->in_frame = false; c->pending = 0; drop_guides(c);
-  int rc = ensure_lane_queues(c, n);
+  int rc = glass_debug_prepare(c, n, "debug_glass_closest");
   if (rc) return rc;
-  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
-  if ((rc = alpha_upload(c))) return rc;
-  if ((rc = glass_upload(c))) return rc;
-  if (alpha_on(c)) {
-    if ((rc = ensure_alpha_queues(c))) return rc;
-    HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
-  }
-  if (glass_on(c)) {
-    if ((rc = ensure_glass_queues(c))) return rc;
-    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
-  }
-  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
-  c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions;
   const Lane& ln = c->lanes[0];
   std::vector<float4> A(n), B(n), C(n);
   for (uint32_t i = 0; i < n; ++i) {
@@ -187,6 +250,54 @@ int ptc_debug_glass_closest(ptc_ctx* c, const float* origins, const float* dirs,
     float* r = out_ray10 + (size_t)i * 10;
     r[0] = A[i].x; r[1] = A[i].y; r[2] = A[i].z; r[3] = A[i].w; r[4] = B[i].x; r[5] = B[i].y; r[6] = B[i].z; r[7] = B[i].w; r[8] = C[i].x; r[9] = C[i].y;
   }
+  return PTC_OK;
+}
+
+int ptc_debug_glass_any(ptc_ctx* c, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_tr3, uint32_t* out_layers) {
+  if (!c) return PTC_E_ARG;
+  if (c->device >= 0 && (!origins || !dirs || !tmax || !out_tr3 || !out_layers || n == 0)) return fail(c, PTC_E_ARG, "debug_glass_any: bad argument");
+  { int rc = glass_debug_prepare(c, n, "debug_glass_any"); if (rc) return rc; }
+  const Lane& ln = c->lanes[0];
+  std::vector<float4> A(n), B(n), C(n, make_float4(0, 0, 0, 0));
+  for (uint32_t i = 0; i < n; ++i) {
+    float fi; std::memcpy(&fi, &i, 4);
+    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
+    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], tmax[i], fi);
+  }
+  HIP_TRY(c, hipMemcpy(ln.q.shadow.A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.shadow.B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.shadow.C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  DevBuf<float> tr;
+  DevBuf<uint32_t> layers;
+  DevBuf<uint8_t> occ;
+  { int rc = ensure_buf(c, tr, (size_t)n * 3u); if (!rc) rc = ensure_buf(c, layers, n); if (!rc) rc = ensure_buf(c, occ, n); if (rc) return rc; }
+  HIP_TRY(c, hipMemset(tr.p, 0, (size_t)n * 12));
+  HIP_TRY(c, hipMemset(layers.p, 0, (size_t)n * 4));
+  const DevQueues q = batch_queues(c, 0, n);
+  const DevScene sc = lane_scene(c, 0);
+  const bool walk = glass_shadows_on(c);
+  pt_launch_set_counts(ln.stream, c->cfg, q, 0, n);
+  if (walk) glass_resolve_shadow(c, 0, ln.stream, c->cfg, sc, q, tr.p, layers.p);
+  else pt_launch_trace_any(ln.stream, c->cfg, sc, q, occ.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(ln.stream));
+  HIP_TRY(c, hipMemcpy(out_layers, layers.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (walk) HIP_TRY(c, hipMemcpy(out_tr3, tr.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+  else {
+    std::vector<uint8_t> o(n);
+    HIP_TRY(c, hipMemcpy(o.data(), occ.p, n, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n * 3u; ++i) out_tr3[i] = o[i / 3u] ? 0.0f : 1.0f;
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_glass_shadow_transmit(const ptc_transmission_params* p, ptc_glass_shadow_hit* io) {
+  if (!p || !io) return PTC_E_ARG;
+  const pt_glass_mat m = pt_glass_make_mat(*p);
+  float F_t = 0.0f;
+  const v3 W = pt_glass_shadow_transmit(m, V3(io->ng), V3(io->ns), V3(io->d), V3(io->base), io->metallic, F_t);
+  io->W[0] = W.x; io->W[1] = W.y; io->W[2] = W.z;
+  io->F_t = F_t;
   return PTC_OK;
 }
 

@@ -555,7 +555,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
   c->lens = c0->lens;
   c->alpha.mode = c0->alpha.mode; c->alpha.cutoff = c0->alpha.cutoff;      // every member builds context 0's alpha tables
-  c->glass.params = c0->glass.params;      // and its glass tables
+  c->glass.params = c0->glass.params; c->glass.shadows = c0->glass.shadows;      // and its glass tables, with its choice of transparent shadows
   take_lights(c, c0);
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
@@ -590,7 +590,7 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload w
   c->committed = false;
   release_scene(c);
   c->alpha.dirty = true; c->alpha.n_prims = 0;      // the alpha tables follow the primitive ids of the build being laid out: the next ptc_frame_begin uploads them (alpha_upload)
-  c->glass.dirty = true; c->glass.n_prims = 0;      // the glass tables likewise (glass_upload)
+  c->glass.dirty = true; c->glass.n_prims = 0; c->glass.n_thin = 0;      // the glass tables likewise (glass_upload)
   CommittedScene& s = c->scene;
   s.insts = c->insts.size();
   deform_all_live(c);      // every caller lays the scene out from the fully evaluated description
@@ -684,7 +684,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   ptc_lens_default_params(&c->lens);
   c->lights.dirty = c->lights.dirty || !c->lights.list.empty(); c->lights.list.clear();
   c->alpha.mode.clear(); c->alpha.cutoff.clear(); c->alpha.dirty = true; c->alpha.n_prims = 0;      // every material of the next description starts OPAQUE; max_layers stays
-  c->glass.params.clear(); c->glass.dirty = true; c->glass.n_prims = 0;      // and without transmission; max_interactions stays
+  c->glass.params.clear(); c->glass.dirty = true; c->glass.n_prims = 0; c->glass.n_thin = 0;      // and without transmission; max_interactions and shadows stay
   drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
   if (c->display.state.p) HIP_TRY(c, hipMemset(c->display.state.p, 0, sizeof(pt_display_state)));      // the adaptation state goes with the scene; the display parameters stay
   release_scene(c);

@@ -20,6 +20,7 @@
 #include "pt_lights.h"
 #include "pt_alpha.h"
 #include "pt_glass.h"
+#include "pt_glass_shadow.h"
 #include "pt_display.h"
 #include "pt_probes.h"
 
@@ -100,6 +101,7 @@ struct Lane {
   std::vector<void*> aq_allocs;
   // dielectric transmission (pt_glass.h): the lane's glass queue, a DevQueues view like aq.  Allocated only while the committed scene has a transmissive material
   DevQueues gq{};
+  uint8_t* gq_flags = nullptr;      // k_trace_any's flags for the shadow walk through thin glass (pt_glass_shadow.h): only once a frame began with ptc_set_glass_shadows on
   std::vector<void*> gq_allocs;
   void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
   void teardown();                  // ptc_destroy: everything but the overflow slabs (release_scene's), the streams after what ran on them
@@ -201,6 +203,11 @@ struct Glass {
   DevBuf<float4> mats;
   DevBuf<unsigned long long> counters;
   double seconds = 0.0;             // the frame's glass resolutions (spans of kind 6)
+  // transparent shadows (pt_glass_shadow.h)
+  int shadows = 0;                  // ptc_set_glass_shadows: a context setting, kept across ptc_scene_begin
+  int frame_shadows = 0;            // what the frame in progress (or the last ray hook) was begun with
+  uint32_t n_thin = 0;              // primitives of the committed scene whose material is transmissive AND thin-walled, as of the last upload; 0: no shadow walk
+  DevBuf<unsigned long long> shadow_counters;
 };
 
 // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
@@ -533,7 +540,7 @@ int scene_commit(ptc_ctx* c, bool device_ok);
 // ---- ptc_api_alpha.cpp: alpha coverage (pt_alpha.h) ------------------------------------------------------------------------------------------------
 int alpha_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
 inline bool alpha_on(const ptc_ctx* c) { return c->alpha.n_prims > 0; }
-int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags);      // ptc_api_alpha.cpp: what the two below share
+int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags, bool with_flags = true);      // ptc_api_alpha.cpp: what the two below share
 int ensure_alpha_queues(ptc_ctx* c);                   // every lane: an alpha queue as large as its queues (grow only; waits for the work in flight first)
 void alpha_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, int form, uint32_t* layers_out);
 void alpha_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out);
@@ -542,8 +549,11 @@ void alpha_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cf
 int glass_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
 inline bool glass_on(const ptc_ctx* c) { return c->glass.n_prims > 0; }
 inline float glass_tau(const ptc_ctx* c, int material) { return (size_t)material < c->glass.params.size() ? c->glass.params[(size_t)material].transmission : 0.0f; }
-int ensure_glass_queues(ptc_ctx* c);                   // every lane: a glass queue as large as its queues (grow only; waits for the work in flight first)
+int ensure_glass_queues(ptc_ctx* c);                   // every lane: a glass queue as large as its queues, with flag bytes when the frame has transparent shadows (grow only; waits for the work in flight first)
 void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, uint32_t* j_out);
+// transparent shadows (pt_glass_shadow.h): the frame walks its shadow records through thin panes — the feature is on and the scene has a thin transmissive primitive
+inline bool glass_shadows_on(const ptc_ctx* c) { return c->glass.frame_shadows != 0 && c->glass.n_thin > 0; }
+void glass_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out, uint32_t* layers_out);
 
 // ---- ptc_api_image.cpp ---------------------------------------------------------------------------------------------------------------------------
 DevAdaptive dev_adaptive(const ptc_ctx* c);

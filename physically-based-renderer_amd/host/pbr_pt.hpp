@@ -138,6 +138,11 @@ public:
   auto light(int id) const -> ptc_light_params { ptc_light_params p = lightDefaults(); ptc_get_light(_ctx, id, &p); return p; }
   auto lightCount() const -> int { return ptc_light_count(_ctx); }
   auto clearLights() -> void { ck(ptc_clear_lights(_ctx)); }
+  // transparent shadows (include/ptc_glass_shadows.h): shadow rays pass thin-walled transmissive panes with their expected transmittance.  Off by
+  // default, kept across beginScene; a frame renders with the value it was begun with
+  auto setGlassShadows(bool on) -> void { ck(ptc_set_glass_shadows(_ctx, on ? 1 : 0)); }
+  auto glassShadows() const -> bool { int on = 0; ptc_get_glass_shadows(_ctx, &on); return on != 0; }
+  auto glassShadowStats() -> ptc_glass_shadow_stats { ptc_glass_shadow_stats s{}; ck(ptc_get_glass_shadow_stats(_ctx, &s)); return s; }
   // the view depth of what pixel (x, y)'s centre sees, 0 on a miss: needs frameGuides() of the current frame
   auto focusDistanceAtPixel(int x, int y) -> float { float d = 0.0f; ck(ptc_focus_distance_at_pixel(_ctx, x, y, &d)); return d; }
   // PTC_BVH_SAH (default) or PTC_BVH_LBVH, for the scene being described

@@ -4,7 +4,7 @@
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
-//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission]
+//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission] [--glass-shadows]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
 //              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
 // --probe-grid NX,NY,NZ / --probes FILE with --probes-out sh.pfm: bake light probes instead of an image (ptc_render_probes) — the centres of the
@@ -22,6 +22,8 @@
 // attenuated shadows; ptc_set_material_alpha), path integrator only; --no-alpha renders every material opaque, as the raster integrators always do.
 // --no-transmission: a --gltf scene is rendered with KHR_materials_transmission, KHR_materials_ior and KHR_materials_volume of its materials (glass and thin panes;
 // ptc_set_material_transmission), path integrator only; --no-transmission renders them as the opaque surfaces they were before.
+// --glass-shadows: shadow rays pass thin-walled transmissive panes with their expected transmittance (ptc_set_glass_shadows): punctual lights, emitters
+// and the environment light what lies behind a window directly.  Off by default; with --gpus device D's setting goes to every member.
 // --aperture R: the thin lens (ptc_set_camera_lens) with aperture radius R in world units — depth of field, path integrator only.  --blades N: a regular polygon
 // of 3..16 sides instead of the disk, --aperture-rotation T: its rotation in turns, [0, 1).  --focus D: the view depth of the plane of focus (default 1);
 // --focus-pixel X,Y: focus on what that pixel's centre sees — the guides are traced once before the render and ptc_focus_distance_at_pixel is taken (a miss is
@@ -217,6 +219,7 @@ int main(int argc, char** argv) {
   bool noGltfLights = false;
   bool noAlpha = false;                      // --no-alpha: ignore the asset's alpha modes
   bool noTransmission = false;               // --no-transmission: ignore the asset's transmission extensions
+  bool glassShadows = false;                 // --glass-shadows: transparent shadows through thin panes
   ptc_display_params disp = pbr::PathTraceRenderSystem::displayDefaults();      // --exposure / --auto-exposure / --key / --tonemap / --srgb
   bool useDisplay = false, haveKey = false;
   double exposureEv = 0.0;
@@ -239,7 +242,7 @@ int main(int argc, char** argv) {
     else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
-    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true;
+    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true; else if (a == "--glass-shadows") glassShadows = true;
     else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
     else if (a == "--key") { disp.key = (float)std::atof(next()); haveKey = true; } else if (a == "--srgb") { disp.oetf = PTC_OETF_SRGB; useDisplay = true; }
     else if (a == "--tonemap") {
@@ -307,8 +310,10 @@ int main(int argc, char** argv) {
     for (const std::string& sp : lightSpecs) lights.push_back(parseLight(sp));
     if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
     if (noGltfLights && gltf.empty()) throw std::runtime_error("--no-gltf-lights drops the lights of a --gltf scene");
-    // after the scene: the punctual lights (they need no commit) — the asset's own unless dropped, then the command line's
+    if (glassShadows && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--glass-shadows applies to the path integrator (not with --raster / --raster16)");
+    // after the scene: the punctual lights (they need no commit) — the asset's own unless dropped, then the command line's — and how shadow rays see thin glass
     auto applyLights = [&](pbr::PathTraceRenderSystem& rs) {
+      rs.setGlassShadows(glassShadows);
       if (noGltfLights && ptc_clear_lights(rs.handle()) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
       for (const ptc_light_params& l : lights)
         if (ptc_add_light(rs.handle(), &l) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
@@ -435,7 +440,7 @@ int main(int argc, char** argv) {
       for (int i = 0; i < gpus; ++i) ids.push_back(device + i);
       group.reset(new pbr::DeviceGroup(ids));
       buildScene(group->device(0));
-      applyLights(group->device(0)); // the group commit and the group render give every member device 0's lights
+      applyLights(group->device(0)); // the group commit and the group render give every member device 0's lights and its choice of transparent shadows
       applyLens(group->device(0));   // the group commit copies the lens with the camera
       group->commitScene();          // one flatten + BVH build on the host, uploaded to every device
       img = group->render(w, h, spp, seed, bounces, integrator);

@@ -144,6 +144,14 @@ class PtcGlassInteraction(_Struct):
                 ("ray_eps", C.c_float), ("outcome", C.c_int), ("o_out", C.c_float * 3), ("d_out", C.c_float * 3), ("T_out", C.c_float * 3), ("F", C.c_float)]
 
 
+class PtcGlassShadowStats(_Struct):
+    _fields_ = [("walked", C.c_uint64), ("passes", C.c_uint64), ("visible", C.c_uint64), ("exhausted", C.c_uint64)]
+
+
+class PtcGlassShadowHit(_Struct):
+    _fields_ = [("ng", C.c_float * 3), ("ns", C.c_float * 3), ("d", C.c_float * 3), ("base", C.c_float * 3), ("metallic", C.c_float), ("W", C.c_float * 3), ("F_t", C.c_float)]
+
+
 class PtcDenoiseParams(_Struct):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
     _defaults_ = "ptc_denoise_default_params"
@@ -372,9 +380,23 @@ def _glass_prototypes():
     }
 
 
+def _glass_shadow_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_glass_shadows.h declares, in the header's order; exported under ptcx_ like ptc_glass.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, ip, fp, u32p = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    return {
+        "ptc_set_glass_shadows": (i, [vp, i]),
+        "ptc_get_glass_shadows": (i, [vp, ip]),
+        "ptc_get_glass_shadow_stats": (i, [vp, C.POINTER(PtcGlassShadowStats)]),
+        "ptc_debug_glass_any": (i, [vp, fp, fp, fp, u32, fp, u32p]),
+        "ptc_debug_glass_shadow_transmit": (i, [C.POINTER(PtcTransmissionParams), C.POINTER(PtcGlassShadowHit)]),
+    }
+
+
 _PROTOTYPES = _prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
 _GLASS_PROTOTYPES = _glass_prototypes()
+_GLASS_SHADOW_PROTOTYPES = _glass_shadow_prototypes()
 # every function include/ptc_glass.h declares, by the header's names
 GLASS_SYMBOLS = list(_GLASS_PROTOTYPES)
 # every function include/ptc_alpha.h declares, by the header's names
@@ -397,7 +419,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -536,6 +558,16 @@ def glass_interact(params, **fields):
     rc = load_library().ptc_debug_glass_interact(C.byref(params), C.byref(io))
     if rc < 0:
         raise PtcError("glass_interact: bad argument")
+    return io.as_dict()
+
+
+def glass_shadow_transmit(params, **fields):
+    """ptc_debug_glass_shadow_transmit: the host's evaluation of csrc/pt_glass_shadow.h's pt_glass_shadow_transmit for one hit (ng, ns, d, base, metallic).  Returns
+    the struct as a dict (W, F_t, ..)."""
+    io = PtcGlassShadowHit().update(**fields)
+    rc = load_library().ptc_debug_glass_shadow_transmit(C.byref(params), C.byref(io))
+    if rc < 0:
+        raise PtcError("glass_shadow_transmit: bad argument")
     return io.as_dict()
 
 
@@ -808,6 +840,31 @@ class PathTracer:
         bits, mats = np.zeros((npr.value + 31) // 32, np.uint32), np.zeros((nm.value, 8), np.float32)
         rc = self._ck(self._L.ptc_debug_get_glass_tables(self._h, None, _ptr(bits), None, _ptr(mats)))
         return bits, mats, int(npr.value), bool(rc)
+
+    # ---- transparent shadows through thin glass (csrc/pt_glass_shadow.h) --------------------------------------
+    def set_glass_shadows(self, on=True):
+        """ptc_set_glass_shadows: shadow rays pass thin-walled panes with their expected transmittance (off by default; the next frame uses it)."""
+        self._ck(self._L.ptc_set_glass_shadows(self._h, 1 if on else 0))
+        return self
+
+    def get_glass_shadows(self):
+        on = C.c_int(0)
+        self._ck(self._L.ptc_get_glass_shadows(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def glass_shadow_stats(self):
+        return self._get(self._L.ptc_get_glass_shadow_stats, PtcGlassShadowStats)
+
+    def glass_any(self, origins, dirs, tmax):
+        """ptc_debug_glass_any: explicit shadow rays through the shadow resolution: (the RGB transmittance per ray (n, 3) — 0: occluded —, the surfaces passed (n,))."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        tm, tp = _f(tmax)
+        n = o.shape[0]
+        assert d.shape[0] == n and tm.size == n
+        out, layers = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        self._ck(self._L.ptc_debug_glass_any(self._h, op, dp, tp, n, _ptr(out), _ptr(layers)))
+        return out, layers
 
     def set_camera(self, position, target, fov_y, aspect):
         self._ck(self._L.ptc_set_camera(self._h, _f(position)[1], _f(target)[1], fov_y, aspect))

@@ -454,6 +454,53 @@ def glass_slab(thin: bool = False, thickness: float = 0.5, transmission: float =
     return d
 
 
+def glass_panes(n: int = 3, spacing: float = 0.25, tilt: float = 0.0, transmission: float = 1.0, ior: float = 1.5, base=(0.9, 0.8, 0.7), metallic: float = 0.0,
+                emitter: bool = False, sheets=(), texture_filter: str = "nearest", textured: bool = False) -> SceneDesc:
+    """The transparent-shadow test scene (csrc/pt_glass_shadow.h): a Lambert floor at y = 0 (primitives 0-1), an optional emissive quad facing down at y = 4
+    (emitter=True: primitives 2-3), then a stack of n thin-walled panes over x, z in [-2, 2] at y = 1 + spacing k (normal +y, one material; pane k is primitives
+    first + 2k, first + 2k + 1).  tilt > 0 turns the four vertex normals of every pane away from +y by different amounts (tan of the angle up to `tilt`), so that the
+    shading normal differs from the face normal and varies over the pane.  textured=True gives the panes a 4x4 base-colour texture.  sheets: alpha sheets below the
+    panes, added last, from y = 0.75 downwards 0.25 apart: "blend" (8x8 texture, alpha in {0, 64, 128, 192, 255}) or "mask" (8x8 checker of 2x2-texel cells, cutoff 0.5).
+    Seen from above, slanted, as glass_slab."""
+    mats = [Material((0.7, 0.7, 0.7, 1.0), 0.0, 1.0)]
+    meshes = [MeshDesc(*_quad((-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4)), 0)]
+    if emitter:
+        mats.append(Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (20.0, 20.0, 20.0)))
+        meshes.append(MeshDesc(*_quad((-1.0, 4.0, -1.0), (1.0, 4.0, -1.0), (1.0, 4.0, 1.0), (-1.0, 4.0, 1.0)), len(mats) - 1))     # normal -y
+    textures = []
+    if textured:
+        yy, xx = np.mgrid[0:4, 0:4]
+        textures.append(np.stack([(37 * xx + 90) % 200 + 55, (53 * yy + 60) % 200 + 55, (17 * (xx + yy)) % 200 + 55, np.full((4, 4), 255)], -1).astype(np.uint8))
+    mats.append(Material(tuple(base) + (1.0,), metallic, 0.2, (0, 0, 0), 0 if textured else -1, -1, -1, "opaque", 0.5, transmission, ior, True))
+    g = len(mats) - 1
+    a = 2.0
+    lean = np.array([(1.0, 0.0, 0.3), (-0.4, 0.0, 1.0), (0.2, 0.0, -0.9), (-1.0, 0.0, -0.5)])
+    for k in range(n):
+        y = 1.0 + spacing * k
+        v, i = _quad((-a, y, a), (a, y, a), (a, y, -a), (-a, y, -a))
+        if tilt > 0.0:
+            nrm = np.array([0.0, 1.0, 0.0]) + tilt * np.roll(lean, k, 0)
+            v["normal"] = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32)
+        meshes.append(MeshDesc(v, i, g))
+    yy, xx = np.mgrid[0:8, 0:8]
+    for k, kind in enumerate(sheets):
+        if kind == "mask":
+            alpha = np.where(((xx // 2 + yy // 2) % 2) == 0, 255, 0)
+        else:
+            alpha = np.asarray([0, 64, 128, 192, 255])[(xx + 2 * yy + k) % 5]
+        rgb = np.stack([(37 * xx + 11 * k) % 200 + 40, (53 * yy + 29 * k) % 200 + 40, (17 * (xx + yy) + 71 * k) % 200 + 40], -1)
+        textures.append(np.concatenate([rgb, alpha[..., None]], -1).astype(np.uint8))
+        mats.append(Material((1.0, 1.0, 1.0, 1.0), 0.0, 1.0, (0, 0, 0), len(textures) - 1, -1, -1, kind, 0.5))
+        y = 0.75 - 0.25 * k
+        meshes.append(MeshDesc(*_quad((-3, y, 3), (3, y, 3), (3, y, -3), (-3, y, -3)), len(mats) - 1))
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    cam = CameraDesc((1.5, 6.0, 2.5), (0.0, 1.0, 0.0), math.radians(20.0), 1.0)
+    d = SceneDesc(mats, meshes, inst, cam, "glass_panes")
+    d.textures = textures
+    d.texture_filter = texture_filter
+    return d
+
+
 def glass_ball(nu: int = 24, nv: int = 12, ior: float = 1.5, transmission: float = 1.0, base=(1.0, 1.0, 1.0), env: float = 1.0, attenuation_color=(1.0, 1.0, 1.0),
                attenuation_distance: float = 0.0) -> SceneDesc:
     """A closed solid glass ball of radius 1 (smooth normals, 2 nu (nv - 1) triangles) in a constant environment of radiance `env`, and nothing else: with base 1
@@ -469,4 +516,4 @@ def glass_ball(nu: int = 24, nv: int = 12, ior: float = 1.5, transmission: float
 
 def by_name(name: str, **kw) -> SceneDesc:
     return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
-            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_ball": glass_ball}[name](**kw)
+            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_panes": glass_panes, "glass_ball": glass_ball}[name](**kw)
