@@ -793,4 +793,5 @@ int ptc_debug_refit_host_parts(ptc_ctx*, uint64_t out[8]);
 #include "ptc_alpha.h"   /* alpha coverage: an extension with a header and a symbol prefix of its own */
 #include "ptc_glass.h"   /* dielectric transmission: likewise */
 #include "ptc_glass_shadows.h"   /* transparent shadows through thin glass: likewise */
+#include "ptc_shade_debug.h"   /* test hooks around k_shade: likewise */
 #endif /* PTC_H */

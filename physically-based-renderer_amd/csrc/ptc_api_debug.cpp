@@ -181,6 +181,114 @@ int ptc_debug_punctual_nee(ptc_ctx* c, const float* origins, const float* dirs, 
   return PTC_OK;
 }
 
+// One k_shade step of explicit rays (include/ptc_shade_debug.h).  The kernel variant is chosen through a copy of the launch configuration, so the launcher and
+// the kernels are the frame's.
+int ptc_debug_shade_step(ptc_ctx* c, const float* origins, const float* dirs, const float* throughput, const float* prev_pdf, const uint32_t* keys, uint32_t n,
+                         uint32_t bounce, uint32_t max_bounces, int variant, float* out_hit, float* out_lpath, uint8_t* out_alive, float* out_cont,
+                         uint8_t* out_shadow_valid, float* out_shadow) {
+  if (!c) return PTC_E_ARG;
+  if (!origins || !dirs || !throughput || !prev_pdf || !keys || !out_hit || !out_lpath || !out_alive || !out_cont || !out_shadow_valid || !out_shadow || n == 0 ||
+      bounce > (1u << 20) || max_bounces > (1u << 20) || variant < 0 || variant > 2)
+    return fail(c, PTC_E_ARG, "debug_shade_step: bad argument");
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* d = dirs + (size_t)i * 3;
+    bool ok = std::isfinite(prev_pdf[i]);
+    for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(origins[(size_t)i * 3 + k]) && std::isfinite(d[k]) && std::isfinite(throughput[(size_t)i * 3 + k]);
+    const double len2 = (double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2];
+    if (!ok || !(std::fabs(std::sqrt(len2) - 1.0) <= 1e-3)) return fail(c, PTC_E_ARG, "debug_shade_step: a ray is not finite or its direction not of unit length");
+  }
+  { int rc = debug_prepare(c, n, "debug_shade_step"); if (rc) return rc; }
+  for (int32_t m : c->alpha.mode)
+    if (m != PTC_ALPHA_OPAQUE) return fail(c, PTC_E_STATE, "debug_shade_step: the scene has a material with alpha coverage (that pass sits between trace and shade)");
+  for (size_t m = 0; m < c->mats.size(); ++m)
+    if (glass_tau(c, (int)m) > 0.0f) return fail(c, PTC_E_STATE, "debug_shade_step: the scene has a transmissive material (that pass sits between trace and shade)");
+  LaunchCfg cfg = c->cfg;
+  if (variant == 1) cfg.shade_sort = 1;
+  if (variant == 2) {
+    if (!pt_shade_tables_fit(c->scene.dsc)) return fail(c, PTC_E_STATE, "debug_shade_step: the scene's tables do not fit k_shade's copies in LDS (variant 2)");
+    cfg.shade_sort = 0; cfg.shade_tables_lds = 1;
+  }
+  const Lane& ln = c->lanes[0];
+  std::vector<float4> A(n), B(n), C(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
+    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
+    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], throughput[i * 3], throughput[i * 3 + 1]);
+    C[i] = make_float4(throughput[i * 3 + 2], prev_pdf[i], fi, fk);
+  }
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(ln.q.lpath, 0, (size_t)n * sizeof(float4)));
+  const DevQueues q = batch_queues(c, 0, n);
+  const DevScene sc = lane_scene(c, 0);
+  DevFrame fr{};
+  fr.max_bounces = (int)max_bounces;
+  pt_launch_set_counts(ln.stream, cfg, q, n, 0);
+  pt_launch_trace_closest(ln.stream, cfg, sc, q, 0, false);
+  pt_launch_shade(ln.stream, cfg, ln.d_scene, fr, q, 0, bounce);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(ln.stream));
+  std::vector<float4> H(n), L(n);
+  HIP_TRY(c, hipMemcpy(H.data(), ln.q.hit, n * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(L.data(), ln.q.lpath, n * sizeof(float4), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i) {
+    std::memcpy(out_hit + (size_t)i * 4, &H[i], 16);
+    out_lpath[i * 3] = L[i].x; out_lpath[i * 3 + 1] = L[i].y; out_lpath[i * 3 + 2] = L[i].z;
+  }
+  // the records lie at the front of each segment; a record says which path it belongs to
+  std::vector<uint32_t> seg_a(q.n_seg), seg_s(q.n_seg);
+  HIP_TRY(c, hipMemcpy(seg_a.data(), q.seg_ray[1], (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(seg_s.data(), q.seg_sh, (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
+  const size_t slots = (size_t)q.n_seg * q.seg_len;
+  std::vector<float4> RA(slots), RB(slots), RC(slots);
+  std::memset(out_alive, 0, n); std::memset(out_shadow_valid, 0, n);
+  std::memset(out_cont, 0, (size_t)n * 40); std::memset(out_shadow, 0, (size_t)n * 40);
+  HIP_TRY(c, hipMemcpy(RA.data(), q.ray[1].A, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(RB.data(), q.ray[1].B, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(RC.data(), q.ray[1].C, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
+    if (seg_a[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_shade_step: a segment holds more continuation records than slots");
+    for (uint32_t k = 0; k < seg_a[sg]; ++k) {
+      const size_t at = (size_t)sg * q.seg_len + k;
+      uint32_t path; std::memcpy(&path, &RC[at].z, 4);
+      if (path >= n || out_alive[path]) return fail(c, PTC_E_DEVICE, "debug_shade_step: a continuation record carries a path id that is out of range or taken");
+      out_alive[path] = 1;
+      const float r[10] = {RA[at].x, RA[at].y, RA[at].z, RA[at].w, RB[at].x, RB[at].y, RB[at].z, RB[at].w, RC[at].x, RC[at].y};
+      std::memcpy(out_cont + (size_t)path * 10, r, sizeof r);
+    }
+  }
+  HIP_TRY(c, hipMemcpy(RA.data(), q.shadow.A, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(RB.data(), q.shadow.B, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(RC.data(), q.shadow.C, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
+    if (seg_s[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_shade_step: a segment holds more shadow records than slots");
+    for (uint32_t k = 0; k < seg_s[sg]; ++k) {
+      const size_t at = (size_t)sg * q.seg_len + k;
+      uint32_t path; std::memcpy(&path, &RB[at].w, 4);
+      if (path >= n || out_shadow_valid[path]) return fail(c, PTC_E_DEVICE, "debug_shade_step: a shadow record carries a path id that is out of range or taken");
+      out_shadow_valid[path] = 1;
+      const float r[10] = {RA[at].x, RA[at].y, RA[at].z, RA[at].w, RB[at].x, RB[at].y, RB[at].z, RC[at].x, RC[at].y, RC[at].z};
+      std::memcpy(out_shadow + (size_t)path * 10, r, sizeof r);
+    }
+  }
+  return PTC_OK;
+}
+
+int ptc_debug_get_env_tables(ptc_ctx* c, int* w, int* h, int* ok, float* env, float* marg, float* cond) {
+  if (!c) return PTC_E_ARG;
+  if (!c->committed) return fail(c, PTC_E_STATE, "debug_get_env_tables: scene not committed");
+  const HostBuilt& B = *c->built;
+  if (w) *w = B.env_w;
+  if (h) *h = B.env_h;
+  if (ok) *ok = B.env_ok;
+  if (B.env_w <= 0 || B.env_h <= 0) return PTC_OK;
+  if (env) std::memcpy(env, B.env.data(), B.env.size() * 4);
+  if (marg) std::memcpy(marg, B.env_marg.data(), B.env_marg.size() * 4);
+  if (cond) std::memcpy(cond, B.env_cond.data(), B.env_cond.size() * 4);
+  return PTC_OK;
+}
+
 int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t first_sample, uint32_t n_samples, const uint32_t* pixels, uint32_t n_pixels,
                           float* origins, float* dirs) {
   if (!c) return PTC_E_ARG;

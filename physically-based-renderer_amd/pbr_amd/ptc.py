@@ -393,10 +393,21 @@ def _glass_shadow_prototypes():
     }
 
 
+def _shade_debug_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_shade_debug.h declares, in the header's order; exported under ptcx_ like ptc_alpha.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, ip, fp, u8p, u32p = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    return {
+        "ptc_debug_shade_step": (i, [vp, fp, fp, fp, fp, u32p, u32, u32, u32, i, fp, fp, u8p, fp, u8p, fp]),
+        "ptc_debug_get_env_tables": (i, [vp, ip, ip, ip, fp, fp, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
 _GLASS_PROTOTYPES = _glass_prototypes()
 _GLASS_SHADOW_PROTOTYPES = _glass_shadow_prototypes()
+_SHADE_DEBUG_PROTOTYPES = _shade_debug_prototypes()
 # every function include/ptc_glass.h declares, by the header's names
 GLASS_SYMBOLS = list(_GLASS_PROTOTYPES)
 # every function include/ptc_alpha.h declares, by the header's names
@@ -419,7 +430,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -1357,6 +1368,36 @@ class PathTracer:
         cdf = np.zeros(max(nl.value, 1), np.float32)
         self._ck(self._L.ptc_debug_get_shading_tables(self._h, None, _ptr(shade), None, _ptr(lights), _ptr(cdf)))
         return shade, lights[:max(nl.value, 1)], cdf
+
+    def shade_step(self, origins, dirs, throughput, prev_pdf, keys, bounce=0, max_bounces=8, variant=0):
+        """ptc_debug_shade_step: explicit rays (path id = index) through k_trace_closest and one k_shade launch at `bounce`.  A dict of arrays per ray: t, word
+        (the hit word, int32), uv, lpath (n, 3), alive, o / d / T (n, 3) and pdf of the continuation, shadow, so / sd (n, 3), tmax and contrib (n, 3) of the
+        shadow record; rows without a record are zero.  variant: 0 the launch policy's kernel, 1 k_shade<SORT>, 2 k_shade<TABLES_LDS>."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        T, Tp = _f(throughput)
+        pp, ppp = _f(prev_pdf)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = o.shape[0]
+        assert o.shape == d.shape == T.shape == (n, 3) and pp.shape == (n,) and k.shape == (n,)
+        hit, lp = np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32)
+        alive, sh = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        cont, srec = np.zeros((n, 10), np.float32), np.zeros((n, 10), np.float32)
+        self._ck(self._L.ptc_debug_shade_step(self._h, op, dp, Tp, ppp, _ptr(k), n, int(bounce), int(max_bounces), int(variant), _ptr(hit), _ptr(lp), _ptr(alive),
+                                              _ptr(cont), _ptr(sh), _ptr(srec)))
+        return dict(t=hit[:, 0].copy(), word=hit[:, 1].copy().view(np.int32), uv=hit[:, 2:4].copy(), lpath=lp, alive=alive.astype(bool), o=cont[:, 0:3].copy(),
+                    d=cont[:, 3:6].copy(), T=cont[:, 6:9].copy(), pdf=cont[:, 9].copy(), shadow=sh.astype(bool), so=srec[:, 0:3].copy(), sd=srec[:, 3:6].copy(),
+                    tmax=srec[:, 6].copy(), contrib=srec[:, 7:10].copy())
+
+    def env_tables(self):
+        """ptc_debug_get_env_tables: (env (h, w, 4) float32 = radiance rgb and texel pmf, marg (h,), cond (h, w), ok) of the committed scene; empty arrays
+        where the scene has no environment.  Works on a description-only context."""
+        w, h, ok = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self._L.ptc_debug_get_env_tables(self._h, C.byref(w), C.byref(h), C.byref(ok), None, None, None))
+        env, marg, cond = np.zeros((h.value, w.value, 4), np.float32), np.zeros(h.value, np.float32), np.zeros((h.value, w.value), np.float32)
+        if env.size:
+            self._ck(self._L.ptc_debug_get_env_tables(self._h, None, None, None, _ptr(env), _ptr(marg), _ptr(cond)))
+        return env, marg, cond, bool(ok.value)
 
     def raw_counters(self):
         buf = (C.c_uint64 * 32)()

@@ -514,6 +514,105 @@ def glass_ball(nu: int = 24, nv: int = 12, ior: float = 1.5, transmission: float
     return d
 
 
+# ---- the scenes of the k_shade step tests (tests/shade_reference.py): a floor in the plane z = 0 seen from +z, so that the face normal is exactly (0, 0, 1) ----
+SHADE_GRID = [(0.0, 1.0), (0.0, 0.0), (0.0, 0.05), (0.0, 0.5), (1.0, 0.0), (1.0, 0.05), (1.0, 0.5), (1.0, 1.0)]      # (metallic, roughness); (0, 1) is the Lambert class
+
+
+def _shade_floor(nx: int, ny: int, half: float, material_of, uv_of=None, normal_of=None, tangent_w_of=None):
+    """nx x ny square patches over [-half, half]^2 in the plane z = 0, front towards +z, one mesh of two triangles per patch: [(vertices, indices, material)]."""
+    out = []
+    sx, sy = 2.0 * half / nx, 2.0 * half / ny
+    for j in range(ny):
+        for i in range(nx):
+            k = j * nx + i
+            x0, y0 = -half + i * sx, -half + j * sy
+            P = [(x0, y0, 0.0), (x0 + sx, y0, 0.0), (x0 + sx, y0 + sy, 0.0), (x0, y0 + sy, 0.0)]
+            N = normal_of(k) if normal_of else [(0.0, 0.0, 1.0)] * 4
+            N = [np.asarray(n, np.float64) / np.linalg.norm(n) for n in N]
+            w = tangent_w_of(k) if tangent_w_of else 1.0
+            T = [(1.0, 0.0, 0.0, w)] * 4
+            (u0, v0), (u1, v1) = uv_of(k) if uv_of else ((0.0, 0.0), (1.0, 1.0))
+            uv = [(u0, v0), (u1, v0), (u1, v1), (u0, v1)]
+            out.append((_verts(P, N, T, uv), np.asarray([0, 1, 2, 0, 2, 3], np.uint32), material_of(k)))
+    return out
+
+
+def _shade_desc(parts, mats, name, fov=1.0) -> SceneDesc:
+    meshes = [MeshDesc(v, i, m) for v, i, m in parts]
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    return SceneDesc(mats, meshes, inst, CameraDesc((0.0, 0.0, 4.0), (0.0, 0.0, 0.0), fov, 1.0), name)
+
+
+def shade_lobes() -> SceneDesc:
+    """3 x 3 floor patches over the material grid SHADE_GRID (the ninth: roughness 0.2 without metal), a tiny bright emitter above the floor and a large dim one standing at
+    the floor's +x edge, which the floor next to that edge sees nearly edge-on.  The camera sees the floor and its surroundings, not the large emitter: a ray that
+    hits an emitter samples that emitter's own plane half of the time, which no precision decides.  No environment.  21 triangles."""
+    cols = [(0.8, 0.7, 0.6), (0.9, 0.5, 0.3), (0.4, 0.8, 0.5), (0.5, 0.5, 0.9), (0.95, 0.8, 0.4), (0.9, 0.9, 0.9), (0.7, 0.3, 0.3), (0.6, 0.6, 0.2)]
+    mats = [Material(c + (1.0,), m, r) for c, (m, r) in zip(cols, SHADE_GRID)] + [Material((0.2, 0.3, 0.7, 1.0), 0.0, 0.2)]
+    mats += [Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (4000.0, 3000.0, 2000.0)), Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (0.4, 0.5, 0.6))]
+    parts = _shade_floor(3, 3, 1.5, lambda k: k)
+    e = 0.01
+    tiny = _verts([(0.3 - e, 0.2 - e, 2.0), (0.3 - e, 0.2 + e, 2.0), (0.3 + e, 0.2 - e, 2.0)], [(0, 0, -1)] * 3, [(1, 0, 0)] * 3, [(0, 0), (0, 1), (1, 0)])
+    parts.append((tiny, np.asarray([0, 1, 2], np.uint32), 9))
+    parts.append((*_quad((1.6, -1.5, 0.3), (1.6, -1.5, 1.8), (1.6, -0.5, 1.8), (1.6, -0.5, 0.3)), 10))      # faces -x; outside the camera's view
+    return _shade_desc(parts, mats, "shade_lobes", fov=0.8)
+
+
+def _shade_textures():
+    """Six RGBA8 textures: colour, normal and metal-rough of 5 x 3 (one set), and a second normal map of 4 x 4, colour and metal-rough of 5 x 3 (sizes differ: no
+    interleaved copy).  Normal texels stay within 45 degrees of +z."""
+    rng = np.random.default_rng(41)
+
+    def colour(w, h):
+        return np.concatenate([rng.integers(30, 256, (h, w, 3)), np.full((h, w, 1), 255)], -1).astype(np.uint8)
+
+    def normal(w, h):
+        xy = rng.integers(128 - 60, 128 + 61, (h, w, 2))
+        return np.concatenate([xy, rng.integers(215, 256, (h, w, 1)), np.full((h, w, 1), 255)], -1).astype(np.uint8)
+
+    def metal_rough(w, h):
+        t = rng.integers(0, 256, (h, w, 4))
+        t[..., 2] = rng.integers(0, 2, (h, w)) * 255 * rng.integers(0, 2, (h, w)) + rng.integers(0, 256, (h, w)) * (1 - rng.integers(0, 2, (h, w)))
+        return np.clip(t, 0, 255).astype(np.uint8)
+
+    return [colour(5, 3), normal(5, 3), metal_rough(5, 3), colour(5, 3), normal(4, 4), metal_rough(5, 3)]
+
+
+def shade_textured(texture_filter: str = "nearest") -> SceneDesc:
+    """3 x 2 floor patches with colour, normal and metal-rough textures of 5 x 3 texels (one interleaved texture set, one material whose normal map has another size,
+    one with a colour texture alone), texture coordinates from -0.7 to 1.9, tilted vertex normals, tangents of both handednesses; an 8 x 4 environment with zero
+    texels and one emitter above the floor.  14 triangles."""
+    mats = [Material((0.9, 0.8, 0.7, 1.0), 0.0, 1.0, (0, 0, 0), 0, -1, -1), Material((1.0, 0.9, 0.8, 1.0), 1.0, 0.9, (0, 0, 0), 0, 1, 2),
+            Material((0.8, 0.9, 1.0, 1.0), 0.8, 1.0, (0, 0, 0), 3, 4, 5), Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (6.0, 5.0, 4.0))]
+    uvs = [((-0.7, -0.4), (1.9, 1.3)), ((0.1, 0.2), (0.9, 0.8)), ((1.9, 1.6), (-0.6, -0.3))]
+    tilt = np.random.default_rng(43).uniform(-0.25, 0.25, (6, 4, 2))
+    parts = _shade_floor(3, 2, 1.5, lambda k: k % 3, uv_of=lambda k: uvs[(k + k // 3) % 3], normal_of=lambda k: [(tx, ty, 1.0) for tx, ty in tilt[k]],
+                         tangent_w_of=lambda k: -1.0 if k in (1, 2, 3) else 1.0)
+    parts.append((*_quad((1.2, -0.4, 2.5), (1.2, 0.4, 2.5), (2.0, 0.4, 2.5), (2.0, -0.4, 2.5)), 3))      # faces -z; outside the camera's view
+    d = _shade_desc(parts, mats, "shade_textured", fov=1.1)
+    d.textures = _shade_textures()
+    d.texture_filter = texture_filter
+    env = np.random.default_rng(47).uniform(0.0, 1.5, (4, 8, 3)).astype(np.float32)
+    env[0, 2:5] = 0.0
+    env[2, :] = 0.0
+    env[3, 6] = 0.0
+    d.env = env
+    return d
+
+
+def shade_sky() -> SceneDesc:
+    """The floor of shade_lobes without emitters under a 64 x 32 environment whose two polar rows are the brightest.  18 triangles."""
+    d = shade_lobes()
+    d.meshes, d.instances, d.materials, d.name = d.meshes[:9], d.instances[:9], d.materials[:9], "shade_sky"
+    env = np.random.default_rng(53).uniform(0.05, 1.0, (32, 64, 3)).astype(np.float32)
+    env[0] *= 40.0
+    env[31] *= 25.0
+    env[10, 20:30] = 0.0
+    d.env = env
+    return d
+
+
 def by_name(name: str, **kw) -> SceneDesc:
     return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
-            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_panes": glass_panes, "glass_ball": glass_ball}[name](**kw)
+            "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_panes": glass_panes, "glass_ball": glass_ball,
+            "shade_lobes": shade_lobes, "shade_textured": shade_textured, "shade_sky": shade_sky}[name](**kw)

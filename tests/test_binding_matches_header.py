@@ -47,6 +47,27 @@ def test_prototype_table_is_in_the_headers_order(pbr, ptc_h):
     assert list(pbr.ptc._PROTOTYPES) == list(ptc_h.prototypes)
 
 
+def test_shade_debug_table_matches_its_header(pbr):
+    """include/ptc_shade_debug.h against the binding's table: same functions in the same order, every one mapped to its ptcx_ name, the loaded library carrying
+    the table; the core interface is what it was."""
+    import re
+
+    path = os.path.join(ROOT, "include", "ptc_shade_debug.h")
+    h = c_header.Header(path, "ptc_")
+    table = pbr.ptc._SHADE_DEBUG_PROTOTYPES
+    macros = dict(re.findall(r"^#define (ptc_\w+) (ptcx_\w+)$", open(path).read(), flags=re.M))
+    assert list(h.prototypes) == list(table) == list(macros) == ["ptc_debug_shade_step", "ptc_debug_get_env_tables"]
+    assert all(macros[n] == "ptcx_" + n[4:] for n in macros)
+    assert c_header.check_prototypes(h, table) == []
+    assert list(h.structs) == []
+    L = pbr.load_library()
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert L.ptc_abi_version() == 4 and not set(table) & set(pbr.ptc.ABI_SYMBOLS)
+    assert '#include "ptc_shade_debug.h"' in open(os.path.join(ROOT, "include", "ptc.h")).read()
+
+
 def test_struct_mirrors_match_the_header(pbr, ptc_h):
     assert len(ptc_h.structs) == 9 and "ptc_ctx" not in ptc_h.structs and "ptc_group" not in ptc_h.structs
     bad = []
