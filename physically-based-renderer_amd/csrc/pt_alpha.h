@@ -19,7 +19,8 @@
 // Shadow rays (no random numbers): the shadow queue is first traced by k_trace_any in its flag-writing form.  A record flagged free adds its contribution
 // as AnyRay::publish does.  A flagged record is walked through its occluders by the closest-hit kernel: Tr = 1, rem = tmax; a miss or a hit with t >= rem ends
 // the walk as visible; a hit with t < rem multiplies Tr by pt_alpha_transmit; Tr == 0: occluded; k == max_layers: occluded (exhaustion, counted); otherwise on
-// from o' with rem = rem - t, k = k + 1.  Visible: lpath[path].c = lpath[path].c + Tr * contrib.c, the product skipped when Tr == 1.
+// from o' with rem = rem - t, k = k + 1.  Visible: lpath[path].c = lpath[path].c + Tr * contrib.c, the product skipped when Tr == 1.  The kernel is the shadow
+// walk of pt_glass_shadow.h (k_glass_filter_shadow) without a glass table: it carries Tr in three equal channels.
 //
 // RNG: k_shade draws at the indices 0 .. max_bounces + 1 and the punctual pass at PT_LIGHTS_RNG_BASE + ..; PT_ALPHA_RNG_BASE + .. is disjoint from both.
 //
@@ -82,14 +83,10 @@ inline uint32_t pt_alpha_tables(const std::vector<int32_t>& tri_mat, size_t n_ma
 
 // ---- the kernel (pt_alpha.hip) ---------------------------------------------------------------------------------------------------------------------
 // `aq` is the lane's alpha queue as a DevQueues view (ray[0] = the continuation records, hit, cnt, seg_ray[0], pre_ray of its own; seg_sh all zero): the unchanged
-// pt_launch_scan and pt_launch_trace_closest take it as they take the batch's queues.  Continuation records: A = (o', d.x), B = (d.y, d.z, t_base or rem, source slot) —
-// the B.zw words the non-culling trace ignores —, C = (key, k, Tr, -).
+// pt_launch_scan and pt_launch_trace_closest take it as they take the batch's queues.  Continuation records: A = (o', d.x), B = (d.y, d.z, t_base, source slot) —
+// the B.zw words the non-culling trace ignores —, C = (key, k, -, -); the shadow walk's own: pt_glass_shadow.h.
 enum { PT_ALPHA_FORM_CLOSEST = 0, PT_ALPHA_FORM_GUIDE = 1, PT_ALPHA_FORM_SHADOW = 2 };
 // round 0 of a closest-hit resolution (first = true): the batch's rays ray[qi] and their hit records -> the rays that pass, compacted to the front of each segment of aq.
 // a later round (first = false): aq's records and THEIR hit records -> standing results scattered to the source slots of q.hit, the rays that pass compacted in place.
 // form: PT_ALPHA_FORM_CLOSEST (stochastic) or PT_ALPHA_FORM_GUIDE (deterministic).  layers_out (or null): per source slot, the layers a ray passed (debug hook).
 void pt_launch_alpha_filter_closest(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& aq, int qi, uint32_t bounce, const DevAlpha&, int form, bool first, uint32_t* layers_out);
-// round 0 of a shadow resolution (first = true): the shadow queue and k_trace_any's flags -> free records published, flagged ones to aq with Tr = 1, rem = tmax.
-// a later round: aq's records and their hit records -> visible ones published with Tr, occluded ones dropped, the rest compacted in place.
-// tr_out (or null): per source slot, the transmittance of a visible record INSTEAD of the addition to lpath (debug hook).
-void pt_launch_alpha_filter_shadow(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& aq, const DevAlpha&, const uint8_t* flags, bool first, float* tr_out);

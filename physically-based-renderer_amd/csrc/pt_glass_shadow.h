@@ -13,7 +13,8 @@
 // kernel: Tr = (1, 1, 1), rem = tmax, k = 0; a miss or a hit with !(t < rem) ends the walk as visible; a hit on an alpha primitive multiplies every Tr_c by
 // pt_alpha_transmit and goes on from alpha's onward point; a hit on a transmissive primitive multiplies Tr_c by W_c and goes on from vfma(ng, -ray_eps, P), ng on
 // the ray's side; a hit on anything else: occluded; Tr == (0, 0, 0): occluded; k == L: occluded (exhaustion, counted); otherwise on with rem = rem - t, k = k + 1.
-// L = max(max_interactions, max_layers when the scene has alpha materials) of the frame.  Visible: lpath[path].c = lpath[path].c + Tr_c * contrib.c, the products
+// L = max(max_interactions, max_layers when the scene has alpha materials) of the frame; alpha's own walk (pt_alpha.h: no transparent shadows) is the same walk
+// without a glass table and with L = max_layers.  Visible: lpath[path].c = lpath[path].c + Tr_c * contrib.c, the products
 // skipped when Tr == (1, 1, 1): an unobstructed record adds the bits it always added, and a record that met alpha surfaces only adds what alpha's own walk adds.
 //
 // MIS.  Next-event estimation now reaches a light through thin panes, so a BSDF-sampled ray whose events were ALL thin transmissions (it went straight on) is no
@@ -59,11 +60,15 @@ PT_HD v3 pt_glass_shadow_transmit(const pt_glass_mat& m, v3 ng, v3 ns, v3 d, v3 
 // counters of the walk, one 64-bit word each: a wave adds its totals once, when it ends
 enum { PT_GLASS_SHADOW_WALKED = 0, PT_GLASS_SHADOW_PASSES, PT_GLASS_SHADOW_VISIBLE, PT_GLASS_SHADOW_EXHAUSTED, PT_GLASS_SHADOW_COUNTERS };
 
+// where a walk counts: a frame with transparent shadows into the four words above, alpha's own walk (pt_alpha.h) into PT_ALPHA_SHADOW_WALKED / _PASSES and
+// PT_ALPHA_EXHAUSTED of DevAlpha::counters, with no word for `visible` (null)
+struct ShadowWalkCounters { unsigned long long *walked, *passes, *visible, *exhausted; };
+
 // ---- the kernel (pt_glass_shadow.hip) ---------------------------------------------------------------------------------------------------------------
-// `gq` is the lane's glass queue (pt_glass.h).  Continuation records: A = (o', d.x), B = (d.y, d.z, rem, source slot), C = (Tr.xyz, k).
-// first = true: the shadow queue and k_trace_any's flags -> free records published, flagged ones to gq with Tr = 1, rem = tmax, k = 0.
-// a later round: gq's records and their hit records -> visible ones published with Tr, occluded ones dropped, the rest compacted in place.
-// al.bits == nullptr: the scene has no alpha material.  max_rounds is L above.  counters: [PT_GLASS_SHADOW_COUNTERS].
+// `sq` is the lane's glass queue (pt_glass.h), or its alpha queue for alpha's own walk.  Continuation records: A = (o', d.x), B = (d.y, d.z, rem, source slot), C = (Tr.xyz, k).
+// first = true: the shadow queue and k_trace_any's flags -> free records published, flagged ones to sq with Tr = 1, rem = tmax, k = 0.
+// a later round: sq's records and their hit records -> visible ones published with Tr, occluded ones dropped, the rest compacted in place.
+// al.bits == nullptr: the scene has no alpha material.  gl.bits == nullptr: alpha's own walk, every other hit is an opaque occluder.  max_rounds is L above.
 // tr_out / layers_out (or null): per source slot, the RGB transmittance of a visible record INSTEAD of the addition to lpath, and the surfaces it passed (debug hook).
-void pt_launch_glass_filter_shadow(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& gq, const DevAlpha& al, const DevGlass& gl, uint32_t max_rounds,
-                                   unsigned long long* counters, const uint8_t* flags, bool first, float* tr_out, uint32_t* layers_out);
+void pt_launch_glass_filter_shadow(hipStream_t, const DevScene&, const DevQueues& q, const DevQueues& sq, const DevAlpha& al, const DevGlass& gl, uint32_t max_rounds,
+                                   const ShadowWalkCounters& ctr, const uint8_t* flags, bool first, float* tr_out, uint32_t* layers_out);

@@ -9,6 +9,42 @@ PT_DEV bool alpha_bit(const DevAlpha& al, uint32_t prim) { return (al.bits[prim 
 PT_DEV bool glass_bit(const DevGlass& gl, uint32_t prim) { return (gl.bits[prim >> 5] >> (prim & 31u)) & 1u; }
 PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
 
+// ---- the segment walk: the loop of every filter kernel (pt_alpha.hip, pt_glass.hip, pt_glass_shadow.hip) ---------------------------------------------
+// Blocks of WALK_BLOCK threads, one WAVE owns one queue segment (seg = blockIdx.x * WALK_WAVES + wave), takes its `seg_count[seg]` slots 64 at a time in queue order,
+// and compacts the records that go on to the front of the same segment of the side queue `sq` with a ballot and mbcnt64: no atomic on the data path, no block
+// barrier, and a wave never writes more records than it read — which is also why a later round can compact IN PLACE (seg_count == sq.seg_ray[0]): a batch of 64 is
+// loaded whole before anything is stored, and what it stores lies at or before its own slots.  An empty round (every segment count 0) is a launch whose waves
+// read one word each.
+//   record(slot) -> WalkNext   one lane's record: whether it goes on, and then its continuation (A, B, C); a result that stands it stores itself, to its SOURCE slot
+//                              (single owner, one continuation per source record); what the kernel counts it leaves in the kernel's own flags
+//   tally(mp)                  once per batch, whole wave: mp is the ballot of the lanes that go on; the kernel adds its flags' ballots to its sums and clears the
+//                              flags (a lane past the segment's end never ran record).  The sums go to wave_count when the walk returns (a wave without a
+//                              segment returns with every sum 0)
+#define WALK_BLOCK 256
+#define WALK_WAVES (WALK_BLOCK / 64)
+inline dim3 walk_grid(const DevQueues& q) { return dim3((q.n_seg + WALK_WAVES - 1u) / WALK_WAVES); }      // one wave per segment
+struct WalkNext { bool go_on; float4 A, B, C; };
+
+template <class Record, class Tally>
+PT_DEV void walk_segments(const DevQueues& q, const DevQueues& sq, const uint32_t* seg_count, Record record, Tally tally) {
+  const uint32_t lane = lane_id();
+  const uint32_t seg = blockIdx.x * WALK_WAVES + (threadIdx.x >> 6);
+  if (seg >= q.n_seg) return;
+  const RayQ rout = sq.ray[0];
+  const uint32_t base = seg * q.seg_len;
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg_count[seg]);
+  uint32_t out = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+    WalkNext c{};
+    if (i0 + lane < n) c = record(base + i0 + lane);
+    const uint64_t mp = __ballot(c.go_on);
+    if (c.go_on) { const uint32_t o = base + out + mbcnt64(mp); rout.A[o] = c.A; rout.B[o] = c.B; rout.C[o] = c.C; }
+    out += (uint32_t)__popcll(mp);
+    tally(mp);
+  }
+  if (lane == 0) sq.seg_ray[0][seg] = out;
+}
+
 // the alpha-mapped surface of a hit: its material's (mode, cutoff), its coverage a, and where a ray (.., d) that passes through it goes on from
 PT_DEV void alpha_surface(const DevScene& sc, const DevAlpha& al, float4 H, v3 d, int& mode, float& cutoff, float& a, v3& onward) {
   const uint32_t hw_word = (uint32_t)__float_as_int(H.y);

@@ -88,8 +88,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     const bool glass_shadows = glass_shadows_on(c);
     auto trace_shadows = [&]() {
       ScopedSpan t(c, st, 1);
-      if (glass_shadows) glass_resolve_shadow(c, l, st, cfg, sc, q, nullptr, nullptr);
-      else if (alpha) alpha_resolve_shadow(c, l, st, cfg, sc, q, nullptr);
+      if (glass_shadows || alpha) resolve_shadow(c, l, st, cfg, sc, q, glass_shadows, nullptr, nullptr);
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
@@ -298,8 +297,8 @@ int sum_lane_stats(ptc_ctx* c, unsigned long long st[ST_N]) {
 void Lane::teardown() {
   if (acc_done) (void)hipEventDestroy(acc_done);
   free_all(allocs);
-  free_all(aq_allocs);
-  free_all(gq_allocs);
+  free_all(alpha.allocs);
+  free_all(glass.allocs);
   if (q.cnt) (void)hipFree(q.cnt);
   if (q.stats) (void)hipFree(q.stats);
   if (q.seg_ray[0]) (void)hipFree(q.seg_ray[0]);
@@ -376,7 +375,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
     size_t free_b = 0, total_b = 0, held = 0;
     const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0) + (glass_shadows_on(c) ? kGlassFlagBytesPerPath : 0);
     for (const auto& ln : c->lanes)
-      held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.aq.cap * kAlphaBytesPerPath + (size_t)ln.gq.cap * (kGlassBytesPerPath + (ln.gq_flags ? kGlassFlagBytesPerPath : 0));
+      held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.alpha.q.cap * kAlphaBytesPerPath + (size_t)ln.glass.q.cap * (kGlassBytesPerPath + (ln.glass.flags ? kGlassFlagBytesPerPath : 0));
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
       const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / per_path;
       if (fit < batch_paths) batch_paths = fit;

@@ -4,19 +4,6 @@
 using namespace ptc_detail;
 
 namespace {
-// what the ray hooks need: a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared
-int debug_prepare(ptc_ctx* c, uint32_t n, const char* who) {
-  { int rd = need_device(c); if (rd) return rd; }
-  if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
-  { int rf = flush(c); if (rf) return rf; }
-  { int rs = sync_all_lanes(c); if (rs) return rs; }
-  c->in_frame = false; c->pending = 0; drop_guides(c);
-  int rc = ensure_lane_queues(c, n);
-  if (rc) return rc;
-  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
-  return PTC_OK;
-}
-
 // The debug getters read the host build: after a refit on the device its vertex-dependent arrays come back from HBM first.
 int refresh_host_copy(ptc_ctx* c) {
   if (!c->scene.host_stale || c->device < 0) return PTC_OK;
@@ -41,12 +28,90 @@ int probe_debug_prepare(ptc_ctx* c, uint32_t n) {
   c->in_frame = false; c->pending = 0; drop_guides(c);
   return ensure_lane_queues(c, n);
 }
+// which path a record belongs to: a shadow record says so in B.w, a ray record in C.z
+uint32_t shadow_path(const float4& B, const float4&) { return __builtin_bit_cast(uint32_t, B.w); }
+uint32_t ray_path(const float4&, const float4& C) { return __builtin_bit_cast(uint32_t, C.z); }
 bool probe_debug_args_bad(int n, uint32_t base, uint32_t first_sample, uint32_t n_samples) {
   return n < 1 || n > PTC_MAX_PROBES || n_samples == 0 || (uint64_t)n * (uint64_t)n_samples > 0x7fffffffull || (uint64_t)first_sample + n_samples > 0x100000000ull ||
          (uint64_t)base + (uint64_t)n > 0x100000000ull;
 }
 
 }  // namespace
+
+namespace ptc_detail {
+int debug_prepare(ptc_ctx* c, uint32_t n, const char* who, DebugFeatures features) {
+  { int rd = need_device(c); if (rd) return rd; }
+  if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
+  { int rf = flush(c); if (rf) return rf; }
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  c->in_frame = false; c->pending = 0; drop_guides(c);
+  int rc = ensure_lane_queues(c, n);
+  if (rc) return rc;
+  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
+  if (features == DebugPlain) return PTC_OK;
+  const bool glass = features == DebugAlphaGlass;
+  if ((rc = alpha_upload(c))) return rc;
+  if (glass && (rc = glass_upload(c))) return rc;
+  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
+  if (glass) { c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions; c->glass.frame_shadows = c->glass.shadows; }
+  if (alpha_on(c)) {
+    if ((rc = ensure_alpha_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
+  }
+  if (glass && glass_on(c)) {
+    if ((rc = ensure_glass_queues(c))) return rc;
+    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
+  }
+  return PTC_OK;
+}
+
+int stage_rays(ptc_ctx* c, const RayQ& rq, uint32_t n, const float* origins, const float* dirs, const RayFill& fill) {
+  std::vector<float4> A(n), B(n), C(n, make_float4(0, 0, 0, 0));
+  for (uint32_t i = 0; i < n; ++i) {
+    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
+    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 0.0f, 0.0f);
+    fill(i, B[i], C[i]);
+  }
+  HIP_TRY(c, hipMemcpy(rq.A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(rq.B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(rq.C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  return PTC_OK;
+}
+
+int read_hits(ptc_ctx* c, uint32_t n, float* out_t, int32_t* out_prim, float* out_uv) {
+  std::vector<float4> H(n);
+  HIP_TRY(c, hipMemcpy(H.data(), c->lanes[0].q.hit, n * sizeof(float4), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i) {
+    int32_t pc; std::memcpy(&pc, &H[i].y, 4);   // prim | class<<28, or -1
+    out_t[i] = H[i].x; out_prim[i] = pc < 0 ? -1 : (pc & 0x0fffffff); out_uv[i * 2] = H[i].z; out_uv[i * 2 + 1] = H[i].w;
+  }
+  return PTC_OK;
+}
+
+int scatter_segment_records(ptc_ctx* c, const DevQueues& q, const uint32_t* seg_counts, const RayQ& rq, uint32_t (*path_of)(const float4& B, const float4& C), uint32_t n,
+                            const char* who, const char* what, const RecordSink& sink) {
+  std::vector<uint32_t> count(q.n_seg);
+  HIP_TRY(c, hipMemcpy(count.data(), seg_counts, (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
+  const size_t slots = (size_t)q.n_seg * q.seg_len;
+  std::vector<float4> A(slots), B(slots), C(slots);
+  HIP_TRY(c, hipMemcpy(A.data(), rq.A, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.data(), rq.B, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(C.data(), rq.C, slots * sizeof(float4), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> taken(n, 0);
+  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
+    if (count[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, std::string(who) + ": a segment holds more " + what + " records than slots");
+    for (uint32_t k = 0; k < count[sg]; ++k) {
+      const size_t at = (size_t)sg * q.seg_len + k;
+      const uint32_t path = path_of(B[at], C[at]);
+      if (path >= n || taken[path]) return fail(c, PTC_E_DEVICE, std::string(who) + ": a " + what + " record carries a path id that is out of range or taken");
+      taken[path] = 1;
+      sink(path, A[at], B[at], C[at]);
+    }
+  }
+  return PTC_OK;
+}
+}  // namespace ptc_detail
 
 extern "C" {
 // ---- test hooks -----------------------------------------------------------------------------------
@@ -55,25 +120,13 @@ int ptc_debug_trace_closest(ptc_ctx* c, const float* origins, const float* dirs,
   if (c->device >= 0 && (!origins || !dirs || !out_t || !out_prim || !out_uv || n == 0)) return fail(c, PTC_E_ARG, "debug_trace_closest: bad argument");
   { int rc = debug_prepare(c, n, "debug_trace_closest"); if (rc) return rc; }
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 0.0f, 0.0f);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  { int rc = stage_rays(c, ln.q.ray[0], n, origins, dirs, [](uint32_t, float4&, float4&) {}); if (rc) return rc; }
   const DevQueues q = batch_queues(c, 0, n);
   pt_launch_set_counts(ln.stream, c->cfg, q, n, 0);
   pt_launch_trace_closest(ln.stream, c->cfg, lane_scene(c, 0), q, 0, false);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(ln.stream));
-  std::vector<float4> H(n);
-  HIP_TRY(c, hipMemcpy(H.data(), ln.q.hit, n * sizeof(float4), hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n; ++i) {
-    int32_t pc; std::memcpy(&pc, &H[i].y, 4);   // prim | class<<28, or -1
-    out_t[i] = H[i].x; out_prim[i] = pc < 0 ? -1 : (pc & 0x0fffffff); out_uv[i * 2] = H[i].z; out_uv[i * 2 + 1] = H[i].w;
-  }
-  return PTC_OK;
+  return read_hits(c, n, out_t, out_prim, out_uv);
 }
 
 int ptc_debug_trace_any(ptc_ctx* c, const float* origins, const float* dirs, const float* tmax, uint32_t n, uint8_t* out_occluded) {
@@ -81,23 +134,15 @@ int ptc_debug_trace_any(ptc_ctx* c, const float* origins, const float* dirs, con
   if (c->device >= 0 && (!origins || !dirs || !tmax || !out_occluded || n == 0)) return fail(c, PTC_E_ARG, "debug_trace_any: bad argument");
   { int rc = debug_prepare(c, n, "debug_trace_any"); if (rc) return rc; }
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], tmax[i], 0.0f);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.shadow.A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.shadow.B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  uint8_t* d_out = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_out, n));
+  { int rc = stage_rays(c, as_rays(ln.q.shadow), n, origins, dirs, [&](uint32_t i, float4& B, float4&) { B.z = tmax[i]; }); if (rc) return rc; }
+  DevBuf<uint8_t> occ;
+  { int rc = ensure_buf(c, occ, n); if (rc) return rc; }
   const DevQueues q = batch_queues(c, 0, n);
   pt_launch_set_counts(ln.stream, c->cfg, q, 0, n);
-  pt_launch_trace_any(ln.stream, c->cfg, lane_scene(c, 0), q, d_out);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
-  if (e == hipSuccess) e = hipMemcpy(out_occluded, d_out, n, hipMemcpyDeviceToHost);
-  (void)hipFree(d_out);
-  if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_trace_any: ") + hipGetErrorString(e));
+  pt_launch_trace_any(ln.stream, c->cfg, lane_scene(c, 0), q, occ.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(ln.stream));
+  HIP_TRY(c, hipMemcpy(out_occluded, occ.p, n, hipMemcpyDeviceToHost));
   return PTC_OK;
 }
 
@@ -138,16 +183,9 @@ int ptc_debug_punctual_nee(ptc_ctx* c, const float* origins, const float* dirs, 
   if (c->lights.list.empty()) return fail(c, PTC_E_STATE, "debug_punctual_nee: no punctual light (ptc_add_light)");
   { int rc = upload_lights(c); if (rc) return rc; }
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n), C(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 1.0f, 1.0f);
-    C[i] = make_float4(1.0f, 0.0f, fi, fk);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  { int rc = stage_rays(c, ln.q.ray[0], n, origins, dirs, [&](uint32_t i, float4& B, float4& C) {
+      B.z = B.w = 1.0f; C = make_float4(1.0f, 0.0f, __builtin_bit_cast(float, i), __builtin_bit_cast(float, keys[i]));
+    }); if (rc) return rc; }
   const DevQueues q = batch_queues(c, 0, n);
   const DevScene sc = lane_scene(c, 0);
   pt_launch_set_counts(ln.stream, c->cfg, q, n, 0);
@@ -155,30 +193,15 @@ int ptc_debug_punctual_nee(ptc_ctx* c, const float* origins, const float* dirs, 
   pt_launch_shade_punctual(ln.stream, sc, q, 0, bounce, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(ln.stream));
-  // the records lie at the front of each segment; a record says which ray it belongs to
-  std::vector<uint32_t> seg_sh(q.n_seg);
-  HIP_TRY(c, hipMemcpy(seg_sh.data(), q.seg_sh, (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
-  const size_t slots = (size_t)q.n_seg * q.seg_len;
-  std::vector<float4> SA(slots), SB(slots), SC(slots);
-  HIP_TRY(c, hipMemcpy(SA.data(), q.shadow.A, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(SB.data(), q.shadow.B, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(SC.data(), q.shadow.C, slots * sizeof(float4), hipMemcpyDeviceToHost));
   std::memset(out_valid, 0, n);
   std::memset(out_origin, 0, (size_t)n * 12); std::memset(out_dir, 0, (size_t)n * 12); std::memset(out_tmax, 0, (size_t)n * 4); std::memset(out_contrib, 0, (size_t)n * 12);
-  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
-    if (seg_sh[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_punctual_nee: a segment holds more shadow records than slots");
-    for (uint32_t k = 0; k < seg_sh[sg]; ++k) {
-      const size_t at = (size_t)sg * q.seg_len + k;
-      uint32_t path; std::memcpy(&path, &SB[at].w, 4);
-      if (path >= n || out_valid[path]) return fail(c, PTC_E_DEVICE, "debug_punctual_nee: a shadow record carries a path id that is out of range or taken");
-      out_valid[path] = 1;
-      out_origin[path * 3] = SA[at].x; out_origin[path * 3 + 1] = SA[at].y; out_origin[path * 3 + 2] = SA[at].z;
-      out_dir[path * 3] = SA[at].w; out_dir[path * 3 + 1] = SB[at].x; out_dir[path * 3 + 2] = SB[at].y;
-      out_tmax[path] = SB[at].z;
-      out_contrib[path * 3] = SC[at].x; out_contrib[path * 3 + 1] = SC[at].y; out_contrib[path * 3 + 2] = SC[at].z;
-    }
-  }
-  return PTC_OK;
+  return scatter_segment_records(c, q, q.seg_sh, as_rays(q.shadow), shadow_path, n, "debug_punctual_nee", "shadow", [&](uint32_t path, const float4& A, const float4& B, const float4& C) {
+    out_valid[path] = 1;
+    out_origin[path * 3] = A.x; out_origin[path * 3 + 1] = A.y; out_origin[path * 3 + 2] = A.z;
+    out_dir[path * 3] = A.w; out_dir[path * 3 + 1] = B.x; out_dir[path * 3 + 2] = B.y;
+    out_tmax[path] = B.z;
+    out_contrib[path * 3] = C.x; out_contrib[path * 3 + 1] = C.y; out_contrib[path * 3 + 2] = C.z;
+  });
 }
 
 // One k_shade step of explicit rays (include/ptc_shade_debug.h).  The kernel variant is chosen through a copy of the launch configuration, so the launcher and
@@ -209,16 +232,10 @@ int ptc_debug_shade_step(ptc_ctx* c, const float* origins, const float* dirs, co
     cfg.shade_sort = 0; cfg.shade_tables_lds = 1;
   }
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n), C(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], throughput[i * 3], throughput[i * 3 + 1]);
-    C[i] = make_float4(throughput[i * 3 + 2], prev_pdf[i], fi, fk);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  { int rc = stage_rays(c, ln.q.ray[0], n, origins, dirs, [&](uint32_t i, float4& B, float4& C) {
+      B.z = throughput[i * 3]; B.w = throughput[i * 3 + 1];
+      C = make_float4(throughput[i * 3 + 2], prev_pdf[i], __builtin_bit_cast(float, i), __builtin_bit_cast(float, keys[i]));
+    }); if (rc) return rc; }
   HIP_TRY(c, hipMemset(ln.q.lpath, 0, (size_t)n * sizeof(float4)));
   const DevQueues q = batch_queues(c, 0, n);
   const DevScene sc = lane_scene(c, 0);
@@ -236,43 +253,18 @@ int ptc_debug_shade_step(ptc_ctx* c, const float* origins, const float* dirs, co
     std::memcpy(out_hit + (size_t)i * 4, &H[i], 16);
     out_lpath[i * 3] = L[i].x; out_lpath[i * 3 + 1] = L[i].y; out_lpath[i * 3 + 2] = L[i].z;
   }
-  // the records lie at the front of each segment; a record says which path it belongs to
-  std::vector<uint32_t> seg_a(q.n_seg), seg_s(q.n_seg);
-  HIP_TRY(c, hipMemcpy(seg_a.data(), q.seg_ray[1], (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(seg_s.data(), q.seg_sh, (size_t)q.n_seg * 4, hipMemcpyDeviceToHost));
-  const size_t slots = (size_t)q.n_seg * q.seg_len;
-  std::vector<float4> RA(slots), RB(slots), RC(slots);
   std::memset(out_alive, 0, n); std::memset(out_shadow_valid, 0, n);
   std::memset(out_cont, 0, (size_t)n * 40); std::memset(out_shadow, 0, (size_t)n * 40);
-  HIP_TRY(c, hipMemcpy(RA.data(), q.ray[1].A, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(RB.data(), q.ray[1].B, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(RC.data(), q.ray[1].C, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
-    if (seg_a[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_shade_step: a segment holds more continuation records than slots");
-    for (uint32_t k = 0; k < seg_a[sg]; ++k) {
-      const size_t at = (size_t)sg * q.seg_len + k;
-      uint32_t path; std::memcpy(&path, &RC[at].z, 4);
-      if (path >= n || out_alive[path]) return fail(c, PTC_E_DEVICE, "debug_shade_step: a continuation record carries a path id that is out of range or taken");
+  { int rc = scatter_segment_records(c, q, q.seg_ray[1], q.ray[1], ray_path, n, "debug_shade_step", "continuation", [&](uint32_t path, const float4& A, const float4& B, const float4& C) {
       out_alive[path] = 1;
-      const float r[10] = {RA[at].x, RA[at].y, RA[at].z, RA[at].w, RB[at].x, RB[at].y, RB[at].z, RB[at].w, RC[at].x, RC[at].y};
+      const float r[10] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, C.x, C.y};
       std::memcpy(out_cont + (size_t)path * 10, r, sizeof r);
-    }
-  }
-  HIP_TRY(c, hipMemcpy(RA.data(), q.shadow.A, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(RB.data(), q.shadow.B, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(RC.data(), q.shadow.C, slots * sizeof(float4), hipMemcpyDeviceToHost));
-  for (uint32_t sg = 0; sg < q.n_seg; ++sg) {
-    if (seg_s[sg] > q.seg_len) return fail(c, PTC_E_DEVICE, "debug_shade_step: a segment holds more shadow records than slots");
-    for (uint32_t k = 0; k < seg_s[sg]; ++k) {
-      const size_t at = (size_t)sg * q.seg_len + k;
-      uint32_t path; std::memcpy(&path, &RB[at].w, 4);
-      if (path >= n || out_shadow_valid[path]) return fail(c, PTC_E_DEVICE, "debug_shade_step: a shadow record carries a path id that is out of range or taken");
-      out_shadow_valid[path] = 1;
-      const float r[10] = {RA[at].x, RA[at].y, RA[at].z, RA[at].w, RB[at].x, RB[at].y, RB[at].z, RC[at].x, RC[at].y, RC[at].z};
-      std::memcpy(out_shadow + (size_t)path * 10, r, sizeof r);
-    }
-  }
-  return PTC_OK;
+    }); if (rc) return rc; }
+  return scatter_segment_records(c, q, q.seg_sh, as_rays(q.shadow), shadow_path, n, "debug_shade_step", "shadow", [&](uint32_t path, const float4& A, const float4& B, const float4& C) {
+    out_shadow_valid[path] = 1;
+    const float r[10] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, C.x, C.y, C.z};
+    std::memcpy(out_shadow + (size_t)path * 10, r, sizeof r);
+  });
 }
 
 int ptc_debug_get_env_tables(ptc_ctx* c, int* w, int* h, int* ok, float* env, float* marg, float* cond) {

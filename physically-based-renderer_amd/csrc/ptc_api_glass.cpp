@@ -10,43 +10,8 @@ using namespace ptc_detail;
 namespace {
 DevGlass dev_glass(const ptc_ctx* c) { return DevGlass{c->glass.bits.p, c->glass.mats.p, (uint32_t)c->glass.frame_interactions, c->glass.counters.p}; }
 
-// the lane's glass queue with the segment layout of the batch whose queues are q
-DevQueues glass_view(const ptc_ctx* c, int l, const DevQueues& q) {
-  DevQueues gq = c->lanes[(size_t)l].gq;
-  gq.lpath = q.lpath;
-  gq.n_seg = q.n_seg; gq.seg_len = q.seg_len;
-  return gq;
-}
-
 void glass_tables(const ptc_ctx* c, std::vector<uint32_t>& bits, std::vector<pt_glass_mat>& mats, uint32_t& n) {
   n = pt_glass_tables(c->built->tri_mat, c->mats.size(), c->glass.params, bits, mats);
-}
-
-// ptc_debug_glass_*: what ptc_api_debug.cpp's ray hooks need — a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters
-// cleared — and the alpha and glass tables, queues and counters of the committed scene
-int glass_debug_prepare(ptc_ctx* c, uint32_t n, const char* who) {
-  { int rd = need_device(c); if (rd) return rd; }
-  if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
-  { int rf = flush(c); if (rf) return rf; }
-  { int rs = sync_all_lanes(c); if (rs) return rs; }
-  c->in_frame = false; c->pending = 0; drop_guides(c);
-  int rc = ensure_lane_queues(c, n);
-  if (rc) return rc;
-  for (auto& ln : c->lanes) HIP_TRY(c, hipMemset(ln.q.stats, 0, ST_N * ST_STRIDE * sizeof(unsigned long long)));
-  if ((rc = alpha_upload(c))) return rc;
-  if ((rc = glass_upload(c))) return rc;
-  c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
-  c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions; c->glass.frame_shadows = c->glass.shadows;
-  if (alpha_on(c)) {
-    if ((rc = ensure_alpha_queues(c))) return rc;
-    HIP_TRY(c, hipMemset(c->alpha.counters.p, 0, PT_ALPHA_COUNTERS * sizeof(unsigned long long)));
-  }
-  if (glass_on(c)) {
-    if ((rc = ensure_glass_queues(c))) return rc;
-    HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
-  }
-  return PTC_OK;
 }
 }  // namespace
 
@@ -77,44 +42,33 @@ int glass_upload(ptc_ctx* c) {
 }
 
 // flag bytes only for a frame (or ray hook) that walks its shadow records through thin panes: turning the feature on after frames have run allocates the queue anew
-int ensure_glass_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::gq, &Lane::gq_allocs, &Lane::gq_flags, glass_shadows_on(c)); }
+int ensure_glass_queues(ptc_ctx* c) { return ensure_side_queues(c, &Lane::glass, glass_shadows_on(c)); }
 
-// The host cannot know how many rays go on without a read-back, so a resolution queues every round it may need: filter, then max_interactions x (scan, trace, [alpha],
-// filter).  A round with nothing left is launches that find their queue empty.  In round r the continuations' hits are first resolved by the alpha pass on the glass
-// view; its bounce argument only enters alpha's RNG index, and the value gives fresh numbers per interaction.
+// filter, then max_interactions x (scan, trace, [alpha], filter).  In round r the continuations' hits are first resolved by the alpha pass on the glass view; its
+// bounce argument only enters alpha's RNG index, and the value gives fresh numbers per interaction.
 void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, uint32_t* j_out) {
   ScopedSpan t(c, st, 6);
-  const DevQueues gq = glass_view(c, l, q);
+  const DevQueues gq = side_view(c->lanes[(size_t)l].glass, q);
   const DevGlass gl = dev_glass(c);
   const bool alpha = alpha_on(c), shadows = glass_shadows_on(c);
-  pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/true, shadows, j_out);
-  for (uint32_t r = 0; r < gl.max_interactions; ++r) {
-    pt_launch_scan(st, cfg, gq, 0);
-    pt_launch_trace_closest(st, cfg, sc, gq, 0, false);
-    if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, gq, 0, 0x01000000u + (bounce + 1u) * 64u + r, PT_ALPHA_FORM_CLOSEST, nullptr);
-    pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, /*first=*/false, shadows, j_out);
-  }
+  resolve_rounds(st, cfg, sc, gq, gl.max_interactions, [&](bool first) { pt_launch_glass_filter(st, sc, q, gq, qi, bounce, gl, first, shadows, j_out); },
+                 [&](uint32_t r) { if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, gq, 0, 0x01000000u + (bounce + 1u) * 64u + r, PT_ALPHA_FORM_CLOSEST, nullptr); });
 }
 
-// the shadow queue of q, counted and scanned, resolved to an RGB transmittance per record (pt_glass_shadow.h): the coarse flags by k_trace_any, then the walk through
-// the glass queue — a record that starts at k = 0 may be traced L + 1 times before it is exhausted, L the larger of the frame's max_interactions and, in a scene
-// with alpha materials, its max_layers
-void glass_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out, uint32_t* layers_out) {
-  ScopedSpan t(c, st, 6);
-  const DevQueues gq = glass_view(c, l, q);
-  const DevGlass gl = dev_glass(c);
-  const bool alpha = alpha_on(c);
-  const DevAlpha al = alpha ? DevAlpha{c->alpha.bits.p, c->alpha.mode_cutoff.p, (uint32_t)c->alpha.frame_layers, c->alpha.counters.p} : DevAlpha{nullptr, nullptr, 0u, nullptr};
-  const uint32_t L = alpha && al.max_layers > gl.max_interactions ? al.max_layers : gl.max_interactions;
-  const uint8_t* flags = c->lanes[(size_t)l].gq_flags;
-  unsigned long long* ctr = c->glass.shadow_counters.p;
-  pt_launch_trace_any(st, cfg, sc, q, c->lanes[(size_t)l].gq_flags);
-  pt_launch_glass_filter_shadow(st, sc, q, gq, al, gl, L, ctr, flags, /*first=*/true, tr_out, layers_out);
-  for (uint32_t r = 0; r <= L; ++r) {
-    pt_launch_scan(st, cfg, gq, 0);
-    pt_launch_trace_closest(st, cfg, sc, gq, 0, false);
-    pt_launch_glass_filter_shadow(st, sc, q, gq, al, gl, L, ctr, flags, /*first=*/false, tr_out, layers_out);
-  }
+// a record that starts at k = 0 may be traced L + 1 times before it is exhausted: L is the frame's max_layers for alpha's own walk; through glass, the larger of its
+// max_interactions and, in a scene with alpha materials, its max_layers
+void resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, bool through_glass, float* tr3_out, uint32_t* layers_out) {
+  ScopedSpan t(c, st, through_glass ? 6 : 5);
+  const SideQueue& side = through_glass ? c->lanes[(size_t)l].glass : c->lanes[(size_t)l].alpha;
+  const DevQueues sq = side_view(side, q);
+  const DevAlpha al = alpha_on(c) ? dev_alpha(c) : DevAlpha{nullptr, nullptr, 0u, nullptr};
+  const DevGlass gl = through_glass ? dev_glass(c) : DevGlass{nullptr, nullptr, 0u, nullptr};
+  const uint32_t L = al.max_layers > gl.max_interactions ? al.max_layers : gl.max_interactions;
+  unsigned long long *a = c->alpha.counters.p, *g = c->glass.shadow_counters.p;
+  const ShadowWalkCounters ctr = through_glass ? ShadowWalkCounters{g + PT_GLASS_SHADOW_WALKED, g + PT_GLASS_SHADOW_PASSES, g + PT_GLASS_SHADOW_VISIBLE, g + PT_GLASS_SHADOW_EXHAUSTED}
+                                               : ShadowWalkCounters{a + PT_ALPHA_SHADOW_WALKED, a + PT_ALPHA_SHADOW_PASSES, nullptr, a + PT_ALPHA_EXHAUSTED};
+  pt_launch_trace_any(st, cfg, sc, q, side.flags);
+  resolve_rounds(st, cfg, sc, sq, L + 1u, [&](bool first) { pt_launch_glass_filter_shadow(st, sc, q, sq, al, gl, L, ctr, side.flags, first, tr3_out, layers_out); }, [](uint32_t) {});
 }
 }  // namespace ptc_detail
 
@@ -214,19 +168,12 @@ int ptc_debug_glass_closest(ptc_ctx* c, const float* origins, const float* dirs,
                             float* out_t, int32_t* out_prim, float* out_uv, float* out_ray10, uint32_t* out_j) {
   if (!c) return PTC_E_ARG;
   if (c->device >= 0 && (!origins || !dirs || !keys || !out_t || !out_prim || !out_uv || !out_ray10 || !out_j || n == 0 || bounce > 0x0000ffffu)) return fail(c, PTC_E_ARG, "debug_glass_closest: bad argument");
-  int rc = glass_debug_prepare(c, n, "debug_glass_closest");
+  int rc = debug_prepare(c, n, "debug_glass_closest", DebugAlphaGlass);
   if (rc) return rc;
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n), C(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    float fi, fk; std::memcpy(&fi, &i, 4); std::memcpy(&fk, &keys[i], 4);
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], 1.0f, 1.0f);
-    C[i] = make_float4(1.0f, 1.0f, fi, fk);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.ray[0].C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  if ((rc = stage_rays(c, ln.q.ray[0], n, origins, dirs, [&](uint32_t i, float4& B, float4& C) {
+         B.z = B.w = 1.0f; C = make_float4(1.0f, 1.0f, __builtin_bit_cast(float, i), __builtin_bit_cast(float, keys[i]));
+       }))) return rc;
   DevBuf<uint32_t> jn;
   if ((rc = ensure_buf(c, jn, n))) return rc;
   HIP_TRY(c, hipMemset(jn.p, 0, (size_t)n * 4));
@@ -238,35 +185,24 @@ int ptc_debug_glass_closest(ptc_ctx* c, const float* origins, const float* dirs,
   if (glass_on(c)) glass_resolve_closest(c, 0, ln.stream, c->cfg, sc, q, 0, bounce, jn.p);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(ln.stream));
-  std::vector<float4> H(n);
-  HIP_TRY(c, hipMemcpy(H.data(), ln.q.hit, n * sizeof(float4), hipMemcpyDeviceToHost));
+  std::vector<float4> A(n), B(n), C(n);
   HIP_TRY(c, hipMemcpy(A.data(), ln.q.ray[0].A, n * sizeof(float4), hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(B.data(), ln.q.ray[0].B, n * sizeof(float4), hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(C.data(), ln.q.ray[0].C, n * sizeof(float4), hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemcpy(out_j, jn.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < n; ++i) {
-    int32_t pc; std::memcpy(&pc, &H[i].y, 4);
-    out_t[i] = H[i].x; out_prim[i] = pc < 0 ? -1 : (pc & 0x0fffffff); out_uv[i * 2] = H[i].z; out_uv[i * 2 + 1] = H[i].w;
     float* r = out_ray10 + (size_t)i * 10;
     r[0] = A[i].x; r[1] = A[i].y; r[2] = A[i].z; r[3] = A[i].w; r[4] = B[i].x; r[5] = B[i].y; r[6] = B[i].z; r[7] = B[i].w; r[8] = C[i].x; r[9] = C[i].y;
   }
-  return PTC_OK;
+  return read_hits(c, n, out_t, out_prim, out_uv);
 }
 
 int ptc_debug_glass_any(ptc_ctx* c, const float* origins, const float* dirs, const float* tmax, uint32_t n, float* out_tr3, uint32_t* out_layers) {
   if (!c) return PTC_E_ARG;
   if (c->device >= 0 && (!origins || !dirs || !tmax || !out_tr3 || !out_layers || n == 0)) return fail(c, PTC_E_ARG, "debug_glass_any: bad argument");
-  { int rc = glass_debug_prepare(c, n, "debug_glass_any"); if (rc) return rc; }
+  { int rc = debug_prepare(c, n, "debug_glass_any", DebugAlphaGlass); if (rc) return rc; }
   const Lane& ln = c->lanes[0];
-  std::vector<float4> A(n), B(n), C(n, make_float4(0, 0, 0, 0));
-  for (uint32_t i = 0; i < n; ++i) {
-    float fi; std::memcpy(&fi, &i, 4);
-    A[i] = make_float4(origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2], dirs[i * 3]);
-    B[i] = make_float4(dirs[i * 3 + 1], dirs[i * 3 + 2], tmax[i], fi);
-  }
-  HIP_TRY(c, hipMemcpy(ln.q.shadow.A, A.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.shadow.B, B.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(ln.q.shadow.C, C.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  { int rc = stage_rays(c, as_rays(ln.q.shadow), n, origins, dirs, [&](uint32_t i, float4& B, float4&) { B.z = tmax[i]; B.w = __builtin_bit_cast(float, i); }); if (rc) return rc; }
   DevBuf<float> tr;
   DevBuf<uint32_t> layers;
   DevBuf<uint8_t> occ;
@@ -277,7 +213,7 @@ int ptc_debug_glass_any(ptc_ctx* c, const float* origins, const float* dirs, con
   const DevScene sc = lane_scene(c, 0);
   const bool walk = glass_shadows_on(c);
   pt_launch_set_counts(ln.stream, c->cfg, q, 0, n);
-  if (walk) glass_resolve_shadow(c, 0, ln.stream, c->cfg, sc, q, tr.p, layers.p);
+  if (walk) resolve_shadow(c, 0, ln.stream, c->cfg, sc, q, /*through_glass=*/true, tr.p, layers.p);
   else pt_launch_trace_any(ln.stream, c->cfg, sc, q, occ.p);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(ln.stream));
@@ -326,7 +262,7 @@ int ptc_debug_get_glass_tables(ptc_ctx* c, uint32_t* n_prims, uint32_t* bits, ui
   if (n_mats) *n_mats = (uint32_t)c->mats.size();
   if (bits && !b.empty()) std::memcpy(bits, b.data(), b.size() * sizeof(uint32_t));
   if (mats8 && !m.empty()) std::memcpy(mats8, m.data(), m.size() * sizeof(pt_glass_mat));
-  for (const Lane& ln : c->lanes) if (ln.gq.cap) return 1;
+  for (const Lane& ln : c->lanes) if (ln.glass.q.cap) return 1;
   return PTC_OK;
 }
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -53,7 +54,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg);
     if (r_ != ncclSuccess) return fail((c), PTC_E_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
   } while (0)
 
-struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution, 6 a glass resolution
+struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution (alpha's own shadow walk included), 6 a glass resolution (the shadow walk of a frame with transparent shadows included)
 
 // An array in HBM and its owner: freed when the owner goes (with the context: after ptc_destroy made the device current), or early by release()
 template <class T> struct DevBuf {
@@ -82,6 +83,10 @@ struct StageTimer {
   int seconds(ptc_ctx* c, double* out);             // 0.0 when nothing was recorded; else waits for the stop event
 };
 
+// A lane's side queue as a DevQueues view — continuation records in ray[0], their hit records, header words, segment counts and statistics of its own — and the
+// flags k_trace_any writes for the shadow queue when a shadow walk goes through it
+struct SideQueue { DevQueues q{}; uint8_t* flags = nullptr; std::vector<void*> allocs; };
+
 // One lane: a stream with its own wavefront queues.  cnt/stats are allocated once; the large arrays grow on demand.
 struct Lane {
   hipStream_t stream = nullptr;
@@ -94,15 +99,9 @@ struct Lane {
   hipStream_t stream2 = nullptr;
   uint2* stack_ovf2 = nullptr;      // the any-hit launches' own overflow slab (concurrent kernels must not share one)
   std::vector<hipEvent_t> ev_scan, ev_any;
-  // alpha coverage (pt_alpha.h): the lane's alpha queue as a DevQueues view — continuation records in ray[0], their hit records, header words, segment counts and
-  // statistics of its own — and the flags k_trace_any writes for the shadow queue.  Allocated only while the committed scene has an alpha material (ensure_alpha_queues)
-  DevQueues aq{};
-  uint8_t* aq_flags = nullptr;
-  std::vector<void*> aq_allocs;
-  // dielectric transmission (pt_glass.h): the lane's glass queue, a DevQueues view like aq.  Allocated only while the committed scene has a transmissive material
-  DevQueues gq{};
-  uint8_t* gq_flags = nullptr;      // k_trace_any's flags for the shadow walk through thin glass (pt_glass_shadow.h): only once a frame began with ptc_set_glass_shadows on
-  std::vector<void*> gq_allocs;
+  // alpha coverage (pt_alpha.h) and dielectric transmission (pt_glass.h): a side queue each, allocated only while the committed scene has such a material
+  // (ensure_alpha_queues, ensure_glass_queues).  glass.flags only once a frame began with ptc_set_glass_shadows on (pt_glass_shadow.h)
+  SideQueue alpha, glass;
   void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
   void teardown();                  // ptc_destroy: everything but the overflow slabs (release_scene's), the streams after what ran on them
 };
@@ -540,10 +539,30 @@ int scene_commit(ptc_ctx* c, bool device_ok);
 // ---- ptc_api_alpha.cpp: alpha coverage (pt_alpha.h) ------------------------------------------------------------------------------------------------
 int alpha_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
 inline bool alpha_on(const ptc_ctx* c) { return c->alpha.n_prims > 0; }
-int ensure_side_queues(ptc_ctx* c, DevQueues Lane::*queue, std::vector<void*> Lane::*owner, uint8_t* Lane::*flags, bool with_flags = true);      // ptc_api_alpha.cpp: what the two below share
+inline DevAlpha dev_alpha(const ptc_ctx* c) { return DevAlpha{c->alpha.bits.p, c->alpha.mode_cutoff.p, (uint32_t)c->alpha.frame_layers, c->alpha.counters.p}; }
+int ensure_side_queues(ptc_ctx* c, SideQueue Lane::*side, bool with_flags);      // what the two ensure_*_queues share
 int ensure_alpha_queues(ptc_ctx* c);                   // every lane: an alpha queue as large as its queues (grow only; waits for the work in flight first)
 void alpha_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, int form, uint32_t* layers_out);
-void alpha_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out);
+
+// the lane's side queue with the segment layout of the batch whose queues are q
+inline DevQueues side_view(const SideQueue& side, const DevQueues& q) {
+  DevQueues sq = side.q;
+  sq.lpath = q.lpath;
+  sq.n_seg = q.n_seg; sq.seg_len = q.seg_len;
+  return sq;
+}
+// The host cannot know how many records go on without a read-back, so a resolution queues every round it may need: filter(first), then rounds x (scan, trace,
+// between(r), filter(later)) on the side-queue view.  A round with nothing left is launches that find their queue empty.
+template <class Filter, class Between>
+void resolve_rounds(hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& view, uint32_t rounds, Filter filter, Between between) {
+  filter(/*first=*/true);
+  for (uint32_t r = 0; r < rounds; ++r) {
+    pt_launch_scan(st, cfg, view, 0);
+    pt_launch_trace_closest(st, cfg, sc, view, 0, false);
+    between(r);
+    filter(/*first=*/false);
+  }
+}
 
 // ---- ptc_api_glass.cpp: dielectric transmission (pt_glass.h) ---------------------------------------------------------------------------------------
 int glass_upload(ptc_ctx* c);                          // the committed scene's tables -> device memory, when a commit came since (every lane idle)
@@ -553,7 +572,27 @@ int ensure_glass_queues(ptc_ctx* c);                   // every lane: a glass qu
 void glass_resolve_closest(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, uint32_t bounce, uint32_t* j_out);
 // transparent shadows (pt_glass_shadow.h): the frame walks its shadow records through thin panes — the feature is on and the scene has a thin transmissive primitive
 inline bool glass_shadows_on(const ptc_ctx* c) { return c->glass.frame_shadows != 0 && c->glass.n_thin > 0; }
-void glass_resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, float* tr_out, uint32_t* layers_out);
+// the shadow queue of q, counted and scanned, resolved to an RGB transmittance per record: k_trace_any's flags, then the walk (pt_glass_shadow.h).  through_glass: a
+// frame with transparent shadows — the glass queue, alpha and glass tables, a span of kind 6; else alpha's own walk — the alpha queue, no glass table, kind 5.
+// tr3_out / layers_out (or null): the debug hooks' outputs instead of the additions to lpath
+void resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, bool through_glass, float* tr3_out, uint32_t* layers_out);
+
+// ---- ptc_api_debug.cpp: what the ray hooks of the three files share ----------------------------------------------------------------------------------
+// a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared; with DebugAlpha the alpha tables, queues and counters
+// of the committed scene and the frame settings a ray hook runs with, with DebugAlphaGlass those of the glass pass and of transparent shadows as well
+enum DebugFeatures { DebugPlain = 0, DebugAlpha = 1, DebugAlphaGlass = 2 };
+int debug_prepare(ptc_ctx* c, uint32_t n, const char* who, DebugFeatures features = DebugPlain);
+// n explicit rays into a queue of lane 0: A = (o, d.x), B = (d.y, d.z, ..), C; fill(i, B, C) supplies B.zw and C of ray i (C starts as zero)
+typedef std::function<void(uint32_t i, float4& B, float4& C)> RayFill;
+inline RayQ as_rays(const ShadowQ& s) { return RayQ{s.A, s.B, s.C}; }      // the shadow queue's three arrays, for the two helpers that take either queue
+int stage_rays(ptc_ctx* c, const RayQ& rq, uint32_t n, const float* origins, const float* dirs, const RayFill& fill);
+// lane 0's first n hit records as (t, prim or -1, uv)
+int read_hits(ptc_ctx* c, uint32_t n, float* out_t, int32_t* out_prim, float* out_uv);
+// the records of rq lie at the front of each segment of q (seg_counts: device, per segment) and say which of the n paths they belong to (path_of): sink(path, A, B, C) for
+// each; a count above seg_len or a path id out of range or taken is an error about "<what> records"
+typedef std::function<void(uint32_t path, const float4& A, const float4& B, const float4& C)> RecordSink;
+int scatter_segment_records(ptc_ctx* c, const DevQueues& q, const uint32_t* seg_counts, const RayQ& rq, uint32_t (*path_of)(const float4& B, const float4& C), uint32_t n,
+                            const char* who, const char* what, const RecordSink& sink);
 
 // ---- ptc_api_image.cpp ---------------------------------------------------------------------------------------------------------------------------
 DevAdaptive dev_adaptive(const ptc_ctx* c);

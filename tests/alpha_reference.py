@@ -2,7 +2,8 @@
 
 Three parts:
   accept / transmit / tables     pt_alpha_accept, pt_alpha_transmit and the tables the commit builds (bit table per primitive, (mode, cutoff) per material), float32
-  resolve_closest / resolve_any  the rounds of k_alpha_filter in float32, bit for bit: the candidate hits come from a `trace(o, d)` callable (the library's own
+  resolve_closest / resolve_any  the rounds of k_alpha_filter_closest and of alpha's shadow walk (k_glass_filter_shadow of csrc/pt_glass_shadow.hip without a glass table) in
+                                 float32, bit for bit: the candidate hits come from a `trace(o, d)` callable (the library's own
                                  ptc_debug_trace_closest), the decision, the onward origin o' and t_base are restated here
   walk_closest                   the INDEPENDENT reference: a float64 search of all triangles per ray, sorted by (t, primitive id), walked with the same decision
                                  rule; it also says which rays float32 and float64 need not agree about (`undecided`)."""
