@@ -22,9 +22,10 @@ inline uint32_t pt_ad_blocks(uint32_t n) { return (n + PTC_AD_BLOCK - 1u) / PTC_
 
 // active list := the owned list, slot[j] = j
 void pt_launch_ad_init(hipStream_t, uint32_t n_owned, const uint32_t* owned, uint32_t* pix, uint32_t* slot);
-// k_accumulate's three additions per sample on accum[slot[j]], then m1, m2 and count; lpath[s * n_active + j] is sample s of active entry j.  With ad.cov4 set
-// the six product sums follow (a second instantiation: a frame without them runs the kernel it always ran)
-void pt_launch_ad_accumulate(hipStream_t, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive&, uint32_t n_samples);
+// k_accumulate's three additions per sample on accum[slot[j]], then m1, m2 and count; sample s of active entry j is lpath[pt_path_id(path_order, j, s, n_active,
+// n_samples)] (pt_device.h): s * n_active + j in a sample-major batch, j * n_samples + s in a pixel-major one, whose rows a wave transposes through LDS.  With
+// ad.cov4 set the six product sums follow (further instantiations: a sample-major frame without them runs the kernel it always ran)
+void pt_launch_ad_accumulate(hipStream_t, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive&, uint32_t n_samples, int path_order);
 // flags[pixel] = e > threshold for every active entry, n = the samples every active pixel has received
 void pt_launch_ad_error(hipStream_t, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, const DevAdaptive&, uint32_t n, float threshold);
 // the keep rule (a flagged pixel within `radius`, inside the image and the tile) + the stable compaction of (pix, slot) into (pix_out, slot_out); the new length goes to ad.n_out

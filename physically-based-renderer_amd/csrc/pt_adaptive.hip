@@ -15,6 +15,7 @@
 // Arithmetic: IEEE binary32 in the order written (the Makefile's -ffp-contract=off and correctly rounded division and square root): tests/adaptive_reference.py
 // performs the same operations in numpy and the sample counts are compared exactly.
 #include "pt_adaptive.h"
+#include "pt_device.h"
 
 #define AD_SCAN_BLOCK 1024
 
@@ -27,27 +28,54 @@ __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_init(uint32_t n_owned, cons
   pix[j] = owned[j]; slot[j] = j;
 }
 
+// one sample's additions to an entry's sums, in the order every form of k_ad_accumulate performs them
 template <bool COV>
+__device__ __forceinline__ void ad_add(const float4 L, float4& a, float2& m, float4& q4, float2& q2) {
+  a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z;
+  const float l = ad_lum(L.x, L.y, L.z);
+  m.x = m.x + l; m.y = m.y + l * l;
+  if (COV) {
+    q4.x = q4.x + L.x * L.x; q4.y = q4.y + L.y * L.y; q4.z = q4.z + L.z * L.z; q4.w = q4.w + L.x * L.y;
+    q2.x = q2.x + L.x * L.z; q2.y = q2.y + L.y * L.z;
+  }
+}
+
+// PIXEL_MAJOR: the batch numbers its paths entry by entry (PT_ORDER_PIXEL); a wave then owns PT_ACC_ROWS entries (AD_PM_ENTRIES a block) and takes their rows of
+// lpath through LDS a 1-KiB run per row at a time, as k_accumulate_pixel_major does (pt_device.h, pt_lpath_tile_*); the sums and their order are the same.
+// The loop bounds are the block's.
+#define AD_PM_ENTRIES (PTC_AD_BLOCK / 64u * PT_ACC_ROWS)
+template <bool COV, bool PIXEL_MAJOR>
 __global__ __launch_bounds__(PTC_AD_BLOCK) void k_ad_accumulate(uint32_t n_active, const uint32_t* __restrict__ slot, const float4* __restrict__ lpath, float4* __restrict__ accum,
                                                                 float2* __restrict__ moments, uint32_t* __restrict__ count, float4* __restrict__ cov4, float2* __restrict__ cov2,
                                                                 uint32_t n_samples) {
-  const uint32_t j = blockIdx.x * PTC_AD_BLOCK + threadIdx.x;
-  if (j >= n_active) return;
-  const uint32_t o = slot[j];
-  float4 a = accum[o];
-  float2 m = moments[o];
+  __shared__ float4 s_tile[PIXEL_MAJOR ? PTC_AD_BLOCK / 64 : 1][PIXEL_MAJOR ? PT_ACC_TILE_UNITS : 1];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t j0 = PIXEL_MAJOR ? blockIdx.x * AD_PM_ENTRIES + wv * PT_ACC_ROWS : blockIdx.x * PTC_AD_BLOCK + wv * 64u, j = j0 + lane;
+  const bool live = j < n_active && (!PIXEL_MAJOR || lane < PT_ACC_ROWS);      // this lane owns entry j
+  if (!PIXEL_MAJOR && !live) return;
+  const uint32_t o = live ? slot[j] : 0u;
+  float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float2 m = make_float2(0.0f, 0.0f);
   float4 q4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float2 q2 = make_float2(0.0f, 0.0f);
-  if (COV) { q4 = cov4[o]; q2 = cov2[o]; }
-  for (uint32_t s = 0; s < n_samples; ++s) {
-    const float4 L = lpath[(size_t)s * n_active + j];
-    a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z;
-    const float l = ad_lum(L.x, L.y, L.z);
-    m.x = m.x + l; m.y = m.y + l * l;
-    if (COV) {
-      q4.x = q4.x + L.x * L.x; q4.y = q4.y + L.y * L.y; q4.z = q4.z + L.z * L.z; q4.w = q4.w + L.x * L.y;
-      q2.x = q2.x + L.x * L.z; q2.y = q2.y + L.y * L.z;
+  if (live) { a = accum[o]; m = moments[o]; }
+  if (COV && live) { q4 = cov4[o]; q2 = cov2[o]; }
+  if (PIXEL_MAJOR) {
+    float4* tile = s_tile[wv];
+    const uint32_t first = pt_path_id(PT_ORDER_PIXEL, j, 0u, n_active, n_samples), n_tiles = pt_lpath_tiles(n_samples);
+    PtAccRegs v = pt_lpath_tile_fetch(lpath, j0, n_active, n_samples, 0u, lane);
+    for (uint32_t k = 0; k < n_tiles; ++k) {
+      pt_lpath_tile_put(tile, lane, v);
+      __syncthreads();
+      if (k + 1u < n_tiles) v = pt_lpath_tile_fetch(lpath, j0, n_active, n_samples, k + 1u, lane);
+      if (live)
+        for (uint32_t t = 0; t < PT_ACC_RUN; ++t)
+          if (pt_lpath_tile_has(first, n_samples, k, t)) ad_add<COV>(tile[lane * PT_ACC_ROW + t], a, m, q4, q2);
+      __syncthreads();
     }
+    if (!live) return;
+  } else {
+    for (uint32_t s = 0; s < n_samples; ++s) ad_add<COV>(lpath[pt_path_id(PT_ORDER_SAMPLE, j, s, n_active, n_samples)], a, m, q4, q2);
   }
   accum[o] = a; moments[o] = m; count[o] += n_samples;
   if (COV) { cov4[o] = q4; cov2[o] = q2; }
@@ -195,10 +223,16 @@ void pt_launch_ad_init(hipStream_t s, uint32_t n_owned, const uint32_t* owned, u
   if (!n_owned) return;
   hipLaunchKernelGGL(k_ad_init, dim3(pt_ad_blocks(n_owned)), dim3(PTC_AD_BLOCK), 0, s, n_owned, owned, pix, slot);
 }
-void pt_launch_ad_accumulate(hipStream_t s, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive& ad, uint32_t n_samples) {
+template <bool PIXEL_MAJOR>
+static void launch_ad_accumulate(hipStream_t s, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive& ad, uint32_t n_samples) {
   if (!n_active) return;
-  if (ad.cov4) hipLaunchKernelGGL(k_ad_accumulate<true>, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
-  else hipLaunchKernelGGL(k_ad_accumulate<false>, dim3(pt_ad_blocks(n_active)), dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
+  const dim3 grid(PIXEL_MAJOR ? (n_active + AD_PM_ENTRIES - 1u) / AD_PM_ENTRIES : pt_ad_blocks(n_active));
+  if (ad.cov4) hipLaunchKernelGGL((k_ad_accumulate<true, PIXEL_MAJOR>), grid, dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
+  else hipLaunchKernelGGL((k_ad_accumulate<false, PIXEL_MAJOR>), grid, dim3(PTC_AD_BLOCK), 0, s, n_active, slot, lpath, accum, ad.moments, ad.count, ad.cov4, ad.cov2, n_samples);
+}
+void pt_launch_ad_accumulate(hipStream_t s, uint32_t n_active, const uint32_t* slot, const float4* lpath, float4* accum, const DevAdaptive& ad, uint32_t n_samples, int path_order) {
+  if (path_order == PT_ORDER_PIXEL) launch_ad_accumulate<true>(s, n_active, slot, lpath, accum, ad, n_samples);
+  else launch_ad_accumulate<false>(s, n_active, slot, lpath, accum, ad, n_samples);
 }
 void pt_launch_ad_error(hipStream_t s, uint32_t n_active, const uint32_t* pix, const uint32_t* slot, const DevAdaptive& ad, uint32_t n, float threshold) {
   if (!n_active) return;

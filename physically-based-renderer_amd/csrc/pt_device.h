@@ -67,6 +67,18 @@ PT_HD float rng_f(uint32_t key, uint32_t bounce, uint32_t dim) {
   return (float)(x >> 8) * (1.0f / 16777216.0f);
 }
 
+// ---- path numbering of a batch: (entry j of the owned / active list, sample s of the batch) <-> path id p = queue slot at bounce 0 ----
+// A batch of n entries x S samples numbers its paths in one of two orders (DevFrame::path_order):
+//   sample-major  p = s n + j   a wave of bounce 0 carries one sample of 64 neighbouring entries
+//   pixel-major   p = j S + s   a wave of bounce 0 carries 64 samples of one entry (S >= 64), and an entry's samples lie side by side in lpath
+// n S fits 32 bits (ptc_frame_begin).  Every kernel and host evaluation that forms or inverts a path id calls these two.
+enum { PT_ORDER_SAMPLE = 0, PT_ORDER_PIXEL = 1 };
+PT_HD uint32_t pt_path_id(int order, uint32_t j, uint32_t s, uint32_t n, uint32_t S) { return order == PT_ORDER_PIXEL ? j * S + s : s * n + j; }
+PT_HD void pt_path_entry(int order, uint32_t p, uint32_t n, uint32_t S, uint32_t& j, uint32_t& s) {
+  if (order == PT_ORDER_PIXEL) { j = p / S; s = p % S; }
+  else { j = p % n; s = p / n; }
+}
+
 // ---- sin(2πu), cos(2πu), u ∈ [0,1): quadrant + octant reduction, Taylor on [0, π/4] ------------
 PT_HD void sincos2pi(float u, float& so, float& co) {
   float x4 = u * 4.0f;
@@ -259,4 +271,45 @@ PT_DEV bool tri_test(const ray_t& r, v3 v0, v3 e1, v3 e2, float& t, float& u, fl
 PT_DEV uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 PT_DEV uint32_t mbcnt64(uint64_t m) {   // number of set bits of m below this lane
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// ---- a pixel-major batch's path radiance, transposed: what k_accumulate and k_ad_accumulate read under PT_ORDER_PIXEL -------------
+// An entry's S samples are S x 16 contiguous bytes of lpath (its row), and the rows of consecutive entries lie back to back.  One lane per entry
+// reading its own row would touch 64 lines per load, so a wave owns PT_ACC_ROWS entries [j0, j0 + PT_ACC_ROWS) and takes their rows through LDS a
+// tile at a time: tile k holds, of every row, the k-th run of PT_ACC_RUN units (1 KiB) counted from the 128-byte line the row starts in, so that
+// load i of a tile is ONE coalesced 1-KiB read of row i on line boundaries, lane = unit inside the run.  Lane r < PT_ACC_ROWS then reads row r's
+// units from LDS in address = sample order, skipping the units of the first and the last run that belong to the neighbouring rows
+// (pt_lpath_tile_has).  The other lanes only load: the kernels move 16 bytes per three additions and are bound by memory, so the shape is chosen for
+// the memory side -- whole 1-KiB runs on line boundaries, PT_ACC_ROWS of them in flight per lane and no branch around a load (times under both orders:
+// profiles/path_order.txt).  A row of the LDS tile is padded to PT_ACC_RUN + 1 units: rows 260 words apart fall on distinct banks
+// for 16-byte reads.  Units outside [j S, (j + 1) S) and entries >= n are never loaded: nothing outside the batch's n S units is touched.
+#define PT_ACC_ROWS 8u                         // entries of a wave = loads per lane and tile (PtAccRegs has one member each)
+#define PT_ACC_RUN 64u                         // units (float4) of a row per tile: one load instruction of the wave
+#define PT_ACC_LINE 8u                         // units of a 128-byte line: a row's runs start on a line
+#define PT_ACC_ROW (PT_ACC_RUN + 1u)
+#define PT_ACC_TILE_UNITS (PT_ACC_ROWS * PT_ACC_ROW)   // float4 units of one wave's tile
+PT_DEV uint32_t pt_lpath_tiles(uint32_t S) { return (S + PT_ACC_LINE - 1u + PT_ACC_RUN - 1u) / PT_ACC_RUN; }   // runs a row of S units can touch
+// the unit of lpath that is unit t of run k of the row starting at unit `first`, and whether it lies inside the row (its sample index is then unit - first)
+PT_DEV uint32_t pt_lpath_tile_unit(uint32_t first, uint32_t k, uint32_t t) { return (first & ~(PT_ACC_LINE - 1u)) + k * PT_ACC_RUN + t; }
+PT_DEV bool pt_lpath_tile_has(uint32_t first, uint32_t S, uint32_t k, uint32_t t) {
+  const uint32_t e = pt_lpath_tile_unit(first, k, t);
+  return e >= first && e - first < S;
+}
+struct PtAccRegs { float4 r0, r1, r2, r3, r4, r5, r6, r7; };      // a lane's PT_ACC_ROWS loads of a tile; named members, not an array: the array went to scratch
+PT_DEV float4 pt_lpath_tile_load(const float4* __restrict__ lpath, uint32_t j, uint32_t n, uint32_t S, uint32_t k, uint32_t lane) {
+  const uint32_t first = pt_path_id(PT_ORDER_PIXEL, j, 0u, n, S);
+  const bool inside = j < n && pt_lpath_tile_has(first, S, k, lane);
+  return lpath[inside ? pt_lpath_tile_unit(first, k, lane) : 0u];      // no branch around a load: the loads of a tile issue back to back.  Unit 0 exists (n S > 0) and nobody reads what a lane outside its row fetched
+}
+PT_DEV PtAccRegs pt_lpath_tile_fetch(const float4* __restrict__ lpath, uint32_t j0, uint32_t n, uint32_t S, uint32_t k, uint32_t lane) {
+  PtAccRegs v;
+  v.r0 = pt_lpath_tile_load(lpath, j0, n, S, k, lane); v.r1 = pt_lpath_tile_load(lpath, j0 + 1u, n, S, k, lane);
+  v.r2 = pt_lpath_tile_load(lpath, j0 + 2u, n, S, k, lane); v.r3 = pt_lpath_tile_load(lpath, j0 + 3u, n, S, k, lane);
+  v.r4 = pt_lpath_tile_load(lpath, j0 + 4u, n, S, k, lane); v.r5 = pt_lpath_tile_load(lpath, j0 + 5u, n, S, k, lane);
+  v.r6 = pt_lpath_tile_load(lpath, j0 + 6u, n, S, k, lane); v.r7 = pt_lpath_tile_load(lpath, j0 + 7u, n, S, k, lane);
+  return v;
+}
+PT_DEV void pt_lpath_tile_put(float4* tile, uint32_t lane, const PtAccRegs& v) {      // row i of the tile <- load i; units outside their row hold values nobody reads
+  tile[lane] = v.r0; tile[PT_ACC_ROW + lane] = v.r1; tile[2u * PT_ACC_ROW + lane] = v.r2; tile[3u * PT_ACC_ROW + lane] = v.r3;
+  tile[4u * PT_ACC_ROW + lane] = v.r4; tile[5u * PT_ACC_ROW + lane] = v.r5; tile[6u * PT_ACC_ROW + lane] = v.r6; tile[7u * PT_ACC_ROW + lane] = v.r7;
 }

@@ -133,14 +133,15 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan(DevQueues q, int qi_next, u
 }
 
 // =================================================================================================
-// P1 ray generation.  path id p → owned pixel j = p % n_owned, sample = first + p / n_owned.
+// P1 ray generation.  path id p → (owned pixel j, sample first + s) by the frame's path order (pt_device.h: pt_path_entry).
 // ndc = 2·((px+ξ)/W, (py+η)/H) − 1, y-down, no flip (PbrRenderSystem.cpp:425-430);
 // view-space dir (ndc.x·aspect·tan(fov/2), ndc.y·tan(fov/2), −1) taken to world by the lookAtRH basis.
 template <bool RASTER>
-__global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_paths) {
+__global__ __launch_bounds__(256) void k_raygen(DevCamera cam, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_samples) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-  if (p >= n_paths) return;
-  const uint32_t j = p % fr.n_owned, sl = p / fr.n_owned;
+  if (p >= fr.n_owned * n_samples) return;
+  uint32_t j, sl;
+  pt_path_entry(fr.path_order, p, fr.n_owned, n_samples, j, sl);
   const uint32_t pixel = fr.owned[j];
   const uint32_t px = pixel % (uint32_t)fr.w, py = pixel / (uint32_t)fr.w;
   const uint32_t sample = first_sample + sl;
@@ -1083,10 +1084,40 @@ __global__ __launch_bounds__(256) void k_accumulate(DevFrame fr, const float4* l
   if (j >= fr.n_owned) return;
   float4 a = accum[j];
   for (uint32_t s = 0; s < n_samples; ++s) {
-    const float4 L = lpath[(size_t)s * fr.n_owned + j];
+    const float4 L = lpath[pt_path_id(PT_ORDER_SAMPLE, j, s, fr.n_owned, n_samples)];
     a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z;
   }
   accum[j] = a;
+}
+// The same sums of a pixel-major batch: a wave owns PT_ACC_ROWS pixels and takes their rows of lpath through LDS a 1-KiB run per row at a time (pt_device.h,
+// pt_lpath_tile_*), the next tile's loads in flight while lane r < PT_ACC_ROWS adds the current one's units of row r in sample order.  The loop bounds are the block's.
+#define ACC_PM_ENTRIES (256u / 64u * PT_ACC_ROWS)      // pixels of a block
+__global__ __launch_bounds__(256) void k_accumulate_pixel_major(DevFrame fr, const float4* lpath, float4* accum, uint32_t n_samples) {
+  __shared__ float4 s_tile[256 / 64][PT_ACC_TILE_UNITS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t j0 = blockIdx.x * ACC_PM_ENTRIES + wv * PT_ACC_ROWS, j = j0 + lane;
+  const bool owner = lane < PT_ACC_ROWS && j < fr.n_owned;
+  float4* tile = s_tile[wv];
+  float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (owner) a = accum[j];
+  const uint32_t first = pt_path_id(PT_ORDER_PIXEL, j, 0u, fr.n_owned, n_samples), n_tiles = pt_lpath_tiles(n_samples);
+  PtAccRegs v = pt_lpath_tile_fetch(lpath, j0, fr.n_owned, n_samples, 0u, lane);
+  for (uint32_t k = 0; k < n_tiles; ++k) {
+    pt_lpath_tile_put(tile, lane, v);
+    __syncthreads();
+    if (k + 1u < n_tiles) v = pt_lpath_tile_fetch(lpath, j0, fr.n_owned, n_samples, k + 1u, lane);
+    if (owner) {
+      const float4* row = tile + lane * PT_ACC_ROW;
+      if (pt_lpath_tile_has(first, n_samples, k, 0u) && pt_lpath_tile_has(first, n_samples, k, PT_ACC_RUN - 1u)) {      // a run inside the row: all of it
+        for (uint32_t t = 0; t < PT_ACC_RUN; ++t) { const float4 L = row[t]; a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z; }
+      } else {
+        for (uint32_t t = 0; t < PT_ACC_RUN; ++t)
+          if (pt_lpath_tile_has(first, n_samples, k, t)) { const float4 L = row[t]; a.x = a.x + L.x; a.y = a.y + L.y; a.z = a.z + L.z; }
+      }
+    }
+    __syncthreads();
+  }
+  if (owner) accum[j] = a;
 }
 
 // sum / spp → full-frame RGBA32F, alpha 1 (path) or the shaded alpha (raster-compat)
@@ -1228,8 +1259,8 @@ int pt_shade_block_threads() { return SHADE_BLOCK; }
 void pt_launch_raygen(hipStream_t s, const DevCamera& cam, const DevFrame& fr, const DevQueues& q, uint32_t first_sample, uint32_t n_samples, bool raster) {
   const uint32_t n_paths = fr.n_owned * n_samples;
   const dim3 grid((n_paths + 255u) / 256u);
-  if (raster) hipLaunchKernelGGL(k_raygen<true>, grid, dim3(256), 0, s, cam, fr, q, first_sample, n_paths);
-  else hipLaunchKernelGGL(k_raygen<false>, grid, dim3(256), 0, s, cam, fr, q, first_sample, n_paths);
+  if (raster) hipLaunchKernelGGL(k_raygen<true>, grid, dim3(256), 0, s, cam, fr, q, first_sample, n_samples);
+  else hipLaunchKernelGGL(k_raygen<false>, grid, dim3(256), 0, s, cam, fr, q, first_sample, n_samples);
 }
 
 void pt_launch_trace_closest(hipStream_t s, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, int qi, bool cull) {
@@ -1257,7 +1288,9 @@ bool pt_shade_tables_fit(const DevScene& sc) {
   return sc.n_lights <= SHADE_LDS_LIGHTS && sc.n_mats <= SHADE_LDS_MATS && (!sc.env_ok || sc.env_h <= (int)SHADE_LDS_ENV_ROWS);
 }
 void pt_launch_accumulate(hipStream_t s, const DevFrame& fr, const DevQueues& q, float4* accum, uint32_t n_samples) {
-  hipLaunchKernelGGL(k_accumulate, dim3((fr.n_owned + 255u) / 256u), dim3(256), 0, s, fr, (const float4*)q.lpath, accum, n_samples);
+  if (fr.path_order == PT_ORDER_PIXEL)
+    hipLaunchKernelGGL(k_accumulate_pixel_major, dim3((fr.n_owned + ACC_PM_ENTRIES - 1u) / ACC_PM_ENTRIES), dim3(256), 0, s, fr, (const float4*)q.lpath, accum, n_samples);
+  else hipLaunchKernelGGL(k_accumulate, dim3((fr.n_owned + 255u) / 256u), dim3(256), 0, s, fr, (const float4*)q.lpath, accum, n_samples);
 }
 void pt_launch_shade_raster(hipStream_t s, const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevQueues& q, float4* accum, bool gbuffer16) {
   if (gbuffer16) hipLaunchKernelGGL(k_shade_raster<true>, dim3((fr.n_owned + 255u) / 256u), dim3(256), 0, s, sc, cam, fr, q, accum);

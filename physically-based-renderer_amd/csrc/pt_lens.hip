@@ -1,6 +1,7 @@
 // pt_lens.hip — ray generation through a thin lens (see pt_lens.h; the definition of every value is pt_lens_ray there, which the host evaluation calls too).
 //
-//   k_raygen_lens   one thread per path, k_raygen's path id -> (owned pixel j = p % n_owned, sample = first + p / n_owned) mapping, so adaptive frames (the
+//   k_raygen_lens   one thread per path, k_raygen's path id -> (owned pixel j, sample first + s) mapping in the frame's path order (pt_device.h: pt_path_entry;
+//                   sample-major j = p % n_owned, s = p / n_owned, pixel-major j = p / n_samples, s = p % n_samples), so adaptive frames (the
 //                   active-pixel list in DevFrame::owned), tile shares and sample ranges need nothing of their own here.  One 4-byte load of the pixel index,
 //                   four coalesced 16-byte stores: the ray record A = (o, d.x), B = (d.y, d.z, 1, 1), C = (1, 0, p, key) and the cleared path radiance.
 // A streaming kernel like k_raygen: 64 B written per path, every byte once.  Beside k_raygen's work it hashes two more RNG dimensions and evaluates a square
@@ -8,10 +9,11 @@
 #include "pt_lens.h"
 
 namespace {
-__global__ __launch_bounds__(256) void k_raygen_lens(DevCamera cam, ptc_lens_params lens, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_paths) {
+__global__ __launch_bounds__(256) void k_raygen_lens(DevCamera cam, ptc_lens_params lens, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_samples) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-  if (p >= n_paths) return;
-  const uint32_t j = p % fr.n_owned, sl = p / fr.n_owned;
+  if (p >= fr.n_owned * n_samples) return;
+  uint32_t j, sl;
+  pt_path_entry(fr.path_order, p, fr.n_owned, n_samples, j, sl);
   const uint32_t pixel = fr.owned[j];
   float o[3], d[3];
   uint32_t key;
@@ -29,5 +31,5 @@ void pt_launch_raygen_lens(hipStream_t s, const DevCamera& cam, const ptc_lens_p
   const uint32_t n_paths = fr.n_owned * n_samples;
   if (!n_paths) return;
   const dim3 grid((n_paths + 255u) / 256u);
-  hipLaunchKernelGGL(k_raygen_lens, grid, dim3(256), 0, s, cam, lens, fr, q, first_sample, n_paths);
+  hipLaunchKernelGGL(k_raygen_lens, grid, dim3(256), 0, s, cam, lens, fr, q, first_sample, n_samples);
 }

@@ -127,7 +127,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       const int prev = (int)((c->batches_issued - 1) % (uint64_t)c->n_lanes);
       if (prev != l) HIP_TRY(c, hipStreamWaitEvent(st, c->lanes[(size_t)prev].acc_done, 0));
     }
-    if (c->adaptive.on) pt_launch_ad_accumulate(st, c->fr.n_owned, c->adaptive.slot[c->adaptive.cur].p, q.lpath, c->accum.p, dev_adaptive(c), n_samples);
+    if (c->adaptive.on) pt_launch_ad_accumulate(st, c->fr.n_owned, c->adaptive.slot[c->adaptive.cur].p, q.lpath, c->accum.p, dev_adaptive(c), n_samples, c->fr.path_order);
     else pt_launch_accumulate(st, c->fr, q, c->accum.p, n_samples);
     // a probe frame: the SH projection of the same path radiance, inside the same sample-order bracket (it has its own sums, so the two do not order each other)
     if (c->probes.on) pt_launch_accumulate_sh(st, c->fr.n_owned, c->probes.base, c->fr.seed_hash, q.lpath, c->probes.acc.p, first_sample, n_samples);
@@ -360,6 +360,9 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->rad_w = w; c->rad_h = h;
   c->fr.w = w; c->fr.h = h; c->fr.max_bounces = max_bounces; c->fr.n_owned = (uint32_t)n_owned; c->fr.owned = c->owned.p;
   c->fr.seed_hash = seed_hash(seed);
+  // the path integrator's camera frames number a batch's paths in the context's order; raster frames (one sample) and probe frames (k_raygen_probe and
+  // k_accumulate_sh, whose order ptc_debug_probe_project publishes) stay sample-major
+  c->fr.path_order = is_raster(integrator) || probe_pos ? PT_ORDER_SAMPLE : c->path_order;
   c->spp_total = is_raster(integrator) ? 1 : spp_total;
   c->integrator = integrator; c->samples_done = 0; c->sample_base = 0; c->resolve_divisor = 0;
   // samples of one full batch: as many as fit max_batch_paths split over the lanes.  The queues themselves are sized by the
@@ -415,9 +418,9 @@ const char* ptc_launch_policy(const ptc_ctx* c) {
   static const ptc_ctx defaults;                     // member initialisers = the built-in defaults (ptc_create then reads the environment)
   const ptc_ctx& x = c ? *c : defaults;
   char buf[512];
-  std::snprintf(buf, sizeof buf, " | stack_lds_max=6 segments_per_cu_default=64 nodelets=%u lanes=%d batch_paths=%zu trace_overlap=%d(<=2^26 paths) rays_per_lane=%d shade_sort=%d refit=%s bvh=%s",
+  std::snprintf(buf, sizeof buf, " | stack_lds_max=6 segments_per_cu_default=64 nodelets=%u lanes=%d batch_paths=%zu trace_overlap=%d(<=2^26 paths) rays_per_lane=%d shade_sort=%d refit=%s bvh=%s path_order=%s",
                 x.toplet_budget, x.n_lanes, x.max_batch_paths, x.trace_overlap, x.trace_rays_per_lane, x.cfg.shade_sort, x.refit_on_device ? "device" : "host",
-                x.bvh_builder == PTC_BVH_LBVH ? "lbvh" : "sah");
+                x.bvh_builder == PTC_BVH_LBVH ? "lbvh" : "sah", x.path_order == PT_ORDER_PIXEL ? "pixel" : "sample");
   out = std::string(pt_kernel_policy()) + buf;
   if (c && c->committed && c->device >= 0) {
     std::snprintf(buf, sizeof buf, " | trace_blocks_per_cu=%d stack_lds=%d lds_units=%u ovf_depth=%u shade_segments=%d shade_tables_lds=%d", c->cfg.trace_blocks_per_cu, c->cfg.stack_lds,
@@ -468,6 +471,7 @@ ptc_ctx* ptc_create(int device_id) {
   if (const char* s = std::getenv("PTC_BATCH_PATHS")) { size_t v = std::strtoull(s, nullptr, 10); if (v >= 1024) c->max_batch_paths = v; }
   if (const char* s = std::getenv("PTC_TIMING")) { const int v = std::atoi(s); c->timing = v < 0 ? 0 : (v > 2 ? 2 : v); }
   if (const char* s = std::getenv("PTC_LANES")) { int v = std::atoi(s); if (v >= 1 && v <= 8) c->n_lanes = v; }
+  if (const char* s = std::getenv("PTC_PATH_ORDER")) { if (std::strcmp(s, "sample") == 0) c->path_order = PT_ORDER_SAMPLE; else if (std::strcmp(s, "pixel") == 0) c->path_order = PT_ORDER_PIXEL; }
   c->lanes.resize((size_t)c->n_lanes);
   bool ok = true;
   for (auto& ln : c->lanes) {

@@ -297,8 +297,9 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     DevCamera cam;
     ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, cam);
     for (uint32_t p = 0; p < n; ++p) {
-      uint32_t key;
-      pt_lens_ray(cam, c->lens, w, h, seed_hash, pixels[p % n_pixels], first_sample + p / n_pixels, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);
+      uint32_t key, j, s;
+      pt_path_entry(PT_ORDER_SAMPLE, p, n_pixels, n_samples, j, s);      // the output's order, whatever order the context's frames use
+      pt_lens_ray(cam, c->lens, w, h, seed_hash, pixels[j], first_sample + s, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);
     }
     return PTC_OK;
   }
@@ -311,6 +312,7 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
   if (e == hipSuccess) {
     DevFrame fr{};
     fr.w = w; fr.h = h; fr.seed_hash = seed_hash; fr.max_bounces = 0; fr.n_owned = n_pixels; fr.owned = list.p;
+    fr.path_order = c->path_order;      // the kernels run as a camera frame runs them; the read-back below re-maps the slots to the output's sample-major order
     const DevQueues q = batch_queues(c, 0, n);
     if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(ln.stream, c->cam, c->lens, fr, q, first_sample, n_samples);      // run_batch's choice
     else pt_launch_raygen(ln.stream, c->cam, fr, q, first_sample, n_samples, false);
@@ -321,9 +323,12 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
   if (e == hipSuccess) e = hipMemcpy(B.data(), ln.q.ray[0].B, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
   list.release();      // the pixel list lives for this call only
   if (e != hipSuccess) return fail(c, PTC_E_DEVICE, std::string("debug_camera_rays: ") + hipGetErrorString(e));
-  for (size_t p = 0; p < n; ++p) {
-    origins[p * 3] = A[p].x; origins[p * 3 + 1] = A[p].y; origins[p * 3 + 2] = A[p].z;
-    dirs[p * 3] = A[p].w; dirs[p * 3 + 1] = B[p].x; dirs[p * 3 + 2] = B[p].y;
+  for (uint32_t p = 0; p < n; ++p) {      // output ray p = sample p / n_pixels of pixels[p % n_pixels]; the device wrote it to the slot of the context's path order
+    uint32_t j, s;
+    pt_path_entry(PT_ORDER_SAMPLE, p, n_pixels, n_samples, j, s);
+    const size_t d = pt_path_id(c->path_order, j, s, n_pixels, n_samples), o = (size_t)p * 3;
+    origins[o] = A[d].x; origins[o + 1] = A[d].y; origins[o + 2] = A[d].z;
+    dirs[o] = A[d].w; dirs[o + 1] = B[d].x; dirs[o + 2] = B[d].y;
   }
   return PTC_OK;
 }

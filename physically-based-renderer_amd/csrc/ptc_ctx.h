@@ -352,6 +352,9 @@ struct ptc_ctx {
   int n_lanes = 1;                  // PTC_LANES: >1 runs successive batches on separate streams.  With the round-2 kernels one lane
                                     // is 3.7 % faster than two (co-scheduled launches slow each other down by more than the tails they fill)
   uint64_t batches_issued = 0;
+  int path_order = PT_ORDER_PIXEL;  // PTC_PATH_ORDER=sample|pixel: how a camera frame of the path integrator numbers a batch's paths (pt_device.h, pt_path_id).  Pixel-major:
+                                    // a wave of bounce 0 carries 64 samples of one pixel instead of one sample of 64 pixels; the image is the same bit for bit
+                                    // (profiles/path_order.txt has the A/B that chose the default)
   // frame
   bool in_frame = false;
   DevFrame fr{};

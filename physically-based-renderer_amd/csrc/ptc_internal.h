@@ -52,6 +52,7 @@ struct DevFrame {
   int max_bounces;
   uint32_t n_owned;            // pixels this context owns
   const uint32_t* owned;       // their indices y*w+x, tile-Morton order
+  int path_order;              // PT_ORDER_*: how a batch numbers its paths (pt_device.h, pt_path_id); 0 = sample-major, what raster, probe and debug frames use
 };
 
 // ---- wavefront queues (SoA of 16-byte lanes) ------------------------------------------------------
