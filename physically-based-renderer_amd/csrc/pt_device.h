@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pt_exact.h"
 
 #define PT_DEV __device__ __forceinline__
 #define PT_HD __host__ __device__ __forceinline__
@@ -44,8 +45,9 @@ PT_HD float dot3(v3 a, v3 b) { return pt_fma(a.z, b.z, pt_fma(a.y, b.y, a.x * b.
 PT_HD v3 cross3(v3 a, v3 b) {
   return V3(pt_fma(a.y, b.z, -(a.z * b.y)), pt_fma(a.z, b.x, -(a.x * b.z)), pt_fma(a.x, b.y, -(a.y * b.x)));
 }
-PT_HD float pt_sqrt(float x) { return __builtin_sqrtf(x); }
-PT_HD v3 normalize3(v3 a) { float inv = 1.0f / pt_sqrt(dot3(a, a)); return a * inv; }
+// pt_sqrt, pt_rnorm: pt_exact.h.  inv = 1 / sqrt(dot) in two roundings, as ever; on the device ONE test of the squared length guards both (a squared length
+// inside [2^-32, 2^32) has its root and the root's reciprocal inside [2^-16, 2^16]), anything else — a zero vector among them — takes the compiler's expansions
+PT_HD v3 normalize3(v3 a) { float inv = pt_rnorm(dot3(a, a)); return a * inv; }
 PT_HD v3 vfma(v3 a, float s, v3 b) { return V3(pt_fma(a.x, s, b.x), pt_fma(a.y, s, b.y), pt_fma(a.z, s, b.z)); }
 PT_HD float fmin2(float a, float b) { return a < b ? a : b; }
 PT_HD float fmax2(float a, float b) { return a > b ? a : b; }
@@ -208,7 +210,7 @@ PT_DEV bool bsdf_sample(const bsdf_t& b, v3 wo, float ps, float ul, float s1, fl
     v3 vh = normalize3(V3(a * wo.x, a * wo.y, wo.z));
     float lensq = pt_fma(vh.y, vh.y, vh.x * vh.x);
     v3 t1 = V3(1.0f, 0.0f, 0.0f);
-    if (lensq > 0.0f) { float il = 1.0f / pt_sqrt(lensq); t1 = V3(-vh.y * il, vh.x * il, 0.0f); }
+    if (lensq > 0.0f) { float il = pt_rnorm(lensq); t1 = V3(-vh.y * il, vh.x * il, 0.0f); }
     v3 t2 = cross3(vh, t1);
     float p1 = r * cs, p2 = r * sn;
     float s = 0.5f * (1.0f + vh.z);

@@ -1011,8 +1011,8 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
           const v3 dv = y - P;
           const float dist2 = dot3(dv, dv);
           if (dist2 > 0.0f) {
-            const float dist = pt_sqrt(dist2);
-            const v3 wi = dv * (1.0f / dist);
+            float dist;
+            const v3 wi = dv * pt_rnorm(dist2, dist);
             const float cosl = -dot3(V3(l3.x, l3.y, l3.z), wi);
             const v3 wil = V3(dot3(tx, wi), dot3(ty, wi), dot3(ns, wi));
             if (cosl > 0.0f && wil.z > 0.0f && dot3(ng, wi) > 0.0f) {
@@ -1024,8 +1024,8 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
               has_shadow = true;
               // visibility: the segment from the offset origin porg to the sampled point, minus its last 0.1 %
               const v3 sv = y - porg;
-              const float sd = pt_sqrt(dot3(sv, sv));
-              const v3 sdir = sv * (1.0f / sd);
+              float sd;
+              const v3 sdir = sv * pt_rnorm(dot3(sv, sv), sd);
               sA = make_float4(porg.x, porg.y, porg.z, sdir.x);
               sB = make_float4(sdir.y, sdir.z, sd * 0.999f, __uint_as_float(path));
               sC = make_float4(T.x * f.x * l4.x * k, T.y * f.y * l4.y * k, T.z * f.z * l4.z * k, 0.0f);
@@ -1056,7 +1056,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, SHADE_MIN_WAVES) void k_shade(const De
             const float pr = fmin2(fmax2(qq, PT_RR_PMIN), 1.0f);
             const float ur = rng_f(key, rb, 6);
             ok = !(ur >= pr);
-            if (ok) T = V3(T.x / pr, T.y / pr, T.z / pr);
+            if (ok) pt_div3(T.x, T.y, T.z, pr);      // pr lies in [PT_RR_PMIN, 1] by the clamp above, inside pt_div3's [2^-5, 1]: one reciprocal, no test of the divisor's range
           }
         }
         if (ok) {

@@ -1,5 +1,6 @@
 // ptc_api_debug.cpp — the ptc_debug_* hooks: what the tests use to look inside the library (single rays, tables, the host build, the host halves of the device paths).
 #include "ptc_ctx.h"
+#include "pt_exact_debug.h"
 
 using namespace ptc_detail;
 
@@ -660,6 +661,34 @@ int ptc_debug_meter(const ptc_display_params* params, const float* rgba, uint64_
   if (M_out) *M_out = M;
   if (rejected_out) *rejected_out = rejected;
   if (hist_out) std::memcpy(hist_out, hist.data(), PT_DISPLAY_BINS * sizeof(uint32_t));
+  return PTC_OK;
+}
+
+// The fast paths of csrc/pt_exact.h against the compiler's / and sqrtf, on the device (include/ptc_exact_debug.h).  Needs a device, no scene; touches nothing
+// of the context but its error string.
+int ptc_debug_exact_arith(ptc_ctx* c, int op, const float* a, const float* b, uint64_t n, uint32_t first, int cross, uint64_t* out) {
+  if (!c) return PTC_E_ARG;
+  if (!out || op < PTC_EXACT_RCP || op > PTC_EXACT_DIV3 || n == 0 || n > (1ull << 32) || (b && !a) || (a && n > (1ull << 28)) ||
+      (cross && (!a || !b || n > (1ull << 16) || (op != PTC_EXACT_DIV && op != PTC_EXACT_DIV3))))
+    return fail(c, PTC_E_ARG, "debug_exact_arith: bad argument");
+  { int rd = need_device(c); if (rd) return rd; }
+  DevBuf<float> da, db;
+  DevBuf<unsigned long long> dout;
+  const size_t words = 1 + 4 * PTC_EXACT_OFFENDERS;
+  { int rc = ensure_buf(c, dout, words); if (rc) return rc; }
+  HIP_TRY(c, hipMemset(dout.p, 0, words * sizeof(unsigned long long)));
+  if (a) {
+    { int rc = ensure_buf(c, da, (size_t)n); if (rc) return rc; }
+    HIP_TRY(c, hipMemcpy(da.p, a, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  if (b) {
+    { int rc = ensure_buf(c, db, (size_t)n); if (rc) return rc; }
+    HIP_TRY(c, hipMemcpy(db.p, b, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  pt_launch_exact_arith(nullptr, op, da.p, db.p, n, first, cross, dout.p);
+  HIP_TRY(c, hipGetLastError());
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
+  HIP_TRY(c, hipMemcpy(out, dout.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return PTC_OK;
 }
 }  // extern "C"

@@ -403,11 +403,21 @@ def _shade_debug_prototypes():
     }
 
 
+def _exact_debug_prototypes():
+    """name -> (restype, argtypes) of the function include/ptc_exact_debug.h declares; exported under ptcx_ like ptc_shade_debug.h's."""
+    i, u32, u64 = C.c_int, C.c_uint32, C.c_uint64
+    vp, fp, u64p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)
+    return {
+        "ptc_debug_exact_arith": (i, [vp, i, fp, fp, u64, u32, i, u64p]),
+    }
+
+
 _PROTOTYPES = _prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
 _GLASS_PROTOTYPES = _glass_prototypes()
 _GLASS_SHADOW_PROTOTYPES = _glass_shadow_prototypes()
 _SHADE_DEBUG_PROTOTYPES = _shade_debug_prototypes()
+_EXACT_DEBUG_PROTOTYPES = _exact_debug_prototypes()
 # every function include/ptc_glass.h declares, by the header's names
 GLASS_SYMBOLS = list(_GLASS_PROTOTYPES)
 # every function include/ptc_alpha.h declares, by the header's names
@@ -430,7 +440,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -1398,6 +1408,23 @@ class PathTracer:
         if env.size:
             self._ck(self._L.ptc_debug_get_env_tables(self._h, None, None, None, _ptr(env), _ptr(marg), _ptr(cond)))
         return env, marg, cond, bool(ok.value)
+
+    def exact_arith(self, op, a=None, b=None, n=None, first=0, cross=False):
+        """ptc_debug_exact_arith: fast path `op` (0 rcp, 1 sqrt, 2 rnorm, 3 div, 4 div3) of csrc/pt_exact.h against the compiler's / and sqrtf on the device.
+        Explicit operands a (and b), or with a = None the n bit patterns from `first` on (hashed pairs for div and div3); cross: every a[i] with every b[j].
+        Returns (mismatches, offenders): offenders (k, 4) uint32 = bits of a, b, the fast path's result and the reference's, k <= 16."""
+        out = np.zeros(1 + 4 * 16, np.uint64)
+        if a is None:
+            ap = bp = None
+        else:
+            a = np.ascontiguousarray(a, np.float32)
+            ap, n = _ptr(a), a.shape[0]
+            b = None if b is None else np.ascontiguousarray(b, np.float32)
+            assert b is None or b.shape == a.shape
+            bp = None if b is None else _ptr(b)
+        self._ck(self._L.ptc_debug_exact_arith(self._h, int(op), ap, bp, int(n), int(first) & 0xffffffff, int(bool(cross)), _ptr(out)))
+        k = int(min(out[0], 16))
+        return int(out[0]), out[1:1 + 4 * k].reshape(k, 4).astype(np.uint32)
 
     def raw_counters(self):
         buf = (C.c_uint64 * 32)()

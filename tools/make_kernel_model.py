@@ -40,7 +40,7 @@ model = {"git_commit": commit + ("+uncommitted csrc changes" if dirty else ""), 
          # what the launches of the profiled run looked like (ptc_launch_policy): grid sizing, LDS split, batch size, overlap mode ... — bench.py reports
          # model_stale when the library it runs launches differently, tests/test_profiles.py when the library's DEFAULTS have moved since
          "launch_policy": bench["launch_policy"], "launch_policy_defaults": bench["launch_policy_defaults"],
-         "source": f"{prof}: rocprofv3 --pmc passes of `bench.py --steps {K} --warmup {W}` ({bench['config']['workload']})",
+         "source": f"{os.path.basename(os.path.normpath(prof))}: rocprofv3 --pmc passes of `bench.py --steps {K} --warmup {W}` ({bench['config']['workload']})",
          "fetch_note": "fetch bytes = FETCH_SIZE KiB x 1024 x 2 (gfx950 tallies 128-B requests at 64 B; calibrated for streaming reads, uncalibrated for 16-B gathers: true value between 0.5x and 1x)"}
 for kname, u in units.items():
     key = [k for k in pmc if kname in k and "<true" not in k]
