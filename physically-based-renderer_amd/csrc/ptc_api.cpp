@@ -23,6 +23,7 @@ constexpr size_t kQueueBytesPerPath = 176;   // ensure_lane_queues: 2 x 48 (ray 
 constexpr size_t kAlphaBytesPerPath = 65;    // ensure_alpha_queues: 48 (continuation) + 16 (its hit record) + 1 (k_trace_any's flag)
 constexpr size_t kGlassBytesPerPath = 64;    // ensure_glass_queues: 48 (continuation) + 16 (its hit record)
 constexpr size_t kGlassFlagBytesPerPath = 1; // ... + 1 (k_trace_any's flag) in a frame with transparent shadows
+constexpr size_t kMediumBytesPerPath = 144;  // ensure_medium_queues: 3 x 48 (parked continuation, emitter / environment shadow and punctual shadow records)
 constexpr size_t kMaxSpans = 1024;   // timing spans (event pairs) kept at most; see run_batch
 
 // the timing spans that have completed (all_done: every one) go into the statistics, their events back to the pool
@@ -40,6 +41,7 @@ void collect_times(ptc_ctx* c, bool all_done) {
       else if (s.kind == 4) c->stats.seconds_reduce += sec;
       else if (s.kind == 5) c->alpha.seconds += sec;
       else if (s.kind == 6) c->glass.seconds += sec;
+      else if (s.kind == 7) c->medium.seconds += sec;
       else c->stats.seconds_render += sec;
     }
     c->free_events.push_back(s.a); c->free_events.push_back(s.b);
@@ -86,13 +88,17 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     const bool glass = glass_on(c);
     // transparent shadows (pt_glass_shadow.hip): every shadow queue to an RGB transmittance per record, one walk for alpha surfaces and thin panes
     const bool glass_shadows = glass_shadows_on(c);
+    // the participating medium (pt_medium.hip): k_medium_decide between closest(b) and shade(b), k_medium_append behind shade(b) and behind the punctual pass, each before
+    // the scan that follows — on this stream alone, so any(b) does not run beside closest(b + 1) while a medium is on either.  Off: none of these branches, nothing allocated
+    const bool medium = medium_on(c);
+    const DevMediumQ mq = medium ? dev_medium_q(c, l) : DevMediumQ{};
     auto trace_shadows = [&]() {
       ScopedSpan t(c, st, 1);
       if (glass_shadows || alpha) resolve_shadow(c, l, st, cfg, sc, q, glass_shadows, nullptr, nullptr);
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
-    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass;
+    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass && !medium;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
       while (ln.ev_scan.size() < need) { hipEvent_t e = nullptr; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ln.ev_scan.push_back(e); }
@@ -105,10 +111,12 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       { ScopedSpan t(c, st, 0, per_kernel); pt_launch_trace_closest(st, cfg, sc, q, b & 1, false); c->stats.launches_trace_closest++; }
       if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, PT_ALPHA_FORM_CLOSEST, nullptr);
       if (glass) glass_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, nullptr);
+      if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_decide(st, sc, q, mq, c->medium.frame, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev); }
       // k_shade(b) overwrites the shadow queue any(b - 1) reads and adds to the path radiance it adds to
       if (overlap && b > 0) HIP_TRY(c, hipStreamWaitEvent(st, ln.ev_any[(size_t)b - 1], 0));
       { ScopedSpan t(c, st, 2, per_kernel); pt_launch_shade(st, cfg, ln.d_scene, c->fr, q, b & 1, (uint32_t)b); }
       if (b == c->fr.max_bounces) break;                         // the last bounce's shade produces no rays
+      if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, false); }
       pt_launch_scan(st, cfg, q, (b + 1) & 1);
       if (overlap) {      // any(b) on the second stream, beside closest(b + 1)
         HIP_TRY(c, hipEventRecord(ln.ev_scan[(size_t)b], st));
@@ -118,6 +126,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       } else if (shadows) trace_shadows();
       if (punctual) {     // behind emission (k_shade) and the emitter / environment sample (any): the punctual sample, through the same shadow queue
         { ScopedSpan t(c, st, 2); pt_launch_shade_punctual(st, sc, q, b & 1, (uint32_t)b, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev); }
+        if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, true); }
         pt_launch_scan(st, cfg, q, (b + 1) & 1);      // the same ray prefix again, the new shadow counts, the work counters zeroed: nothing runs beside it
         trace_shadows();
       }
@@ -155,6 +164,7 @@ int issue(ptc_ctx* c, uint32_t k) {
   if (rc) return rc;
   if (alpha_on(c) && (rc = ensure_alpha_queues(c))) return rc;
   if (glass_on(c) && (rc = ensure_glass_queues(c))) return rc;
+  if (medium_on(c) && (rc = ensure_medium_queues(c))) return rc;
   if ((rc = run_batch(c, (int)(c->batches_issued % (uint64_t)c->n_lanes), c->sample_base + c->samples_done, k))) return rc;
   c->samples_done += k;
   c->stats.paths += cap;
@@ -299,6 +309,7 @@ void Lane::teardown() {
   free_all(allocs);
   free_all(alpha.allocs);
   free_all(glass.allocs);
+  free_all(medium.allocs);
   if (q.cnt) (void)hipFree(q.cnt);
   if (q.stats) (void)hipFree(q.stats);
   if (q.seg_ray[0]) (void)hipFree(q.seg_ray[0]);
@@ -314,6 +325,7 @@ void Lane::teardown() {
 // pixels" are the probes in their own order, the positions go to the device, the 27 w sums are cleared and the probe flag is set
 int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const float* probe_pos,
                 uint32_t probe_base) {
+  if (c) { if (const char* why = medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }      // before the device: a description-only context can tell
   { int rd = need_device(c); if (rd) return rd; }
   c->in_frame = false; c->pending = 0; c->adaptive.on = false; c->adaptive.cov_on = false; c->adaptive.cov_resolved = false; c->adaptive.sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
   const std::string who = probe_pos ? "probes_begin" : "frame_begin";      // the entry the caller used, for ptc_last_error
@@ -330,6 +342,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   if (c->glass.counters.p) HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
   if (c->glass.shadow_counters.p) HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
   c->glass.frame_shadows = c->glass.shadows;      // before the queues are sized: a frame with transparent shadows keeps a flag byte per path
+  if ((rc = medium_frame_begin(c, integrator == PTC_INTEGRATOR_PATH))) return rc;      // likewise: a frame with a medium keeps a medium queue
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
   if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
@@ -376,9 +389,11 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
     // no need to ask the driver how much memory is free (a call of 0.1-0.2 ms, every frame of a viewer's loop)
   } else {   // no more than 60 % of the device memory that is free now (plus what the lanes' queues already hold) goes into queues
     size_t free_b = 0, total_b = 0, held = 0;
-    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0) + (glass_shadows_on(c) ? kGlassFlagBytesPerPath : 0);
+    const size_t per_path = kQueueBytesPerPath + (alpha_on(c) ? kAlphaBytesPerPath : 0) + (glass_on(c) ? kGlassBytesPerPath : 0) + (glass_shadows_on(c) ? kGlassFlagBytesPerPath : 0) +
+                            (medium_on(c) ? kMediumBytesPerPath : 0);
     for (const auto& ln : c->lanes)
-      held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.alpha.q.cap * kAlphaBytesPerPath + (size_t)ln.glass.q.cap * (kGlassBytesPerPath + (ln.glass.flags ? kGlassFlagBytesPerPath : 0));
+      held += (size_t)ln.q.cap * kQueueBytesPerPath + (size_t)ln.alpha.q.cap * kAlphaBytesPerPath + (size_t)ln.glass.q.cap * (kGlassBytesPerPath + (ln.glass.flags ? kGlassFlagBytesPerPath : 0)) +
+              (size_t)ln.medium.cap * kMediumBytesPerPath;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
       const size_t fit = (size_t)(0.6 * (double)(free_b + held)) / per_path;
       if (fit < batch_paths) batch_paths = fit;
@@ -397,6 +412,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->stats.bvh_sa_cost = keep.bvh_sa_cost; c->stats.bvh_sa_cost_built = keep.bvh_sa_cost_built; c->stats.seconds_rebuild = keep.seconds_rebuild;
   c->alpha.seconds = 0.0; c->alpha.frame_layers = c->alpha.max_layers;
   c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions;
+  c->medium.seconds = 0.0;
   c->in_frame = true;
   c->probes.on = probe_pos != nullptr; c->probes.base = probe_base;
   return PTC_OK;

@@ -187,7 +187,7 @@ int ptc_group_render(ptc_group* g, int w, int h, int spp, uint64_t seed, int max
   const int n = (int)g->ctx.size();
   auto bail = [&](int i, int rc) { g->err = std::string("device ") + std::to_string(i) + ": " + ptc_last_error(g->ctx[(size_t)i]); return rc; };
   // every device traces all samples of its tiles; all of it is queued before anything is waited for
-  for (int i = 1; i < n; ++i) take_lights(g->ctx[(size_t)i], g->ctx[0]);
+  for (int i = 1; i < n; ++i) { take_lights(g->ctx[(size_t)i], g->ctx[0]); take_medium(g->ctx[(size_t)i], g->ctx[0]); }
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_begin(g->ctx[(size_t)i], w, h, spp, seed, max_bounces, integrator, i, n); if (rc) return bail(i, rc); }
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_add_samples(g->ctx[(size_t)i], spp); if (rc) return bail(i, rc); }
   for (int i = 0; i < n; ++i) { int rc = ptc_frame_resolve(g->ctx[(size_t)i]); if (rc) return bail(i, rc); }

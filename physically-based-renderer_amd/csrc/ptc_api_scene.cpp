@@ -557,6 +557,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   c->alpha.mode = c0->alpha.mode; c->alpha.cutoff = c0->alpha.cutoff;      // every member builds context 0's alpha tables
   c->glass.params = c0->glass.params; c->glass.shadows = c0->glass.shadows;      // and its glass tables, with its choice of transparent shadows
   take_lights(c, c0);
+  take_medium(c, c0);
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
 }
 
@@ -685,7 +686,8 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->lights.dirty = c->lights.dirty || !c->lights.list.empty(); c->lights.list.clear();
   c->alpha.mode.clear(); c->alpha.cutoff.clear(); c->alpha.dirty = true; c->alpha.n_prims = 0;      // every material of the next description starts OPAQUE; max_layers stays
   c->glass.params.clear(); c->glass.dirty = true; c->glass.n_prims = 0; c->glass.n_thin = 0;      // and without transmission; max_interactions and shadows stay
-  drop_history(c);         // the history is about the primitives of the scene that goes, and reads its shading records in place
+  c->medium.set = false; c->medium.params = ptc_medium_params{};      // the medium goes as the lights do
+  drop_history(c);        // the history is about the primitives of the scene that goes, and reads its shading records in place
   if (c->display.state.p) HIP_TRY(c, hipMemset(c->display.state.p, 0, sizeof(pt_display_state)));      // the adaptation state goes with the scene; the display parameters stay
   release_scene(c);
   return PTC_OK;

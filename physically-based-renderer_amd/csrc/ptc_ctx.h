@@ -23,6 +23,7 @@
 #include "pt_glass_shadow.h"
 #include "pt_display.h"
 #include "pt_probes.h"
+#include "pt_medium.h"
 
 #include <rccl/rccl.h>
 
@@ -54,7 +55,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg);
     if (r_ != ncclSuccess) return fail((c), PTC_E_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
   } while (0)
 
-struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution (alpha's own shadow walk included), 6 a glass resolution (the shadow walk of a frame with transparent shadows included)
+struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution (alpha's own shadow walk included), 6 a glass resolution (the shadow walk of a frame with transparent shadows included), 7 the medium pass's kernels
 
 // An array in HBM and its owner: freed when the owner goes (with the context: after ptc_destroy made the device current), or early by release()
 template <class T> struct DevBuf {
@@ -86,6 +87,8 @@ struct StageTimer {
 // A lane's side queue as a DevQueues view — continuation records in ray[0], their hit records, header words, segment counts and statistics of its own — and the
 // flags k_trace_any writes for the shadow queue when a shadow walk goes through it
 struct SideQueue { DevQueues q{}; uint8_t* flags = nullptr; std::vector<void*> allocs; };
+// A lane's medium queue (pt_medium.h): the parked records of the scatter events and their per-segment counts, for `cap` paths
+struct MediumQueue { DevMediumQ q{}; uint32_t cap = 0; std::vector<void*> allocs; };
 
 // One lane: a stream with its own wavefront queues.  cnt/stats are allocated once; the large arrays grow on demand.
 struct Lane {
@@ -102,6 +105,8 @@ struct Lane {
   // alpha coverage (pt_alpha.h) and dielectric transmission (pt_glass.h): a side queue each, allocated only while the committed scene has such a material
   // (ensure_alpha_queues, ensure_glass_queues).  glass.flags only once a frame began with ptc_set_glass_shadows on (pt_glass_shadow.h)
   SideQueue alpha, glass;
+  // the participating medium (pt_medium.h): allocated only once a frame runs with a medium on (ensure_medium_queues)
+  MediumQueue medium;
   void free_overflow_slabs() { for (uint2* p : {stack_ovf, stack_ovf2}) if (p) (void)hipFree(p); stack_ovf = stack_ovf2 = nullptr; }
   void teardown();                  // ptc_destroy: everything but the overflow slabs (release_scene's), the streams after what ran on them
 };
@@ -207,6 +212,17 @@ struct Glass {
   int frame_shadows = 0;            // what the frame in progress (or the last ray hook) was begun with
   uint32_t n_thin = 0;              // primitives of the committed scene whose material is transmissive AND thin-walled, as of the last upload; 0: no shadow walk
   DevBuf<unsigned long long> shadow_counters;
+};
+
+// the participating medium (pt_medium.h): `params` is what the calls recorded (set: there is one), with the lifetime of the punctual lights; `frame` is what the
+// frame in progress (or the last ptc_debug_medium_step) was begun with, frame_on whether its batches launch the pass.  Nothing is allocated before that
+struct Medium {
+  bool set = false;
+  ptc_medium_params params{};
+  bool frame_on = false;
+  pt_medium frame{};
+  DevBuf<unsigned long long> counters;
+  double seconds = 0.0;             // the frame's medium kernels (spans of kind 7)
 };
 
 // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
@@ -328,6 +344,7 @@ struct ptc_ctx {
   ptc_detail::Lights lights;
   ptc_detail::Alpha alpha;
   ptc_detail::Glass glass;
+  ptc_detail::Medium medium;
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -579,6 +596,16 @@ inline bool glass_shadows_on(const ptc_ctx* c) { return c->glass.frame_shadows !
 // frame with transparent shadows — the glass queue, alpha and glass tables, a span of kind 6; else alpha's own walk — the alpha queue, no glass table, kind 5.
 // tr3_out / layers_out (or null): the debug hooks' outputs instead of the additions to lpath
 void resolve_shadow(ptc_ctx* c, int l, hipStream_t st, const LaunchCfg& cfg, const DevScene& sc, const DevQueues& q, bool through_glass, float* tr3_out, uint32_t* layers_out);
+
+// ---- ptc_api_medium.cpp: the participating medium (pt_medium.h) ----------------------------------------------------------------------------------------
+inline bool medium_on(const ptc_ctx* c) { return c->medium.frame_on; }
+inline void take_medium(ptc_ctx* c, const ptc_ctx* c0) { c->medium.set = c0->medium.set; c->medium.params = c0->medium.params; }
+// the frame about to begin would run the medium pass over a scene whose committed primitives have alpha coverage or transmission: the message, else nullptr.
+// Decided from the description and the host build, so a description-only context can tell
+const char* medium_conflict(const ptc_ctx* c, int integrator);
+int medium_frame_begin(ptc_ctx* c, bool on);           // the frame's copy of the parameters, the counters allocated and cleared when it is on (every lane idle)
+int ensure_medium_queues(ptc_ctx* c);                  // every lane: a medium queue as large as its queues (grow only; waits for the work in flight first)
+inline DevMediumQ dev_medium_q(const ptc_ctx* c, int l) { DevMediumQ m = c->lanes[(size_t)l].medium.q; m.counters = c->medium.counters.p; return m; }
 
 // ---- ptc_api_debug.cpp: what the ray hooks of the three files share ----------------------------------------------------------------------------------
 // a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared; with DebugAlpha the alpha tables, queues and counters

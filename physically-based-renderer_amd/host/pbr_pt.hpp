@@ -143,6 +143,11 @@ public:
   auto setGlassShadows(bool on) -> void { ck(ptc_set_glass_shadows(_ctx, on ? 1 : 0)); }
   auto glassShadows() const -> bool { int on = 0; ptc_get_glass_shadows(_ctx, &on); return on != 0; }
   auto glassShadowStats() -> ptc_glass_shadow_stats { ptc_glass_shadow_stats s{}; ck(ptc_get_glass_shadow_stats(_ctx, &s)); return s; }
+  // the participating medium (include/ptc_medium.h): a homogeneous fog box.  Recorded like a light — no commit, dropped by beginScene — and used by the
+  // next frame; sigma_t 0 or clearMedium(): off
+  auto setMedium(const ptc_medium_params& m) -> void { ck(ptc_set_medium(_ctx, &m)); }
+  auto clearMedium() -> void { ck(ptc_clear_medium(_ctx)); }
+  auto mediumStats() -> ptc_medium_stats { ptc_medium_stats s{}; ck(ptc_get_medium_stats(_ctx, &s)); return s; }
   // the view depth of what pixel (x, y)'s centre sees, 0 on a miss: needs frameGuides() of the current frame
   auto focusDistanceAtPixel(int x, int y) -> float { float d = 0.0f; ck(ptc_focus_distance_at_pixel(_ctx, x, y, &d)); return d; }
   // PTC_BVH_SAH (default) or PTC_BVH_LBVH, for the scene being described

@@ -5,6 +5,7 @@
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
 //              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission] [--glass-shadows]
+//              [--fog x,y,z:x,y,z:sigma_t[:albedo[:g]] | --fog scene:sigma_t[:albedo[:g]]]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
 //              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
 // --probe-grid NX,NY,NZ / --probes FILE with --probes-out sh.pfm: bake light probes instead of an image (ptc_render_probes) — the centres of the
@@ -24,6 +25,10 @@
 // ptc_set_material_transmission), path integrator only; --no-transmission renders them as the opaque surfaces they were before.
 // --glass-shadows: shadow rays pass thin-walled transmissive panes with their expected transmittance (ptc_set_glass_shadows): punctual lights, emitters
 // and the environment light what lies behind a window directly.  Off by default; with --gpus device D's setting goes to every member.
+// --fog LO:HI:SIGMA_T[:ALBEDO[:G]]: a homogeneous fog box from corner LO to corner HI (ptc_set_medium) with extinction SIGMA_T per world unit, grey
+// single-scattering albedo (default 0.9) and Henyey-Greenstein anisotropy G (default 0); --fog scene:SIGMA_T[:ALBEDO[:G]] takes the bounding box of the committed
+// scene, its faces moved out by a thousandth of its diagonal, and prints it; path integrator only, and not with alpha or transmissive materials
+// (--no-alpha, --no-transmission).  With --gpus device D's medium goes to every member.
 // --aperture R: the thin lens (ptc_set_camera_lens) with aperture radius R in world units — depth of field, path integrator only.  --blades N: a regular polygon
 // of 3..16 sides instead of the disk, --aperture-rotation T: its rotation in turns, [0, 1).  --focus D: the view depth of the plane of focus (default 1);
 // --focus-pixel X,Y: focus on what that pixel's centre sees — the guides are traced once before the render and ptc_focus_distance_at_pixel is taken (a miss is
@@ -220,6 +225,8 @@ int main(int argc, char** argv) {
   bool noAlpha = false;                      // --no-alpha: ignore the asset's alpha modes
   bool noTransmission = false;               // --no-transmission: ignore the asset's transmission extensions
   bool glassShadows = false;                 // --glass-shadows: transparent shadows through thin panes
+  std::string fogSpec;                       // --fog: the medium
+  ptc_medium_params fog{};
   ptc_display_params disp = pbr::PathTraceRenderSystem::displayDefaults();      // --exposure / --auto-exposure / --key / --tonemap / --srgb
   bool useDisplay = false, haveKey = false;
   double exposureEv = 0.0;
@@ -243,6 +250,7 @@ int main(int argc, char** argv) {
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
     else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true; else if (a == "--glass-shadows") glassShadows = true;
+    else if (a == "--fog") fogSpec = next();
     else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
     else if (a == "--key") { disp.key = (float)std::atof(next()); haveKey = true; } else if (a == "--srgb") { disp.oetf = PTC_OETF_SRGB; useDisplay = true; }
     else if (a == "--tonemap") {
@@ -311,9 +319,36 @@ int main(int argc, char** argv) {
     if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
     if (noGltfLights && gltf.empty()) throw std::runtime_error("--no-gltf-lights drops the lights of a --gltf scene");
     if (glassShadows && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--glass-shadows applies to the path integrator (not with --raster / --raster16)");
+    bool fogSceneBox = false;                  // --fog scene:...: the box is the committed scene's bounding box
+    if (!fogSpec.empty()) {
+      float al = 0.9f, g = 0.0f;
+      int got;
+      if (fogSpec.compare(0, 6, "scene:") == 0) { fogSceneBox = true; got = 6 + std::sscanf(fogSpec.c_str() + 6, "%f:%f:%f", &fog.sigma_t, &al, &g); }
+      else got = std::sscanf(fogSpec.c_str(), "%f,%f,%f:%f,%f,%f:%f:%f:%f", &fog.box_lo[0], &fog.box_lo[1], &fog.box_lo[2], &fog.box_hi[0], &fog.box_hi[1], &fog.box_hi[2], &fog.sigma_t, &al, &g);
+      if (got < 7) throw std::runtime_error("--fog x,y,z:x,y,z:sigma_t[:albedo[:g]] or --fog scene:sigma_t[:albedo[:g]]");
+      if (integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--fog applies to the path integrator (not with --raster / --raster16)");
+      fog.albedo[0] = fog.albedo[1] = fog.albedo[2] = al; fog.g = g;
+    }
+    // --fog scene:...: the bounding box of the committed scene's vertices (--probe-grid's box), each face moved out by a thousandth of the diagonal so that the
+    // scene's outer surfaces lie inside the fog and a flat scene still has a box
+    auto sceneFogBox = [&](pbr::PathTraceRenderSystem& rs) {
+      std::uint32_t nv = 0, nt = 0;
+      if (ptc_debug_get_flat_scene(rs.handle(), &nv, &nt, nullptr, nullptr, nullptr) < 0 || nv == 0) throw std::runtime_error("--fog scene: the scene has no geometry");
+      std::vector<ptc_vertex> verts(nv);
+      if (ptc_debug_get_flat_scene(rs.handle(), &nv, &nt, verts.data(), nullptr, nullptr) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+      float lo[3] = {verts[0].position[0], verts[0].position[1], verts[0].position[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+      for (const ptc_vertex& v : verts)
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], v.position[k]); hi[k] = std::max(hi[k], v.position[k]); }
+      const float pad = 1e-3f * std::max(1e-3f, std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2])));
+      for (int k = 0; k < 3; ++k) { fog.box_lo[k] = lo[k] - pad; fog.box_hi[k] = hi[k] + pad; }
+      std::printf("{\"fog_box\": [[%.9g, %.9g, %.9g], [%.9g, %.9g, %.9g]], \"sigma_t\": %.9g}\n", (double)fog.box_lo[0], (double)fog.box_lo[1], (double)fog.box_lo[2], (double)fog.box_hi[0],
+                  (double)fog.box_hi[1], (double)fog.box_hi[2], (double)fog.sigma_t);
+    };
     // after the scene: the punctual lights (they need no commit) — the asset's own unless dropped, then the command line's — and how shadow rays see thin glass
     auto applyLights = [&](pbr::PathTraceRenderSystem& rs) {
       rs.setGlassShadows(glassShadows);
+      if (fogSceneBox) sceneFogBox(rs);
+      if (!fogSpec.empty()) rs.setMedium(fog);
       if (noGltfLights && ptc_clear_lights(rs.handle()) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
       for (const ptc_light_params& l : lights)
         if (ptc_add_light(rs.handle(), &l) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));

@@ -152,6 +152,21 @@ class PtcGlassShadowHit(_Struct):
     _fields_ = [("ng", C.c_float * 3), ("ns", C.c_float * 3), ("d", C.c_float * 3), ("base", C.c_float * 3), ("metallic", C.c_float), ("W", C.c_float * 3), ("F_t", C.c_float)]
 
 
+class PtcMediumParams(_Struct):
+    _fields_ = [("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3), ("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
+    _unknown_ = "unknown medium field {}"
+
+
+class PtcMediumStats(_Struct):
+    _fields_ = [("crossed", C.c_uint64), ("scattered", C.c_uint64), ("attenuated", C.c_uint64), ("seconds_medium", C.c_double)]
+
+
+class PtcMediumSample(_Struct):
+    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("t_end", C.c_float), ("u0", C.c_float), ("u1", C.c_float), ("u2", C.c_float),
+                ("so", C.c_float * 3), ("sd", C.c_float * 3), ("stmax", C.c_float), ("crosses", C.c_int), ("t0", C.c_float), ("t1", C.c_float), ("s", C.c_float),
+                ("scatters", C.c_int), ("P", C.c_float * 3), ("cos_theta", C.c_float), ("wi", C.c_float * 3), ("pdf", C.c_float), ("transmittance", C.c_float)]
+
+
 class PtcDenoiseParams(_Struct):
     _fields_ = [("iterations", C.c_int), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float), ("demodulate", C.c_int)]
     _defaults_ = "ptc_denoise_default_params"
@@ -412,7 +427,24 @@ def _exact_debug_prototypes():
     }
 
 
+def _medium_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_medium.h declares, in the header's order; exported under ptcx_ like ptc_glass.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, fp, u8p, u32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    mp = C.POINTER(PtcMediumParams)
+    return {
+        "ptc_set_medium": (i, [vp, mp]),
+        "ptc_get_medium": (i, [vp, mp]),
+        "ptc_clear_medium": (i, [vp]),
+        "ptc_get_medium_stats": (i, [vp, C.POINTER(PtcMediumStats)]),
+        "ptc_debug_medium_sample": (i, [mp, C.POINTER(PtcMediumSample)]),
+        "ptc_debug_medium_step": (i, [vp, fp, fp, fp, fp, u32p, u32, u32, u32, fp, u8p, fp, u8p, fp, u8p, fp]),
+        "ptc_debug_medium_env": (i, [vp, fp, fp, fp, u32, fp, fp, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
+_MEDIUM_PROTOTYPES = _medium_prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
 _GLASS_PROTOTYPES = _glass_prototypes()
 _GLASS_SHADOW_PROTOTYPES = _glass_shadow_prototypes()
@@ -440,7 +472,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -592,6 +624,22 @@ def glass_shadow_transmit(params, **fields):
     return io.as_dict()
 
 
+def medium_params(box_lo, box_hi, sigma_t, albedo=(1.0, 1.0, 1.0), g=0.0):
+    """A ptc_medium_params: the fog box [box_lo, box_hi], its extinction per world unit, single-scattering albedo (a number or rgb) and HG anisotropy."""
+    a = (albedo,) * 3 if np.isscalar(albedo) else albedo
+    return PtcMediumParams().update(box_lo=box_lo, box_hi=box_hi, sigma_t=sigma_t, albedo=a, g=g)
+
+
+def medium_sample(params, **fields):
+    """ptc_debug_medium_sample: the host's evaluation of csrc/pt_medium.h for one ray (o, d, t_end, u0, u1, u2) and one shadow segment (so, sd, stmax).  Returns
+    the struct as a dict (crosses, t0, t1, s, scatters, P, cos_theta, wi, pdf, transmittance, ..)."""
+    io = PtcMediumSample().update(**fields)
+    rc = load_library().ptc_debug_medium_sample(C.byref(params), C.byref(io))
+    if rc < 0:
+        raise PtcError("medium_sample: bad argument")
+    return io.as_dict()
+
+
 def display_params(**fields):
     """A ptc_display_params: the defaults with `fields` replaced.  `tonemap` takes a name (aces, neutral, reinhard, clamp) or a TONEMAP_* value, `oetf` a name
     (gamma22, srgb) or an OETF_* value."""
@@ -731,6 +779,8 @@ class PathTracer:
         self.set_camera_lens(getattr(c, "aperture_radius", 0.0), getattr(c, "focus_distance", 1.0), getattr(c, "blades", 0), getattr(c, "aperture_rotation", 0.0))
         for l in getattr(desc, "lights", []):
             self.add_light(l)
+        if getattr(desc, "medium", None) is not None:      # a dict of medium_params' arguments
+            self.set_medium(**desc.medium)
         self._ck(L.ptc_scene_commit(h))
         return self
 
@@ -861,6 +911,57 @@ class PathTracer:
         bits, mats = np.zeros((npr.value + 31) // 32, np.uint32), np.zeros((nm.value, 8), np.float32)
         rc = self._ck(self._L.ptc_debug_get_glass_tables(self._h, None, _ptr(bits), None, _ptr(mats)))
         return bits, mats, int(npr.value), bool(rc)
+
+    # ---- a homogeneous participating medium (csrc/pt_medium.h) ------------------------------------------------
+    def set_medium(self, params=None, **fields):
+        """ptc_set_medium: a medium_params(...) or its arguments as keywords (box_lo, box_hi, sigma_t, albedo, g).  Recorded; the next frame uses it."""
+        self._ck(self._L.ptc_set_medium(self._h, C.byref(params if params is not None else medium_params(**fields))))
+        return self
+
+    def get_medium(self):
+        """ptc_get_medium: the parameters as a dict, or None when no medium is set."""
+        p = PtcMediumParams()
+        return p.as_dict() if self._ck(self._L.ptc_get_medium(self._h, C.byref(p))) else None
+
+    def clear_medium(self):
+        self._ck(self._L.ptc_clear_medium(self._h))
+        return self
+
+    def medium_stats(self):
+        return self._get(self._L.ptc_get_medium_stats, PtcMediumStats)
+
+    def medium_step(self, origins, dirs, throughput, prev_pdf, keys, bounce=0, max_bounces=8):
+        """ptc_debug_medium_step: explicit rays (path id = index) through k_trace_closest and the medium pass of one bounce, k_shade between its kernels as in a
+        frame.  A dict of arrays per ray: t, word (the hit record as k_shade saw it), uv, alive, o / d / T (n, 3) and pdf of the continuation, shadow, so / sd
+        (n, 3), tmax, contrib (n, 3) of the emitter-or-environment shadow record, punctual, po / pd, ptmax, pcontrib of the punctual one; rows without a record
+        are zero."""
+        o, op = _f(origins)
+        d, dp = _f(dirs)
+        T, Tp = _f(throughput)
+        pp, ppp = _f(prev_pdf)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = o.shape[0]
+        assert o.shape == d.shape == T.shape == (n, 3) and pp.shape == (n,) and k.shape == (n,)
+        hit = np.zeros((n, 4), np.float32)
+        alive, sh, pl = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        cont, srec, prec = np.zeros((n, 10), np.float32), np.zeros((n, 10), np.float32), np.zeros((n, 10), np.float32)
+        self._ck(self._L.ptc_debug_medium_step(self._h, op, dp, Tp, ppp, _ptr(k), n, int(bounce), int(max_bounces), _ptr(hit), _ptr(alive), _ptr(cont), _ptr(sh),
+                                               _ptr(srec), _ptr(pl), _ptr(prec)))
+        return dict(t=hit[:, 0].copy(), word=hit[:, 1].copy().view(np.int32), uv=hit[:, 2:4].copy(), alive=alive.astype(bool), o=cont[:, 0:3].copy(),
+                    d=cont[:, 3:6].copy(), T=cont[:, 6:9].copy(), pdf=cont[:, 9].copy(), shadow=sh.astype(bool), so=srec[:, 0:3].copy(), sd=srec[:, 3:6].copy(),
+                    tmax=srec[:, 6].copy(), contrib=srec[:, 7:10].copy(), punctual=pl.astype(bool), po=prec[:, 0:3].copy(), pd=prec[:, 3:6].copy(),
+                    ptmax=prec[:, 6].copy(), pcontrib=prec[:, 7:10].copy())
+
+    def medium_env(self, r1, r2, dir_in):
+        """ptc_debug_medium_env: the medium pass's environment sampler and lookup on their own: (direction sampled from (r1, r2) (n, 3), Le (n, 3) and pdf (n,) of dir_in)."""
+        a, ap = _f(r1)
+        b, bp = _f(r2)
+        d, dp = _f(dir_in)
+        n = a.shape[0]
+        assert a.shape == b.shape == (n,) and d.shape == (n, 3)
+        wi, Le, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._ck(self._L.ptc_debug_medium_env(self._h, ap, bp, dp, n, _ptr(wi), _ptr(Le), _ptr(pdf)))
+        return wi, Le, pdf
 
     # ---- transparent shadows through thin glass (csrc/pt_glass_shadow.h) --------------------------------------
     def set_glass_shadows(self, on=True):

@@ -242,6 +242,7 @@ class SceneDesc:
     texture_filter: str = "nearest"  # "nearest" (the reference's default-constructed sampler) or "linear" (bilinear, REPEAT)
     bvh_builder: "str | None" = None  # "sah" (binned surface-area splits), "lbvh" (Morton-code radix tree) or None = the context's default
     lights: List[LightDesc] = dataclasses.field(default_factory=list)  # punctual lights; loading the description adds them (ptc_add_light)
+    medium: Optional[dict] = None  # the fog box: ptc.medium_params' arguments (box_lo, box_hi, sigma_t, albedo, g); loading the description sets it (ptc_set_medium)
 
     @property
     def n_triangles(self) -> int:

@@ -612,7 +612,26 @@ def shade_sky() -> SceneDesc:
     return d
 
 
+def fog_box(sigma_t: float = 0.7, albedo=(0.9, 0.9, 0.9), g: float = 0.0, slit: float = 0.3, emitter: float = 8.0) -> SceneDesc:
+    """A 4 x 4 floor at y = 0, a blocker at y = 1.5 with a slit of width `slit` along z, a small emissive quad under the blocker facing down, and fog between
+    floor and blocker (the medium of the description; sigma_t 0: none).  A sun above the blocker — the tests and tools add one — draws a shaft through the slit.
+    8 triangles."""
+    mats = [Material((0.6, 0.6, 0.6, 1.0), 0.0, 1.0), Material((0.3, 0.3, 0.3, 1.0), 0.0, 1.0), Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (emitter,) * 3)]
+    h, s = 1.5, 0.5 * slit
+    q = [(_quad((-2, 0, 2), (2, 0, 2), (2, 0, -2), (-2, 0, -2)), 0),                    # floor, normal +y
+         (_quad((-2, h, 2), (-s, h, 2), (-s, h, -2), (-2, h, -2)), 1),                  # blocker, x < -s, normal +y
+         (_quad((s, h, 2), (2, h, 2), (2, h, -2), (s, h, -2)), 1),                      # blocker, x > s
+         (_quad((1.0, h - 0.01, -0.3), (1.6, h - 0.01, -0.3), (1.6, h - 0.01, 0.3), (1.0, h - 0.01, 0.3)), 2)]      # emitter, normal -y
+    meshes = [MeshDesc(v, i, m) for (v, i), m in q]
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    cam = CameraDesc((0.0, 0.8, 5.0), (0.0, 0.6, 0.0), math.radians(45.0), 1.0)
+    d = SceneDesc(mats, meshes, inst, cam, "fog_box")
+    if sigma_t > 0.0:
+        d.medium = dict(box_lo=(-2.0, 0.0, -2.0), box_hi=(2.0, h, 2.0), sigma_t=sigma_t, albedo=albedo, g=g)
+    return d
+
+
 def by_name(name: str, **kw) -> SceneDesc:
     return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
             "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_panes": glass_panes, "glass_ball": glass_ball,
-            "shade_lobes": shade_lobes, "shade_textured": shade_textured, "shade_sky": shade_sky}[name](**kw)
+            "shade_lobes": shade_lobes, "shade_textured": shade_textured, "shade_sky": shade_sky, "fog_box": fog_box}[name](**kw)
