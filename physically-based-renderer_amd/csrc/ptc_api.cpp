@@ -10,7 +10,7 @@
 // There is no CPU path in this library: without a usable HIP device ptc_create fails.
 //
 // This file: the context's lifetime, lanes and batches, frames, the radiance read-backs, ptc_get_stats.  The scene calls are in ptc_api_scene.cpp, the image-space
-// features in ptc_api_image.cpp, RCCL and groups in ptc_api_multi.cpp, the ptc_debug_* hooks in ptc_api_debug.cpp; what a context owns is in ptc_ctx.h.
+// features in ptc_api_image.cpp, lightmaps in ptc_api_lightmap.cpp, RCCL and groups in ptc_api_multi.cpp, the ptc_debug_* hooks in ptc_api_debug.cpp; what a context owns is in ptc_ctx.h.
 #include "ptc_ctx.h"
 
 #define PTC_STR2(x) #x
@@ -73,7 +73,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     { ScopedSpan t(c, st, 0); pt_launch_trace_closest(st, cfg, sc, q, 0, true); c->stats.launches_trace_closest++; }
     pt_launch_shade_raster(st, sc, c->cam, c->fr, q, c->accum.p, c->integrator == PTC_INTEGRATOR_RASTER_GBUFFER16);
   } else {
-    if (c->probes.on) pt_launch_raygen_probe(st, c->probes.pos.p, c->fr.n_owned, c->probes.base, c->fr.seed_hash, q, first_sample, n_samples);      // a probe frame (pt_probes.hip) has no camera and no lens
+    if (c->lightmap.on) pt_launch_raygen_texel(st, c->lightmap.texels.p, c->fr.n_owned, c->lightmap.base, c->fr.seed_hash, q, first_sample, n_samples);      // a lightmap frame (pt_lightmap.hip): oriented rays from the texels
+    else if (c->probes.on) pt_launch_raygen_probe(st, c->probes.pos.p, c->fr.n_owned, c->probes.base, c->fr.seed_hash, q, first_sample, n_samples);      // a probe frame (pt_probes.hip) has no camera and no lens
     else if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(st, c->cam, c->lens, c->fr, q, first_sample, n_samples);      // the thin lens (pt_lens.hip); the raster integrators above ignore it
     else pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
     const bool shadows = sc.n_lights > 0 || sc.env_ok;
@@ -111,6 +112,8 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       { ScopedSpan t(c, st, 0, per_kernel); pt_launch_trace_closest(st, cfg, sc, q, b & 1, false); c->stats.launches_trace_closest++; }
       if (alpha) alpha_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, PT_ALPHA_FORM_CLOSEST, nullptr);
       if (glass) glass_resolve_closest(c, l, st, cfg, sc, q, b & 1, (uint32_t)b, nullptr);
+      // a lightmap frame counts the back-face first hits of its texels: the geometric hit of bounce 0, before the medium may turn it into a scatter event
+      if (b == 0 && c->lightmap.on) pt_launch_lm_first_hit(st, sc, q, 0, c->fr.n_owned, c->lightmap.back.p);
       if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_decide(st, sc, q, mq, c->medium.frame, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev); }
       // k_shade(b) overwrites the shadow queue any(b - 1) reads and adds to the path radiance it adds to
       if (overlap && b > 0) HIP_TRY(c, hipStreamWaitEvent(st, ln.ev_any[(size_t)b - 1], 0));
@@ -321,16 +324,18 @@ void Lane::teardown() {
 }
 
 
-// ptc_frame_begin, and ptc_probes_begin's share of it: probe_pos != nullptr begins a probe frame of w probes (h = 1, the path integrator, no tiles) — the "owned
-// pixels" are the probes in their own order, the positions go to the device, the 27 w sums are cleared and the probe flag is set
-int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const float* probe_pos,
-                uint32_t probe_base) {
+// ptc_frame_begin, and ptc_probes_begin's and ptc_lightmap_begin's share of it: `entries` begins a frame over a list of w entries (h = 1, the path integrator, no
+// tiles) — the "owned pixels" are the entries in their own order.  Probes: the positions go to the device, the 27 w sums are cleared and the probe flag is set.
+// A lightmap: the texel list is on the device already (lightmap_begin built it), the back-face counts are cleared and the lightmap flag is set
+int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const FrameEntries* entries) {
+  const float* probe_pos = entries ? entries->probe_pos : nullptr;
+  const bool lightmap = entries && !probe_pos;
   if (c) { if (const char* why = medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }      // before the device: a description-only context can tell
   { int rd = need_device(c); if (rd) return rd; }
   c->in_frame = false; c->pending = 0; c->adaptive.on = false; c->adaptive.cov_on = false; c->adaptive.cov_resolved = false; c->adaptive.sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
-  const std::string who = probe_pos ? "probes_begin" : "frame_begin";      // the entry the caller used, for ptc_last_error
+  const std::string who = entries ? entries->who : "frame_begin";      // the entry the caller used, for ptc_last_error
   if (!c->committed) return fail(c, PTC_E_STATE, who + ": scene not committed");
-  if (w <= 0 || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, who + ": bad size");
+  if ((w <= 0 && !(lightmap && w == 0)) || h <= 0 || spp_total <= 0 || max_bounces < 0 || (uint64_t)w * (uint64_t)h > 0x7fffffffull) return fail(c, PTC_E_ARG, who + ": bad size");
   if (integrator != PTC_INTEGRATOR_PATH && !is_raster(integrator)) return fail(c, PTC_E_ARG, who + ": unknown integrator");
   if (tile_count < 1 || tile_rank < 0 || tile_rank >= tile_count) return fail(c, PTC_E_ARG, who + ": bad tile rank/count");
   { int rs = sync_all_lanes(c); if (rs) return rs; }
@@ -345,15 +350,22 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   if ((rc = medium_frame_begin(c, integrator == PTC_INTEGRATOR_PATH))) return rc;      // likewise: a frame with a medium keeps a medium queue
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at
   // one size keeps the list it has on the device (2 M entries: 10 ms of host time and an 8 MB upload per frame otherwise — tools/viewer_loop.py)
-  if (probe_pos) {      // probe j is "pixel" j: the identity list (the next camera frame makes its own)
+  if (entries) {      // entry j is "pixel" j: the identity list (the next camera frame makes its own)
     std::vector<uint32_t> owned((size_t)w);
-    std::vector<float4> pos((size_t)w);
-    for (int j = 0; j < w; ++j) { owned[(size_t)j] = (uint32_t)j; pos[(size_t)j] = make_float4(probe_pos[j * 3], probe_pos[j * 3 + 1], probe_pos[j * 3 + 2], 0.0f); }
+    for (int j = 0; j < w; ++j) owned[(size_t)j] = (uint32_t)j;
     c->owned_key_valid = false;
-    if ((rc = ensure_buf(c, c->owned, owned.size())) || (rc = ensure_buf(c, c->probes.pos, pos.size())) || (rc = ensure_buf(c, c->probes.acc, (size_t)PT_SH9_FLOATS * (size_t)w))) return rc;
-    HIP_TRY(c, hipMemcpy(c->owned.p, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->probes.pos.p, pos.data(), pos.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemsetAsync(c->probes.acc.p, 0, (size_t)PT_SH9_FLOATS * (size_t)w * sizeof(float), c->lanes[0].stream));
+    if ((rc = ensure_buf(c, c->owned, owned.size()))) return rc;
+    if (w) HIP_TRY(c, hipMemcpy(c->owned.p, owned.data(), owned.size() * 4, hipMemcpyHostToDevice));
+    if (probe_pos) {
+      std::vector<float4> pos((size_t)w);
+      for (int j = 0; j < w; ++j) pos[(size_t)j] = make_float4(probe_pos[j * 3], probe_pos[j * 3 + 1], probe_pos[j * 3 + 2], 0.0f);
+      if ((rc = ensure_buf(c, c->probes.pos, pos.size())) || (rc = ensure_buf(c, c->probes.acc, (size_t)PT_SH9_FLOATS * (size_t)w))) return rc;
+      HIP_TRY(c, hipMemcpy(c->probes.pos.p, pos.data(), pos.size() * sizeof(float4), hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemsetAsync(c->probes.acc.p, 0, (size_t)PT_SH9_FLOATS * (size_t)w * sizeof(float), c->lanes[0].stream));
+    } else {
+      if ((rc = ensure_buf(c, c->lightmap.back, (size_t)w))) return rc;
+      HIP_TRY(c, hipMemsetAsync(c->lightmap.back.p, 0, (size_t)(w ? w : 1) * sizeof(uint32_t), c->lanes[0].stream));
+    }
     c->owned_n = (uint32_t)w;
   } else if (!(c->owned_key_valid && c->owned_w == w && c->owned_h == h && c->owned_rank == tile_rank && c->owned_count == tile_count && c->owned.p)) {
     std::vector<uint32_t> owned;
@@ -373,9 +385,9 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->rad_w = w; c->rad_h = h;
   c->fr.w = w; c->fr.h = h; c->fr.max_bounces = max_bounces; c->fr.n_owned = (uint32_t)n_owned; c->fr.owned = c->owned.p;
   c->fr.seed_hash = seed_hash(seed);
-  // the path integrator's camera frames number a batch's paths in the context's order; raster frames (one sample) and probe frames (k_raygen_probe and
-  // k_accumulate_sh, whose order ptc_debug_probe_project publishes) stay sample-major
-  c->fr.path_order = is_raster(integrator) || probe_pos ? PT_ORDER_SAMPLE : c->path_order;
+  // the path integrator's camera frames number a batch's paths in the context's order; raster frames (one sample), probe frames (k_raygen_probe and
+  // k_accumulate_sh, whose order ptc_debug_probe_project publishes) and lightmap frames (k_raygen_texel, k_lm_first_hit) stay sample-major
+  c->fr.path_order = is_raster(integrator) || entries ? PT_ORDER_SAMPLE : c->path_order;
   c->spp_total = is_raster(integrator) ? 1 : spp_total;
   c->integrator = integrator; c->samples_done = 0; c->sample_base = 0; c->resolve_divisor = 0;
   // samples of one full batch: as many as fit max_batch_paths split over the lanes.  The queues themselves are sized by the
@@ -414,7 +426,9 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   c->glass.seconds = 0.0; c->glass.frame_interactions = c->glass.max_interactions;
   c->medium.seconds = 0.0;
   c->in_frame = true;
-  c->probes.on = probe_pos != nullptr; c->probes.base = probe_base;
+  c->probes.on = probe_pos != nullptr; c->lightmap.on = lightmap;
+  if (probe_pos) c->probes.base = entries->base;
+  if (lightmap) c->lightmap.base = entries->base;
   return PTC_OK;
 }
 }  // namespace ptc_detail
@@ -521,7 +535,7 @@ void ptc_destroy(ptc_ctx* c) {
 const char* ptc_last_error(const ptc_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
 int ptc_frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count) {
-  return frame_begin(c, w, h, spp_total, seed, max_bounces, integrator, tile_rank, tile_count, nullptr, 0);
+  return frame_begin(c, w, h, spp_total, seed, max_bounces, integrator, tile_rank, tile_count, nullptr);
 }
 
 int ptc_frame_reserve(ptc_ctx* c) {
@@ -584,7 +598,7 @@ int ptc_frame_checkpoint(ptc_ctx* c, float* accum_rgba, uint64_t* n_owned_pixels
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_checkpoint: no frame");
   if (is_raster(c->integrator)) return fail(c, PTC_E_ARG, "frame_checkpoint: the raster integrators have nothing to resume");
   if (c->adaptive.on) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in an adaptive frame");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in a probe frame");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "frame_checkpoint: not available in a probe or lightmap frame");
   { int rf = flush(c); if (rf) return rf; }
   { int rs = sync_all_lanes(c); if (rs) return rs; }
   if (n_owned_pixels) *n_owned_pixels = c->fr.n_owned;
@@ -596,7 +610,7 @@ int ptc_frame_checkpoint(ptc_ctx* c, float* accum_rgba, uint64_t* n_owned_pixels
 int ptc_frame_restore(ptc_ctx* c, const float* accum_rgba, uint64_t n_owned_pixels, uint32_t samples_done) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_restore: no frame (ptc_frame_begin with the checkpointed frame's parameters first)");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "frame_restore: not available in a probe frame");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "frame_restore: not available in a probe or lightmap frame");
   if (!accum_rgba) return fail(c, PTC_E_ARG, "frame_restore: null pointer");
   if (c->adaptive.on) return fail(c, PTC_E_STATE, "frame_restore: not available in an adaptive frame");
   if (c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_restore: call it right after ptc_frame_begin, before any sample");

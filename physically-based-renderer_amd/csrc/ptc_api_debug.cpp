@@ -5,22 +5,6 @@
 using namespace ptc_detail;
 
 namespace {
-// The debug getters read the host build: after a refit on the device its vertex-dependent arrays come back from HBM first.
-int refresh_host_copy(ptc_ctx* c) {
-  if (!c->scene.host_stale || c->device < 0) return PTC_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  { int rs = sync_all_lanes(c); if (rs) return rs; }
-  HostBuilt& B = *c->built;
-  B.recs.resize((size_t)B.n_units * 4);                                     // a tree or a commit made on the device left the host arrays unsized
-  B.shade.resize((size_t)B.n_tris * B.shade_stride * 4);
-  B.wverts.resize(B.n_wverts);
-  HIP_TRY(c, hipMemcpy(B.recs.data(), c->scene.dsc.recs, B.recs.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(B.shade.data(), c->scene.dsc.shade, B.shade.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(B.wverts.data(), c->scene.drf.wverts, B.wverts.size() * sizeof(HostVertex), hipMemcpyDeviceToHost));
-  c->scene.host_stale = false;
-  return PTC_OK;
-}
-
 // what the two probe hooks need of debug_prepare: a device, idle lanes, the frame ended, lane 0's queues for n paths.  No scene: neither kernel reads one.
 int probe_debug_prepare(ptc_ctx* c, uint32_t n) {
   { int rd = need_device(c); if (rd) return rd; }
@@ -40,6 +24,22 @@ bool probe_debug_args_bad(int n, uint32_t base, uint32_t first_sample, uint32_t 
 }  // namespace
 
 namespace ptc_detail {
+// The debug getters read the host build: after a refit on the device its vertex-dependent arrays come back from HBM first.
+int refresh_host_copy(ptc_ctx* c) {
+  if (!c->scene.host_stale || c->device < 0) return PTC_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int rs = sync_all_lanes(c); if (rs) return rs; }
+  HostBuilt& B = *c->built;
+  B.recs.resize((size_t)B.n_units * 4);                                     // a tree or a commit made on the device left the host arrays unsized
+  B.shade.resize((size_t)B.n_tris * B.shade_stride * 4);
+  B.wverts.resize(B.n_wverts);
+  HIP_TRY(c, hipMemcpy(B.recs.data(), c->scene.dsc.recs, B.recs.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.shade.data(), c->scene.dsc.shade, B.shade.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(B.wverts.data(), c->scene.drf.wverts, B.wverts.size() * sizeof(HostVertex), hipMemcpyDeviceToHost));
+  c->scene.host_stale = false;
+  return PTC_OK;
+}
+
 int debug_prepare(ptc_ctx* c, uint32_t n, const char* who, DebugFeatures features) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->committed) return fail(c, PTC_E_STATE, std::string(who) + ": scene not committed");
@@ -290,7 +290,7 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     return fail(c, PTC_E_ARG, "debug_camera_rays: bad argument");
   for (uint32_t j = 0; j < n_pixels; ++j)
     if (pixels[j] >= (uint32_t)w * (uint32_t)h) return fail(c, PTC_E_ARG, "debug_camera_rays: pixel index outside the frame");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "debug_camera_rays: a probe frame is in progress (its rays: ptc_debug_probe_rays)");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "debug_camera_rays: a probe or lightmap frame is in progress (its rays: ptc_debug_probe_rays, ptc_debug_lightmap_rays)");
   const uint32_t n = n_pixels * n_samples;
   const uint32_t seed_hash = ::seed_hash(seed);
   if (c->device < 0) {      // the host evaluation of pt_lens.h

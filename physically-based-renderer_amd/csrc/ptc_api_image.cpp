@@ -30,7 +30,7 @@ extern "C" {
 int ptc_frame_guides(ptc_ctx* c) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_guides: no frame");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "frame_guides: a probe frame has no camera image to guide");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "frame_guides: a probe or lightmap frame has no camera image to guide");
   if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_guides: the frame is not a PTC_INTEGRATOR_PATH frame (the raster integrators are noise-free)");
   const uint32_t n = (uint32_t)c->fr.w * (uint32_t)c->fr.h;      // every pixel, whatever the frame's tile share: the root of a sharded frame denoises the whole image
   int rc;
@@ -92,7 +92,7 @@ int ptc_read_guide_hit(ptc_ctx* c, int32_t* prim, float* uv) {
 int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!out) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: null pointer");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: a probe frame has no camera image");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: a probe or lightmap frame has no camera image");
   if (!c->guides.valid) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: no guides (ptc_frame_guides)");
   const int w = c->rad_w, h = c->rad_h;
   if (px < 0 || py < 0 || px >= w || py >= h) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: pixel outside the frame");
@@ -117,7 +117,7 @@ namespace {
 // sampled: the input is the radiance, demodulated by k_ad_sampled_variance, with the variance of the frame's own samples (§8d) where a pixel has four or more
 int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated, bool sampled = false) {
   { int rd = need_device(c); if (rd) return rd; }
-  if (c->probes.on) return fail(c, PTC_E_STATE, "denoise: a probe frame has no image to denoise");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "denoise: a probe or lightmap frame has no image to denoise");
   const ptc_denoise_params p = with_defaults(params, ptc_denoise_default_params);
   auto bad = [](float v) { return !(v >= 0.0f) || !(v <= 3.0e38f); };      // NaN, negative, infinite
   if (p.iterations < 0 || p.iterations > PTC_DENOISE_MAX_ITERATIONS) return fail(c, PTC_E_ARG, "denoise: iterations outside 0..8");
@@ -186,7 +186,7 @@ void ptc_temporal_default_params(ptc_temporal_params* p) {
 
 int ptc_temporal_accumulate(ptc_ctx* c, const ptc_temporal_params* params) {
   { int rd = need_device(c); if (rd) return rd; }
-  if (c->probes.on) return fail(c, PTC_E_STATE, "temporal_accumulate: a probe frame has no image to accumulate");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "temporal_accumulate: a probe or lightmap frame has no image to accumulate");
   const ptc_temporal_params p = with_defaults(params, ptc_temporal_default_params);
   if (p.max_history < 1 || p.max_history > PTC_TEMPORAL_MAX_HISTORY) return fail(c, PTC_E_ARG, "temporal_accumulate: max_history outside 1..1024");
   if (!(p.sigma_z >= 0.0f) || !(p.sigma_z <= 3.0e38f)) return fail(c, PTC_E_ARG, "temporal_accumulate: sigma_z is negative or not finite");
@@ -284,7 +284,7 @@ extern "C" {
 int ptc_frame_set_adaptive(ptc_ctx* c, const ptc_adaptive_params* params) {
   { int rd = need_device(c); if (rd) return rd; }
   if (!c->in_frame) return fail(c, PTC_E_STATE, "frame_set_adaptive: no frame");
-  if (c->probes.on) return fail(c, PTC_E_STATE, "frame_set_adaptive: not available in a probe frame");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "frame_set_adaptive: not available in a probe or lightmap frame");
   if (c->integrator != PTC_INTEGRATOR_PATH) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame is not a PTC_INTEGRATOR_PATH frame");
   if (c->adaptive.on || c->samples_done || c->pending) return fail(c, PTC_E_STATE, "frame_set_adaptive: call it once, right after ptc_frame_begin, before any sample");
   if (c->resolve_divisor) return fail(c, PTC_E_STATE, "frame_set_adaptive: the frame has a resolve divisor (ptc_frame_set_sample_range)");
@@ -380,7 +380,7 @@ int ptc_get_adaptive_stats(ptc_ctx* c, ptc_adaptive_stats* out) {
 int ptc_set_sample_covariance(ptc_ctx* c, int on) {
   if (!c) return PTC_E_ARG;
   if (on != 0 && on != 1) return fail(c, PTC_E_ARG, "set_sample_covariance: 0 or 1");
-  if (on == 1 && c->probes.on) return fail(c, PTC_E_STATE, "set_sample_covariance: a probe frame keeps no per-sample covariance (the setting is unchanged)");
+  if (on == 1 && entry_frame(c)) return fail(c, PTC_E_STATE, "set_sample_covariance: a probe or lightmap frame keeps no per-sample covariance (the setting is unchanged)");
   c->adaptive.cov_setting = on == 1;
   return PTC_OK;
 }
@@ -574,7 +574,8 @@ int ptc_probes_begin(ptc_ctx* c, const float* positions_xyz, int n_probes, uint3
   if ((uint64_t)probe_index_base + (uint64_t)n_probes > 0x100000000ull) return fail(c, PTC_E_ARG, "probes_begin: probe indices exceed 32 bits");
   for (size_t i = 0; i < (size_t)n_probes * 3; ++i)
     if (!std::isfinite(positions_xyz[i])) return fail(c, PTC_E_ARG, "probes_begin: a position is not finite");
-  return frame_begin(c, n_probes, 1, spp_total, seed, max_bounces, PTC_INTEGRATOR_PATH, 0, 1, positions_xyz, probe_index_base);
+  const FrameEntries fe{"probes_begin", positions_xyz, probe_index_base};
+  return frame_begin(c, n_probes, 1, spp_total, seed, max_bounces, PTC_INTEGRATOR_PATH, 0, 1, &fe);
 }
 
 int ptc_probes_read_sh(ptc_ctx* c, float* out) {

@@ -59,7 +59,7 @@ int ptc_comm_init(ptc_ctx* c, const uint8_t id[PTC_COMM_ID_BYTES], int rank, int
 
 int ptc_comm_reduce_radiance(ptc_ctx* c, int root) {
   { int rd = need_device(c); if (rd) return rd; }
-  if (c->probes.on) return fail(c, PTC_E_STATE, "comm_reduce_radiance: a probe frame is not a tile share of an image (shard probes by probe_index_base)");
+  if (entry_frame(c)) return fail(c, PTC_E_STATE, "comm_reduce_radiance: a probe or lightmap frame is not a tile share of an image (shard probes by probe_index_base, texels by texel_index_base)");
   if (!c->comm.handle) return fail(c, PTC_E_STATE, "comm_reduce_radiance: no communicator (ptc_comm_init / ptc_group_create)");
   if (root < 0 || root >= c->comm.size) return fail(c, PTC_E_ARG, "comm_reduce_radiance: bad root");
   if (!c->radiance.p || c->rad_w == 0) return fail(c, PTC_E_STATE, "comm_reduce_radiance: nothing rendered");

@@ -1,7 +1,7 @@
 // ptc_ctx.h — the private state of the C-ABI: what a context owns, and the helpers the ptc_api*.cpp files share.
 //
 // Private to ptc_api.cpp (context, lanes, batches, frames), ptc_api_scene.cpp (description, commit, refit, rebuild, deformation), ptc_api_image.cpp (guides, denoisers,
-// temporal, adaptive, display, probes), ptc_api_multi.cpp (RCCL, groups) and ptc_api_debug.cpp (the ptc_debug_* hooks).  It is not one of the kernel sources
+// temporal, adaptive, display, probes), ptc_api_lightmap.cpp (lightmaps), ptc_api_multi.cpp (RCCL, groups) and ptc_api_debug.cpp (the ptc_debug_* hooks).  It is not one of the kernel sources
 // whose hash the library reports (ptc_build_info).
 //
 // Ownership is in the types: a DevBuf, a TreeBufs and a StageTimer free what they hold when they go, so `delete c` releases every feature's device memory and
@@ -24,6 +24,7 @@
 #include "pt_display.h"
 #include "pt_probes.h"
 #include "pt_medium.h"
+#include "pt_lightmap.h"
 
 #include <rccl/rccl.h>
 
@@ -296,6 +297,25 @@ struct Probes {
   DevBuf<float> acc;                // 27 running sums per probe, [probe][k][rgb]
 };
 
+// lightmaps (pt_lightmap.h).  A lightmap frame is a frame of n x 1 "pixels", the covered texels of the atlas in ascending atlas index — `fr`, accum, radiance, the
+// batching and the sample range are the frame's own — whose batches start at k_raygen_texel, count back-face first hits at bounce 0 and end with k_accumulate
+// alone.  The flag lives as long as the frame does (drop_guides ends it).  Nothing here is allocated by a context that never bakes
+struct Lightmap {
+  bool on = false;
+  int w = 0, h = 0;
+  uint32_t base = 0;                // index of texel 0 in the RNG key (ptc_lightmap_desc: texel_index_base)
+  uint32_t n = 0, dropped = 0;      // entries of the list; owned texels dropped for a degenerate world triangle
+  DevBuf<float4> texels;            // two per entry: (origin, atlas index bits) (normal, primitive bits)
+  DevBuf<uint32_t> back;            // per entry: samples whose first hit was a back face
+  DevBuf<float4> atlas[2];          // the resolve's target and the dilation's ping-pong
+  DevBuf<float> fraction;           // ptc_lightmap_read's out_backface
+  // the texel-list build: the owner image, the compaction's scratch, the list; the instance's geometry when it comes from the host build
+  DevBuf<uint32_t> owner, block, counts, list, idx;
+  DevBuf<uint8_t> flags;
+  DevBuf<float> uv;
+  DevBuf<HostVertex> verts;
+};
+
 // multi-GPU
 struct Comm {
   ncclComm_t handle = nullptr;
@@ -398,6 +418,7 @@ struct ptc_ctx {
   ptc_detail::Temporal temporal;
   ptc_detail::Display display;
   ptc_detail::Probes probes;
+  ptc_detail::Lightmap lightmap;
   ptc_detail::Comm comm;
   // stats
   ptc_stats stats{};
@@ -422,8 +443,10 @@ inline const char* const kDescriptionChanged = "scene_refit: the scene's meshes 
 // commit_upload(Upload::NewScene)) ends it, and with it the position snapshot's claim to be current.  Refits and rebuilds keep the ids and the history.
 inline void drop_history(ptc_ctx* c) { c->temporal.live = false; c->temporal.snap_current = false; }
 // the frame is over or the scene changed: its guides and its denoised image go with it, the read-backs serve the radiance again
-inline void drop_guides(ptc_ctx* c) { c->probes.on = false; c->guides.valid = false; c->denoise.valid = false; c->temporal.accum_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
+inline void drop_guides(ptc_ctx* c) { c->probes.on = false; c->lightmap.on = false; c->guides.valid = false; c->denoise.valid = false; c->temporal.accum_valid = false; c->output = PTC_OUTPUT_RADIANCE; }
 // the image ptc_read_radiance_rgba32f / _rgba16f / ptc_tonemap_rgba8 serve (ptc_select_output)
+// a frame whose "pixels" are a list of entries — probes, or the texels of a lightmap — and no image: what has no meaning without a camera image refuses it
+inline bool entry_frame(const ptc_ctx* c) { return c->probes.on || c->lightmap.on; }
 inline const float4* served_image(const ptc_ctx* c) {
   return c->output == PTC_OUTPUT_DENOISED ? c->denoise.denoised.p : c->output == PTC_OUTPUT_ACCUMULATED ? c->temporal.accum.p : c->radiance.p;
 }
@@ -511,8 +534,10 @@ uint32_t batch_samples(const ptc_ctx* c, size_t n_pixels, size_t batch_paths);
 int flush(ptc_ctx* c);
 int join_lanes_on_stream0(ptc_ctx* c);
 int sum_lane_stats(ptc_ctx* c, unsigned long long st[ST_N]);
-int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const float* probe_pos,
-                uint32_t probe_base);
+// a frame over a list of w entries instead of an image (h = 1, the path integrator, no tiles): probes at probe_pos (3 floats each), or — probe_pos == nullptr — the
+// texel list the lightmap state holds (w may be 0: nothing is covered); base: the index of entry 0 in the RNG key; who: the entry the caller used, for ptc_last_error
+struct FrameEntries { const char* who; const float* probe_pos; uint32_t base; };
+int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const FrameEntries* entries);
 
 struct ScopedSpan {   // records a start/stop event pair around launches on one of the context's streams
   ptc_ctx* c; hipStream_t st; Span s{}; bool on;
@@ -623,6 +648,9 @@ int read_hits(ptc_ctx* c, uint32_t n, float* out_t, int32_t* out_prim, float* ou
 typedef std::function<void(uint32_t path, const float4& A, const float4& B, const float4& C)> RecordSink;
 int scatter_segment_records(ptc_ctx* c, const DevQueues& q, const uint32_t* seg_counts, const RayQ& rq, uint32_t (*path_of)(const float4& B, const float4& C), uint32_t n,
                             const char* who, const char* what, const RecordSink& sink);
+
+// ---- ptc_api_debug.cpp: the host's copy of the vertex-dependent arrays, fetched from HBM when a refit on the device left it stale ----------------------------
+int refresh_host_copy(ptc_ctx* c);
 
 // ---- ptc_api_image.cpp ---------------------------------------------------------------------------------------------------------------------------
 DevAdaptive dev_adaptive(const ptc_ctx* c);

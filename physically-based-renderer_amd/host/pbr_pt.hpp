@@ -304,6 +304,20 @@ public:
     ck(ptc_probes_read_sh(_ctx, out.data()));
     return out;
   }
+  // lightmaps (ptc_lightmap_begin ...): the irradiance over the width x height atlas of one instance, spp samples per covered texel: width * height
+  // RGBA floats, row 0 first — RGB the irradiance, alpha 1 baked / 0.5 filled by dilation / 0 empty.  uv: 2 floats per vertex of the instance's mesh, or empty = the
+  // mesh's texCoords; texels whose first hits are back faces in more than backfaceThreshold of their samples are invalid and filled from their neighbours
+  auto bakeLightmap(int instance, int width, int height, int spp, std::vector<float> const& uv = {}, std::uint64_t seed = 0, int maxBounces = 8, int dilateIters = 2,
+                    float backfaceThreshold = 0.1f, std::uint32_t indexBase = 0) -> std::vector<float> {
+    ptc_lightmap_desc d{};
+    d.instance = instance; d.width = width; d.height = height; d.uv = uv.empty() ? nullptr : uv.data(); d.texel_index_base = indexBase; d.spp_total = spp; d.seed = seed;
+    d.max_bounces = maxBounces;
+    std::vector<float> out(width > 0 && height > 0 ? (std::size_t)width * (std::size_t)height * 4 : 0);
+    ck(ptc_render_lightmap(_ctx, &d, dilateIters, backfaceThreshold, out.empty() ? nullptr : out.data()));
+    return out;
+  }
+  // (entries, owned texels dropped for a degenerate world triangle) of the lightmap frame in progress
+  auto lightmapTexelCount() -> std::array<std::uint32_t, 2> { std::array<std::uint32_t, 2> n{}; ck(ptc_lightmap_texel_count(_ctx, &n[0], &n[1])); return n; }
   static auto sh9Eval(float const* sh27, std::array<float, 3> const& dir) -> std::array<float, 3> { std::array<float, 3> o{}; ptc_sh9_eval(sh27, dir.data(), o.data()); return o; }
   static auto sh9Irradiance(float const* sh27, std::array<float, 3> const& normal) -> std::array<float, 3> { std::array<float, 3> o{}; ptc_sh9_irradiance(sh27, normal.data(), o.data()); return o; }
   auto stats() -> ptc_stats { ptc_stats s; ck(ptc_get_stats(_ctx, &s)); return s; }

@@ -8,6 +8,12 @@
 //              [--fog x,y,z:x,y,z:sigma_t[:albedo[:g]] | --fog scene:sigma_t[:albedo[:g]]]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
 //              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
+//              [--lightmap INSTANCE:WxH --lightmap-out lm.pfm [--lightmap-alpha a.pfm] [--lightmap-dilate N] [--lightmap-backface F]]
+// --lightmap INSTANCE:WxH with --lightmap-out lm.pfm: bake the irradiance on instance INSTANCE over its W x H UV atlas (the mesh's texture coordinates) instead of an
+// image (ptc_render_lightmap), at --spp samples per covered texel, --seed, --bounces.  lm.pfm holds the irradiance, row 0 of the atlas (v = 0) at the
+// top; --lightmap-alpha writes the coverage (1 baked, 0.5 filled, 0 empty) in all three channels.  --lightmap-dilate N: N dilation iterations into the gutters
+// (default 2, 0..64); --lightmap-backface F: a texel whose first hits are back faces in more than F of its samples is invalid and filled from its neighbours
+// (default 0.1; 1 switches the test off).  One context, path integrator.  Bad values are reported before any device work.
 // --probe-grid NX,NY,NZ / --probes FILE with --probes-out sh.pfm: bake light probes instead of an image (ptc_render_probes) — the centres of the
 // NX x NY x NZ cells of the scene's bounding box (x fastest, then y, then z; the grid's origin and cell size are printed), or the `x y z` lines of a text file —
 // at --spp samples each, --seed, --bounces.  sh.pfm is a 9 x n RGB image: row j holds the nine SH coefficients of probe j.  One context, path integrator.
@@ -232,6 +238,9 @@ int main(int argc, char** argv) {
   double exposureEv = 0.0;
   int probeGrid[3] = {0, 0, 0};              // --probe-grid
   std::string probesFile, probesOut;         // --probes, --probes-out
+  std::string lmSpec, lmOut, lmAlpha;        // --lightmap, --lightmap-out, --lightmap-alpha
+  int lmInstance = -1, lmW = 0, lmH = 0, lmDilate = 2;
+  float lmBackface = 0.1f;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -261,6 +270,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--probe-grid") { if (std::sscanf(next(), "%d,%d,%d", &probeGrid[0], &probeGrid[1], &probeGrid[2]) != 3) { std::cerr << "--probe-grid NX,NY,NZ\n"; return 2; } }
     else if (a == "--probes") probesFile = next(); else if (a == "--probes-out") probesOut = next();
+    else if (a == "--lightmap") lmSpec = next(); else if (a == "--lightmap-out") lmOut = next(); else if (a == "--lightmap-alpha") lmAlpha = next();
+    else if (a == "--lightmap-dilate") lmDilate = std::atoi(next()); else if (a == "--lightmap-backface") lmBackface = (float)std::atof(next());
     else if (a == "--env") envPath = next(); else if (a == "--sky") sky = true;
     else if (a == "--filter") { const std::string f = next(); if (f == "linear") filter = PTC_FILTER_LINEAR; else if (f == "nearest") filter = PTC_FILTER_NEAREST; else { std::cerr << "--filter nearest|linear\n"; return 2; } }
     else if (a == "--cam-pos") { for (float& v : camPos) v = (float)std::atof(next()); haveCam = true; }
@@ -314,6 +325,16 @@ int main(int argc, char** argv) {
         while (f >> x >> y >> z) { probePos.push_back(x); probePos.push_back(y); probePos.push_back(z); }
         if (!f.eof() || probePos.empty()) throw std::runtime_error("--probes FILE: lines of `x y z`, at least one");
       }
+    }
+    const bool bakeLightmap = !lmSpec.empty() || !lmOut.empty() || !lmAlpha.empty();
+    if (bakeLightmap) {      // a lightmap: refused here, before a device is touched
+      if (lmSpec.empty() || lmOut.empty()) throw std::runtime_error("--lightmap INSTANCE:WxH needs --lightmap-out lm.pfm, and the other way round");
+      if (std::sscanf(lmSpec.c_str(), "%d:%dx%d", &lmInstance, &lmW, &lmH) != 3 || lmInstance < 0 || lmW < 1 || lmW > 8192 || lmH < 1 || lmH > 8192)
+        throw std::runtime_error("--lightmap INSTANCE:WxH: an instance index >= 0 and an atlas of 1..8192 texels a side");
+      if (bakeProbes || gpus != 0 || integrator != PTC_INTEGRATOR_PATH || adaptive || denoise) throw std::runtime_error("a lightmap is baked on one context with the path integrator (not with --gpus / --raster / --adaptive / --denoise / probes)");
+      if (lmDilate < 0 || lmDilate > 64) throw std::runtime_error("--lightmap-dilate N: 0..64 iterations");
+      if (!(lmBackface >= 0.0f) || !std::isfinite(lmBackface)) throw std::runtime_error("--lightmap-backface F: a finite fraction >= 0");
+      if (spp < 1) throw std::runtime_error("--spp N: at least one sample per texel");
     }
     for (const std::string& sp : lightSpecs) lights.push_back(parseLight(sp));
     if (!lights.empty() && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--light applies to the path integrator (not with --raster / --raster16)");
@@ -464,6 +485,22 @@ int main(int argc, char** argv) {
         const ptc_stats st = rs.stats();
         std::printf("{\"scene\": \"%s\", \"probes\": %zu, \"spp\": %d, \"paths\": %llu, \"seconds_render\": %.6f, \"mpaths_per_s\": %.2f}\n", (gltf.empty() ? scene : gltf).c_str(), n, spp,
                     (unsigned long long)st.paths, st.seconds_render, st.seconds_render > 0 ? st.paths / st.seconds_render / 1e6 : 0.0);
+        return 0;
+      }
+      if (bakeLightmap) {
+        pbr::PathTraceRenderSystem& rs = *single;
+        const std::vector<float> lm = rs.bakeLightmap(lmInstance, lmW, lmH, spp, {}, seed, bounces, lmDilate, lmBackface);
+        const auto count = rs.lightmapTexelCount();
+        pbr::image::write_pfm(lmOut, lm.data(), lmW, lmH);
+        if (!lmAlpha.empty()) {
+          std::vector<float> al(lm.size());
+          for (std::size_t p = 0; p < lm.size() / 4; ++p) { al[p * 4] = al[p * 4 + 1] = al[p * 4 + 2] = lm[p * 4 + 3]; al[p * 4 + 3] = 1.0f; }
+          pbr::image::write_pfm(lmAlpha, al.data(), lmW, lmH);
+        }
+        const ptc_stats st = rs.stats();
+        std::printf("{\"scene\": \"%s\", \"lightmap\": [%d, %d, %d], \"texels\": %u, \"dropped\": %u, \"spp\": %d, \"paths\": %llu, \"seconds_render\": %.6f, \"mpaths_per_s\": %.2f}\n",
+                    (gltf.empty() ? scene : gltf).c_str(), lmInstance, lmW, lmH, count[0], count[1], spp, (unsigned long long)st.paths, st.seconds_render,
+                    st.seconds_render > 0 ? st.paths / st.seconds_render / 1e6 : 0.0);
         return 0;
       }
       applyLens(*single);

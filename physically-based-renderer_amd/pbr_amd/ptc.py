@@ -161,6 +161,11 @@ class PtcMediumStats(_Struct):
     _fields_ = [("crossed", C.c_uint64), ("scattered", C.c_uint64), ("attenuated", C.c_uint64), ("seconds_medium", C.c_double)]
 
 
+class PtcLightmapDesc(_Struct):
+    _fields_ = [("instance", C.c_int), ("width", C.c_int), ("height", C.c_int), ("uv", C.POINTER(C.c_float)), ("texel_index_base", C.c_uint32), ("spp_total", C.c_int),
+                ("seed", C.c_uint64), ("max_bounces", C.c_int)]
+
+
 class PtcMediumSample(_Struct):
     _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("t_end", C.c_float), ("u0", C.c_float), ("u1", C.c_float), ("u2", C.c_float),
                 ("so", C.c_float * 3), ("sd", C.c_float * 3), ("stmax", C.c_float), ("crosses", C.c_int), ("t0", C.c_float), ("t1", C.c_float), ("s", C.c_float),
@@ -443,7 +448,25 @@ def _medium_prototypes():
     }
 
 
+def _lightmap_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_lightmap.h declares, in the header's order; exported under ptcx_ like ptc_medium.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, fp, u32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    dp = C.POINTER(PtcLightmapDesc)
+    return {
+        "ptc_lightmap_begin": (i, [vp, dp]),
+        "ptc_lightmap_texel_count": (i, [vp, u32p, u32p]),
+        "ptc_lightmap_read_texels": (i, [vp, u32p, u32p, fp, fp]),
+        "ptc_lightmap_read": (i, [vp, i, C.c_float, fp, fp]),
+        "ptc_render_lightmap": (i, [vp, dp, i, C.c_float, fp]),
+        "ptc_debug_lightmap_cover": (i, [vp, u32p, u32, fp, u32, i, i, u32p]),
+        "ptc_debug_lightmap_rays": (i, [vp, dp, u32, u32, u32p, u32p, u32p, fp, fp, fp, u32p]),
+        "ptc_debug_lightmap_dilate": (i, [vp, i, i, i, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
+_LIGHTMAP_PROTOTYPES = _lightmap_prototypes()
 _MEDIUM_PROTOTYPES = _medium_prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
 _GLASS_PROTOTYPES = _glass_prototypes()
@@ -472,7 +495,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()) + list(_LIGHTMAP_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -1130,6 +1153,94 @@ class PathTracer:
         self.probes_begin(p, spp, seed, max_bounces, index_base)
         self.frame_add_samples(spp)
         return self.read_probes_sh()
+
+    # ---- lightmaps (csrc/pt_lightmap.h, include/ptc_lightmap.h) -------------------------------------------------------------
+    def _lightmap_desc(self, instance, width, height, spp_total, uv, seed, max_bounces, index_base):
+        """(ptc_lightmap_desc, the array its uv points into): uv is (n_verts, 2) float32 or None = the mesh's texcoord."""
+        d = PtcLightmapDesc()
+        d.instance, d.width, d.height, d.texel_index_base, d.spp_total, d.seed, d.max_bounces = int(instance), int(width), int(height), int(index_base), int(spp_total), int(seed), int(max_bounces)
+        keep = None
+        if uv is not None:
+            keep = np.ascontiguousarray(uv, np.float32)
+            if keep.ndim != 2 or keep.shape[1] != 2:
+                raise PtcError(f"lightmap uv must be (n_verts, 2), got {keep.shape}")
+            d.uv = _ptr(keep)
+        return d, keep
+
+    def lightmap_begin(self, instance, width, height, spp_total, uv=None, seed=0, max_bounces=8, index_base=0):
+        """ptc_lightmap_begin: a lightmap frame over the covered texels of `instance`'s width x height atlas; frame_add_samples / frame_set_sample_range / sync work
+        as in any frame, and read_lightmap resolves what has been accumulated."""
+        d, keep = self._lightmap_desc(instance, width, height, spp_total, uv, seed, max_bounces, index_base)
+        self._ck(self._L.ptc_lightmap_begin(self._h, C.byref(d)))
+        n = C.c_uint32(0)
+        self._ck(self._L.ptc_lightmap_texel_count(self._h, C.byref(n), None))
+        self._w, self._h_px = int(n.value), 1
+        self._lm_size = (int(height), int(width))
+
+    def lightmap_texel_count(self):
+        """ptc_lightmap_texel_count: (entries of the lightmap frame in progress, owned texels dropped for a degenerate world triangle)."""
+        n, dr = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._L.ptc_lightmap_texel_count(self._h, C.byref(n), C.byref(dr)))
+        return int(n.value), int(dr.value)
+
+    def lightmap_texels(self):
+        """ptc_lightmap_read_texels: dict(atlas_index (n,) uint32, prim (n,) uint32, origin (n, 3) float32, normal (n, 3) float32) of the frame in progress."""
+        n, _ = self.lightmap_texel_count()
+        a, pr, o, nr = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        self._ck(self._L.ptc_lightmap_read_texels(self._h, _ptr(a), _ptr(pr), _ptr(o), _ptr(nr)))
+        return dict(atlas_index=a, prim=pr, origin=o, normal=nr)
+
+    def read_lightmap(self, dilate=2, backface_threshold=0.1, with_backface=False):
+        """ptc_lightmap_read: the atlas (H, W, 4) float32 — RGB irradiance, alpha 1 baked / 0.5 filled by dilation / 0 empty; with_backface: and the back-face
+        fraction per entry, (n,) float32."""
+        h, w = getattr(self, "_lm_size", (1, 1))
+        out = np.zeros((h, w, 4), np.float32)
+        frac = np.zeros(max(self.lightmap_texel_count()[0], 1) if with_backface else 0, np.float32)
+        self._ck(self._L.ptc_lightmap_read(self._h, int(dilate), float(backface_threshold), _ptr(out), _ptr(frac) if with_backface else None))
+        return (out, frac[:self.lightmap_texel_count()[0]]) if with_backface else out
+
+    def render_lightmap(self, instance, width, height, spp, uv=None, seed=0, max_bounces=8, index_base=0, dilate=2, backface_threshold=0.1):
+        """ptc_render_lightmap: bake `instance` into a width x height atlas with spp samples per covered texel: (H, W, 4) float32 as read_lightmap returns it."""
+        d, keep = self._lightmap_desc(instance, width, height, spp, uv, seed, max_bounces, index_base)
+        out = np.zeros((int(height), int(width), 4), np.float32)
+        self._ck(self._L.ptc_render_lightmap(self._h, C.byref(d), int(dilate), float(backface_threshold), _ptr(out)))
+        n = C.c_uint32(0)
+        self._ck(self._L.ptc_lightmap_texel_count(self._h, C.byref(n), None))
+        self._w, self._h_px, self._lm_size = int(n.value), 1, (int(height), int(width))
+        return out
+
+    def debug_lightmap_cover(self, indices, uv, width, height):
+        """ptc_debug_lightmap_cover: the owner image (H, W) uint32 of the triangles `indices` (n, 3) with the UVs `uv` (n_verts, 2); 0xffffffff: nobody."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+        t = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((int(height), int(width)), np.uint32)
+        self._ck(self._L.ptc_debug_lightmap_cover(self._h, _ptr(idx), idx.shape[0], _ptr(t), t.shape[0], int(width), int(height), _ptr(out)))
+        return out
+
+    def debug_lightmap_rays(self, instance, width, height, seed, first_sample, n_samples, uv=None, index_base=0, rays=True):
+        """ptc_debug_lightmap_rays: dict(covered, dropped, atlas_index, prim, origin, normal) of the texel list, and with rays=True ray_o, ray_d (n_samples * n, 3)
+        float32 and key (n_samples * n,) uint32 in path order p = sample_local * n + entry."""
+        d, keep = self._lightmap_desc(instance, width, height, 1, uv, seed, 0, index_base)
+        cap = int(width) * int(height)
+        counts = np.zeros(2, np.uint32)
+        a, pr, o, nr = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.float32)
+        od, key = (np.zeros((cap * int(n_samples), 6), np.float32), np.zeros(cap * int(n_samples), np.uint32)) if rays else (None, None)
+        self._ck(self._L.ptc_debug_lightmap_rays(self._h, C.byref(d), int(first_sample), int(n_samples), _ptr(counts), _ptr(a), _ptr(pr), _ptr(o), _ptr(nr),
+                                                 _ptr(od) if rays else None, _ptr(key) if rays else None))
+        n = int(counts[0])
+        out = dict(covered=n, dropped=int(counts[1]), atlas_index=a[:n].copy(), prim=pr[:n].copy(), origin=o[:n].copy(), normal=nr[:n].copy())
+        if rays:
+            m = n * int(n_samples)
+            out.update(ray_o=od[:m, :3].copy(), ray_d=od[:m, 3:].copy(), key=key[:m].copy())
+        return out
+
+    def debug_lightmap_dilate(self, rgba, iters):
+        """ptc_debug_lightmap_dilate: `iters` dilation iterations over the (H, W, 4) image; a new array."""
+        img = np.array(rgba, np.float32, order="C")
+        if img.ndim != 3 or img.shape[2] != 4:
+            raise PtcError(f"the image must be (H, W, 4), got {img.shape}")
+        self._ck(self._L.ptc_debug_lightmap_dilate(self._h, img.shape[1], img.shape[0], int(iters), _ptr(img)))
+        return img
 
     def debug_probe_rays(self, positions, seed, first_sample, n_samples, index_base=0):
         """ptc_debug_probe_rays: (origins, dirs, keys) of the probe rays in path order p = sample_local * n + j: (n_samples * n, 3) float32 twice and uint32."""
