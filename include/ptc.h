@@ -797,4 +797,5 @@ int ptc_debug_refit_host_parts(ptc_ctx*, uint64_t out[8]);
 #include "ptc_exact_debug.h"   /* test hook for the exact fast paths of division and square root: likewise */
 #include "ptc_medium.h"   /* a homogeneous participating medium: likewise */
 #include "ptc_lightmap.h"   /* lightmaps, irradiance over an instance's UV atlas: likewise */
+#include "ptc_emissive_tex.h"   /* textured emission, glTF emissiveTexture as a light set of its own: likewise */
 #endif /* PTC_H */

@@ -28,6 +28,13 @@ extern "C" {
 long long ptc_gltf_load(ptc_ctx* ctx, const char* path, int scene_index, int compose_parents, float bbox6[6],
                         char* err, int err_len);
 
+/* emissiveTexture.  A material whose emissiveFactor is not zero and that has an emissiveTexture gets that texture as its emission texture, with emissiveFactor x
+ * KHR_materials_emissive_strength as the factor and a base emission of zero (ptc_set_material_emission_texture, ptc_emissive_tex.h); like every emitter it stays
+ * OPAQUE and without transmission, whatever the asset says.  ptc_gltf_emissive_textures(0) makes ptc_gltf_load and ptc_gltf_asset_load read such a material as a
+ * uniform emitter of its factor instead, as they did before; (1) is the default; a negative argument changes nothing.  One setting per process, not thread-safe: a process that loads
+ * assets from several threads sets it once, before the loads; returns the previous one. */
+int ptc_gltf_emissive_textures(int on);
+
 /* ---- the asset as a handle: skins, morph targets and animations ---------------------------------------------------------------------
  * ptc_gltf_load is stateless and reads the bind pose only.  A handle keeps the parsed file, so that the scene it loaded can be posed:
  *   ptc_gltf_open          parse the file; NULL on failure (text in err)

@@ -42,6 +42,7 @@ void collect_times(ptc_ctx* c, bool all_done) {
       else if (s.kind == 5) c->alpha.seconds += sec;
       else if (s.kind == 6) c->glass.seconds += sec;
       else if (s.kind == 7) c->medium.seconds += sec;
+      else if (s.kind == 8) { c->stats.seconds_shade += sec; c->emtex.seconds += sec; }
       else c->stats.seconds_render += sec;
     }
     c->free_events.push_back(s.a); c->free_events.push_back(s.b);
@@ -93,13 +94,17 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
     // the scan that follows — on this stream alone, so any(b) does not run beside closest(b + 1) while a medium is on either.  Off: none of these branches, nothing allocated
     const bool medium = medium_on(c);
     const DevMediumQ mq = medium ? dev_medium_q(c, l) : DevMediumQ{};
+    // textured emission (pt_emissive_tex.hip): a third next-event pass per bounce behind the punctual one, with the hit side of its MIS pair — on this stream alone as
+    // well: it needs hit and ray[b & 1] of bounce b intact and adds to lpath itself, so any(b) does not run beside closest(b + 1) while the table exists
+    const bool emtex = emtex_on(c);
+    const DevEmTex et = emtex ? dev_emtex(c) : DevEmTex{};
     auto trace_shadows = [&]() {
       ScopedSpan t(c, st, 1);
       if (glass_shadows || alpha) resolve_shadow(c, l, st, cfg, sc, q, glass_shadows, nullptr, nullptr);
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
-    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass && !medium;
+    const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass && !medium && !emtex;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
       while (ln.ev_scan.size() < need) { hipEvent_t e = nullptr; HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ln.ev_scan.push_back(e); }
@@ -118,7 +123,10 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       // k_shade(b) overwrites the shadow queue any(b - 1) reads and adds to the path radiance it adds to
       if (overlap && b > 0) HIP_TRY(c, hipStreamWaitEvent(st, ln.ev_any[(size_t)b - 1], 0));
       { ScopedSpan t(c, st, 2, per_kernel); pt_launch_shade(st, cfg, ln.d_scene, c->fr, q, b & 1, (uint32_t)b); }
-      if (b == c->fr.max_bounces) break;                         // the last bounce's shade produces no rays
+      if (b == c->fr.max_bounces) {                              // the last bounce's shade produces no rays; a textured emitter it hit still counts, as k_shade's emission does
+        if (emtex) { ScopedSpan t(c, st, 8); pt_launch_shade_emissive_tex(st, sc, q, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, et); }
+        break;
+      }
       if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, false); }
       pt_launch_scan(st, cfg, q, (b + 1) & 1);
       if (overlap) {      // any(b) on the second stream, beside closest(b + 1)
@@ -132,6 +140,13 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
         if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, true); }
         pt_launch_scan(st, cfg, q, (b + 1) & 1);      // the same ray prefix again, the new shadow counts, the work counters zeroed: nothing runs beside it
         trace_shadows();
+      }
+      if (emtex) {        // behind the punctual sample: textured emission at the hit, then the textured sample through the same shadow queue
+        { ScopedSpan t(c, st, 8); pt_launch_shade_emissive_tex(st, sc, q, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, et); }
+        if (et.sample) {
+          pt_launch_scan(st, cfg, q, (b + 1) & 1);
+          trace_shadows();
+        }
       }
     }
     // sample-order accumulation: wait for the previous batch's accumulate (it ran on the previous lane)
@@ -330,7 +345,8 @@ void Lane::teardown() {
 int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_bounces, int integrator, int tile_rank, int tile_count, const FrameEntries* entries) {
   const float* probe_pos = entries ? entries->probe_pos : nullptr;
   const bool lightmap = entries && !probe_pos;
-  if (c) { if (const char* why = medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }      // before the device: a description-only context can tell
+  if (c) { if (const char* why = medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }
+  if (c) { if (const char* why = emtex_medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }      // before the device: a description-only context can tell
   { int rd = need_device(c); if (rd) return rd; }
   c->in_frame = false; c->pending = 0; c->adaptive.on = false; c->adaptive.cov_on = false; c->adaptive.cov_resolved = false; c->adaptive.sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
   const std::string who = entries ? entries->who : "frame_begin";      // the entry the caller used, for ptc_last_error
@@ -346,6 +362,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   if ((rc = glass_upload(c))) return rc;       // the glass tables likewise
   if (c->glass.counters.p) HIP_TRY(c, hipMemset(c->glass.counters.p, 0, PT_GLASS_COUNTERS * sizeof(unsigned long long)));
   if (c->glass.shadow_counters.p) HIP_TRY(c, hipMemset(c->glass.shadow_counters.p, 0, PT_GLASS_SHADOW_COUNTERS * sizeof(unsigned long long)));
+  if ((rc = emtex_upload(c))) return rc;       // the textured emitters' table likewise, and after a refit or rebuild; its counters cleared
   c->glass.frame_shadows = c->glass.shadows;      // before the queues are sized: a frame with transparent shadows keeps a flag byte per path
   if ((rc = medium_frame_begin(c, integrator == PTC_INTEGRATOR_PATH))) return rc;      // likewise: a frame with a medium keeps a medium queue
   // the list of owned pixels (tile-Morton order) depends on the image size and the tile assignment only: a viewer that renders frame after frame at

@@ -84,6 +84,7 @@ int ptc_set_material_alpha(ptc_ctx* c, int material, int mode, float cutoff) {
   if (m.emissive[0] != 0.0f || m.emissive[1] != 0.0f || m.emissive[2] != 0.0f)
     return fail(c, PTC_E_ARG, "set_material_alpha: the material is emissive (emitters are sampled by area without regard to coverage: they stay opaque)");
   if (glass_tau(c, material) > 0.0f) return fail(c, PTC_E_ARG, "set_material_alpha: the material is transmissive (ptc_set_material_transmission: such a material stays OPAQUE)");
+  if (mode != PTC_ALPHA_OPAQUE && emtex_has(c, material)) return fail(c, PTC_E_ARG, "set_material_alpha: the material has an emission texture (ptc_set_material_emission_texture: an emitter stays opaque)");
   if (c->alpha.mode.size() < c->mats.size()) { c->alpha.mode.resize(c->mats.size(), PTC_ALPHA_OPAQUE); c->alpha.cutoff.resize(c->mats.size(), 0.5f); }
   c->alpha.mode[(size_t)material] = mode; c->alpha.cutoff[(size_t)material] = cutoff;
   return PTC_OK;

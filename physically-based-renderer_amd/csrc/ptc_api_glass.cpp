@@ -96,6 +96,8 @@ int ptc_set_material_transmission(ptc_ctx* c, int material, const ptc_transmissi
     return fail(c, PTC_E_ARG, "set_material_transmission: the material is emissive (emitters are sampled by area as opaque surfaces)");
   if ((size_t)material < c->alpha.mode.size() && c->alpha.mode[(size_t)material] != PTC_ALPHA_OPAQUE)
     return fail(c, PTC_E_ARG, "set_material_transmission: the material's alpha mode is not OPAQUE");
+  if (p->transmission > 0.0f && emtex_has(c, material))
+    return fail(c, PTC_E_ARG, "set_material_transmission: the material has an emission texture (ptc_set_material_emission_texture: an emitter stays opaque)");
   if (c->glass.params.size() < c->mats.size()) {
     ptc_transmission_params def;
     ptc_transmission_default_params(&def);

@@ -556,6 +556,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   c->lens = c0->lens;
   c->alpha.mode = c0->alpha.mode; c->alpha.cutoff = c0->alpha.cutoff;      // every member builds context 0's alpha tables
   c->glass.params = c0->glass.params; c->glass.shadows = c0->glass.shadows;      // and its glass tables, with its choice of transparent shadows
+  c->emtex.mats = c0->emtex.mats;      // and its emission textures
   take_lights(c, c0);
   take_medium(c, c0);
   c->have_cam = true; c->tex_linear = c0->tex_linear; c->bvh_builder = c0->bvh_builder; c->toplet_budget = c0->toplet_budget;
@@ -596,6 +597,7 @@ int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload w
   s.insts = c->insts.size();
   deform_all_live(c);      // every caller lays the scene out from the fully evaluated description
   for (MeshPose& P : c->poses) if (P.active()) P.dev_fresh = P.host_fresh;
+  emtex_commit(c);      // the textured emitters' table follows the description being laid out, on a description-only context too; the next ptc_frame_begin uploads it (emtex_upload)
   if (c->device < 0) {   // description-only context: nothing to upload
     c->committed = true;
     commit_stats(c, t0);
@@ -687,6 +689,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->alpha.mode.clear(); c->alpha.cutoff.clear(); c->alpha.dirty = true; c->alpha.n_prims = 0;      // every material of the next description starts OPAQUE; max_layers stays
   c->glass.params.clear(); c->glass.dirty = true; c->glass.n_prims = 0; c->glass.n_thin = 0;      // and without transmission; max_interactions and shadows stay
   c->medium.set = false; c->medium.params = ptc_medium_params{};      // the medium goes as the lights do
+  c->emtex.mats.clear(); c->emtex.dirty = c->emtex.dirty || c->emtex.n_dev > 0; c->emtex.table.clear();      // and no material has an emission texture
   drop_history(c);        // the history is about the primitives of the scene that goes, and reads its shading records in place
   if (c->display.state.p) HIP_TRY(c, hipMemset(c->display.state.p, 0, sizeof(pt_display_state)));      // the adaptation state goes with the scene; the display parameters stay
   release_scene(c);
@@ -851,6 +854,7 @@ int ptc_scene_refit(ptc_ctx* c) {
   if (c->built.use_count() > 1) c->built = std::make_shared<HostBuilt>(*c->built);      // a group shares one build: this context now gets its own
   if (c->device >= 0 && refit_on_device(c)) {
     const int rd = device_refit(c, t0);
+    if (rd == 0) emtex_place(c);
     if (rd <= 0) return rd;
   }
   if (!c->built->topology) return host_build_and_upload(c, t0, /*as_refit=*/true);      // the tree in HBM was built on the device (ptc_scene_rebuild): the host has no topology to refit
@@ -867,6 +871,7 @@ int ptc_scene_refit(ptc_ctx* c) {
     if (rc) return rc;
   }
   { int rc = deform_after_host_refit(c); if (rc) return rc; }
+  emtex_place(c);
   c->stats.seconds_refit = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return PTC_OK;
 }
@@ -884,7 +889,7 @@ int ptc_scene_rebuild(ptc_ctx* c) {
   int rd = (how && std::strcmp(how, "host") == 0) ? 1 : device_rebuild(c, c->device_builder);
   if (rd < 0) return rd;
   if (rd > 0) { if ((rd = host_build_and_upload(c, t0, /*as_refit=*/false))) return rd; }      // PTC_REBUILD=host, an emitter appeared or vanished, a single triangle
-  else c->stats.seconds_rebuild = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  else { emtex_place(c); c->stats.seconds_rebuild = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
   c->in_frame = false; c->pending = 0; drop_guides(c);
   return PTC_OK;
 }

@@ -25,6 +25,7 @@
 #include "pt_probes.h"
 #include "pt_medium.h"
 #include "pt_lightmap.h"
+#include "pt_emissive_tex.h"
 
 #include <rccl/rccl.h>
 
@@ -56,7 +57,7 @@ int fail(ptc_ctx* c, int code, const std::string& msg);
     if (r_ != ncclSuccess) return fail((c), PTC_E_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
   } while (0)
 
-struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution (alpha's own shadow walk included), 6 a glass resolution (the shadow walk of a frame with transparent shadows included), 7 the medium pass's kernels
+struct Span { hipEvent_t a, b; int kind; };   // kind: 0 trace_closest, 1 trace_any, 2 shade, 3 whole batch, 4 the RCCL reduce, 5 an alpha resolution (alpha's own shadow walk included), 6 a glass resolution (the shadow walk of a frame with transparent shadows included), 7 the medium pass's kernels, 8 the textured-emission pass's kernel
 
 // An array in HBM and its owner: freed when the owner goes (with the context: after ptc_destroy made the device current), or early by release()
 template <class T> struct DevBuf {
@@ -226,6 +227,21 @@ struct Medium {
   double seconds = 0.0;             // the frame's medium kernels (spans of kind 7)
 };
 
+// textured emission (pt_emissive_tex.h): `mats` is what the calls recorded, by material id (shorter than the material list: the rest has none).  `table` is the
+// committed scene's, built by the commit and placed anew by every refit and rebuild from these primitives' vertices alone — a description-only context has it too;
+// the device copies follow it (emtex_upload: ptc_frame_begin or a ray hook, every lane idle).  Nothing is allocated while the table is empty
+struct EmTex {
+  std::vector<pt_emtex_material> mats;
+  pt_emtex_table table;
+  bool dirty = false;               // the table changed since the upload
+  uint32_t n_dev = 0;               // entries in the device table; 0: no pass
+  DevBuf<pt_emtex_rec> recs;
+  DevBuf<float> cdf;
+  DevBuf<int32_t> prim_map;
+  DevBuf<unsigned long long> counters;
+  double seconds = 0.0;             // the frame's launches of the pass (spans of kind 8)
+};
+
 // display transform (pt_display.h): the parameters are a context setting; the histogram (4096 bins + the rejected count) and the state record live in HBM,
 // allocated by the first call that needs them.  Nothing here is touched by a context that never calls the display functions
 struct Display {
@@ -365,6 +381,7 @@ struct ptc_ctx {
   ptc_detail::Alpha alpha;
   ptc_detail::Glass glass;
   ptc_detail::Medium medium;
+  ptc_detail::EmTex emtex;
   int tex_linear = 0;                    // PTC_FILTER_*: texture filter of the scene being described
   int bvh_default = PTC_BVH_SAH;         // PTC_BVH_*: builder a new scene description starts with (PTC_BVH=lbvh in the environment changes it)
   int bvh_builder = PTC_BVH_SAH;         // builder of the scene being described
@@ -631,6 +648,17 @@ const char* medium_conflict(const ptc_ctx* c, int integrator);
 int medium_frame_begin(ptc_ctx* c, bool on);           // the frame's copy of the parameters, the counters allocated and cleared when it is on (every lane idle)
 int ensure_medium_queues(ptc_ctx* c);                  // every lane: a medium queue as large as its queues (grow only; waits for the work in flight first)
 inline DevMediumQ dev_medium_q(const ptc_ctx* c, int l) { DevMediumQ m = c->lanes[(size_t)l].medium.q; m.counters = c->medium.counters.p; return m; }
+
+// ---- ptc_api_emissive_tex.cpp: textured emission (pt_emissive_tex.h) ------------------------------------------------------------------------------------
+inline bool emtex_has(const ptc_ctx* c, int material) { return (size_t)material < c->emtex.mats.size() && c->emtex.mats[(size_t)material].tex >= 0; }
+void emtex_commit(ptc_ctx* c);                         // the table of the scene just committed (fixed part and placement); c->built holds its textures
+void emtex_place(ptc_ctx* c);                          // a refit or rebuild went through: geometry, areas, pmf and cdf of the description's current transforms and poses
+int emtex_upload(ptc_ctx* c);                          // the table -> device memory, when it changed (every lane idle); the counters cleared
+inline bool emtex_on(const ptc_ctx* c) { return c->emtex.n_dev > 0; }
+inline DevEmTex dev_emtex(const ptc_ctx* c) {
+  return DevEmTex{(const float4*)c->emtex.recs.p, c->emtex.cdf.p, c->emtex.prim_map.p, c->emtex.n_dev, c->emtex.table.total > 0.0f ? 1 : 0, c->emtex.counters.p};
+}
+const char* emtex_medium_conflict(const ptc_ctx* c, int integrator);      // a medium together with emission textures: the message, else nullptr
 
 // ---- ptc_api_debug.cpp: what the ray hooks of the three files share ----------------------------------------------------------------------------------
 // a device, the committed scene, idle lanes, the frame ended, lane 0's queues for n paths, the counters cleared; with DebugAlpha the alpha tables, queues and counters

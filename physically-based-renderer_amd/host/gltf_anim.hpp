@@ -43,12 +43,9 @@ public:
     insts_.clear(); meshes_.clear(); lights_.clear();
     std::vector<int> tex_id, mat_id;
     for (const Texture& t : fs.textures) { const int id = ptc_add_texture_rgba8(ctx, t.rgba.data(), t.w, t.h); if (id < 0) return id; tex_id.push_back(id); }
-    auto tex = [&](int k) { return k < 0 ? -1 : tex_id[(size_t)k]; };
     for (const Material& m : fs.materials) {
-      const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
+      const int id = add_material(ctx, m, tex_id);
       if (id < 0) return id;
-      if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
-      if (m.transmission.transmission > 0.0f) { const int rc = ptc_set_material_transmission(ctx, id, &m.transmission); if (rc < 0) return rc; }
       mat_id.push_back(id);
     }
     // primitive index (FlatScene order: mesh order, then primitive order) -> its JSON

@@ -151,6 +151,7 @@ private:
 
 // ---- flat result ------------------------------------------------------------------------------------
 struct Material { float base_color[4] = {1, 1, 1, 1}; float metallic = 1.0f, roughness = 1.0f; float emissive[3] = {0, 0, 0}; int tex_color = -1, tex_normal = -1, tex_mr = -1;      // tex_*: index into FlatScene::textures
+                  int tex_emissive = -1;      // emissiveTexture of a material whose emissive factor is not zero: `emissive` (factor x strength) then is the texture's factor (add_material)
                   int alpha_mode = PTC_ALPHA_OPAQUE; float alpha_cutoff = 0.5f;
                   // KHR_materials_transmission / _ior / _volume (ptc_set_material_transmission): transmission 0 unless the material is OPAQUE and not emissive
                   ptc_transmission_params transmission = {0.0f, 1.5f, 1, {1.0f, 1.0f, 1.0f}, 0.0f}; };   // glTF alphaMode / alphaCutoff (an emissive material stays OPAQUE: ptc_set_material_alpha's rule)
@@ -540,6 +541,8 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
       }
       if (o.alpha_mode != PTC_ALPHA_OPAQUE || o.emissive[0] != 0.0f || o.emissive[1] != 0.0f || o.emissive[2] != 0.0f) t.transmission = 0.0f;
     }
+    // emissiveTexture masks the emission (ptc_set_material_emission_texture).  The emission has won over alpha and transmission above, as it does without a texture
+    if (o.emissive[0] != 0.0f || o.emissive[1] != 0.0f || o.emissive[2] != 0.0f) o.tex_emissive = texture_of(m.get("emissiveTexture"));
     out.materials.push_back(o);
   }
   int default_material = -1;
@@ -704,6 +707,23 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
   return out;
 }
 
+// Whether add_material gives a material with an emissiveTexture its emission texture (the default), or reads it as a uniform emitter of its factor, as the loader
+// did before there were emission textures (ptc_gltf_emissive_textures, ptc_render --no-emissive-textures).  One setting per process, not thread-safe: set it before loading from several threads.
+inline bool& emissive_textures_enabled() { static bool on = true; return on; }
+
+// One material of a loaded scene through the C-ABI; tex_id: the ptc texture of every FlatScene texture.  Returns the material id or an error code.
+inline int add_material(ptc_ctx* ctx, const Material& m, const std::vector<int>& tex_id) {
+  auto tex = [&](int k) { return k < 0 ? -1 : tex_id[(size_t)k]; };
+  const bool textured = m.tex_emissive >= 0 && emissive_textures_enabled();
+  const float none[3] = {0.0f, 0.0f, 0.0f};
+  const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, textured ? none : m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
+  if (id < 0) return id;
+  if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
+  if (m.transmission.transmission > 0.0f) { const int rc = ptc_set_material_transmission(ctx, id, &m.transmission); if (rc < 0) return rc; }
+  if (textured) { const int rc = ptc_set_material_emission_texture(ctx, id, tex(m.tex_emissive), m.emissive); if (rc < 0) return rc; }
+  return id;
+}
+
 // Issue the C-ABI calls for a loaded scene (between ptc_scene_begin and ptc_scene_commit).  Returns the first error code.
 inline int upload(ptc_ctx* ctx, const FlatScene& s) {
   std::vector<int> tex_id, mat_id, mesh_id;
@@ -712,12 +732,9 @@ inline int upload(ptc_ctx* ctx, const FlatScene& s) {
     if (id < 0) return id;
     tex_id.push_back(id);
   }
-  auto tex = [&](int k) { return k < 0 ? -1 : tex_id[(size_t)k]; };
   for (const Material& m : s.materials) {
-    const int id = ptc_add_material(ctx, m.base_color, m.metallic, m.roughness, m.emissive, tex(m.tex_color), tex(m.tex_normal), tex(m.tex_mr));
+    const int id = add_material(ctx, m, tex_id);
     if (id < 0) return id;
-    if (m.alpha_mode != PTC_ALPHA_OPAQUE) { const int rc = ptc_set_material_alpha(ctx, id, m.alpha_mode, m.alpha_cutoff); if (rc < 0) return rc; }
-    if (m.transmission.transmission > 0.0f) { const int rc = ptc_set_material_transmission(ctx, id, &m.transmission); if (rc < 0) return rc; }
     mat_id.push_back(id);
   }
   for (const Primitive& p : s.primitives) {

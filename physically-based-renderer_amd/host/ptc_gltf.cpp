@@ -23,6 +23,12 @@ extern "C" long long ptc_gltf_load(ptc_ctx* ctx, const char* path, int scene_ind
   }
 }
 
+extern "C" int ptc_gltf_emissive_textures(int on) {
+  const bool was = pbr::gltf::emissive_textures_enabled();
+  if (on >= 0) pbr::gltf::emissive_textures_enabled() = on != 0;
+  return was ? 1 : 0;
+}
+
 // ---- the asset as a handle: skins, morph targets, animations (host/gltf_anim.hpp) ----
 struct ptc_gltf_asset { pbr::gltf::Asset asset; std::string err; explicit ptc_gltf_asset(const char* path) : asset(path) {} };
 

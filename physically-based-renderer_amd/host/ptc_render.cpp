@@ -4,7 +4,7 @@
 //              --out image.pfm [--png image.png] [--ppm image.ppm] [--half image.f16] [--denoise] [--denoise-iters N] [--denoise-sampled] [--guides PREFIX]
 //              [--adaptive THRESH [--min-spp N] [--spp-step N] [--adaptive-radius R] [--counts out.pfm]]
 //              [--aperture R [--blades N] [--aperture-rotation T] [--focus D | --focus-pixel X,Y]]
-//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission] [--glass-shadows]
+//              [--light point:x,y,z:r,g,b[:range]] [--light spot:x,y,z:dx,dy,dz:r,g,b:inner_deg,outer_deg[:range]] [--light sun:dx,dy,dz:r,g,b] [--no-gltf-lights] [--no-alpha] [--no-transmission] [--no-emissive-textures] [--glass-shadows]
 //              [--fog x,y,z:x,y,z:sigma_t[:albedo[:g]] | --fog scene:sigma_t[:albedo[:g]]]
 //              [--exposure EV] [--auto-exposure [--key K]] [--tonemap aces|neutral|reinhard|clamp] [--srgb]
 //              [(--probe-grid NX,NY,NZ | --probes positions.txt) --probes-out sh.pfm]
@@ -29,6 +29,8 @@
 // attenuated shadows; ptc_set_material_alpha), path integrator only; --no-alpha renders every material opaque, as the raster integrators always do.
 // --no-transmission: a --gltf scene is rendered with KHR_materials_transmission, KHR_materials_ior and KHR_materials_volume of its materials (glass and thin panes;
 // ptc_set_material_transmission), path integrator only; --no-transmission renders them as the opaque surfaces they were before.
+// --no-emissive-textures: a --gltf scene is rendered with the emissiveTexture of its materials (ptc_set_material_emission_texture, DESIGN.md §2h: the texture masks the
+// emission; path integrator only, and not with --fog); --no-emissive-textures reads such a material as a uniform emitter of its emissiveFactor, as before.
 // --glass-shadows: shadow rays pass thin-walled transmissive panes with their expected transmittance (ptc_set_glass_shadows): punctual lights, emitters
 // and the environment light what lies behind a window directly.  Off by default; with --gpus device D's setting goes to every member.
 // --fog LO:HI:SIGMA_T[:ALBEDO[:G]]: a homogeneous fog box from corner LO to corner HI (ptc_set_medium) with extinction SIGMA_T per world unit, grey
@@ -230,6 +232,7 @@ int main(int argc, char** argv) {
   bool noGltfLights = false;
   bool noAlpha = false;                      // --no-alpha: ignore the asset's alpha modes
   bool noTransmission = false;               // --no-transmission: ignore the asset's transmission extensions
+  bool noEmissiveTextures = false;           // --no-emissive-textures: ignore the asset's emissiveTexture
   bool glassShadows = false;                 // --glass-shadows: transparent shadows through thin panes
   std::string fogSpec;                       // --fog: the medium
   ptc_medium_params fog{};
@@ -258,7 +261,7 @@ int main(int argc, char** argv) {
     else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
-    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true; else if (a == "--glass-shadows") glassShadows = true;
+    else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true; else if (a == "--no-emissive-textures") noEmissiveTextures = true; else if (a == "--glass-shadows") glassShadows = true;
     else if (a == "--fog") fogSpec = next();
     else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
     else if (a == "--key") { disp.key = (float)std::atof(next()); haveKey = true; } else if (a == "--srgb") { disp.oetf = PTC_OETF_SRGB; useDisplay = true; }
@@ -390,6 +393,7 @@ int main(int argc, char** argv) {
     auto buildScene = [&](pbr::PathTraceRenderSystem& rs) {
     if (deviceBvh >= 0) rs.setDeviceBuilder(deviceBvh);
     if (!gltf.empty()) {
+      pbr::gltf::emissive_textures_enabled() = !noEmissiveTextures;
       pbr::gltf::FlatScene fs;
       if (animation >= 0) {      // the asset as a handle: targets, skins, and the pose of the animation at --time; the box that frames it is the bind pose's
         pbr::gltf::Asset asset(gltf);

@@ -32,6 +32,8 @@ def _load():
         L = C.CDLL(_LIB)
         L.ptc_gltf_load.restype = C.c_longlong
         L.ptc_gltf_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_char_p, C.c_int]
+        L.ptc_gltf_emissive_textures.restype = C.c_int
+        L.ptc_gltf_emissive_textures.argtypes = [C.c_int]
         L.ptc_gltf_open.restype = C.c_void_p
         L.ptc_gltf_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
         L.ptc_gltf_close.restype = None
@@ -109,16 +111,28 @@ class Asset:
         return self
 
 
-def load_into(pt, path: str, camera=None, scene_index: int = -1, compose_parents: bool = True, env=None):
+def emissive_textures(on=None) -> bool:
+    """ptc_gltf_emissive_textures: whether the loaders give a material with an emissiveTexture its emission texture (the default) or read it as a uniform emitter of its
+    factor.  on=None only asks.  Returns the previous setting."""
+    return bool(_load().ptc_gltf_emissive_textures(-1 if on is None else int(bool(on))))
+
+
+def load_into(pt, path: str, camera=None, scene_index: int = -1, compose_parents: bool = True, env=None, emissive_textures: bool = True):
     """scene_begin → materials/meshes/instances from the file → camera → scene_commit.
     Returns (n_triangles, bbox_lo, bbox_hi).  camera: CameraDesc, or None to frame the bounding box from +z.
-    env: optional (h, w, 3) float32 lat-long environment map (glTF has no such thing; ptc_set_env_latlong_rgb32f)."""
+    env: optional (h, w, 3) float32 lat-long environment map (glTF has no such thing; ptc_set_env_latlong_rgb32f).
+    emissive_textures=False: a material with an emissiveTexture is read as a uniform emitter of its factor (ptc_render --no-emissive-textures).  The loader's switch is
+    one per process and is set around this call: not to be used from two threads with different values at once."""
     L = _load()
     h = pt._h
     pt._ck(pt._L.ptc_scene_begin(h))
     bbox = (C.c_float * 6)()
     err = C.create_string_buffer(512)
-    n = L.ptc_gltf_load(h, os.fsencode(path), scene_index, 1 if compose_parents else 0, bbox, err, 512)
+    was = L.ptc_gltf_emissive_textures(1 if emissive_textures else 0)
+    try:
+        n = L.ptc_gltf_load(h, os.fsencode(path), scene_index, 1 if compose_parents else 0, bbox, err, 512)
+    finally:
+        L.ptc_gltf_emissive_textures(was)
     if n < 0:
         raise _ptc.PtcError(err.value.decode() or f"ptc_gltf_load failed ({n})")
     lo, hi = np.array(bbox[0:3], np.float32), np.array(bbox[3:6], np.float32)
@@ -409,6 +423,11 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
             g["pbrMetallicRoughness"]["metallicRoughnessTexture"] = {"index": int(m.tex_mr)}
         if getattr(m, "tex_normal", -1) >= 0:
             g["normalTexture"] = {"index": int(m.tex_normal)}
+        if getattr(m, "emissive_texture", -1) >= 0:      # the texture's factor goes where glTF has it: emissiveFactor x emissive_strength
+            e = [float(x) for x in getattr(m, "emissive_texture_factor", (1.0, 1.0, 1.0))]
+            strength = max(1.0, max(e))
+            g["emissiveFactor"] = [x / strength for x in e]
+            g["emissiveTexture"] = {"index": int(m.emissive_texture)}
         if strength > 1.0:
             g["extensions"] = {"KHR_materials_emissive_strength": {"emissiveStrength": strength}}
         mode = getattr(m, "alpha_mode", None)      # None: the key is left out (glTF's default, OPAQUE); any string is written as given

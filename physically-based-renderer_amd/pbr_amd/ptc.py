@@ -144,6 +144,17 @@ class PtcGlassInteraction(_Struct):
                 ("ray_eps", C.c_float), ("outcome", C.c_int), ("o_out", C.c_float * 3), ("d_out", C.c_float * 3), ("T_out", C.c_float * 3), ("F", C.c_float)]
 
 
+class PtcEmissiveTexStats(_Struct):
+    _fields_ = [("entries", C.c_uint64), ("hit_additions", C.c_uint64), ("shadow_records", C.c_uint64), ("seconds_emissive_tex", C.c_double)]
+
+
+class PtcEmissiveTexSample(_Struct):
+    _fields_ = [("P", C.c_float * 3), ("r1", C.c_float), ("r2", C.c_float), ("hit_u", C.c_float), ("hit_v", C.c_float), ("bounce", C.c_uint32),
+                ("prev_pdf", C.c_float), ("hit_t", C.c_float), ("hit_cos", C.c_float), ("ok", C.c_int), ("y", C.c_float * 3), ("wi", C.c_float * 3),
+                ("pl", C.c_float), ("Le", C.c_float * 3), ("hit_Le", C.c_float * 3), ("hit_weight", C.c_float)]
+    _unknown_ = "unknown emissive-texture sample field {}"
+
+
 class PtcGlassShadowStats(_Struct):
     _fields_ = [("walked", C.c_uint64), ("passes", C.c_uint64), ("visible", C.c_uint64), ("exhausted", C.c_uint64)]
 
@@ -465,7 +476,22 @@ def _lightmap_prototypes():
     }
 
 
+def _emissive_tex_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_emissive_tex.h declares, in the header's order; exported under ptcx_ like ptc_glass.h's."""
+    i, u32 = C.c_int, C.c_uint32
+    vp, ip, fp, u8p, u32p, i32p = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    return {
+        "ptc_set_material_emission_texture": (i, [vp, i, i, fp]),
+        "ptc_get_material_emission_texture": (i, [vp, i, ip, fp]),
+        "ptc_get_emissive_tex_stats": (i, [vp, C.POINTER(PtcEmissiveTexStats)]),
+        "ptc_debug_get_emissive_tex_table": (i, [vp, u32p, fp, fp, u32p, i32p, fp]),
+        "ptc_debug_emissive_tex_sample": (i, [fp, u8p, i, i, i, C.POINTER(PtcEmissiveTexSample)]),
+        "ptc_debug_emissive_tex_step": (i, [vp, fp, fp, fp, fp, u32p, u32, u32, u32, fp, u8p, fp]),
+    }
+
+
 _PROTOTYPES = _prototypes()
+_EMISSIVE_TEX_PROTOTYPES = _emissive_tex_prototypes()
 _LIGHTMAP_PROTOTYPES = _lightmap_prototypes()
 _MEDIUM_PROTOTYPES = _medium_prototypes()
 _ALPHA_PROTOTYPES = _alpha_prototypes()
@@ -495,7 +521,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()) + list(_LIGHTMAP_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()) + list(_LIGHTMAP_PROTOTYPES.items()) + list(_EMISSIVE_TEX_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -634,6 +660,19 @@ def glass_interact(params, **fields):
     rc = load_library().ptc_debug_glass_interact(C.byref(params), C.byref(io))
     if rc < 0:
         raise PtcError("glass_interact: bad argument")
+    return io.as_dict()
+
+
+def emissive_tex_sample(entry, texture, linear=False, **fields):
+    """ptc_debug_emissive_tex_sample: the host's evaluation of csrc/pt_emissive_tex.h for one table entry (28 floats) over one (h, w, 4) uint8 texture.  fields: P, r1,
+    r2 of the sample; hit_u, hit_v, bounce, prev_pdf, hit_t, hit_cos of the hit side.  Returns the struct as a dict (ok, y, wi, pl, Le, hit_Le, hit_weight, ..)."""
+    e = np.ascontiguousarray(entry, np.float32).reshape(28)
+    t = np.ascontiguousarray(texture, np.uint8)
+    assert t.ndim == 3 and t.shape[2] == 4, "the texture is (h, w, 4) uint8"
+    io = PtcEmissiveTexSample().update(**fields)
+    rc = load_library().ptc_debug_emissive_tex_sample(_ptr(e), _ptr(t), t.shape[1], t.shape[0], 1 if linear else 0, C.byref(io))
+    if rc < 0:
+        raise PtcError("emissive_tex_sample: bad argument")
     return io.as_dict()
 
 
@@ -782,6 +821,8 @@ class PathTracer:
                 self.set_material_alpha(mid, m.alpha_mode, getattr(m, "alpha_cutoff", 0.5))
             if getattr(m, "transmission", 0.0) > 0.0:
                 self.set_material_transmission(mid, _material_transmission(m))
+            if getattr(m, "emissive_texture", -1) >= 0:
+                self.set_material_emission_texture(mid, m.emissive_texture, getattr(m, "emissive_texture_factor", (1.0, 1.0, 1.0)))
         for me in desc.meshes:
             v = np.ascontiguousarray(me.vertices)
             i = np.ascontiguousarray(me.indices, np.uint32)
@@ -985,6 +1026,41 @@ class PathTracer:
         wi, Le, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
         self._ck(self._L.ptc_debug_medium_env(self._h, ap, bp, dp, n, _ptr(wi), _ptr(Le), _ptr(pdf)))
         return wi, Le, pdf
+
+    # ---- textured emission (csrc/pt_emissive_tex.h) -----------------------------------------------------------
+    def set_material_emission_texture(self, material, texture, factor=(1.0, 1.0, 1.0)):
+        """ptc_set_material_emission_texture, between add_material and the commit: the surfaces of `material` emit factor x texel of `texture` (texture -1 removes it)."""
+        self._ck(self._L.ptc_set_material_emission_texture(self._h, int(material), int(texture), _f(np.asarray(factor, np.float32).reshape(3))[1]))
+        return self
+
+    def get_material_emission_texture(self, material):
+        """(texture id or -1, factor (3,) float32)."""
+        tex, f = C.c_int(-1), np.zeros(3, np.float32)
+        self._ck(self._L.ptc_get_material_emission_texture(self._h, int(material), C.byref(tex), _ptr(f)))
+        return int(tex.value), f
+
+    def emissive_tex_stats(self):
+        return self._get(self._L.ptc_get_emissive_tex_stats, PtcEmissiveTexStats)
+
+    def emissive_tex_table(self):
+        """ptc_debug_get_emissive_tex_table: (records (n, 28) float32 — word 11 holds the texture id's int bits —, cdf (n,), prim_map (n_prims,) int32, total)."""
+        n, npr, total = C.c_uint32(0), C.c_uint32(0), C.c_float(0)
+        self._ck(self._L.ptc_debug_get_emissive_tex_table(self._h, C.byref(n), None, None, C.byref(npr), None, C.byref(total)))
+        recs, cdf, pm = np.zeros((n.value, 28), np.float32), np.zeros(n.value, np.float32), np.zeros(npr.value, np.int32)
+        self._ck(self._L.ptc_debug_get_emissive_tex_table(self._h, None, _ptr(recs), _ptr(cdf), None, _ptr(pm), None))
+        return recs, cdf, pm, float(total.value)
+
+    def emissive_tex_step(self, origins, dirs, throughput, prev_pdf, keys, bounce, max_bounces, lpath=None):
+        """ptc_debug_emissive_tex_step: explicit rays through k_trace_closest and one launch of k_shade_emissive_tex: (lpath (n, 3) — the paths' radiance `lpath`, zero
+        by default, with what the hit side added —, shadow valid (n,) bool, shadow records (n, 10): origin, direction, tmax, contribution), by path id."""
+        (o, op), (d, dp), (t, tp), (pp, ppp) = _f(origins), _f(dirs), _f(throughput), _f(prev_pdf)
+        k = np.ascontiguousarray(keys, np.uint32)
+        n = k.size
+        assert o.size == n * 3 and d.size == n * 3 and t.size == n * 3 and pp.size == n
+        lp = np.zeros((n, 3), np.float32) if lpath is None else np.array(lpath, np.float32, order="C").reshape(n, 3)
+        valid, sh = np.zeros(n, np.uint8), np.zeros((n, 10), np.float32)
+        self._ck(self._L.ptc_debug_emissive_tex_step(self._h, op, dp, tp, ppp, _ptr(k), n, int(bounce), int(max_bounces), _ptr(lp), _ptr(valid), _ptr(sh)))
+        return lp, valid.astype(bool), sh
 
     # ---- transparent shadows through thin glass (csrc/pt_glass_shadow.h) --------------------------------------
     def set_glass_shadows(self, on=True):

@@ -47,6 +47,8 @@ class Material:
     thin_walled: bool = True        # glTF's "no volume"; False: a solid (KHR_materials_volume)
     attenuation_color: tuple = (1.0, 1.0, 1.0)
     attenuation_distance: float = 0.0   # 0: no attenuation
+    emissive_texture: int = -1          # glTF emissiveTexture (ptc_set_material_emission_texture): the surface emits emissive_texture_factor x texel; `emissive` stays 0
+    emissive_texture_factor: tuple = (1.0, 1.0, 1.0)   # emissiveFactor x KHR_materials_emissive_strength of such a material
 
 
 @dataclasses.dataclass
