@@ -631,7 +631,69 @@ def fog_box(sigma_t: float = 0.7, albedo=(0.9, 0.9, 0.9), g: float = 0.0, slit: 
     return d
 
 
+def passes_surface(top: str = "normal") -> SceneDesc:
+    """Everything that may share a frame with alpha and glass (tests/test_gpu_pass_policies.py), 30 triangles, seen from above through a camera that looks down:
+    a Lambert floor at y = 0 (primitives 0-1), a plain emitter facing down at y = 2.4 (2-3), two floor patches at y = 0.01 with colour, normal and metal-rough
+    textures — one interleaved set, one whose normal map has another size — (4-7), a quad with an emission texture facing down at y = 2.2 (8-9), a BLEND sheet at
+    y = 0.6 (10-11), a solid glass slab from y = 1 to 1.3 (12-23) and a 4 x 8 environment.  Added LAST, so that every other primitive keeps its id without them, and
+    ABOVE everything else: a clear thin pane at y = 2.8, a MASK sheet with a checkerboard alpha texture at y = 3 and a tinted thin pane at y = 3.2 (24-29).
+    top = "invisible": the MASK sheet's alpha texture is all zero and both panes are the invisible pane (ior 1, white, transmission 1); top = "none": the three are
+    left out.  A ray from below that passes them meets nothing afterwards, whose radiance depends on its direction and throughput alone, and the scene's largest
+    extent — the floor's, which sets the ray epsilon — does not depend on them: a frame without a camera (probes, a lightmap) of the invisible variant computes
+    the bits of the variant without."""
+    assert top in ("normal", "invisible", "none")
+    T = _shade_textures()
+    yy, xx = np.mgrid[0:8, 0:8]
+    rgb = np.stack([(37 * xx + 11) % 200 + 40, (53 * yy + 29) % 200 + 40, (17 * (xx + yy) + 71) % 200 + 40], -1)
+    blend = np.concatenate([rgb, np.asarray([0, 64, 128, 192, 255])[(xx + 2 * yy) % 5][..., None]], -1).astype(np.uint8)
+    check = np.where(((xx // 2 + yy // 2) % 2) == 0, 255, 0) if top != "invisible" else np.zeros((8, 8), np.int64)
+    mask = np.concatenate([rgb[..., ::-1], check[..., None]], -1).astype(np.uint8)
+    glow = np.array([[[0, 0, 0, 255], [255, 255, 255, 255], [255, 128, 64, 255]], [[64, 128, 255, 255], [0, 0, 0, 255], [200, 200, 200, 255]]], np.uint8)
+    textures = T + [blend, mask, glow]
+    invisible = top == "invisible"
+    mats = [Material((0.7, 0.7, 0.7, 1.0), 0.0, 1.0),
+            Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, (15.0, 15.0, 15.0)),
+            Material((1.0, 0.9, 0.8, 1.0), 1.0, 0.9, (0, 0, 0), 0, 1, 2),
+            Material((0.8, 0.9, 1.0, 1.0), 0.8, 1.0, (0, 0, 0), 3, 4, 5),
+            Material((0.0, 0.0, 0.0, 1.0), 0.0, 1.0, emissive_texture=8, emissive_texture_factor=(6.0, 4.0, 2.0)),
+            Material((1.0, 1.0, 1.0, 1.0), 0.0, 1.0, (0, 0, 0), 6, -1, -1, "blend", 0.5),
+            Material((1.0, 1.0, 1.0, 1.0), 0.0, 0.2, (0, 0, 0), -1, -1, -1, "opaque", 0.5, 1.0, 1.5, False),
+            Material((1.0, 1.0, 1.0, 1.0), 0.0, 1.0, (0, 0, 0), 7, -1, -1, "mask", 0.5),
+            Material((1.0, 1.0, 1.0, 1.0), 0.0, 0.2, (0, 0, 0), -1, -1, -1, "opaque", 0.5, 1.0, 1.0 if invisible else 1.5, True),
+            Material(((1.0, 1.0, 1.0) if invisible else (0.9, 0.7, 0.5)) + (1.0,), 0.0, 0.2, (0, 0, 0), -1, -1, -1, "opaque", 0.5, 1.0, 1.0 if invisible else 1.5, True)]
+
+    def flat(x0, x1, z0, z1, y):      # normal +y
+        return _quad((x0, y, z1), (x1, y, z1), (x1, y, z0), (x0, y, z0))
+
+    def down(x0, x1, z0, z1, y):      # normal -y
+        return _quad((x0, y, z0), (x1, y, z0), (x1, y, z1), (x0, y, z1))
+
+    q = [(flat(-4, 4, -4, 4, 0.0), 0), (down(2.2, 3.2, -0.5, 0.5, 2.4), 1), (flat(-3.5, -2.0, 1.5, 3.5, 0.01), 2), (flat(2.0, 3.5, -3.5, -1.5, 0.01), 3),
+         (down(-3.2, -2.0, -0.6, 0.6, 2.2), 4), (flat(-1.5, 1.5, -1.5, 1.5, 0.6), 5)]
+    a, y0, y1 = 1.2, 1.0, 1.3
+    q += [(flat(-a, a, -a, a, y1), 6), (down(-a, a, -a, a, y0), 6),
+          (_quad((-a, y0, a), (a, y0, a), (a, y1, a), (-a, y1, a)), 6), (_quad((a, y0, -a), (-a, y0, -a), (-a, y1, -a), (a, y1, -a)), 6),
+          (_quad((a, y0, a), (a, y0, -a), (a, y1, -a), (a, y1, a)), 6), (_quad((-a, y0, -a), (-a, y0, a), (-a, y1, a), (-a, y1, -a)), 6)]
+    if top != "none":
+        q += [(flat(-2, 2, -2, 2, 2.8), 8), (flat(-2, 2, -2, 2, 3.0), 7), (flat(-2, 2, -2, 2, 3.2), 9)]
+    meshes = [MeshDesc(v, i, m) for (v, i), m in q]
+    inst = [InstanceDesc(k, (0.0, 0.0, 0.0), _ID_Q, (1.0, 1.0, 1.0)) for k in range(len(meshes))]
+    cam = CameraDesc((1.0, 9.0, 2.5), (0.0, 0.0, 0.0), math.radians(50.0), 1.5)
+    d = SceneDesc(mats, meshes, inst, cam, "passes_surface")
+    d.textures = textures
+    d.env = np.random.default_rng(59).uniform(0.2, 1.0, (4, 8, 3)).astype(np.float32)
+    return d
+
+
+def passes_volume() -> SceneDesc:
+    """The medium's side of the pass tests: fog_box with its emitter under a 4 x 8 environment.  The tests add a sun, a point light and a lens.  8 triangles."""
+    d = fog_box()
+    d.name = "passes_volume"
+    d.env = np.random.default_rng(61).uniform(0.1, 0.6, (4, 8, 3)).astype(np.float32)
+    return d
+
+
 def by_name(name: str, **kw) -> SceneDesc:
-    return {"cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
+    return {"passes_surface": passes_surface, "passes_volume": passes_volume, "cornell": cornell_box, "sphere10k": sphere_scene, "atrium": atrium, "two_tris_sphere": two_triangles_and_sphere,
             "textured_objects": textured_objects, "textured_atrium": textured_atrium, "alpha_layers": alpha_layers, "glass_slab": glass_slab, "glass_panes": glass_panes, "glass_ball": glass_ball,
             "shade_lobes": shade_lobes, "shade_textured": shade_textured, "shade_sky": shade_sky, "fog_box": fog_box}[name](**kw)
