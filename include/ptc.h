@@ -798,4 +798,5 @@ int ptc_debug_refit_host_parts(ptc_ctx*, uint64_t out[8]);
 #include "ptc_medium.h"   /* a homogeneous participating medium: likewise */
 #include "ptc_lightmap.h"   /* lightmaps, irradiance over an instance's UV atlas: likewise */
 #include "ptc_emissive_tex.h"   /* textured emission, glTF emissiveTexture as a light set of its own: likewise */
+#include "ptc_camera.h"   /* camera models, a camera-to-world matrix with a perspective, orthographic or equirectangular projection: likewise */
 #endif /* PTC_H */

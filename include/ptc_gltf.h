@@ -11,8 +11,8 @@
  * KHR_lights_punctual: every light a node of the scene references is added with ptc_add_light, in the order the traversal first reaches the nodes — position = the
  * node's origin, direction = its -Z axis after the composed transform, intensity = color x intensity (candela for point and spot, lux for directional), range,
  * and the spot's cone angles as cosines; ptc_clear_lights afterwards drops them.
- * Call between ptc_scene_begin and ptc_scene_commit; the camera stays the caller's (the reference ignores glTF
- * cameras too and injects its own, Asset.cpp:262-265).  Host-only: works on a PTC_DEVICE_NONE context.
+ * Call between ptc_scene_begin and ptc_scene_commit; the camera stays the caller's: ptc_gltf_load sets none.  The asset's own cameras are read for the caller
+ * to apply (ptc_gltf_cameras, ptc_gltf_asset_camera below -> ptc_set_camera_ex).  Host-only: works on a PTC_DEVICE_NONE context.
  */
 #ifndef PTC_GLTF_H
 #define PTC_GLTF_H
@@ -58,6 +58,19 @@ int ptc_gltf_asset_animations(const ptc_gltf_asset* asset);
 double ptc_gltf_asset_duration(const ptc_gltf_asset* asset, int animation);
 int ptc_gltf_asset_pose(ptc_gltf_asset* asset, ptc_ctx* ctx, int animation, double time_seconds);
 const char* ptc_gltf_asset_last_error(const ptc_gltf_asset* asset);
+
+/* glTF cameras.  A camera node is a node of the scene with a `camera`; they are counted in the order the scene traversal first reaches them (the lights' order).
+ * The ptc_camera_params of one (ptc_camera.h) is ready for ptc_set_camera_ex: camera_to_world = the node's world matrix (a scale inherited from parents is
+ * accepted there), PERSPECTIVE with the camera's yfov and aspect = its aspectRatio when it has one, else frame_aspect; or ORTHOGRAPHIC with its xmag, ymag.  znear
+ * and zfar are not applied: the path integrator clips nowhere.
+ *   ptc_gltf_asset_cameras   the number of camera nodes of the scene ptc_gltf_asset_load read (before it: of the asset's default scene)
+ *   ptc_gltf_asset_camera    camera node `index`; animation < 0: the rest pose, otherwise the node's world matrix is the one ptc_gltf_asset_pose gives it at
+ *                            time_seconds, so a flythrough animates.  Needs no context.  PTC_E_ARG: no such camera or animation
+ *   ptc_gltf_cameras         the stateless loader's: the rest-pose cameras of ptc_gltf_load(path, scene_index, compose_parents), the first `capacity` of them
+ *                            into out (may be NULL with capacity 0).  Returns their number */
+int ptc_gltf_asset_cameras(const ptc_gltf_asset* asset);
+int ptc_gltf_asset_camera(ptc_gltf_asset* asset, int index, int animation, double time_seconds, float frame_aspect, ptc_camera_params* out);
+int ptc_gltf_cameras(const char* path, int scene_index, int compose_parents, float frame_aspect, ptc_camera_params* out, int capacity, char* err, int err_len);
 void ptc_gltf_close(ptc_gltf_asset* asset);
 
 /* PNG file image (any colour type / bit depth / interlacing) → w*h*4 bytes RGBA8, row 0 on top; the decoder the loader

@@ -8,6 +8,7 @@ struct DenoiseArgs {
   float sigma_l, sigma_n, sigma_p;
   int demodulate;
   float pix;                    // 2 tan(fov_y / 2) / h: the world size of a pixel at unit distance
+  int pix_flat;                 // 1: pix is the world size of a pixel at every depth (an orthographic camera, pt_camera.h): the plane-distance weight leaves Z out
   const float4* radiance;       // (C.rgb, alpha)
   GuideBufs g;
 };

@@ -4,7 +4,7 @@
 // Only class-1 pixels are filtered; the others pass through bit for bit and never contribute to a class-1 pixel.
 //   prepare     D = C / max(A, 1e-3) (or C), L = lum(D); Var = normal-weighted variance of L over the same-class taps of the 7x7 window
 //   iteration i step s = 2^i; S = sqrt(3x3 binomial blur of Var); 25 taps q = p + s (dx, dy) of the same class, weight
-//               B3[dx] B3[dy] · max(0, Np·Nq)^sigma_n · exp(-|Np·(Pq - Pp)| / (sigma_p Zp pix s |(dx, dy)|)) · exp(-|Lq - Lp| / (sigma_l S + 1e-6));
+//               B3[dx] B3[dy] · max(0, Np·Nq)^sigma_n · exp(-|Np·(Pq - Pp)| / (sigma_p Zp pix s |(dx, dy)|); without Zp under an orthographic camera, a.pix_flat) · exp(-|Lq - Lp| / (sigma_l S + 1e-6));
 //               D' = sum w Dq / sum w, Var' = sum w^2 Varq / (sum w)^2
 //   the last iteration writes D' · max(A, 1e-3) with the radiance's alpha (re-modulation fused)
 // Colour and variance travel as one float4, so a tap is three 16-byte loads: (D, Var), (N, Z), (P, K) — 48 B read + 16 B written per pixel and iteration when
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(DN_BW * DN_BH) void k_dn_atrous(DenoiseArgs a, int 
   const float sd = sqrtf(fmaxf(gv / gw, 0.0f));
   const float lp = dn_lum(cvp.x, cvp.y, cvp.z);
   const float den_l = a.sigma_l * sd + DN_EPS_L;
-  const float den_p = a.sigma_p * nzp.w * a.pix;
+  const float den_p = a.pix_flat ? a.sigma_p * a.pix : a.sigma_p * nzp.w * a.pix;
   float ax = 0.0f, ay = 0.0f, az = 0.0f, vacc = 0.0f, wsum = 0.0f;
 #pragma unroll
   for (int dy = -2; dy <= 2; ++dy) {

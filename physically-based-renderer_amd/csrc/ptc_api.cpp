@@ -76,6 +76,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
   } else {
     if (c->lightmap.on) pt_launch_raygen_texel(st, c->lightmap.texels.p, c->fr.n_owned, c->lightmap.base, c->fr.seed_hash, q, first_sample, n_samples);      // a lightmap frame (pt_lightmap.hip): oriented rays from the texels
     else if (c->probes.on) pt_launch_raygen_probe(st, c->probes.pos.p, c->fr.n_owned, c->probes.base, c->fr.seed_hash, q, first_sample, n_samples);      // a probe frame (pt_probes.hip) has no camera and no lens
+    else if (cam_projection(c) != PTC_PROJ_PERSPECTIVE) pt_launch_raygen_proj(st, c->cam, cam_proj(c), c->fr, q, first_sample, n_samples);      // an orthographic or equirectangular camera (pt_camera.hip); it has no lens
     else if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(st, c->cam, c->lens, c->fr, q, first_sample, n_samples);      // the thin lens (pt_lens.hip); the raster integrators above ignore it
     else pt_launch_raygen(st, c->cam, c->fr, q, first_sample, n_samples, false);
     const bool shadows = sc.n_lights > 0 || sc.env_ok;
@@ -347,6 +348,7 @@ int frame_begin(ptc_ctx* c, int w, int h, int spp_total, uint64_t seed, int max_
   const bool lightmap = entries && !probe_pos;
   if (c) { if (const char* why = medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }
   if (c) { if (const char* why = emtex_medium_conflict(c, integrator)) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }      // before the device: a description-only context can tell
+  if (c && !entries && is_raster(integrator)) { const std::string why = projection_refusal(c, "frame_begin", "a raster integrator"); if (!why.empty()) { c->in_frame = false; return fail(c, PTC_E_STATE, why); } }
   { int rd = need_device(c); if (rd) return rd; }
   c->in_frame = false; c->pending = 0; c->adaptive.on = false; c->adaptive.cov_on = false; c->adaptive.cov_resolved = false; c->adaptive.sv_valid = false; drop_guides(c);      // whatever happens below, the previous frame is over
   const std::string who = entries ? entries->who : "frame_begin";      // the entry the caller used, for ptc_last_error

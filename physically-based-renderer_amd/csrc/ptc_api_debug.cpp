@@ -296,11 +296,13 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
   if (c->device < 0) {      // the host evaluation of pt_lens.h
     if (!c->have_cam) return fail(c, PTC_E_STATE, "debug_camera_rays: no camera (ptc_set_camera)");
     DevCamera cam;
-    ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, cam);
+    make_camera_in_force(c, cam);
+    const PtCamProj proj = cam_proj(c);
     for (uint32_t p = 0; p < n; ++p) {
       uint32_t key, j, s;
       pt_path_entry(PT_ORDER_SAMPLE, p, n_pixels, n_samples, j, s);      // the output's order, whatever order the context's frames use
-      pt_lens_ray(cam, c->lens, w, h, seed_hash, pixels[j], first_sample + s, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);
+      if (proj.projection != PTC_PROJ_PERSPECTIVE) pt_proj_ray(cam, proj, w, h, seed_hash, pixels[j], first_sample + s, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);      // pt_camera.h
+      else pt_lens_ray(cam, c->lens, w, h, seed_hash, pixels[j], first_sample + s, origins + (size_t)p * 3, dirs + (size_t)p * 3, key);
     }
     return PTC_OK;
   }
@@ -315,7 +317,8 @@ int ptc_debug_camera_rays(ptc_ctx* c, int w, int h, uint64_t seed, uint32_t firs
     fr.w = w; fr.h = h; fr.seed_hash = seed_hash; fr.max_bounces = 0; fr.n_owned = n_pixels; fr.owned = list.p;
     fr.path_order = c->path_order;      // the kernels run as a camera frame runs them; the read-back below re-maps the slots to the output's sample-major order
     const DevQueues q = batch_queues(c, 0, n);
-    if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(ln.stream, c->cam, c->lens, fr, q, first_sample, n_samples);      // run_batch's choice
+    if (cam_projection(c) != PTC_PROJ_PERSPECTIVE) pt_launch_raygen_proj(ln.stream, c->cam, cam_proj(c), fr, q, first_sample, n_samples);      // run_batch's choice
+    else if (c->lens.aperture_radius > 0.0f) pt_launch_raygen_lens(ln.stream, c->cam, c->lens, fr, q, first_sample, n_samples);
     else pt_launch_raygen(ln.stream, c->cam, fr, q, first_sample, n_samples, false);
     e = hipGetLastError();
   }

@@ -51,6 +51,7 @@ int ptc_frame_guides(ptc_ctx* c) {
   hipStream_t st = ln.stream;
   const DevScene sc = lane_scene(c, 0);
   const GuideBufs g = c->guides.dev();
+  const PtCamProj proj = cam_proj(c);
   const uint32_t chunk = ln.q.cap < n ? ln.q.cap : n;
   if ((rc = c->guides.timer.begin(c, st))) return rc;
   for (uint32_t first = 0; first < n; first += chunk) {
@@ -59,10 +60,12 @@ int ptc_frame_guides(ptc_ctx* c) {
     q.stats = c->guides.stats.p;            // the frame's counters do not see the guide rays
     const LaunchCfg cfg = batch_cfg(c, m);
     pt_launch_set_counts(st, cfg, q, m, 0);
-    pt_launch_raygen_guides(st, c->cam, c->fr.w, c->fr.h, first, m, q);
+    if (proj.projection != PTC_PROJ_PERSPECTIVE) pt_launch_raygen_guides_proj(st, c->cam, proj, c->fr.w, c->fr.h, first, m, q);      // pt_camera.hip
+    else pt_launch_raygen_guides(st, c->cam, c->fr.w, c->fr.h, first, m, q);
     pt_launch_trace_closest(st, cfg, sc, q, 0, false);
     if (alpha_on(c)) alpha_resolve_closest(c, 0, st, cfg, sc, q, 0, 0, PT_ALPHA_FORM_GUIDE, nullptr);      // the first COVERING surface, decided without random numbers
     pt_launch_guides(st, sc, c->cam, c->fr.w, c->fr.h, first, m, q, g);
+    if (proj.projection != PTC_PROJ_PERSPECTIVE) pt_launch_guides_pos_proj(st, c->cam, proj, c->fr.w, c->fr.h, first, m, g.normal_depth, g.pos_class);      // k_guides took the ray for a perspective one in this field alone
   }
   if ((rc = c->guides.timer.end(c, st))) return rc;
   HIP_TRY(c, hipGetLastError());
@@ -90,6 +93,7 @@ int ptc_read_guide_hit(ptc_ctx* c, int32_t* prim, float* uv) {
 }
 
 int ptc_focus_distance_at_pixel(ptc_ctx* c, int px, int py, float* out) {
+  if (c) { const std::string why = projection_refusal(c, "focus_distance_at_pixel", "the view depth of a pixel"); if (!why.empty()) return fail(c, PTC_E_STATE, why); }      // before the device: a description-only context can tell
   { int rd = need_device(c); if (rd) return rd; }
   if (!out) return fail(c, PTC_E_ARG, "focus_distance_at_pixel: null pointer");
   if (entry_frame(c)) return fail(c, PTC_E_STATE, "focus_distance_at_pixel: a probe or lightmap frame has no camera image");
@@ -116,6 +120,7 @@ namespace {
 // accumulated: the input is the accumulated image of the frame's ptc_temporal_accumulate, i.e. D_new of the new history (demodulated already) with the temporal variance
 // sampled: the input is the radiance, demodulated by k_ad_sampled_variance, with the variance of the frame's own samples (§8d) where a pixel has four or more
 int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated, bool sampled = false) {
+  if (c && accumulated) { const std::string why = projection_refusal(c, "denoise_accumulated", "the accumulated image"); if (!why.empty()) return fail(c, PTC_E_STATE, why); }      // follows ptc_temporal_accumulate's refusal
   { int rd = need_device(c); if (rd) return rd; }
   if (entry_frame(c)) return fail(c, PTC_E_STATE, "denoise: a probe or lightmap frame has no image to denoise");
   const ptc_denoise_params p = with_defaults(params, ptc_denoise_default_params);
@@ -142,7 +147,8 @@ int denoise_image(ptc_ctx* c, const ptc_denoise_params* params, bool accumulated
   else {
     DenoiseArgs a{};
     a.w = c->rad_w; a.h = c->rad_h; a.sigma_l = p.sigma_l; a.sigma_n = p.sigma_n; a.sigma_p = p.sigma_p; a.demodulate = p.demodulate ? 1 : 0;
-    a.pix = (2.0f * c->cam.sy) / (float)c->rad_h;
+    if (cam_projection(c) == PTC_PROJ_PERSPECTIVE) a.pix = (2.0f * c->cam.sy) / (float)c->rad_h;
+    else a.pix = pt_proj_footprint(c->cam, cam_proj(c), c->rad_h, a.pix_flat);      // pt_camera.h: pi / h, or 2 ymag / h at every depth
     a.radiance = c->radiance.p;
     a.g = c->guides.dev();
     if (sampled) {
@@ -185,6 +191,7 @@ void ptc_temporal_default_params(ptc_temporal_params* p) {
 }
 
 int ptc_temporal_accumulate(ptc_ctx* c, const ptc_temporal_params* params) {
+  if (c) { const std::string why = projection_refusal(c, "temporal_accumulate", "the reprojection of the history"); if (!why.empty()) return fail(c, PTC_E_STATE, why); }      // it needs the inverse projection; before the device: a description-only context can tell
   { int rd = need_device(c); if (rd) return rd; }
   if (entry_frame(c)) return fail(c, PTC_E_STATE, "temporal_accumulate: a probe or lightmap frame has no image to accumulate");
   const ptc_temporal_params p = with_defaults(params, ptc_temporal_default_params);

@@ -554,6 +554,7 @@ void copy_description(ptc_ctx* c, const ptc_ctx* c0) {
   for (size_t m = 0; m < c->poses.size(); ++m) if (c->poses[m].active()) c->poses[m].host_fresh = c->poses[m].emis_fresh = c0->poses[m].host_fresh;
   std::memcpy(c->cam_pos, c0->cam_pos, 12); std::memcpy(c->cam_target, c0->cam_target, 12); c->cam_fov = c0->cam_fov; c->cam_aspect = c0->cam_aspect;
   c->lens = c0->lens;
+  take_camera_ex(c, c0);      // the extended camera goes wherever the camera goes
   c->alpha.mode = c0->alpha.mode; c->alpha.cutoff = c0->alpha.cutoff;      // every member builds context 0's alpha tables
   c->glass.params = c0->glass.params; c->glass.shadows = c0->glass.shadows;      // and its glass tables, with its choice of transparent shadows
   c->emtex.mats = c0->emtex.mats;      // and its emission textures
@@ -587,7 +588,7 @@ const char* lens_params_error(const ptc_lens_params& p) {
 // skeleton: c->built is ptc_build_skeleton's — the tables are uploaded, the shading records allocated and zeroed, there is no tree yet: device_commit goes on from here.
 int commit_upload(ptc_ctx* c, std::chrono::steady_clock::time_point t0, Upload what, bool skeleton) {
   if (what == Upload::NewScene) drop_history(c);      // every commit passes here — ptc_scene_commit on the host or on the device, each context of ptc_group_scene_commit
-  ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
+  make_camera_in_force(c, c->cam);      // the stored look-at, or the extended camera (ptc_api_camera.cpp)
   c->in_frame = false; c->pending = 0; drop_guides(c);
   c->committed = false;
   release_scene(c);
@@ -685,6 +686,7 @@ int ptc_scene_begin(ptc_ctx* c) {
   c->poses.clear();
   c->have_cam = false; c->committed = false; c->in_frame = false; c->pending = 0; drop_guides(c);
   ptc_lens_default_params(&c->lens);
+  c->cam_ex_set = false; c->cam_ex = ptc_camera_params{};      // the extended camera goes with the camera
   c->lights.dirty = c->lights.dirty || !c->lights.list.empty(); c->lights.list.clear();
   c->alpha.mode.clear(); c->alpha.cutoff.clear(); c->alpha.dirty = true; c->alpha.n_prims = 0;      // every material of the next description starts OPAQUE; max_layers stays
   c->glass.params.clear(); c->glass.dirty = true; c->glass.n_prims = 0; c->glass.n_thin = 0;      // and without transmission; max_interactions and shadows stay
@@ -899,6 +901,7 @@ int ptc_set_camera(ptc_ctx* c, const float pos[3], const float target[3], float 
   if (!pos || !target) return fail(c, PTC_E_ARG, "set_camera: null pointer");
   std::memcpy(c->cam_pos, pos, 12); std::memcpy(c->cam_target, target, 12); c->cam_fov = fov_y; c->cam_aspect = aspect;
   c->have_cam = true;
+  c->cam_ex_set = false; c->cam_ex = ptc_camera_params{};      // ptc_set_camera and ptc_set_camera_ex replace one another
   c->guides.valid = false;      // the guides are those of the camera they were traced from
   if (c->committed) ptc_make_camera(c->cam_pos, c->cam_target, c->cam_fov, c->cam_aspect, c->cam);
   return PTC_OK;

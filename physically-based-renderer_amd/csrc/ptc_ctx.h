@@ -26,6 +26,7 @@
 #include "pt_medium.h"
 #include "pt_lightmap.h"
 #include "pt_emissive_tex.h"
+#include "pt_camera.h"
 
 #include <rccl/rccl.h>
 
@@ -376,6 +377,8 @@ struct ptc_ctx {
   HostEnv env;
   float cam_pos[3]{}, cam_target[3]{}, cam_fov = 0, cam_aspect = 1;
   bool have_cam = false;
+  bool cam_ex_set = false;            // the camera in force is ptc_set_camera_ex's (include/ptc_camera.h): its matrix and projection instead of the look-at above
+  ptc_camera_params cam_ex{};         // as it was set; ptc_set_camera and ptc_scene_begin drop it
   ptc_lens_params lens{0.0f, 1.0f, 0, 0.0f};   // the camera's lens (ptc_set_camera_lens): kept across ptc_set_camera, reset by ptc_scene_begin; R = 0: the pinhole, k_raygen
   ptc_detail::Lights lights;
   ptc_detail::Alpha alpha;
@@ -648,6 +651,15 @@ const char* medium_conflict(const ptc_ctx* c, int integrator);
 int medium_frame_begin(ptc_ctx* c, bool on);           // the frame's copy of the parameters, the counters allocated and cleared when it is on (every lane idle)
 int ensure_medium_queues(ptc_ctx* c);                  // every lane: a medium queue as large as its queues (grow only; waits for the work in flight first)
 inline DevMediumQ dev_medium_q(const ptc_ctx* c, int l) { DevMediumQ m = c->lanes[(size_t)l].medium.q; m.counters = c->medium.counters.p; return m; }
+
+// ---- ptc_api_camera.cpp: camera models (pt_camera.h) ------------------------------------------------------------------------------------------------------
+// the DevCamera of the camera in force: the extended camera's basis, or ptc_make_camera of the stored look-at.  Every place that (re)makes c->cam calls this
+void make_camera_in_force(const ptc_ctx* c, DevCamera& cam);
+inline int cam_projection(const ptc_ctx* c) { return c->cam_ex_set ? c->cam_ex.projection : PTC_PROJ_PERSPECTIVE; }
+inline PtCamProj cam_proj(const ptc_ctx* c) { return PtCamProj{cam_projection(c), c->cam_ex.xmag, c->cam_ex.ymag}; }
+inline void take_camera_ex(ptc_ctx* c, const ptc_ctx* c0) { c->cam_ex_set = c0->cam_ex_set; c->cam_ex = c0->cam_ex; }
+// what serves the perspective projection alone, asked under another: "<who>: ... PTC_PROJ_<name> ...", else empty.  Needs no device
+std::string projection_refusal(const ptc_ctx* c, const char* who, const char* what);
 
 // ---- ptc_api_emissive_tex.cpp: textured emission (pt_emissive_tex.h) ------------------------------------------------------------------------------------
 inline bool emtex_has(const ptc_ctx* c, int material) { return (size_t)material < c->emtex.mats.size() && c->emtex.mats[(size_t)material].tex >= 0; }

@@ -9,6 +9,8 @@
 //               ptc_update_instance_matrix for every instance and ptc_update_mesh_pose for every deforming mesh, with the joint matrices
 //               inverse(global(mesh node)) global(joint) inverseBind.  The caller refits or rebuilds (or commits).  KHR_lights_punctual lights follow their nodes
 //               through ptc_update_light.
+//   camera      the ptc_camera_params of camera node `index` (the scene's camera nodes in the order load() reaches them) at rest or at time t of an animation:
+//               the node's world matrix as pose composes the instance matrices, so a camera on an animated node flies.  Needs no context and no load_into.
 // Node matrices for the instances are composed in binary32 exactly as load() composes them; joint matrices are composed in binary64 and rounded once.
 #pragma once
 #include "gltf_loader.hpp"
@@ -39,7 +41,7 @@ public:
   long long load_into(ptc_ctx* ctx, int scene_index, bool compose_parents, float bbox6[6]) {
     using namespace detail;
     const FlatScene fs = load(path_, scene_index, compose_parents);
-    compose_ = compose_parents;
+    compose_ = compose_parents; scene_ = scene_index;
     insts_.clear(); meshes_.clear(); lights_.clear();
     std::vector<int> tex_id, mat_id;
     for (const Texture& t : fs.textures) { const int id = ptc_add_texture_rgba8(ctx, t.rgba.data(), t.w, t.h); if (id < 0) return id; tex_id.push_back(id); }
@@ -155,6 +157,19 @@ public:
     return apply(ctx, sample(a, t), /*instances=*/true);
   }
 
+  // the camera nodes of the scene (load_into's, or the asset's default one), in load()'s order
+  int cameras() const { return (int)camera_nodes().size(); }
+  // animation < 0: the rest pose.  PTC_E_ARG: no such camera or animation
+  int camera(int index, int a, double t, float frame_aspect, ptc_camera_params* out) const {
+    const std::vector<long> cn = camera_nodes();
+    if (!out || index < 0 || (size_t)index >= cn.size() || a >= (int)anims_.size()) return PTC_E_ARG;
+    const long node = cn[(size_t)index];
+    Camera c = detail::camera_def(doc_.root, doc_.root.array("nodes")[(size_t)node].integer("camera", -1));
+    c.node = node; c.world = world32(sample(a < 0 ? -1 : a, t), node);
+    detail::camera_params(c, frame_aspect, out);
+    return PTC_OK;
+  }
+
 private:
   struct Channel { long node; int path; int interp; std::vector<float> times, values; int width; };      // path 0 T, 1 R, 2 S, 3 weights; interp 0 LINEAR, 1 STEP, 2 CUBICSPLINE
   struct Anim { std::vector<Channel> ch; float t_min = 0, t_max = 0; };
@@ -172,6 +187,23 @@ private:
   std::vector<InstRec> insts_;
   std::vector<LightRec> lights_;
   bool compose_ = true;
+  long scene_ = -1;      // the scene load_into read (-1: the asset's default)
+
+  void walk_cameras(long n, int depth, std::vector<long>& out) const {      // pre-order: the order load()'s traversal first reaches the nodes
+    const auto& nodes = doc_.root.array("nodes");
+    if (n < 0 || (size_t)n >= nodes.size()) throw std::runtime_error("node index out of range");
+    if (depth > 256) throw std::runtime_error("node hierarchy too deep (cycle?)");
+    if (nodes[(size_t)n].integer("camera", -1) >= 0) out.push_back(n);
+    for (const JValue& c : nodes[(size_t)n].array("children")) walk_cameras((long)c.num, depth + 1, out);
+  }
+  std::vector<long> camera_nodes() const {
+    const auto& scenes = doc_.root.array("scenes");
+    const long si = scene_ >= 0 ? scene_ : doc_.root.integer("scene", 0);
+    if (si < 0 || (size_t)si >= scenes.size()) throw std::runtime_error("scene index out of range");
+    std::vector<long> out;
+    for (const JValue& r : scenes[(size_t)si].array("nodes")) walk_cameras((long)r.num, 0, out);
+    return out;
+  }
 
   void walk(long n, int depth, std::vector<long>& out) const {
     const auto& nodes = doc_.root.array("nodes");

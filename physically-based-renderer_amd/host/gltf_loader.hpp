@@ -161,12 +161,16 @@ struct Instance { int primitive; std::array<float, 16> model; };   // column-maj
 // KHR_lights_punctual: `params` is the light in world space (position = the node's origin, direction = its -Z axis after the composed transform, not yet normalised:
 // ptc_add_light does that); intensity = color x intensity; the cone angles have become cosines through libm
 struct Light { long node; ptc_light_params params; };
+// A camera of `cameras[]` as a node carries it: projection PTC_PROJ_PERSPECTIVE (yfov, aspect_ratio: the camera's aspectRatio, 0 when it has none) or
+// PTC_PROJ_ORTHOGRAPHIC (xmag, ymag); world: the node's composed transform = the camera-to-world matrix of ptc_camera_params.  znear / zfar are not read
+struct Camera { long node; int projection; float yfov, aspect_ratio, xmag, ymag; std::array<float, 16> world; };
 struct FlatScene {
   std::vector<Texture> textures;        // decoded images, one per glTF image that a material references (first-use order)
   std::vector<Material> materials;      // glTF materials in index order, plus a trailing default one if any primitive needs it
   std::vector<Primitive> primitives;    // one per glTF mesh primitive, mesh order then primitive order
   std::vector<Instance> instances;      // scene traversal order (depth-first, children before the node's own mesh — Scene.cpp:77-82)
   std::vector<Light> lights;            // KHR_lights_punctual lights of the scene's nodes, in the order the traversal first reaches their nodes
+  std::vector<Camera> cameras;          // the camera nodes of the scene, in the same order (rest pose)
   float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};   // world-space bounds of all instanced vertices
   std::uint64_t n_triangles = 0;
 };
@@ -245,6 +249,33 @@ inline Mat4 from_trs(const float t[3], const float q_wxyz[4], const float s[3]) 
   for (int c = 0; c < 3; ++c) { for (int k = 0; k < 3; ++k) m[c * 4 + k] = R[c * 3 + k] * s[c]; m[c * 4 + 3] = 0.0f; }
   m[12] = t[0]; m[13] = t[1]; m[14] = t[2]; m[15] = 1.0f;
   return m;
+}
+
+// camera `ci` of the document's `cameras`: the projection and its parameters (node and world are the caller's)
+template <class J> inline Camera camera_def(const J& root, long ci) {
+  const auto& cams = root.array("cameras");
+  if (ci < 0 || (size_t)ci >= cams.size()) throw std::runtime_error("camera index out of range");
+  const auto& c = cams[(size_t)ci];
+  Camera d{-1, PTC_PROJ_PERSPECTIVE, 0.0f, 0.0f, 1.0f, 1.0f, {}};
+  const std::string type = c.string("type");
+  if (type == "perspective") {
+    const auto* p = c.get("perspective");
+    if (!p) throw std::runtime_error("camera of type perspective without a perspective object");
+    d.yfov = (float)p->number("yfov", 0.0); d.aspect_ratio = (float)p->number("aspectRatio", 0.0);
+  } else if (type == "orthographic") {
+    const auto* o = c.get("orthographic");
+    if (!o) throw std::runtime_error("camera of type orthographic without an orthographic object");
+    d.projection = PTC_PROJ_ORTHOGRAPHIC; d.xmag = (float)o->number("xmag", 0.0); d.ymag = (float)o->number("ymag", 0.0);
+  } else throw std::runtime_error("unknown camera type '" + type + "'");
+  return d;
+}
+// the ptc_camera_params of a camera: aspect = the camera's aspectRatio when it has one, else the frame's
+inline void camera_params(const Camera& c, float frame_aspect, ptc_camera_params* out) {
+  ptc_camera_default_params(out);
+  out->projection = c.projection;
+  for (int k = 0; k < 16; ++k) out->camera_to_world[k] = c.world[(size_t)k];
+  if (c.projection == PTC_PROJ_PERSPECTIVE) { out->yfov = c.yfov; out->aspect = c.aspect_ratio > 0.0f ? c.aspect_ratio : frame_aspect; }
+  else { out->xmag = c.xmag; out->ymag = c.ymag; }
 }
 
 // a light's node transform -> its world-space position and direction (the node's -Z axis)
@@ -681,6 +712,11 @@ inline FlatScene load(const std::string& path, int scene_index = -1, bool compos
             place_light(world, L.params);
             out.lights.push_back(L);
           }
+        if (const long ci = n.integer("camera", -1); ci >= 0) {
+          Camera c = camera_def(d.root, ci);
+          c.node = fr.node; c.world = world;
+          out.cameras.push_back(c);
+        }
         stack.push_back({Frame{fr.node, fr.parent, fr.depth}, true});
         const auto& ch = n.array("children");
         for (size_t k = ch.size(); k-- > 0;) stack.push_back({Frame{(long)ch[k].num, world, fr.depth + 1}, false});

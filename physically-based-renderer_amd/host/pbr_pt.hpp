@@ -130,6 +130,11 @@ public:
     setCameraLens(ptc_lens_params{apertureRadius, focusDistance, blades, rotation});
   }
   auto cameraLens() const -> ptc_lens_params { ptc_lens_params p; ptc_get_camera_lens(_ctx, &p); return p; }
+  // ---- camera models (include/ptc_camera.h): a camera-to-world matrix in glTF camera space with a perspective, orthographic or equirectangular projection ----
+  // Replaces setCamera's camera and is replaced by it; dropped by beginScene; needs no commit
+  static auto cameraDefaults() -> ptc_camera_params { ptc_camera_params p; ptc_camera_default_params(&p); return p; }
+  auto setCameraEx(ptc_camera_params const& camera) -> void { ck(ptc_set_camera_ex(_ctx, &camera)); }
+  auto cameraEx(ptc_camera_params& out) const -> bool { return ptc_get_camera_ex(_ctx, &out) == 1; }
   // punctual lights (ptc_add_light ...): point / spot / directional, sampled by the path integrator in a pass of its own.  They need no commit and no
   // refit; a frame sees the lights recorded when it began.  Dropped by beginScene
   static auto lightDefaults() -> ptc_light_params { ptc_light_params p; ptc_light_default_params(&p); return p; }

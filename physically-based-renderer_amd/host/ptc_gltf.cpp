@@ -59,6 +59,29 @@ extern "C" int ptc_gltf_asset_pose(ptc_gltf_asset* a, ptc_ctx* ctx, int animatio
   } catch (std::exception const& e) { a->err = std::string("ptc_gltf_asset_pose: ") + e.what(); return PTC_E_ARG; }
 }
 
+extern "C" int ptc_gltf_asset_cameras(const ptc_gltf_asset* a) {
+  if (!a) return PTC_E_ARG;
+  try { return a->asset.cameras(); }
+  catch (std::exception const&) { return PTC_E_ARG; }
+}
+extern "C" int ptc_gltf_asset_camera(ptc_gltf_asset* a, int index, int animation, double time_seconds, float frame_aspect, ptc_camera_params* out) {
+  if (!a || !out) return PTC_E_ARG;
+  try {
+    const int rc = a->asset.camera(index, animation, time_seconds, frame_aspect, out);
+    if (rc < 0) a->err = animation >= a->asset.animations() ? "ptc_gltf_asset_camera: animation out of range" : "ptc_gltf_asset_camera: camera index out of range";
+    return rc;
+  } catch (std::exception const& e) { a->err = std::string("ptc_gltf_asset_camera: ") + e.what(); return PTC_E_ARG; }
+}
+extern "C" int ptc_gltf_cameras(const char* path, int scene_index, int compose_parents, float frame_aspect, ptc_camera_params* out, int capacity, char* err, int err_len) {
+  auto say = [&](const std::string& m) { if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str()); };
+  if (!path || capacity < 0 || (capacity > 0 && !out)) { say("ptc_gltf_cameras: bad argument"); return PTC_E_ARG; }
+  try {
+    const pbr::gltf::FlatScene s = pbr::gltf::load(path, scene_index, compose_parents != 0);
+    for (size_t k = 0; k < s.cameras.size() && k < (size_t)capacity; ++k) pbr::gltf::detail::camera_params(s.cameras[k], frame_aspect, out + k);
+    return (int)s.cameras.size();
+  } catch (std::exception const& e) { say(std::string("ptc_gltf_cameras: ") + e.what()); return PTC_E_ARG; }
+}
+
 namespace {
 template <class Decode>
 int decode_into(const char* who, Decode&& dec, unsigned char* out, unsigned long long out_capacity, int* w, int* h, char* err, int err_len) {

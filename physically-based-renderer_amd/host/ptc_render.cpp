@@ -57,7 +57,11 @@
 // ptc_set_env_latlong_rgb32f takes row 0 = +y, so the rows are flipped on the way in.  --sky: a built-in gradient sky with a sun, for
 // assets that carry no emitters.
 // --animation N --time T: the glTF scene is loaded with its skins and morph targets (host/gltf_anim.hpp) and posed at T seconds of its animation N before the commit.
-// Without --cam-* a glTF scene is framed from its bounding box (the reference ignores glTF cameras and injects its own).
+// Without --cam-* a glTF scene is framed from its bounding box.  Camera models (ptc_set_camera_ex), path integrator:
+// --camera N: camera node N of the --gltf asset (scene-traversal order), frame aspect W/H, at --time of --animation when given.  --cam-matrix m0,...,m15: a
+// column-major camera-to-world matrix in glTF camera space (looks along -Z, +Y up), perspective with --fov.  --ortho XMAG,YMAG and --panorama switch the
+// projection of whatever camera is in force: the asset's, the matrix's, or the look-at camera's (+Y up; --panorama takes its position with the rotation identity).
+// A --panorama image (--out / --pfm, --png, --ppm) is written as --env reads a map, its rows reversed: `--panorama --pfm p.pfm`, then `--env p.pfm`, round-trips exactly.
 // The scenes are the procedural stand-ins of BASELINE configs 1 and 2 (the reference's assets are stripped).
 #include "gltf_anim.hpp"
 #include "gltf_loader.hpp"
@@ -224,6 +228,9 @@ int main(int argc, char** argv) {
   std::string countsPath;
   ptc_lens_params lens = pbr::PathTraceRenderSystem::lensDefaults();      // --aperture / --blades / --aperture-rotation / --focus
   bool haveFocus = false, haveFocusPixel = false, haveLensShape = false;
+  int cameraIndex = -1;                      // --camera N: the asset's camera node N
+  bool haveOrtho = false, panorama = false, haveCamMatrix = false;      // --ortho XMAG,YMAG / --panorama / --cam-matrix
+  float orthoMag[2] = {1.0f, 1.0f}, camMatrix[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   int focusX = 0, focusY = 0;
   int animation = -1;                        // --animation: pose the glTF scene along this animation ...
   double animTime = 0.0;                     // ... at --time seconds, before the commit
@@ -261,6 +268,14 @@ int main(int argc, char** argv) {
     else if (a == "--blades") { lens.blades = std::atoi(next()); haveLensShape = true; } else if (a == "--aperture-rotation") { lens.rotation = (float)std::atof(next()); haveLensShape = true; }
     else if (a == "--focus") { lens.focus_distance = (float)std::atof(next()); haveFocus = true; }
     else if (a == "--focus-pixel") { if (std::sscanf(next(), "%d,%d", &focusX, &focusY) != 2) { std::cerr << "--focus-pixel X,Y\n"; return 2; } haveFocusPixel = true; }
+    else if (a == "--camera") cameraIndex = std::atoi(next()); else if (a == "--panorama") panorama = true;
+    else if (a == "--ortho") { if (std::sscanf(next(), "%f,%f", &orthoMag[0], &orthoMag[1]) != 2) { std::cerr << "--ortho XMAG,YMAG\n"; return 2; } haveOrtho = true; }
+    else if (a == "--cam-matrix") {
+      const char* s = next(); char* end = nullptr; int n = 0;
+      for (; n < 16; ++n) { camMatrix[n] = std::strtof(s, &end); if (end == s) break; s = *end == ',' ? end + 1 : end; }
+      if (n != 16 || *end != '\0') { std::cerr << "--cam-matrix m0,...,m15 (column-major camera-to-world)\n"; return 2; }
+      haveCamMatrix = true;
+    }
     else if (a == "--light") lightSpecs.push_back(next()); else if (a == "--no-gltf-lights") noGltfLights = true; else if (a == "--no-alpha") noAlpha = true; else if (a == "--no-transmission") noTransmission = true; else if (a == "--no-emissive-textures") noEmissiveTextures = true; else if (a == "--glass-shadows") glassShadows = true;
     else if (a == "--fog") fogSpec = next();
     else if (a == "--exposure") { exposureEv = std::atof(next()); useDisplay = true; } else if (a == "--auto-exposure") { disp.auto_exposure = 1; useDisplay = true; }
@@ -288,7 +303,7 @@ int main(int argc, char** argv) {
     else if (a == "--fov") fovDeg = (float)std::atof(next());
     else if (a == "--bvh") { const std::string f = next(); if (f == "lbvh") bvh = PTC_BVH_LBVH; else if (f == "sah") bvh = PTC_BVH_SAH; else { std::cerr << "--bvh sah|lbvh\n"; return 2; } }
     else if (a == "--device-bvh") { const std::string f = next(); if (f == "lbvh") deviceBvh = PTC_BVH_LBVH; else if (f == "sah") deviceBvh = PTC_BVH_SAH; else { std::cerr << "--device-bvh sah|lbvh\n"; return 2; } }
-    else if (a == "--out") out = next(); else if (a == "--png") png = next(); else if (a == "--ppm") ppm = next(); else if (a == "--raster") integrator = PTC_INTEGRATOR_RASTER_COMPAT;
+    else if (a == "--out" || a == "--pfm") out = next(); else if (a == "--png") png = next(); else if (a == "--ppm") ppm = next(); else if (a == "--raster") integrator = PTC_INTEGRATOR_RASTER_COMPAT;
     else { std::cerr << "unknown argument " << a << "\n"; return 2; }
   }
   try {
@@ -306,6 +321,46 @@ int main(int argc, char** argv) {
       if (!(lens.rotation >= 0.0f && lens.rotation < 1.0f)) throw std::runtime_error("--aperture-rotation T: turns in [0, 1)");
       if (haveFocusPixel && (focusX < 0 || focusY < 0 || focusX >= w || focusY >= h)) throw std::runtime_error("--focus-pixel X,Y: a pixel of the image");
     }
+    const bool cameraEx = cameraIndex >= 0 || haveOrtho || panorama || haveCamMatrix;
+    {   // the camera models: everything that can be refused is refused here, before a device is touched
+      if (cameraIndex >= 0 && gltf.empty()) throw std::runtime_error("--camera N takes camera N of a --gltf scene");
+      if (cameraIndex >= 0 && haveCamMatrix) throw std::runtime_error("--camera and --cam-matrix exclude each other");
+      if (haveOrtho && panorama) throw std::runtime_error("--ortho and --panorama exclude each other");
+      if (haveOrtho && !(orthoMag[0] > 0.0f && orthoMag[1] > 0.0f && std::isfinite(orthoMag[0]) && std::isfinite(orthoMag[1]))) throw std::runtime_error("--ortho XMAG,YMAG: finite half extents > 0");
+      if ((haveOrtho || panorama) && integrator != PTC_INTEGRATOR_PATH) throw std::runtime_error("--ortho / --panorama apply to the path integrator (not with --raster / --raster16)");
+      if ((haveOrtho || panorama) && (haveFocusPixel || lens.aperture_radius != 0.0f)) throw std::runtime_error("--ortho / --panorama have no lens (not with --aperture / --focus-pixel)");
+      if (cameraEx && gltf.empty() && !haveCamMatrix) throw std::runtime_error("--ortho / --panorama on a built-in scene need --cam-matrix");
+      if (cameraEx && gltf.empty() && gpus != 0) throw std::runtime_error("a camera model on a built-in scene renders on one context (not with --gpus)");
+    }
+    // the extended camera (ptc_set_camera_ex) of --camera / --cam-matrix / --ortho / --panorama; needs no commit
+    auto applyCameraEx = [&](pbr::PathTraceRenderSystem& rs) {
+      if (!cameraEx) return;
+      ptc_camera_params p;
+      ptc_camera_default_params(&p);
+      p.yfov = viewerFov > 0.0f ? viewerFov : fovDeg * 3.14159265f / 180.0f; p.aspect = (float)w / h;
+      if (cameraIndex >= 0) {      // the asset's camera, at --time of --animation when given
+        pbr::gltf::Asset asset(gltf);
+        if (cameraIndex >= asset.cameras()) throw std::runtime_error("--camera: the asset has " + std::to_string(asset.cameras()) + " camera(s)");
+        if (asset.camera(cameraIndex, animation, animTime, (float)w / h, &p) < 0) throw std::runtime_error("--camera: the asset's camera could not be read");
+      } else if (haveCamMatrix) std::memcpy(p.camera_to_world, camMatrix, sizeof camMatrix);
+      else {      // the look-at camera in force: +Y up; a panorama takes its position alone
+        float Z[3] = {camPos[0] - camTarget[0], camPos[1] - camTarget[1], camPos[2] - camTarget[2]};
+        const float lz = std::sqrt(Z[0] * Z[0] + Z[1] * Z[1] + Z[2] * Z[2]);
+        for (float& v : Z) v /= lz;
+        float X[3] = {Z[2], 0.0f, -Z[0]};      // (0, 1, 0) x Z
+        const float lx = std::sqrt(X[0] * X[0] + X[2] * X[2]);
+        if (!(lz > 0.0f) || !(lx > 0.0f)) throw std::runtime_error("--ortho: the camera looks straight up or down; give --cam-matrix");
+        for (float& v : X) v /= lx;
+        const float Y[3] = {Z[1] * X[2] - Z[2] * X[1], Z[2] * X[0] - Z[0] * X[2], Z[0] * X[1] - Z[1] * X[0]};
+        for (int k = 0; k < 3; ++k) { p.camera_to_world[k] = X[k]; p.camera_to_world[4 + k] = Y[k]; p.camera_to_world[8 + k] = Z[k]; p.camera_to_world[12 + k] = camPos[k]; }
+      }
+      if (haveOrtho) { p.projection = PTC_PROJ_ORTHOGRAPHIC; p.xmag = orthoMag[0]; p.ymag = orthoMag[1]; }
+      if (panorama) {
+        p.projection = PTC_PROJ_EQUIRECT;
+        if (cameraIndex < 0 && !haveCamMatrix) for (int k = 0; k < 12; ++k) p.camera_to_world[k] = (k % 5 == 0) ? 1.0f : 0.0f;      // the rotation identity
+      }
+      if (ptc_set_camera_ex(rs.handle(), &p) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
+    };
     {   // the display transform
       disp.gain = (float)std::exp2(exposureEv);
       if (!std::isfinite(exposureEv) || !(disp.gain > 0.0f) || !std::isfinite(disp.gain)) throw std::runtime_error("--exposure EV: 2^EV must be a finite float > 0");
@@ -452,8 +507,9 @@ int main(int argc, char** argv) {
           }
         if (ptc_set_env_latlong_rgb32f(rs.handle(), env.data(), ew, eh) < 0) throw std::runtime_error(ptc_last_error(rs.handle()));
       }
+      applyCameraEx(rs);
       rs.commitScene();
-    } else if (scene == "cornell") buildCornell(rs); else if (scene == "sphere") buildSphere(rs, (float)w / h); else throw std::runtime_error("unknown scene " + scene);
+    } else if (scene == "cornell") { buildCornell(rs); applyCameraEx(rs); } else if (scene == "sphere") { buildSphere(rs, (float)w / h); applyCameraEx(rs); } else throw std::runtime_error("unknown scene " + scene);
     };
     std::unique_ptr<pbr::PathTraceRenderSystem> single;
     std::unique_ptr<pbr::DeviceGroup> group;
@@ -569,10 +625,19 @@ int main(int argc, char** argv) {
       std::ofstream g(halfPath, std::ios::binary);
       g.write(reinterpret_cast<const char*>(hb.data()), (std::streamsize)(hb.size() * 2));
     }
+    // A panorama is written the way --env reads a map: top row = up in the reference's y-down world = -y, i.e. with its rows reversed (the library's row 0 is +y).
+    // `--panorama --pfm p.pfm` followed by `--env p.pfm` therefore hands the library the image it rendered: the round trip is exact.
+    auto panoramaRows = [&](auto& pixels) {
+      if (!panorama) return;
+      const std::size_t row = (std::size_t)w * 4;
+      for (int y = 0; y < h / 2; ++y) std::swap_ranges(pixels.begin() + (std::ptrdiff_t)(y * row), pixels.begin() + (std::ptrdiff_t)((y + 1) * row), pixels.begin() + (std::ptrdiff_t)((h - 1 - y) * row));
+    };
+    panoramaRows(img);
     pbr::image::write_pfm(out, img.data(), w, h);
-    if (!png.empty()) { const std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap(); pbr::image::write_png(png, ldr.data(), w, h); }
+    if (!png.empty()) { std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap(); panoramaRows(ldr); pbr::image::write_png(png, ldr.data(), w, h); }
     if (!ppm.empty()) {
-      const std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap();
+      std::vector<std::uint8_t> ldr = useDisplay ? rs.display() : rs.tonemap();
+      panoramaRows(ldr);
       std::ofstream g(ppm, std::ios::binary);
       g << "P6\n" << w << " " << h << "\n255\n";
       for (std::size_t p = 0; p < (std::size_t)w * h; ++p) g.write(reinterpret_cast<const char*>(&ldr[p * 4]), 3);

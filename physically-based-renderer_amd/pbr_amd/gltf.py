@@ -2,7 +2,7 @@
 
 `load_into(pt, path)` is the path-tracer counterpart of the reference's `gltf::Loader::loadAsset` +
 `Asset::loadScene` (src/pbr_engine/gltf/pbr/gltf/Loader.cpp:10-32, Asset.cpp:259-273): it fills a PathTracer's scene
-from a file; the camera stays the caller's (the reference ignores glTF cameras too, Asset.cpp:262-265).
+from a file; the camera stays the caller's unless it asks for one of the asset's (Asset.cameras, Asset.apply_camera, cameras()).
 
 `write_glb(desc, path)` serialises a SceneDesc — used by the tests to produce assets, since the reference's own
 (assets/models/test_scene.glb) is stripped from the checkout (.MISSING_LARGE_BLOBS).
@@ -44,6 +44,10 @@ def _load():
         L.ptc_gltf_asset_duration.restype = C.c_double
         L.ptc_gltf_asset_duration.argtypes = [C.c_void_p, C.c_int]
         L.ptc_gltf_asset_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double]
+        cp = C.POINTER(_ptc.PtcCameraParams)
+        L.ptc_gltf_asset_cameras.argtypes = [C.c_void_p]
+        L.ptc_gltf_asset_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, cp]
+        L.ptc_gltf_cameras.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_float, cp, C.c_int, C.c_char_p, C.c_int]
         L.ptc_gltf_asset_last_error.restype = C.c_char_p
         L.ptc_gltf_asset_last_error.argtypes = [C.c_void_p]
         _lib = L
@@ -105,10 +109,44 @@ class Asset:
         pt._ck(pt._L.ptc_scene_commit(h))
         return int(n), lo, hi
 
+    @property
+    def n_cameras(self) -> int:
+        return int(self._ck(self._L.ptc_gltf_asset_cameras(self._a)))
+
+    def camera(self, index: int = 0, frame_aspect: float = 1.0, animation=None, time: float = 0.0):
+        """ptc_gltf_asset_camera: the PtcCameraParams of camera node `index` (scene-traversal order) at rest, or at `time` of `animation`.  aspect is the
+        camera's aspectRatio when it has one, else frame_aspect."""
+        p = _ptc.PtcCameraParams()
+        self._ck(self._L.ptc_gltf_asset_camera(self._a, int(index), -1 if animation is None else int(animation), float(time), float(frame_aspect), C.byref(p)))
+        return p
+
+    @property
+    def cameras(self):
+        """The asset's camera nodes at rest, as dicts (ptc_camera_params; aspect 1 where the camera has no aspectRatio)."""
+        return [self.camera(k).as_dict() for k in range(self.n_cameras)]
+
+    def apply_camera(self, pt, index: int = 0, frame_aspect: float = 1.0, animation=None, time: float = 0.0):
+        """The asset's camera `index` becomes pt's camera (ptc_set_camera_ex).  Needs no commit; call it again with a time to fly along an animation."""
+        p = self.camera(index, frame_aspect, animation, time)
+        pt._ck(pt._L.ptc_set_camera_ex(pt._h, C.byref(p)))
+        return p.as_dict()
+
     def pose(self, pt, animation: int, time: float):
         """ptc_gltf_asset_pose: instance matrices and mesh poses of `animation` at `time` (clamped); the caller refits or rebuilds."""
         self._ck(self._L.ptc_gltf_asset_pose(self._a, pt._h, int(animation), float(time)))
         return self
+
+
+def cameras(path: str, frame_aspect: float = 1.0, scene_index: int = -1, compose_parents: bool = True):
+    """ptc_gltf_cameras: the rest-pose cameras of the stateless loader, a list of PtcCameraParams."""
+    L = _load()
+    err = C.create_string_buffer(512)
+    n = L.ptc_gltf_cameras(os.fsencode(path), scene_index, 1 if compose_parents else 0, float(frame_aspect), None, 0, err, 512)
+    if n < 0:
+        raise _ptc.PtcError(err.value.decode() or f"ptc_gltf_cameras failed ({n})")
+    out = (_ptc.PtcCameraParams * max(n, 1))()
+    L.ptc_gltf_cameras(os.fsencode(path), scene_index, 1 if compose_parents else 0, float(frame_aspect), out, n, err, 512)
+    return [out[k] for k in range(n)]
 
 
 def emissive_textures(on=None) -> bool:
@@ -327,7 +365,7 @@ def _pad4(b: bytes, fill: bytes = b"\x00") -> bytes:
 
 
 def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = False, nodes=None, skins=None, animations=None,
-              joints_type: str = "u16", weights_type: str = "f32", lights=None) -> None:
+              joints_type: str = "u16", weights_type: str = "f32", lights=None, cameras=None) -> None:
     """SceneDesc → GLB.  One glTF mesh per MeshDesc (one primitive each), one node per instance (TRS, or `matrix`
     when the instance carries one).  `nodes`: optional explicit node list (dicts with mesh/translation/rotation/
     scale/matrix/children) + root list, to exercise hierarchies: nodes=(node_dicts, root_indices).
@@ -338,7 +376,10 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
     ("translation" | "rotation" (x, y, z, w) | "scale" | "weights"), "times", "values", "interpolation" ("LINEAR" | "STEP" | "CUBICSPLINE")}]}].
     lights: KHR_lights_punctual — [{"type" ("point" | "spot" | "directional"), "color", "intensity", "range", "inner", "outer" (cone angles, radians)}], each either on an
     existing node ("node": its index) or on a node of its own, appended behind the others in list order, with "translation", "rotation" (w, x, y, z), "scale" and "parent"
-    (the index IN `lights` of the light whose node it hangs under; none: a root).  A light shines along its node's -Z."""
+    (the index IN `lights` of the light whose node it hangs under; none: a root).  A light shines along its node's -Z.
+    cameras: [{"type" ("perspective": "yfov", optional "aspectRatio", "znear"; "orthographic": "xmag", "ymag", "znear", "zfar")}], placed as lights are: on an existing
+    node ("node"), or on a node of its own behind the others (and behind the lights' own nodes) with "translation", "rotation" (w, x, y, z), "scale" and "parent" (the
+    index IN `cameras`).  A camera looks along its node's -Z with +Y up."""
     blob = bytearray()
     views, accessors, meshes = [], [], []
 
@@ -494,8 +535,40 @@ def write_glb(desc, path: str, index_type: str = "auto", interleaved: bool = Fal
                 else:
                     roots.append(own[k])
             nd.setdefault("extensions", {})["KHR_lights_punctual"] = {"light": k}
+    camera_defs = []
+    if cameras:
+        node_list, roots = [dict(n) for n in node_list], list(roots)
+        own = {}      # index in `cameras` -> its own node
+        for k, c in enumerate(cameras):
+            if c["type"] == "perspective":
+                g = {"yfov": float(c["yfov"]), "znear": float(c.get("znear", 0.01))}
+                if c.get("aspectRatio") is not None:
+                    g["aspectRatio"] = float(c["aspectRatio"])
+            else:
+                g = {"xmag": float(c["xmag"]), "ymag": float(c["ymag"]), "znear": float(c.get("znear", 0.01)), "zfar": float(c.get("zfar", 1000.0))}
+            camera_defs.append({"type": c["type"], c["type"]: g})
+            if "node" in c:
+                nd = node_list[int(c["node"])]
+            else:
+                nd = {"name": f"camera{k}"}
+                if "translation" in c:
+                    nd["translation"] = [float(x) for x in c["translation"]]
+                if "rotation" in c:
+                    q = c["rotation"]
+                    nd["rotation"] = [float(q[1]), float(q[2]), float(q[3]), float(q[0])]
+                if "scale" in c:
+                    nd["scale"] = [float(x) for x in c["scale"]]
+                node_list.append(nd)
+                own[k] = len(node_list) - 1
+                if c.get("parent") is not None:
+                    node_list[own[int(c["parent"])]].setdefault("children", []).append(own[k])
+                else:
+                    roots.append(own[k])
+            nd["camera"] = k
     doc = {"asset": {"version": "2.0", "generator": "pbr_amd.gltf.write_glb"}, "scene": 0, "scenes": [{"nodes": list(roots)}], "nodes": node_list,
            "meshes": meshes, "materials": mats, "accessors": accessors, "bufferViews": views, "buffers": [{"byteLength": len(blob)}]}
+    if camera_defs:
+        doc["cameras"] = camera_defs
     if skins:
         doc["skins"] = []
         for sk in skins:

@@ -113,6 +113,16 @@ class PtcLensParams(_Struct):
     _defaults_ = "ptc_lens_default_params"
 
 
+_PROJECTIONS = {"perspective": 0, "orthographic": 1, "equirect": 2}      # PTC_PROJ_* of include/ptc_camera.h
+
+
+class PtcCameraParams(_Struct):
+    _fields_ = [("projection", C.c_int), ("camera_to_world", C.c_float * 16), ("yfov", C.c_float), ("aspect", C.c_float), ("xmag", C.c_float), ("ymag", C.c_float)]
+    _defaults_ = "ptc_camera_default_params"
+    _unknown_ = "unknown camera field {}"
+    _names_ = {"projection": _PROJECTIONS}
+
+
 _ALPHA_MODES = {"opaque": ALPHA_OPAQUE, "mask": ALPHA_MASK, "blend": ALPHA_BLEND}
 _LIGHT_TYPES = {"point": LIGHT_POINT, "spot": LIGHT_SPOT, "directional": LIGHT_DIRECTIONAL, "sun": LIGHT_DIRECTIONAL}
 
@@ -490,7 +500,19 @@ def _emissive_tex_prototypes():
     }
 
 
+def _camera_prototypes():
+    """name -> (restype, argtypes) of every function include/ptc_camera.h declares, in the header's order; exported under ptcx_ like ptc_medium.h's."""
+    cp = C.POINTER(PtcCameraParams)
+    return {
+        "ptc_camera_default_params": (None, [cp]),
+        "ptc_set_camera_ex": (C.c_int, [C.c_void_p, cp]),
+        "ptc_get_camera_ex": (C.c_int, [C.c_void_p, cp]),
+        "ptc_debug_read_guide_positions": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    }
+
+
 _PROTOTYPES = _prototypes()
+_CAMERA_PROTOTYPES = _camera_prototypes()
 _EMISSIVE_TEX_PROTOTYPES = _emissive_tex_prototypes()
 _LIGHTMAP_PROTOTYPES = _lightmap_prototypes()
 _MEDIUM_PROTOTYPES = _medium_prototypes()
@@ -521,7 +543,7 @@ def load_library():
     for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
-    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()) + list(_LIGHTMAP_PROTOTYPES.items()) + list(_EMISSIVE_TEX_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(_ALPHA_PROTOTYPES.items()) + list(_GLASS_PROTOTYPES.items()) + list(_GLASS_SHADOW_PROTOTYPES.items()) + list(_SHADE_DEBUG_PROTOTYPES.items()) + list(_EXACT_DEBUG_PROTOTYPES.items()) + list(_MEDIUM_PROTOTYPES.items()) + list(_LIGHTMAP_PROTOTYPES.items()) + list(_EMISSIVE_TEX_PROTOTYPES.items()) + list(_CAMERA_PROTOTYPES.items()):
         fn = getattr(L, "ptcx_" + name[len("ptc_"):])
         fn.restype, fn.argtypes = restype, argtypes
         setattr(L, name, fn)
@@ -541,6 +563,39 @@ def _ptr(a):
 def _f(a):
     a = np.ascontiguousarray(a, np.float32)
     return a, _ptr(a)
+
+
+def camera_default_params():
+    return PtcCameraParams.defaults().as_dict()
+
+
+def look_at_matrix(position, target, up=(0.0, 1.0, 0.0)):
+    """The camera-to-world matrix (4x4 float64) of a glTF camera at `position` that looks at `target` with `up` upwards in the image."""
+    pos, tgt, up = (np.asarray(v, np.float64) for v in (position, target, up))
+    z = pos - tgt
+    z /= np.linalg.norm(z)
+    x = np.cross(up, z)
+    x /= np.linalg.norm(x)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2], m[:3, 3] = x, np.cross(z, x), z, pos
+    return m
+
+
+def _camera_ex_fields(cam):
+    """set_camera_ex's arguments for a scene.CameraDesc with a matrix or a projection of its own.  Without a matrix: the panorama is taken at the camera's
+    position with the identity rotation, the other projections look from position to target with +Y up."""
+    projection = getattr(cam, "projection", "perspective")
+    matrix = getattr(cam, "matrix", None)
+    if matrix is None:
+        matrix = look_at_matrix(cam.position, cam.target)
+        if projection == "equirect":
+            matrix[:3, :3] = np.eye(3)
+    fields = dict(matrix=matrix, projection=projection)
+    if projection == "perspective":
+        fields.update(yfov=cam.fov_y, aspect=cam.aspect)
+    elif projection == "orthographic":
+        fields.update(xmag=cam.xmag, ymag=cam.ymag)
+    return fields
 
 
 def lens_default_params():
@@ -840,6 +895,8 @@ class PathTracer:
                 self._ck(L.ptc_add_instance(h, it.mesh, _f(it.t)[1], _f(it.q_wxyz)[1], _f(it.s)[1]))
         c = desc.camera
         self._ck(L.ptc_set_camera(h, _f(c.position)[1], _f(c.target)[1], c.fov_y, c.aspect))
+        if getattr(c, "matrix", None) is not None or getattr(c, "projection", "perspective") != "perspective":      # an extended camera replaces the look-at
+            self.set_camera_ex(**_camera_ex_fields(c))
         self.set_camera_lens(getattr(c, "aperture_radius", 0.0), getattr(c, "focus_distance", 1.0), getattr(c, "blades", 0), getattr(c, "aperture_rotation", 0.0))
         for l in getattr(desc, "lights", []):
             self.add_light(l)
@@ -1100,6 +1157,34 @@ class PathTracer:
 
     def get_camera_lens(self):
         return self._get(self._L.ptc_get_camera_lens, PtcLensParams)
+
+    # ---- camera models (csrc/pt_camera.h, include/ptc_camera.h) ------------------------------------------------
+    def set_camera_ex(self, matrix=None, projection="perspective", **fields):
+        """ptc_set_camera_ex: the camera given by its camera-to-world `matrix` (4x4, glTF camera space: looks along -Z, +Y up, +X right; None is the
+        identity) and a projection: "perspective" (yfov radians, aspect), "orthographic" (xmag, ymag: half extents) or "equirect" (the 360-degree panorama,
+        no parameters).  Fields left out keep the library's defaults.  Replaces set_camera's camera, and is replaced by it."""
+        p = PtcCameraParams.defaults(projection=projection, **fields)
+        if matrix is not None:
+            m = np.asarray(matrix, np.float32)
+            if m.shape not in ((4, 4), (16,)):
+                raise PtcError(f"set_camera_ex: the matrix must be 4x4 (or its 16 entries in column-major order), got {m.shape}")
+            p.update(camera_to_world=(m.T if m.ndim == 2 else m).reshape(16))      # a 4x4 array is the mathematical matrix: its columns go out one after the other
+        self._ck(self._L.ptc_set_camera_ex(self._h, C.byref(p)))
+        return self
+
+    def debug_guide_positions(self):
+        """ptc_debug_read_guide_positions: (h, w, 4) = (P, class) of the current frame's guides, P = origin + Z direction of the pixel-centre ray."""
+        return self._read(self._L.ptc_debug_read_guide_positions, (self._h_px, self._w, 4), np.float32)
+
+    def get_camera_ex(self):
+        """ptc_get_camera_ex: the extended camera as a dict (camera_to_world: the 16 column-major entries; projection: its name), or None when set_camera's
+        camera is in force."""
+        p = PtcCameraParams()
+        if not self._ck(self._L.ptc_get_camera_ex(self._h, C.byref(p))):
+            return None
+        d = p.as_dict()
+        d["projection"] = {v: k for k, v in _PROJECTIONS.items()}[d["projection"]]
+        return d
 
     def focus_distance_at_pixel(self, x, y):
         """ptc_focus_distance_at_pixel: the view depth of what pixel (x, y)'s centre sees (0 on a miss), from the current frame's guides (frame_guides())."""

@@ -215,6 +215,12 @@ class CameraDesc:
     focus_distance: float = 1.0
     blades: int = 0
     aperture_rotation: float = 0.0
+    # an extended camera (ptc_set_camera_ex): a 4x4 camera-to-world matrix in glTF camera space (looks along -Z, +Y up) instead of position / target, and a
+    # projection: "perspective" (fov_y, aspect), "orthographic" (xmag, ymag: half extents) or "equirect" (the 360-degree panorama)
+    matrix: Optional[Sequence[Sequence[float]]] = None
+    projection: str = "perspective"
+    xmag: float = 1.0
+    ymag: float = 1.0
 
 
 @dataclasses.dataclass
