@@ -3,13 +3,14 @@
 //
 //   k_raygen_proj          one thread per path, k_raygen's path id -> (owned pixel j, sample first + s) mapping in the frame's path order (pt_device.h:
 //                          pt_path_entry), so adaptive frames (the active-pixel list in DevFrame::owned), tile shares, sample ranges and both path orders need
-//                          nothing of their own here.  One 4-byte load of the pixel index, four coalesced 16-byte stores: the ray record A = (o, d.x),
-//                          B = (d.y, d.z, 1, 1), C = (1, 0, p, key) and the cleared path radiance — k_raygen_lens' record.
+//                          nothing of their own here.  One 4-byte load of the pixel index, four coalesced 16-byte stores: store_primary_ray
+//                          (pt_pass_common.h).
 //   k_raygen_guides_proj   the pixel-centre rays of a chunk of the frame, k_raygen_guides' record.
 //   k_guides_pos_proj      rewrites the one field k_guides derived from a perspective ray: pos_class.xyz = o + Z d (a product and a sum per component, as k_guides
 //                          writes it) with the projection's own origin and direction; Z and the class are read back from what k_guides wrote.
 // Streaming kernels like k_raygen: 64 B written per path, every byte once.  Beside k_raygen's work EQUIRECT evaluates two sincos polynomials and a normalisation.
 #include "pt_camera.h"
+#include "pt_pass_common.h"
 
 namespace {
 __global__ __launch_bounds__(256) void k_raygen_proj(DevCamera cam, PtCamProj proj, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_samples) {
@@ -21,11 +22,7 @@ __global__ __launch_bounds__(256) void k_raygen_proj(DevCamera cam, PtCamProj pr
   float o[3], d[3];
   uint32_t key;
   pt_proj_ray(cam, proj, fr.w, fr.h, fr.seed_hash, pixel, first_sample + sl, o, d, key);
-  const RayQ& r = q.ray[0];
-  r.A[p] = make_float4(o[0], o[1], o[2], d[0]);
-  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
-  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), __uint_as_float(key));
-  q.lpath[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  store_primary_ray(q, p, V3(o), V3(d), key, true);
 }
 
 __global__ __launch_bounds__(256) void k_raygen_guides_proj(DevCamera cam, PtCamProj proj, int w, int h, uint32_t first_pixel, uint32_t n, DevQueues q) {
@@ -33,10 +30,7 @@ __global__ __launch_bounds__(256) void k_raygen_guides_proj(DevCamera cam, PtCam
   if (p >= n) return;
   float o[3], d[3];
   pt_proj_guide_ray(cam, proj, w, h, first_pixel + p, o, d);
-  const RayQ& r = q.ray[0];
-  r.A[p] = make_float4(o[0], o[1], o[2], d[0]);
-  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
-  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), 0.0f);
+  store_primary_ray(q, p, V3(o), V3(d), 0u, false);      // no key (its bits are 0.0f), and lpath is not a guide pass's
 }
 
 __global__ __launch_bounds__(256) void k_guides_pos_proj(DevCamera cam, PtCamProj proj, int w, int h, uint32_t first_pixel, uint32_t n,

@@ -3,10 +3,11 @@
 //   k_raygen_lens   one thread per path, k_raygen's path id -> (owned pixel j, sample first + s) mapping in the frame's path order (pt_device.h: pt_path_entry;
 //                   sample-major j = p % n_owned, s = p / n_owned, pixel-major j = p / n_samples, s = p % n_samples), so adaptive frames (the
 //                   active-pixel list in DevFrame::owned), tile shares and sample ranges need nothing of their own here.  One 4-byte load of the pixel index,
-//                   four coalesced 16-byte stores: the ray record A = (o, d.x), B = (d.y, d.z, 1, 1), C = (1, 0, p, key) and the cleared path radiance.
+//                   four coalesced 16-byte stores: store_primary_ray (pt_pass_common.h).
 // A streaming kernel like k_raygen: 64 B written per path, every byte once.  Beside k_raygen's work it hashes two more RNG dimensions and evaluates a square
 // root and one (disk) or two (blades) sincos polynomials; profiles/lens_1080p.txt has the two kernels' times at equal path counts.
 #include "pt_lens.h"
+#include "pt_pass_common.h"
 
 namespace {
 __global__ __launch_bounds__(256) void k_raygen_lens(DevCamera cam, ptc_lens_params lens, DevFrame fr, DevQueues q, uint32_t first_sample, uint32_t n_samples) {
@@ -18,11 +19,7 @@ __global__ __launch_bounds__(256) void k_raygen_lens(DevCamera cam, ptc_lens_par
   float o[3], d[3];
   uint32_t key;
   pt_lens_ray(cam, lens, fr.w, fr.h, fr.seed_hash, pixel, first_sample + sl, o, d, key);
-  const RayQ& r = q.ray[0];
-  r.A[p] = make_float4(o[0], o[1], o[2], d[0]);
-  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
-  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), __uint_as_float(key));
-  q.lpath[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  store_primary_ray(q, p, V3(o), V3(d), key, true);
 }
 }  // namespace
 

@@ -8,17 +8,17 @@
 //   k_lm_list         the kept texels to their places — block prefix + the waves before + the kept lanes before: a stable compaction, ascending atlas index
 //   k_lm_texels       one thread per entry: the owner's edge values at the centre again, barycentrics, P, n, the origin; two 16-byte stores
 //   k_raygen_texel    one thread per path, k_raygen_probe's grid and queue bytes: two 16-byte loads of the entry's record, four coalesced 16-byte stores
-//   k_lm_first_hit    bounce 0 only, between closest(0) and shade(0): one wave per segment of the ray queue, as k_medium_decide walks it; the hit record and the ray
+//   k_lm_first_hit    bounce 0 only, between closest(0) and shade(0): one wave per segment of the ray queue (pt_pass_common.h); the hit record and the ray
 //                     are read only; back[path % n] += 1 where the face normal of the hit primitive looks along the ray.  Integer atomicAdd: the count does not
 //                     depend on the order.  Nothing another kernel of the batch reads is written
 //   k_lm_scatter      one thread per entry: E = sum * (pi / N) to the entry's texel with alpha 1, nothing for an invalid entry
 //   k_lm_dilate       one thread per texel, one iteration, ping-pong
 // No float atomic anywhere.  profiles/lightmap_atrium.txt has the kernels' times against their byte floors.
 #include "pt_lightmap.h"
-#include "pt_shading.h"
+#include "pt_pass_common.h"
 
 namespace {
-#define LM_WAVES (PT_LM_BLOCK / 64u)
+#define LM_WAVES (PT_LM_BLOCK / 64u)      // k_lm_cover's wave per triangle, and the per-wave sums of a block
 #define LM_SCAN_BLOCK 1024
 
 struct LmCorners { uint32_t i0, i1, i2; };
@@ -139,19 +139,15 @@ __global__ __launch_bounds__(256) void k_raygen_texel(const float4* __restrict__
   float d[3];
   uint32_t key;
   pt_lm_dir(seed_hash, base + __float_as_uint(T0.w), first_sample + sl, V3(T1.x, T1.y, T1.z), d, key);
-  const RayQ& r = q.ray[0];
-  r.A[p] = make_float4(T0.x, T0.y, T0.z, d[0]);
-  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
-  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), __uint_as_float(key));
-  q.lpath[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  store_primary_ray(q, p, V3(T0.x, T0.y, T0.z), V3(d), key, true);
 }
 
-__global__ __launch_bounds__(PT_LM_BLOCK) void k_lm_first_hit(DevScene sc, DevQueues q, int qi, uint32_t n_entries, uint32_t* __restrict__ back) {
-  const uint32_t lane = lane_id(), seg = blockIdx.x * LM_WAVES + (threadIdx.x >> 6);
-  if (seg >= q.n_seg) return;
+__global__ __launch_bounds__(WALK_BLOCK) void k_lm_first_hit(DevScene sc, DevQueues q, int qi, uint32_t n_entries, uint32_t* __restrict__ back) {
+  const uint32_t lane = lane_id();
+  const WaveSegment w = wave_segment(q);
+  if (!w.owned) return;
   const RayQ rin = q.ray[qi];
-  const uint32_t first = seg * q.seg_len;                       // first slot of the segment, in every queue array
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.seg_ray[qi][seg]);
+  const uint32_t first = w.base(q), n = w.count(q.seg_ray[qi]);
   for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
     if (i0 + lane >= n) continue;
     const uint32_t slot = first + i0 + lane;
@@ -212,7 +208,7 @@ void pt_launch_raygen_texel(hipStream_t s, const float4* texels, uint32_t n_entr
 
 void pt_launch_lm_first_hit(hipStream_t s, const DevScene& sc, const DevQueues& q, int qi, uint32_t n_entries, uint32_t* back) {
   if (!n_entries) return;
-  hipLaunchKernelGGL(k_lm_first_hit, dim3((q.n_seg + LM_WAVES - 1u) / LM_WAVES), dim3(PT_LM_BLOCK), 0, s, sc, q, qi, n_entries, back);
+  hipLaunchKernelGGL(k_lm_first_hit, walk_grid(q), dim3(WALK_BLOCK), 0, s, sc, q, qi, n_entries, back);
 }
 
 void pt_launch_lm_scatter(hipStream_t s, const float4* texels, uint32_t n_entries, const float4* accum, const uint32_t* back, uint32_t n_samples, float threshold, float4* atlas,

@@ -8,14 +8,9 @@
 //                           environment shadow records behind k_shade's in q.shadow, both counts are raised, and then EVERY shadow record of the segment is attenuated.
 //                           A segment cannot overflow: k_shade wrote nothing for the rays the medium took (the copies are bounded by seg_len all the same).
 //   k_medium_append<1>(b)   behind k_shade_punctual(b), before its scan: the same for the parked punctual records and the punctual pass's own.
-// Layout: k_shade_punctual's.  Blocks of 256 threads, one WAVE owns one queue segment (seg = blockIdx.x * 4 + wave), takes its slots 64 at a time in queue order and
-// compacts what it produces with a ballot and mbcnt64: vector stores only, no atomic on the data path, no block barrier after the staging of the punctual table,
-// counters added once per wave.
+// Layout: the per-segment pass of pt_pass_common.h, into the three medium queues; counters added once per wave.
 #include "pt_walk_surfaces.h"
 #include "pt_medium.h"
-
-#define MEDIUM_BLOCK 256
-#define MEDIUM_WAVES (MEDIUM_BLOCK / 64)
 
 namespace {
 // ---- the environment: k_shade's env_lookup, cdf_search_guided and env_sample (pt_kernels.hip, whose text is hashed and so cannot be shared), line for line,
@@ -57,22 +52,16 @@ PT_DEV v3 medium_env_sample(const DevScene& sc, float r1, float r2) {
   return V3(st * -c2, ct, st * -s2);
 }
 
-__global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_decide(DevScene sc, DevQueues q, DevMediumQ mq, pt_medium med, int qi, uint32_t b, uint32_t max_bounces,
-                                                                const float4* __restrict__ lights, const float* __restrict__ cdf, uint32_t n_punctual) {
+__global__ __launch_bounds__(WALK_BLOCK) void k_medium_decide(DevScene sc, DevQueues q, DevMediumQ mq, pt_medium med, int qi, uint32_t b, uint32_t max_bounces,
+                                                            const float4* __restrict__ lights, const float* __restrict__ cdf, uint32_t n_punctual) {
   __shared__ float4 s_light[PT_LIGHTS_MAX * 4];
   __shared__ float s_cdf[PT_LIGHTS_MAX];
-  if (n_punctual) {      // uniform over the grid
-    for (uint32_t i = threadIdx.x; i < n_punctual * 4u; i += MEDIUM_BLOCK) s_light[i] = lights[i];
-    for (uint32_t i = threadIdx.x; i < n_punctual; i += MEDIUM_BLOCK) s_cdf[i] = cdf[i];
-    __syncthreads();
-  }
+  if (n_punctual) stage_light_table(s_light, s_cdf, lights, cdf, n_punctual);      // uniform over the grid
   const uint32_t lane = lane_id();
-  const uint32_t wave = threadIdx.x >> 6;
-  const uint32_t seg = blockIdx.x * MEDIUM_WAVES + wave;
-  if (seg >= q.n_seg) return;
+  const WaveSegment w = wave_segment(q);
+  if (!w.owned) return;
   const RayQ rin = q.ray[qi];
-  const uint32_t base = seg * q.seg_len;                       // first slot of the segment, in every queue array
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.seg_ray[qi][seg]);
+  const uint32_t base = w.base(q), n = w.count(q.seg_ray[qi]);
   // light-kind selection probabilities for NEE: k_shade's
   const bool has_env = sc.env_w > 0, env_nee = has_env && sc.env_ok != 0;
   const float p_env = env_nee ? (sc.n_lights > 0u ? 0.5f : 1.0f) : 0.0f, p_area = 1.0f - p_env;
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_decide(DevScene sc, Dev
             if (n_punctual) {
               const uint32_t li = cdf_search(s_cdf, n_punctual, rng_f(key, PT_MEDIUM_RNG_PUNCTUAL + b + 1u, 0));
               const float4 l0 = s_light[li * 4u], l1 = s_light[li * 4u + 1u], l2 = s_light[li * 4u + 2u], l3 = s_light[li * 4u + 3u];
-              pt_light_rec L;
+              pt_light_rec L;      // load_light_rec's text (pt_pass_common.h), kept here: through the helper the index arithmetic compiles differently
               L.pos[0] = l0.x; L.pos[1] = l0.y; L.pos[2] = l0.z; L.type = __float_as_int(l0.w);
               L.dir[0] = l1.x; L.dir[1] = l1.y; L.dir[2] = l1.z; L.range = l1.w;
               L.I[0] = l2.x; L.I[1] = l2.y; L.I[2] = l2.z; L.pmf = l2.w;
@@ -157,14 +146,8 @@ __global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_decide(DevScene sc, Dev
               float dist;
               if (pt_light_sample(L, P, wi, dist, Li) && (Li.x > 0.0f || Li.y > 0.0f || Li.z > 0.0f)) {
                 const float k = pt_hg_phase(med.g, dot3(d, wi)) / L.pmf;
-                v3 sdir = wi;
-                float tmax = PT_T_INF;
-                if (L.type != PTC_LIGHT_DIRECTIONAL) {      // §2b: the segment from the origin to the light, minus its last 0.1 %
-                  const v3 sv = V3(L.pos) - P;
-                  const float sd = pt_sqrt(dot3(sv, sv));
-                  sdir = sv * (1.0f / sd);
-                  tmax = sd * 0.999f;
-                }
+                v3 sdir; float tmax;
+                punctual_segment(L, P, wi, sdir, tmax);
                 has_p = true;
                 pA = make_float4(P.x, P.y, P.z, sdir.x);
                 pB = make_float4(sdir.y, sdir.z, tmax, __uint_as_float(path));
@@ -186,6 +169,8 @@ __global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_decide(DevScene sc, Dev
       }
     }
     // ---- compaction into the wave's own segment of the medium queue ----
+    // the kernel's own text, not three put_compacted: the three ballots are taken first, then the stores, then the advances.  One compaction after the other is
+    // other machine code, and the fog frame at 64 spp came out above the parent's range with it (profiles/pass_common.txt)
     const uint64_t mc = __ballot(alive), ms = __ballot(has_s), mp = __ballot(has_p);
     if (alive) { const uint32_t at = base + out_c + mbcnt64(mc); mq.cont.A[at] = oA; mq.cont.B[at] = oB; mq.cont.C[at] = oC; }
     if (has_s) { const uint32_t at = base + out_s + mbcnt64(ms); mq.sh.A[at] = sA; mq.sh.B[at] = sB; mq.sh.C[at] = sC; }
@@ -194,15 +179,15 @@ __global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_decide(DevScene sc, Dev
     n_cross += (unsigned long long)__popcll(__ballot(crossed));
     n_scat += (unsigned long long)__popcll(__ballot(scattered));
   }
-  if (lane == 0) { mq.n_cont[seg] = out_c; mq.n_sh[seg] = out_s; mq.n_pl[seg] = out_p; }
+  if (lane == 0) { mq.n_cont[w.seg] = out_c; mq.n_sh[w.seg] = out_s; mq.n_pl[w.seg] = out_p; }
   wave_count(&mq.counters[PT_MEDIUM_CROSSED], n_cross, lane);
   wave_count(&mq.counters[PT_MEDIUM_SCATTERED], n_scat, lane);
 }
 
 // ptc_debug_medium_env: the two texts above on their own — per item the sample of (r1, r2) and the lookup of dir_in, seven floats (wi, Le, pdf)
-__global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_env(DevScene sc, const float* __restrict__ r1, const float* __restrict__ r2, const float* __restrict__ din, uint32_t n,
-                                                             float* __restrict__ out) {
-  const uint32_t i = blockIdx.x * MEDIUM_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(256) void k_medium_env(DevScene sc, const float* __restrict__ r1, const float* __restrict__ r2, const float* __restrict__ din, uint32_t n,
+                                                   float* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const v3 wi = medium_env_sample(sc, r1[i], r2[i]);
   v3 Le; float pdf;
@@ -224,24 +209,21 @@ PT_DEV uint32_t append_records(const float4* sA, const float4* sB, const float4*
 }
 
 template <int PUNCTUAL>
-__global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_append(DevQueues q, DevMediumQ mq, pt_medium med, int qi) {
+__global__ __launch_bounds__(WALK_BLOCK) void k_medium_append(DevQueues q, DevMediumQ mq, pt_medium med, int qi) {
   const uint32_t lane = lane_id();
-  const uint32_t wave = threadIdx.x >> 6;
-  const uint32_t seg = blockIdx.x * MEDIUM_WAVES + wave;
-  if (seg >= q.n_seg) return;
-  const uint32_t base = seg * q.seg_len;
+  const WaveSegment w = wave_segment(q);
+  if (!w.owned) return;
+  const uint32_t seg = w.seg, base = w.base(q);
   if (!PUNCTUAL) {
     const RayQ rout = q.ray[qi ^ 1];
-    const uint32_t have = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.seg_ray[qi ^ 1][seg]);
-    const uint32_t parked = (uint32_t)__builtin_amdgcn_readfirstlane((int)mq.n_cont[seg]);
+    const uint32_t have = w.count(q.seg_ray[qi ^ 1]), parked = w.count(mq.n_cont);
     const uint32_t total = append_records(mq.cont.A, mq.cont.B, mq.cont.C, rout.A, rout.B, rout.C, base, have, parked, q.seg_len, lane);
     if (lane == 0 && parked) q.seg_ray[qi ^ 1][seg] = total;
   }
   // ---- 6 and the shadow records: every lane reads only what an earlier kernel wrote and writes each word once — the pass's own records (k_shade's, or
   // k_shade_punctual's) are attenuated in place, the parked ones on their way behind them ----
   const ShadowQ src = PUNCTUAL ? mq.pl : mq.sh;
-  uint32_t have = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.seg_sh[seg]);
-  uint32_t parked = (uint32_t)__builtin_amdgcn_readfirstlane((int)(PUNCTUAL ? mq.n_pl[seg] : mq.n_sh[seg]));
+  uint32_t have = w.count(q.seg_sh), parked = w.count(PUNCTUAL ? mq.n_pl : mq.n_sh);
   if (have > q.seg_len) have = q.seg_len;
   if (parked > q.seg_len - have) parked = q.seg_len - have;
   unsigned long long n_att = 0;
@@ -285,16 +267,14 @@ __global__ __launch_bounds__(MEDIUM_BLOCK) void k_medium_append(DevQueues q, Dev
 void pt_launch_medium_decide(hipStream_t s, const DevScene& sc, const DevQueues& q, const DevMediumQ& mq, const pt_medium& med, int qi, uint32_t bounce, uint32_t max_bounces,
                              const pt_light_rec* lights, const float* cdf, uint32_t n_punctual) {
   if (n_punctual > PT_LIGHTS_MAX) return;
-  const dim3 grid((q.n_seg + MEDIUM_WAVES - 1u) / MEDIUM_WAVES);      // one wave per segment
-  hipLaunchKernelGGL(k_medium_decide, grid, dim3(MEDIUM_BLOCK), 0, s, sc, q, mq, med, qi, bounce, max_bounces, (const float4*)lights, cdf, n_punctual);
+  hipLaunchKernelGGL(k_medium_decide, walk_grid(q), dim3(WALK_BLOCK), 0, s, sc, q, mq, med, qi, bounce, max_bounces, (const float4*)lights, cdf, n_punctual);
 }
 
 void pt_launch_medium_append(hipStream_t s, const DevQueues& q, const DevMediumQ& mq, const pt_medium& med, int qi, bool punctual) {
-  const dim3 grid((q.n_seg + MEDIUM_WAVES - 1u) / MEDIUM_WAVES);
-  if (punctual) hipLaunchKernelGGL(k_medium_append<1>, grid, dim3(MEDIUM_BLOCK), 0, s, q, mq, med, qi);
-  else hipLaunchKernelGGL(k_medium_append<0>, grid, dim3(MEDIUM_BLOCK), 0, s, q, mq, med, qi);
+  if (punctual) hipLaunchKernelGGL(k_medium_append<1>, walk_grid(q), dim3(WALK_BLOCK), 0, s, q, mq, med, qi);
+  else hipLaunchKernelGGL(k_medium_append<0>, walk_grid(q), dim3(WALK_BLOCK), 0, s, q, mq, med, qi);
 }
 
 void pt_launch_medium_env(hipStream_t s, const DevScene& sc, const float* r1, const float* r2, const float* dir_in, uint32_t n, float* out7) {
-  hipLaunchKernelGGL(k_medium_env, dim3((n + MEDIUM_BLOCK - 1u) / MEDIUM_BLOCK), dim3(MEDIUM_BLOCK), 0, s, sc, r1, r2, dir_in, n, out7);
+  hipLaunchKernelGGL(k_medium_env, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, r1, r2, dir_in, n, out7);
 }

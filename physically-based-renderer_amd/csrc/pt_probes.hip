@@ -2,7 +2,7 @@
 // calls too).
 //
 //   k_raygen_probe    one thread per path, k_raygen's path id -> (probe j = p % n, sample = first + p / n) mapping.  One 16-byte load of the position, four coalesced
-//                     16-byte stores: the ray record A = (o, d.x), B = (d.y, d.z, 1, 1), C = (1, 0, p, key) and the cleared path radiance.  A streaming kernel like
+//                     16-byte stores: store_primary_ray (pt_pass_common.h).  A streaming kernel like
 //                     k_raygen: 64 B written per path, every byte once.
 //   k_accumulate_sh   the SH projection of a batch's path radiance.  Every one of a probe's 27 sums runs in sample order with one owner (no atomic: the result does
 //                     not depend on how the samples were cut into batches), so only the products L_c b_k are parallel over samples.  A 256-thread block takes 8
@@ -15,6 +15,7 @@
 //                     0.63 us per sample, is bound by that chain alone.
 // profiles/probes_atrium.txt has the kernels' times against their byte floors.
 #include "pt_probes.h"
+#include "pt_pass_common.h"
 
 namespace {
 __global__ __launch_bounds__(256) void k_raygen_probe(const float4* __restrict__ pos, uint32_t n_probes, uint32_t base, uint32_t seed_hash, DevQueues q, uint32_t first_sample,
@@ -26,11 +27,7 @@ __global__ __launch_bounds__(256) void k_raygen_probe(const float4* __restrict__
   float d[3];
   uint32_t key;
   pt_probe_dir(seed_hash, base + j, first_sample + sl, d, key);
-  const RayQ& r = q.ray[0];
-  r.A[p] = make_float4(o.x, o.y, o.z, d[0]);
-  r.B[p] = make_float4(d[1], d[2], 1.0f, 1.0f);
-  r.C[p] = make_float4(1.0f, 0.0f, __uint_as_float(p), __uint_as_float(key));
-  q.lpath[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  store_primary_ray(q, p, V3(o.x, o.y, o.z), V3(d), key, true);
 }
 
 // tile of k_accumulate_sh: 8 probes (one 128-byte line of lpath per sample) x 32 samples = 256 threads

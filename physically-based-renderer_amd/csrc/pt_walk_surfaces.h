@@ -1,7 +1,7 @@
 // pt_walk_surfaces.h — what the alpha pass, the glass pass and the shadow walk through thin glass need of a hit (device only): the bit of a primitive, the
 // alpha-mapped surface and the transmissive surface, each from the pt_shading.h helpers — k_shade's loads, texels and arithmetic.
 #pragma once
-#include "pt_shading.h"
+#include "pt_pass_common.h"
 #include "pt_alpha.h"
 #include "pt_glass.h"
 
@@ -9,40 +9,33 @@ PT_DEV bool alpha_bit(const DevAlpha& al, uint32_t prim) { return (al.bits[prim 
 PT_DEV bool glass_bit(const DevGlass& gl, uint32_t prim) { return (gl.bits[prim >> 5] >> (prim & 31u)) & 1u; }
 PT_DEV void wave_count(unsigned long long* ctr, unsigned long long v, uint32_t lane) { if (lane == 0 && v) atomicAdd(ctr, v); }
 
-// ---- the segment walk: the loop of every filter kernel (pt_alpha.hip, pt_glass.hip, pt_glass_shadow.hip) ---------------------------------------------
-// Blocks of WALK_BLOCK threads, one WAVE owns one queue segment (seg = blockIdx.x * WALK_WAVES + wave), takes its `seg_count[seg]` slots 64 at a time in queue order,
-// and compacts the records that go on to the front of the same segment of the side queue `sq` with a ballot and mbcnt64: no atomic on the data path, no block
-// barrier, and a wave never writes more records than it read — which is also why a later round can compact IN PLACE (seg_count == sq.seg_ray[0]): a batch of 64 is
-// loaded whole before anything is stored, and what it stores lies at or before its own slots.  An empty round (every segment count 0) is a launch whose waves
-// read one word each.
+// ---- the segment walk: the loop of every filter kernel (pt_alpha.hip, pt_glass.hip, pt_glass_shadow.hip), on pt_pass_common.h's segment and cursor ---------------
+// The records that go on are compacted to the front of the same segment of the side queue `sq`, which is also why a later round can compact IN PLACE
+// (seg_count == sq.seg_ray[0]): a batch of 64 is loaded whole before anything is stored, and what it stores lies at or before its own slots.  An empty round
+// (every segment count 0) is a launch whose waves read one word each.
 //   record(slot) -> WalkNext   one lane's record: whether it goes on, and then its continuation (A, B, C); a result that stands it stores itself, to its SOURCE slot
 //                              (single owner, one continuation per source record); what the kernel counts it leaves in the kernel's own flags
 //   tally(mp)                  once per batch, whole wave: mp is the ballot of the lanes that go on; the kernel adds its flags' ballots to its sums and clears the
 //                              flags (a lane past the segment's end never ran record).  The sums go to wave_count when the walk returns (a wave without a
 //                              segment returns with every sum 0)
-#define WALK_BLOCK 256
-#define WALK_WAVES (WALK_BLOCK / 64)
-inline dim3 walk_grid(const DevQueues& q) { return dim3((q.n_seg + WALK_WAVES - 1u) / WALK_WAVES); }      // one wave per segment
 struct WalkNext { bool go_on; float4 A, B, C; };
 
 template <class Record, class Tally>
 PT_DEV void walk_segments(const DevQueues& q, const DevQueues& sq, const uint32_t* seg_count, Record record, Tally tally) {
   const uint32_t lane = lane_id();
-  const uint32_t seg = blockIdx.x * WALK_WAVES + (threadIdx.x >> 6);
-  if (seg >= q.n_seg) return;
+  const WaveSegment w = wave_segment(q);
+  if (!w.owned) return;
   const RayQ rout = sq.ray[0];
-  const uint32_t base = seg * q.seg_len;
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg_count[seg]);
+  const uint32_t base = w.base(q), n = w.count(seg_count);
   uint32_t out = 0;
   for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
     WalkNext c{};
     if (i0 + lane < n) c = record(base + i0 + lane);
-    const uint64_t mp = __ballot(c.go_on);
-    if (c.go_on) { const uint32_t o = base + out + mbcnt64(mp); rout.A[o] = c.A; rout.B[o] = c.B; rout.C[o] = c.C; }
+    const uint64_t mp = put_compacted(rout, base + out, c.go_on, c.A, c.B, c.C);
     out += (uint32_t)__popcll(mp);
     tally(mp);
   }
-  if (lane == 0) sq.seg_ray[0][seg] = out;
+  if (lane == 0) sq.seg_ray[0][w.seg] = out;
 }
 
 // the alpha-mapped surface of a hit: its material's (mode, cutoff), its coverage a, and where a ray (.., d) that passes through it goes on from
@@ -70,30 +63,14 @@ PT_DEV void alpha_surface(const DevScene& sc, const DevAlpha& al, float4 H, v3 d
   onward = vfma(n, sc.ray_eps, P);
 }
 
-// the transmissive surface of a hit H of a ray of direction d: k_shade's loads and its P5 — P, ng and ns after record_material and orient_normals(-d, ..), base,
-// metallic — and the glass record of its material
-struct GlassSurface { v3 P, ng, ns, base; float metallic; bool front; pt_glass_mat m; };
+// the transmissive surface of a hit H of a ray of direction d: hit_surface and the glass record of its material
+struct GlassSurface : HitSurface { pt_glass_mat m; };
 PT_DEV GlassSurface glass_surface(const DevScene& sc, const DevGlass& gl, float4 H, v3 d) {
-  const int pw = __float_as_int(H.y);
-  const uint32_t prim = (uint32_t)pw & ((1u << HIT_CLASS_SHIFT) - 1u);
-  const float hu = H.z, hv = H.w, hw = 1.0f - hu - hv;
-  const size_t rec = (size_t)prim * sc.shade_stride;
-  const float4 r0 = sc.shade[rec], r1 = sc.shade[rec + 1], r2 = sc.shade[rec + 2], r3 = sc.shade[rec + 3], r4 = sc.shade[rec + 4];
-  float4 x0, x1, x2, x3, x4, x5;
-  x0 = x1 = x2 = x3 = x4 = x5 = make_float4(0, 0, 0, 0);
-  if (((uint32_t)pw >> HIT_CLASS_SHIFT) >= 2u) { x0 = sc.shade[rec + 5]; x1 = sc.shade[rec + 6]; x2 = sc.shade[rec + 7]; x3 = sc.shade[rec + 8]; x4 = sc.shade[rec + 9]; x5 = sc.shade[rec + 10]; }
-  const int mat = __float_as_int(r0.w);
+  const HitUnits u = load_hit_units(sc, H);
+  const HitUnitsRest x = load_hit_units_rest(sc, H, u);
+  const int mat = __float_as_int(u.r0.w);
   const float4 g0 = gl.mats[(size_t)mat * 2u], g1 = gl.mats[(size_t)mat * 2u + 1u];
-  GlassSurface s;
-  s.P = record_position(r0, r1, r2, hu, hv, hw);
-  s.ng = record_face_normal(r0, r1, r2);
-  const v3 ni = record_normal(r2, r3, r4, hu, hv, hw);
-  s.ns = normalize3(ni);
-  float base_c[4], roughness;
-  bool lambert;
-  record_material(sc, sc.mats, mat, x0, x1, x2, x3, x4, x5, hu, hv, hw, ni, base_c, s.metallic, roughness, lambert, s.ns);
-  s.front = orient_normals(-d, s.ng, s.ns);
-  s.base = V3(base_c[0], base_c[1], base_c[2]);
+  GlassSurface s{hit_surface(sc, d, u, x, hit_face_normal(u)), {}};
   s.m.tau = g0.x; s.m.ior = g0.y; s.m.thin = __float_as_int(g0.z); s.m.pad0 = 0.0f; s.m.sigma2[0] = g1.x; s.m.sigma2[1] = g1.y; s.m.sigma2[2] = g1.z; s.m.pad1 = 0.0f;
   return s;
 }

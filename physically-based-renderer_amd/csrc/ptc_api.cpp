@@ -105,6 +105,9 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       else pt_launch_trace_any(st, cfg, sc, q, nullptr);
       c->stats.launches_trace_any++;
     };
+    // behind a further next-event pass of bounce b: the same ray prefix again, the new shadow counts, the work counters zeroed (nothing runs beside it), its records traced
+    auto scan_and_trace_shadows = [&](int b) { pt_launch_scan(st, cfg, q, (b + 1) & 1); trace_shadows(); };
+    auto medium_append = [&](int b, bool behind_punctual) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, behind_punctual); };
     const bool overlap = (c->trace_overlap == 2 || (c->trace_overlap == 1 && small_batch)) && shadows && ln.stream2 && ln.stack_ovf2 && !punctual && !alpha && !glass && !medium && !emtex;
     if (overlap) {
       const size_t need = (size_t)c->fr.max_bounces + 1;
@@ -128,7 +131,7 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
         if (emtex) { ScopedSpan t(c, st, 8); pt_launch_shade_emissive_tex(st, sc, q, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, et); }
         break;
       }
-      if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, false); }
+      if (medium) medium_append(b, false);
       pt_launch_scan(st, cfg, q, (b + 1) & 1);
       if (overlap) {      // any(b) on the second stream, beside closest(b + 1)
         HIP_TRY(c, hipEventRecord(ln.ev_scan[(size_t)b], st));
@@ -138,16 +141,12 @@ int run_batch(ptc_ctx* c, int l, uint32_t first_sample, uint32_t n_samples) {
       } else if (shadows) trace_shadows();
       if (punctual) {     // behind emission (k_shade) and the emitter / environment sample (any): the punctual sample, through the same shadow queue
         { ScopedSpan t(c, st, 2); pt_launch_shade_punctual(st, sc, q, b & 1, (uint32_t)b, c->lights.recs.p, c->lights.cdf.p, c->lights.n_dev); }
-        if (medium) { ScopedSpan t(c, st, 7); pt_launch_medium_append(st, q, mq, c->medium.frame, b & 1, true); }
-        pt_launch_scan(st, cfg, q, (b + 1) & 1);      // the same ray prefix again, the new shadow counts, the work counters zeroed: nothing runs beside it
-        trace_shadows();
+        if (medium) medium_append(b, true);
+        scan_and_trace_shadows(b);
       }
       if (emtex) {        // behind the punctual sample: textured emission at the hit, then the textured sample through the same shadow queue
         { ScopedSpan t(c, st, 8); pt_launch_shade_emissive_tex(st, sc, q, b & 1, (uint32_t)b, (uint32_t)c->fr.max_bounces, et); }
-        if (et.sample) {
-          pt_launch_scan(st, cfg, q, (b + 1) & 1);
-          trace_shadows();
-        }
+        if (et.sample) scan_and_trace_shadows(b);
       }
     }
     // sample-order accumulation: wait for the previous batch's accumulate (it ran on the previous lane)
